@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the fused hot path (mog + hsv + erode/dilate + blob) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
 
 One "step" = one frame for every camera stream a rank owns, through the whole
 fused chain (MOG2 update, setTo, BGR2HSV, inRange, erode, dilate, labelling,
@@ -221,9 +221,10 @@ def free_port():
 
 def spawn_ranks_if_asked(args, argv):
     """`bench.py --gpus N` IS an N-rank run (VERDICT r04 missing-2).  Launched plainly (no WORLD_SIZE) with N > 1 the
-    script replaces itself by `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>`,
-    one rank per device; with the "nccl" (= RCCL) backend fewer visible devices than ranks is an error (rc 3), never a
-    silent N = 1.  Under a launcher (WORLD_SIZE set) the world must equal --gpus.  Returns the world size."""
+    script runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>` as a child
+    process and exits with its status, one rank per device; with the "nccl" (= RCCL) backend fewer visible devices than
+    ranks is an error (rc 3), never a silent N = 1.  Under a launcher (WORLD_SIZE set) the world must equal --gpus.
+    Returns the world size."""
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is not None:
         world = int(env_world)
@@ -238,7 +239,13 @@ def spawn_ranks_if_asked(args, argv):
         sys.exit(2)
     if n == 1:
         return 1
-    ndev = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    # counted in a short-lived child: this process only waits for the ranks and never opens the device itself
+    try:
+        probe = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"],
+                               capture_output=True, text=True, timeout=300)
+        ndev = int(probe.stdout.split()[-1]) if probe.returncode == 0 and probe.stdout.split() else 0
+    except (subprocess.TimeoutExpired, ValueError):
+        ndev = 0                                     # a probe that hangs or prints nonsense found no device
     if ndev < 1 or (args.backend == "nccl" and ndev < n):
         log(f"bench.py: --gpus {n} needs {n} visible device(s), found {ndev} (backend {args.backend}: one rank per device; "
             f"`--backend gloo` lets ranks share a device for control-flow smoke tests)")
@@ -247,8 +254,10 @@ def spawn_ranks_if_asked(args, argv):
            "--master-port", str(free_port()), os.path.abspath(__file__)] + list(argv)
     log("bench.py: starting", n, "ranks:", " ".join(cmd))
     sys.stdout.flush()
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    os.execv(sys.executable, cmd)
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    rc = subprocess.run(cmd, env=env).returncode     # a child process, never an exec of this one
+    sys.exit(rc if rc >= 0 else 128 - rc)          # a launcher killed by a signal exits as a shell reports it
 
 
 def open_device_with_retry(dev, rank, attempts=6):
@@ -624,7 +633,7 @@ class Leg:
         self.pool = gen(wl["rows"], wl["cols"], self.ns, pool, rank, self.dev)
         torch.cuda.synchronize()
         self.hp = make_hotpath(wl, dev_index, dense=dense)
-        self.hp.set_fusion(FUSION)
+        self.set_fusion(FUSION)
         if EARLY_BLOB is not None:
             self.hp.set_early_blob(EARLY_BLOB)
         self.step = 0                    # frames consumed so far
@@ -634,6 +643,11 @@ class Leg:
             self.host_pool = [[f.numpy() for f in p.cpu().pin_memory()] for p in self.pool]
         elif input_mode == "host-sync":  # pageable frames through the synchronous oatgpu_track_batch
             self.host_pool = [[np.ascontiguousarray(f) for f in p.cpu().numpy()] for p in self.pool]
+
+    def set_fusion(self, frames_per_launch):
+        """oatgpu_set_fusion; a run of the pipelined path launches its frames in groups of this many from its first frame."""
+        self.hp.set_fusion(frames_per_launch)
+        self.frames_per_launch = frames_per_launch
 
     def pool_index(self, step):          # step 0 = the initialisation frame
         return 0 if step == 0 else (step % len(self.pool))
@@ -736,7 +750,7 @@ CAL_STEPS = 50                  # steps of the (untimed) calibration run that si
 
 
 def timed_run(leg, K, W, barrier, prof_every, age_frames, export=True, spin=0.0, spin_args=None, reduce_max=None,
-              min_ms=None, isolated=False):
+              min_ms=None, isolated=False, exact=False):
     """Model initialisation, ageing (untimed), [export of the aged models for the parity gate, device spin-up on a
     scratch context while the real one rests], W warm-up steps, then the timed region between barriers:
     R back-to-back BLOCKS of exactly K steps in one pipelined run, R chosen so that the region lasts >= min_ms
@@ -744,7 +758,7 @@ def timed_run(leg, K, W, barrier, prof_every, age_frames, export=True, spin=0.0,
     bK+K-1's result was collected minus the moment step bK-1's was: oatgpu_track_sequence_dev_timed), so blocks
     1..R-1 are K steps of the pipeline in steady state; block 0 also carries the pipeline's fill.  The reported
     step time is the MEDIAN block / K.  reduce_max: all-reduce(MAX) of a list of floats over the ranks (N > 1).
-    Returns a dict."""
+    exact: the benched leg's form instead -- exactly K timed steps (exact_region below).  Returns a dict."""
     import ctypes as C
     from oat_amd.components import Position2D
     hp = leg.hp
@@ -758,6 +772,9 @@ def timed_run(leg, K, W, barrier, prof_every, age_frames, export=True, spin=0.0,
     log(tag, "models exported" if export else "no export")
     if spin > 0 and spin_args:
         spin_up(*spin_args, spin)       # the export left the device idle: warm it again, on a scratch context
+    if exact:
+        return dict(exact_region(leg, K, W, barrier, prof_every, reduce_max, isolated),
+                    models=models, handover=handover, aged=aged)
     if W:
         leg.run(W)
     # calibration (untimed, part of the warm-up as far as the model is concerned): how long does a step take?
@@ -842,6 +859,89 @@ def timed_run(leg, K, W, barrier, prof_every, age_frames, export=True, spin=0.0,
                 positions=positions, found=found, prof=prof, models=models, handover=handover, aged=aged,
                 gate_offset=W + cal + skipped, step_s_calibration=t_cal, region_attempts=attempts,
                 saturated_latency_us=lat, with_target=with_target)
+
+
+def exact_region(leg, K, W, barrier, prof_every, reduce_max, isolated):
+    """The benched leg's timed region: EXACTLY K steps, so that --steps is the number of timed steps and the last one is
+    the same frame on the same model in every run with the same arguments (--dump-outputs).  Device-frame input: the W
+    warm-up steps (rounded up to whole launches) and the K timed steps are ONE pipelined run between two barriers, and the
+    region runs from the collection of the last warm-up step's result to the collection of the last timed step's (from
+    the start of the run when W = 0: the pipeline's fill is then inside) -- one block of the timed_run form.  Host
+    input: W steps, then the K steps alone between two barriers.  One block, so block_s = region_s (max over the ranks).
+    `last` = the Position records the caller received for the last timed step, one dict a stream."""
+    import ctypes as C
+    from oat_amd import ffi
+    from oat_amd.components import Position2D
+    hp = leg.hp
+    tag = f"[{leg.name} r{os.environ.get('RANK', '0')}]"
+    timed_dev = leg.host_pool is None
+    if W and not timed_dev:
+        leg.run(W)
+    # steps of the run ahead of the first timed one.  The run launches its frames in groups of frames_per_launch counted
+    # from its first frame, and one ring event covers a group's results: the lead is rounded up to a whole number of
+    # groups, so that no launch holds both a warm-up step and a timed one -- otherwise the clock would start when part of
+    # the timed work is already done (--warmup 5 runs 6 steps with --fusion 2)
+    fpl = max(int(leg.frames_per_launch), 1)
+    lead = -(-W // fpl) * fpl if timed_dev else 0
+    n = lead + K
+    hp.profile(prof_every if n < 16 else max(prof_every, 8))     # HIP events around K1 on every Nth step of the run
+    hp.profile_reset()
+    prepared = leg.prepare(n)
+    done = (C.c_double * n)() if timed_dev else None
+    enq = (C.c_double * n)() if timed_dev else None
+    barrier()
+    t0 = time.perf_counter()
+    out = leg.run(n, prepared, keep=True, done_s=done, enq_s=enq)
+    barrier()
+    elapsed = time.perf_counter() - t0
+    prof = hp.profile_read()
+    hp.profile(0)
+    local = (done[n - 1] - (done[lead - 1] if lead else 0.0)) if timed_dev else elapsed
+    log(tag, f"timed region: {K} steps in {local * 1e3:.3f} ms ({lead} warm-up steps ahead in the same run)")
+    region = reduce_max([local])[0] if reduce_max else local
+    first_step = leg.step - K                    # the timed region's first step; pool frame 0 (it initialises the models) has no disc
+    with_target = sum(1 for t in range(K) if leg.pool_index(first_step + t) != 0) * leg.ns
+    iso = None
+    if isolated:                 # K steps alone between two barriers: fill AND drain inside (what rounds 1-2 reported)
+        prepared = leg.prepare(K)
+        barrier()
+        t0 = time.perf_counter()
+        leg.run(K, prepared)
+        barrier()
+        iso = time.perf_counter() - t0
+        if reduce_max:
+            iso = reduce_max([iso])[0]
+    ns = leg.ns
+    G = min(K, 256)              # the gate replays at most this many timed steps
+    positions = [[Position2D.from_c(out[(lead + t) * ns + s]) for s in range(ns)] for t in range(G)]
+    found = sum(1 for t in range(lead, n) for s_ in range(ns) if out[t * ns + s_].valid == 1)
+    last = [{f: getattr(out[(n - 1) * ns + s], f) for f, _ in ffi.Position._fields_} for s in range(ns)]
+    lat = None
+    if timed_dev and K >= 8:     # enqueue -> result collected, per frame, timed steps after the first quarter (the ring is kept full)
+        l_ = sorted((done[i] - enq[i]) * 1e6 for i in range(lead + K // 4, n))
+        lat = dict(p50=l_[len(l_) // 2], p99=l_[min(len(l_) - 1, int(len(l_) * 0.99))], ring_depth=RING)
+    ahead = lead if timed_dev else W             # steps between the hand-over of the models and the first timed step
+    return dict(block_s=region, local_block_s=local, blocks=[region], n_blocks=1, region_s=region, steps_timed=K,
+                isolated_block_s=iso, positions=positions, found=found, prof=prof, gate_offset=ahead, warmup_steps_run=ahead,
+                step_s_calibration=None, region_attempts=1, saturated_latency_us=lat, with_target=with_target, last=last)
+
+
+def dump_outputs(path, last, world, rank):
+    """--dump-outputs DIR: what the timed path handed its caller in its LAST timed step -- every stream's Position record
+    (oatgpu_track_sequence_dev) -- as DIR/position_<field>.npy, one float64 array over the global streams (rank 0's
+    first).  The inputs are seeded and the timed steps exactly --steps, so the same arguments give the same arrays."""
+    if world > 1:
+        import torch.distributed as dist
+        every = [None] * world
+        dist.all_gather_object(every, last)
+        last = [rec for part in every for rec in part]
+    if rank != 0:
+        return
+    from oat_amd import ffi
+    os.makedirs(path, exist_ok=True)
+    for f, _ in ffi.Position._fields_:
+        np.save(os.path.join(path, f"position_{f}.npy"), np.array([rec[f] for rec in last], dtype=np.float64))
+    log(f"outputs of the last timed step ({len(last)} stream(s)) written to {path}")
 
 
 def single_frame_latency(leg, n):
@@ -1372,8 +1472,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks = devices of this node (default 1, or the launcher's WORLD_SIZE).  N > 1 without a launcher: "
                          "the script starts the N ranks itself through torch.distributed.run")
-    ap.add_argument("--steps", type=int, default=1000)
-    ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=1000, help="timed steps of the benched workload (exactly these)")
+    ap.add_argument("--warmup", type=int, default=100, help="warm-up steps ahead of them, in the same pipelined run")
     ap.add_argument("--workload", default="4k1", choices=sorted(WORKLOADS))
     ap.add_argument("--pool", type=int, default=48, help="distinct frame sets resident in HBM")
     ap.add_argument("--input", default="device", choices=["device", "host", "host-sync"],
@@ -1414,6 +1514,9 @@ def main():
                          "(oatgpu_set_early_blob(-1): on for at most three streams at 4 MP a step and more)")
     ap.add_argument("--k1-wg", type=int, default=0, choices=[0, 64, 256], help=argparse.SUPPRESS)   # PMC child: oatgpu_set_k1_workgroup
     ap.add_argument("--detail-out", default=None, help="where the full result goes (default: bench_detail.json beside bench.py)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the benched path returned for its last timed step (every "
+                         "stream's position record) as DIR/position_<field>.npy, float64 (e.g. DIR = bench_outputs)")
     ap.add_argument("--no-scatter", action="store_true", help="N > 1: skip the scatter_ingest leg (frames from rank 0 through "
                                                               "the stream->rank scatter)")
     ap.add_argument("--scatter-steps", type=int, default=200, help="steps of the scatter_ingest leg (N > 1)")
@@ -1422,6 +1525,8 @@ def main():
     ap.add_argument("--dense-noise", type=int, default=5, help=argparse.SUPPRESS)   # lab: 3 keeps every dense pixel background (no shadow test)
     ap.add_argument("--lab-calm", action="store_true", help=argparse.SUPPRESS)   # kernel lab: SURVEY 8d input WITHOUT the flickering pixels
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     world = 1 if args.pmc_child else spawn_ranks_if_asked(args, sys.argv[1:])
     global DETAIL_PATH
     if args.detail_out:
@@ -1496,9 +1601,11 @@ def main():
     assert len(mine) == ns and mine.start == rank * ns, (list(mine), rank, ns, world)
     tr = timed_run(leg, K, W, barrier, prof_every=8 if K >= 64 else 1, age_frames=AGE, export=want_gate,
                    spin=0.0 if args.no_spin_up else 0.35, spin_args=(args.workload, local_rank, rank),
-                   reduce_max=reduce_max, isolated=True)
+                   reduce_max=reduce_max, isolated=True, exact=True)
     positions, prof, models, handover, aged = tr["positions"], tr["prof"], tr["models"], tr["handover"], tr["aged"]
     n_found_local = tr["found"]
+    if args.dump_outputs:
+        dump_outputs(os.path.abspath(args.dump_outputs), tr["last"], world, rank)
 
     # (the parity gates -- minutes of many-threaded CPU work -- run after ALL device timing of this process: the small
     # workloads are bound by the host's launch calls and measured up to 40 % lower behind them)
@@ -1586,7 +1693,7 @@ def main():
     if solo and FUSION == 2 and not args.no_extra and args.input == "device" and not args.dense_model:
         try:
             l1 = Leg(args.workload, local_rank, rank, pool=args.pool)
-            l1.hp.set_fusion(1)
+            l1.set_fusion(1)
             o = timed_run(l1, K, max(W, 50), local_barrier(l1), 8, age_frames=AGE, export=False,
                           spin=0.0 if args.no_spin_up else 0.2, spin_args=(args.workload, local_rank, rank))
             one_frame = dict(value=ns * K / o["block_s"], unit="frames/s", steps=K, blocks=o["n_blocks"],
@@ -1704,7 +1811,7 @@ def main():
                     # the same leg with one frame a launch (oatgpu_set_fusion(1): what a caller that collects every
                     # frame before the next gets, and SURVEY 8d's 205 B/px case), sustained state as above
                     d1 = Leg("4k1", local_rank, rank, dense=True, pool=10)
-                    d1.hp.set_fusion(1)
+                    d1.set_fusion(1)
                     r1 = timed_run(d1, 300, 1200, local_barrier(d1), 2, age_frames=60, export=False, min_ms=0.0)
                     dense["one_frame_avg_launch_ms"] = k1_ms(r1["prof"])[0]
                     dense["one_frame_ms_per_step"] = r1["block_s"] / 300 * 1e3
@@ -1870,7 +1977,7 @@ def main():
     line = {
         "metric": "frames/sec/GPU (1080p & 4K) mog+hsv+ccl fused; % HBM roofline",
         "value": fps,
-        # the whole timed region / its steps (every block, the first one's pipeline fill included): `value` is the MEDIAN block's
+        # the whole timed region / its steps: the region is one block of exactly --steps steps, so this equals `value`
         "value_mean": total_streams * tr["steps_timed"] / tr["region_s"],
         "value_one_frame_a_launch": one_frame["value"] if one_frame else None,
         "value_default_learning_rate_0": frozen["value"] if frozen else None,
@@ -1900,20 +2007,20 @@ def main():
                       "per_rank": per_rank if per_rank else [dict(rank=0, device=local_rank, streams=[0, ns], parity=parity,
                                                                   positions_found=n_found_local, k_mog_fused_ms=mog_ms)]},
         "timing": {
-            "method": f"{tr['n_blocks']} back-to-back blocks of exactly --steps {K} steps in ONE pipelined run between two "
-                      "barriers (+ device synchronisation), sized so that the region lasts >= "
-                      f"{MIN_TIMED_MS:.0f} ms whatever --steps is; a block's time runs from the collection of the previous "
-                      "block's last result to the collection of its own last result (max over ranks per block); "
-                      "ms_per_step = MEDIAN of blocks 1.. / steps (block 0 also carries the pipeline's fill).  "
-                      "isolated_block = the same K steps ALONE between two barriers, fill and drain inside: what "
-                      "rounds 1-2 put into `value`",
-            "blocks": tr["n_blocks"], "steps_timed": tr["steps_timed"], "timed_region_ms": region_ms,
+            "method": f"exactly --steps {K} timed steps behind --warmup {W} warm-up steps (rounded up to whole launches of "
+                      f"--fusion {FUSION} frames: warmup_steps_run) in ONE pipelined run between two "
+                      "barriers (+ device synchronisation); the region runs from the collection of the last warm-up "
+                      "step's result to the collection of the last timed step's (from the start of the run when "
+                      "--warmup is 0), max over ranks; ms_per_step = region / steps.  isolated_block = K further steps "
+                      "ALONE between two barriers, fill and drain inside: what rounds 1-2 put into `value`",
+            "blocks": tr["n_blocks"], "steps_timed": tr["steps_timed"], "warmup_steps_run": tr["warmup_steps_run"],
+            "timed_region_ms": region_ms,
             "whole_region_ms_per_step": region_ms / tr["steps_timed"],
             "block_ms": {"first": tr["blocks"][0] * 1e3, "median": block_s * 1e3,
                          "min": min(tr["blocks"][1:] or tr["blocks"]) * 1e3, "max": max(tr["blocks"][1:] or tr["blocks"]) * 1e3},
             "isolated_block_ms": tr["isolated_block_s"] * 1e3 if tr["isolated_block_s"] else None,
             "value_isolated_block": (total_streams * K / tr["isolated_block_s"]) if tr["isolated_block_s"] else None,
-            "calibration_ms_per_step": tr["step_s_calibration"] * 1e3,
+            "calibration_ms_per_step": tr["step_s_calibration"] * 1e3 if tr["step_s_calibration"] is not None else None,
         },
         "timed_region_ms": region_ms,
         "model_age_frames": handover,

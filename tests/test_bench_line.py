@@ -206,3 +206,118 @@ def test_slim_line_survives_a_run_that_measured_almost_nothing():
     assert j["value"] == 1.0 and j["roofline"]["frac"] is None and j["cpu_baseline"] is None
     assert j["scatter_ingest"] == {"error": "boom", "parity": "error"} and j["partition"]["ranks"] == []
     assert float("nan") != float("nan") and bench._sig(float("nan")) is None and bench._sig(float("inf")) is None
+
+
+class _FakeHotPath:
+    """Stands in for oat_amd.HotPath where exact_region touches it (no device)."""
+
+    def profile(self, every):
+        self.every = every
+
+    def profile_reset(self):
+        pass
+
+    def profile_read(self):
+        return dict(steps=1, mog_ms=0.1, morph_ms=0.1, blob_ms=0.1, total_ms=0.3, event_pair_ms=0.0, mog_frames=2, dropped=0)
+
+    def synchronize(self):
+        pass
+
+
+class _FakeLeg:
+    """A leg whose pipelined run launches its frames in groups of frames_per_launch counted from the run's first frame (a
+    trailing partial group alone), as oatgpu_track_sequence_dev does: a launch takes 2 ms a frame, and all results of a
+    launch are collected at the same moment (one ring event covers them).  Every result carries its step's number."""
+    name, ns = "vga1", 2
+
+    def __init__(self, host=False, frames_per_launch=2):
+        self.hp, self.step, self.runs, self.pool = _FakeHotPath(), 1, [], [None] * 48
+        self.host_pool = [] if host else None
+        self.frames_per_launch = frames_per_launch
+
+    def pool_index(self, step):
+        return 0 if step == 0 else step % len(self.pool)
+
+    def prepare(self, n):
+        return None
+
+    def run(self, n, prepared=None, keep=False, done_s=None, enq_s=None):
+        from oat_amd import ffi
+        self.runs.append(n)
+        out = (ffi.Position * (n * self.ns))()
+        t = 1.0
+        for g0 in range(0, n, self.frames_per_launch):
+            group = range(g0, min(g0 + self.frames_per_launch, n))
+            t += 0.002 * len(group)
+            for i in group:
+                if done_s is not None:
+                    done_s[i], enq_s[i] = t, 0.9 + 0.002 * i
+        for i in range(n):
+            for s in range(self.ns):
+                p = out[i * self.ns + s]
+                p.valid, p.x, p.y, p.a00 = 1, float(self.step + i), float(s), self.step + i
+        self.step += n
+        return out if keep else None
+
+
+@pytest.mark.parametrize("fpl,W,K,lead", [(2, 0, 20, 0), (2, 5, 20, 6), (2, 6, 20, 6), (2, 3, 7, 4), (1, 5, 20, 5), (1, 3, 7, 3)])
+def test_the_benched_region_is_exactly_steps_timed_steps(fpl, W, K, lead):
+    """--steps K times exactly K steps: ONE pipelined run of the warm-up steps + K timed steps, timed from the last warm-up
+    result to the last timed one (from the run's start when W = 0).  The warm-up is rounded up to whole launches: with two
+    frames a launch and W odd, step W - 1 and step W would share one launch, and the clock would start with the first timed
+    step's work already done.  `last` is what the caller got for the last timed step."""
+    leg = _FakeLeg(frames_per_launch=fpl)
+    r = bench.exact_region(leg, K, W, lambda: None, 1, None, False)
+    assert leg.runs == [lead + K] and leg.step == 1 + lead + K
+    assert r["steps_timed"] == K and r["n_blocks"] == 1 and r["gate_offset"] == r["warmup_steps_run"] == lead
+    want = 0.002 * K if lead else 1.0 + 0.002 * K            # the work of exactly K frames (+ the run's start when W = 0)
+    assert r["block_s"] == pytest.approx(want) and r["region_s"] == r["block_s"] == r["blocks"][0]
+    assert r["found"] == K * leg.ns and len(r["positions"]) == K
+    assert r["positions"][0][0].x == 1 + lead                   # the first timed step follows the warm-up steps
+    assert [q["x"] for q in r["last"]] == [float(lead + K)] * 2 and [q["y"] for q in r["last"]] == [0.0, 1.0]
+
+
+def test_host_input_times_the_k_steps_alone():
+    leg = _FakeLeg(host=True)
+    r = bench.exact_region(leg, 7, 3, lambda: None, 1, None, False)
+    assert leg.runs == [3, 7] and r["steps_timed"] == 7 and r["gate_offset"] == 3 and r["last"][1]["a00"] == 10
+
+
+def test_dump_outputs_writes_the_last_steps_records_as_float64(tmp_path):
+    from oat_amd import ffi
+    r = bench.exact_region(_FakeLeg(), 9, 4, lambda: None, 1, None, False)
+    bench.dump_outputs(str(tmp_path / "out"), r["last"], 1, 0)
+    names = sorted(os.listdir(tmp_path / "out"))
+    assert names == sorted(f"position_{f}.npy" for f, _ in ffi.Position._fields_)
+    import numpy as np
+    x = np.load(tmp_path / "out" / "position_x.npy")
+    assert x.dtype == np.float64 and x.tolist() == [13.0, 13.0]
+    assert np.load(tmp_path / "out" / "position_valid.npy").tolist() == [1.0, 1.0]
+
+
+def test_steps_must_be_positive():
+    r = _run(["--steps", "0"])
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_same_in_two_runs_with_the_same_arguments(tmp_path):
+    """`--dump-outputs DIR` on the device: exactly --steps timed steps, and two runs with the same arguments hand their caller
+    the same records for the last of them (seeded inputs, a fixed number of steps ahead of it)."""
+    import numpy as np
+    from oat_amd import ffi
+    args = ["--gpus", "1", "--workload", "vga1", "--steps", "30", "--warmup", "4", "--age", "100", "--quick", "--no-dense-leg",
+            "--check-steps", "8", "--detail-out", str(tmp_path / "d.json")]
+    got = []
+    for k in range(2):
+        out = tmp_path / f"out{k}"
+        r = _run(args + ["--dump-outputs", str(out)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert j["steps"] == 30 and j["warmup"] == 4 and j["parity"] == "ok" and j["ms_per_step"] > 0
+        with open(tmp_path / "d.json") as f:
+            assert json.load(f)["timing"]["steps_timed"] == 30
+        got.append({n: np.load(out / n) for n in sorted(os.listdir(out))})
+    assert sorted(got[0]) == sorted(f"position_{f}.npy" for f, _ in ffi.Position._fields_) == sorted(got[1])
+    for n, a in got[0].items():
+        assert a.dtype == np.float64 and a.shape == (1,) and np.array_equal(a, got[1][n]), n

@@ -54,8 +54,8 @@ def test_bench_two_ranks_over_gloo_share_one_gpu():
     j = json.loads(lines[0])
     assert j["n_gpus"] == 2 and j["steps"] == 60 and j["scaling"] == "weak"
     d = _detail()                                       # everything else the run measured
-    timed = d["timing"]["steps_timed"]                 # blocks x 60 steps: the region is stretched to >= 50 ms
-    assert timed % 60 == 0 and timed == d["timing"]["blocks"] * 60 and j["timed_region_ms"] >= 50.0
+    timed = d["timing"]["steps_timed"]                 # exactly --steps timed steps, one block, max over the ranks
+    assert timed == 60 and d["timing"]["blocks"] == 1 and j["timed_region_ms"] == pytest.approx(60 * j["ms_per_step"], rel=1e-3)
     assert j["positions_expected"] == 2 * timed and j["positions_found"] >= 0.95 * 2 * timed   # (the oracle gate checks WHICH)
     assert abs(j["value"] - 2 * 60 / (j["ms_per_step"] * 60 / 1e3)) < 1e-5 * j["value"]
     assert j["parity"] == "ok"
@@ -86,18 +86,24 @@ def test_bench_gpus_2_as_a_plain_process_starts_two_ranks():
     assert j["fps_per_gpu"] * 2 == pytest.approx(j["value"], rel=1e-4)
 
 
+# Ranks of the multi-rank runs that share the one GPU: with the test process (it opens the device first) and the launcher
+# in front of the ranks, no more than six processes have the device open at once.
+RANKS = 3
+
+
 @pytest.mark.parametrize("workload,per_rank", [("1080p8", 8), ("4k1", 1)])
-def test_bench_eight_ranks_on_one_gpu_run_configs_3_and_4(workload, per_rank):
-    """BASELINE configs[3] (64 x 1080p as 8 ranks x 8 streams) and configs[4] (8 x 4K, one per rank) in their 8-RANK form
-    on the one GPU there is: `torch.distributed.run --nproc-per-node 8 bench.py --gpus 8 --backend
-    gloo`.  Eight processes, eight contexts, ~13 GB / ~7 GB of models on device 0.  Asserted: SURVEY 8e's partition (rank
-    r owns global streams r*per .. r*per + per - 1), BOTH parity gates green on EVERY rank for every stream of its shard,
-    one JSON line from rank 0 whose value counts all ranks' streams, the N = 1-only legs absent.  What this cannot
-    show is scaling over xGMI: that stays unmeasured until a SCALE record exists."""
+def test_bench_three_ranks_on_one_gpu_run_configs_3_and_4(workload, per_rank):
+    """BASELINE configs[3] (8 x 1080p a rank) and configs[4] (one 4K stream a rank) in their multi-rank form on the one GPU
+    there is: `torch.distributed.run --nproc-per-node 3 bench.py --gpus 3 --backend gloo`.  Three
+    processes, three contexts on device 0.  Asserted: SURVEY 8e's partition (rank r owns global streams r*per .. r*per +
+    per - 1), BOTH parity gates green on EVERY rank for every stream of its shard, one JSON line from rank 0 whose value
+    counts all ranks' streams, the N = 1-only legs absent.  What this cannot show is scaling over xGMI: that stays
+    unmeasured until a SCALE record exists."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     K = 20
-    cmd = lambda port: [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo",
+    N = RANKS
+    cmd = lambda port: [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(N), "--master-addr", "127.0.0.1",
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(N), "--backend", "gloo",
                         "--workload", workload, "--steps", str(K), "--warmup", "5", "--age", "40", "--pool", "8", "--check-steps", "4",
                         "--no-spin-up", "--scatter-steps", "12", "--no-extra"]
     r = _launch(cmd, env, 900)
@@ -105,35 +111,36 @@ def test_bench_eight_ranks_on_one_gpu_run_configs_3_and_4(workload, per_rank):
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and len(lines[0]) <= 4096, r.stdout[-2000:]
     j = json.loads(lines[0])
-    assert j["n_gpus"] == 8 and j["steps"] == K and j["scaling"] == "weak" and j["config"]["workload"] == workload
+    assert j["n_gpus"] == N and j["steps"] == K and j["scaling"] == "weak" and j["config"]["workload"] == workload
     assert j["config"]["streams_per_gpu"] == per_rank
     part = _detail()["partition"]
-    assert part["streams_total"] == 8 * per_rank and len(part["per_rank"]) == 8
+    assert part["streams_total"] == N * per_rank and len(part["per_rank"]) == N
     for rk, rec in enumerate(part["per_rank"]):
         assert rec["rank"] == rk and rec["streams"] == [rk * per_rank, (rk + 1) * per_rank], rec
         assert rec["parity"] == "ok", rec                      # every rank gated its own shard
         assert rec["positions_found"] > 0, rec
-    assert [q[:5] for q in j["partition"]["ranks"]] == [[rk, 0, rk * per_rank, (rk + 1) * per_rank, "ok"] for rk in range(8)]
+    assert [q[:5] for q in j["partition"]["ranks"]] == [[rk, 0, rk * per_rank, (rk + 1) * per_rank, "ok"] for rk in range(N)]
     assert j["parity"] == "ok", j["parity"]
     timed = _detail()["timing"]["steps_timed"]
-    assert timed % K == 0 and j["positions_expected"] == 8 * per_rank * timed
+    assert timed == K and j["positions_expected"] == N * per_rank * timed
     assert j["positions_found"] >= 0.7 * j["positions_expected"]       # (young models, 40 frames: the gates check WHICH)
-    assert abs(j["value"] - 8 * per_rank * K / (j["ms_per_step"] * K / 1e3)) < 1e-5 * j["value"]
+    assert abs(j["value"] - N * per_rank * K / (j["ms_per_step"] * K / 1e3)) < 1e-5 * j["value"]
     assert j["cpu_baseline"] is None and j["roofline"]["frac"] is None and j.get("extra_workloads") is None
     assert j["scatter_ingest"]["parity"] == "ok" and j["scatter_ingest"]["bytes_per_peer"] == per_rank * (1080 * 1920 if per_rank == 8 else 2160 * 3840) * 3
 
 
-def test_the_drivers_own_multi_gpu_command_yields_the_whole_record_on_one_gpu():
-    """`python3 bench.py --gpus 8 --steps 20 --warmup 5` -- the driver's exact argv for its one-shot SCALE run, plus `--backend
-    gloo` so that eight ranks can share the one GPU there is here.  ONE invocation, no launcher in front,
-    default ageing / pool / gates: one line <= 4 KB with n_gpus 8 that carries BOTH north-star sizes at N GPUs -- `value` on
+def test_the_drivers_multi_gpu_command_at_three_ranks_yields_the_whole_record_on_one_gpu():
+    """`python3 bench.py --gpus 3 --steps 20 --warmup 5` -- the driver's argv for its one-shot SCALE run (there with --gpus 8),
+    plus `--backend gloo` so that the ranks can share the one GPU there is here.  ONE invocation, no
+    launcher in front, default ageing / pool / gates: one line <= 4 KB with n_gpus 3 that carries BOTH north-star sizes at N GPUs -- `value` on
     configs[4]'s shard (one 4K stream a rank) and `extra_workloads.1080p8` on configs[3]'s (8 x 1080p a rank), both parity
     gates green on every rank for both --, the benched per-pixel launch as a fraction of the HBM peak from the slowest
     rank's HIP events (no profiler child at N > 1), the per-rank kernel times, and the stream->rank scatter for both sizes."""
     import time
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = lambda port: [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--backend", "gloo"]
+    N = RANKS
+    cmd = lambda port: [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(N), "--steps", "20", "--warmup", "5", "--backend", "gloo"]
     t0 = time.perf_counter()
     r = _launch(cmd, env, 900)
     wall = time.perf_counter() - t0
@@ -148,13 +155,13 @@ def test_the_drivers_own_multi_gpu_command_yields_the_whole_record_on_one_gpu():
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and len(lines[0]) <= 4096, r.stdout[-2000:]
     j = json.loads(lines[0])
-    assert j["n_gpus"] == 8 and j["steps"] == 20 and j["warmup"] == 5 and j["config"]["workload"] == "4k1"
-    assert j["parity"] == "ok" and [q[4] for q in j["partition"]["ranks"]] == ["ok"] * 8
+    assert j["n_gpus"] == N and j["steps"] == 20 and j["warmup"] == 5 and j["config"]["workload"] == "4k1"
+    assert j["parity"] == "ok" and [q[4] for q in j["partition"]["ranks"]] == ["ok"] * N
     assert set(j["extra_workloads"]) == {"1080p8"} and j["extra_workloads"]["1080p8"] > 0 and j["extra_parity"] == "ok"
     d = _detail()
     ex = d["extra_workloads"]["1080p8"]
-    assert ex["streams_total"] == 64 and [q["parity"] for q in ex["per_rank"]] == ["ok"] * 8 and ex["timed_region_ms"] >= 50.0
-    assert ex["value"] == pytest.approx(64 * 20 / (ex["ms_per_step"] * 20 / 1e3), rel=1e-6)
+    assert ex["streams_total"] == 8 * N and [q["parity"] for q in ex["per_rank"]] == ["ok"] * N and ex["timed_region_ms"] >= 50.0
+    assert ex["value"] == pytest.approx(8 * N * 20 / (ex["ms_per_step"] * 20 / 1e3), rel=1e-6)
     rf = j["roofline"]
     assert rf["frac"] is None and rf["frac_benched"] is not None and 0.0 < rf["frac_benched"] < 1.0 and rf["frac_benched_source"] == "audit"
     assert rf["benched_launch_ms"] == pytest.approx(rf["k1_ms_ranks"][1], rel=1e-3) and rf["k1_ms_ranks"][0] <= rf["k1_ms_ranks"][1]
@@ -162,7 +169,7 @@ def test_the_drivers_own_multi_gpu_command_yields_the_whole_record_on_one_gpu():
     sc = j["scatter_ingest"]
     assert sc["parity"] == "ok" and sc["bytes_per_peer"] == 2160 * 3840 * 3
     assert sc["also"]["workload"] == "1080p8" and sc["also"]["parity"] == "ok" and sc["also"]["bytes_per_peer"] == 8 * 1080 * 1920 * 3
-    assert j["rccl"] == {"ranks": 8, "backend": "gloo", "version": None}
+    assert j["rccl"] == {"ranks": N, "backend": "gloo", "version": None}
     assert j["value_mean"] > 0 and j["positions_with_target"] <= j["positions_expected"]
     with open(os.path.join(ROOT, "gpurun_out", "drivers_multi_gpu_command_wall_s.txt"), "w") as f:
         f.write("%.1f s wall, line %d bytes\n%s\n" % (wall, len(lines[0]), lines[0]))

@@ -1,5 +1,5 @@
-import sys, numpy as np, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench, oat_amd
 from oat_amd.synth import disc_hsv_window
 rows, cols = 1080, 1920
