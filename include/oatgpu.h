@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define OATGPU_ABI_VERSION 9     /* 2: oatgpu_position grew (filter outputs), new entry points; 3: oatgpu_config.mog_restore_nmodes; 4: oatgpu_cvt_color, oatgpu_set_fusion, oatgpu_set_homography, oatgpu_profile.mog_frames; 5: oatgpu_track_sequence_dev_timed, oatgpu_track_enqueue_dev pairs frames only after oatgpu_set_fusion(2); 6: oatgpu_track_input_consumed_stream, oatgpu_track_stage, oatgpu_track_enqueue_staged; 7: oatgpu_track_stage_abort, oatgpu_set_early_blob, oatgpu_set_stage_copy, oatgpu_set_deferred / _fetch_frame / _fetch_position, a failed pipelined launch is fatal for its context; 8: oatgpu_track_sequence_dev_latency, oatgpu_device_open_retries, oatgpu_set_k1_workgroup, oatgpu_last_step_shape, oatgpu_early_blob_timeouts, a parked blob workgroup that times out switches early dispatch off for its context; 9: oatgpu_profile.dropped, every scratch set is allocated by oatgpu_create (an out-of-memory is reported there, never in the middle of a step) */
+#define OATGPU_ABI_VERSION 9     /* 2: oatgpu_position grew (filter outputs), new entry points; 3: oatgpu_config.mog_restore_nmodes; 4: oatgpu_cvt_color, oatgpu_set_fusion, oatgpu_set_homography, oatgpu_profile.mog_frames; 5: oatgpu_track_sequence_dev_timed, oatgpu_track_enqueue_dev pairs frames only after oatgpu_set_fusion(2); 6: oatgpu_track_input_consumed_stream, oatgpu_track_stage, oatgpu_track_enqueue_staged; 7: oatgpu_track_stage_abort, oatgpu_set_early_blob, oatgpu_set_stage_copy, oatgpu_set_deferred / _fetch_frame / _fetch_position, a failed pipelined launch is fatal for its context; 8: oatgpu_track_sequence_dev_latency, oatgpu_device_open_retries, oatgpu_set_k1_workgroup, oatgpu_last_step_shape, oatgpu_early_blob_timeouts, a parked blob workgroup that times out switches early dispatch off for its context; 9: oatgpu_profile.dropped, every scratch set is allocated by oatgpu_create (an out-of-memory is reported there, never in the middle of a step); additive entries of 9 (detect them by symbol): oatgpu_undistort_map, oatgpu_set_undistort, oatgpu_undistort_filter, oatgpu_undistort_dev */
 
 enum {
     OATGPU_OK = 0,
@@ -267,8 +267,32 @@ int oatgpu_mask_filter(oatgpu_ctx *ctx, int32_t stream, const uint8_t *in, uint8
 int oatgpu_thresh_filter(oatgpu_ctx *ctx, const uint8_t *frame_in, uint8_t *frame_out, int32_t i_min,
                          int32_t i_max);
 
+/* Undistorter::filter (`framefilt undistort`, src/framefilter/Undistorter.cpp:83-88): cv::undistort(frame, K, D) of OpenCV 3.1
+ * with no new camera matrix -- the map of initUndistortRectifyMap (CV_16SC2, built in cv::undistort's stripes of
+ * max(1, 4096 / cols) rows) and remap(INTER_LINEAR, BORDER_CONSTANT 0) in its fixed point, on 8-bit GREY or BGR frames.
+ * K: the camera matrix, row-major [K11, K12, ..., K33] (--camera-matrix); dist: k1, k2, p1, p2, k3[, k4, k5, k6]
+ * (--distortion-coeffs).  n_dist must be 5 or 8: fewer than 5 or more than 8 fail with the reference's text
+ * (Undistorter.cpp:61-62); 6 and 7 pass the reference's check but OpenCV 3.1 asserts on them at the first frame, so they are
+ * refused here.
+ *
+ * oatgpu_undistort_map: the map alone, on the host, without a device or a context -- exactly OpenCV's two planes:
+ * map1 rows*cols*2 shorts (sx, sy), map2 rows*cols fractions (fy*32 + fx, in 1/32 px). */
+int oatgpu_undistort_map(int32_t rows, int32_t cols, const double K[9], const double *dist, int32_t n_dist,
+                         int16_t *map1, uint16_t *map2);
+/* The map of camera stream s, built on the host once (cv::undistort rebuilds the same map every frame) and kept on the
+ * device; the first call allocates the context's map planes (6 B a pixel and stream).  n_dist = 0 removes the stream's map.
+ * Each stream may have its own calibration. */
+int oatgpu_set_undistort(oatgpu_ctx *ctx, int32_t stream, const double K[9], const double *dist, int32_t n_dist);
+/* One frame of stream s (rows*cols*channels bytes); out may equal in (the reference clones first).  OATGPU_E_INVALID when
+ * the stream has no map. */
+int oatgpu_undistort_filter(oatgpu_ctx *ctx, int32_t stream, const uint8_t *in, uint8_t *out);
+/* Throughput form: one frame for EVERY stream, device memory, stream-major (as oatgpu_track_batch_dev), in ONE kernel launch
+ * on the context's stream; returns once it is queued (oatgpu_synchronize / the stream from oatgpu_get_stream order the
+ * caller's work behind it).  Every stream needs a map; out_dev must not overlap frames_dev. */
+int oatgpu_undistort_dev(oatgpu_ctx *ctx, const void *frames_dev, void *out_dev);
+
 /* Deferred completion of the stage-by-stage operators below (default off).  With on = 1 a frame filter (oatgpu_mog_filter,
- * _bsub_filter, _mask_filter, _thresh_filter, _bgr2hsv, _cvt_color) or a detector (oatgpu_detect_hsv / _thresh / _diff)
+ * _bsub_filter, _mask_filter, _thresh_filter, _undistort_filter, _bgr2hsv, _cvt_color) or a detector (oatgpu_detect_hsv / _thresh / _diff)
  * returns as soon as its INPUT frame has been read -- the point where the reference posts its SOURCE, right after its
  * memcpy (FrameFilter.cpp:73-80, PositionDetector.cpp:78-86) -- leaves its output argument untouched (it may be NULL for the
  * detectors) and keeps the result on the device; oatgpu_fetch_frame / oatgpu_fetch_position then deliver it: a component

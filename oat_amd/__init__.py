@@ -10,7 +10,8 @@ by the tests and the benchmark; there is no CPU fallback -- importing
 from .ffi import OatGpuError, lib_path  # noqa: F401
 from .components import (  # noqa: F401
     BackgroundSubtractorMOG, BackgroundSubtractor, Threshold, ColorConvert, HSVDetector, SimpleThreshold, DifferenceDetector, HotPath, Position2D,
+    Undistorter, undistort_map,
 )
 
 __all__ = ["BackgroundSubtractorMOG", "BackgroundSubtractor", "Threshold", "ColorConvert", "HSVDetector", "SimpleThreshold", "DifferenceDetector", "HotPath",
-           "Position2D", "OatGpuError", "lib_path"]
+           "Undistorter", "undistort_map", "Position2D", "OatGpuError", "lib_path"]

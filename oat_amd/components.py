@@ -7,6 +7,7 @@ reference's call sites:
     ColorConvert.filter(frame)                 src/framefilter/ColorConvert.cpp:101-107
     HSVDetector.detectPosition(frame, pos)     src/positiondetector/HSVDetector.cpp:142-173
     SimpleThreshold.detectPosition(frame, pos) src/positiondetector/SimpleThreshold.cpp:114-134
+    Undistorter.filter(frame)                  src/framefilter/Undistorter.cpp:83-88
 
 ``HotPath`` is the fused, batched form (N camera streams, one launch per stage).
 All pixel work happens in liboatgpu.so on the GPU.
@@ -194,6 +195,63 @@ class Threshold(_Context):
         out = np.empty_like(f)
         self._chk(self.lib.oatgpu_thresh_filter(self.ctx, ffi.u8(f), ffi.u8(out), self.i_min_, self.i_max_))
         return out
+
+
+def _calibration(camera_matrix, distortion_coeffs):
+    K = np.ascontiguousarray(camera_matrix, np.float64).reshape(-1)
+    if K.size != 9:
+        raise ValueError("'camera-matrix' must be a TOML vector containing 9 elements.")   # TOMLSanitize.h:338-341
+    D = np.ascontiguousarray(distortion_coeffs, np.float64).reshape(-1)
+    return K, D
+
+
+def undistort_map(rows, cols, camera_matrix, distortion_coeffs):
+    """cv::undistort's map (OpenCV 3.1, CV_16SC2) of a rows x cols frame, built on the host without a device:
+    (map1 int16 (rows, cols, 2) = (sx, sy), map2 uint16 (rows, cols) = fy * 32 + fx in 1/32 px)."""
+    lib = ffi.load()
+    K, D = _calibration(camera_matrix, distortion_coeffs)
+    map1 = np.empty((rows, cols, 2), np.int16)
+    map2 = np.empty((rows, cols), np.uint16)
+    ffi.check(lib, None, lib.oatgpu_undistort_map(rows, cols, K.ctypes.data_as(C.POINTER(C.c_double)),
+                                                  D.ctypes.data_as(C.POINTER(C.c_double)), D.size,
+                                                  map1.ctypes.data_as(C.POINTER(C.c_int16)),
+                                                  map2.ctypes.data_as(C.POINTER(C.c_uint16))))
+    return map1, map2
+
+
+class Undistorter(_Context):
+    """framefilt undistort (Undistorter.cpp): -k camera matrix (9 values), -d distortion coefficients (5 or 8).
+    Every stream starts with the same calibration; set_calibration gives one stream its own."""
+
+    def __init__(self, rows, cols, camera_matrix, distortion_coeffs, channels=3, n_streams=1, **kw):
+        super().__init__(rows, cols, n_streams=n_streams, channels=channels, **kw)
+        for s in range(n_streams):
+            self.set_calibration(s, camera_matrix, distortion_coeffs)
+
+    def set_calibration(self, stream, camera_matrix, distortion_coeffs):
+        """New calibration of one stream; distortion_coeffs None or empty removes its map."""
+        if distortion_coeffs is None or len(distortion_coeffs) == 0:
+            self._chk(self.lib.oatgpu_set_undistort(self.ctx, stream, None, None, 0))
+            return
+        K, D = _calibration(camera_matrix, distortion_coeffs)
+        self._chk(self.lib.oatgpu_set_undistort(self.ctx, stream, K.ctypes.data_as(C.POINTER(C.c_double)),
+                                                D.ctypes.data_as(C.POINTER(C.c_double)), D.size))
+
+    def filter(self, frame, stream=0):
+        f = _frame(frame, self.frame_shape)
+        out = np.empty_like(f)
+        self._chk(self.lib.oatgpu_undistort_filter(self.ctx, stream, ffi.u8(f), ffi.u8(out)))
+        return out
+
+    def filter_dev(self, frames_dev, out_dev):
+        """Every stream's frame, device pointers (stream-major), one launch on the context's stream (not waited for)."""
+        self._chk(self.lib.oatgpu_undistort_dev(self.ctx, C.c_void_p(frames_dev), C.c_void_p(out_dev)))
+
+    def synchronize(self):
+        self._chk(self.lib.oatgpu_synchronize(self.ctx))
+
+    def get_stream(self):
+        return self.lib.oatgpu_get_stream(self.ctx)
 
 
 PIX_BINARY, PIX_GREY, PIX_BGR, PIX_HSV = 0, 1, 2, 3      # oat::PixelColor (Color.h:29-34)

@@ -172,6 +172,10 @@ struct oatgpu_ctx {
     uint8_t *diff_last = nullptr;  // [n][H*W] previous GREY frame of posidet diff, allocated on first use
     std::vector<char> diff_have;   // per camera stream
     u64 *roi = nullptr;            // [n][Palloc/64] ROI bits, allocated on first oatgpu_set_roi_mask
+    uint32_t *ud_map1 = nullptr;   // [n][ud_stride] framefilt undistort maps (sx | sy << 16) and [n][ud_stride] fractions,
+    uint16_t *ud_map2 = nullptr;   //   allocated on first oatgpu_set_undistort (kernels_undistort.hip)
+    size_t ud_stride = 0;
+    std::vector<char> ud_have;     // per camera stream: has a map
     BlobBuffers bb[kSets]{};          // scratch sets (bb[0].thr holds the ring's threshold buffers), all made with the context
     const u64 *last_morph = nullptr;
     const u64 *last_fin = nullptr;
@@ -394,7 +398,7 @@ struct DevBuf {             // scoped device allocation
 static void free_all(oatgpu_ctx *c)
 {
     if (!c) return;
-    hipFree(c->bsub_bg); hipFree(c->bsub_f); hipFree(c->diff_last); hipFree(c->roi); hipFree(c->state); hipFree(c->nmodes); hipFree(c->frames); hipFree(c->aux_a); hipFree(c->aux_b);
+    hipFree(c->bsub_bg); hipFree(c->bsub_f); hipFree(c->diff_last); hipFree(c->roi); hipFree(c->ud_map1); hipFree(c->ud_map2); hipFree(c->state); hipFree(c->nmodes); hipFree(c->frames); hipFree(c->aux_a); hipFree(c->aux_b);
     hipFree(c->bb[0].thr);
     hipFree(c->nopark);
     hipFree(c->kal.state);
@@ -550,6 +554,7 @@ extern "C" oatgpu_ctx *oatgpu_create(const oatgpu_config *cfg)
     c->wild_model.assign(n, 0);
     c->diff_have.assign(n, 0);
     c->bsub_have.assign(n, 0);
+    c->ud_have.assign(n, 0);
 
     bool ok = true;
     auto A = [&](void **p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) ok = false; };
@@ -1105,6 +1110,94 @@ extern "C" int oatgpu_thresh_filter(oatgpu_ctx *c, const uint8_t *in, uint8_t *o
     launch_thresh_filter(c->aux_a, c->aux_b, npx, c->cfg.channels, lo, hi, c->stream);
     HIPCHK(c, hipGetLastError());
     return finish_frame(c, out, c->aux_b, nb);
+}
+
+// ------------------------------------------------------- framefilt undistort (Undistorter.cpp:83-88) ----
+
+static int check_undistort_args(oatgpu_ctx *c, const double *K, const double *dist, int n_dist)
+{
+    const char *why = nullptr;
+    if (!K || !dist) return fail(c, OATGPU_E_INVALID, "null argument");
+    if (undistort_check_coeffs(n_dist, &why)) return fail(c, OATGPU_E_INVALID, "%s", why);
+    return OATGPU_OK;
+}
+
+extern "C" int oatgpu_undistort_map(int32_t rows, int32_t cols, const double K[9], const double *dist, int32_t n_dist,
+                                    int16_t *map1, uint16_t *map2)
+{
+    if (rows < 1 || cols < 1) return fail(nullptr, OATGPU_E_INVALID, "rows and cols must be >= 1");
+    if (!map1 || !map2) return fail(nullptr, OATGPU_E_INVALID, "null argument");
+    const int rc = check_undistort_args(nullptr, K, dist, n_dist);
+    if (rc) return rc;
+    undistort_build_map(rows, cols, K, dist, n_dist, map1, map2);
+    return OATGPU_OK;
+}
+
+extern "C" int oatgpu_set_undistort(oatgpu_ctx *c, int32_t s, const double K[9], const double *dist, int32_t n_dist)
+{
+    int rc = check_stream_ix(c, s);
+    if (rc) return rc;
+    if (n_dist == 0) { c->ud_have[(size_t)s] = 0; return OATGPU_OK; }   // (nothing on the device reads a stream without a map)
+    rc = check_undistort_args(c, K, dist, n_dist);
+    if (rc) return rc;
+    const Geom &g = c->g;
+    const size_t npx = (size_t)g.H * g.W, n = c->cfg.n_streams;
+    std::vector<int16_t> m1(npx * 2);
+    std::vector<uint16_t> m2(npx);
+    undistort_build_map(g.H, g.W, K, dist, n_dist, m1.data(), m2.data());
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    rc = quiesce(c);                    // an undistortion still in flight may be reading the old map
+    if (rc) return rc;
+    if (!c->ud_map1) {
+        c->ud_stride = undistort_map_stride(g.H, g.W);
+        HIPCHK(c, hipMalloc((void **)&c->ud_map1, n * c->ud_stride * sizeof(uint32_t)));
+        if (hipMalloc((void **)&c->ud_map2, n * c->ud_stride * sizeof(uint16_t)) != hipSuccess) {
+            hipFree(c->ud_map1);
+            c->ud_map1 = nullptr;
+            return fail(c, OATGPU_E_NOMEM, "device allocation of the undistortion maps failed");
+        }
+        HIPCHK(c, hipMemsetAsync(c->ud_map1, 0, n * c->ud_stride * sizeof(uint32_t), c->stream));   // (the padding is read)
+        HIPCHK(c, hipMemsetAsync(c->ud_map2, 0, n * c->ud_stride * sizeof(uint16_t), c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->ud_map1 + (size_t)s * c->ud_stride, m1.data(), npx * sizeof(uint32_t), hipMemcpyHostToDevice,
+                             c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->ud_map2 + (size_t)s * c->ud_stride, m2.data(), npx * sizeof(uint16_t), hipMemcpyHostToDevice,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ud_have[(size_t)s] = 1;
+    return OATGPU_OK;
+}
+
+extern "C" int oatgpu_undistort_filter(oatgpu_ctx *c, int32_t s, const uint8_t *in, uint8_t *out)
+{
+    int rc = check_stream_ix(c, s);
+    if (rc) return rc;
+    if (!in || !out) return fail(c, OATGPU_E_INVALID, "null argument");
+    if (!c->ud_have[(size_t)s]) return fail(c, OATGPU_E_INVALID, "stream %d has no undistortion map (oatgpu_set_undistort)", s);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    rc = quiesce(c);
+    if (rc) return rc;
+    const size_t nb = (size_t)c->g.H * c->g.W * c->cfg.channels;
+    rc = stage_in(c, c->aux_a, in, nb);             // (the reference clones first: out == in is fine, the kernel reads aux_a)
+    if (rc) return rc;
+    launch_undistort(c->aux_a, c->aux_b, c->ud_map1 + (size_t)s * c->ud_stride, c->ud_map2 + (size_t)s * c->ud_stride,
+                     c->ud_stride, c->g.H, c->g.W, c->cfg.channels, 1, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return finish_frame(c, out, c->aux_b, nb);
+}
+
+extern "C" int oatgpu_undistort_dev(oatgpu_ctx *c, const void *frames_dev, void *out_dev)
+{
+    if (!c) return OATGPU_E_INVALID;
+    if (!frames_dev || !out_dev) return fail(c, OATGPU_E_INVALID, "null argument");
+    if (frames_dev == out_dev) return fail(c, OATGPU_E_INVALID, "undistort_dev cannot work in place");
+    for (int s = 0; s < c->cfg.n_streams; ++s)
+        if (!c->ud_have[(size_t)s]) return fail(c, OATGPU_E_INVALID, "stream %d has no undistortion map (oatgpu_set_undistort)", s);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    launch_undistort((const uint8_t *)frames_dev, (uint8_t *)out_dev, c->ud_map1, c->ud_map2, c->ud_stride, c->g.H, c->g.W,
+                     c->cfg.channels, c->cfg.n_streams, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return OATGPU_OK;
 }
 
 extern "C" int oatgpu_bgr2hsv(oatgpu_ctx *c, const uint8_t *bgr_in, uint8_t *hsv_out)

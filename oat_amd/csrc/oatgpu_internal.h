@@ -153,6 +153,18 @@ void launch_state_import(const Geom &g, float *state, uint8_t *nmodes, int nmix,
                          const uint8_t *modes_used, const float *weight, const float *variance,
                          const float *mean, hipStream_t st);
 
+// --- kernels_undistort.hip --- (framefilt undistort, Undistorter.cpp:83-88)
+// 0, or -1 with the reason in *why: 5 to 8 coefficients (the reference's check) and not 6 or 7 (OpenCV 3.1 asserts on those)
+int undistort_check_coeffs(int n_dist, const char **why);
+// cv::undistort's map of a rows x cols frame (stripes of initUndistortRectifyMap, CV_16SC2): map1 rows*cols*2, map2 rows*cols
+void undistort_build_map(int rows, int cols, const double K[9], const double *dist, int n_dist, int16_t *map1, uint16_t *map2);
+// device map planes of one stream are padded to a multiple of kMapAlign entries: map1 as one u32 (sx | sy << 16) a pixel
+constexpr int kMapAlign = 64;
+size_t undistort_map_stride(int H, int W);
+// remap of n_streams consecutive frames (stream-major, H*W*channels bytes each) with map planes map1 / map2 + s * map_stride
+void launch_undistort(const uint8_t *in, uint8_t *out, const uint32_t *map1, const uint16_t *map2, size_t map_stride, int H,
+                      int W, int channels, int n_streams, hipStream_t st);
+
 // --- kernels_blob.hip ---
 struct BlobBuffers {
     u64 *thr;        // [2][n][Palloc/64] inRange output, double-buffered across frames

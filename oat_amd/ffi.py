@@ -87,6 +87,11 @@ SIGNATURES = {
     "oatgpu_bsub_set_background": (C.c_int, [_ctx, C.c_int32, _u8p]),
     "oatgpu_mask_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p]),
     "oatgpu_thresh_filter": (C.c_int, [_ctx, _u8p, _u8p, C.c_int32, C.c_int32]),
+    "oatgpu_undistort_map": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32,
+                                       C.POINTER(C.c_int16), C.POINTER(C.c_uint16)]),
+    "oatgpu_set_undistort": (C.c_int, [_ctx, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32]),
+    "oatgpu_undistort_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p]),
+    "oatgpu_undistort_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
     "oatgpu_mog_apply": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_mog_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_bgr2hsv": (C.c_int, [_ctx, _u8p, _u8p]),

@@ -435,6 +435,31 @@ struct Options {
         if (sscanf(s.c_str(), " [ %lf , %lf ]", &a, &b) != 2) throw std::runtime_error("'" + k + "' must be a 2-element array, e.g. [0,256]");
         return true;
     }
+    // "[x1,x2,...]" -> any number of values (getArray<double>, TOMLSanitize.h:279-316); getArray<double, N>'s size check
+    // is the caller's ("'key' must be a TOML vector containing N elements.", :338-341)
+    bool arr(const std::string &k, std::vector<double> &out) const
+    {
+        if (!has(k)) return false;
+        const std::string &s = kv.at(k);
+        const size_t a = s.find_first_not_of(" \t"), b = s.find_last_not_of(" \t");
+        if (a == std::string::npos || s[a] != '[' || s[b] != ']') throw std::runtime_error("'" + k + "' must be a TOML array.");
+        out.clear();
+        const std::string body = s.substr(a + 1, b - a - 1);
+        if (body.find_first_not_of(" \t") == std::string::npos) return true;
+        size_t pos = 0;
+        while (true) {
+            const size_t comma = body.find(',', pos);
+            const std::string item = body.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos);
+            char *end = nullptr;
+            const double v = strtod(item.c_str(), &end);
+            if (end == item.c_str() || item.find_first_not_of(" \t", end - item.c_str()) != std::string::npos)
+                throw std::runtime_error("'" + k + "' must be a TOML array of numbers.");
+            out.push_back(v);
+            if (comma == std::string::npos) break;
+            pos = comma + 1;
+        }
+        return true;
+    }
     // "[h11,...,h33]" -> 9 numbers (getArray<double, 9>, HomographyTransform2D.cpp:48-58)
     bool arr9(const std::string &k, double *h) const
     {

@@ -3,6 +3,7 @@
 //         col   MI355X replacement of `oat framefilt col`  (src/framefilter/ColorConvert.cpp): every pair of oat::color_conv_table
 //         bsub  MI355X replacement of `oat framefilt bsub` (src/framefilter/BackgroundSubtractor.cpp)
 //         thresh MI355X replacement of `oat framefilt thresh` (src/framefilter/Threshold.cpp)
+//         undistort MI355X replacement of `oat framefilt undistort` (src/framefilter/Undistorter.cpp)
 // Drop-in: same positional arguments, same option names (src/framefilter/main.cpp:91-296).
 #include "component.hpp"
 #include <unistd.h>
@@ -195,11 +196,40 @@ protected:
     GpuCtx gpu_;
 };
 
+// src/framefilter/Undistorter.cpp:83-88: cv::undistort(temp, frame, camera_matrix_, dist_coeff_); the map is built once
+class Undistorter : public FrameFilter {
+public:
+    using FrameFilter::FrameFilter;
+    double camera_matrix_[9] = {};
+    std::vector<double> dist_coeff_;
+    int gpu_index_{0};
+
+protected:
+    void configure_for(const FrameParams &p) override
+    {
+        oatgpu_config cfg;
+        oatgpu_default_config(&cfg);
+        cfg.device = gpu_index_; cfg.rows = (int)p.rows; cfg.cols = (int)p.cols; cfg.channels = color_bytes(p.color);
+        if (cfg.channels != 1 && cfg.channels != 3) throw std::runtime_error("framefilt undistort (hip) needs 1- or 3-byte pixels");
+        gpu_.create(cfg);
+        gpu_.check(oatgpu_set_undistort(gpu_.ctx, 0, camera_matrix_, dist_coeff_.data(), (int32_t)dist_coeff_.size()));
+    }
+    void filter(Frame &frame) override { gpu_.check(oatgpu_undistort_filter(gpu_.ctx, 0, frame.data(), frame.data())); }
+    bool filter_from_shm(const Frame &in, Frame &out) override
+    {
+        gpu_.check(oatgpu_undistort_filter(gpu_.ctx, 0, in.data(), out.data()));
+        return true;
+    }
+    oatgpu_ctx *deferred_ctx() override { return gpu_.ctx; }
+    GpuCtx gpu_;
+};
+
 static void usage()
 {
     std::cout << "Usage: oat-framefilt-hip TYPE SOURCE SINK [CONFIGURATION]\n"
                  "TYPE\n  mog: MOG2 background segmentation on an MI355X\n  col: colour conversion (BGR -> HSV | GREY, GREY -> BGR, HSV -> BGR) on an MI355X\n"
                  "  bsub | thresh | mask: the other per-pixel filters of oat-framefilt\n"
+                 "  undistort: lens-distortion correction (cv::undistort) on an MI355X\n"
                  "all:  --gpu-index N           HIP device ordinal (default 0)\n"
                  "mog:  -a, --adaptation-coeff  0..1, default 0 (no adaptation)\n"
                  "      --model-file FILE    resume the background model from FILE if it exists; checkpoint it there on exit\n"
@@ -207,7 +237,9 @@ static void usage()
                  "bsub: -a, --adaptation-coeff  0..1, default 0 (static background = first frame)\n"
                  "      -f, --background FILE   PGM/PPM background image instead of the first frame\n"
                  "mask: -f, --mask FILE         PGM/PPM: pixels where it is 0 are set to 0\n"
-                 "thresh: -I, --intensity       [min,max] in [0,256]\n";
+                 "thresh: -I, --intensity       [min,max] in [0,256]\n"
+                 "undistort: -k, --camera-matrix [K11,K12,...,K33] (required)\n"
+                 "      -d, --distortion-coeffs [k1,k2,p1,p2,k3] or [k1,k2,p1,p2,k3,k4,k5,k6] (required)\n";
 }
 
 int main(int argc, char **argv)
@@ -216,7 +248,8 @@ int main(int argc, char **argv)
         // -f is "background" for bsub and "mask" for mask (BackgroundSubtractor.cpp:52, FrameMasker.cpp:45)
         const bool is_mask = argc > 1 && std::string(argv[1]) == "mask";
         Options o = Options::parse(argc, argv, {{"a", "adaptation-coeff"}, {"C", "color"}, {"I", "intensity"},
-                                                {"f", is_mask ? "mask" : "background"}, {"h", "help"}, {"v", "version"}}, {"help", "version"});
+                                                {"f", is_mask ? "mask" : "background"}, {"k", "camera-matrix"},
+                                                {"d", "distortion-coeffs"}, {"h", "help"}, {"v", "version"}}, {"help", "version"});
         if (o.has("version")) { std::cout << "oat-framefilt-hip (MI355X drop-in, liboatgpu ABI " << oatgpu_abi_version() << ")\n"; return 0; }
         if (o.has("help") || o.positional.size() != 3) { usage(); return o.has("help") ? 0 : -1; }
         const std::string type = o.positional[0];
@@ -227,6 +260,7 @@ int main(int argc, char **argv)
         else if (type == "bsub") o.apply_config({"adaptation-coeff", "background", "gpu-index"});
         else if (type == "thresh") o.apply_config({"intensity", "gpu-index"});
         else if (type == "mask") o.apply_config({"mask", "gpu-index"});
+        else if (type == "undistort") o.apply_config({"camera-matrix", "distortion-coeffs", "gpu-index"});   // Undistorter.cpp:43-53
         const int gpu_index = (int)o.num("gpu-index", 0, 0, 64);
         std::unique_ptr<Component> comp;
         if (type == "mog") {
@@ -260,6 +294,23 @@ int main(int argc, char **argv)
                     throw std::runtime_error("Values of intensity should be between 0 and 256.");   // Threshold.cpp:62-63
                 f->i_min_ = (int)a; f->i_max_ = (int)b;
             }
+            f->gpu_index_ = gpu_index;
+            comp = std::move(f);
+        } else if (type == "undistort") {
+            // Undistorter.cpp:57-81, checked here, before any device is opened: distortion-coeffs first, then camera-matrix
+            auto f = std::make_unique<Undistorter>(o.positional[1], o.positional[2]);
+            if (!o.arr("distortion-coeffs", f->dist_coeff_))
+                throw std::runtime_error("Required configuration value 'distortion-coeffs' was not specified.");   // TOMLSanitize.h:198
+            if (f->dist_coeff_.size() < 5 || f->dist_coeff_.size() > 8)
+                throw std::runtime_error("Distortion coefficients consist of 5 to 8 values.");
+            std::vector<double> K;
+            if (!o.arr("camera-matrix", K)) throw std::runtime_error("Required configuration value 'camera-matrix' was not specified.");
+            if (K.size() != 9) throw std::runtime_error("'camera-matrix' must be a TOML vector containing 9 elements.");   // TOMLSanitize.h:338-341
+            std::copy(K.begin(), K.end(), f->camera_matrix_);
+            int16_t m1[2];
+            uint16_t m2[1];
+            if (oatgpu_undistort_map(1, 1, f->camera_matrix_, f->dist_coeff_.data(), (int32_t)f->dist_coeff_.size(), m1, m2) != OATGPU_OK)
+                throw std::runtime_error(oatgpu_last_error(nullptr));      // 6 or 7 coefficients: OpenCV 3.1 would assert (the library says why)
             f->gpu_index_ = gpu_index;
             comp = std::move(f);
         } else {
