@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the fused hot path (mog + hsv + erode/dilate + blob) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
+
+A plain run measures the headline alone: it sets up, ages the models, warms up, times exactly K steps, writes
+--dump-outputs and prints the line.  Everything else below -- the parity gates against the oracle, roofline, audits,
+PMC passes, latency probes, extra_workloads, the other learning rate and frames-per-launch legs, the process pipeline,
+cpu_baseline and, at N > 1, the second workload and the scatter legs -- runs only with --full (the --no-* switches and
+--quick trim a --full run).
 
 One "step" = one frame for every camera stream a rank owns, through the whole
 fused chain (MOG2 update, setTo, BGR2HSV, inRange, erode, dilate, labelling,
@@ -34,7 +40,7 @@ bench_detail.json beside this file and, as one line, to stderr.
 `--gpus N` IS an N-rank run: without WORLD_SIZE in the environment the script re-executes itself through
 `python -m torch.distributed.run --nproc-per-node N` (one rank per device; fewer devices than ranks is an error with the
 "nccl" backend); under a launcher whose world differs from --gpus it refuses to run.
-The PMC numbers come from rocprofv3 child processes of this very run (--no-pmc to skip them).
+The PMC numbers come from rocprofv3 child processes of this very --full run (--no-pmc to skip them).
 """
 import argparse
 import json
@@ -188,6 +194,7 @@ def slim_line(full):
     line["device_open_retries"] = full.get("device_open_retries")
     line["timed_region_ms"] = _sig(full.get("timed_region_ms"))
     line["bench_wall_s"] = _sig(full.get("bench_wall_s"), 4)
+    line["full_run"] = full.get("full_run")
     line["detail"] = "bench_detail.json"
     return line
 
@@ -1485,6 +1492,10 @@ def main():
     ap.add_argument("--dense-model", action="store_true",
                     help="make the dense diagnostic the benched workload: input that keeps all 5 mixture modes live on "
                          "every pixel (K1 moves the full 205 B/px) and a threshold window nothing passes")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: parity gates, roofline and PMC passes, audits, latency "
+                         "probes, extra workloads and legs, process pipeline, CPU baseline, N > 1 scatter (a plain run sets "
+                         "up, warms up, times --steps steps, writes --dump-outputs and prints the line)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC child passes (roofline.traffic = null)")
@@ -1492,7 +1503,7 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the extra_workloads legs (1080p16, 1080p8, 1080p1, vga1)")
     ap.add_argument("--no-spin-up", action="store_true")
     ap.add_argument("--no-pipeline", action="store_true", help="skip the drop-in process pipeline block (BASELINE.md section 1 methodology)")
-    ap.add_argument("--quick", action="store_true", help="= --no-pmc --no-extra --no-cpu-baseline --no-pipeline (kernel A/B runs)")
+    ap.add_argument("--quick", action="store_true", help="with --full: = --no-pmc --no-extra --no-cpu-baseline --no-pipeline (kernel A/B runs)")
     ap.add_argument("--check-steps", type=int, default=64,
                     help="timed steps of every stream replayed through the oracle after the run (0 = off)")
     ap.add_argument("--learning-rate", type=float, default=None,
@@ -1544,6 +1555,9 @@ def main():
         return pmc_child(args)
     if args.quick:
         args.no_pmc = args.no_extra = args.no_cpu_baseline = args.no_pipeline = True
+    if not args.full:                   # a plain run: the headline and nothing else (the module docstring)
+        args.no_parity = args.no_pmc = args.no_dense_leg = args.no_extra = args.no_pipeline = True
+        args.no_cpu_baseline = args.no_scatter = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1601,7 +1615,7 @@ def main():
     assert len(mine) == ns and mine.start == rank * ns, (list(mine), rank, ns, world)
     tr = timed_run(leg, K, W, barrier, prof_every=8 if K >= 64 else 1, age_frames=AGE, export=want_gate,
                    spin=0.0 if args.no_spin_up else 0.35, spin_args=(args.workload, local_rank, rank),
-                   reduce_max=reduce_max, isolated=True, exact=True)
+                   reduce_max=reduce_max, isolated=args.full, exact=True)
     positions, prof, models, handover, aged = tr["positions"], tr["prof"], tr["models"], tr["handover"], tr["aged"]
     n_found_local = tr["found"]
     if args.dump_outputs:
@@ -1613,7 +1627,7 @@ def main():
     # the kernel's own traffic count and the model's mode histogram, continuing this run's model
     aud = hist = None
     hbm_read = hbm_copy = None
-    if rank == 0 and args.input == "device":
+    if rank == 0 and args.input == "device" and args.full:
         try:
             aud = audit(leg)
             hist = mode_histogram(leg)
@@ -1632,7 +1646,7 @@ def main():
     k1_wg_benched, early_benched = leg.hp.last_step_shape()
     early_timeouts = leg.hp.early_blob_timeouts()
     one_lat = None
-    if rank == 0 and args.input == "device":
+    if rank == 0 and args.input == "device" and args.full:
         try:
             one_lat = single_frame_latency(leg, 300)
         except Exception as e:
@@ -1746,7 +1760,8 @@ def main():
     px_per_launch = rows * cols * ns
     mog_ms, mog_ms_raw = k1_ms(prof)
     fpl = prof["mog_frames"] / max(prof["steps"], 1)          # frames a launch of the per-pixel kernel covered (1..2)
-    pool_host0 = [leg.pool[leg.pool_index(i)][0].cpu().numpy() for i in range(8)]
+    want_cpu = solo and not args.no_cpu_baseline         # (rank 0 at N = 1 only: the other ranks would idle meanwhile)
+    pool_host0 = [leg.pool[leg.pool_index(i)][0].cpu().numpy() for i in range(8)] if want_cpu else None
     benched = dict(workload=args.workload + (" --dense-model" if args.dense_model else ""), avg_launch_ms=mog_ms,
                    avg_launch_ms_raw_events=mog_ms_raw, empty_event_pair_ms=prof["event_pair_ms"],
                    px_per_launch=px_per_launch, frames_per_launch=fpl, k_mog_fused_ms_per_frame=mog_ms / fpl,
@@ -1932,7 +1947,8 @@ def main():
         roofline["value_dense_fps"] = 1e3 / dense["ms_per_step"] if dense.get("ms_per_step") else None
     else:
         roofline.update(leg=None, achieved=None, frac=None, traffic=None,
-                        note="dense leg not run (N > 1, --no-dense-leg or host input): no defensible fraction on this line")
+                        note="dense leg not run (a plain run, N > 1, --no-dense-leg or host input): no defensible fraction "
+                             "on this line")
     if pmc and pmc.get("benched"):
         b = pmc["benched"]["bytes_per_launch"]
         benched.update(traffic=b, moved_bytes_per_px=b / px_per_launch, moved_bytes_per_px_frame=b / px_per_launch / fpl,
@@ -2048,6 +2064,7 @@ def main():
         "parity_detail": parity_detail,
         "input": args.input,
         "dense_model": bool(args.dense_model),
+        "full_run": bool(args.full),
     }
 
     if solo and not args.no_extra and args.input == "device" and not args.dense_model:
@@ -2063,7 +2080,7 @@ def main():
             log(f"pipeline block: {time.perf_counter() - t0:.1f} s")
         except Exception as e:
             log("pipeline block failed:", e)
-    if not args.no_cpu_baseline and solo:          # rank 0 at N = 1 only (the other ranks would idle meanwhile)
+    if want_cpu:
         line["cpu_baseline"] = cpu_baseline(args.workload, pool_host0)
     else:
         line["cpu_baseline"] = None

@@ -5,6 +5,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -295,6 +296,13 @@ def test_dump_outputs_writes_the_last_steps_records_as_float64(tmp_path):
     assert np.load(tmp_path / "out" / "position_valid.npy").tolist() == [1.0, 1.0]
 
 
+def test_the_line_says_whether_the_run_was_full():
+    full = _full()
+    for v in (False, True):
+        full["full_run"] = v
+        assert bench.slim_line(full)["full_run"] is v
+
+
 def test_steps_must_be_positive():
     r = _run(["--steps", "0"])
     assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
@@ -306,7 +314,7 @@ def test_dump_outputs_are_the_same_in_two_runs_with_the_same_arguments(tmp_path)
     the same records for the last of them (seeded inputs, a fixed number of steps ahead of it)."""
     import numpy as np
     from oat_amd import ffi
-    args = ["--gpus", "1", "--workload", "vga1", "--steps", "30", "--warmup", "4", "--age", "100", "--quick", "--no-dense-leg",
+    args = ["--gpus", "1", "--workload", "vga1", "--steps", "30", "--warmup", "4", "--age", "100", "--full", "--quick", "--no-dense-leg",
             "--check-steps", "8", "--detail-out", str(tmp_path / "d.json")]
     got = []
     for k in range(2):
@@ -321,3 +329,36 @@ def test_dump_outputs_are_the_same_in_two_runs_with_the_same_arguments(tmp_path)
     assert sorted(got[0]) == sorted(f"position_{f}.npy" for f, _ in ffi.Position._fields_) == sorted(got[1])
     for n, a in got[0].items():
         assert a.dtype == np.float64 and a.shape == (1,) and np.array_equal(a, got[1][n]), n
+
+
+@pytest.mark.gpu
+def test_a_plain_run_is_the_headline_alone_and_hands_over_what_a_full_run_does(tmp_path):
+    """Without --full the run sets up, warms up, times exactly --steps steps, writes --dump-outputs and prints the line: no
+    gate, probe or other leg runs.  The records of its last timed step are those a --full run with the same arguments, gated
+    against the oracle, hands over."""
+    import numpy as np
+    base = ["--gpus", "1", "--workload", "vga1", "--steps", "30", "--warmup", "4", "--age", "100"]
+    runs = {}
+    for kind, more in (("plain", []), ("full", ["--full", "--quick", "--no-dense-leg", "--check-steps", "8"])):
+        out, det = tmp_path / kind, tmp_path / f"{kind}.json"
+        t0 = time.perf_counter()
+        r = _run(base + more + ["--dump-outputs", str(out), "--detail-out", str(det)])
+        wall = time.perf_counter() - t0
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        with open(det) as f:
+            d = json.load(f)
+        runs[kind] = dict(line=j, detail=d, wall=wall, outputs={n: np.load(out / n) for n in sorted(os.listdir(out))})
+    j, d = runs["plain"]["line"], runs["plain"]["detail"]
+    assert j["steps"] == 30 and j["warmup"] == 4 and j["ms_per_step"] > 0 and j["full_run"] is False
+    assert j["value"] == pytest.approx(30 / (j["ms_per_step"] * 30 / 1e3), rel=1e-5)
+    assert d["timing"]["steps_timed"] == 30 and d["timing"]["isolated_block_ms"] is None
+    assert j["parity"] == "skipped" and j["cpu_baseline"] is None and j["pipeline"] is None and j["extra_workloads"] is None
+    assert j["roofline"]["frac"] is None and d["roofline"]["pmc"] is None and "audit" not in d["roofline"]["benched_workload"]
+    assert j["latency_us"]["single_p50"] is None and j["value_one_frame_a_launch"] is None
+    assert runs["plain"]["wall"] < 60, runs["plain"]["wall"]
+    jf = runs["full"]["line"]
+    assert jf["parity"] == "ok" and jf["full_run"] is True and jf["latency_us"]["single_p50"] is not None
+    assert sorted(runs["full"]["outputs"]) == sorted(runs["plain"]["outputs"])
+    for n, a in runs["full"]["outputs"].items():
+        assert np.array_equal(a, runs["plain"]["outputs"][n]), n

@@ -40,13 +40,13 @@ def _free_port():
 
 
 def test_bench_two_ranks_over_gloo_share_one_gpu():
-    """`torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 --backend gloo`: both ranks run the hot path on
+    """`torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 --backend gloo --full`: both ranks run the hot path on
     the one GPU, barriers and max-over-ranks timing work, rank 0 alone prints one line whose value counts BOTH
     ranks' streams, and every position of both ranks was found."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = lambda port: [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                        "--workload", "vga1", "--steps", "60", "--warmup", "10", "--check-steps", "8", "--scatter-steps", "24"]
+                        "--workload", "vga1", "--steps", "60", "--warmup", "10", "--check-steps", "8", "--scatter-steps", "24", "--full"]
     r = _launch(cmd, env, 600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -75,7 +75,7 @@ def test_bench_gpus_2_as_a_plain_process_starts_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = lambda port: [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", "vga1",
-                        "--steps", "40", "--warmup", "10", "--check-steps", "4", "--scatter-steps", "16"]
+                        "--steps", "40", "--warmup", "10", "--check-steps", "4", "--scatter-steps", "16", "--full"]
     r = _launch(cmd, env, 600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -86,6 +86,25 @@ def test_bench_gpus_2_as_a_plain_process_starts_two_ranks():
     assert j["fps_per_gpu"] * 2 == pytest.approx(j["value"], rel=1e-4)
 
 
+def test_bench_gpus_2_without_full_times_both_ranks_and_runs_nothing_else():
+    """`python3 bench.py --gpus 2` without --full: both ranks time their shard, rank 0 prints one line whose value counts both
+    ranks' streams, and no gate, second workload or scatter leg runs."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
+    cmd = lambda port: [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", "vga1",
+                        "--steps", "40", "--warmup", "10"]
+    r = _launch(cmd, env, 600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and len(lines[0]) <= 4096, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["n_gpus"] == 2 and j["steps"] == 40 and j["full_run"] is False and j["parity"] == "skipped"
+    assert abs(j["value"] - 2 * 40 / (j["ms_per_step"] * 40 / 1e3)) < 1e-5 * j["value"]
+    assert j["positions_expected"] == 80 and j["positions_found"] >= 0.95 * 80
+    assert j["scatter_ingest"] is None and j["extra_workloads"] is None and j["cpu_baseline"] is None
+    assert [q[:5] for q in j["partition"]["ranks"]] == [[0, 0, 0, 1, "skipped"], [1, 0, 1, 2, "skipped"]]
+
+
 # Ranks of the multi-rank runs that share the one GPU: with the test process (it opens the device first) and the launcher
 # in front of the ranks, no more than six processes have the device open at once.
 RANKS = 3
@@ -94,7 +113,7 @@ RANKS = 3
 @pytest.mark.parametrize("workload,per_rank", [("1080p8", 8), ("4k1", 1)])
 def test_bench_three_ranks_on_one_gpu_run_configs_3_and_4(workload, per_rank):
     """BASELINE configs[3] (8 x 1080p a rank) and configs[4] (one 4K stream a rank) in their multi-rank form on the one GPU
-    there is: `torch.distributed.run --nproc-per-node 3 bench.py --gpus 3 --backend gloo`.  Three
+    there is: `torch.distributed.run --nproc-per-node 3 bench.py --gpus 3 --backend gloo --full`.  Three
     processes, three contexts on device 0.  Asserted: SURVEY 8e's partition (rank r owns global streams r*per .. r*per +
     per - 1), BOTH parity gates green on EVERY rank for every stream of its shard, one JSON line from rank 0 whose value
     counts all ranks' streams, the N = 1-only legs absent.  What this cannot show is scaling over xGMI: that stays
@@ -105,7 +124,7 @@ def test_bench_three_ranks_on_one_gpu_run_configs_3_and_4(workload, per_rank):
     cmd = lambda port: [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(N), "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(N), "--backend", "gloo",
                         "--workload", workload, "--steps", str(K), "--warmup", "5", "--age", "40", "--pool", "8", "--check-steps", "4",
-                        "--no-spin-up", "--scatter-steps", "12", "--no-extra"]
+                        "--no-spin-up", "--scatter-steps", "12", "--no-extra", "--full"]
     r = _launch(cmd, env, 900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -130,9 +149,9 @@ def test_bench_three_ranks_on_one_gpu_run_configs_3_and_4(workload, per_rank):
 
 
 def test_the_drivers_multi_gpu_command_at_three_ranks_yields_the_whole_record_on_one_gpu():
-    """`python3 bench.py --gpus 3 --steps 20 --warmup 5` -- the driver's argv for its one-shot SCALE run (there with --gpus 8),
-    plus `--backend gloo` so that the ranks can share the one GPU there is here.  ONE invocation, no
-    launcher in front, default ageing / pool / gates: one line <= 4 KB with n_gpus 3 that carries BOTH north-star sizes at N GPUs -- `value` on
+    """`python3 bench.py --gpus 3 --steps 20 --warmup 5 --full` -- the driver's argv for its one-shot SCALE run (there with
+    --gpus 8) with everything beyond the headline, plus `--backend gloo` so that the ranks can share the one GPU there is
+    (VERDICT r05 next-1).  ONE invocation, no launcher in front, default ageing / pool / gates: one line <= 4 KB with n_gpus 3 that carries BOTH north-star sizes at N GPUs -- `value` on
     configs[4]'s shard (one 4K stream a rank) and `extra_workloads.1080p8` on configs[3]'s (8 x 1080p a rank), both parity
     gates green on every rank for both --, the benched per-pixel launch as a fraction of the HBM peak from the slowest
     rank's HIP events (no profiler child at N > 1), the per-rank kernel times, and the stream->rank scatter for both sizes."""
@@ -140,7 +159,8 @@ def test_the_drivers_multi_gpu_command_at_three_ranks_yields_the_whole_record_on
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     N = RANKS
-    cmd = lambda port: [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(N), "--steps", "20", "--warmup", "5", "--backend", "gloo"]
+    cmd = lambda port: [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(N), "--steps", "20", "--warmup", "5", "--backend", "gloo",
+                        "--full"]
     t0 = time.perf_counter()
     r = _launch(cmd, env, 900)
     wall = time.perf_counter() - t0

@@ -5,7 +5,7 @@ export OATGPU_MEASURE_PY=1 OATGPU_LIB=$R/build/variants/liboatgpu_meas.so
 for n in $ns; do
   export OATGPU_A_RESERVE=$n
   for set in "--workload 4k1 --steps 1000" "--workload 1080p16 --steps 200 --warmup 40" "--workload 1080p1 --steps 1500"; do
-    python bench.py $set --quick --check-steps 16 --detail-out $out/r${n}.json > $out/r${n}.line 2> $out/r${n}.log
+    python bench.py $set --full --quick --check-steps 16 --detail-out $out/r${n}.json > $out/r${n}.line 2> $out/r${n}.log
     python - $out/r${n}.json "reserve $n" "$set" <<'PY'
 import json, sys
 try:
