@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define OATGPU_ABI_VERSION 9     /* 2: oatgpu_position grew (filter outputs), new entry points; 3: oatgpu_config.mog_restore_nmodes; 4: oatgpu_cvt_color, oatgpu_set_fusion, oatgpu_set_homography, oatgpu_profile.mog_frames; 5: oatgpu_track_sequence_dev_timed, oatgpu_track_enqueue_dev pairs frames only after oatgpu_set_fusion(2); 6: oatgpu_track_input_consumed_stream, oatgpu_track_stage, oatgpu_track_enqueue_staged; 7: oatgpu_track_stage_abort, oatgpu_set_early_blob, oatgpu_set_stage_copy, oatgpu_set_deferred / _fetch_frame / _fetch_position, a failed pipelined launch is fatal for its context; 8: oatgpu_track_sequence_dev_latency, oatgpu_device_open_retries, oatgpu_set_k1_workgroup, oatgpu_last_step_shape, oatgpu_early_blob_timeouts, a parked blob workgroup that times out switches early dispatch off for its context; 9: oatgpu_profile.dropped, every scratch set is allocated by oatgpu_create (an out-of-memory is reported there, never in the middle of a step); additive entries of 9 (detect them by symbol): oatgpu_undistort_map, oatgpu_set_undistort, oatgpu_undistort_filter, oatgpu_undistort_dev */
+#define OATGPU_ABI_VERSION 9     /* 2: oatgpu_position grew (filter outputs), new entry points; 3: oatgpu_config.mog_restore_nmodes; 4: oatgpu_cvt_color, oatgpu_set_fusion, oatgpu_set_homography, oatgpu_profile.mog_frames; 5: oatgpu_track_sequence_dev_timed, oatgpu_track_enqueue_dev pairs frames only after oatgpu_set_fusion(2); 6: oatgpu_track_input_consumed_stream, oatgpu_track_stage, oatgpu_track_enqueue_staged; 7: oatgpu_track_stage_abort, oatgpu_set_early_blob, oatgpu_set_stage_copy, oatgpu_set_deferred / _fetch_frame / _fetch_position, a failed pipelined launch is fatal for its context; 8: oatgpu_track_sequence_dev_latency, oatgpu_device_open_retries, oatgpu_set_k1_workgroup, oatgpu_last_step_shape, oatgpu_early_blob_timeouts, a parked blob workgroup that times out switches early dispatch off for its context; 9: oatgpu_profile.dropped, every scratch set is allocated by oatgpu_create (an out-of-memory is reported there, never in the middle of a step); additive entries of 9 (detect them by symbol): oatgpu_undistort_map, oatgpu_set_undistort, oatgpu_undistort_filter, oatgpu_undistort_dev, oatgpu_set_track_undistort */
 
 enum {
     OATGPU_OK = 0,
@@ -290,6 +290,19 @@ int oatgpu_undistort_filter(oatgpu_ctx *ctx, int32_t stream, const uint8_t *in, 
  * on the context's stream; returns once it is queued (oatgpu_synchronize / the stream from oatgpu_get_stream order the
  * caller's work behind it).  Every stream needs a map; out_dev must not overlap frames_dev. */
 int oatgpu_undistort_dev(oatgpu_ctx *ctx, const void *frames_dev, void *out_dev);
+/* framefilt undistort INSIDE the fused tracker (default off).  With on = 1 every fused track call (oatgpu_track_batch,
+ * _batch_dev, _enqueue, _enqueue_dev, _stage / _enqueue_staged, _sequence_dev and its _timed / _latency forms) remaps each
+ * stream's frame with that stream's map (oatgpu_set_undistort) before anything else: the chain is undistort -> ROI mask
+ * (so the mask is defined on the UNDISTORTED image) -> MOG2 -> colour -> detector -> position filter -> homography.  One
+ * remap launch a step covers every stream and both frames of a two-frame step; the per-pixel kernel then reads the
+ * context's undistorted copy.  on = 1 fails (OATGPU_E_INVALID, naming the stream) if any stream has no map; while it is on,
+ * oatgpu_set_undistort(s, ..., n_dist = 0) is refused, a recalibration is allowed (it drains outstanding work and takes
+ * effect from the next frame).  The call drains outstanding work; on = 1 allocates two undistorted-frame buffers of
+ * n_streams*rows*cols*channels bytes each the first time (an out-of-memory is reported here, never in the middle of a
+ * step).  With it off nothing changes, maps or none; the stage-by-stage calls never look at it.  oatgpu_track_input_consumed
+ * keeps its rule for device frames: it returns once the step's per-pixel kernel has finished, which runs behind the remap
+ * that read the caller's frame. */
+int oatgpu_set_track_undistort(oatgpu_ctx *ctx, int32_t on);
 
 /* Deferred completion of the stage-by-stage operators below (default off).  With on = 1 a frame filter (oatgpu_mog_filter,
  * _bsub_filter, _mask_filter, _thresh_filter, _undistort_filter, _bgr2hsv, _cvt_color) or a detector (oatgpu_detect_hsv / _thresh / _diff)
@@ -396,7 +409,8 @@ int oatgpu_track_stage_abort(oatgpu_ctx *ctx);
 /* oatgpu_track_input_consumed blocks until every frame handed over so far has been read out of the caller's
  * buffers -- host frames (oatgpu_track_enqueue): their H2D copies are done; device frames
  * (oatgpu_track_enqueue_dev): the per-pixel kernel that reads them has finished (a frame that was only
- * registered, oatgpu_set_fusion(2), is launched first).  From then on the caller may release or overwrite
+ * registered, oatgpu_set_fusion(2), is launched first; with oatgpu_set_track_undistort(1) the same point: the remap that
+ * reads the caller's frame runs before that kernel on the same stream, so "consumed" is never earlier than without it).  From then on the caller may release or overwrite
  * them, i.e. post() the shared-memory SOURCEs while the device is still computing (the reference releases
  * its source right after its memcpy, FrameFilter.cpp:73-80 / PositionDetector.cpp:78-86).
  * oatgpu_track_ready: 1 if oatgpu_track_collect would return without blocking, 0 if the oldest outstanding

@@ -344,15 +344,37 @@ def _merge(position, p):
 
 
 class HotPath(_Context):
-    """The fused chain for N camera streams: mog + setTo + BGR2HSV + inRange + erode + dilate + blob."""
+    """The fused chain for N camera streams: mog + setTo + BGR2HSV + inRange + erode + dilate + blob.
+
+    undistort: `framefilt undistort` in front of the chain (oatgpu_set_track_undistort) -- one (camera_matrix,
+    distortion_coeffs) tuple for every stream, or a list of n_streams such tuples (one calibration per camera)."""
 
     def __init__(self, rows, cols, n_streams=1, adaptation_coeff=0.0, h_thresh=(0, 256), s_thresh=(0, 256),
-                 v_thresh=(0, 256), erode=0, dilate=10, area=(0.0, DBL_MAX), **kw):
+                 v_thresh=(0, 256), erode=0, dilate=10, area=(0.0, DBL_MAX), undistort=None, **kw):
         super().__init__(rows, cols, n_streams=n_streams, h_lo=h_thresh[0], h_hi=h_thresh[1], s_lo=s_thresh[0],
                          s_hi=s_thresh[1], v_lo=v_thresh[0], v_hi=v_thresh[1], erode=erode, dilate=dilate,
                          min_area=area[0], max_area=area[1], **kw)
         self.learning_coeff_ = float(adaptation_coeff)
         self._pos = (ffi.Position * n_streams)()
+        if undistort is not None:
+            cals = undistort if isinstance(undistort, list) else [undistort] * n_streams
+            if len(cals) != n_streams:
+                raise ValueError(f"undistort: {len(cals)} calibrations for {n_streams} streams (give one, or one a stream)")
+            for st, (K, D) in enumerate(cals):
+                self.set_undistort(st, K, D)
+            self.undistort(True)
+
+    def set_undistort(self, stream, camera_matrix, distortion_coeffs):
+        """The undistortion map of one camera stream (oatgpu_set_undistort): camera_matrix 9 values, distortion_coeffs
+        5 or 8.  Allowed while undistort() is on (a recalibration: it takes effect from the next frame)."""
+        K, D = _calibration(camera_matrix, distortion_coeffs)
+        self._chk(self.lib.oatgpu_set_undistort(self.ctx, int(stream), K.ctypes.data_as(C.POINTER(C.c_double)),
+                                                D.ctypes.data_as(C.POINTER(C.c_double)), D.size))
+
+    def undistort(self, on=True):
+        """oatgpu_set_track_undistort: every track call remaps each stream's frame with its map before the ROI mask and
+        MOG2.  Every stream needs a map (set_undistort) to switch it on."""
+        self._chk(self.lib.oatgpu_set_track_undistort(self.ctx, 1 if on else 0))
 
     def _out(self):
         return [Position2D.from_c(p) for p in self._pos]

@@ -146,20 +146,14 @@ __device__ __forceinline__ void remap_px(const uint8_t *__restrict__ src, int H,
         out[c] = (s00[c] * w00 + s01[c] * w01 + s10[c] * w10 + s11[c] * w11 + 512u) >> 10;
 }
 
-// grid: x = lanes of kPx pixels over one frame, y = stream of the launch
+// kPx output pixels of one frame from its stream's map planes, starting at raster position p0 (< H*W)
 template <int CH>
-__global__ __launch_bounds__(kUndistortWG) void k_undistort(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
-                                                            const uint32_t *__restrict__ map1, const uint16_t *__restrict__ map2,
-                                                            size_t map_stride, int H, int W)
+__device__ __forceinline__ void remap_lane(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
+                                           const uint32_t *__restrict__ map1, const uint16_t *__restrict__ map2, size_t p0,
+                                           size_t npx, int H, int W)
 {
-    const size_t npx = (size_t)H * W;
-    const size_t p0 = ((size_t)blockIdx.x * kUndistortWG + threadIdx.x) * kPx;
-    if (p0 >= npx) return;
-    const int s = blockIdx.y;
-    const uint8_t *src = in + (size_t)s * npx * CH;
-    uint8_t *dst = out + (size_t)s * npx * CH;
-    const uint4 m1 = *(const uint4 *)(map1 + (size_t)s * map_stride + p0);
-    const uint2 m2p = *(const uint2 *)(map2 + (size_t)s * map_stride + p0);
+    const uint4 m1 = *(const uint4 *)(map1 + p0);
+    const uint2 m2p = *(const uint2 *)(map2 + p0);
     const uint32_t m1v[kPx] = {m1.x, m1.y, m1.z, m1.w};
     const uint32_t m2v[kPx] = {m2p.x & 0xffffu, m2p.x >> 16, m2p.y & 0xffffu, m2p.y >> 16};
     uint32_t v[kPx][CH];
@@ -184,6 +178,39 @@ __global__ __launch_bounds__(kUndistortWG) void k_undistort(const uint8_t *__res
     }
 }
 
+// grid: x = lanes of kPx pixels over one frame, y = stream of the launch
+template <int CH>
+__global__ __launch_bounds__(kUndistortWG) void k_undistort(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                            const uint32_t *__restrict__ map1, const uint16_t *__restrict__ map2,
+                                                            size_t map_stride, int H, int W)
+{
+    const size_t npx = (size_t)H * W;
+    const size_t p0 = ((size_t)blockIdx.x * kUndistortWG + threadIdx.x) * kPx;
+    if (p0 >= npx) return;
+    const int s = blockIdx.y;
+    remap_lane<CH>(in + (size_t)s * npx * CH, out + (size_t)s * npx * CH, map1 + (size_t)s * map_stride,
+                   map2 + (size_t)s * map_stride, p0, npx, H, W);
+}
+
+// The fused tracker's form (oatgpu_set_track_undistort): grid x = lanes of kPx pixels over one frame, y = stream (its map),
+// z = frame of the step, each frame with input and output planes of its own (stream-major sets of n_streams frames).
+struct UndistortFrames { const uint8_t *in[2]; uint8_t *out[2]; };
+
+template <int CH>
+__global__ __launch_bounds__(kUndistortWG) void k_undistort_frames(UndistortFrames f, const uint32_t *__restrict__ map1,
+                                                                   const uint16_t *__restrict__ map2, size_t map_stride, int H,
+                                                                   int W)
+{
+    const size_t npx = (size_t)H * W;
+    const size_t p0 = ((size_t)blockIdx.x * kUndistortWG + threadIdx.x) * kPx;
+    if (p0 >= npx) return;
+    const int s = blockIdx.y;
+    const uint8_t *in = blockIdx.z ? f.in[1] : f.in[0];
+    uint8_t *out = blockIdx.z ? f.out[1] : f.out[0];
+    remap_lane<CH>(in + (size_t)s * npx * CH, out + (size_t)s * npx * CH, map1 + (size_t)s * map_stride,
+                   map2 + (size_t)s * map_stride, p0, npx, H, W);
+}
+
 size_t undistort_map_stride(int H, int W) { return ((size_t)H * W + kMapAlign - 1) / kMapAlign * kMapAlign; }
 
 void launch_undistort(const uint8_t *in, uint8_t *out, const uint32_t *map1, const uint16_t *map2, size_t map_stride, int H,
@@ -195,6 +222,22 @@ void launch_undistort(const uint8_t *in, uint8_t *out, const uint32_t *map1, con
         hipLaunchKernelGGL(k_undistort<3>, grid, dim3(kUndistortWG), 0, st, in, out, map1, map2, map_stride, H, W);
     else
         hipLaunchKernelGGL(k_undistort<1>, grid, dim3(kUndistortWG), 0, st, in, out, map1, map2, map_stride, H, W);
+}
+
+void launch_undistort_frames(const uint8_t *const *in, uint8_t *const *out, int n_frames, const uint32_t *map1,
+                             const uint16_t *map2, size_t map_stride, int H, int W, int channels, int n_streams, hipStream_t st)
+{
+    const size_t npx = (size_t)H * W, lanes = (npx + kPx - 1) / kPx;
+    UndistortFrames f{};
+    for (int i = 0; i < 2; ++i) {
+        f.in[i] = in[i < n_frames ? i : 0];
+        f.out[i] = out[i < n_frames ? i : 0];
+    }
+    const dim3 grid((unsigned)((lanes + kUndistortWG - 1) / kUndistortWG), (unsigned)n_streams, (unsigned)n_frames);
+    if (channels == 3)
+        hipLaunchKernelGGL(k_undistort_frames<3>, grid, dim3(kUndistortWG), 0, st, f, map1, map2, map_stride, H, W);
+    else
+        hipLaunchKernelGGL(k_undistort_frames<1>, grid, dim3(kUndistortWG), 0, st, f, map1, map2, map_stride, H, W);
 }
 
 }  // namespace oatgpu

@@ -169,6 +169,9 @@ struct oatgpu_ctx {
     uint16_t *ud_map2 = nullptr;   //   allocated on first oatgpu_set_undistort (kernels_undistort.hip)
     size_t ud_stride = 0;
     std::vector<char> ud_have;     // per camera stream: has a map
+    bool ud_track = false;         // oatgpu_set_track_undistort: the fused track calls remap every frame first (launch_front)
+    uint8_t *ud_frames[2] = {};    // [2][n][H*W*ch] the remapped frames of a step (frame i of a two-frame step in buffer i): K1
+                                   //   reads them in place of the caller's; allocated by oatgpu_set_track_undistort(1)
     BlobBuffers bb[kSets]{};          // scratch sets (bb[0].thr holds the ring's threshold buffers), all made with the context
     const u64 *last_morph = nullptr;
     const u64 *last_fin = nullptr;
@@ -379,7 +382,7 @@ struct DevBuf {             // scoped device allocation
 static void free_all(oatgpu_ctx *c)
 {
     if (!c) return;
-    hipFree(c->bsub_bg); hipFree(c->bsub_f); hipFree(c->diff_last); hipFree(c->roi); hipFree(c->ud_map1); hipFree(c->ud_map2); hipFree(c->state); hipFree(c->nmodes); hipFree(c->frames); hipFree(c->aux_a); hipFree(c->aux_b);
+    hipFree(c->bsub_bg); hipFree(c->bsub_f); hipFree(c->diff_last); hipFree(c->roi); hipFree(c->ud_map1); hipFree(c->ud_map2); hipFree(c->ud_frames[0]); hipFree(c->ud_frames[1]); hipFree(c->state); hipFree(c->nmodes); hipFree(c->frames); hipFree(c->aux_a); hipFree(c->aux_b);
     hipFree(c->bb[0].thr);
     hipFree(c->nopark);
     hipFree(c->kal.state);
@@ -1091,7 +1094,12 @@ extern "C" int oatgpu_set_undistort(oatgpu_ctx *c, int32_t s, const double K[9],
 {
     int rc = check_stream_ix(c, s);
     if (rc) return rc;
-    if (n_dist == 0) { c->ud_have[(size_t)s] = 0; return OATGPU_OK; }   // (nothing on the device reads a stream without a map)
+    if (n_dist == 0) {
+        if (c->ud_track)                // (the fused track calls remap every stream: each needs its map while the switch is on)
+            return fail(c, OATGPU_E_INVALID, "stream %d: the map cannot be removed while the tracker undistorts (oatgpu_set_track_undistort)", s);
+        c->ud_have[(size_t)s] = 0;      // (nothing on the device reads a stream without a map)
+        return OATGPU_OK;
+    }
     rc = check_undistort_args(c, K, dist, n_dist);
     if (rc) return rc;
     const Geom &g = c->g;
@@ -1119,6 +1127,30 @@ extern "C" int oatgpu_set_undistort(oatgpu_ctx *c, int32_t s, const double K[9],
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->ud_have[(size_t)s] = 1;
+    return OATGPU_OK;
+}
+
+extern "C" int oatgpu_set_track_undistort(oatgpu_ctx *c, int32_t on)
+{
+    if (!c) return OATGPU_E_INVALID;
+    if (on != 0 && on != 1) return fail(c, OATGPU_E_INVALID, "track undistort must be 0 (off) or 1 (on)");
+    if (on)
+        for (int s = 0; s < c->cfg.n_streams; ++s)
+            if (!c->ud_have[(size_t)s]) return fail(c, OATGPU_E_INVALID, "stream %d has no undistortion map (oatgpu_set_undistort)", s);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const int rc = quiesce(c);          // frames registered or in flight were handed over under the old setting
+    if (rc) return rc;
+    if (on && !c->ud_frames[0]) {       // (allocated here, never in the middle of a step)
+        const size_t sb = (size_t)c->g.H * c->g.W * c->cfg.channels * c->cfg.n_streams;
+        for (int i = 0; i < 2; ++i)
+            if (hipMalloc((void **)&c->ud_frames[i], sb) != hipSuccess) {
+                (void)hipGetLastError();
+                hipFree(c->ud_frames[0]);
+                c->ud_frames[0] = c->ud_frames[1] = nullptr;
+                return fail(c, OATGPU_E_NOMEM, "device allocation of the undistorted-frame buffers (2 x %zu bytes) failed", sb);
+            }
+    }
+    c->ud_track = on != 0;
     return OATGPU_OK;
 }
 
@@ -1589,6 +1621,17 @@ static int launch_front(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, co
     // previous reader finished before that slot's result was collected: nothing to wait for.
     for (int i = 0; i < nj; ++i)
         if (j[i].ready) HIPCHK(c, hipStreamWaitEvent(A, j[i].ready, 0));
+    // framefilt undistort in front of everything (oatgpu_set_track_undistort): every stream's frames of the step in ONE launch
+    // into the context's buffers, which K1 then reads in place of the caller's.  Two buffers are enough: the next step's
+    // remap queues behind this step's K1 on stream A.  (Outside the profile's K1 event pair.)
+    const void *fr[2] = {j[0].frames, nj == 2 ? j[1].frames : nullptr};
+    if (c->ud_track) {
+        const uint8_t *in[2] = {(const uint8_t *)j[0].frames, (const uint8_t *)fr[1]};
+        launch_undistort_frames(in, c->ud_frames, nj, c->ud_map1, c->ud_map2, c->ud_stride, c->g.H, c->g.W, c->cfg.channels, n, A);
+        HIPCHK(c, hipGetLastError());
+        fr[0] = c->ud_frames[0];
+        fr[1] = c->ud_frames[1];
+    }
     if (ps) HIPCHK(c, hipEventRecord(ps->e[0], A));
 
     // every camera stream advances one frame per job; launches are batched while the streams share a
@@ -1610,11 +1653,11 @@ static int launch_front(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, co
         while (s1 < n && same(s1, s0)) ++s1;
         const bool pair = nj == 2 && !rates[s0].fresh && !rates[(size_t)n + s0].fresh && !(c->audit_on && c->cfg.channels != 3);
         for (int i = 0; i < (pair ? 1 : nj); ++i) {
-            MogLaunch a = mog_launch_base(c, (const uint8_t *)j[i].frames, rates[(size_t)i * n + s0]);
+            MogLaunch a = mog_launch_base(c, (const uint8_t *)fr[i], rates[(size_t)i * n + s0]);
             a.thr_bits = thr_buf(c, j[i].slot);
             if (pair) {
                 const Rate &r2 = rates[(size_t)n + s0];
-                a.frames2 = (const uint8_t *)j[1].frames;
+                a.frames2 = (const uint8_t *)fr[1];
                 a.thr_bits2 = thr_buf(c, j[1].slot);
                 a.alphaT2 = r2.alphaT; a.alpha12 = r2.alpha1; a.prune2 = r2.prune;
             }

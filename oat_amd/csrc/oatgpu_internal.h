@@ -164,6 +164,10 @@ size_t undistort_map_stride(int H, int W);
 // remap of n_streams consecutive frames (stream-major, H*W*channels bytes each) with map planes map1 / map2 + s * map_stride
 void launch_undistort(const uint8_t *in, uint8_t *out, const uint32_t *map1, const uint16_t *map2, size_t map_stride, int H,
                       int W, int channels, int n_streams, hipStream_t st);
+// the fused tracker's remap of a whole step: n_frames (1 or 2) sets of n_streams frames, set i from in[i] into out[i], stream s
+// of every set with map planes map1 / map2 + s * map_stride -- one launch (grid z = frame)
+void launch_undistort_frames(const uint8_t *const *in, uint8_t *const *out, int n_frames, const uint32_t *map1,
+                             const uint16_t *map2, size_t map_stride, int H, int W, int channels, int n_streams, hipStream_t st);
 
 // --- kernels_blob.hip ---
 struct BlobBuffers {

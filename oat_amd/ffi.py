@@ -92,6 +92,7 @@ SIGNATURES = {
     "oatgpu_set_undistort": (C.c_int, [_ctx, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32]),
     "oatgpu_undistort_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p]),
     "oatgpu_undistort_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
+    "oatgpu_set_track_undistort": (C.c_int, [_ctx, C.c_int32]),
     "oatgpu_mog_apply": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_mog_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_bgr2hsv": (C.c_int, [_ctx, _u8p, _u8p]),

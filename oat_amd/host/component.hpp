@@ -473,4 +473,27 @@ struct Options {
     }
 };
 
+// `framefilt undistort`'s calibration (Undistorter.cpp:57-81), checked without a device in the reference's order:
+// distortion-coeffs first, then camera-matrix; 6 or 7 coefficients are refused as OpenCV 3.1 would assert on them
+struct UndistortCalibration {
+    double K[9];
+    std::vector<double> dist;
+};
+inline UndistortCalibration read_undistort_calibration(const Options &o)
+{
+    UndistortCalibration c{};
+    if (!o.arr("distortion-coeffs", c.dist))
+        throw std::runtime_error("Required configuration value 'distortion-coeffs' was not specified.");   // TOMLSanitize.h:198
+    if (c.dist.size() < 5 || c.dist.size() > 8) throw std::runtime_error("Distortion coefficients consist of 5 to 8 values.");
+    std::vector<double> K;
+    if (!o.arr("camera-matrix", K)) throw std::runtime_error("Required configuration value 'camera-matrix' was not specified.");
+    if (K.size() != 9) throw std::runtime_error("'camera-matrix' must be a TOML vector containing 9 elements.");   // TOMLSanitize.h:338-341
+    std::copy(K.begin(), K.end(), c.K);
+    int16_t m1[2];
+    uint16_t m2[1];
+    if (oatgpu_undistort_map(1, 1, c.K, c.dist.data(), (int32_t)c.dist.size(), m1, m2) != OATGPU_OK)
+        throw std::runtime_error(oatgpu_last_error(nullptr));      // 6 or 7 coefficients: OpenCV 3.1 would assert (the library says why)
+    return c;
+}
+
 }  // namespace oat

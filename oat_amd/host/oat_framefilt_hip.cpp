@@ -299,18 +299,9 @@ int main(int argc, char **argv)
         } else if (type == "undistort") {
             // Undistorter.cpp:57-81, checked here, before any device is opened: distortion-coeffs first, then camera-matrix
             auto f = std::make_unique<Undistorter>(o.positional[1], o.positional[2]);
-            if (!o.arr("distortion-coeffs", f->dist_coeff_))
-                throw std::runtime_error("Required configuration value 'distortion-coeffs' was not specified.");   // TOMLSanitize.h:198
-            if (f->dist_coeff_.size() < 5 || f->dist_coeff_.size() > 8)
-                throw std::runtime_error("Distortion coefficients consist of 5 to 8 values.");
-            std::vector<double> K;
-            if (!o.arr("camera-matrix", K)) throw std::runtime_error("Required configuration value 'camera-matrix' was not specified.");
-            if (K.size() != 9) throw std::runtime_error("'camera-matrix' must be a TOML vector containing 9 elements.");   // TOMLSanitize.h:338-341
-            std::copy(K.begin(), K.end(), f->camera_matrix_);
-            int16_t m1[2];
-            uint16_t m2[1];
-            if (oatgpu_undistort_map(1, 1, f->camera_matrix_, f->dist_coeff_.data(), (int32_t)f->dist_coeff_.size(), m1, m2) != OATGPU_OK)
-                throw std::runtime_error(oatgpu_last_error(nullptr));      // 6 or 7 coefficients: OpenCV 3.1 would assert (the library says why)
+            const UndistortCalibration cal = read_undistort_calibration(o);
+            std::copy(cal.K, cal.K + 9, f->camera_matrix_);
+            f->dist_coeff_ = cal.dist;
             f->gpu_index_ = gpu_index;
             comp = std::move(f);
         } else {

@@ -32,6 +32,10 @@
 // scatter") -- one process, one thread, the same partition.  Without it every shard ingests its own cameras (the realistic
 // camera topology).
 //
+// --camera-matrix / --distortion-coeffs (one calibration for every camera) or --undistort-key T0[,T1,...] (tables of the -c
+// file, one for every camera or one per camera) put `framefilt undistort` in front of the chain, inside the same context
+// (oatgpu_set_track_undistort): undistort -> mask -> mog -> col -> detector, the ROI mask on the undistorted image.
+//
 // --thresh [lo,hi] selects the GREY chain instead:  framefilt mog -> posidet thresh  on SOURCEs that carry GREY
 // frames (a mono camera or `framefilt col -C GREY`; SimpleThreshold.cpp:46 requires them), the one-channel model
 // and the intensity window of SimpleThreshold.cpp:171-174 in the same fused launches.
@@ -113,6 +117,7 @@ public:
     bool timing_{false};            // --timing: where the loop's wall clock goes, printed at exit (stderr)
     bool homography_on_{false};     // --homography: `posifilt homography` behind the detector / the position filter
     double homography_[9]{1, 0, 0, 0, 1, 0, 0, 0, 1};
+    std::vector<UndistortCalibration> undistort_;   // one per camera of this shard: `framefilt undistort` fused in front (empty: off)
     ~BatchedTracker() override
     {
         if (!model_file_.empty() && gpu_.ctx)
@@ -175,6 +180,11 @@ protected:
         cfg_.channels = grey_ ? 1 : 3;
         if (cfg_.ring_depth < 2) cfg_.ring_depth = 2;
         gpu_.create(cfg_);
+        if (!undistort_.empty()) {
+            for (int s = 0; s < n_; ++s)
+                gpu_.check(oatgpu_set_undistort(gpu_.ctx, s, undistort_[s].K, undistort_[s].dist.data(), (int32_t)undistort_[s].dist.size()));
+            gpu_.check(oatgpu_set_track_undistort(gpu_.ctx, 1));
+        }
         if (!model_file_.empty())
             for (int s = 0; s < n_; ++s)
                 if (access(model_path(s).c_str(), R_OK) == 0) gpu_.check(oatgpu_mog_load(gpu_.ctx, s, model_path(s).c_str()));
@@ -330,6 +340,10 @@ int main(int argc, char **argv)
                          "       [--thresh [lo,hi]]   GREY SOURCEs: framefilt mog -> posidet thresh instead of the HSV chain\n"
                          "       [--homography [h11,h12,...,h33]]   posifilt homography fused in (positions in world units)\n"
                          "       [--kalman [--dt s] [-T|--timeout s] [--sigma-accel a] [-n|--sigma-noise n]]   (posifilt kalman fused in)\n"
+                         "       [--camera-matrix [K11,...,K33] --distortion-coeffs [k1,k2,p1,p2,k3(,k4,k5,k6)] | --undistort-key T0[,T1,..]]\n"
+                         "                            framefilt undistort fused in front of the chain (the mask applies to the undistorted image):\n"
+                         "                            one calibration for every camera, or tables of the -c file holding camera-matrix /\n"
+                         "                            distortion-coeffs, one for every camera or one per SOURCE\n"
                          "N SOURCEs / N SINKs: N cameras batched into one device pass per frame; SOURCE i feeds SINK i.\n"
                          "--gpu-index N0,N1,..: the cameras are split into contiguous blocks, one per listed device (own context and thread).\n"
                          "--ingest-root D0 (with --gpu-index D0,D1,..): all frames are ingested on device D0 and scattered to their devices\n"
@@ -337,9 +351,11 @@ int main(int argc, char **argv)
                          "--print-partition: print which cameras go to which device (both forms) and exit; no device is touched.\n";
             return o.has("help") ? 0 : -1;
         }
+        const char *ud_exclusive = "--camera-matrix / --distortion-coeffs and --undistort-key are mutually exclusive";
+        if ((o.has("camera-matrix") || o.has("distortion-coeffs")) && o.has("undistort-key")) throw std::runtime_error(ud_exclusive);
         o.apply_config({"adaptation-coeff", "h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "model-file",
                         "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "gpu-index", "ring", "mask", "thresh", "homography", "stage-copy", "timing",
-                        "ingest-root", "print-partition"}, {"kalman", "timing", "print-partition"});
+                        "ingest-root", "print-partition", "camera-matrix", "distortion-coeffs", "undistort-key"}, {"kalman", "timing", "print-partition"});
         const std::vector<std::string> sources = split_list(o.positional[0]), sinks = split_list(o.positional[1]);
         if (sources.size() != sinks.size()) throw std::runtime_error("need as many SINKs as SOURCEs");
         // --gpu-index N | N0,N1,...: one shard of the SOURCE list per listed device (contiguous blocks)
@@ -359,6 +375,29 @@ int main(int argc, char **argv)
                           << (o.has("ingest-root") ? (devices[k] == (int)o.num("ingest-root", 0, 0, 1023) ? " root" : " peer") : "") << "\n";
             return 0;
         }
+        // `framefilt undistort` in front of the chain: one calibration per SOURCE, every one checked here, before any device is
+        // opened (Undistorter.cpp:57-81).  --undistort-key names tables of the -c file (the reference's [undistort] table as it
+        // is); the tracker's own table may be one of them, otherwise it may not hold a calibration of its own as well.
+        std::vector<UndistortCalibration> cals;
+        if (o.has("undistort-key")) {
+            const std::vector<std::string> keys = split_list(o.kv["undistort-key"]);
+            if (o.config_file.empty()) throw std::runtime_error("--undistort-key names tables of the configuration file: give -c FILE KEY");
+            if ((o.has("camera-matrix") || o.has("distortion-coeffs")) && std::find(keys.begin(), keys.end(), o.config_key) == keys.end())
+                throw std::runtime_error(ud_exclusive);
+            if (keys.size() != 1 && keys.size() != sources.size())
+                throw std::runtime_error("--undistort-key: " + std::to_string(keys.size()) + " tables for " + std::to_string(sources.size()) +
+                                         " SOURCEs (give one for every camera or one per SOURCE)");
+            for (const std::string &k : keys) {
+                Options t;
+                t.config_file = o.config_file;
+                t.config_key = k;
+                t.apply_config({"camera-matrix", "distortion-coeffs"});     // Undistorter.cpp:43-53
+                cals.push_back(read_undistort_calibration(t));
+            }
+            if (cals.size() == 1) cals.assign(sources.size(), cals[0]);
+        } else if (o.has("camera-matrix") || o.has("distortion-coeffs")) {
+            cals.assign(sources.size(), read_undistort_calibration(o));
+        }
         if (o.has("ingest-root")) {                                       // the stream-to-rank scatter over RCCL (scatter_tracker.hpp)
             for (const char *k : {"kalman", "thresh", "mask", "model-file", "homography", "stage-copy"})
                 if (o.has(k)) throw std::runtime_error(std::string("--ingest-root does not take --") + k);
@@ -373,6 +412,7 @@ int main(int argc, char **argv)
             if (o.arr2("area", a, b)) { t.cfg_.min_area = a; t.cfg_.max_area = b; }
             t.cfg_.ring_depth = (int)o.num("ring", 2, 2, 64);
             t.timing_ = o.has("timing");
+            t.undistort_ = cals;
             return t.run();
         }
         const int S = (int)sources.size(), N = (int)devices.size(), per = (S + N - 1) / N;
@@ -405,6 +445,7 @@ int main(int argc, char **argv)
             t->timing_ = o.has("timing");
             t->kalman_ = o.has("kalman");
             t->homography_on_ = o.arr9("homography", t->homography_);
+            if (!cals.empty()) t->undistort_.assign(cals.begin() + s0, cals.begin() + s1);
             t->dt_ = o.num("dt", 0.02, 0, 1e9);                        // KalmanFilter2D.cpp:69-85 (lower bound 0)
             t->timeout_ = o.num("timeout", 0.0, 0, 1e18);
             t->sig_accel_ = o.num("sigma-accel", 5.0, 0, 1e18);

@@ -85,6 +85,7 @@ public:
     oatgpu_config cfg_;
     double learning_coeff_{0.0};
     bool timing_{false};
+    std::vector<UndistortCalibration> undistort_;   // one per SOURCE: `framefilt undistort` fused in front (empty: off)
 
     void print_timing() const
     {
@@ -158,6 +159,14 @@ protected:
             if (c.ring_depth < 2) c.ring_depth = 2;
             gpu_.push_back(std::make_unique<GpuCtx>());
             gpu_.back()->create(c);
+            if (!undistort_.empty()) {                         // each shard's context gets its own cameras' maps
+                GpuCtx &g = *gpu_.back();
+                for (int i = 0; i < c.n_streams; ++i) {
+                    const UndistortCalibration &u = undistort_[(size_t)block_begin(k) + i];
+                    g.check(oatgpu_set_undistort(g.ctx, i, u.K, u.dist.data(), (int32_t)u.dist.size()));
+                }
+                g.check(oatgpu_set_track_undistort(g.ctx, 1));
+            }
         }
         for (int s = 0; s < S_; ++s) {
             position_sinks_[s].bind(sink_addresses_[s], sink_addresses_[s]);

@@ -5,7 +5,8 @@ perf methodology, test/perf/*.sh: `time` a free-running frame server with the co
     python tools/pipeline_fps.py [--rows 480 --cols 640] [--frames 1000] [--fused] [--cameras N] [--ring D]
 
 --cameras N (with --fused): N free-running frame servers -> ONE batched, pipelined oat-track-hip -> N readers;
-the reported rate is the aggregate over all cameras.
+the reported rate is the aggregate over all cameras.  --camera-matrix K --distortion-coeffs D puts `framefilt undistort`
+in front: inside oat-track-hip (fused), or with --separate-undistort as one oat-framefilt-hip undistort per camera feeding it.
 """
 import argparse
 import os
@@ -46,6 +47,9 @@ def batched(a):
     n = a.cameras
     srcs = [f"{tag}raw{s}" for s in range(n)]
     snks = [f"{tag}pos{s}" for s in range(n)]
+    ud = bool(a.camera_matrix)
+    cal = ["--camera-matrix", a.camera_matrix, "--distortion-coeffs", a.distortion_coeffs] if ud else []
+    tsrcs = [f"{tag}und{s}" for s in range(n)] if ud and a.separate_undistort else srcs
     raws = []
     for s in range(n):
         st = SyntheticStream(a.rows, a.cols, s, n_discs=2)
@@ -57,10 +61,12 @@ def batched(a):
     readers = [subprocess.Popen([B("oat-posi-cout"), x], stdout=o, text=True) for x, o in zip(snks, outs)]
     terr = open(f"/dev/shm/{tag}.trk.err", "w+") if a.timing else None
     tracker = subprocess.Popen((a.tracker_prefix.split() if a.tracker_prefix else []) +
-                               [B("oat-track-hip"), ",".join(srcs), ",".join(snks), "-a", "0.01", "--area", "[20,100000]",
+                               [B("oat-track-hip"), ",".join(tsrcs), ",".join(snks), "-a", "0.01", "--area", "[20,100000]",
                                 "-H", "[100,125]", "-S", "[150,256]", "-V", "[100,256]", "-e", "3", "-d", "7",
-                                "--ring", str(a.ring)] + (["--stage-copy", a.stage_copy] if a.stage_copy else []) + (["--timing"] if a.timing else []) + a.tracker_extra.split(),
-                               stderr=terr)
+                                "--ring", str(a.ring)] + (["--stage-copy", a.stage_copy] if a.stage_copy else []) + (["--timing"] if a.timing else []) + a.tracker_extra.split() +
+                               ([] if a.separate_undistort else cal), stderr=terr)
+    filters = [subprocess.Popen([B("oat-framefilt-hip"), "undistort", srcs[s], tsrcs[s]] + cal)
+               for s in range(n)] if ud and a.separate_undistort else []
     time.sleep(12.0 if a.tracker_prefix else 4.0)
     t0 = time.perf_counter()
     feeders = [subprocess.Popen([B("oat-frameserve-raw"), srcs[s], "-f", raws[s], "--rows", str(a.rows), "--cols",
@@ -78,10 +84,12 @@ def batched(a):
         ok += sum('"pos_ok":true' in l for l in out.splitlines())
     for f in feeders:
         f.wait(timeout=60)
+    for f in filters:
+        f.wait(timeout=60)
     tracker.wait(timeout=60)
     for raw in raws:
         os.unlink(raw)
-    subprocess.run([B("oat-clean-hip")] + srcs + snks, capture_output=True)
+    subprocess.run([B("oat-clean-hip")] + srcs + snks + (tsrcs if filters else []), capture_output=True)
     steady = ""
     if terr:
         terr.seek(0)
@@ -96,7 +104,8 @@ def batched(a):
                     steady = f"; the tracker's own clock, rounds 17..: {m.group(1)} fps aggregate"
             elif l.strip() and "Exiting" not in l:
                 print(l, file=sys.stderr)
-    print(f"batched oat-track-hip, {n} cameras x {a.cols}x{a.rows}, ring {a.ring}: {tokens} tokens in {el:.2f} s = "
+    form = "" if not ud else ", undistort in separate processes" if filters else ", undistort fused"
+    print(f"batched oat-track-hip{form}, {n} cameras x {a.cols}x{a.rows}, ring {a.ring}: {tokens} tokens in {el:.2f} s = "
           f"{tokens / el:.1f} fps aggregate, {tokens / el / n:.1f} per camera ({ok} valid positions){steady}")
 
 
@@ -112,6 +121,10 @@ def main():
     ap.add_argument("--tracker-extra", default="", help="more oat-track-hip options, e.g. '--gpu-index 0 --ingest-root 0' (the RCCL scatter form)")
     ap.add_argument("--timing", action="store_true", help="oat-track-hip --timing: where the tracker's loop spends its wall clock")
     ap.add_argument("--stage-copy", default="", choices=["", "dma", "kernel"], help="oat-track-hip --stage-copy (oatgpu_set_stage_copy)")
+    ap.add_argument("--camera-matrix", default="", help="with --cameras: framefilt undistort in front, K = [K11,...,K33]")
+    ap.add_argument("--distortion-coeffs", default="", help="... and its coefficients [k1,k2,p1,p2,k3(,k4,k5,k6)]")
+    ap.add_argument("--separate-undistort", action="store_true",
+                    help="one oat-framefilt-hip undistort process per camera instead of the tracker's own")
     ap.add_argument("--feeder-node", type=int, default=-1,
                     help="keep the frame servers (and so, by first touch, the shared-memory frames) on the CPUs of this NUMA "
                          "node; -2 = the node GPU 0 hangs off (oatgpu_device_numa_node)")
