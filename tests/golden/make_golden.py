@@ -19,14 +19,18 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 f32 = np.float32
 
 
-def mog2_pixel_trace(pixels, rates, nmix=5, restore=True):
+def mog2_pixel_trace(pixels, rates, nmix=5, restore=True, Tb=16, TB=0.9, Tg=9, var_init=15, var_min=4, var_max=75,
+                     ct=0.05, tau=0.5, detect_shadows=True, shadow_value=127, history=500):
     """One pixel, 3 channels.  pixels: list of (b,g,r); rates: learning rate per frame.
     restore: the mode count is set back to its value at entry after the renormalisation
     (MOG2Invoker's `nmodes = nNewModes;`, see oracle/mog2.c "Mode count"); False = pruning shrinks it.
+    The keywords are BackgroundSubtractorMOG2's parameters (varThreshold, backgroundRatio, varThresholdGen, fVarInit,
+    fVarMin, fVarMax, fCT, fTau, detectShadows, nShadowDetection, history), each rounded to float32 as the class stores
+    it; their defaults are OpenCV's.
     Returns per frame: mask, nmodes, weights, variances, means (python floats of f32)."""
-    Tb, TB, Tg = f32(16), f32(0.9), f32(9)
-    varInit, varMin, varMax, tau = f32(15), f32(4), f32(75), f32(0.5)
-    CT = np.float32(0.05)
+    Tb, TB, Tg = f32(Tb), f32(TB), f32(Tg)
+    varInit, varMin, varMax, tau = f32(var_init), f32(var_min), f32(var_max), f32(tau)
+    CT = np.float32(ct)
     w = [f32(0)] * nmix
     var = [f32(0)] * nmix
     mu = [[f32(0)] * 3 for _ in range(nmix)]
@@ -38,7 +42,7 @@ def mog2_pixel_trace(pixels, rates, nmix=5, restore=True):
             w = [f32(0)] * nmix; var = [f32(0)] * nmix
             mu = [[f32(0)] * 3 for _ in range(nmix)]; nmodes = 0; nframes = 0
         nframes += 1
-        lr = rate if (rate >= 0 and nframes > 1) else 1.0 / min(2 * nframes, 500)
+        lr = rate if (rate >= 0 and nframes > 1) else 1.0 / min(2 * nframes, history)
         alphaT = f32(lr)
         prune = f32(-lr * float(CT))          # product in double, then to float
         alpha1 = f32(1) - alphaT
@@ -114,6 +118,7 @@ def mog2_pixel_trace(pixels, rates, nmix=5, restore=True):
             mask = 0
         else:
             mask = 255
+        if not background and detect_shadows:
             tw = f32(0)
             for m in range(nmodes):
                 num = f32(0); den = f32(0)
@@ -129,7 +134,7 @@ def mog2_pixel_trace(pixels, rates, nmix=5, restore=True):
                         dd = f32(f32(a * mu[m][c]) - x[c])
                         d2 = f32(d2 + f32(dd * dd))
                     if d2 < f32(f32(f32(Tb * var[m]) * a) * a):
-                        mask = 127
+                        mask = int(shadow_value)
                         break
                 tw = f32(tw + w[m])
                 if tw > TB:

@@ -78,19 +78,28 @@ def _model_hash(hp, streams):
     return h.hexdigest()
 
 
-@pytest.mark.parametrize("kind", ["bgr_fused", "bgr_one_frame", "bgr_dense_streaming_loads", "grey_fused", "bgr_audited"])
+@pytest.mark.parametrize("kind", ["bgr_fused", "bgr_one_frame", "bgr_dense_streaming_loads", "grey_fused",
+                                  "grey_dense_streaming_loads", "bgr_audited"])
 def test_whole_model_determinism_4k(A, kind):
-    """Three runs of the same 4K sequence through every instantiation of the per-pixel kernel the product can launch
-    (two frames a launch, one frame a launch, the streaming-load one a dense model switches to, GREY, and the audited
-    one): the whole model must hash the same every time.  A run-to-run difference is how the wide-store hazard showed."""
+    """Three runs of the same 4K sequence, one stream at a learning rate, through six kinds of run of the per-pixel kernel:
+    BGR two frames a launch, BGR one frame a launch, the BGR and the GREY streaming-load kernels a dense model switches
+    to (two frames a launch), GREY two frames a launch, and BGR through the audited kernels.  The whole model must hash
+    the same every time: a run-to-run difference is how the wide-store hazard showed.  (Frozen models, 64-thread plain
+    workgroups and one-frame GREY launches are not run here; tests/test_mog_matrix_gpu.py reaches every instantiation,
+    on small frames.)"""
     import numpy as np
     from oat_amd.synth import SyntheticStream, disc_hsv_window
     rows, cols = 2160, 3840
-    dense = kind == "bgr_dense_streaming_loads"
-    grey = kind == "grey_fused"
+    dense = kind.endswith("_dense_streaming_loads")
+    grey = kind.startswith("grey")
     n = 40 if dense else 14
     rng = np.random.default_rng(7)
-    if dense:
+    if dense and grey:
+        levels = np.array([20, 70, 120, 170, 230], np.int16)             # tests/mog_matrix.py's GREY levels
+        phase = rng.integers(0, 5, (rows, cols))
+        fr = [np.clip(levels[(phase + t) % 5] + rng.integers(-3, 4, (rows, cols), dtype=np.int16), 0, 255).astype(np.uint8)
+              for t in range(5)]
+    elif dense:
         table = np.array([[20, 30, 40], [90, 200, 60], [200, 60, 120], [240, 240, 230], [40, 130, 220]], np.int16)
         phase = rng.integers(0, 5, (rows, cols))
         fr = [np.clip(table[(phase + t) % 5] + rng.integers(-5, 6, (rows, cols, 3), dtype=np.int16), 0, 255).astype(np.uint8)
@@ -123,6 +132,8 @@ def test_whole_model_determinism_4k(A, kind):
         if kind == "bgr_audited":
             assert hp.traffic_read()["launches"] > 0
             hp.traffic_audit(False)
+        if dense:
+            assert hp.last_step_shape()[0] == 64, kind          # the density switch happened: streaming-load launches
         hashes.append(_model_hash(hp, 1))
         hp.close()
     assert hashes[0] == hashes[1] == hashes[2], (kind, hashes)
