@@ -39,6 +39,9 @@ extern "C" {
 #endif
 
 #define OATGPU_ABI_VERSION 9     /* 2: oatgpu_position grew (filter outputs), new entry points; 3: oatgpu_config.mog_restore_nmodes; 4: oatgpu_cvt_color, oatgpu_set_fusion, oatgpu_set_homography, oatgpu_profile.mog_frames; 5: oatgpu_track_sequence_dev_timed, oatgpu_track_enqueue_dev pairs frames only after oatgpu_set_fusion(2); 6: oatgpu_track_input_consumed_stream, oatgpu_track_stage, oatgpu_track_enqueue_staged; 7: oatgpu_track_stage_abort, oatgpu_set_early_blob, oatgpu_set_stage_copy, oatgpu_set_deferred / _fetch_frame / _fetch_position, a failed pipelined launch is fatal for its context; 8: oatgpu_track_sequence_dev_latency, oatgpu_device_open_retries, oatgpu_set_k1_workgroup, oatgpu_last_step_shape, oatgpu_early_blob_timeouts, a parked blob workgroup that times out switches early dispatch off for its context; 9: oatgpu_profile.dropped, every scratch set is allocated by oatgpu_create (an out-of-memory is reported there, never in the middle of a step); additive entries of 9 (detect them by symbol): oatgpu_undistort_map, oatgpu_set_undistort, oatgpu_undistort_filter, oatgpu_undistort_dev, oatgpu_set_track_undistort */
+/* Further additive entries of ABI 9 (detect them by symbol; no existing struct or entry changes): the marker sets --
+ * oatgpu_set_markers, oatgpu_set_marker_window, oatgpu_track_markers_dev, oatgpu_track_markers, oatgpu_read_marker_mask,
+ * with the structs oatgpu_marker and oatgpu_combined. */
 
 enum {
     OATGPU_OK = 0,
@@ -303,6 +306,64 @@ int oatgpu_undistort_dev(oatgpu_ctx *ctx, const void *frames_dev, void *out_dev)
  * keeps its rule for device frames: it returns once the step's per-pixel kernel has finished, which runs behind the remap
  * that read the caller's frame. */
 int oatgpu_set_track_undistort(oatgpu_ctx *ctx, int32_t on);
+
+/* ---- marker sets: several colour windows per camera behind ONE MOG2 pass, `posicom mean` behind them ----
+ *
+ * The canonical rig: an animal wearing two or three coloured LEDs, one `framefilt mog`, one `framefilt col`, ONE `posidet hsv`
+ * PER COLOUR (HSVDetector.cpp:142-173) and `posicom mean --heading-anchor i` behind them
+ * (src/positioncombiner/MeanPosition.cpp:60-118): position = mean of the markers, heading = direction from the anchor marker
+ * to the others.  MOG2 does not depend on the detector, so one model pass serves every marker.
+ *
+ * How: the context's OWN window must be the NON-ZERO window -- H [0,256], S [0,256], V [1,256] (channels == 1: intensity
+ * h_lo/h_hi = [1,256]; erode / dilate / area are free).  Its threshold plane (OATGPU_TAP_THRESHOLD) is then Z = "the pixel
+ * of the frame `framefilt mog` published is non-zero"; a foreground pixel that is pure black is a zero in that frame like any
+ * background pixel, so Z ? px : 0 IS that frame and marker m's mask is inRange_m(hsv(Z ? px : 0)), hsv(0) = (0,0,0) -- a
+ * window that contains (0,0,0) selects the background, as in the reference.  One small kernel makes all M masks from the
+ * frame the per-pixel kernel read and Z; each mask then goes through the ordinary morphology + blob analysis with its
+ * marker's erode / dilate / area; a last kernel combines each camera's M positions.
+ *
+ * oatgpu_marker: one marker's detector.  Windows as oatgpu_set_detector's (0..256, lo > hi = empty; channels == 1: h_lo/h_hi
+ * are the intensity window, s_* / v_* ignored). */
+typedef struct oatgpu_marker {
+    int32_t h_lo, h_hi, s_lo, s_hi, v_lo, v_hi;
+    int32_t erode, dilate;         /* -e / -d of this marker's posidet, 0 = off */
+    double min_area, max_area;     /* -a [min,max)                              */
+} oatgpu_marker;
+/* What `posicom mean` publishes for one camera (oat::Position2D).  MeanPosition::combine is kept as it is: x, y add
+ * (1.0 / M) * position of every VALID marker in marker order, position_valid is 0 as soon as one marker is invalid (x, y are
+ * then the partial sum); with a heading anchor (hx, hy) adds position_m - position_anchor while the running position_valid is
+ * still set (an invalid position is (0, 0)) and heading_valid goes 0 otherwise; the sum is then divided by its length --
+ * NaN for M = 1 or coincident markers, with heading_valid 1, as the reference.  Without an anchor heading_valid = 0
+ * (detectors set no heading); velocity_valid = 0 (no position filter runs on markers).  n_valid: markers found. */
+typedef struct oatgpu_combined {
+    int32_t position_valid, heading_valid, velocity_valid, n_valid;
+    double x, y, hx, hy;
+} oatgpu_combined;
+/* Switches marker sets on with n_markers (1..8) markers, the same defaults[m] for every camera, and allocates everything a
+ * marker step needs (one more back-half scratch set of 30 B a pixel and stream + n_markers / 2 B of bit planes; an
+ * out-of-memory is OATGPU_E_NOMEM from THIS call, never from a step).  heading_anchor: -1 none, else a marker index < n_markers
+ * (`posicom mean --heading-anchor`).  n_markers = 0 frees it all and switches markers off (defaults may be NULL).  Drains
+ * outstanding work.  The ordinary track calls do not look at any of it. */
+int oatgpu_set_markers(oatgpu_ctx *ctx, int32_t n_markers, const oatgpu_marker *defaults, int32_t heading_anchor);
+/* The COLOUR window of one marker for one camera (16 cameras do not have 16 identical lighting conditions): takes m's six
+ * threshold values; erode / dilate / area stay per marker (m's are ignored). */
+int oatgpu_set_marker_window(oatgpu_ctx *ctx, int32_t stream, int32_t marker, const oatgpu_marker *m);
+/* One synchronous step: one frame for EVERY stream (device memory, stream-major, as oatgpu_track_batch_dev), the model
+ * advances by one frame with oatgpu_track_batch_dev's learning_rate rule.  fg[n_streams] (or NULL): what oatgpu_track_batch_dev
+ * returns under the non-zero window -- the largest foreground blob of each camera; markers[s * n_markers + m]: marker m of
+ * camera s (`posidet hsv` number m); mean[n_streams] (or NULL): the combined positions.  With oatgpu_set_track_undistort(1)
+ * and / or a ROI mask the markers see the undistorted, masked frame, as the model does.
+ * OATGPU_E_INVALID -- before anything has moved -- when results are outstanding (oatgpu_track_enqueue*), markers are not
+ * configured, the context's own window is not the non-zero window, or oatgpu_set_kalman / oatgpu_set_homography is on.
+ * Two-frame launches, the result ring and the early blob dispatch do not extend to markers. */
+int oatgpu_track_markers_dev(oatgpu_ctx *ctx, const void *frames_dev, double learning_rate, oatgpu_position *fg,
+                             oatgpu_position *markers, oatgpu_combined *mean);
+/* Same with the frames in host memory: frames_host[i] -> rows*cols*channels bytes of stream i, n == n_streams. */
+int oatgpu_track_markers(oatgpu_ctx *ctx, const uint8_t *const *frames_host, int32_t n, double learning_rate,
+                         oatgpu_position *fg, oatgpu_position *markers, oatgpu_combined *mean);
+/* oatgpu_read_mask for marker m's masks of the latest marker step: which = OATGPU_TAP_THRESHOLD (its inRange output),
+ * _MORPH, _FINAL; rows*cols bytes {0,255}. */
+int oatgpu_read_marker_mask(oatgpu_ctx *ctx, int32_t stream, int32_t marker, int32_t which, uint8_t *out);
 
 /* Deferred completion of the stage-by-stage operators below (default off).  With on = 1 a frame filter (oatgpu_mog_filter,
  * _bsub_filter, _mask_filter, _thresh_filter, _undistort_filter, _bgr2hsv, _cvt_color) or a detector (oatgpu_detect_hsv / _thresh / _diff)

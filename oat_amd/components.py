@@ -47,6 +47,40 @@ class Position2D:
                           bool(p.velocity_valid), p.vx, p.vy, bool(p.raw_valid), p.raw_x, p.raw_y)
 
 
+@dataclass
+class Combined:
+    """What `posicom mean` writes into oat::Position2D (src/positioncombiner/MeanPosition.cpp:60-118): the mean of a camera's
+    markers and, with a heading anchor, the unit vector from the anchor marker to the others."""
+    position_valid: bool = False
+    x: float = 0.0
+    y: float = 0.0
+    heading_valid: bool = False
+    hx: float = 0.0
+    hy: float = 0.0
+    velocity_valid: bool = False   # always False: no position filter runs on markers
+    n_valid: int = 0               # markers found
+
+    @staticmethod
+    def from_c(p):
+        return Combined(bool(p.position_valid), p.x, p.y, bool(p.heading_valid), p.hx, p.hy, bool(p.velocity_valid), p.n_valid)
+
+
+def _marker(m):
+    """dict(h=(lo,hi), s=(lo,hi), v=(lo,hi), erode=K, dilate=K, area=(a,b)) -- every key optional, the defaults are
+    HSVDetector's (all-pass window, erode off, dilate 10, area [0, DBL_MAX)); GREY contexts: h is the intensity window --
+    or an ffi.Marker."""
+    if isinstance(m, ffi.Marker):
+        return m
+    m = dict(m)
+    h, s, v = m.pop("h", (0, 256)), m.pop("s", (0, 256)), m.pop("v", (0, 256))
+    area = m.pop("area", (0.0, DBL_MAX))
+    out = ffi.Marker(int(h[0]), int(h[1]), int(s[0]), int(s[1]), int(v[0]), int(v[1]), int(m.pop("erode", 0)),
+                     int(m.pop("dilate", 10)), float(area[0]), float(area[1]))
+    if m:
+        raise TypeError(f"unknown marker option(s) {sorted(m)}")
+    return out
+
+
 def _frame(a, shape):
     a = np.ascontiguousarray(a, dtype=np.uint8)
     if a.shape != shape:
@@ -405,6 +439,53 @@ class HotPath(_Context):
             self._chk(self.lib.oatgpu_track_sequence_dev(self.ctx, arr, n, self.learning_coeff_, out))
         res = [[Position2D.from_c(out[t * self.n_streams + s]) for s in range(self.n_streams)] for t in range(n)]
         return (res, [done[t] for t in range(n)]) if timed else res
+
+    # -- marker sets: several colour windows per camera behind one model pass, `posicom mean` behind them --------------
+    def set_markers(self, markers, heading_anchor=None):
+        """oatgpu_set_markers: markers = a list of up to 8 marker dicts (see _marker) used for every camera; heading_anchor =
+        index of the marker headings are taken from (`posicom mean --heading-anchor`), None for no heading.  An empty list
+        switches markers off and frees their scratch.  The context's own window must be the non-zero window
+        (h_thresh=(0,256), s_thresh=(0,256), v_thresh=(1,256); GREY: h_thresh=(1,256)) when track_markers is called."""
+        ms = [_marker(m) for m in markers]
+        arr = (ffi.Marker * max(len(ms), 1))(*ms)
+        self._chk(self.lib.oatgpu_set_markers(self.ctx, len(ms), arr if ms else None,
+                                              -1 if heading_anchor is None else int(heading_anchor)))
+        self.n_markers = len(ms)
+        self._mpos = (ffi.Position * max(self.n_streams * len(ms), 1))()
+        self._mean = (ffi.Combined * self.n_streams)()
+
+    def set_marker_window(self, stream, marker, h=(0, 256), s=(0, 256), v=(0, 256)):
+        """oatgpu_set_marker_window: the colour window of one marker for ONE camera; morphology and area stay per marker."""
+        m = _marker(dict(h=h, s=s, v=v))
+        self._chk(self.lib.oatgpu_set_marker_window(self.ctx, int(stream), int(marker), C.byref(m)))
+
+    def _markers_out(self):
+        M = self.n_markers
+        return (self._out(), [[Position2D.from_c(self._mpos[s * M + m]) for m in range(M)] for s in range(self.n_streams)],
+                [Combined.from_c(p) for p in self._mean])
+
+    def track_markers(self, frames):
+        """One synchronous marker step on host frames (oatgpu_track_markers) -> (fg[n], markers[n][M], mean[n]): the largest
+        foreground blob of each camera, every marker's Position2D, the combined position and heading."""
+        if not getattr(self, "n_markers", 0):
+            raise ffi.OatGpuError(-1, "marker sets are not configured (set_markers)")
+        fs = [_frame(f, self.frame_shape) for f in frames]
+        ptrs = (ffi._u8p * len(fs))(*[ffi.u8(f) for f in fs])
+        self._chk(self.lib.oatgpu_track_markers(self.ctx, ptrs, len(fs), self.learning_coeff_, self._pos, self._mpos, self._mean))
+        return self._markers_out()
+
+    def track_markers_dev(self, dev_ptr):
+        """The same on frames in device memory (oatgpu_track_markers_dev; dev_ptr as track_dev's)."""
+        if not getattr(self, "n_markers", 0):
+            raise ffi.OatGpuError(-1, "marker sets are not configured (set_markers)")
+        self._chk(self.lib.oatgpu_track_markers_dev(self.ctx, C.c_void_p(dev_ptr), self.learning_coeff_, self._pos, self._mpos,
+                                                    self._mean))
+        return self._markers_out()
+
+    def read_marker_mask(self, marker, which=ffi.TAP_MORPH, stream=0):
+        out = np.empty((self.rows, self.cols), np.uint8)
+        self._chk(self.lib.oatgpu_read_marker_mask(self.ctx, int(stream), int(marker), which, ffi.u8(out)))
+        return out
 
     def enqueue(self, frames):
         """Pipelined host-frame form (oatgpu_track_enqueue): frames must stay untouched until the

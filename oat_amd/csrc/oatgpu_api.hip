@@ -202,6 +202,20 @@ struct oatgpu_ctx {
     std::vector<char> wild_model;              // [n_streams] 1: an imported model with weights no run of the kernel produces
     bool audit_on = false;
     long long audit_launches = 0;
+
+    // marker sets (oatgpu_set_markers; kernels_markers.hip): M colour windows per camera behind the one model pass.  Everything
+    // below is made by oatgpu_set_markers and used by the synchronous marker step alone, on stream A.
+    int mk_n = 0;                              // M; 0: markers off
+    int mk_anchor = -1;                        // `posicom mean --heading-anchor`, -1: none
+    std::vector<oatgpu_marker> mk_def;         // [M] erode / dilate / area of each marker (and its default window)
+    std::vector<RangeParams> mk_win_host;      // [n][M] normalised colour windows, per camera and marker
+    RangeParams *mk_win = nullptr;             // ... on the device
+    u64 *mk_planes = nullptr;                  // [M][n][Palloc/64] k_marker_bits' output = launch_blob's src_bits
+    u64 *mk_masks = nullptr;                   // [M][3][n][Palloc/64] each marker's own tmp / morph / fin planes (the taps)
+    BlobBuffers mk_bb{};                       // the rest of one back-half scratch set, shared by the markers (they run one after the other)
+    ResultRec *mk_res = nullptr;               // device: [M][n] result records, then [n] MarkerCombined
+    void *mk_res_host = nullptr;               // page-locked mirror: one copy back a step
+    std::vector<const u64 *> mk_tap_morph;     // [M] where marker m's mask after erode / dilate is
 };
 
 static int fail(oatgpu_ctx *c, int code, const char *fmt, ...)
@@ -379,9 +393,21 @@ struct DevBuf {             // scoped device allocation
 };
 }  // namespace
 
+static void free_scratch(BlobBuffers &b);
+static void free_markers(oatgpu_ctx *c)
+{
+    hipFree(c->mk_win); hipFree(c->mk_planes); hipFree(c->mk_masks); hipFree(c->mk_res);
+    if (c->mk_res_host) hipHostFree(c->mk_res_host);
+    c->mk_win = nullptr; c->mk_planes = nullptr; c->mk_masks = nullptr; c->mk_res = nullptr; c->mk_res_host = nullptr;
+    free_scratch(c->mk_bb);
+    c->mk_n = 0; c->mk_anchor = -1;
+    c->mk_def.clear(); c->mk_win_host.clear(); c->mk_tap_morph.clear();
+}
+
 static void free_all(oatgpu_ctx *c)
 {
     if (!c) return;
+    free_markers(c);
     hipFree(c->bsub_bg); hipFree(c->bsub_f); hipFree(c->diff_last); hipFree(c->roi); hipFree(c->ud_map1); hipFree(c->ud_map2); hipFree(c->ud_frames[0]); hipFree(c->ud_frames[1]); hipFree(c->state); hipFree(c->nmodes); hipFree(c->frames); hipFree(c->aux_a); hipFree(c->aux_b);
     hipFree(c->bb[0].thr);
     hipFree(c->nopark);
@@ -448,11 +474,10 @@ extern "C" int oatgpu_device_open_retries(void) { return g_open_retries.load(); 
 // the paired layout, and the repair set -- 150 bytes a pixel and stream in all.  An allocation in the middle of a pipelined
 // step would stall a camera-paced caller for as long as hipMalloc takes, and its failure would come after the model had
 // moved.
-static bool alloc_scratch_set(oatgpu_ctx *c, int q)
+static bool alloc_scratch(oatgpu_ctx *c, BlobBuffers &b)
 {
     const Geom &g = c->g;
     const size_t n = c->cfg.n_streams, PA = g.Palloc, NW = PA / 64;
-    BlobBuffers &b = c->bb[q];
     bool ok = true;
     auto A = [&](void **p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) ok = false; };
     b.thr = c->bb[0].thr;
@@ -474,6 +499,15 @@ static bool alloc_scratch_set(oatgpu_ctx *c, int q)
     for (unsigned *p : {b.done, b.nroots, b.lds_ok, b.ready})
         if (ok && hipMemsetAsync(p, 0, n * sizeof(unsigned), c->stream) != hipSuccess) ok = false;
     return ok;
+}
+static bool alloc_scratch_set(oatgpu_ctx *c, int q) { return alloc_scratch(c, c->bb[q]); }
+static void free_scratch(BlobBuffers &b)
+{
+    hipFree(b.tmp); hipFree(b.morph); hipFree(b.fin); hipFree(b.trans);
+    hipFree(b.carry); hipFree(b.parent); hipFree(b.acc); hipFree(b.done);
+    hipFree(b.roots); hipFree(b.nroots); hipFree(b.wpre); hipFree(b.rowinfo); hipFree(b.lds_ok);
+    hipFree(b.ready);
+    b = BlobBuffers{};
 }
 
 extern "C" oatgpu_ctx *oatgpu_create(const oatgpu_config *cfg)
@@ -2159,6 +2193,206 @@ extern "C" int oatgpu_track_batch(oatgpu_ctx *c, const uint8_t *const *frames_ho
         HIPCHK(c, hipMemcpyAsync(c->frames + (size_t)s * fb, frames_host[s], fb, hipMemcpyHostToDevice, c->stream));
     }
     return oatgpu_track_batch_dev(c, c->frames, lr, out);
+}
+
+// ----------------------------------------------------------- marker sets ----
+// Several colour windows per camera behind ONE model pass, and `posicom mean` behind them (kernels_markers.hip).
+
+static RangeParams range_of_marker(const oatgpu_marker &m)
+{
+    RangeParams r;
+    norm_range(m.h_lo, m.h_hi, r.lo[0], r.hi[0]);
+    norm_range(m.s_lo, m.s_hi, r.lo[1], r.hi[1]);
+    norm_range(m.v_lo, m.v_hi, r.lo[2], r.hi[2]);
+    return r;
+}
+static int check_marker(oatgpu_ctx *c, const oatgpu_marker &m)
+{
+    oatgpu_config k = c->cfg;           // the rules of oatgpu_set_detector
+    k.h_lo = m.h_lo; k.h_hi = m.h_hi; k.s_lo = m.s_lo; k.s_hi = m.s_hi; k.v_lo = m.v_lo; k.v_hi = m.v_hi;
+    k.erode = m.erode; k.dilate = m.dilate; k.min_area = m.min_area; k.max_area = m.max_area;
+    return check_detector(c, k);
+}
+// the context's own window is the NON-ZERO window: its threshold plane is then Z (kernels_markers.hip)
+static bool own_window_is_nonzero(const oatgpu_ctx *c)
+{
+    const RangeParams r = range_of(c->cfg);
+    if (c->cfg.channels == 1) return r.lo[0] == 1 && r.hi[0] == 255;
+    return r.lo[0] == 0 && r.hi[0] == 255 && r.lo[1] == 0 && r.hi[1] == 255 && r.lo[2] == 1 && r.hi[2] == 255;
+}
+
+extern "C" int oatgpu_set_markers(oatgpu_ctx *c, int32_t n_markers, const oatgpu_marker *defaults, int32_t heading_anchor)
+{
+    if (!c) return OATGPU_E_INVALID;
+    if (n_markers < 0 || n_markers > kMaxMarkers) return fail(c, OATGPU_E_INVALID, "n_markers must be in 0..%d", kMaxMarkers);
+    if (n_markers > 0 && !defaults) return fail(c, OATGPU_E_INVALID, "null argument");
+    if (n_markers > 0 && (heading_anchor < -1 || heading_anchor >= n_markers))      // MeanPosition.cpp:55-57
+        return fail(c, OATGPU_E_INVALID, "heading anchor %d out of range: -1 (none) or a marker index below %d", heading_anchor, n_markers);
+    for (int m = 0; m < n_markers; ++m) { const int rc = check_marker(c, defaults[m]); if (rc) return rc; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    int rc = quiesce(c);
+    if (rc) return rc;
+    free_markers(c);
+    if (n_markers == 0) return OATGPU_OK;
+
+    const size_t n = c->cfg.n_streams, M = (size_t)n_markers, NW = (size_t)c->g.Palloc / 64;
+    const size_t res_bytes = M * n * sizeof(ResultRec) + n * sizeof(MarkerCombined);
+    bool ok = true;
+    auto A = [&](void **p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) ok = false; };
+    A((void **)&c->mk_win, n * M * sizeof(RangeParams));
+    A((void **)&c->mk_planes, M * n * NW * 8);
+    A((void **)&c->mk_masks, M * 3 * n * NW * 8);
+    A((void **)&c->mk_res, res_bytes);
+    if (ok && hipHostMalloc(&c->mk_res_host, res_bytes, hipHostMallocDefault) != hipSuccess) ok = false;
+    if (ok) { c->mk_bb.thr = c->bb[0].thr; c->mk_bb.nopark = c->nopark; ok = alloc_scratch(c, c->mk_bb); }
+    // (the taps read these before the first step; words beyond the frame are never written by the back half)
+    if (ok && hipMemsetAsync(c->mk_planes, 0, M * n * NW * 8, c->stream) != hipSuccess) ok = false;
+    if (ok && hipMemsetAsync(c->mk_masks, 0, M * 3 * n * NW * 8, c->stream) != hipSuccess) ok = false;
+    if (ok) {
+        c->mk_win_host.resize(n * M);
+        for (size_t s = 0; s < n; ++s)
+            for (size_t m = 0; m < M; ++m) c->mk_win_host[s * M + m] = range_of_marker(defaults[m]);
+        if (hipMemcpy(c->mk_win, c->mk_win_host.data(), n * M * sizeof(RangeParams), hipMemcpyHostToDevice) != hipSuccess) ok = false;
+    }
+    if (ok && hipStreamSynchronize(c->stream) != hipSuccess) ok = false;
+    if (!ok) {
+        const hipError_t e = hipGetLastError();
+        free_markers(c);
+        return fail(c, OATGPU_E_NOMEM, "marker sets: device allocation failed: %s", hipGetErrorString(e));
+    }
+    c->mk_n = n_markers;
+    c->mk_anchor = heading_anchor;
+    c->mk_def.assign(defaults, defaults + n_markers);
+    c->mk_tap_morph.resize(M);
+    for (size_t m = 0; m < M; ++m) c->mk_tap_morph[m] = c->mk_planes + m * n * NW;
+    return OATGPU_OK;
+}
+
+static int check_marker_ix(oatgpu_ctx *c, int s, int m)
+{
+    const int rc = check_stream_ix(c, s);
+    if (rc) return rc;
+    if (c->mk_n == 0) return fail(c, OATGPU_E_INVALID, "marker sets are not configured (oatgpu_set_markers)");
+    if (m < 0 || m >= c->mk_n) return fail(c, OATGPU_E_INVALID, "marker index %d out of range (have %d)", m, c->mk_n);
+    return OATGPU_OK;
+}
+
+extern "C" int oatgpu_set_marker_window(oatgpu_ctx *c, int32_t s, int32_t marker, const oatgpu_marker *m)
+{
+    int rc = check_marker_ix(c, s, marker);
+    if (rc) return rc;
+    if (!m) return fail(c, OATGPU_E_INVALID, "null argument");
+    oatgpu_marker w = c->mk_def[(size_t)marker];      // erode / dilate / area stay the marker's: only the window is checked and taken
+    w.h_lo = m->h_lo; w.h_hi = m->h_hi; w.s_lo = m->s_lo; w.s_hi = m->s_hi; w.v_lo = m->v_lo; w.v_hi = m->v_hi;
+    rc = check_marker(c, w);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    rc = quiesce(c);
+    if (rc) return rc;
+    const size_t i = (size_t)s * c->mk_n + marker;
+    c->mk_win_host[i] = range_of_marker(w);
+    HIPCHK(c, hipMemcpy(c->mk_win + i, &c->mk_win_host[i], sizeof(RangeParams), hipMemcpyHostToDevice));
+    return OATGPU_OK;
+}
+
+// what a marker step refuses, checked before anything has moved
+static int marker_step_refusals(oatgpu_ctx *c)
+{
+    if (c->ring_count) return fail(c, OATGPU_E_INVALID, "track_markers while enqueued results are outstanding");
+    if (c->mk_n == 0) return fail(c, OATGPU_E_INVALID, "marker sets are not configured (oatgpu_set_markers)");
+    if (!own_window_is_nonzero(c))
+        return fail(c, OATGPU_E_INVALID, "track_markers needs the context's own window to be the non-zero window: %s",
+                    c->cfg.channels == 1 ? "intensity [1,256]" : "H [0,256], S [0,256], V [1,256]");
+    if (c->kal_on) return fail(c, OATGPU_E_INVALID, "track_markers with the position filter on (oatgpu_set_kalman) is not supported");
+    if (c->homo_on) return fail(c, OATGPU_E_INVALID, "track_markers with a homography on (oatgpu_set_homography) is not supported");
+    return OATGPU_OK;
+}
+
+extern "C" int oatgpu_track_markers_dev(oatgpu_ctx *c, const void *frames_dev, double lr, oatgpu_position *fg,
+                                        oatgpu_position *markers, oatgpu_combined *mean)
+{
+    static_assert(sizeof(oatgpu_combined) == sizeof(MarkerCombined), "k_marker_combine writes oatgpu_combined's layout");
+    if (!c) return OATGPU_E_INVALID;
+    if (!frames_dev || !markers) return fail(c, OATGPU_E_INVALID, "null argument");
+    // ---- 1. refusals, before anything has moved ----
+    { const int rrc = marker_step_refusals(c); if (rrc) return rrc; }
+    const Geom &g = c->g;
+    const int n = c->cfg.n_streams, M = c->mk_n;
+    const size_t NW = (size_t)g.Palloc / 64;
+    // ---- 2. the existing step, unchanged: enqueue + collect ----
+    std::vector<oatgpu_position> fg_own;
+    if (!fg) { fg_own.resize((size_t)n); fg = fg_own.data(); }
+    int rc = oatgpu_track_batch_dev(c, frames_dev, lr, fg);
+    if (rc) return rc;
+    // ---- 3. every marker's mask from the frames the per-pixel kernel read and the Z plane it has just written ----
+    hipStream_t A = c->stream;
+    const uint8_t *seen = c->ud_track ? c->ud_frames[0] : (const uint8_t *)frames_dev;
+    launch_marker_bits(g, seen, c->cfg.channels, thr_buf(c, c->last_q), c->mk_win, M, c->mk_planes, n, A);
+    HIPCHK(c, hipGetLastError());
+    // ---- 4. each marker's back half on its plane, with its erode / dilate / area ----
+    for (int m = 0; m < M; ++m) {
+        const oatgpu_marker &k = c->mk_def[(size_t)m];
+        BlobBuffers bb = c->mk_bb;
+        u64 *own = c->mk_masks + (size_t)m * 3 * n * NW;
+        bb.tmp = own; bb.morph = own + (size_t)n * NW; bb.fin = own + 2 * (size_t)n * NW;
+        const u64 *src = c->mk_planes + (size_t)m * n * NW;
+        const int dil = k.dilate > 1 ? k.dilate : 0;
+        int ero = k.erode > 1 ? k.erode : 0;
+        if (ero && rowscan_lds_bytes(g, dil) > kRowscanLdsMax) {     // very wide rows x large dilation (as back_half)
+            launch_morph(g, src, bb.tmp, ero, true, 0, n, A);
+            src = bb.tmp;
+            ero = 0;
+        }
+        c->mk_tap_morph[(size_t)m] = (dil || ero) ? bb.morph : src;
+        launch_blob(g, bb, src, ero, dil, k.min_area, k.max_area, c->mk_res + (size_t)m * n, 0, n, A, kBlobFull);
+        HIPCHK(c, hipGetLastError());
+    }
+    // ---- 5. posicom mean, one copy back, one synchronisation ----
+    MarkerCombined *comb_dev = (MarkerCombined *)(c->mk_res + (size_t)M * n);
+    launch_marker_combine(c->mk_res, M, c->mk_anchor, n, comb_dev, A);
+    HIPCHK(c, hipGetLastError());
+    const size_t res_bytes = (size_t)M * n * sizeof(ResultRec) + (size_t)n * sizeof(MarkerCombined);
+    HIPCHK(c, hipMemcpyAsync(c->mk_res_host, c->mk_res, res_bytes, hipMemcpyDeviceToHost, A));
+    HIPCHK(c, hipStreamSynchronize(A));
+    const ResultRec *r = (const ResultRec *)c->mk_res_host;
+    for (int s = 0; s < n; ++s)
+        for (int m = 0; m < M; ++m) to_position(r[(size_t)m * n + s], &markers[(size_t)s * M + m]);
+    if (mean) memcpy(mean, r + (size_t)M * n, (size_t)n * sizeof(oatgpu_combined));
+    return OATGPU_OK;
+}
+
+extern "C" int oatgpu_track_markers(oatgpu_ctx *c, const uint8_t *const *frames_host, int32_t n, double lr, oatgpu_position *fg,
+                                    oatgpu_position *markers, oatgpu_combined *mean)
+{
+    if (!c || !frames_host || !markers) return fail(c, OATGPU_E_INVALID, "null argument");
+    if (n != c->cfg.n_streams) return fail(c, OATGPU_E_INVALID, "expected %d frames, got %d", c->cfg.n_streams, n);
+    { const int rrc = marker_step_refusals(c); if (rrc) return rrc; }           // (before the staging buffer is written)
+    for (int s = 0; s < n; ++s) if (!frames_host[s]) return fail(c, OATGPU_E_INVALID, "null frame %d", s);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const size_t fb = (size_t)c->g.H * c->g.W * c->cfg.channels;
+    for (int s = 0; s < n; ++s)
+        HIPCHK(c, hipMemcpyAsync(c->frames + (size_t)s * fb, frames_host[s], fb, hipMemcpyHostToDevice, c->stream));
+    return oatgpu_track_markers_dev(c, c->frames, lr, fg, markers, mean);
+}
+
+extern "C" int oatgpu_read_marker_mask(oatgpu_ctx *c, int32_t s, int32_t marker, int32_t which, uint8_t *out)
+{
+    int rc = check_marker_ix(c, s, marker);
+    if (rc) return rc;
+    if (!out) return fail(c, OATGPU_E_INVALID, "null argument");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    rc = quiesce(c);
+    if (rc) return rc;
+    const size_t n = c->cfg.n_streams, NW = (size_t)c->g.Palloc / 64;
+    const u64 *base = which == OATGPU_TAP_THRESHOLD ? c->mk_planes + (size_t)marker * n * NW
+                    : which == OATGPU_TAP_MORPH ? c->mk_tap_morph[(size_t)marker]
+                    : which == OATGPU_TAP_FINAL ? c->mk_masks + ((size_t)marker * 3 + 2) * n * NW : nullptr;
+    if (!base) return fail(c, OATGPU_E_INVALID, "unknown tap %d", which);
+    launch_unpack_bits(c->g, base + (size_t)s * NW, c->aux_b, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, c->aux_b, (size_t)c->g.H * c->g.W, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return OATGPU_OK;
 }
 
 // ------------------------------------------------------------------ taps ----

@@ -256,4 +256,18 @@ void launch_blob_pair(const Geom &g, const BlobBuffers *b, const u64 *const *src
 void launch_blob_tail2(const Geom &g, const BlobBuffers *b, double min_area, double max_area, ResultRec *const *results,
                        int n_streams, const unsigned *ticket, int nf, hipStream_t st_tail);
 
+// --- kernels_markers.hip --- (marker sets: M colour windows per camera behind one MOG2 pass, `posicom mean`)
+constexpr int kMaxMarkers = 8;
+struct MarkerCombined {   // device-side record of k_marker_combine, one per stream per step: oatgpu_combined's layout
+    int position_valid, heading_valid, velocity_valid, n_valid;
+    double x, y, hx, hy;
+};
+// bit planes [M][n_streams][Palloc/64] of inRange_m(hsv(Z ? px : 0)) for every stream in one launch: frames = what the
+// per-pixel kernel read (stream-major), zbits = the threshold plane it wrote under the non-zero window, win = [n_streams][M]
+// windows in DEVICE memory
+void launch_marker_bits(const Geom &g, const uint8_t *frames, int channels, const u64 *zbits, const RangeParams *win, int M,
+                        u64 *planes, int n_streams, hipStream_t st);
+// MeanPosition::combine over results[M][n_streams] (anchor -1: no heading) into out[n_streams]
+void launch_marker_combine(const ResultRec *results, int M, int anchor, int n_streams, MarkerCombined *out, hipStream_t st);
+
 }  // namespace oatgpu

@@ -54,6 +54,19 @@ class Traffic(C.Structure):
                                          "sector64_bytes_read", "sector64_bytes_written")]
 
 
+class Marker(C.Structure):
+    """oatgpu_marker: one marker's detector (windows as oatgpu_set_detector's)."""
+    _fields_ = [("h_lo", C.c_int32), ("h_hi", C.c_int32), ("s_lo", C.c_int32), ("s_hi", C.c_int32),
+                ("v_lo", C.c_int32), ("v_hi", C.c_int32), ("erode", C.c_int32), ("dilate", C.c_int32),
+                ("min_area", C.c_double), ("max_area", C.c_double)]
+
+
+class Combined(C.Structure):
+    """oatgpu_combined: what `posicom mean` publishes for one camera."""
+    _fields_ = [("position_valid", C.c_int32), ("heading_valid", C.c_int32), ("velocity_valid", C.c_int32),
+                ("n_valid", C.c_int32), ("x", C.c_double), ("y", C.c_double), ("hx", C.c_double), ("hy", C.c_double)]
+
+
 E_RING_FULL = -4
 E_RING_EMPTY = -5
 ABI_VERSION = 9          # must equal OATGPU_ABI_VERSION of include/oatgpu.h
@@ -93,6 +106,13 @@ SIGNATURES = {
     "oatgpu_undistort_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p]),
     "oatgpu_undistort_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
     "oatgpu_set_track_undistort": (C.c_int, [_ctx, C.c_int32]),
+    "oatgpu_set_markers": (C.c_int, [_ctx, C.c_int32, C.POINTER(Marker), C.c_int32]),
+    "oatgpu_set_marker_window": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.POINTER(Marker)]),
+    "oatgpu_track_markers_dev": (C.c_int, [_ctx, C.c_void_p, C.c_double, C.POINTER(Position), C.POINTER(Position),
+                                           C.POINTER(Combined)]),
+    "oatgpu_track_markers": (C.c_int, [_ctx, C.POINTER(_u8p), C.c_int32, C.c_double, C.POINTER(Position), C.POINTER(Position),
+                                       C.POINTER(Combined)]),
+    "oatgpu_read_marker_mask": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32, _u8p]),
     "oatgpu_mog_apply": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_mog_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_bgr2hsv": (C.c_int, [_ctx, _u8p, _u8p]),

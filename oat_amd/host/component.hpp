@@ -310,6 +310,7 @@ inline GreyImage read_pnm_grey(const std::string &path)
 struct Options {
     std::vector<std::string> positional;
     std::map<std::string, std::string> kv;
+    std::map<std::string, std::vector<std::string>> all;   // every value an option was given on the command line, in order (repeatable options)
     std::string config_file, config_key;      // -c FILE KEY (Configurable.h:46-49)
 
     // `-c FILE KEY`: table [KEY] of a TOML file supplies options the command line did not
@@ -411,6 +412,7 @@ struct Options {
                 if (is_flag) { o.kv[key] = "true"; continue; }
                 if (i + 1 >= argc) throw std::runtime_error("option '" + a + "' needs a value");
                 o.kv[key] = argv[++i];
+                o.all[key].push_back(o.kv[key]);
             } else {
                 o.positional.push_back(a);
             }

@@ -45,6 +45,7 @@
 #include <deque>
 #include <fstream>
 #include <sched.h>
+#include <sstream>
 #include <thread>
 #include <unistd.h>
 
@@ -90,6 +91,85 @@ static bool pin_thread_to_device_node(int dev)
     return n > 0 && sched_setaffinity(0, sizeof set, &set) == 0;
 }
 
+// ---- marker sets: one `posidet hsv` per colour and `posicom mean` behind them, in ONE tracker (oatgpu_set_markers) ----
+// --marker "H=[lo,hi] S=[lo,hi] V=[lo,hi] e=K d=K area=[a,b]": every item optional, HSVDetector's defaults otherwise
+// (HSVDetector.h:77-94: all-pass window, erode off, dilate 10, area [0, DBL_MAX)).
+static oatgpu_marker default_marker()
+{
+    oatgpu_config c;
+    oatgpu_default_config(&c);
+    oatgpu_marker m{};
+    m.h_lo = c.h_lo; m.h_hi = c.h_hi; m.s_lo = c.s_lo; m.s_hi = c.s_hi; m.v_lo = c.v_lo; m.v_hi = c.v_hi;
+    m.erode = c.erode; m.dilate = c.dilate; m.min_area = c.min_area; m.max_area = c.max_area;
+    return m;
+}
+static void marker_item(oatgpu_marker &m, const std::string &key, const std::string &val, const std::string &where)
+{
+    double a = 0, b = 0;
+    char tail = 0;
+    const bool pair = sscanf(val.c_str(), " [ %lf , %lf %c", &a, &b, &tail) == 3 && tail == ']';
+    char *end = nullptr;
+    const double v = strtod(val.c_str(), &end);
+    const bool scalar = end != val.c_str() && *end == 0;
+    auto need = [&](bool ok, const char *what) {
+        if (!ok) throw std::runtime_error(where + ": '" + key + "' must be " + what + ", got '" + val + "'");
+    };
+    if (key == "H" || key == "h-thresh") { need(pair, "a 2-element array, e.g. [0,256]"); m.h_lo = (int)a; m.h_hi = (int)b; }
+    else if (key == "S" || key == "s-thresh") { need(pair, "a 2-element array, e.g. [0,256]"); m.s_lo = (int)a; m.s_hi = (int)b; }
+    else if (key == "V" || key == "v-thresh") { need(pair, "a 2-element array, e.g. [0,256]"); m.v_lo = (int)a; m.v_hi = (int)b; }
+    else if (key == "area") { need(pair, "a 2-element array [min,max]"); m.min_area = a; m.max_area = b; }
+    else if (key == "e" || key == "erode") { need(scalar && v >= 0 && v <= 1e6, "a number >= 0"); m.erode = (int)v; }
+    else if (key == "d" || key == "dilate") { need(scalar && v >= 0 && v <= 1e6, "a number >= 0"); m.dilate = (int)v; }
+    else throw std::runtime_error(where + ": unknown item '" + key + "' (H, S, V, e, d, area)");
+}
+static oatgpu_marker parse_marker(const std::string &text)
+{
+    oatgpu_marker m = default_marker();
+    std::istringstream in(text);
+    std::string tok;
+    while (in >> tok) {
+        const size_t eq = tok.find('=');
+        if (eq == std::string::npos || eq == 0) throw std::runtime_error("--marker: expected KEY=VALUE items, got '" + tok + "'");
+        marker_item(m, tok.substr(0, eq), tok.substr(eq + 1), "--marker");
+    }
+    return m;
+}
+// The TOML form: every [[KEY.marker]] table of the -c file is one marker, in file order, with posidet hsv's option names
+// (h-thresh, s-thresh, v-thresh, erode, dilate, area).
+static std::vector<oatgpu_marker> read_marker_tables(const std::string &file, const std::string &key)
+{
+    std::vector<oatgpu_marker> out;
+    std::ifstream in(file);
+    if (!in) return out;
+    auto trim = [](std::string t) {
+        const size_t a = t.find_first_not_of(" \t\r\n"), b = t.find_last_not_of(" \t\r\n");
+        return a == std::string::npos ? std::string() : t.substr(a, b - a + 1);
+    };
+    const std::string header = "[[" + key + ".marker]]", where = "[[" + key + ".marker]]";
+    std::string line;
+    bool inside = false;
+    while (std::getline(in, line)) {
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) line = line.substr(0, hash);
+        line = trim(line);
+        if (line.empty()) continue;
+        if (line.front() == '[' && line.find('=') == std::string::npos) {
+            std::string h;
+            for (char ch : line) if (ch != ' ' && ch != '\t') h += ch;
+            inside = h == header;
+            if (inside) out.push_back(default_marker());
+            continue;
+        }
+        if (!inside) continue;
+        const size_t eq = line.find('=');
+        if (eq == std::string::npos) throw std::runtime_error(where + ": expected key = value");
+        std::string val;
+        for (char ch : trim(line.substr(eq + 1))) if (ch != ' ' && ch != '\t') val += ch;
+        marker_item(out.back(), trim(line.substr(0, eq)), val, where);
+    }
+    return out;
+}
+
 class BatchedTracker : public Component {
 public:
     // stream_base / n_total: where this shard's cameras sit in the command line's SOURCE list (model file names)
@@ -106,6 +186,16 @@ public:
         src_pins_ = std::vector<ShmRegistration>(n_);
     }
     std::string name() const override { return name_; }
+    // marker mode: the context's own window becomes the non-zero window (its threshold plane is then "the masked frame's
+    // pixel is non-zero", what every marker's mask is made from); sinks[s][m] = address of camera s' marker m
+    void set_markers(const std::vector<oatgpu_marker> &markers, int heading_anchor, const std::vector<std::vector<std::string>> &sinks)
+    {
+        markers_ = markers;
+        heading_anchor_ = heading_anchor;
+        marker_sink_addresses_ = sinks;
+        marker_sinks_ = std::vector<Sink<Position2D>>((size_t)n_ * markers.size());
+        cfg_.h_lo = 0; cfg_.h_hi = 256; cfg_.s_lo = 0; cfg_.s_hi = 256; cfg_.v_lo = 1; cfg_.v_hi = 256;
+    }
     oatgpu_config cfg_;
     double learning_coeff_{0.0};
     bool kalman_{false};            // --kalman: `posifilt kalman` fused behind the detector
@@ -118,6 +208,11 @@ public:
     bool homography_on_{false};     // --homography: `posifilt homography` behind the detector / the position filter
     double homography_[9]{1, 0, 0, 0, 1, 0, 0, 0, 1};
     std::vector<UndistortCalibration> undistort_;   // one per camera of this shard: `framefilt undistort` fused in front (empty: off)
+    // marker sets (--marker, repeatable): M `posidet hsv` detectors per camera behind the one model pass and `posicom mean`
+    // behind them; marker m of camera s is published on marker_sink_addresses_[s][m], the combined position on SINK s
+    std::vector<oatgpu_marker> markers_;
+    int heading_anchor_{-1};        // --heading-anchor (`posicom mean`), -1: no heading
+    std::vector<std::vector<std::string>> marker_sink_addresses_;
     ~BatchedTracker() override
     {
         if (!model_file_.empty() && gpu_.ctx)
@@ -161,6 +256,10 @@ protected:
                 if ((size_t)s < shared_positions_.size()) continue;        // bound before the failure
                 try { position_sinks_[s].bind(sink_addresses_[s], sink_addresses_[s]); } catch (...) {}
             }
+            for (size_t i = marker_shared_.size(); i < marker_sinks_.size(); ++i) {
+                const std::string &a = marker_sink_addresses_[i / markers_.size()][i % markers_.size()];
+                try { marker_sinks_[i].bind(a, a); } catch (...) {}
+            }
             throw;
         }
     }
@@ -202,6 +301,17 @@ protected:
         }
         frame_ptrs_.resize(n_);
         results_.resize(n_);
+        if (!markers_.empty()) {
+            const int M = (int)markers_.size();
+            gpu_.check(oatgpu_set_markers(gpu_.ctx, M, markers_.data(), heading_anchor_));
+            for (size_t i = 0; i < marker_sinks_.size(); ++i) {
+                const std::string &a = marker_sink_addresses_[i / M][i % M];
+                marker_sinks_[i].bind(a, a);
+                marker_shared_.push_back(marker_sinks_[i].retrieve());
+            }
+            marker_results_.resize((size_t)n_ * M);
+            combined_.resize(n_);
+        }
         return true;
     }
 
@@ -246,8 +356,57 @@ protected:
     void publish() { publish_some(n_, false); }
     bool results_owed() const { return collected_ || !pending_.empty(); }
 
+    // Marker mode: the synchronous marker step once per round of frames (oatgpu_track_markers).  Every camera's frame is
+    // waited for, the step runs, the SOURCEs are posted, then every marker's Position2D leaves on its sink and the combined
+    // one (`posicom mean`: position, heading) on the camera's ordinary SINK.
+    static void put(Sink<Position2D> &sink, Position2D *shared, const Position2D &pos)
+    {
+        sink.wait();
+        *shared = pos;
+        sink.post();
+    }
+    int process_markers()
+    {
+        const int M = (int)markers_.size();
+        std::vector<Sample> samples(n_);
+        for (int s = 0; s < n_; ++s) {
+            if (frame_sources_[s].wait() == NodeState::END) {
+                for (int q = 0; q < s; ++q) frame_sources_[q].post();      // the round is dropped: nothing is owed for it
+                return 1;
+            }
+            const Frame &shm = *frame_sources_[s].retrieve();
+            src_pins_[s].pin(shm);
+            samples[s] = shm.sample();
+            frame_ptrs_[s] = shm.data();
+        }
+        gpu_.check(oatgpu_track_markers(gpu_.ctx, frame_ptrs_.data(), n_, learning_coeff_, results_.data(), marker_results_.data(),
+                                        combined_.data()));
+        for (int s = 0; s < n_; ++s) frame_sources_[s].post();
+        for (int s = 0; s < n_; ++s) {
+            for (int m = 0; m < M; ++m) {                                   // `posidet hsv` number m of camera s
+                const oatgpu_position &r = marker_results_[(size_t)s * M + m];
+                Position2D pos("");
+                pos.set_sample(samples[s]);
+                pos.position_valid = r.valid != 0;
+                if (r.valid) { pos.position.x = r.x; pos.position.y = r.y; }   // DetectorFunc.cpp:46,58-60
+                put(marker_sinks_[(size_t)s * M + m], marker_shared_[(size_t)s * M + m], pos);
+            }
+            const oatgpu_combined &c = combined_[s];                        // MeanPosition.cpp:60-118
+            Position2D pos("");
+            pos.set_sample(samples[s]);
+            pos.position_valid = c.position_valid != 0;
+            pos.position.x = c.x; pos.position.y = c.y;
+            pos.heading_valid = c.heading_valid != 0;
+            pos.heading.x = c.hx; pos.heading.y = c.hy;
+            put(position_sinks_[s], shared_positions_[s], pos);
+        }
+        ++rounds_;
+        return 0;
+    }
+
     int process() override
     {
+        if (!markers_.empty()) return process_markers();
         // ---- a frame from every camera (PositionDetector.cpp:63-75), camera by camera: as soon as camera s has delivered,
         // its H2D copy starts (oatgpu_track_stage), and camera s - 1, whose copy has meanwhile left its segment, is
         // posted (PositionDetector.cpp:78-86 per camera) -- the n frames cross one PCIe link one after the other, and
@@ -319,6 +478,10 @@ protected:
     std::vector<ShmRegistration> src_pins_;    // declared after the sources: unregistered before the segments are unmapped
     std::vector<const uint8_t *> frame_ptrs_;
     std::vector<oatgpu_position> results_;
+    std::vector<Sink<Position2D>> marker_sinks_;       // [n][M]
+    std::vector<Position2D *> marker_shared_;
+    std::vector<oatgpu_position> marker_results_;      // [n][M]
+    std::vector<oatgpu_combined> combined_;            // [n]
     std::deque<std::vector<Sample>> pending_;  // Samples of the frames whose results are still on the device
     std::vector<Sample> pub_samples_;          // ... and of the result set that is being handed out (publish_some)
     bool collected_{false};
@@ -344,6 +507,14 @@ int main(int argc, char **argv)
                          "                            framefilt undistort fused in front of the chain (the mask applies to the undistorted image):\n"
                          "                            one calibration for every camera, or tables of the -c file holding camera-matrix /\n"
                          "                            distortion-coeffs, one for every camera or one per SOURCE\n"
+                         "       [--marker \"H=[lo,hi] S=[lo,hi] V=[lo,hi] e=K d=K area=[a,b]\"]... --marker-sinks M0,M1,..  [--heading-anchor I]\n"
+                         "                            marker sets: one posidet hsv per --marker (repeatable, up to 8) behind ONE mog pass, and\n"
+                         "                            posicom mean behind them: marker m of a camera is published on the m-th address of that\n"
+                         "                            camera's --marker-sinks list (one list per camera, repeat the option), the mean position and --\n"
+                         "                            with --heading-anchor I -- the heading from marker I to the others on the camera's SINK.\n"
+                         "                            In a -c file: one [[track.marker]] table per marker (h-thresh, s-thresh, v-thresh, erode, dilate,\n"
+                         "                            area) under the tracker's table name, marker-sinks = [\"a,b\", ..], heading-anchor = I.\n"
+                         "                            Not with --kalman, --homography, --ring > 1, --ingest-root, -H/-S/-V, --thresh.\n"
                          "N SOURCEs / N SINKs: N cameras batched into one device pass per frame; SOURCE i feeds SINK i.\n"
                          "--gpu-index N0,N1,..: the cameras are split into contiguous blocks, one per listed device (own context and thread).\n"
                          "--ingest-root D0 (with --gpu-index D0,D1,..): all frames are ingested on device D0 and scattered to their devices\n"
@@ -355,9 +526,56 @@ int main(int argc, char **argv)
         if ((o.has("camera-matrix") || o.has("distortion-coeffs")) && o.has("undistort-key")) throw std::runtime_error(ud_exclusive);
         o.apply_config({"adaptation-coeff", "h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "model-file",
                         "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "gpu-index", "ring", "mask", "thresh", "homography", "stage-copy", "timing",
-                        "ingest-root", "print-partition", "camera-matrix", "distortion-coeffs", "undistort-key"}, {"kalman", "timing", "print-partition"});
+                        "ingest-root", "print-partition", "camera-matrix", "distortion-coeffs", "undistort-key", "marker-sinks", "heading-anchor"},
+                       {"kalman", "timing", "print-partition"});
         const std::vector<std::string> sources = split_list(o.positional[0]), sinks = split_list(o.positional[1]);
         if (sources.size() != sinks.size()) throw std::runtime_error("need as many SINKs as SOURCEs");
+        // marker sets: --marker (repeatable) or the [[KEY.marker]] tables of the -c file; refused with what the synchronous
+        // marker step does not extend to
+        std::vector<oatgpu_marker> markers;
+        if (o.all.count("marker")) for (const std::string &m : o.all["marker"]) markers.push_back(parse_marker(m));
+        else if (!o.config_file.empty()) markers = read_marker_tables(o.config_file, o.config_key);
+        std::vector<std::vector<std::string>> marker_sinks;
+        int heading_anchor = -1;
+        if (markers.empty()) {
+            if (o.has("marker-sinks") || o.has("heading-anchor")) throw std::runtime_error("--marker-sinks / --heading-anchor need at least one --marker");
+        } else {
+            for (const char *k : {"kalman", "homography", "ingest-root", "thresh"})
+                if (o.has(k)) throw std::runtime_error(std::string("--marker does not go with --") + k);
+            for (const char *k : {"h-thresh", "s-thresh", "v-thresh"})
+                if (o.has(k)) throw std::runtime_error(std::string("--marker does not go with --") + k + ": each marker has its own window (H= S= V= inside --marker)");
+            if (o.num("ring", 1, 1, 64) > 1) throw std::runtime_error("--marker does not go with --ring > 1: the marker step is synchronous, one round of frames at a time");
+            if (markers.size() > 8) throw std::runtime_error("--marker: at most 8 markers");
+            std::vector<std::string> lists;
+            if (o.all.count("marker-sinks")) lists = o.all["marker-sinks"];
+            else if (o.has("marker-sinks")) {                              // the -c file: "a,b" or ["a,b", "c,d"]
+                const std::string &v = o.kv["marker-sinks"];
+                size_t a = 0;
+                while ((a = v.find_first_of("\"'", a)) != std::string::npos) {
+                    const size_t b = v.find(v[a], a + 1);
+                    if (b == std::string::npos) break;
+                    lists.push_back(v.substr(a + 1, b - a - 1));
+                    a = b + 1;
+                }
+                if (lists.empty()) lists.push_back(v);
+            }
+            if (lists.size() != sources.size())
+                throw std::runtime_error("--marker-sinks: " + std::to_string(lists.size()) + " lists for " + std::to_string(sources.size()) +
+                                         " SOURCEs (one comma list per camera: repeat the option)");
+            for (const std::string &l : lists) {
+                marker_sinks.push_back(split_list(l));
+                if (marker_sinks.back().size() != markers.size())
+                    throw std::runtime_error("--marker-sinks: '" + l + "' names " + std::to_string(marker_sinks.back().size()) + " sinks for " +
+                                             std::to_string(markers.size()) + " markers");
+            }
+            if (o.has("heading-anchor")) {
+                char *end = nullptr;
+                const long v = strtol(o.kv["heading-anchor"].c_str(), &end, 10);
+                if (end == o.kv["heading-anchor"].c_str() || *end || v < 0 || v >= (long)markers.size())   // MeanPosition.cpp:55-57
+                    throw std::runtime_error("--heading-anchor: expected a marker index in 0.." + std::to_string(markers.size() - 1));
+                heading_anchor = (int)v;
+            }
+        }
         // --gpu-index N | N0,N1,...: one shard of the SOURCE list per listed device (contiguous blocks)
         std::vector<int> devices;
         for (const std::string &d : split_list(o.has("gpu-index") ? o.kv["gpu-index"] : std::string("0"))) {
@@ -446,6 +664,8 @@ int main(int argc, char **argv)
             t->kalman_ = o.has("kalman");
             t->homography_on_ = o.arr9("homography", t->homography_);
             if (!cals.empty()) t->undistort_.assign(cals.begin() + s0, cals.begin() + s1);
+            if (!markers.empty())
+                t->set_markers(markers, heading_anchor, std::vector<std::vector<std::string>>(marker_sinks.begin() + s0, marker_sinks.begin() + s1));
             t->dt_ = o.num("dt", 0.02, 0, 1e9);                        // KalmanFilter2D.cpp:69-85 (lower bound 0)
             t->timeout_ = o.num("timeout", 0.0, 0, 1e18);
             t->sig_accel_ = o.num("sigma-accel", 5.0, 0, 1e18);
