@@ -67,9 +67,14 @@ struct oatgpu_ctx {
     // kSpecAfter frames in a row were taken by the LDS kernel again.
     bool lds_spec = true;
     int lds_streak = 0;
-    std::vector<char> slot_spec, slot_q;      // per ring slot: launched speculatively? which scratch set / B stream?
-    std::vector<int> slot_ev;                 // per ring slot: the slot whose ring event covers this slot's result (itself,
-                                              // or the second frame of its launch when both back halves share a B stream)
+    struct Slot {                   // per ring slot
+        bool spec = false;          // launched speculatively (row scan + LDS kernel alone): redone in the repair set if declined
+        bool filtered = false;      // was the position filter applied to this slot?
+        bool repair = false;        // the global kernels are redoing this frame (ready/quiesce)
+        int ev = 0;                 // the slot whose ring event covers this slot's result (itself, or the second frame of its
+                                    // launch when both back halves share a B stream)
+    };
+    std::vector<Slot> slots;        // [ring_slots]
     int ring_slots = 0;                               // internal ring size (= ring_depth); one threshold-bit buffer per slot
     hipStream_t stream_c = nullptr;  // H2D copies of oatgpu_track_enqueue (created on first use)
     uint8_t *frames_ring = nullptr;  // [ring_slots][n_streams*rows*cols*channels] staging for host frames
@@ -120,9 +125,7 @@ struct oatgpu_ctx {
     unsigned early_frames = 0;       // frames that took the early path (their parity picks scratch set and row-scan stream)
     hipEvent_t ev_blob[kSets] = {};  // scratch set q: its latest reader is done
     bool ev_blob_valid[kSets] = {};
-    std::vector<char> slot_st;       // per ring slot: B stream its result event was recorded on / its repair goes to
-    std::vector<char> slot_filtered;                  // [ring_slots] was the position filter applied to this slot?
-    int last_q = 0;
+    int last_slot = 0;               // ring slot whose threshold bits the latest back half read (oatgpu_read_mask)
     std::string err;
     // Deferred completion of the single-stage calls (oatgpu_set_deferred): the call returns when its INPUT has been read
     // (the H2D copy is done), the result stays on the device until oatgpu_fetch_frame / oatgpu_fetch_position
@@ -148,7 +151,6 @@ struct oatgpu_ctx {
     bool in_sequence = false;                         // inside oatgpu_track_sequence_dev: its frames are all in hand
     hipEvent_t ev_in = nullptr;                       // stream A has read every frame handed over so far (input_consumed)
     bool dev_unconsumed = false;                      // device frames were enqueued since the last input_consumed
-    std::vector<char> slot_repair;                    // per ring slot: the global kernels are redoing this frame (ready/quiesce)
     bool pend_valid = false;
     FrameJob pend;
     unsigned long long launched_total = 0;            // frames whose kernels are out (<= enq_total)
@@ -238,6 +240,22 @@ static int fail(oatgpu_ctx *c, int code, const char *fmt, ...)
                         __FILE__, __LINE__);                                                    \
     } while (0)
 
+static int quiesce(oatgpu_ctx *c);
+static int flush_pending(oatgpu_ctx *c);
+static int repair_outstanding(oatgpu_ctx *c);
+
+// wait for the B streams this context has launched on (all of them, whatever one of them answers)
+static hipError_t drain_b(oatgpu_ctx *c)
+{
+    hipError_t first = hipSuccess;
+    for (int q = 0; q < oatgpu_ctx::kNB; ++q)
+        if (c->stream_b[q] && c->b_used[q]) {
+            const hipError_t e = hipStreamSynchronize(c->stream_b[q]);
+            if (first == hipSuccess) first = e;
+        }
+    return first;
+}
+
 extern "C" int oatgpu_abi_version(void) { return OATGPU_ABI_VERSION; }
 
 extern "C" int oatgpu_default_config(oatgpu_config *c)
@@ -257,7 +275,12 @@ extern "C" int oatgpu_default_config(oatgpu_config *c)
     return OATGPU_OK;
 }
 
-static int check_detector(oatgpu_ctx *c, const oatgpu_config &k)
+// the ten values of a detector: an oatgpu_marker holds a marker's, the context's own come out of its config
+static oatgpu_marker detector_of(const oatgpu_config &k)
+{
+    return {k.h_lo, k.h_hi, k.s_lo, k.s_hi, k.v_lo, k.v_hi, k.erode, k.dilate, k.min_area, k.max_area};
+}
+static int check_detector(oatgpu_ctx *c, const oatgpu_marker &k, int blur = 0)
 {
     const int v[6] = { k.h_lo, k.h_hi, k.s_lo, k.s_hi, k.v_lo, k.v_hi };
     for (int i = 0; i < 6; ++i)
@@ -266,7 +289,7 @@ static int check_detector(oatgpu_ctx *c, const oatgpu_config &k)
     if (k.erode < 0 || k.dilate < 0) return fail(c, OATGPU_E_INVALID, "erode/dilate must be >= 0");
     if (k.erode > 63 || k.dilate > 63)
         return fail(c, OATGPU_E_INVALID, "erode/dilate kernel sizes above 63 are not supported");
-    if (k.blur < 0 || k.blur > 22)
+    if (blur < 0 || blur > 22)
         return fail(c, OATGPU_E_INVALID, "blur must be in 0..22 (above that a box blur is no longer a dilation)");
     if (!(k.min_area < k.max_area))   // HSVDetector.cpp:135
         return fail(c, OATGPU_E_INVALID, "Max area should be larger than min area.");
@@ -280,7 +303,7 @@ static void norm_range(int lo, int hi, int &l, int &h)
     l = lo < 0 ? 0 : lo;
     h = hi > 255 ? 255 : hi;
 }
-static RangeParams range_of(const oatgpu_config &k)
+static RangeParams range_of(const oatgpu_marker &k)
 {
     RangeParams r;
     norm_range(k.h_lo, k.h_hi, r.lo[0], r.hi[0]);
@@ -391,9 +414,27 @@ struct DevBuf {             // scoped device allocation
     ~DevBuf() { if (p) hipFree(p); }
     hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
 };
+struct ModelBufs {          // one stream's model in the logical layout of oatgpu_mog_get_state: modes used, weights, variances, means
+    DevBuf mu, w, v, m;
+    hipError_t alloc(size_t npx, size_t k, size_t mean_bytes)
+    {
+        hipError_t e = mu.alloc(npx);
+        if (e == hipSuccess) e = w.alloc(npx * k * 4);
+        if (e == hipSuccess) e = v.alloc(npx * k * 4);
+        if (e == hipSuccess) e = m.alloc(npx * k * mean_bytes);
+        return e;
+    }
+};
 }  // namespace
 
-static void free_scratch(BlobBuffers &b);
+static void free_scratch(BlobBuffers &b)      // (thr and nopark are the context's: reset with the rest, freed by free_all)
+{
+    hipFree(b.tmp); hipFree(b.morph); hipFree(b.fin); hipFree(b.trans);
+    hipFree(b.carry); hipFree(b.parent); hipFree(b.acc); hipFree(b.done);
+    hipFree(b.roots); hipFree(b.nroots); hipFree(b.wpre); hipFree(b.rowinfo); hipFree(b.lds_ok);
+    hipFree(b.ready);
+    b = BlobBuffers{};
+}
 static void free_markers(oatgpu_ctx *c)
 {
     hipFree(c->mk_win); hipFree(c->mk_planes); hipFree(c->mk_masks); hipFree(c->mk_res);
@@ -420,12 +461,7 @@ static void free_all(oatgpu_ctx *c)
     if (c->ev_c2) hipEventDestroy(c->ev_c2);
     for (auto e : c->copy_ev) hipEventDestroy(e);
     for (auto e : c->copy_ev_s) hipEventDestroy(e);
-    for (auto &b : c->bb) {
-        hipFree(b.tmp); hipFree(b.morph); hipFree(b.fin); hipFree(b.trans);
-        hipFree(b.carry); hipFree(b.parent); hipFree(b.acc); hipFree(b.done);
-        hipFree(b.roots); hipFree(b.nroots); hipFree(b.wpre); hipFree(b.rowinfo); hipFree(b.lds_ok);
-        hipFree(b.ready);
-    }
+    for (auto &b : c->bb) free_scratch(b);
     if (c->res_host) hipHostFree(c->res_host);
     if (c->dens_host) hipHostFree(c->dens_host);
     for (int q = 0; q < oatgpu_ctx::kNB; ++q) if (c->ev_k1[q]) hipEventDestroy(c->ev_k1[q]);
@@ -500,15 +536,6 @@ static bool alloc_scratch(oatgpu_ctx *c, BlobBuffers &b)
         if (ok && hipMemsetAsync(p, 0, n * sizeof(unsigned), c->stream) != hipSuccess) ok = false;
     return ok;
 }
-static bool alloc_scratch_set(oatgpu_ctx *c, int q) { return alloc_scratch(c, c->bb[q]); }
-static void free_scratch(BlobBuffers &b)
-{
-    hipFree(b.tmp); hipFree(b.morph); hipFree(b.fin); hipFree(b.trans);
-    hipFree(b.carry); hipFree(b.parent); hipFree(b.acc); hipFree(b.done);
-    hipFree(b.roots); hipFree(b.nroots); hipFree(b.wpre); hipFree(b.rowinfo); hipFree(b.lds_ok);
-    hipFree(b.ready);
-    b = BlobBuffers{};
-}
 
 extern "C" oatgpu_ctx *oatgpu_create(const oatgpu_config *cfg)
 {
@@ -533,7 +560,7 @@ extern "C" oatgpu_ctx *oatgpu_create(const oatgpu_config *cfg)
         fail(nullptr, OATGPU_E_INVALID, "frame too large");
         return nullptr;
     }
-    if (check_detector(nullptr, *cfg) != OATGPU_OK) return nullptr;
+    if (check_detector(nullptr, detector_of(*cfg), cfg->blur) != OATGPU_OK) return nullptr;
 
     int ndev = 0;
     const hipError_t oe = open_device(cfg->device, &ndev);
@@ -595,7 +622,7 @@ extern "C" oatgpu_ctx *oatgpu_create(const oatgpu_config *cfg)
     A((void **)&c->bb[0].thr, (size_t)c->ring_slots * n * NW * 8);
     A((void **)&c->nopark, sizeof(unsigned));
     if (ok && hipMemsetAsync(c->nopark, 0, sizeof(unsigned), c->stream) != hipSuccess) ok = false;
-    for (int q = 0; q < oatgpu_ctx::kSets && ok; ++q) ok = alloc_scratch_set(c, q);   // (an out-of-memory shows HERE, as OATGPU_E_NOMEM from oatgpu_create)
+    for (int q = 0; q < oatgpu_ctx::kSets && ok; ++q) ok = alloc_scratch(c, c->bb[q]);   // (an out-of-memory shows HERE, as OATGPU_E_NOMEM from oatgpu_create)
     const size_t slots = (size_t)c->ring_slots + 1;
     if (ok && hipHostMalloc((void **)&c->res_host, slots * n * sizeof(ResultRec), hipHostMallocMapped) != hipSuccess)
         ok = false;
@@ -607,13 +634,8 @@ extern "C" oatgpu_ctx *oatgpu_create(const oatgpu_config *cfg)
     if (ok && hipMemset(c->wild_sink, 0, 8 * sizeof(unsigned long long)) != hipSuccess) ok = false;
     if (ok) {
         c->ring_ev.resize(c->ring_slots);
-        c->slot_filtered.assign(c->ring_slots, 0);
-        c->slot_spec.assign(c->ring_slots + 1, 0);
-        c->slot_q.assign(c->ring_slots + 1, 0);
-        c->slot_st.assign(c->ring_slots + 1, 0);
-        c->slot_repair.assign(c->ring_slots + 1, 0);
-        c->slot_ev.resize(c->ring_slots);
-        for (int i = 0; i < c->ring_slots; ++i) c->slot_ev[i] = i;
+        c->slots.assign(c->ring_slots, oatgpu_ctx::Slot{});
+        for (int i = 0; i < c->ring_slots; ++i) c->slots[i].ev = i;
         for (auto &e : c->ring_ev)
             if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) ok = false;
     }
@@ -638,7 +660,7 @@ extern "C" void oatgpu_destroy(oatgpu_ctx *c)
     hipSetDevice(c->cfg.device);
     c->pend_valid = false;            // a registered frame nobody collected: nothing to launch for
     if (c->stream) hipStreamSynchronize(c->stream);
-    for (int q = 0; q < oatgpu_ctx::kNB; ++q) if (c->stream_b[q] && c->b_used[q]) hipStreamSynchronize(c->stream_b[q]);
+    drain_b(c);
     free_all(c);
 }
 
@@ -689,18 +711,16 @@ extern "C" void *oatgpu_host_alloc(size_t bytes)
 }
 extern "C" void oatgpu_host_free(void *ptr) { if (ptr) hipHostFree(ptr); }
 
-static int flush_pending(oatgpu_ctx *c);
 extern "C" int oatgpu_set_stream(oatgpu_ctx *c, void *s)
 {
     if (!c) return OATGPU_E_INVALID;
     { const int frc = flush_pending(c); if (frc) return frc; }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int q = 0; q < oatgpu_ctx::kNB; ++q) if (c->stream_b[q] && c->b_used[q]) HIPCHK(c, hipStreamSynchronize(c->stream_b[q]));
+    HIPCHK(c, drain_b(c));
     c->stream = (hipStream_t)s;
     return OATGPU_OK;
 }
 extern "C" void *oatgpu_get_stream(oatgpu_ctx *c) { return c ? (void *)c->stream : nullptr; }
-static int quiesce(oatgpu_ctx *c);
 extern "C" int oatgpu_synchronize(oatgpu_ctx *c)
 {
     if (!c) return OATGPU_E_INVALID;
@@ -758,9 +778,6 @@ extern "C" int oatgpu_set_fusion(oatgpu_ctx *c, int32_t frames_per_launch)
     return OATGPU_OK;
 }
 
-static int quiesce(oatgpu_ctx *c);
-static int flush_pending(oatgpu_ctx *c);
-
 extern "C" int oatgpu_set_detector(oatgpu_ctx *c, int32_t h_lo, int32_t h_hi, int32_t s_lo, int32_t s_hi,
                                    int32_t v_lo, int32_t v_hi, int32_t erode, int32_t dilate,
                                    double min_area, double max_area)
@@ -769,7 +786,7 @@ extern "C" int oatgpu_set_detector(oatgpu_ctx *c, int32_t h_lo, int32_t h_hi, in
     oatgpu_config k = c->cfg;
     k.h_lo = h_lo; k.h_hi = h_hi; k.s_lo = s_lo; k.s_hi = s_hi; k.v_lo = v_lo; k.v_hi = v_hi;
     k.erode = erode; k.dilate = dilate; k.min_area = min_area; k.max_area = max_area;
-    int rc = check_detector(c, k);
+    int rc = check_detector(c, detector_of(k), k.blur);
     if (rc) return rc;
     rc = quiesce(c);
     if (rc) return rc;
@@ -794,6 +811,10 @@ static Rate mog_begin(oatgpu_ctx *c, int s, double learningRate)
     return r;
 }
 
+// ring slot of the next frame to be enqueued / collected
+static int enq_slot(const oatgpu_ctx *c) { return (int)(c->enq_total % (unsigned long long)c->ring_slots); }
+static int col_slot(const oatgpu_ctx *c) { return (int)(c->col_total % (unsigned long long)c->ring_slots); }
+
 static u64 *thr_buf(oatgpu_ctx *c, int parity)
 {
     return c->bb[0].thr + (size_t)parity * c->cfg.n_streams * (c->g.Palloc >> 6);
@@ -801,20 +822,23 @@ static u64 *thr_buf(oatgpu_ctx *c, int parity)
 
 // The single-stage calls are synchronous and share scratch with the pipelined path:
 // wait until both HIP streams have drained.
-static int flush_pending(oatgpu_ctx *c);
-
-static int repair_outstanding(oatgpu_ctx *c);
-
 static int quiesce(oatgpu_ctx *c)
 {
     if (c->defer_kind) return fail(c, OATGPU_E_INVALID, "a deferred result is waiting: fetch it first (oatgpu_fetch_frame / oatgpu_fetch_position)");
     const int frc = flush_pending(c);
     if (frc) return frc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int q = 0; q < oatgpu_ctx::kNB; ++q) if (c->stream_b[q] && c->b_used[q]) HIPCHK(c, hipStreamSynchronize(c->stream_b[q]));
+    HIPCHK(c, drain_b(c));
     // Outstanding frames whose speculative back half declined them are redone NOW, while their threshold bits are still
     // in their ring slots: the single-stage calls that follow a quiesce() write theirs into slot 0's buffer.
     return repair_outstanding(c);
+}
+
+// ... which is how every synchronous call opens, once its own arguments are in order
+static int open_sync(oatgpu_ctx *c)
+{
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return quiesce(c);
 }
 
 static MogLaunch mog_launch_base(oatgpu_ctx *c, const uint8_t *frames, const Rate &r)
@@ -824,7 +848,7 @@ static MogLaunch mog_launch_base(oatgpu_ctx *c, const uint8_t *frames, const Rat
     a.out_bgr = nullptr; a.out_mask = nullptr; a.out_base = 0; a.roi_bits = c->roi;
     a.alphaT = r.alphaT; a.alpha1 = r.alpha1; a.prune = r.prune; a.fresh = r.fresh; a.nt_loads = c->nt_loads ? 1 : 0;
     a.mp = mogparams_of(c->cfg);
-    a.rp = range_of(c->cfg);
+    a.rp = range_of(detector_of(c->cfg));
     a.audit = c->audit_on ? c->audit_dev : nullptr;
 #ifdef OATGPU_RS_TIMING             // measurement builds: the per-pixel launch's last workgroups stamp the wall clock here (kernels_mog.hip)
     if (!c->rs_k1_end && hipMalloc((void **)&c->rs_k1_end, 64) == hipSuccess) hipMemset(c->rs_k1_end, 0, 64);
@@ -900,8 +924,7 @@ static int mog_single(oatgpu_ctx *c, int s, const uint8_t *bgr_in, uint8_t *mask
     int rc = check_stream_ix(c, s);
     if (rc) return rc;
     if (!bgr_in) return fail(c, OATGPU_E_INVALID, "null frame");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    rc = quiesce(c);
+    rc = open_sync(c);
     if (rc) return rc;
     const size_t npx = (size_t)c->g.H * c->g.W;
     const size_t ch = c->cfg.channels;
@@ -983,8 +1006,7 @@ extern "C" int oatgpu_set_roi_mask(oatgpu_ctx *c, int32_t s, const uint8_t *roi_
 {
     int rc = check_stream_ix(c, s);
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    rc = quiesce(c);
+    rc = open_sync(c);
     if (rc) return rc;
     const Geom &g = c->g;
     const size_t NW = g.Palloc >> 6, n = c->cfg.n_streams, npx = (size_t)g.H * g.W;
@@ -1016,20 +1038,25 @@ extern "C" int oatgpu_mog_filter(oatgpu_ctx *c, int32_t s, const uint8_t *bgr_in
     return mog_single(c, s, bgr_in, nullptr, bgr_out, lr);
 }
 
+// framefilt bsub's background and its fp32 accumulator, made on first use
+static int ensure_bsub(oatgpu_ctx *c, size_t nb)
+{
+    if (c->bsub_bg) return OATGPU_OK;
+    HIPCHK(c, hipMalloc((void **)&c->bsub_bg, (size_t)c->cfg.n_streams * nb));
+    HIPCHK(c, hipMalloc((void **)&c->bsub_f, (size_t)c->cfg.n_streams * nb * sizeof(float)));
+    return OATGPU_OK;
+}
+
 extern "C" int oatgpu_bsub_filter(oatgpu_ctx *c, int32_t s, const uint8_t *in, uint8_t *out, double alpha)
 {
     int rc = check_stream_ix(c, s);
     if (rc) return rc;
     if (!in || !out) return fail(c, OATGPU_E_INVALID, "null argument");
     if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(c, OATGPU_E_INVALID, "adaptation-coeff must be in [0,1]");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    rc = quiesce(c);
+    rc = open_sync(c);
     if (rc) return rc;
     const size_t nb = (size_t)c->g.H * c->g.W * c->cfg.channels;
-    if (!c->bsub_bg) {
-        HIPCHK(c, hipMalloc((void **)&c->bsub_bg, (size_t)c->cfg.n_streams * nb));
-        HIPCHK(c, hipMalloc((void **)&c->bsub_f, (size_t)c->cfg.n_streams * nb * sizeof(float)));
-    }
+    { const int arc = ensure_bsub(c, nb); if (arc) return arc; }
     if (c->bsub_have[s] == 2 && alpha > 0.0)        // the reference's accumulateWeighted asserts on its empty fp32 image
         return fail(c, OATGPU_E_INVALID, "a background image from a file cannot adapt (adaptation-coeff must be 0)");
     rc = stage_in(c, c->aux_a, in, nb);
@@ -1047,14 +1074,10 @@ extern "C" int oatgpu_bsub_set_background(oatgpu_ctx *c, int32_t s, const uint8_
     int rc = check_stream_ix(c, s);
     if (rc) return rc;
     if (!image) return fail(c, OATGPU_E_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    rc = quiesce(c);
+    rc = open_sync(c);
     if (rc) return rc;
     const size_t nb = (size_t)c->g.H * c->g.W * c->cfg.channels;
-    if (!c->bsub_bg) {
-        HIPCHK(c, hipMalloc((void **)&c->bsub_bg, (size_t)c->cfg.n_streams * nb));
-        HIPCHK(c, hipMalloc((void **)&c->bsub_f, (size_t)c->cfg.n_streams * nb * sizeof(float)));
-    }
+    { const int arc = ensure_bsub(c, nb); if (arc) return arc; }
     HIPCHK(c, hipMemcpyAsync(c->bsub_bg + (size_t)s * nb, image, nb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->bsub_have[s] = 2;          // from a file: the fp32 accumulator does not exist (BackgroundSubtractor.cpp:63-71)
@@ -1066,8 +1089,7 @@ extern "C" int oatgpu_mask_filter(oatgpu_ctx *c, int32_t s, const uint8_t *in, u
     int rc = check_stream_ix(c, s);
     if (rc) return rc;
     if (!in || !out) return fail(c, OATGPU_E_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    rc = quiesce(c);
+    rc = open_sync(c);
     if (rc) return rc;
     const size_t nb = (size_t)c->g.H * c->g.W * c->cfg.channels;
     if (!c->roi) {                                   // no mask set: FrameMasker::filter leaves the frame alone
@@ -1090,8 +1112,7 @@ extern "C" int oatgpu_thresh_filter(oatgpu_ctx *c, const uint8_t *in, uint8_t *o
     if (!c || !in || !out) return fail(c, OATGPU_E_INVALID, "null argument");
     if (i_min < 0 || i_min > 256 || i_max < 0 || i_max > 256)      // Threshold.cpp:62-63
         return fail(c, OATGPU_E_INVALID, "Values of intensity should be between 0 and 256.");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    int rc = quiesce(c);
+    int rc = open_sync(c);
     if (rc) return rc;
     const size_t npx = (size_t)c->g.H * c->g.W, nb = npx * c->cfg.channels;
     int lo, hi;
@@ -1141,8 +1162,7 @@ extern "C" int oatgpu_set_undistort(oatgpu_ctx *c, int32_t s, const double K[9],
     std::vector<int16_t> m1(npx * 2);
     std::vector<uint16_t> m2(npx);
     undistort_build_map(g.H, g.W, K, dist, n_dist, m1.data(), m2.data());
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    rc = quiesce(c);                    // an undistortion still in flight may be reading the old map
+    rc = open_sync(c);                  // an undistortion still in flight may be reading the old map
     if (rc) return rc;
     if (!c->ud_map1) {
         c->ud_stride = undistort_map_stride(g.H, g.W);
@@ -1171,8 +1191,7 @@ extern "C" int oatgpu_set_track_undistort(oatgpu_ctx *c, int32_t on)
     if (on)
         for (int s = 0; s < c->cfg.n_streams; ++s)
             if (!c->ud_have[(size_t)s]) return fail(c, OATGPU_E_INVALID, "stream %d has no undistortion map (oatgpu_set_undistort)", s);
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    const int rc = quiesce(c);          // frames registered or in flight were handed over under the old setting
+    const int rc = open_sync(c);        // frames registered or in flight were handed over under the old setting
     if (rc) return rc;
     if (on && !c->ud_frames[0]) {       // (allocated here, never in the middle of a step)
         const size_t sb = (size_t)c->g.H * c->g.W * c->cfg.channels * c->cfg.n_streams;
@@ -1194,8 +1213,7 @@ extern "C" int oatgpu_undistort_filter(oatgpu_ctx *c, int32_t s, const uint8_t *
     if (rc) return rc;
     if (!in || !out) return fail(c, OATGPU_E_INVALID, "null argument");
     if (!c->ud_have[(size_t)s]) return fail(c, OATGPU_E_INVALID, "stream %d has no undistortion map (oatgpu_set_undistort)", s);
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    rc = quiesce(c);
+    rc = open_sync(c);
     if (rc) return rc;
     const size_t nb = (size_t)c->g.H * c->g.W * c->cfg.channels;
     rc = stage_in(c, c->aux_a, in, nb);             // (the reference clones first: out == in is fine, the kernel reads aux_a)
@@ -1289,50 +1307,63 @@ static void apply_kalman(const ResultRec &r, oatgpu_position *o)
     o->x = r.kx; o->y = r.ky; o->vx = r.kvx; o->vy = r.kvy;
 }
 
+// How a back half issues erosion and dilation.  Sizes of 0 and 1 do nothing.  Both are fused into the row scan unless its LDS
+// cannot hold the fused erosion (very wide rows x large dilation): the erosion is then a launch of its own into bb.tmp.
+struct MorphPlan {
+    int ero, dil;               // erode / dilate sizes in effect (0: none)
+    bool ero_apart;             // the erosion is a launch of its own, not fused into the row scan
+};
+static MorphPlan plan_morph(const Geom &g, int erode, int dilate)
+{
+    MorphPlan m;
+    m.dil = dilate > 1 ? dilate : 0;
+    m.ero = erode > 1 ? erode : 0;
+    m.ero_apart = m.ero && rowscan_lds_bytes(g, m.dil) > kRowscanLdsMax;
+    return m;
+}
+// ... carried out on stream st for camera streams [s0, s0+n): what the row scan reads, the erosion left for it to do, and where
+// the mask after erode / dilate will be (the MORPH tap)
+struct MorphIssued { const u64 *src; int ero; const u64 *tap; };
+static MorphIssued issue_morph(const Geom &g, const MorphPlan &m, const BlobBuffers &bb, const u64 *thr, int s0, int n, hipStream_t st)
+{
+    MorphIssued r{thr, m.ero, nullptr};
+    if (m.ero_apart) {
+        launch_morph(g, thr, bb.tmp, m.ero, true, s0, n, st);
+        r.src = bb.tmp;
+        r.ero = 0;
+    }
+    r.tap = (m.dil || r.ero) ? bb.morph : r.src;
+    return r;
+}
+
 // erode -> (dilate fused into the row scan) -> blob for camera streams [s0, s0+n), reading
 // the threshold bits `thr`; results land in host-mapped slot `slot`.  All on HIP stream st.
 static int back_half(oatgpu_ctx *c, BlobBuffers &bb, const u64 *thr, int s0, int n, int slot, hipStream_t st,
                      hipEvent_t ev_mid, int erode_k = -1, int dilate_k = -1, int mode = kBlobFull)
 {
     const Geom &g = c->g;
-    const u64 *src = thr;
     if (erode_k < 0) erode_k = c->cfg.erode;
     if (dilate_k < 0) dilate_k = c->cfg.dilate;
-    const int dil = dilate_k > 1 ? dilate_k : 0;
-    int ero = erode_k > 1 ? erode_k : 0;
-    if (ero && rowscan_lds_bytes(g, dil) > kRowscanLdsMax) {     // very wide rows x large dilation
-        launch_morph(g, src, bb.tmp, ero, true, s0, n, st);
-        src = bb.tmp;
-        ero = 0;
-    }
+    const MorphPlan mp = plan_morph(g, erode_k, dilate_k);
+    const MorphIssued m = issue_morph(g, mp, bb, thr, s0, n, st);
     if (ev_mid) HIPCHK(c, hipEventRecord(ev_mid, st));
-    c->last_morph = (dil || ero) ? bb.morph : src;
+    c->last_morph = m.tap;
     c->last_fin = bb.fin;
     ResultRec *rd = c->res_dev + (size_t)slot * c->cfg.n_streams;
-    launch_blob(g, bb, src, ero, dil, c->cfg.min_area, c->cfg.max_area, rd, s0, n, st, mode);
+    launch_blob(g, bb, m.src, m.ero, mp.dil, c->cfg.min_area, c->cfg.max_area, rd, s0, n, st, mode);
     HIPCHK(c, hipGetLastError());
     return OATGPU_OK;
 }
 
-static int detect_single(oatgpu_ctx *c, int s, const uint8_t *in, int channels, oatgpu_position *out)
+// The back half of a synchronous detector on the bits it has just put into slot 0's buffer, into the extra result slot, and
+// the position handed out -- or, deferred, left with the device once the frame has been read (oatgpu_fetch_position)
+static int detect_tail(oatgpu_ctx *c, int s, int erode_k, int dilate_k, oatgpu_position *out)
 {
-    int rc = check_stream_ix(c, s);
-    if (rc) return rc;
-    if (!in || (!out && !c->deferred)) return fail(c, OATGPU_E_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    rc = quiesce(c);
-    if (rc) return rc;
-    const Geom &g = c->g;
-    const size_t npx = (size_t)g.H * g.W;
-    rc = stage_in(c, c->aux_a, in, npx * channels);
-    if (rc) return rc;
-    RangeParams rp = range_of(c->cfg);
-    launch_inrange_bits(g, c->aux_a, channels, rp, thr_buf(c, 0) + (size_t)s * (g.Palloc >> 6), c->stream);
     const int slot = c->ring_slots;       // the extra slot
-    rc = back_half(c, c->bb[0], thr_buf(c, 0), s, 1, slot, c->stream, nullptr);
+    const int rc = back_half(c, c->bb[0], thr_buf(c, 0), s, 1, slot, c->stream, nullptr, erode_k, dilate_k);
     if (rc) return rc;
-    c->last_q = 0;
-    if (c->deferred) {                    // the frame has been read; the position stays with the device (oatgpu_fetch_position)
+    c->last_slot = 0;
+    if (c->deferred) {
         HIPCHK(c, hipEventSynchronize(c->ev_h2d));
         c->defer_kind = 2; c->defer_s = s;
         return OATGPU_OK;
@@ -1342,13 +1373,28 @@ static int detect_single(oatgpu_ctx *c, int s, const uint8_t *in, int channels, 
     return OATGPU_OK;
 }
 
+static int detect_single(oatgpu_ctx *c, int s, const uint8_t *in, int channels, oatgpu_position *out)
+{
+    int rc = check_stream_ix(c, s);
+    if (rc) return rc;
+    if (!in || (!out && !c->deferred)) return fail(c, OATGPU_E_INVALID, "null argument");
+    rc = open_sync(c);
+    if (rc) return rc;
+    const Geom &g = c->g;
+    const size_t npx = (size_t)g.H * g.W;
+    rc = stage_in(c, c->aux_a, in, npx * channels);
+    if (rc) return rc;
+    RangeParams rp = range_of(detector_of(c->cfg));
+    launch_inrange_bits(g, c->aux_a, channels, rp, thr_buf(c, 0) + (size_t)s * (g.Palloc >> 6), c->stream);
+    return detect_tail(c, s, -1, -1, out);
+}
+
 extern "C" int oatgpu_detect_diff(oatgpu_ctx *c, int32_t s, const uint8_t *grey_in, oatgpu_position *out)
 {
     int rc = check_stream_ix(c, s);
     if (rc) return rc;
     if (!grey_in || (!out && !c->deferred)) return fail(c, OATGPU_E_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    rc = quiesce(c);
+    rc = open_sync(c);
     if (rc) return rc;
     const Geom &g = c->g;
     const size_t npx = (size_t)g.H * g.W;
@@ -1359,19 +1405,8 @@ extern "C" int oatgpu_detect_diff(oatgpu_ctx *c, int32_t s, const uint8_t *grey_
     launch_absdiff_bits(g, c->aux_a, c->diff_last + (size_t)s * npx, c->cfg.diff_threshold, have,
                         thr_buf(c, 0) + (size_t)s * (g.Palloc >> 6), c->stream);
     c->diff_have[s] = 1;
-    const int slot = c->ring_slots;
     // the first frame is analysed unblurred (DifferenceDetector.cpp:167-171); afterwards blur == dilation
-    rc = back_half(c, c->bb[0], thr_buf(c, 0), s, 1, slot, c->stream, nullptr, 0, have ? c->cfg.blur : 0);
-    if (rc) return rc;
-    c->last_q = 0;
-    if (c->deferred) {
-        HIPCHK(c, hipEventSynchronize(c->ev_h2d));
-        c->defer_kind = 2; c->defer_s = s;
-        return OATGPU_OK;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    to_position(c->res_host[(size_t)slot * c->cfg.n_streams + s], out);
-    return OATGPU_OK;
+    return detect_tail(c, s, 0, have ? c->cfg.blur : 0, out);
 }
 
 extern "C" int oatgpu_detect_hsv(oatgpu_ctx *c, int32_t s, const uint8_t *hsv_in, oatgpu_position *out)
@@ -1400,7 +1435,7 @@ static void prof_fold(oatgpu_ctx *c)
 {
     if (!c->prof_used) return;
     hipStreamSynchronize(c->stream);
-    for (int q = 0; q < oatgpu_ctx::kNB; ++q) if (c->stream_b[q] && c->b_used[q]) hipStreamSynchronize(c->stream_b[q]);
+    drain_b(c);
     for (size_t i = 0; i < c->prof_used; ++i) {
         float a = 0, b = 0, d = 0, t = 0;
         ProfStep &p = c->prof_steps[i];
@@ -1459,6 +1494,23 @@ static int ensure_stream_events(oatgpu_ctx *c)
     return OATGPU_OK;
 }
 
+// What the pipelined entry points refuse, always in this order; `checks` names the ones that apply to the caller.
+enum : unsigned { kRefStaging = 1, kRefState = 2, kRefRingFull = 4 };
+static int refuse_pipelined(oatgpu_ctx *c, unsigned checks)
+{
+    // (a set being staged owns the next ring slot: nothing else may be enqueued until oatgpu_track_enqueue_staged took it)
+    if ((checks & kRefStaging) && c->staged_count)
+        return fail(c, OATGPU_E_INVALID, "a frame set is being staged (oatgpu_track_stage): finish it with oatgpu_track_enqueue_staged");
+    if (checks & kRefState) {
+        if (c->broken) return fail(c, OATGPU_E_HIP, "context unusable after a failed launch (destroy it): %s", c->err.c_str());
+        // (a deferred detector's kernels may still be running on stream A with threshold slot 0 and scratch set 0: the
+        // pipelined path would write both from its own streams)
+        if (c->defer_kind) return fail(c, OATGPU_E_INVALID, "a deferred result is waiting: fetch it first (oatgpu_fetch_frame / oatgpu_fetch_position)");
+    }
+    if ((checks & kRefRingFull) && c->ring_count == c->cfg.ring_depth) return fail(c, OATGPU_E_RING_FULL, "result ring full: collect first");
+    return OATGPU_OK;
+}
+
 // The host-frame path camera by camera: oatgpu_track_stage starts ONE camera's H2D copy into the next frame set's
 // staging slot; when all n_streams are on their way oatgpu_track_enqueue_staged registers the set exactly as
 // oatgpu_track_enqueue would have.
@@ -1468,14 +1520,12 @@ extern "C" int oatgpu_track_stage(oatgpu_ctx *c, int32_t stream_ix, const uint8_
     const int n = c->cfg.n_streams;
     if (stream_ix < 0 || stream_ix >= n) return fail(c, OATGPU_E_INVALID, "stream index %d out of range", stream_ix);
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (c->broken) return fail(c, OATGPU_E_HIP, "context unusable after a failed launch (destroy it): %s", c->err.c_str());
-    if (c->defer_kind) return fail(c, OATGPU_E_INVALID, "a deferred result is waiting: fetch it first (oatgpu_fetch_frame / oatgpu_fetch_position)");
+    { const int rc = refuse_pipelined(c, kRefState | (c->staged_count == 0 ? kRefRingFull : 0u)); if (rc) return rc; }
     if (c->staged_count == 0) {
-        if (c->ring_count == c->cfg.ring_depth) return fail(c, OATGPU_E_RING_FULL, "result ring full: collect first");
         { const int rc = ensure_host_ring(c); if (rc) return rc; }
         { const int rc = ensure_stream_events(c); if (rc) return rc; }
         c->staged.assign((size_t)n, 0);
-        c->stage_slot = (int)(c->enq_total % (unsigned long long)c->ring_slots);
+        c->stage_slot = enq_slot(c);
     }
     if (c->staged[(size_t)stream_ix]) return fail(c, OATGPU_E_INVALID, "stream %d is already staged for this frame set", stream_ix);
     const size_t fb = (size_t)c->g.H * c->g.W * c->cfg.channels;
@@ -1515,8 +1565,7 @@ extern "C" int oatgpu_track_enqueue_staged(oatgpu_ctx *c, double lr)
     if (!c) return OATGPU_E_INVALID;
     const int n = c->cfg.n_streams;
     if (c->staged_count != n) return fail(c, OATGPU_E_INVALID, "%d of %d streams staged", c->staged_count, n);
-    if (c->broken) return fail(c, OATGPU_E_HIP, "context unusable after a failed launch (destroy it): %s", c->err.c_str());
-    if (c->defer_kind) return fail(c, OATGPU_E_INVALID, "a deferred result is waiting: fetch it first (oatgpu_fetch_frame / oatgpu_fetch_position)");
+    { const int rc = refuse_pipelined(c, kRefState); if (rc) return rc; }
     HIPCHK(c, hipSetDevice(c->cfg.device));
     const int slot = c->stage_slot;
     const size_t sb = (size_t)c->g.H * c->g.W * c->cfg.channels * n;
@@ -1560,16 +1609,14 @@ extern "C" int oatgpu_track_enqueue(oatgpu_ctx *c, const uint8_t *const *frames_
     if (n != c->cfg.n_streams) return fail(c, OATGPU_E_INVALID, "expected %d frames, got %d", c->cfg.n_streams, n);
     // (refused BEFORE a copy out of the caller's frames is queued -- enqueue_frames checks the same again, but by
     // then stream C would be reading buffers of a call that fails, and input_consumed would wait on a set nobody registered)
-    if (c->broken) return fail(c, OATGPU_E_HIP, "context unusable after a failed launch (destroy it): %s", c->err.c_str());
-    if (c->defer_kind) return fail(c, OATGPU_E_INVALID, "a deferred result is waiting: fetch it first (oatgpu_fetch_frame / oatgpu_fetch_position)");
-    if (c->ring_count == c->cfg.ring_depth) return fail(c, OATGPU_E_RING_FULL, "result ring full: collect first");
+    { const int rc = refuse_pipelined(c, kRefState | kRefRingFull); if (rc) return rc; }
     for (int s = 0; s < n; ++s) if (!frames_host[s]) return fail(c, OATGPU_E_INVALID, "null frame %d", s);
     HIPCHK(c, hipSetDevice(c->cfg.device));
     const size_t fb = (size_t)c->g.H * c->g.W * c->cfg.channels, sb = fb * n;
-    if (c->staged_count) return fail(c, OATGPU_E_INVALID, "a frame set is being staged (oatgpu_track_stage): finish it with oatgpu_track_enqueue_staged");
+    { const int rc = refuse_pipelined(c, kRefStaging); if (rc) return rc; }
     { const int rc = ensure_host_ring(c); if (rc) return rc; }
     // the slot's staging buffer was last read by the K1 of the frame collected from this slot
-    const int slot = (int)(c->enq_total % (unsigned long long)c->ring_slots);
+    const int slot = enq_slot(c);
     uint8_t *dst = c->frames_ring + (size_t)slot * sb;
     if (c->per_stream_copy_ev) { const int rc = ensure_stream_events(c); if (rc) return rc; }
     for (int s = 0; s < n; ++s) {
@@ -1584,12 +1631,10 @@ extern "C" int oatgpu_track_enqueue(oatgpu_ctx *c, const uint8_t *const *frames_
 }
 
 // What a pipelined step does, decided before anything of it is launched (plan_step)
-struct StepPlan {
+struct StepPlan : MorphPlan {  // (the context's erode / dilate: plan_morph)
     bool share_b, early, inline_back, paired, spec_plain;
     int k1_wg;                  // threads a K1 workgroup
     hipEvent_t k1_done;         // the step's "K1 done" event (nullptr: inline_back, nobody waits for it)
-    int ero, dil;               // erode / dilate sizes in effect (0: none)
-    bool ero_apart;             // very wide rows x large dilation: the erosion is a launch of its own, not fused into the row scan
 };
 
 // B streams of the plain order for a frame.  Host frames arrive over the copy stream: use one B stream fewer then: the copy
@@ -1603,9 +1648,7 @@ static StepPlan plan_step(const oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, in
     const size_t step_px = (size_t)c->cfg.n_streams * (size_t)g.P;
     const bool lds_geom = g.H > 2 && g.H <= 16383 && g.W <= 16383;      // a frame geometry the LDS kernel takes
     StepPlan p;
-    p.dil = c->cfg.dilate > 1 ? c->cfg.dilate : 0;
-    p.ero = c->cfg.erode > 1 ? c->cfg.erode : 0;
-    p.ero_apart = p.ero && rowscan_lds_bytes(g, p.dil) > kRowscanLdsMax;
+    static_cast<MorphPlan &>(p) = plan_morph(g, c->cfg.erode, c->cfg.dilate);
     // Small frames are bound by the host's launch calls: the two back halves of a two-frame step
     // then go down ONE B stream behind one wait, and one ring event -- recorded behind the second -- covers both
     // results (8 runtime calls a step instead of 10): 3 x 320x240 78 k -> 108 k fps.  From about a megapixel a step on
@@ -1729,12 +1772,11 @@ static int launch_front(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, co
 // in the frame's own set after a switch to the plain order (the decline itself causes one) wrote set 1 from B0 while a plain
 // frame used it from B1 (found by tools/fuzz.py --seed 11, configuration 301: profiles/r07_fuzz_1500.txt).  Set 4 is touched
 // by repairs only, and only from B2.
-static void repair_in_set4(oatgpu_ctx *c, int slot)
+static constexpr int kRepairSet = oatgpu_ctx::kSets - 1, kRepairStream = oatgpu_ctx::kNB - 1;
+static void mark_speculative(oatgpu_ctx *c, int slot)
 {
-    c->slot_spec[slot] = 1;
-    c->slot_q[slot] = 4;
-    c->slot_st[slot] = 2;
-    c->slot_filtered[slot] = 0;
+    c->slots[slot].spec = true;
+    c->slots[slot].filtered = false;
 }
 
 // Paired: both frames' row scans in one launch and both blob analyses in one (grid z = frame) on B[p], steps alternating
@@ -1754,12 +1796,12 @@ static int launch_back_paired(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, cons
     HIPCHK(c, hipGetLastError());
     if (ps) HIPCHK(c, hipEventRecord(ps->e[4], B));
     for (int i = 0; i < 2; ++i) {
-        repair_in_set4(c, j[i].slot);
-        c->slot_ev[j[i].slot] = j[1].slot;               // one ring event behind the step's blob launch covers both results
+        mark_speculative(c, j[i].slot);
+        c->slots[j[i].slot].ev = j[1].slot;               // one ring event behind the step's blob launch covers both results
     }
     c->last_morph = (plan.dil || plan.ero) ? bbs[1].morph : srcs[1];
     c->last_fin = bbs[1].fin;
-    c->last_q = j[1].slot;
+    c->last_slot = j[1].slot;
     HIPCHK(c, hipEventRecord(c->ring_ev[j[1].slot], B));
     return OATGPU_OK;
 }
@@ -1793,21 +1835,15 @@ static int launch_back_early(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int n
         HIPCHK(c, hipStreamWaitEvent(R, plan.k1_done, 0));
         if (c->ev_blob_valid[q]) HIPCHK(c, hipStreamWaitEvent(R, c->ev_blob[q], 0));
         if (pb) HIPCHK(c, hipEventRecord(pb->e[2], R));
-        const u64 *src = thr_buf(c, slot);
-        int ero = plan.ero;
-        if (plan.ero_apart) {
-            launch_morph(g, src, bb.tmp, ero, true, 0, n, R);
-            src = bb.tmp;
-            ero = 0;
-        }
+        const MorphIssued m = issue_morph(g, plan, bb, thr_buf(c, slot), 0, n, R);
         if (pb) HIPCHK(c, hipEventRecord(pb->e[3], R));
-        c->last_morph = (plan.dil || ero) ? bb.morph : src;
+        c->last_morph = m.tap;
         c->last_fin = bb.fin;
         unsigned ticket = ++c->bh_ticket[q];
         if (!ticket) ticket = ++c->bh_ticket[q];
-        launch_rowscan_signal(g, bb, src, ero, plan.dil, 0, n, ticket, R);
+        launch_rowscan_signal(g, bb, m.src, m.ero, plan.dil, 0, n, ticket, R);
         bbs[i] = bb; res[i] = c->res_dev + (size_t)slot * n; tk[i] = ticket;
-        repair_in_set4(c, slot);                         // (behind the blob launches on B2)
+        mark_speculative(c, slot);                       // (repaired behind the blob launches on B2)
     }
     // ---- B2: the blob workgroups of the step's frames, ONE launch, dispatched now, started by their row scans' tickets ----
     launch_blob_tail2(g, bbs, c->cfg.min_area, c->cfg.max_area, res, n, tk, nj, C);
@@ -1815,10 +1851,10 @@ static int launch_back_early(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int n
     if (ps) HIPCHK(c, hipEventRecord(ps->e[4], C));
     for (int i = 0; i < nj; ++i) {
         const int slot = j[i].slot, q = qs[i];
-        c->slot_ev[slot] = j[nj - 1].slot;           // one ring event behind the step's blob launch covers both results
+        c->slots[slot].ev = j[nj - 1].slot;           // one ring event behind the step's blob launch covers both results
         HIPCHK(c, hipEventRecord(c->ev_blob[q], C));
         c->ev_blob_valid[q] = true;
-        c->last_q = slot;
+        c->last_slot = slot;
     }
     HIPCHK(c, hipEventRecord(c->ring_ev[j[nj - 1].slot], C));
     return OATGPU_OK;
@@ -1837,8 +1873,8 @@ static int launch_back_plain(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int n
         ProfStep *pb = i == 0 ? ps : nullptr;           // the back half of the step's first frame is the sampled one
         if (!(plan.share_b && i == 1) && !plan.inline_back) HIPCHK(c, hipStreamWaitEvent(B, plan.k1_done, 0));
         if (pb) HIPCHK(c, hipEventRecord(pb->e[2], B));
-        if (plan.spec_plain) repair_in_set4(c, slot);
-        else { c->slot_spec[slot] = 0; c->slot_q[slot] = c->slot_st[slot] = (char)q; }
+        if (plan.spec_plain) mark_speculative(c, slot);
+        else c->slots[slot].spec = false;
         // (the position filter is sequential: no repairs behind it)
         const int rc = back_half(c, c->bb[q], thr_buf(c, slot), 0, n, slot, B, pb ? pb->e[3] : nullptr, -1, -1,
                                  plan.spec_plain ? kBlobSpec : kBlobFull);
@@ -1849,15 +1885,15 @@ static int launch_back_plain(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int n
             launch_kalman(kl, c->res_dev + (size_t)slot * n, n, B);
             HIPCHK(c, hipGetLastError());
         }
-        c->slot_filtered[slot] = c->kal_on;
+        c->slots[slot].filtered = c->kal_on;
         if (pb) HIPCHK(c, hipEventRecord(pb->e[4], B));
         if (plan.share_b && i == 0) {
-            c->slot_ev[slot] = j[1].slot;                // the second frame's event, recorded below, covers it
+            c->slots[slot].ev = j[1].slot;                // the second frame's event, recorded below, covers it
         } else {
-            c->slot_ev[slot] = slot;
+            c->slots[slot].ev = slot;
             HIPCHK(c, hipEventRecord(c->ring_ev[slot], B));
         }
-        c->last_q = slot;
+        c->last_slot = slot;
     }
     return OATGPU_OK;
 }
@@ -1885,7 +1921,7 @@ static int launch_jobs(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, boo
     { const int rc = launch_front(c, j, nj, plan, ps); if (rc) return rc; }
     const int path = plan.early ? 1 : plan.paired ? 2 : 0;
     if (c->last_early >= 0 && c->last_early != path)          // the paths use the scratch sets from different streams
-        for (int q = 0; q < oatgpu_ctx::kNB; ++q) if (c->stream_b[q] && c->b_used[q]) HIPCHK(c, hipStreamSynchronize(c->stream_b[q]));
+        HIPCHK(c, drain_b(c));
     c->last_early = path;
     if (plan.paired) return launch_back_paired(c, j, plan, ps);
     if (plan.early) return launch_back_early(c, j, nj, plan, ps);
@@ -1914,17 +1950,11 @@ static int flush_pending(oatgpu_ctx *c)
 static int enqueue_frames(oatgpu_ctx *c, const void *frames_dev, double lr, hipEvent_t frames_ready)
 {
     if (!c || !frames_dev) return fail(c, OATGPU_E_INVALID, "null argument");
-    // (a set being staged owns the next ring slot: nothing else may be enqueued until oatgpu_track_enqueue_staged took it)
-    if (c->staged_count) return fail(c, OATGPU_E_INVALID, "a frame set is being staged (oatgpu_track_stage): finish it with oatgpu_track_enqueue_staged");
-    if (c->broken) return fail(c, OATGPU_E_HIP, "context unusable after a failed launch (destroy it): %s", c->err.c_str());
-    // (a deferred detector's kernels may still be running on stream A with threshold slot 0 and scratch set 0: the pipelined
-    // path would write both from its own streams)
-    if (c->defer_kind) return fail(c, OATGPU_E_INVALID, "a deferred result is waiting: fetch it first (oatgpu_fetch_frame / oatgpu_fetch_position)");
-    if (c->ring_count == c->cfg.ring_depth) return fail(c, OATGPU_E_RING_FULL, "result ring full: collect first");
+    { const int rc = refuse_pipelined(c, kRefStaging | kRefState | kRefRingFull); if (rc) return rc; }
     HIPCHK(c, hipSetDevice(c->cfg.device));
     oatgpu_ctx::FrameJob cur;
     cur.frames = frames_dev; cur.lr = lr; cur.ready = frames_ready;
-    cur.slot = (int)(c->enq_total % (unsigned long long)c->ring_slots);
+    cur.slot = enq_slot(c);
     // two frames a launch: only where a second frame can be outstanding
     const bool want_pair = c->fuse == 2 || (c->fuse == 0 && (frames_ready != nullptr || c->in_sequence));
     const bool may_fuse = want_pair && c->cfg.ring_depth >= 2 && !(c->audit_on && c->cfg.channels != 3);
@@ -1960,7 +1990,7 @@ static int enqueue_frames(oatgpu_ctx *c, const void *frames_dev, double lr, hipE
 // kernels then redo it from its threshold bits, which stay in its ring slot until its result was collected.
 static bool slot_needs_global(const oatgpu_ctx *c, int slot)
 {
-    if (!c->slot_spec[slot]) return false;
+    if (!c->slots[slot].spec) return false;
     const ResultRec *r = c->res_host + (size_t)slot * c->cfg.n_streams;
     for (int s = 0; s < c->cfg.n_streams; ++s) if (r[s].valid == kNeedsGlobal) return true;
     return false;
@@ -1973,8 +2003,8 @@ static bool slot_timed_out(const oatgpu_ctx *c, int slot)
     return false;
 }
 
-// ... on the frame's scratch set's stream, behind whatever later frame that is busy with; the slot's ring event is
-// recorded again behind them.  Not waited for here.
+// ... in the repair set on its stream (THE REPAIR SET above); the slot's ring event is recorded again behind them.  Not waited
+// for here.
 static int launch_repair(oatgpu_ctx *c, int slot)
 {
     if (slot_timed_out(c, slot)) {
@@ -1991,15 +2021,14 @@ static int launch_repair(oatgpu_ctx *c, int slot)
                                     "scan that was not dispatched beside it (kernel dispatches are being serialised); results are unaffected";
         }
     }
-    const int q = c->slot_q[slot];
-    hipStream_t B = c->stream_b[(int)c->slot_st[slot]];
-    c->b_used[(int)c->slot_st[slot]] = true;
-    const int rc = back_half(c, c->bb[q], thr_buf(c, slot), 0, c->cfg.n_streams, slot, B, nullptr, -1, -1, kBlobGlobal);
+    hipStream_t B = c->stream_b[kRepairStream];
+    c->b_used[kRepairStream] = true;
+    const int rc = back_half(c, c->bb[kRepairSet], thr_buf(c, slot), 0, c->cfg.n_streams, slot, B, nullptr, -1, -1, kBlobGlobal);
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(c->ring_ev[slot], B));
-    c->slot_ev[slot] = slot;
-    c->slot_repair[slot] = 1;
-    c->slot_spec[slot] = 0;
+    c->slots[slot].ev = slot;
+    c->slots[slot].repair = true;
+    c->slots[slot].spec = false;
     c->lds_spec = false;
     c->lds_streak = 0;
     return OATGPU_OK;
@@ -2009,15 +2038,15 @@ static int launch_repair(oatgpu_ctx *c, int slot)
 static int repair_outstanding(oatgpu_ctx *c)
 {
     bool any = false;
-    for (unsigned long long t = c->col_total; t < c->col_total + (unsigned long long)c->ring_count; ++t) {
-        const int slot = (int)(t % (unsigned long long)c->ring_slots);
-        if (c->slot_repair[slot] || !slot_needs_global(c, slot)) continue;
+    for (int i = 0; i < c->ring_count; ++i) {
+        const int slot = (col_slot(c) + i) % c->ring_slots;
+        if (c->slots[slot].repair || !slot_needs_global(c, slot)) continue;
         const int rc = launch_repair(c, slot);
         if (rc) return rc;
         any = true;
     }
     if (any)
-        for (int q = 0; q < oatgpu_ctx::kNB; ++q) if (c->stream_b[q] && c->b_used[q]) HIPCHK(c, hipStreamSynchronize(c->stream_b[q]));
+        HIPCHK(c, drain_b(c));
     return OATGPU_OK;
 }
 
@@ -2037,21 +2066,21 @@ extern "C" int oatgpu_track_collect(oatgpu_ctx *c, oatgpu_position *out)
 {
     if (!c || !out) return fail(c, OATGPU_E_INVALID, "null argument");
     if (c->ring_count == 0) return fail(c, OATGPU_E_RING_EMPTY, "nothing outstanding");
-    const int slot = (int)(c->col_total % (unsigned long long)c->ring_slots);
+    const int slot = col_slot(c);
     if (c->pend_valid && c->pend.slot == slot) {          // the frame wanted is still only registered: launch it alone
         const int frc = flush_pending(c);
         if (frc) return frc;
     }
     // (polling here, as wait_short does for the copies, made the one-camera latency WORSE: p50 207 -> 257 us free-running)
-    HIPCHK(c, hipEventSynchronize(c->ring_ev[c->slot_ev[slot]]));
+    HIPCHK(c, hipEventSynchronize(c->ring_ev[c->slots[slot].ev]));
     const ResultRec *r = c->res_host + (size_t)slot * c->cfg.n_streams;
-    if (!c->slot_repair[slot] && slot_needs_global(c, slot)) {
+    if (!c->slots[slot].repair && slot_needs_global(c, slot)) {
         const int rc = launch_repair(c, slot);
         if (rc) return rc;
     }
-    if (c->slot_repair[slot]) {                            // (launched here, by oatgpu_track_ready or by a quiesce())
+    if (c->slots[slot].repair) {                            // (launched here, by oatgpu_track_ready or by a quiesce())
         HIPCHK(c, hipEventSynchronize(c->ring_ev[slot]));
-        c->slot_repair[slot] = 0;
+        c->slots[slot].repair = false;
     } else {
         constexpr int kSpecAfter = 16;
         bool all_lds = true;
@@ -2065,7 +2094,7 @@ extern "C" int oatgpu_track_collect(oatgpu_ctx *c, oatgpu_position *out)
     }
     for (int s = 0; s < c->cfg.n_streams; ++s) {
         to_position(r[s], &out[s]);
-        if (c->slot_filtered[slot]) apply_kalman(r[s], &out[s]);
+        if (c->slots[slot].filtered) apply_kalman(r[s], &out[s]);
         if (c->homo_on) apply_homography(c, &out[s]);
     }
     c->col_total++;
@@ -2111,15 +2140,15 @@ extern "C" int oatgpu_track_ready(oatgpu_ctx *c)
 {
     if (!c) return OATGPU_E_INVALID;
     if (c->ring_count == 0) return 0;
-    const int slot = (int)(c->col_total % (unsigned long long)c->ring_slots);
+    const int slot = col_slot(c);
     if (c->pend_valid && c->pend.slot == slot) {          // somebody is waiting for this very frame: send it off
         const int frc = flush_pending(c);
         if (frc) return frc;
     }
-    const hipError_t e = hipEventQuery(c->ring_ev[c->slot_repair[slot] ? slot : c->slot_ev[slot]]);
+    const hipError_t e = hipEventQuery(c->ring_ev[c->slots[slot].repair ? slot : c->slots[slot].ev]);
     if (e == hipErrorNotReady) return 0;
     if (e != hipSuccess) return fail(c, OATGPU_E_HIP, "hipEventQuery failed: %s", hipGetErrorString(e));
-    if (!c->slot_repair[slot] && slot_needs_global(c, slot)) {   // declined by the LDS kernel: collect would block on the
+    if (!c->slots[slot].repair && slot_needs_global(c, slot)) {   // declined by the LDS kernel: collect would block on the
         const int rc = launch_repair(c, slot);                    // global kernels -- start them, not ready yet
         return rc ? rc : 0;
     }
@@ -2181,42 +2210,34 @@ extern "C" int oatgpu_track_batch_dev(oatgpu_ctx *c, const void *frames_dev, dou
     return oatgpu_track_collect(c, out);
 }
 
+// one host frame per camera stream into the staging buffer of the synchronous steps, on stream A; a null one ends it there
+static int upload_frames(oatgpu_ctx *c, const uint8_t *const *frames_host)
+{
+    const size_t fb = (size_t)c->g.H * c->g.W * c->cfg.channels;
+    for (int s = 0; s < c->cfg.n_streams; ++s) {
+        if (!frames_host[s]) return fail(c, OATGPU_E_INVALID, "null frame %d", s);
+        HIPCHK(c, hipMemcpyAsync(c->frames + (size_t)s * fb, frames_host[s], fb, hipMemcpyHostToDevice, c->stream));
+    }
+    return OATGPU_OK;
+}
+
 extern "C" int oatgpu_track_batch(oatgpu_ctx *c, const uint8_t *const *frames_host, int32_t n, double lr,
                                   oatgpu_position *out)
 {
     if (!c || !frames_host || !out) return fail(c, OATGPU_E_INVALID, "null argument");
     if (n != c->cfg.n_streams) return fail(c, OATGPU_E_INVALID, "expected %d frames, got %d", c->cfg.n_streams, n);
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    const size_t fb = (size_t)c->g.H * c->g.W * c->cfg.channels;
-    for (int s = 0; s < n; ++s) {
-        if (!frames_host[s]) return fail(c, OATGPU_E_INVALID, "null frame %d", s);
-        HIPCHK(c, hipMemcpyAsync(c->frames + (size_t)s * fb, frames_host[s], fb, hipMemcpyHostToDevice, c->stream));
-    }
+    { const int rc = upload_frames(c, frames_host); if (rc) return rc; }
     return oatgpu_track_batch_dev(c, c->frames, lr, out);
 }
 
 // ----------------------------------------------------------- marker sets ----
 // Several colour windows per camera behind ONE model pass, and `posicom mean` behind them (kernels_markers.hip).
 
-static RangeParams range_of_marker(const oatgpu_marker &m)
-{
-    RangeParams r;
-    norm_range(m.h_lo, m.h_hi, r.lo[0], r.hi[0]);
-    norm_range(m.s_lo, m.s_hi, r.lo[1], r.hi[1]);
-    norm_range(m.v_lo, m.v_hi, r.lo[2], r.hi[2]);
-    return r;
-}
-static int check_marker(oatgpu_ctx *c, const oatgpu_marker &m)
-{
-    oatgpu_config k = c->cfg;           // the rules of oatgpu_set_detector
-    k.h_lo = m.h_lo; k.h_hi = m.h_hi; k.s_lo = m.s_lo; k.s_hi = m.s_hi; k.v_lo = m.v_lo; k.v_hi = m.v_hi;
-    k.erode = m.erode; k.dilate = m.dilate; k.min_area = m.min_area; k.max_area = m.max_area;
-    return check_detector(c, k);
-}
 // the context's own window is the NON-ZERO window: its threshold plane is then Z (kernels_markers.hip)
 static bool own_window_is_nonzero(const oatgpu_ctx *c)
 {
-    const RangeParams r = range_of(c->cfg);
+    const RangeParams r = range_of(detector_of(c->cfg));
     if (c->cfg.channels == 1) return r.lo[0] == 1 && r.hi[0] == 255;
     return r.lo[0] == 0 && r.hi[0] == 255 && r.lo[1] == 0 && r.hi[1] == 255 && r.lo[2] == 1 && r.hi[2] == 255;
 }
@@ -2228,9 +2249,8 @@ extern "C" int oatgpu_set_markers(oatgpu_ctx *c, int32_t n_markers, const oatgpu
     if (n_markers > 0 && !defaults) return fail(c, OATGPU_E_INVALID, "null argument");
     if (n_markers > 0 && (heading_anchor < -1 || heading_anchor >= n_markers))      // MeanPosition.cpp:55-57
         return fail(c, OATGPU_E_INVALID, "heading anchor %d out of range: -1 (none) or a marker index below %d", heading_anchor, n_markers);
-    for (int m = 0; m < n_markers; ++m) { const int rc = check_marker(c, defaults[m]); if (rc) return rc; }
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    int rc = quiesce(c);
+    for (int m = 0; m < n_markers; ++m) { const int rc = check_detector(c, defaults[m]); if (rc) return rc; }
+    int rc = open_sync(c);
     if (rc) return rc;
     free_markers(c);
     if (n_markers == 0) return OATGPU_OK;
@@ -2244,14 +2264,14 @@ extern "C" int oatgpu_set_markers(oatgpu_ctx *c, int32_t n_markers, const oatgpu
     A((void **)&c->mk_masks, M * 3 * n * NW * 8);
     A((void **)&c->mk_res, res_bytes);
     if (ok && hipHostMalloc(&c->mk_res_host, res_bytes, hipHostMallocDefault) != hipSuccess) ok = false;
-    if (ok) { c->mk_bb.thr = c->bb[0].thr; c->mk_bb.nopark = c->nopark; ok = alloc_scratch(c, c->mk_bb); }
+    if (ok) ok = alloc_scratch(c, c->mk_bb);
     // (the taps read these before the first step; words beyond the frame are never written by the back half)
     if (ok && hipMemsetAsync(c->mk_planes, 0, M * n * NW * 8, c->stream) != hipSuccess) ok = false;
     if (ok && hipMemsetAsync(c->mk_masks, 0, M * 3 * n * NW * 8, c->stream) != hipSuccess) ok = false;
     if (ok) {
         c->mk_win_host.resize(n * M);
         for (size_t s = 0; s < n; ++s)
-            for (size_t m = 0; m < M; ++m) c->mk_win_host[s * M + m] = range_of_marker(defaults[m]);
+            for (size_t m = 0; m < M; ++m) c->mk_win_host[s * M + m] = range_of(defaults[m]);
         if (hipMemcpy(c->mk_win, c->mk_win_host.data(), n * M * sizeof(RangeParams), hipMemcpyHostToDevice) != hipSuccess) ok = false;
     }
     if (ok && hipStreamSynchronize(c->stream) != hipSuccess) ok = false;
@@ -2284,14 +2304,23 @@ extern "C" int oatgpu_set_marker_window(oatgpu_ctx *c, int32_t s, int32_t marker
     if (!m) return fail(c, OATGPU_E_INVALID, "null argument");
     oatgpu_marker w = c->mk_def[(size_t)marker];      // erode / dilate / area stay the marker's: only the window is checked and taken
     w.h_lo = m->h_lo; w.h_hi = m->h_hi; w.s_lo = m->s_lo; w.s_hi = m->s_hi; w.v_lo = m->v_lo; w.v_hi = m->v_hi;
-    rc = check_marker(c, w);
+    rc = check_detector(c, w);
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    rc = quiesce(c);
+    rc = open_sync(c);
     if (rc) return rc;
     const size_t i = (size_t)s * c->mk_n + marker;
-    c->mk_win_host[i] = range_of_marker(w);
+    c->mk_win_host[i] = range_of(w);
     HIPCHK(c, hipMemcpy(c->mk_win + i, &c->mk_win_host[i], sizeof(RangeParams), hipMemcpyHostToDevice));
+    return OATGPU_OK;
+}
+
+// one camera's bit plane as a byte mask on the host: unpack, copy, wait
+static int read_plane(oatgpu_ctx *c, const u64 *plane, uint8_t *out)
+{
+    launch_unpack_bits(c->g, plane, c->aux_b, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, c->aux_b, (size_t)c->g.H * c->g.W, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return OATGPU_OK;
 }
 
@@ -2327,7 +2356,7 @@ extern "C" int oatgpu_track_markers_dev(oatgpu_ctx *c, const void *frames_dev, d
     // ---- 3. every marker's mask from the frames the per-pixel kernel read and the Z plane it has just written ----
     hipStream_t A = c->stream;
     const uint8_t *seen = c->ud_track ? c->ud_frames[0] : (const uint8_t *)frames_dev;
-    launch_marker_bits(g, seen, c->cfg.channels, thr_buf(c, c->last_q), c->mk_win, M, c->mk_planes, n, A);
+    launch_marker_bits(g, seen, c->cfg.channels, thr_buf(c, c->last_slot), c->mk_win, M, c->mk_planes, n, A);
     HIPCHK(c, hipGetLastError());
     // ---- 4. each marker's back half on its plane, with its erode / dilate / area ----
     for (int m = 0; m < M; ++m) {
@@ -2335,16 +2364,10 @@ extern "C" int oatgpu_track_markers_dev(oatgpu_ctx *c, const void *frames_dev, d
         BlobBuffers bb = c->mk_bb;
         u64 *own = c->mk_masks + (size_t)m * 3 * n * NW;
         bb.tmp = own; bb.morph = own + (size_t)n * NW; bb.fin = own + 2 * (size_t)n * NW;
-        const u64 *src = c->mk_planes + (size_t)m * n * NW;
-        const int dil = k.dilate > 1 ? k.dilate : 0;
-        int ero = k.erode > 1 ? k.erode : 0;
-        if (ero && rowscan_lds_bytes(g, dil) > kRowscanLdsMax) {     // very wide rows x large dilation (as back_half)
-            launch_morph(g, src, bb.tmp, ero, true, 0, n, A);
-            src = bb.tmp;
-            ero = 0;
-        }
-        c->mk_tap_morph[(size_t)m] = (dil || ero) ? bb.morph : src;
-        launch_blob(g, bb, src, ero, dil, k.min_area, k.max_area, c->mk_res + (size_t)m * n, 0, n, A, kBlobFull);
+        const MorphPlan mp = plan_morph(g, k.erode, k.dilate);
+        const MorphIssued mi = issue_morph(g, mp, bb, c->mk_planes + (size_t)m * n * NW, 0, n, A);
+        c->mk_tap_morph[(size_t)m] = mi.tap;
+        launch_blob(g, bb, mi.src, mi.ero, mp.dil, k.min_area, k.max_area, c->mk_res + (size_t)m * n, 0, n, A, kBlobFull);
         HIPCHK(c, hipGetLastError());
     }
     // ---- 5. posicom mean, one copy back, one synchronisation ----
@@ -2369,9 +2392,7 @@ extern "C" int oatgpu_track_markers(oatgpu_ctx *c, const uint8_t *const *frames_
     { const int rrc = marker_step_refusals(c); if (rrc) return rrc; }           // (before the staging buffer is written)
     for (int s = 0; s < n; ++s) if (!frames_host[s]) return fail(c, OATGPU_E_INVALID, "null frame %d", s);
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    const size_t fb = (size_t)c->g.H * c->g.W * c->cfg.channels;
-    for (int s = 0; s < n; ++s)
-        HIPCHK(c, hipMemcpyAsync(c->frames + (size_t)s * fb, frames_host[s], fb, hipMemcpyHostToDevice, c->stream));
+    { const int rc = upload_frames(c, frames_host); if (rc) return rc; }
     return oatgpu_track_markers_dev(c, c->frames, lr, fg, markers, mean);
 }
 
@@ -2380,19 +2401,14 @@ extern "C" int oatgpu_read_marker_mask(oatgpu_ctx *c, int32_t s, int32_t marker,
     int rc = check_marker_ix(c, s, marker);
     if (rc) return rc;
     if (!out) return fail(c, OATGPU_E_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    rc = quiesce(c);
+    rc = open_sync(c);
     if (rc) return rc;
     const size_t n = c->cfg.n_streams, NW = (size_t)c->g.Palloc / 64;
     const u64 *base = which == OATGPU_TAP_THRESHOLD ? c->mk_planes + (size_t)marker * n * NW
                     : which == OATGPU_TAP_MORPH ? c->mk_tap_morph[(size_t)marker]
                     : which == OATGPU_TAP_FINAL ? c->mk_masks + ((size_t)marker * 3 + 2) * n * NW : nullptr;
     if (!base) return fail(c, OATGPU_E_INVALID, "unknown tap %d", which);
-    launch_unpack_bits(c->g, base + (size_t)s * NW, c->aux_b, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, c->aux_b, (size_t)c->g.H * c->g.W, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return OATGPU_OK;
+    return read_plane(c, base + (size_t)s * NW, out);
 }
 
 // ------------------------------------------------------------------ taps ----
@@ -2402,20 +2418,14 @@ extern "C" int oatgpu_read_mask(oatgpu_ctx *c, int32_t s, int32_t which, uint8_t
     int rc = check_stream_ix(c, s);
     if (rc) return rc;
     if (!out) return fail(c, OATGPU_E_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    rc = quiesce(c);
+    rc = open_sync(c);
     if (rc) return rc;
-    const u64 *last_thr = thr_buf(c, c->last_q);
+    const u64 *last_thr = thr_buf(c, c->last_slot);
     const u64 *base = which == OATGPU_TAP_THRESHOLD ? last_thr
                     : which == OATGPU_TAP_MORPH ? c->last_morph
                     : which == OATGPU_TAP_FINAL ? c->last_fin : nullptr;
     if (!base) return fail(c, OATGPU_E_INVALID, "unknown tap %d", which);
-    const size_t npx = (size_t)c->g.H * c->g.W;
-    launch_unpack_bits(c->g, base + (size_t)s * (c->g.Palloc >> 6), c->aux_b, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, c->aux_b, npx, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return OATGPU_OK;
+    return read_plane(c, base + (size_t)s * (c->g.Palloc >> 6), out);
 }
 
 extern "C" int oatgpu_mog_get_state(oatgpu_ctx *c, int32_t s, uint8_t *modes_used, float *weight, float *variance,
@@ -2423,17 +2433,13 @@ extern "C" int oatgpu_mog_get_state(oatgpu_ctx *c, int32_t s, uint8_t *modes_use
 {
     int rc = check_stream_ix(c, s);
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    rc = quiesce(c);
+    rc = open_sync(c);
     if (rc) return rc;
     const Geom &g = c->g;
     const size_t npx = (size_t)g.H * g.W, k = c->cfg.nmixtures, mb = 4 * (size_t)c->cfg.channels;
-    DevBuf b_mu, b_w, b_v, b_m;          // freed on every return path
-    HIPCHK(c, b_mu.alloc(npx));
-    HIPCHK(c, b_w.alloc(npx * k * 4));
-    HIPCHK(c, b_v.alloc(npx * k * 4));
-    HIPCHK(c, b_m.alloc(npx * k * mb));
-    uint8_t *d_mu = (uint8_t *)b_mu.p; float *d_w = (float *)b_w.p, *d_v = (float *)b_v.p, *d_m = (float *)b_m.p;
+    ModelBufs b;                         // freed on every return path
+    HIPCHK(c, b.alloc(npx, k, mb));
+    uint8_t *d_mu = (uint8_t *)b.mu.p; float *d_w = (float *)b.w.p, *d_v = (float *)b.v.p, *d_m = (float *)b.m.p;
     launch_state_export(g, c->state + (size_t)s * mog_stream_floats(g.Palloc), c->nmodes + (size_t)s * g.Palloc, (int)k,
                         c->cfg.channels, d_mu, d_w, d_v, d_m, c->stream);
     hipError_t e = hipGetLastError();
@@ -2454,17 +2460,13 @@ extern "C" int oatgpu_mog_set_state(oatgpu_ctx *c, int32_t s, const uint8_t *mod
     if (rc) return rc;
     if (!modes_used || !weight || !variance || !mean || nframes < 0)
         return fail(c, OATGPU_E_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    rc = quiesce(c);
+    rc = open_sync(c);
     if (rc) return rc;
     const Geom &g = c->g;
     const size_t npx = (size_t)g.H * g.W, k = c->cfg.nmixtures, mb = 4 * (size_t)c->cfg.channels;
-    DevBuf b_mu, b_w, b_v, b_m;          // freed on every return path
-    HIPCHK(c, b_mu.alloc(npx));
-    HIPCHK(c, b_w.alloc(npx * k * 4));
-    HIPCHK(c, b_v.alloc(npx * k * 4));
-    HIPCHK(c, b_m.alloc(npx * k * mb));
-    uint8_t *d_mu = (uint8_t *)b_mu.p; float *d_w = (float *)b_w.p, *d_v = (float *)b_v.p, *d_m = (float *)b_m.p;
+    ModelBufs b;                         // freed on every return path
+    HIPCHK(c, b.alloc(npx, k, mb));
+    uint8_t *d_mu = (uint8_t *)b.mu.p; float *d_w = (float *)b.w.p, *d_v = (float *)b.v.p, *d_m = (float *)b.m.p;
     hipError_t e = hipMemcpyAsync(d_mu, modes_used, npx, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_w, weight, npx * k * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_v, variance, npx * k * 4, hipMemcpyHostToDevice, c->stream);
@@ -2587,8 +2589,7 @@ extern "C" int oatgpu_mog_load(oatgpu_ctx *c, int32_t s, const char *path)
 extern "C" int oatgpu_measure_hbm(oatgpu_ctx *c, size_t bytes, int32_t reps, double *read_gbps, double *copy_gbps)
 {
     if (!c || bytes < (1u << 20) || reps < 1) return fail(c, OATGPU_E_INVALID, "bad argument");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    int rc = quiesce(c);
+    int rc = open_sync(c);
     if (rc) return rc;
     const size_t n16 = bytes / 16;
     void *a = nullptr, *b = nullptr;
@@ -2629,8 +2630,7 @@ extern "C" int oatgpu_measure_hbm(oatgpu_ctx *c, size_t bytes, int32_t reps, dou
 extern "C" int oatgpu_traffic_audit(oatgpu_ctx *c, int32_t on)
 {
     if (!c) return OATGPU_E_INVALID;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    int rc = quiesce(c);
+    int rc = open_sync(c);
     if (rc) return rc;
     if (on) {
         if (!c->audit_dev) HIPCHK(c, hipMalloc((void **)&c->audit_dev, 8 * sizeof(unsigned long long)));
@@ -2646,8 +2646,7 @@ extern "C" int oatgpu_traffic_read(oatgpu_ctx *c, oatgpu_traffic *out)
     if (!c || !out) return OATGPU_E_INVALID;
     memset(out, 0, sizeof *out);
     if (!c->audit_dev) return OATGPU_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    int rc = quiesce(c);
+    int rc = open_sync(c);
     if (rc) return rc;
     unsigned long long h[8];
     HIPCHK(c, hipMemcpy(h, c->audit_dev, sizeof h, hipMemcpyDeviceToHost));
