@@ -41,7 +41,8 @@ extern "C" {
 #define OATGPU_ABI_VERSION 9     /* 2: oatgpu_position grew (filter outputs), new entry points; 3: oatgpu_config.mog_restore_nmodes; 4: oatgpu_cvt_color, oatgpu_set_fusion, oatgpu_set_homography, oatgpu_profile.mog_frames; 5: oatgpu_track_sequence_dev_timed, oatgpu_track_enqueue_dev pairs frames only after oatgpu_set_fusion(2); 6: oatgpu_track_input_consumed_stream, oatgpu_track_stage, oatgpu_track_enqueue_staged; 7: oatgpu_track_stage_abort, oatgpu_set_early_blob, oatgpu_set_stage_copy, oatgpu_set_deferred / _fetch_frame / _fetch_position, a failed pipelined launch is fatal for its context; 8: oatgpu_track_sequence_dev_latency, oatgpu_device_open_retries, oatgpu_set_k1_workgroup, oatgpu_last_step_shape, oatgpu_early_blob_timeouts, a parked blob workgroup that times out switches early dispatch off for its context; 9: oatgpu_profile.dropped, every scratch set is allocated by oatgpu_create (an out-of-memory is reported there, never in the middle of a step); additive entries of 9 (detect them by symbol): oatgpu_undistort_map, oatgpu_set_undistort, oatgpu_undistort_filter, oatgpu_undistort_dev, oatgpu_set_track_undistort */
 /* Further additive entries of ABI 9 (detect them by symbol; no existing struct or entry changes): the marker sets --
  * oatgpu_set_markers, oatgpu_set_marker_window, oatgpu_track_markers_dev, oatgpu_track_markers, oatgpu_read_marker_mask,
- * with the structs oatgpu_marker and oatgpu_combined. */
+ * with the structs oatgpu_marker and oatgpu_combined; marker sets on the pipelined path -- oatgpu_set_marker_pipeline,
+ * oatgpu_track_collect_markers, oatgpu_track_markers_sequence_dev. */
 
 enum {
     OATGPU_OK = 0,
@@ -149,7 +150,11 @@ int oatgpu_default_config(oatgpu_config *cfg);
  * Device memory, all of it allocated HERE (an out-of-memory is OATGPU_E_NOMEM from oatgpu_create, never a failure in the middle of a
  * pipelined step): per camera stream and pixel 101 B of model + 150 B of back-half scratch (five sets of 30 B: three launch orders'
  * worth plus the repair set) + ring_depth / 8 B of threshold words + the staging frame; 1080p: 0.52 GB a stream, 4K: 2.1 GB.  The
- * host-frame path (oatgpu_track_enqueue / _stage) adds ring_depth staging frames on first use. */
+ * host-frame path (oatgpu_track_enqueue / _stage) adds ring_depth staging frames on first use.
+ * Marker sets add theirs in oatgpu_set_markers (30 B + n_markers / 2 B a pixel and stream) and, for the pipelined marker path, in
+ * oatgpu_set_marker_pipeline: per pixel, stream and MARKER 60 B of back-half scratch (TWO sets for M x n planes, one for each
+ * frame of a two-frame step; all marker work runs in order on one stream, so no more are needed) + ring_depth / 2 B of per-slot
+ * bit planes and taps -- 1.5 GB at 4K and 6.3 GB for 16 x 1080p with three markers and a ring of 4. */
 oatgpu_ctx *oatgpu_create(const oatgpu_config *cfg);   /* NULL on failure; oatgpu_last_error(NULL) */
 void oatgpu_destroy(oatgpu_ctx *ctx);
 const char *oatgpu_last_error(const oatgpu_ctx *ctx);
@@ -364,6 +369,32 @@ int oatgpu_track_markers(oatgpu_ctx *ctx, const uint8_t *const *frames_host, int
 /* oatgpu_read_mask for marker m's masks of the latest marker step: which = OATGPU_TAP_THRESHOLD (its inRange output),
  * _MORPH, _FINAL; rows*cols bytes {0,255}. */
 int oatgpu_read_marker_mask(oatgpu_ctx *ctx, int32_t stream, int32_t marker, int32_t which, uint8_t *out);
+/* Marker sets on the PIPELINED path (default off).  on = 1 is refused -- before anything has moved, with the synchronous step's
+ * messages -- when results are outstanding, markers are not configured, the context's own window is not the non-zero window, or
+ * oatgpu_set_kalman / oatgpu_set_homography is on.  It allocates everything the path needs (sizes: oatgpu_create's note): per
+ * ring slot the M bit planes and every marker's tmp / morph / fin planes, ring_depth host-mapped record sets (M x n_streams result
+ * records + n_streams combined records), events, and two back-half scratch sets for M x n_streams planes; an out-of-memory is
+ * OATGPU_E_NOMEM from THIS call and leaves an ordinary, working context.  on = 0 frees it all (refused while results are
+ * outstanding).
+ * While it is on, EVERY pipelined entry point (oatgpu_track_enqueue_dev, _enqueue, _stage + _enqueue_staged, the
+ * oatgpu_track_sequence_dev family) also queues the marker work of its frames -- the marker masks from the frames the per-pixel
+ * kernel read, ONE back half for all markers, the combiner -- with no host synchronisation and no copy back added;
+ * oatgpu_track_ready reports a frame set ready when its marker results are, too; oatgpu_track_collect returns the foreground
+ * result alone and retires the marker results with the slot; oatgpu_track_input_consumed[_stream] covers the marker kernel's
+ * reads of the frames.  Marker steps take the paired or the plain launch order, never the early one.  The
+ * synchronous oatgpu_track_markers[_dev] keep working between drained runs.  REFUSED while it is on (switch it off first):
+ * oatgpu_set_markers, enabling oatgpu_set_kalman / oatgpu_set_homography, an oatgpu_set_detector that moves the own window
+ * away from the non-zero window.  oatgpu_set_marker_window stays allowed (it drains first).
+ * oatgpu_read_marker_mask reads the planes of the frame set COLLECTED last -- pipelined or synchronous, whichever was later. */
+int oatgpu_set_marker_pipeline(oatgpu_ctx *ctx, int32_t on);
+/* oatgpu_track_collect for such a context: the oldest outstanding frame set, in enqueue order.  fg[n_streams] (or NULL),
+ * markers[s * n_markers + m], mean[n_streams] (or NULL) as in oatgpu_track_markers_dev.  OATGPU_E_INVALID when the switch is off,
+ * OATGPU_E_RING_EMPTY with nothing outstanding. */
+int oatgpu_track_collect_markers(oatgpu_ctx *ctx, oatgpu_position *fg, oatgpu_position *markers, oatgpu_combined *mean);
+/* The marker counterpart of oatgpu_track_sequence_dev (the library owns the frames' lifetime: two frames a launch by default):
+ * fg[t * n_streams + s] (or NULL), markers[(t * n_streams + s) * n_markers + m], mean[t * n_streams + s] (or NULL). */
+int oatgpu_track_markers_sequence_dev(oatgpu_ctx *ctx, const void *const *frames_dev, int32_t n_frames, double learning_rate,
+                                      oatgpu_position *fg, oatgpu_position *markers, oatgpu_combined *mean);
 
 /* Deferred completion of the stage-by-stage operators below (default off).  With on = 1 a frame filter (oatgpu_mog_filter,
  * _bsub_filter, _mask_filter, _thresh_filter, _undistort_filter, _bgr2hsv, _cvt_color) or a detector (oatgpu_detect_hsv / _thresh / _diff)

@@ -482,6 +482,34 @@ class HotPath(_Context):
                                                     self._mean))
         return self._markers_out()
 
+    def marker_pipeline(self, on=True):
+        """oatgpu_set_marker_pipeline: marker sets on the pipelined path.  While on, every enqueue form (enqueue, enqueue_dev,
+        stage + enqueue_staged, the sequence calls) also queues its frames' marker work; collect_markers() hands it out.
+        Needs markers configured, the non-zero own window, no Kalman filter / homography and nothing outstanding."""
+        self._chk(self.lib.oatgpu_set_marker_pipeline(self.ctx, 1 if on else 0))
+
+    def collect_markers(self):
+        """oatgpu_track_collect_markers: the oldest outstanding frame set -> (fg[n], markers[n][M], mean[n]) as track_markers."""
+        if not getattr(self, "n_markers", 0):              # (nothing configured: the library refuses, with its own words)
+            self._mpos, self._mean = (ffi.Position * 1)(), (ffi.Combined * self.n_streams)()
+        self._chk(self.lib.oatgpu_track_collect_markers(self.ctx, self._pos, self._mpos, self._mean))
+        if getattr(self, "_held", None):
+            self._held.pop(0)
+        return self._markers_out()
+
+    def track_markers_sequence_dev(self, dev_ptrs):
+        """A recorded sequence through the pipelined marker path in one call (oatgpu_track_markers_sequence_dev): dev_ptrs[t] =
+        device address of frame set t; returns one (fg[n], markers[n][M], mean[n]) per frame set."""
+        T, n, M = len(dev_ptrs), self.n_streams, getattr(self, "n_markers", 0)
+        arr = (C.c_void_p * max(T, 1))(*dev_ptrs)
+        fg = (ffi.Position * max(T * n, 1))()
+        mk = (ffi.Position * max(T * n * M, 1))()
+        mean = (ffi.Combined * max(T * n, 1))()
+        self._chk(self.lib.oatgpu_track_markers_sequence_dev(self.ctx, arr, T, self.learning_coeff_, fg, mk, mean))
+        return [([Position2D.from_c(fg[t * n + s]) for s in range(n)],
+                 [[Position2D.from_c(mk[(t * n + s) * M + m]) for m in range(M)] for s in range(n)],
+                 [Combined.from_c(mean[t * n + s]) for s in range(n)]) for t in range(T)]
+
     def read_marker_mask(self, marker, which=ffi.TAP_MORPH, stream=0):
         out = np.empty((self.rows, self.cols), np.uint8)
         self._chk(self.lib.oatgpu_read_marker_mask(self.ctx, int(stream), int(marker), which, ffi.u8(out)))

@@ -200,10 +200,17 @@ extern "C" __attribute__((visibility("default"))) int oatgpu_debug_rs_timing(lon
 #endif
 // blockIdx.z selects one of TWO frames (source mask, scratch set): the two frames of a two-frame step are scanned by ONE
 // launch (launch_blob_pair: a launch is ~4 us of host time, and small frames are bound by exactly that).
-template <bool ERODE>
+// TAB (the marker sets' one back half for all markers, launch_blob_table): the planes of the launch are M x n planes of one
+// geometry, and plane s takes its erode / dilate sizes from tab[s] -- a table in device memory, the index uniform over the
+// workgroup, so the values arrive by scalar loads.  Always the ERODE form: an erosion of size 1 is the identity (a plane
+// without erosion shares the launch with ones that have it; the LDS is sized by the launch's largest dilation), and the
+// mask after erode / dilate is always written to b.morph.
+template <bool ERODE, bool TAB = false>
 __global__ __launch_bounds__(64 * kRsWaves) void k_rowscan(Geom g, const u64 *src0, const u64 *src1, int ero_k, int dil_k, BlobBuffers b0,
-                                                        BlobBuffers b1, int first_stream, int clear_lds_ok, unsigned tag)
+                                                        BlobBuffers b1, int first_stream, int clear_lds_ok, unsigned tag,
+                                                        const BlobTab *__restrict__ tab)
 {
+    static_assert(ERODE || !TAB, "the table form erodes through LDS (size 1: the identity)");
     extern __shared__ u64 er[];
     constexpr int WAVES = kRsWaves, ROWS = kRsRows;
     const bool second = blockIdx.z != 0;
@@ -220,6 +227,7 @@ __global__ __launch_bounds__(64 * kRsWaves) void k_rowscan(Geom g, const u64 *sr
     const int wave = threadIdx.x >> 6;
     const int s = first_stream + blockIdx.y;
     const u64 *src_img = src_all + (size_t)s * (g.Palloc >> 6);
+    if (TAB) { ero_k = tab[s].ero; dil_k = tab[s].dil; }       // (ero >= 1; dil 0 or > 1: launch_blob_table's caller)
     const int dk = dil_k > 1 ? dil_k : 1;
     if (ERODE) {
         const int r0 = grp * ROWS - dk / 2;
@@ -374,9 +382,9 @@ static void launch_rowscan(const Geom &g, const u64 *const *src, int ero_k, int 
     const dim3 grid((g.H + kRsRows - 1) / kRsRows, n_streams, nf), block(64 * kRsWaves);
     if (ero_k > 1)
         hipLaunchKernelGGL(k_rowscan<true>, grid, block, rowscan_lds_bytes(g, dil_k), st, g, src[0], src[k], ero_k, dil_k, b[0], b[k],
-                           first_stream, clear, tag);
+                           first_stream, clear, tag, nullptr);
     else
-        hipLaunchKernelGGL(k_rowscan<false>, grid, block, 0, st, g, src[0], src[k], 0, dil_k, b[0], b[k], first_stream, clear, tag);
+        hipLaunchKernelGGL(k_rowscan<false>, grid, block, 0, st, g, src[0], src[k], 0, dil_k, b[0], b[k], first_stream, clear, tag, nullptr);
 }
 
 // ------------------------------------------------------------ union-find -----
@@ -515,8 +523,10 @@ __device__ __forceinline__ int uf_root(const int *parent, int i)
 // contour list with a strict '>' -- and becomes the stream's result record in host-mapped memory.
 constexpr int kGreenChunks = 4;
 constexpr int kGreenBlock = 1024;          // big workgroups: every workgroup costs one same-address arrival atomic (~12 ns each, serialised)
+// TAB: the area window of plane s comes from tab[s] (k_rowscan)
+template <bool TAB = false>
 __global__ __launch_bounds__(kGreenBlock) void k_green_select(Geom g, BlobBuffers b, double min_area, double max_area,
-                                                      ResultRec *results, int first_stream)
+                                                      ResultRec *results, int first_stream, const BlobTab *__restrict__ tab)
 {
     __shared__ int is_last;
     __shared__ unsigned long long red[kGreenBlock];
@@ -528,6 +538,7 @@ __global__ __launch_bounds__(kGreenBlock) void k_green_select(Geom g, BlobBuffer
     const u64 chunk_bits = (kGreenChunks == 1 ? ~0ull : ((1ull << (64 / kGreenChunks)) - 1ull)) << ((tt % kGreenChunks) * (64 / kGreenChunks));
     const int s = first_stream + blockIdx.y;
     if (b.lds_ok[s]) return;                       // k_blob_lds took this frame (uniform over the workgroup)
+    if (TAB) { min_area = tab[s].min_area; max_area = tab[s].max_area; }
     const size_t soff = (size_t)s * (g.Palloc >> 6);
     const u64 *fin = b.fin + soff;
     const u64 *trans = b.trans + soff;
@@ -769,9 +780,11 @@ template <typename T> __device__ __forceinline__ T ld_pub(const T *p)
 }
 // blockIdx.z selects one of TWO frames (scratch set, result record, ticket): the two frames of a two-frame step park
 // their workgroups with ONE launch (launch_blob_tail2) -- two launches on one stream would run one after the other.
+// TAB: the area window of plane s comes from tab[s] (k_rowscan)
+template <bool TAB = false>
 __global__ __launch_bounds__(kLdsBlock) void k_blob_lds(Geom g, BlobBuffers b0, BlobBuffers b1, double min_area, double max_area,
                                                         ResultRec *results0, ResultRec *results1, int first_stream, int spec,
-                                                        unsigned ticket0, unsigned ticket1)
+                                                        unsigned ticket0, unsigned ticket1, const BlobTab *__restrict__ tab)
 {
     __shared__ int wait_failed;
     const bool second = blockIdx.z != 0;
@@ -793,6 +806,7 @@ __global__ __launch_bounds__(kLdsBlock) void k_blob_lds(Geom g, BlobBuffers b0, 
 
     const int s = first_stream + blockIdx.y;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (TAB) { min_area = tab[s].min_area; max_area = tab[s].max_area; }
     const size_t soff = (size_t)s * (g.Palloc >> 6);
     const u64 *fin = b.fin + soff;
     const u64 *trans = b.trans + soff;
@@ -1229,16 +1243,16 @@ void launch_blob(const Geom &g, const BlobBuffers &b, const u64 *src_bits, int e
     const int clear = mode == kBlobGlobal || !lds_able;          // nobody else resets lds_ok then
     launch_rowscan(g, &src_bits, ero_k, dil_k, &b, 1, first_stream, n_streams, clear, st);
     if (lds_able && mode != kBlobGlobal)
-        hipLaunchKernelGGL(k_blob_lds, dim3(1, n_streams), dim3(kLdsBlock), 0, st, g, b, b, min_area, max_area, results, results,
-                           first_stream, mode == kBlobSpec ? 1 : 0, 0u, 0u);
+        hipLaunchKernelGGL(k_blob_lds<false>, dim3(1, n_streams), dim3(kLdsBlock), 0, st, g, b, b, min_area, max_area, results, results,
+                           first_stream, mode == kBlobSpec ? 1 : 0, 0u, 0u, nullptr);
     if (mode == kBlobSpec) return;
     if (g.H > 1)
         hipLaunchKernelGGL(k_merge, dim3(((g.H - 1) * g.words + 255) / 256, n_streams), dim3(256), 0, st, g, b,
                            first_stream);
     // (grid of at least one workgroup even for H <= 2: the last-arriver logic writes the result)
     const int nw = (g.H > 2 ? (g.H - 2) * g.words : 1) * kGreenChunks;
-    hipLaunchKernelGGL(k_green_select, dim3((nw + kGreenBlock - 1) / kGreenBlock, n_streams), dim3(kGreenBlock), 0, st, g, b,
-                       min_area, max_area, results, first_stream);
+    hipLaunchKernelGGL(k_green_select<false>, dim3((nw + kGreenBlock - 1) / kGreenBlock, n_streams), dim3(kGreenBlock), 0, st, g, b,
+                       min_area, max_area, results, first_stream, nullptr);
 }
 
 // The frame's ticket comes from a kernel of its own behind the row scan: the stream's order and the row scan's
@@ -1264,8 +1278,8 @@ void launch_blob_pair(const Geom &g, const BlobBuffers *b, const u64 *const *src
                       double max_area, ResultRec *const *results, int n_streams, hipStream_t st)
 {
     launch_rowscan(g, src, ero_k, dil_k, b, 2, 0, n_streams, 0, st);
-    hipLaunchKernelGGL(k_blob_lds, dim3(1, n_streams, 2), dim3(kLdsBlock), 0, st, g, b[0], b[1], min_area, max_area, results[0],
-                       results[1], 0, 1, 0u, 0u);
+    hipLaunchKernelGGL(k_blob_lds<false>, dim3(1, n_streams, 2), dim3(kLdsBlock), 0, st, g, b[0], b[1], min_area, max_area, results[0],
+                       results[1], 0, 1, 0u, 0u, nullptr);
 }
 
 // The early blob workgroups of the nf (1 or 2) frames of a step in ONE launch: frame i reads scratch set b[i], writes
@@ -1274,8 +1288,30 @@ void launch_blob_tail2(const Geom &g, const BlobBuffers *b, double min_area, dou
                        int n_streams, const unsigned *ticket, int nf, hipStream_t st)
 {
     const int k = nf > 1 ? 1 : 0;
-    hipLaunchKernelGGL(k_blob_lds, dim3(1, n_streams, nf), dim3(kLdsBlock), 0, st, g, b[0], b[k], min_area, max_area, results[0],
-                       results[k], 0, 1, ticket[0], ticket[k]);
+    hipLaunchKernelGGL(k_blob_lds<false>, dim3(1, n_streams, nf), dim3(kLdsBlock), 0, st, g, b[0], b[k], min_area, max_area, results[0],
+                       results[k], 0, 1, ticket[0], ticket[k], nullptr);
+}
+
+// The marker sets' back half: the n_planes (= M x n) planes of each of the nf (1 or 2) frames of a step in ONE row-scan launch
+// and ONE k_blob_lds launch (grid y = plane, z = frame), every plane with the erode / dilate / area of its table entry; the
+// global kernels are queued behind them (a launch each a frame) and stand down on every plane the LDS kernel took, as in
+// kBlobFull.  The number of launches does not depend on M.  Frame i reads src[i] ([n_planes][Palloc/64]) and scratch set b[i]
+// (made for n_planes planes), writes results[i][n_planes].  LDS-able geometries only (launch_blob), and
+// rowscan_lds_bytes(g, max_dil) <= kRowscanLdsMax, max_dil the largest dilation in the table: the caller checks both.
+void launch_blob_table(const Geom &g, const BlobBuffers *b, const u64 *const *src, const BlobTab *tab, int max_dil,
+                       ResultRec *const *results, int n_planes, int nf, hipStream_t st)
+{
+    const int k = nf > 1 ? 1 : 0;
+    hipLaunchKernelGGL((k_rowscan<true, true>), dim3((g.H + kRsRows - 1) / kRsRows, n_planes, nf), dim3(64 * kRsWaves),
+                       rowscan_lds_bytes(g, max_dil), st, g, src[0], src[k], 0, 0, b[0], b[k], 0, 0, 0u, tab);
+    hipLaunchKernelGGL(k_blob_lds<true>, dim3(1, n_planes, nf), dim3(kLdsBlock), 0, st, g, b[0], b[k], 0.0, 0.0, results[0],
+                       results[k], 0, 0, 0u, 0u, tab);
+    const int nw = (g.H - 2) * g.words * kGreenChunks;
+    for (int i = 0; i < nf; ++i) {
+        hipLaunchKernelGGL(k_merge, dim3(((g.H - 1) * g.words + 255) / 256, n_planes), dim3(256), 0, st, g, b[i], 0);
+        hipLaunchKernelGGL(k_green_select<true>, dim3((nw + kGreenBlock - 1) / kGreenBlock, n_planes), dim3(kGreenBlock), 0, st, g,
+                           b[i], 0.0, 0.0, results[i], 0, tab);
+    }
 }
 
 }  // namespace oatgpu

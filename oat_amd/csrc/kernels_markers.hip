@@ -27,14 +27,20 @@ static_assert(1024 % (kWavePx * kWordsPerWave * kWavesPerGroup) == 0, "Palloc is
 
 }  // namespace
 
-// grid (Palloc / 1024, n_streams), 256 threads; wave w of workgroup b takes mask words (4 b + w) * 4 .. + 3 of stream
-// blockIdx.y.  Lane l of word i owns pixel 64 * word + l.  planes: [M][n_streams][Palloc / 64].
+// grid (Palloc / 1024, n_streams, frames of the step), 256 threads; wave w of workgroup b takes mask words (4 b + w) * 4 .. + 3
+// of stream blockIdx.y.  Lane l of word i owns pixel 64 * word + l.  planes: [M][n_streams][Palloc / 64].  blockIdx.z selects
+// one of the TWO frames of a paired step, each with its own frames, Z plane and output planes (as k_undistort_frames does).
 template <int CH>
-__global__ __launch_bounds__(kWavePx *kWavesPerGroup) void k_marker_bits(Geom g, const uint8_t *__restrict__ frames,
-                                                                        const u64 *__restrict__ zbits,
+__global__ __launch_bounds__(kWavePx *kWavesPerGroup) void k_marker_bits(Geom g, const uint8_t *__restrict__ frames0,
+                                                                        const uint8_t *__restrict__ frames1,
+                                                                        const u64 *__restrict__ zbits0, const u64 *__restrict__ zbits1,
                                                                         const RangeParams *__restrict__ win, int M,
-                                                                        u64 *__restrict__ planes)
+                                                                        u64 *__restrict__ planes0, u64 *__restrict__ planes1)
 {
+    const bool second = blockIdx.z != 0;
+    const uint8_t *__restrict__ frames = second ? frames1 : frames0;
+    const u64 *__restrict__ zbits = second ? zbits1 : zbits0;
+    u64 *__restrict__ planes = second ? planes1 : planes0;
     const unsigned s = blockIdx.y, n = gridDim.y;
     const unsigned lane = threadIdx.x & 63u;
     const unsigned nwords = (unsigned)g.Palloc >> 6, pwords = (unsigned)g.P >> 6;     // P is a multiple of 64 (Wp is)
@@ -92,13 +98,21 @@ __global__ __launch_bounds__(kWavePx *kWavesPerGroup) void k_marker_bits(Geom g,
         planes[((size_t)mi * n + s) * nwords + w0 + wi] = mine;
 }
 
+void launch_marker_bits_frames(const Geom &g, const uint8_t *const *frames, int channels, const u64 *const *zbits,
+                               const RangeParams *win, int M, u64 *const *planes, int n_streams, int nf, hipStream_t st)
+{
+    const int k = nf > 1 ? 1 : 0;
+    const dim3 grid((unsigned)(g.Palloc / (kWavePx * kWordsPerWave * kWavesPerGroup)), (unsigned)n_streams, (unsigned)nf);
+    const dim3 block(kWavePx * kWavesPerGroup);
+    if (channels == 3)
+        hipLaunchKernelGGL(k_marker_bits<3>, grid, block, 0, st, g, frames[0], frames[k], zbits[0], zbits[k], win, M, planes[0], planes[k]);
+    else
+        hipLaunchKernelGGL(k_marker_bits<1>, grid, block, 0, st, g, frames[0], frames[k], zbits[0], zbits[k], win, M, planes[0], planes[k]);
+}
 void launch_marker_bits(const Geom &g, const uint8_t *frames, int channels, const u64 *zbits, const RangeParams *win, int M,
                         u64 *planes, int n_streams, hipStream_t st)
 {
-    const dim3 grid((unsigned)(g.Palloc / (kWavePx * kWordsPerWave * kWavesPerGroup)), (unsigned)n_streams);
-    const dim3 block(kWavePx * kWavesPerGroup);
-    if (channels == 3) hipLaunchKernelGGL(k_marker_bits<3>, grid, block, 0, st, g, frames, zbits, win, M, planes);
-    else hipLaunchKernelGGL(k_marker_bits<1>, grid, block, 0, st, g, frames, zbits, win, M, planes);
+    launch_marker_bits_frames(g, &frames, channels, &zbits, win, M, &planes, n_streams, 1, st);
 }
 
 // MeanPosition::combine (MeanPosition.cpp:60-118), one lane per camera stream, fp64, every product and sum rounded on its own
@@ -107,11 +121,30 @@ void launch_marker_bits(const Geom &g, const uint8_t *frames, int channels, cons
 // the heading takes pos_m - pos_anchor only while the running position_valid is still set (and loses heading_valid
 // otherwise); the sum is divided by its length even when that is 0 (one marker, coincident markers: NaN, heading_valid 1).
 // Detectors never set a heading or a velocity, so without an anchor heading_valid is 0, and velocity_valid always is.
-__global__ __launch_bounds__(64) void k_marker_combine(const ResultRec *__restrict__ results, int M, int anchor, int n_streams,
-                                                       MarkerCombined *__restrict__ out)
+// blockIdx.y selects one of the TWO frames of a paired step.  copy (nullptr: none): where the lane also leaves its stream's M
+// result records as they are -- the pipelined path's host-mapped record set, so that a frame set's marker results and its
+// combined record reach the host by this kernel's stores alone.
+__global__ __launch_bounds__(64) void k_marker_combine(const ResultRec *__restrict__ results0, const ResultRec *__restrict__ results1,
+                                                       int M, int anchor, int n_streams, MarkerCombined *__restrict__ out0,
+                                                       MarkerCombined *__restrict__ out1, ResultRec *__restrict__ copy0,
+                                                       ResultRec *__restrict__ copy1)
 {
+    const bool second = blockIdx.y != 0;
+    const ResultRec *__restrict__ results = second ? results1 : results0;
+    MarkerCombined *__restrict__ out = second ? out1 : out0;
+    ResultRec *__restrict__ copy = second ? copy1 : copy0;
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_streams) return;
+    if (copy) {
+        static_assert(sizeof(ResultRec) % 8 == 0, "a record is copied as 64-bit words");
+        for (int m = 0; m < M; ++m) {
+            const u64 *src = reinterpret_cast<const u64 *>(results + (size_t)m * n_streams + s);
+            u64 *dst = reinterpret_cast<u64 *>(copy + (size_t)m * n_streams + s);
+#pragma unroll
+            for (int i = 0; i < (int)(sizeof(ResultRec) / 8); ++i)       // 64-bit stores (nothing wider)
+                __hip_atomic_store(dst + i, src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
     // posidet's centroid of marker m, exactly as the host epilogue (to_position) and k_kalman derive it from the integer sums;
     // an invalid Position2D keeps its initial (0, 0)
     auto centroid = [&](int m, double &x, double &y) -> bool {
@@ -166,9 +199,17 @@ __global__ __launch_bounds__(64) void k_marker_combine(const ResultRec *__restri
     put(5, (u64)__double_as_longlong(hy));
 }
 
+void launch_marker_combine_frames(const ResultRec *const *results, int M, int anchor, int n_streams, MarkerCombined *const *out,
+                                  ResultRec *const *copy, int nf, hipStream_t st)
+{
+    const int k = nf > 1 ? 1 : 0;
+    hipLaunchKernelGGL(k_marker_combine, dim3((n_streams + 63) / 64, nf), dim3(64), 0, st, results[0], results[k], M, anchor,
+                       n_streams, out[0], out[k], copy[0], copy[k]);
+}
 void launch_marker_combine(const ResultRec *results, int M, int anchor, int n_streams, MarkerCombined *out, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_marker_combine, dim3((n_streams + 63) / 64), dim3(64), 0, st, results, M, anchor, n_streams, out);
+    ResultRec *const none = nullptr;
+    launch_marker_combine_frames(&results, M, anchor, n_streams, &out, &none, 1, st);
 }
 
 }  // namespace oatgpu

@@ -218,6 +218,25 @@ struct oatgpu_ctx {
     ResultRec *mk_res = nullptr;               // device: [M][n] result records, then [n] MarkerCombined
     void *mk_res_host = nullptr;               // page-locked mirror: one copy back a step
     std::vector<const u64 *> mk_tap_morph;     // [M] where marker m's mask after erode / dilate is
+    // the pipelined marker path (oatgpu_set_marker_pipeline): everything below is made by the switch, never inside a step.
+    // A step's marker work: k_marker_bits on stream A right behind its per-pixel kernel (launch_marker_work), the back half of
+    // all M x n planes and the combiner on B2 (a lone frame: on A), results into the slot's host-mapped record set.
+    bool mkp_on = false;
+    bool mkp_table = false;                    // the one-launch back half takes this geometry and these markers (else: marker by marker)
+    int mkp_max_dil = 0;                       // largest dilation of the set: the row scan's LDS
+    u64 *mkp_planes = nullptr;                 // [ring][M][n][Palloc/64] k_marker_bits' output, per ring slot
+    u64 *mkp_masks = nullptr;                  // [ring][3][M][n][Palloc/64] the slot's tmp / morph / fin planes of every marker (the taps)
+    BlobBuffers mkp_bb[2]{};                   // the rest of a back-half scratch set for M x n planes, one for each frame of a step
+    BlobTab *mkp_tab = nullptr;                // [M][n] device table of the one-launch back half
+    ResultRec *mkp_res = nullptr;              // device: [2][M][n] the step's result records, read by k_marker_combine
+    ResultRec *mkp_rec_host = nullptr;         // host-mapped: [ring] sets of M x n ResultRec + n MarkerCombined, written by k_marker_combine
+    ResultRec *mkp_rec_dev = nullptr;          // ... its device alias
+    std::vector<hipEvent_t> mkp_ev;            // [ring] the marker work whose last frame sits in this slot is done
+    std::vector<int> mkp_ev_of;                // [ring] slot -> the slot whose event covers its marker results
+    std::vector<const u64 *> mkp_tap_morph;    // [ring][M] where the MORPH tap of marker m of that slot is
+    hipEvent_t mkp_bits_ev = nullptr;          // stream A: the step's k_marker_bits has finished
+    int mk_last_slot = -1;                     // ring slot of the frame set collected last on the pipelined path; -1: the synchronous step was later
+    size_t mkp_set_bytes() const { return (size_t)mk_n * cfg.n_streams * sizeof(ResultRec) + (size_t)cfg.n_streams * sizeof(MarkerCombined); }
 };
 
 static int fail(oatgpu_ctx *c, int code, const char *fmt, ...)
@@ -241,6 +260,7 @@ static int fail(oatgpu_ctx *c, int code, const char *fmt, ...)
     } while (0)
 
 static int quiesce(oatgpu_ctx *c);
+static bool own_window_is_nonzero(const oatgpu_config &k);
 static int flush_pending(oatgpu_ctx *c);
 static int repair_outstanding(oatgpu_ctx *c);
 
@@ -435,8 +455,23 @@ static void free_scratch(BlobBuffers &b)      // (thr and nopark are the context
     hipFree(b.ready);
     b = BlobBuffers{};
 }
+static void free_marker_pipeline(oatgpu_ctx *c)
+{
+    hipFree(c->mkp_planes); hipFree(c->mkp_masks); hipFree(c->mkp_tab); hipFree(c->mkp_res);
+    if (c->mkp_rec_host) hipHostFree(c->mkp_rec_host);
+    c->mkp_planes = nullptr; c->mkp_masks = nullptr; c->mkp_tab = nullptr; c->mkp_res = nullptr;
+    c->mkp_rec_host = nullptr; c->mkp_rec_dev = nullptr;
+    for (auto &b : c->mkp_bb) free_scratch(b);
+    for (auto e : c->mkp_ev) hipEventDestroy(e);
+    c->mkp_ev.clear(); c->mkp_ev_of.clear(); c->mkp_tap_morph.clear();
+    if (c->mkp_bits_ev) hipEventDestroy(c->mkp_bits_ev);
+    c->mkp_bits_ev = nullptr;
+    c->mkp_on = false;
+    c->mk_last_slot = -1;
+}
 static void free_markers(oatgpu_ctx *c)
 {
+    free_marker_pipeline(c);
     hipFree(c->mk_win); hipFree(c->mk_planes); hipFree(c->mk_masks); hipFree(c->mk_res);
     if (c->mk_res_host) hipHostFree(c->mk_res_host);
     c->mk_win = nullptr; c->mk_planes = nullptr; c->mk_masks = nullptr; c->mk_res = nullptr; c->mk_res_host = nullptr;
@@ -510,10 +545,10 @@ extern "C" int oatgpu_device_open_retries(void) { return g_open_retries.load(); 
 // the paired layout, and the repair set -- 150 bytes a pixel and stream in all.  An allocation in the middle of a pipelined
 // step would stall a camera-paced caller for as long as hipMalloc takes, and its failure would come after the model had
 // moved.
-static bool alloc_scratch(oatgpu_ctx *c, BlobBuffers &b)
+static bool alloc_scratch(oatgpu_ctx *c, BlobBuffers &b, size_t planes = 0)     // planes: how many (0: one a camera stream)
 {
     const Geom &g = c->g;
-    const size_t n = c->cfg.n_streams, PA = g.Palloc, NW = PA / 64;
+    const size_t n = planes ? planes : (size_t)c->cfg.n_streams, PA = g.Palloc, NW = PA / 64;
     bool ok = true;
     auto A = [&](void **p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) ok = false; };
     b.thr = c->bb[0].thr;
@@ -788,6 +823,8 @@ extern "C" int oatgpu_set_detector(oatgpu_ctx *c, int32_t h_lo, int32_t h_hi, in
     k.erode = erode; k.dilate = dilate; k.min_area = min_area; k.max_area = max_area;
     int rc = check_detector(c, detector_of(k), k.blur);
     if (rc) return rc;
+    if (c->mkp_on && !own_window_is_nonzero(k))
+        return fail(c, OATGPU_E_INVALID, "the marker pipeline is on and needs the non-zero window: oatgpu_set_marker_pipeline(0) first");
     rc = quiesce(c);
     if (rc) return rc;
     c->cfg = k;
@@ -951,6 +988,8 @@ extern "C" int oatgpu_set_kalman(oatgpu_ctx *c, int32_t enable, double dt, doubl
     if (!c) return OATGPU_E_INVALID;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (c->ring_count) return fail(c, OATGPU_E_INVALID, "set_kalman while enqueued results are outstanding");
+    if (enable && c->mkp_on)
+        return fail(c, OATGPU_E_INVALID, "the marker pipeline is on and does not take the position filter: oatgpu_set_marker_pipeline(0) first");
     int rc = quiesce(c);
     if (rc) return rc;
     if (!enable) { c->kal_on = false; return OATGPU_OK; }
@@ -997,6 +1036,8 @@ extern "C" int oatgpu_set_homography(oatgpu_ctx *c, int32_t enable, const double
     if (!c) return OATGPU_E_INVALID;
     if (enable && !h9) return fail(c, OATGPU_E_INVALID, "null homography");
     if (c->ring_count) return fail(c, OATGPU_E_INVALID, "set_homography while enqueued results are outstanding");
+    if (enable && c->mkp_on)
+        return fail(c, OATGPU_E_INVALID, "the marker pipeline is on and does not take a homography: oatgpu_set_marker_pipeline(0) first");
     c->homo_on = enable != 0;
     if (enable) for (int i = 0; i < 9; ++i) c->homo[i] = h9[i];
     return OATGPU_OK;
@@ -1661,8 +1702,10 @@ static StepPlan plan_step(const oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, in
     // ... and only while frames go through the LDS kernel alone (kBlobSpec): a step in the full launch sequence -- the position
     // filter is on, or a frame was declined a moment ago -- takes the plain order (the switch drains the B streams)
     const bool early_wanted = c->early_blob < 0 ? c->cfg.n_streams <= 3 : c->early_blob != 0;   // (r06a / r06e: 2 x 1080p 64.8 k -> 70.3 k fps, 3 x: 69.3 k -> 72-74 k, 4 x: 73.0 k -> 65-72 k)
+    // ... and not with the marker pipeline on: its back halves go down B2, where the parked workgroups sit, and nothing may
+    // be queued on B2 in front of a row scan they wait for -- marker steps take the paired or the plain order
     p.early = early_wanted && !(lone && c->lone_plain) && !c->early_off && c->lds_spec && !c->kal_on && !j[0].ready && !p.share_b &&
-              lds_geom && step_px >= c->early_min_px;
+              lds_geom && step_px >= c->early_min_px && !c->mkp_on;
     // Threads a K1 workgroup (kernels_mog.hip, k_mog_fused): one wave a workgroup keeps every wave slot filled (K1 -3.5 % on
     // an everyday 4K model, -5.5 % on a dense one) and starves the back half's workgroups of slots.  Taken where that
     // does not come back as a lower frame rate: steps whose blob workgroup is already resident (early), and dense models
@@ -1772,6 +1815,7 @@ static int launch_front(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, co
 // in the frame's own set after a switch to the plain order (the decline itself causes one) wrote set 1 from B0 while a plain
 // frame used it from B1 (found by tools/fuzz.py --seed 11, configuration 301: profiles/r07_fuzz_1500.txt).  Set 4 is touched
 // by repairs only, and only from B2.
+static int launch_marker_work(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, const StepPlan &plan);
 static constexpr int kRepairSet = oatgpu_ctx::kSets - 1, kRepairStream = oatgpu_ctx::kNB - 1;
 static void mark_speculative(oatgpu_ctx *c, int slot)
 {
@@ -1898,6 +1942,72 @@ static int launch_back_plain(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int n
     return OATGPU_OK;
 }
 
+// The marker work of a step (oatgpu_set_marker_pipeline), queued with the step on every launch order.  It depends on the
+// step's per-pixel kernel and on nothing of the foreground back half:
+//   stream A, right behind the per-pixel launches: k_marker_bits, ONE launch for the step's frames (grid z = frame), on the
+//     frames K1 read and the slots' Z planes, into the slots' own bit planes.  On A because everything that orders itself
+//     against K1's reads then covers this kernel's as well, with nothing added: oatgpu_track_input_consumed's event, the next
+//     step's remap into the two undistort buffers, the reuse of a host-frame staging slot;
+//   stream B2 behind an event on A (a lone frame: stream A itself, no cross-queue dependency): the back half of all M x n
+//     planes of the step's frames -- launch_blob_table, whose launch count does not depend on M; marker by marker where the
+//     row scan's LDS cannot take the set (mkp_table) -- then k_marker_combine, ONE launch, which writes the frame sets' marker
+//     records and combined records into the slots' host-mapped record sets; then the slots' marker event.
+// ONE scratch set a frame of the step serves every step: the marker work of consecutive steps runs in order on B2, and a
+// lone frame is launched with nothing outstanding -- every earlier frame set was collected, its marker event waited for.
+static int launch_marker_work(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, const StepPlan &plan)
+{
+    const Geom &g = c->g;
+    const int n = c->cfg.n_streams, M = c->mk_n;
+    const size_t NW = (size_t)g.Palloc / 64, planes = (size_t)M * n;
+    hipStream_t A = c->stream, S = plan.inline_back ? A : c->stream_b[oatgpu_ctx::kNB - 1];
+    const uint8_t *fr[2] = {};
+    const u64 *z[2] = {}, *src[2] = {};
+    u64 *bits[2] = {};
+    BlobBuffers bbs[2];
+    const ResultRec *res_c[2] = {};
+    ResultRec *res[2] = {}, *rec[2] = {};
+    MarkerCombined *comb[2] = {};
+    for (int i = 0; i < nj; ++i) {
+        const int slot = j[i].slot;
+        fr[i] = c->ud_track ? c->ud_frames[i] : (const uint8_t *)j[i].frames;
+        z[i] = thr_buf(c, slot);
+        src[i] = bits[i] = c->mkp_planes + (size_t)slot * planes * NW;
+        u64 *own = c->mkp_masks + (size_t)slot * 3 * planes * NW;
+        bbs[i] = c->mkp_bb[i];
+        bbs[i].tmp = own; bbs[i].morph = own + planes * NW; bbs[i].fin = own + 2 * planes * NW;
+        res_c[i] = res[i] = c->mkp_res + (size_t)i * planes;
+        rec[i] = (ResultRec *)((char *)c->mkp_rec_dev + (size_t)slot * c->mkp_set_bytes());
+        comb[i] = (MarkerCombined *)(rec[i] + planes);
+        c->mkp_ev_of[(size_t)slot] = j[nj - 1].slot;
+    }
+    launch_marker_bits_frames(g, fr, c->cfg.channels, z, c->mk_win, M, bits, n, nj, A);
+    HIPCHK(c, hipGetLastError());
+    if (S != A) {
+        HIPCHK(c, hipEventRecord(c->mkp_bits_ev, A));
+        HIPCHK(c, hipStreamWaitEvent(S, c->mkp_bits_ev, 0));
+        c->b_used[oatgpu_ctx::kNB - 1] = true;
+    }
+    if (c->mkp_table) {
+        launch_blob_table(g, bbs, src, c->mkp_tab, c->mkp_max_dil, res, (int)planes, nj, S);
+        for (int i = 0; i < nj; ++i)
+            for (int m = 0; m < M; ++m) c->mkp_tap_morph[(size_t)j[i].slot * M + m] = bbs[i].morph + (size_t)m * n * NW;
+    } else {
+        for (int i = 0; i < nj; ++i)
+            for (int m = 0; m < M; ++m) {                     // marker m's planes are "streams" m n .. m n + n - 1 of the set
+                const oatgpu_marker &k = c->mk_def[(size_t)m];
+                const MorphPlan mp = plan_morph(g, k.erode, k.dilate);
+                const MorphIssued mi = issue_morph(g, mp, bbs[i], src[i], m * n, n, S);
+                c->mkp_tap_morph[(size_t)j[i].slot * M + m] = mi.tap + (size_t)m * n * NW;
+                launch_blob(g, bbs[i], mi.src, mi.ero, mp.dil, k.min_area, k.max_area, res[i], m * n, n, S, kBlobFull);
+            }
+    }
+    HIPCHK(c, hipGetLastError());
+    launch_marker_combine_frames(res_c, M, c->mk_anchor, n, comb, rec, nj, S);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->mkp_ev[(size_t)j[nj - 1].slot], S));
+    return OATGPU_OK;
+}
+
 // The kernels of one frame (nj == 1) or of two consecutive frames (nj == 2: K1 once for both where the streams'
 // learning-rate schedules allow, then the back halves in the layout plan_step picked).
 static int launch_jobs(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, bool lone = false)
@@ -1923,9 +2033,10 @@ static int launch_jobs(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, boo
     if (c->last_early >= 0 && c->last_early != path)          // the paths use the scratch sets from different streams
         HIPCHK(c, drain_b(c));
     c->last_early = path;
-    if (plan.paired) return launch_back_paired(c, j, plan, ps);
-    if (plan.early) return launch_back_early(c, j, nj, plan, ps);
-    return launch_back_plain(c, j, nj, plan, ps);
+    const int brc = plan.paired ? launch_back_paired(c, j, plan, ps) : plan.early ? launch_back_early(c, j, nj, plan, ps)
+                                                                                  : launch_back_plain(c, j, nj, plan, ps);
+    if (brc || !c->mkp_on) return brc;
+    return launch_marker_work(c, j, nj, plan);
 }
 
 // launch what oatgpu_track_enqueue[_dev] only registered
@@ -2062,9 +2173,11 @@ static hipError_t wait_short(hipEvent_t e)
     }
 }
 
-extern "C" int oatgpu_track_collect(oatgpu_ctx *c, oatgpu_position *out)
+// out: the foreground result (nullptr: not wanted); markers / mean: the marker records of the frame set, [n][M] and [n], from the
+// slot's host-mapped record set (nullptr: not wanted).  With the marker pipeline on the slot's marker work is waited for in
+// any case: the slot's planes and records are free for the next frame set when this returns.
+static int collect_frame(oatgpu_ctx *c, oatgpu_position *out, oatgpu_position *markers, oatgpu_combined *mean)
 {
-    if (!c || !out) return fail(c, OATGPU_E_INVALID, "null argument");
     if (c->ring_count == 0) return fail(c, OATGPU_E_RING_EMPTY, "nothing outstanding");
     const int slot = col_slot(c);
     if (c->pend_valid && c->pend.slot == slot) {          // the frame wanted is still only registered: launch it alone
@@ -2092,7 +2205,17 @@ extern "C" int oatgpu_track_collect(oatgpu_ctx *c, oatgpu_position *out)
             c->lds_spec = false;
         }
     }
-    for (int s = 0; s < c->cfg.n_streams; ++s) {
+    if (c->mkp_on) {
+        HIPCHK(c, hipEventSynchronize(c->mkp_ev[(size_t)c->mkp_ev_of[(size_t)slot]]));
+        const int n = c->cfg.n_streams, M = c->mk_n;
+        const ResultRec *mr = (const ResultRec *)((const char *)c->mkp_rec_host + (size_t)slot * c->mkp_set_bytes());
+        if (markers)
+            for (int s = 0; s < n; ++s)
+                for (int m = 0; m < M; ++m) to_position(mr[(size_t)m * n + s], &markers[(size_t)s * M + m]);
+        if (mean) memcpy(mean, mr + (size_t)M * n, (size_t)n * sizeof(oatgpu_combined));
+        c->mk_last_slot = slot;
+    }
+    for (int s = 0; out && s < c->cfg.n_streams; ++s) {
         to_position(r[s], &out[s]);
         if (c->slots[slot].filtered) apply_kalman(r[s], &out[s]);
         if (c->homo_on) apply_homography(c, &out[s]);
@@ -2100,6 +2223,19 @@ extern "C" int oatgpu_track_collect(oatgpu_ctx *c, oatgpu_position *out)
     c->col_total++;
     c->ring_count--;
     return OATGPU_OK;
+}
+
+extern "C" int oatgpu_track_collect(oatgpu_ctx *c, oatgpu_position *out)
+{
+    if (!c || !out) return fail(c, OATGPU_E_INVALID, "null argument");
+    return collect_frame(c, out, nullptr, nullptr);
+}
+
+extern "C" int oatgpu_track_collect_markers(oatgpu_ctx *c, oatgpu_position *fg, oatgpu_position *markers, oatgpu_combined *mean)
+{
+    if (!c || !markers) return fail(c, OATGPU_E_INVALID, "null argument");
+    if (!c->mkp_on) return fail(c, OATGPU_E_INVALID, "the marker pipeline is off (oatgpu_set_marker_pipeline)");
+    return collect_frame(c, fg, markers, mean);
 }
 
 extern "C" int oatgpu_track_input_consumed(oatgpu_ctx *c)
@@ -2152,19 +2288,26 @@ extern "C" int oatgpu_track_ready(oatgpu_ctx *c)
         const int rc = launch_repair(c, slot);                    // global kernels -- start them, not ready yet
         return rc ? rc : 0;
     }
+    if (c->mkp_on) {                                              // ... and the frame set's marker results
+        const hipError_t me = hipEventQuery(c->mkp_ev[(size_t)c->mkp_ev_of[(size_t)slot]]);
+        if (me == hipErrorNotReady) return 0;
+        if (me != hipSuccess) return fail(c, OATGPU_E_HIP, "hipEventQuery failed: %s", hipGetErrorString(me));
+    }
     return 1;
 }
 
+// markers / mean: nullptr, or [n_frames][n][M] / [n_frames][n] (the marker pipeline is on: the caller has checked)
 static int sequence_dev(oatgpu_ctx *c, const void *const *frames_dev, int32_t n_frames, double lr, oatgpu_position *out,
-                        double *done_s, double *enq_s)
+                        double *done_s, double *enq_s, oatgpu_position *markers = nullptr, oatgpu_combined *mean = nullptr)
 {
-    if (!c || !frames_dev || !out || n_frames < 0) return fail(c, OATGPU_E_INVALID, "null argument");
+    if (!c || !frames_dev || (!out && !markers) || n_frames < 0) return fail(c, OATGPU_E_INVALID, "null argument");
     if (c->ring_count) return fail(c, OATGPU_E_INVALID, "track_sequence while enqueued results are outstanding");
     const int n = c->cfg.n_streams;
     const auto t0 = std::chrono::steady_clock::now();
     int got = 0, rc = OATGPU_OK;
     auto collect_one = [&]() {
-        const int r = oatgpu_track_collect(c, out + (size_t)got * n);
+        const int r = collect_frame(c, out ? out + (size_t)got * n : nullptr, markers ? markers + (size_t)got * n * c->mk_n : nullptr,
+                                    mean ? mean + (size_t)got * n : nullptr);
         if (!r && done_s) done_s[got] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         ++got;
         return r;
@@ -2197,6 +2340,14 @@ extern "C" int oatgpu_track_sequence_dev(oatgpu_ctx *c, const void *const *frame
                                          oatgpu_position *out)
 {
     return sequence_dev(c, frames_dev, n_frames, lr, out, nullptr, nullptr);
+}
+
+extern "C" int oatgpu_track_markers_sequence_dev(oatgpu_ctx *c, const void *const *frames_dev, int32_t n_frames, double lr,
+                                                 oatgpu_position *fg, oatgpu_position *markers, oatgpu_combined *mean)
+{
+    if (!c || !markers) return fail(c, OATGPU_E_INVALID, "null argument");
+    if (!c->mkp_on) return fail(c, OATGPU_E_INVALID, "the marker pipeline is off (oatgpu_set_marker_pipeline)");
+    return sequence_dev(c, frames_dev, n_frames, lr, fg, nullptr, nullptr, markers, mean);
 }
 
 extern "C" int oatgpu_track_outstanding(const oatgpu_ctx *c) { return c ? c->ring_count : 0; }
@@ -2235,10 +2386,10 @@ extern "C" int oatgpu_track_batch(oatgpu_ctx *c, const uint8_t *const *frames_ho
 // Several colour windows per camera behind ONE model pass, and `posicom mean` behind them (kernels_markers.hip).
 
 // the context's own window is the NON-ZERO window: its threshold plane is then Z (kernels_markers.hip)
-static bool own_window_is_nonzero(const oatgpu_ctx *c)
+static bool own_window_is_nonzero(const oatgpu_config &k)
 {
-    const RangeParams r = range_of(detector_of(c->cfg));
-    if (c->cfg.channels == 1) return r.lo[0] == 1 && r.hi[0] == 255;
+    const RangeParams r = range_of(detector_of(k));
+    if (k.channels == 1) return r.lo[0] == 1 && r.hi[0] == 255;
     return r.lo[0] == 0 && r.hi[0] == 255 && r.lo[1] == 0 && r.hi[1] == 255 && r.lo[2] == 1 && r.hi[2] == 255;
 }
 
@@ -2250,6 +2401,8 @@ extern "C" int oatgpu_set_markers(oatgpu_ctx *c, int32_t n_markers, const oatgpu
     if (n_markers > 0 && (heading_anchor < -1 || heading_anchor >= n_markers))      // MeanPosition.cpp:55-57
         return fail(c, OATGPU_E_INVALID, "heading anchor %d out of range: -1 (none) or a marker index below %d", heading_anchor, n_markers);
     for (int m = 0; m < n_markers; ++m) { const int rc = check_detector(c, defaults[m]); if (rc) return rc; }
+    if (c->mkp_on)       // (its planes, scratch and records are sized by M: refused, like everything that would pull them from under it)
+        return fail(c, OATGPU_E_INVALID, "the marker pipeline is on: oatgpu_set_marker_pipeline(0) before the marker set changes");
     int rc = open_sync(c);
     if (rc) return rc;
     free_markers(c);
@@ -2325,15 +2478,78 @@ static int read_plane(oatgpu_ctx *c, const u64 *plane, uint8_t *out)
 }
 
 // what a marker step refuses, checked before anything has moved
-static int marker_step_refusals(oatgpu_ctx *c)
+static int marker_step_refusals(oatgpu_ctx *c, const char *what = "track_markers")
 {
-    if (c->ring_count) return fail(c, OATGPU_E_INVALID, "track_markers while enqueued results are outstanding");
+    if (c->ring_count || c->staged_count) return fail(c, OATGPU_E_INVALID, "%s while enqueued results are outstanding", what);
     if (c->mk_n == 0) return fail(c, OATGPU_E_INVALID, "marker sets are not configured (oatgpu_set_markers)");
-    if (!own_window_is_nonzero(c))
-        return fail(c, OATGPU_E_INVALID, "track_markers needs the context's own window to be the non-zero window: %s",
+    if (!own_window_is_nonzero(c->cfg))
+        return fail(c, OATGPU_E_INVALID, "%s needs the context's own window to be the non-zero window: %s", what,
                     c->cfg.channels == 1 ? "intensity [1,256]" : "H [0,256], S [0,256], V [1,256]");
-    if (c->kal_on) return fail(c, OATGPU_E_INVALID, "track_markers with the position filter on (oatgpu_set_kalman) is not supported");
-    if (c->homo_on) return fail(c, OATGPU_E_INVALID, "track_markers with a homography on (oatgpu_set_homography) is not supported");
+    if (c->kal_on) return fail(c, OATGPU_E_INVALID, "%s with the position filter on (oatgpu_set_kalman) is not supported", what);
+    if (c->homo_on) return fail(c, OATGPU_E_INVALID, "%s with a homography on (oatgpu_set_homography) is not supported", what);
+    return OATGPU_OK;
+}
+
+// The pipelined marker path, on or off (default off).  On: the refusals of the synchronous step, then EVERYTHING the path needs
+// is allocated here (oatgpu.h has the sizes); a failed allocation is reported here and leaves an ordinary context.
+extern "C" int oatgpu_set_marker_pipeline(oatgpu_ctx *c, int32_t on)
+{
+    if (!c) return OATGPU_E_INVALID;
+    if (!on) {
+        if (!c->mkp_on) return OATGPU_OK;
+        if (c->ring_count || c->staged_count)
+            return fail(c, OATGPU_E_INVALID, "set_marker_pipeline while enqueued results are outstanding");
+        const int rc = open_sync(c);
+        if (rc) return rc;
+        free_marker_pipeline(c);
+        return OATGPU_OK;
+    }
+    { const int rrc = marker_step_refusals(c, "set_marker_pipeline"); if (rrc) return rrc; }
+    if (c->mkp_on) return OATGPU_OK;
+    int rc = open_sync(c);
+    if (rc) return rc;
+    const Geom &g = c->g;
+    const size_t n = c->cfg.n_streams, M = (size_t)c->mk_n, NW = (size_t)g.Palloc / 64, planes = M * n, ring = (size_t)c->ring_slots;
+    // the one-launch back half: a geometry the LDS kernel takes, and a row scan whose LDS holds the largest dilation of the set
+    std::vector<BlobTab> tab(planes);
+    int max_dil = 0;
+    for (size_t m = 0; m < M; ++m) {
+        const oatgpu_marker &k = c->mk_def[m];
+        const MorphPlan mp = plan_morph(g, k.erode, k.dilate);
+        max_dil = std::max(max_dil, mp.dil);
+        for (size_t s = 0; s < n; ++s) tab[m * n + s] = BlobTab{mp.ero ? mp.ero : 1, mp.dil, k.min_area, k.max_area};
+    }
+    c->mkp_max_dil = max_dil;
+    c->mkp_table = g.H > 2 && g.H <= 16383 && g.W <= 16383 && rowscan_lds_bytes(g, max_dil) <= kRowscanLdsMax;
+    bool ok = true;
+    auto A = [&](void **p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) ok = false; };
+    A((void **)&c->mkp_planes, ring * planes * NW * 8);
+    A((void **)&c->mkp_masks, ring * 3 * planes * NW * 8);
+    A((void **)&c->mkp_tab, planes * sizeof(BlobTab));
+    A((void **)&c->mkp_res, 2 * planes * sizeof(ResultRec));
+    if (ok && hipHostMalloc((void **)&c->mkp_rec_host, ring * c->mkp_set_bytes(), hipHostMallocMapped) != hipSuccess) ok = false;
+    if (ok && hipHostGetDevicePointer((void **)&c->mkp_rec_dev, c->mkp_rec_host, 0) != hipSuccess) ok = false;
+    for (auto &b : c->mkp_bb) if (ok) ok = alloc_scratch(c, b, planes);
+    // (the taps may be read before a slot's first step; words beyond the frame are never written by the back half)
+    if (ok && hipMemsetAsync(c->mkp_planes, 0, ring * planes * NW * 8, c->stream) != hipSuccess) ok = false;
+    if (ok && hipMemsetAsync(c->mkp_masks, 0, ring * 3 * planes * NW * 8, c->stream) != hipSuccess) ok = false;
+    if (ok && hipMemcpy(c->mkp_tab, tab.data(), planes * sizeof(BlobTab), hipMemcpyHostToDevice) != hipSuccess) ok = false;
+    if (ok) {
+        c->mkp_ev.assign(ring, nullptr);
+        for (auto &e : c->mkp_ev)
+            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { e = nullptr; ok = false; }
+        if (hipEventCreateWithFlags(&c->mkp_bits_ev, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) ok = false;
+    }
+    if (ok && hipStreamSynchronize(c->stream) != hipSuccess) ok = false;
+    if (!ok) {
+        const hipError_t e = hipGetLastError();
+        c->mkp_ev.erase(std::remove(c->mkp_ev.begin(), c->mkp_ev.end(), (hipEvent_t) nullptr), c->mkp_ev.end());
+        free_marker_pipeline(c);
+        return fail(c, OATGPU_E_NOMEM, "marker pipeline: allocation failed: %s", hipGetErrorString(e));
+    }
+    c->mkp_ev_of.assign(ring, 0);
+    c->mkp_tap_morph.assign(ring * M, nullptr);
+    c->mkp_on = true;
     return OATGPU_OK;
 }
 
@@ -2351,8 +2567,12 @@ extern "C" int oatgpu_track_markers_dev(oatgpu_ctx *c, const void *frames_dev, d
     // ---- 2. the existing step, unchanged: enqueue + collect ----
     std::vector<oatgpu_position> fg_own;
     if (!fg) { fg_own.resize((size_t)n); fg = fg_own.data(); }
+    const bool pipe = c->mkp_on;          // (the step's own marker work follows: nothing of the pipelined path's for this frame)
+    c->mkp_on = false;
     int rc = oatgpu_track_batch_dev(c, frames_dev, lr, fg);
+    c->mkp_on = pipe;
     if (rc) return rc;
+    c->mk_last_slot = -1;
     // ---- 3. every marker's mask from the frames the per-pixel kernel read and the Z plane it has just written ----
     hipStream_t A = c->stream;
     const uint8_t *seen = c->ud_track ? c->ud_frames[0] : (const uint8_t *)frames_dev;
@@ -2404,9 +2624,13 @@ extern "C" int oatgpu_read_marker_mask(oatgpu_ctx *c, int32_t s, int32_t marker,
     rc = open_sync(c);
     if (rc) return rc;
     const size_t n = c->cfg.n_streams, NW = (size_t)c->g.Palloc / 64;
-    const u64 *base = which == OATGPU_TAP_THRESHOLD ? c->mk_planes + (size_t)marker * n * NW
-                    : which == OATGPU_TAP_MORPH ? c->mk_tap_morph[(size_t)marker]
-                    : which == OATGPU_TAP_FINAL ? c->mk_masks + ((size_t)marker * 3 + 2) * n * NW : nullptr;
+    // the planes of the frame set collected last: a ring slot's (the pipelined path), or the synchronous step's
+    const size_t M = (size_t)c->mk_n, slot = (size_t)(c->mk_last_slot < 0 ? 0 : c->mk_last_slot);
+    const bool piped = c->mkp_on && c->mk_last_slot >= 0;
+    const u64 *base = which == OATGPU_TAP_THRESHOLD ? (piped ? c->mkp_planes + (slot * M + marker) * n * NW : c->mk_planes + (size_t)marker * n * NW)
+                    : which == OATGPU_TAP_MORPH ? (piped ? c->mkp_tap_morph[slot * M + marker] : c->mk_tap_morph[(size_t)marker])
+                    : which == OATGPU_TAP_FINAL ? (piped ? c->mkp_masks + ((slot * 3 + 2) * M + marker) * n * NW
+                                                         : c->mk_masks + ((size_t)marker * 3 + 2) * n * NW) : nullptr;
     if (!base) return fail(c, OATGPU_E_INVALID, "unknown tap %d", which);
     return read_plane(c, base + (size_t)s * NW, out);
 }

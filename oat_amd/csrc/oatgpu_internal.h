@@ -256,6 +256,15 @@ void launch_blob_pair(const Geom &g, const BlobBuffers *b, const u64 *const *src
 void launch_blob_tail2(const Geom &g, const BlobBuffers *b, double min_area, double max_area, ResultRec *const *results,
                        int n_streams, const unsigned *ticket, int nf, hipStream_t st_tail);
 
+// The marker sets' table-driven back half (kernels_blob.hip, launch_blob_table): what plane s of the launch -- marker s / n of
+// camera s % n -- takes from its marker, one entry a PLANE ([M][n], the layout of the planes themselves), in device memory
+struct BlobTab {
+    int ero, dil;                // erode size (1: none) and dilate size (0: none) in effect
+    double min_area, max_area;
+};
+void launch_blob_table(const Geom &g, const BlobBuffers *b, const u64 *const *src, const BlobTab *tab, int max_dil,
+                       ResultRec *const *results, int n_planes, int nf, hipStream_t st);
+
 // --- kernels_markers.hip --- (marker sets: M colour windows per camera behind one MOG2 pass, `posicom mean`)
 constexpr int kMaxMarkers = 8;
 struct MarkerCombined {   // device-side record of k_marker_combine, one per stream per step: oatgpu_combined's layout
@@ -267,7 +276,14 @@ struct MarkerCombined {   // device-side record of k_marker_combine, one per str
 // windows in DEVICE memory
 void launch_marker_bits(const Geom &g, const uint8_t *frames, int channels, const u64 *zbits, const RangeParams *win, int M,
                         u64 *planes, int n_streams, hipStream_t st);
+// ... for the nf (1 or 2) frames of a step in one launch (grid z = frame): frame i reads frames[i] and zbits[i], writes planes[i]
+void launch_marker_bits_frames(const Geom &g, const uint8_t *const *frames, int channels, const u64 *const *zbits,
+                               const RangeParams *win, int M, u64 *const *planes, int n_streams, int nf, hipStream_t st);
 // MeanPosition::combine over results[M][n_streams] (anchor -1: no heading) into out[n_streams]
 void launch_marker_combine(const ResultRec *results, int M, int anchor, int n_streams, MarkerCombined *out, hipStream_t st);
+// ... for the nf frames of a step in one launch; copy[i] (nullptr: none) also receives frame i's M x n_streams result records
+// (out and copy may be host-mapped memory: 64-bit stores)
+void launch_marker_combine_frames(const ResultRec *const *results, int M, int anchor, int n_streams, MarkerCombined *const *out,
+                                  ResultRec *const *copy, int nf, hipStream_t st);
 
 }  // namespace oatgpu

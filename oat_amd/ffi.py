@@ -113,6 +113,10 @@ SIGNATURES = {
     "oatgpu_track_markers": (C.c_int, [_ctx, C.POINTER(_u8p), C.c_int32, C.c_double, C.POINTER(Position), C.POINTER(Position),
                                        C.POINTER(Combined)]),
     "oatgpu_read_marker_mask": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32, _u8p]),
+    "oatgpu_set_marker_pipeline": (C.c_int, [_ctx, C.c_int32]),
+    "oatgpu_track_collect_markers": (C.c_int, [_ctx, C.POINTER(Position), C.POINTER(Position), C.POINTER(Combined)]),
+    "oatgpu_track_markers_sequence_dev": (C.c_int, [_ctx, C.POINTER(C.c_void_p), C.c_int32, C.c_double, C.POINTER(Position),
+                                                    C.POINTER(Position), C.POINTER(Combined)]),
     "oatgpu_mog_apply": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_mog_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_bgr2hsv": (C.c_int, [_ctx, _u8p, _u8p]),

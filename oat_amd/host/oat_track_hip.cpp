@@ -212,6 +212,7 @@ public:
     // behind them; marker m of camera s is published on marker_sink_addresses_[s][m], the combined position on SINK s
     std::vector<oatgpu_marker> markers_;
     int heading_anchor_{-1};        // --heading-anchor (`posicom mean`), -1: no heading
+    int marker_ring_{0};            // --marker-ring D: marker mode through the staged loop and a result ring of D (0: the synchronous step)
     std::vector<std::vector<std::string>> marker_sink_addresses_;
     ~BatchedTracker() override
     {
@@ -311,6 +312,7 @@ protected:
             }
             marker_results_.resize((size_t)n_ * M);
             combined_.resize(n_);
+            if (marker_ring_) gpu_.check(oatgpu_set_marker_pipeline(gpu_.ctx, 1));
         }
         return true;
     }
@@ -322,6 +324,7 @@ protected:
     // (r04, `--timing`: 8 x 1080p 6.2 k -> see DESIGN.md section 6).  Order per SINK is the frames' order.
     void publish_sink(int s)
     {
+        if (marker_ring_) return publish_markers(s, pub_samples_[s]);
         const oatgpu_position &r = results_[s];
         Position2D pos("");
         pos.set_sample(pub_samples_[s]);                             // PositionDetector.cpp:80
@@ -343,7 +346,10 @@ protected:
         if (!collected_) {
             if (pending_.empty()) return;
             if (only_if_ready && oatgpu_track_ready(gpu_.ctx) != 1) return;
-            gpu_.check(oatgpu_track_collect(gpu_.ctx, results_.data()));
+            if (marker_ring_)
+                gpu_.check(oatgpu_track_collect_markers(gpu_.ctx, results_.data(), marker_results_.data(), combined_.data()));
+            else
+                gpu_.check(oatgpu_track_collect(gpu_.ctx, results_.data()));
             pub_samples_ = std::move(pending_.front());
             pending_.pop_front();
             collected_ = true;
@@ -356,9 +362,11 @@ protected:
     void publish() { publish_some(n_, false); }
     bool results_owed() const { return collected_ || !pending_.empty(); }
 
-    // Marker mode: the synchronous marker step once per round of frames (oatgpu_track_markers).  Every camera's frame is
-    // waited for, the step runs, the SOURCEs are posted, then every marker's Position2D leaves on its sink and the combined
-    // one (`posicom mean`: position, heading) on the camera's ordinary SINK.
+    // Marker mode.  Without --marker-ring: the synchronous marker step once per round of frames (oatgpu_track_markers).  Every
+    // camera's frame is waited for, the step runs, the SOURCEs are posted, then every marker's Position2D leaves on its sink
+    // and the combined one (`posicom mean`: position, heading) on the camera's ordinary SINK.  With --marker-ring D the
+    // ordinary staged loop below runs (oatgpu_set_marker_pipeline): the cameras are staged one by one, results leave up to
+    // D - 1 rounds behind through oatgpu_track_collect_markers, camera by camera as publish_markers writes them.
     static void put(Sink<Position2D> &sink, Position2D *shared, const Position2D &pos)
     {
         sink.wait();
@@ -367,7 +375,6 @@ protected:
     }
     int process_markers()
     {
-        const int M = (int)markers_.size();
         std::vector<Sample> samples(n_);
         for (int s = 0; s < n_; ++s) {
             if (frame_sources_[s].wait() == NodeState::END) {
@@ -382,31 +389,35 @@ protected:
         gpu_.check(oatgpu_track_markers(gpu_.ctx, frame_ptrs_.data(), n_, learning_coeff_, results_.data(), marker_results_.data(),
                                         combined_.data()));
         for (int s = 0; s < n_; ++s) frame_sources_[s].post();
-        for (int s = 0; s < n_; ++s) {
-            for (int m = 0; m < M; ++m) {                                   // `posidet hsv` number m of camera s
-                const oatgpu_position &r = marker_results_[(size_t)s * M + m];
-                Position2D pos("");
-                pos.set_sample(samples[s]);
-                pos.position_valid = r.valid != 0;
-                if (r.valid) { pos.position.x = r.x; pos.position.y = r.y; }   // DetectorFunc.cpp:46,58-60
-                put(marker_sinks_[(size_t)s * M + m], marker_shared_[(size_t)s * M + m], pos);
-            }
-            const oatgpu_combined &c = combined_[s];                        // MeanPosition.cpp:60-118
-            Position2D pos("");
-            pos.set_sample(samples[s]);
-            pos.position_valid = c.position_valid != 0;
-            pos.position.x = c.x; pos.position.y = c.y;
-            pos.heading_valid = c.heading_valid != 0;
-            pos.heading.x = c.hx; pos.heading.y = c.hy;
-            put(position_sinks_[s], shared_positions_[s], pos);
-        }
+        for (int s = 0; s < n_; ++s) publish_markers(s, samples[s]);
         ++rounds_;
         return 0;
+    }
+    // camera s of the marker results in hand: every marker's Position2D on its sink, the combined one on the camera's SINK
+    void publish_markers(int s, const Sample &sample)
+    {
+        const int M = (int)markers_.size();
+        for (int m = 0; m < M; ++m) {                                   // `posidet hsv` number m of camera s
+            const oatgpu_position &r = marker_results_[(size_t)s * M + m];
+            Position2D pos("");
+            pos.set_sample(sample);
+            pos.position_valid = r.valid != 0;
+            if (r.valid) { pos.position.x = r.x; pos.position.y = r.y; }   // DetectorFunc.cpp:46,58-60
+            put(marker_sinks_[(size_t)s * M + m], marker_shared_[(size_t)s * M + m], pos);
+        }
+        const oatgpu_combined &c = combined_[s];                        // MeanPosition.cpp:60-118
+        Position2D pos("");
+        pos.set_sample(sample);
+        pos.position_valid = c.position_valid != 0;
+        pos.position.x = c.x; pos.position.y = c.y;
+        pos.heading_valid = c.heading_valid != 0;
+        pos.heading.x = c.hx; pos.heading.y = c.hy;
+        put(position_sinks_[s], shared_positions_[s], pos);
     }
 
     int process() override
     {
-        if (!markers_.empty()) return process_markers();
+        if (!markers_.empty() && !marker_ring_) return process_markers();
         // ---- a frame from every camera (PositionDetector.cpp:63-75), camera by camera: as soon as camera s has delivered,
         // its H2D copy starts (oatgpu_track_stage), and camera s - 1, whose copy has meanwhile left its segment, is
         // posted (PositionDetector.cpp:78-86 per camera) -- the n frames cross one PCIe link one after the other, and
@@ -515,6 +526,9 @@ int main(int argc, char **argv)
                          "                            In a -c file: one [[track.marker]] table per marker (h-thresh, s-thresh, v-thresh, erode, dilate,\n"
                          "                            area) under the tracker's table name, marker-sinks = [\"a,b\", ..], heading-anchor = I.\n"
                          "                            Not with --kalman, --homography, --ring > 1, --ingest-root, -H/-S/-V, --thresh.\n"
+                         "       [--marker-ring D]    (D >= 2; marker-ring in a -c file) marker mode through the pipelined loop: the cameras are\n"
+                         "                            staged one by one, two frames a launch, results are published up to D - 1 rounds behind.\n"
+                         "                            Without it a marker round is one synchronous step.\n"
                          "N SOURCEs / N SINKs: N cameras batched into one device pass per frame; SOURCE i feeds SINK i.\n"
                          "--gpu-index N0,N1,..: the cameras are split into contiguous blocks, one per listed device (own context and thread).\n"
                          "--ingest-root D0 (with --gpu-index D0,D1,..): all frames are ingested on device D0 and scattered to their devices\n"
@@ -526,7 +540,7 @@ int main(int argc, char **argv)
         if ((o.has("camera-matrix") || o.has("distortion-coeffs")) && o.has("undistort-key")) throw std::runtime_error(ud_exclusive);
         o.apply_config({"adaptation-coeff", "h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "model-file",
                         "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "gpu-index", "ring", "mask", "thresh", "homography", "stage-copy", "timing",
-                        "ingest-root", "print-partition", "camera-matrix", "distortion-coeffs", "undistort-key", "marker-sinks", "heading-anchor"},
+                        "ingest-root", "print-partition", "camera-matrix", "distortion-coeffs", "undistort-key", "marker-sinks", "heading-anchor", "marker-ring"},
                        {"kalman", "timing", "print-partition"});
         const std::vector<std::string> sources = split_list(o.positional[0]), sinks = split_list(o.positional[1]);
         if (sources.size() != sinks.size()) throw std::runtime_error("need as many SINKs as SOURCEs");
@@ -536,15 +550,23 @@ int main(int argc, char **argv)
         if (o.all.count("marker")) for (const std::string &m : o.all["marker"]) markers.push_back(parse_marker(m));
         else if (!o.config_file.empty()) markers = read_marker_tables(o.config_file, o.config_key);
         std::vector<std::vector<std::string>> marker_sinks;
-        int heading_anchor = -1;
+        int heading_anchor = -1, marker_ring = 0;
         if (markers.empty()) {
             if (o.has("marker-sinks") || o.has("heading-anchor")) throw std::runtime_error("--marker-sinks / --heading-anchor need at least one --marker");
+            if (o.has("marker-ring")) throw std::runtime_error("--marker-ring needs at least one --marker");
         } else {
+            if (o.has("marker-ring")) {
+                char *end = nullptr;
+                const long v = strtol(o.kv["marker-ring"].c_str(), &end, 10);
+                if (end == o.kv["marker-ring"].c_str() || *end || v < 2 || v > 64)
+                    throw std::runtime_error("--marker-ring: expected a ring depth in 2..64, got '" + o.kv["marker-ring"] + "'");
+                marker_ring = (int)v;
+            }
             for (const char *k : {"kalman", "homography", "ingest-root", "thresh"})
                 if (o.has(k)) throw std::runtime_error(std::string("--marker does not go with --") + k);
             for (const char *k : {"h-thresh", "s-thresh", "v-thresh"})
                 if (o.has(k)) throw std::runtime_error(std::string("--marker does not go with --") + k + ": each marker has its own window (H= S= V= inside --marker)");
-            if (o.num("ring", 1, 1, 64) > 1) throw std::runtime_error("--marker does not go with --ring > 1: the marker step is synchronous, one round of frames at a time");
+            if (o.num("ring", 1, 1, 64) > 1) throw std::runtime_error("--marker does not go with --ring > 1: the ring of marker mode is --marker-ring D (without it the marker step is synchronous, one round of frames at a time)");
             if (markers.size() > 8) throw std::runtime_error("--marker: at most 8 markers");
             std::vector<std::string> lists;
             if (o.all.count("marker-sinks")) lists = o.all["marker-sinks"];
@@ -653,7 +675,8 @@ int main(int argc, char **argv)
             if (o.has("dilate")) t->cfg_.dilate = (int)o.num("dilate", 0, 0, 1e6);
             if (o.arr2("area", a, b)) { t->cfg_.min_area = a; t->cfg_.max_area = b; }
             t->cfg_.device = devices[k];
-            t->cfg_.ring_depth = (int)o.num("ring", 2, 1, 64);
+            t->cfg_.ring_depth = marker_ring ? marker_ring : (int)o.num("ring", 2, 1, 64);
+            t->marker_ring_ = marker_ring;
             if (o.has("model-file")) t->model_file_ = o.kv["model-file"];
             if (o.has("mask")) t->mask_file_ = o.kv["mask"];
             if (o.has("stage-copy")) {

@@ -13,7 +13,15 @@
 Shapes: 1 x 4K (bench.py's headline morphology: erode 7, dilate 7), 16 x 1080p and 1 x 640x480 (erode 3, dilate 7), three
 discs a camera, learning rate 0.01.  Every call is synchronous (one frame set in, its results out); a step is timed with a
 pair of HIP events on the context's stream around the call, after the warm-up; medians are reported, with the wall-clock
-median beside them.  Prints one JSON line."""
+median beside them.  Prints one JSON line.
+
+    python tools/markers_bench.py --pipelined [--rounds R] [--sets N] [--tree CHECKOUT --parent]
+The PIPELINED legs (oatgpu_set_marker_pipeline), a host clock around calls that end in a synchronisation, us a frame set, N
+(>= 200) frame sets a call after a warm-up call that ages the models, R rounds of every leg, every round's figure reported:
+  (b) the synchronous marker step;  (c) oatgpu_track_markers_sequence_dev;  (d) M plain contexts, each through
+  oatgpu_track_sequence_dev, summed;  (e) ONE plain context through oatgpu_track_sequence_dev -- the floor, the marker work
+  fully hidden.  With --parent (a library without the pipelined path, e.g. --tree PARENT_CHECKOUT) only the legs it has: the
+  synchronous marker step -- leg (a) -- and (e); its own repeats are the noise floor."""
 import argparse
 import json
 import os
@@ -73,8 +81,75 @@ def timed(torch, stream, step, steps, warmup):
     return (round(statistics.median(a.elapsed_time(b) for a, b in ev) * 1e3, 1), round(statistics.median(wall) * 1e6, 1))
 
 
+def pipelined(a):
+    import numpy as np
+    import torch
+    import oat_amd
+    from oat_amd.synth import make_pool
+    out = []
+    for name, n, rows, cols, ero, dil in SHAPES:
+        frames = min(32, max(8, 1024 * 1024 * 1024 // (n * rows * cols * 3)))
+        pool = torch.from_numpy(np.stack(make_pool(rows, cols, n, frames, n_discs=3))).cuda()
+        ptrs = [pool[t % frames].data_ptr() for t in range(a.sets)]
+        torch.cuda.synchronize()
+        kw = dict(n_streams=n, adaptation_coeff=0.01, erode=ero, dilate=dil, area=AREA, ring_depth=4)
+
+        def ctx(w):
+            return oat_amd.HotPath(rows, cols, h_thresh=w["h"], s_thresh=w["s"], v_thresh=w["v"], **kw)
+
+        def clock(call):
+            """us a frame set of call() over a.sets frame sets, once per round, after one warm-up call"""
+            call()
+            res = []
+            for _ in range(a.rounds):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                call()
+                res.append(round((time.perf_counter() - t0) / a.sets * 1e6, 1))
+            return res
+
+        rec = {"shape": name, "streams": n, "rows": rows, "cols": cols, "sets": a.sets, "rounds": a.rounds}
+        one = ctx(WINDOWS[0])
+        rec["e_plain_pipelined_us"] = clock(lambda: one.track_sequence_dev(ptrs))
+        one.close()
+        for M in (1, 2, 3):
+            markers = [dict(w, erode=ero, dilate=dil, area=AREA) for w in WINDOWS[:M]]
+            hp = ctx(dict(h=(0, 256), s=(0, 256), v=(1, 256)))
+            hp.set_markers(markers, heading_anchor=0)
+
+            def sync_steps():
+                for p_ in ptrs:
+                    hp.track_markers_dev(p_)
+            r = {"a_parent_sync_us" if a.parent else "b_sync_us": clock(sync_steps)}
+            if not a.parent:
+                hp.marker_pipeline(True)
+                r["c_markers_sequence_us"] = clock(lambda: hp.track_markers_sequence_dev(ptrs))
+                r["last_step_shape"] = list(hp.last_step_shape())
+            hp.close()
+            if not a.parent:
+                many = [ctx(w) for w in WINDOWS[:M]]
+
+                def each():
+                    for c in many:
+                        c.track_sequence_dev(ptrs)
+                r["d_contexts_pipelined_sum_us"] = clock(each)
+                for c in many:
+                    c.close()
+            rec[f"M{M}"] = r
+        out.append(rec)
+        del pool
+        torch.cuda.empty_cache()
+    print(json.dumps({"tool": "markers_bench", "mode": "pipelined", "unit": "us a frame set, host clock, one figure a round",
+                      "parent": a.parent, "library": os.path.relpath(oat_amd.lib_path(), os.path.abspath(a.tree)), "shapes": out,
+                      "device": torch.cuda.get_device_name(0)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--pipelined", action="store_true", help="the pipelined legs (see the module's text)")
+    ap.add_argument("--parent", action="store_true", help="with --pipelined: a library without the pipelined marker path")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--sets", type=int, default=256, help="frame sets a timed call (--pipelined)")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--quick", action="store_true", help="few steps (a profiler run)")
@@ -88,6 +163,8 @@ def main():
     if a.quick:
         a.steps, a.warmup = 24, 8
     sys.path.insert(0, os.path.abspath(a.tree))
+    if a.pipelined:
+        return pipelined(a)
     import numpy as np
     import torch
     import oat_amd
