@@ -238,7 +238,8 @@ int oatgpu_set_detector(oatgpu_ctx *ctx, int32_t h_lo, int32_t h_hi, int32_t s_l
  * reference's filter never tracks); sigma_accel: --sigma-accel (default 5); sigma_noise:
  * --sigma-noise (default 0).  All must be >= 0 and dt > 0 (TOMLSanitize lower bound 0).  Calling it
  * (re)starts every stream's filter from the reference's initial state; enable = 0 turns it off.
- * The single-stage oatgpu_detect_* calls are never filtered. */
+ * The single-stage oatgpu_detect_* calls are never filtered.  OATGPU_E_INVALID -- nothing has changed -- while results are
+ * outstanding (oatgpu_track_enqueue*): a filter restarted between a frame's enqueue and its collect would have no frame order. */
 int oatgpu_set_kalman(oatgpu_ctx *ctx, int32_t enable, double dt, double timeout, double sigma_accel,
                       double sigma_noise);
 
@@ -246,7 +247,8 @@ int oatgpu_set_kalman(oatgpu_ctx *ctx, int32_t enable, double dt, double timeout
  * when it is on, the position filter: every result of the fused track calls goes through cv::perspectiveTransform with
  * the row-major 3x3 matrix h9 (--homography [h11,h12,...,h33], :44-58) -- position where valid, velocity where valid
  * with the matrix' offsets zeroed (:79-89).  raw_x / raw_y keep the detector's pixels.  The caller marks the
- * Position2D it publishes as WORLD units with this matrix (Position2D::setCoordSystem, :102).  enable = 0: off. */
+ * Position2D it publishes as WORLD units with this matrix (Position2D::setCoordSystem, :102).  enable = 0: off.
+ * OATGPU_E_INVALID -- nothing has changed -- while results are outstanding (it is applied when a result is collected). */
 int oatgpu_set_homography(oatgpu_ctx *ctx, int32_t enable, const double *h9);
 
 /* `framefilt mask` fused in front of mog (src/framefilter/FrameMasker.cpp:71-75:
@@ -455,7 +457,9 @@ int oatgpu_detect_diff(oatgpu_ctx *ctx, int32_t stream_ix, const uint8_t *grey_i
  * FrameFilter::process -> ColorConvert -> PositionDetector::process,
  * FrameFilter.cpp:59-98, PositionDetector.cpp:58-99, minus the shm hand-offs).
  * frames_host[i] -> rows*cols*channels bytes of stream i.  out[n_streams].
- * With channels == 1 the chain is framefilt mog (GREY) -> posidet thresh. */
+ * With channels == 1 the chain is framefilt mog (GREY) -> posidet thresh.
+ * OATGPU_E_INVALID -- before anything is read or has moved -- while results are outstanding (oatgpu_track_enqueue*) or a
+ * frame set is partly staged (oatgpu_track_stage); the same holds for oatgpu_track_batch_dev. */
 int oatgpu_track_batch(oatgpu_ctx *ctx, const uint8_t *const *frames_host, int32_t n,
                        double learning_rate, oatgpu_position *out);
 
@@ -485,7 +489,12 @@ int oatgpu_track_collect(oatgpu_ctx *ctx, oatgpu_position *out);
  * until the slowest of N has delivered); once every stream 0..n_streams-1 has been staged,
  * oatgpu_track_enqueue_staged registers the set exactly as oatgpu_track_enqueue would have.  While a set is being
  * staged oatgpu_track_input_consumed_stream(i) waits for stream i's own copy (any staged stream, any order).
- * OATGPU_E_RING_FULL from the first oatgpu_track_stage of a set when ring_depth sets are outstanding. */
+ * OATGPU_E_RING_FULL from the first oatgpu_track_stage of a set when ring_depth sets are outstanding.
+ * OATGPU_E_INVALID, the open set staying as it is: a stream index outside 0..n_streams-1; a stream staged twice;
+ * oatgpu_track_enqueue_staged before every stream is staged (also with none); oatgpu_track_enqueue / _enqueue_dev and the
+ * synchronous track calls while a set is open (it owns the next ring slot: finish it or give it up with
+ * oatgpu_track_stage_abort); oatgpu_track_input_consumed_stream(i) for a stream the open set has not staged yet.
+ * oatgpu_track_collect, oatgpu_track_ready, the settings and the single-stage calls stay allowed while a set is open. */
 int oatgpu_track_stage(oatgpu_ctx *ctx, int32_t stream_ix, const uint8_t *frame_host);
 int oatgpu_track_enqueue_staged(oatgpu_ctx *ctx, double learning_rate);
 /* How oatgpu_track_stage moves a camera's frame: 0 (default) a DMA copy (hipMemcpyAsync); 1 a small copy KERNEL that reads

@@ -377,8 +377,9 @@ def _merge(position, p):
     return position
 
 
-class HotPath(_Context):
-    """The fused chain for N camera streams: mog + setTo + BGR2HSV + inRange + erode + dilate + blob.
+class HotPath(_Detector):
+    """The fused chain for N camera streams: mog + setTo + BGR2HSV + inRange + erode + dilate + blob.  The detector is
+    re-configured between frames with _set(h_lo=.., erode=.., min_area=..) (oatgpu_set_detector).
 
     undistort: `framefilt undistort` in front of the chain (oatgpu_set_track_undistort) -- one (camera_matrix,
     distortion_coeffs) tuple for every stream, or a list of n_streams such tuples (one calibration per camera)."""
@@ -412,6 +413,18 @@ class HotPath(_Context):
 
     def _out(self):
         return [Position2D.from_c(p) for p in self._pos]
+
+    def detect_hsv(self, hsv, stream=0):
+        """The single-stage `posidet hsv` of this context (oatgpu_detect_hsv) on an HSV image: synchronous, never filtered."""
+        p = ffi.Position()
+        self._chk(self.lib.oatgpu_detect_hsv(self.ctx, int(stream), ffi.u8(_frame(hsv, (self.rows, self.cols, 3))), C.byref(p)))
+        return Position2D.from_c(p)
+
+    def detect_thresh(self, grey, stream=0):
+        """The single-stage `posidet thresh` (oatgpu_detect_thresh) on a GREY image; -T is the context's h window."""
+        p = ffi.Position()
+        self._chk(self.lib.oatgpu_detect_thresh(self.ctx, int(stream), ffi.u8(_frame(grey, (self.rows, self.cols))), C.byref(p)))
+        return Position2D.from_c(p)
 
     def track(self, frames):
         """frames: sequence of n_streams host arrays (rows, cols, 3), or (rows, cols) when channels == 1."""

@@ -882,7 +882,10 @@ __global__ __launch_bounds__(WG, (k1_waves<CH, AUDIT, NTLD, NF>())) void k_mog_f
 #pragma unroll
     for (int k = 0; k < kMaxMix; ++k) {
         const bool was_live = k == 0 || full_any || ((cnt >> (kLiveShift + k)) & 1);
-        const bool sw = work && wchg && k < nlive && was_live, svm = (dvm >> k) & 1u;
+        // (... or where a fitted mode bubbled up, swap_up marks both slots in dvm: at rate 0 with a renormalisation by exactly 1
+        // no VALUE changes, but a mode that sat behind a pruned slot -- weight 0, kept by `nmodes = nNewModes;` -- and fits again
+        // moves in front of it, as in the reference; its record was stored and its weight was not.  tools/fuzz_api.py, seed 1567)
+        const bool svm = (dvm >> k) & 1u, sw = work && (wchg || svm) && k < nlive && was_live;
         if (sw) STW(k, pm.w[k]);
         if (svm) st_rec(k);
         AU_DW(sw, true);

@@ -1719,6 +1719,8 @@ static StepPlan plan_step(const oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, in
     p.inline_back = lone && c->lone_plain && nj == 1 && !p.early;
     // ONE "K1 done" event for the step: both frames' back halves wait for the same launch (a second record would be
     // a second marker packet between two K1s on stream A)
+    // (which of the events it is does not tie it to a B stream: it is recorded on A, and launch_back_plain waits for it from
+    // whichever B stream it picks -- in a step of a device and a host frame that is not the stream of this index)
     p.k1_done = p.inline_back ? nullptr : c->ev_k1[j[0].slot % plain_b_streams(j[0])];
     // The paired back half: both frames of a two-frame step go through ONE row-scan launch and ONE k_blob_lds launch (grid z =
     // frame) on ONE B stream behind one wait, one ring event covers both results -- 6 runtime calls a step instead of 10.
@@ -1909,9 +1911,15 @@ static int launch_back_early(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int n
 static int launch_back_plain(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, const StepPlan &plan, ProfStep *ps)
 {
     const int n = c->cfg.n_streams;
+    // share_b: ONE B stream and scratch set for the step, chosen once.  A step may hold a device frame and a host frame (a
+    // registered host frame paired with the next oatgpu_track_enqueue_dev, or the reverse under oatgpu_set_fusion(2)), and
+    // j[0].slot % 3 and j[0].slot % 2 are different streams: taken per frame, the second back half went down a stream that
+    // never waited for the step's per-pixel kernel -- it analysed the threshold bits the slot's PREVIOUS frame had left --
+    // and the first frame's ring event sat on a stream its back half was not on (tests/test_api_sequences_gpu.py, seed 22).
+    const int q_step = j[0].slot % (nj == 2 ? std::min(plain_b_streams(j[0]), plain_b_streams(j[1])) : plain_b_streams(j[0]));
     for (int i = 0; i < nj; ++i) {
         const int slot = j[i].slot;                      // (also the threshold-bit buffer of this frame)
-        const int q = (plan.share_b ? j[0].slot : slot) % plain_b_streams(j[i]);   // scratch set / B stream of this frame
+        const int q = plan.share_b ? q_step : slot % plain_b_streams(j[i]);   // scratch set / B stream of this frame
         hipStream_t B = plan.inline_back ? c->stream : c->stream_b[q];
         if (!plan.inline_back) c->b_used[q] = true;
         ProfStep *pb = i == 0 ? ps : nullptr;           // the back half of the step's first frame is the sampled one
@@ -2134,7 +2142,14 @@ static int launch_repair(oatgpu_ctx *c, int slot)
     }
     hipStream_t B = c->stream_b[kRepairStream];
     c->b_used[kRepairStream] = true;
+    // (a repair is not "the last processed frame" of oatgpu_read_mask: it redoes an EARLIER frame, usually after later ones were
+    // launched -- the morph / final taps stay with the frame launched last, where last_slot keeps the threshold tap; the
+    // repaired frame's own planes are those its speculative back half had made.  tools/fuzz_api.py, seed 1459)
+    const auto keep_morph = c->last_morph;
+    const auto keep_fin = c->last_fin;
     const int rc = back_half(c, c->bb[kRepairSet], thr_buf(c, slot), 0, c->cfg.n_streams, slot, B, nullptr, -1, -1, kBlobGlobal);
+    c->last_morph = keep_morph;
+    c->last_fin = keep_fin;
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(c->ring_ev[slot], B));
     c->slots[slot].ev = slot;
@@ -2377,6 +2392,10 @@ extern "C" int oatgpu_track_batch(oatgpu_ctx *c, const uint8_t *const *frames_ho
 {
     if (!c || !frames_host || !out) return fail(c, OATGPU_E_INVALID, "null argument");
     if (n != c->cfg.n_streams) return fail(c, OATGPU_E_INVALID, "expected %d frames, got %d", c->cfg.n_streams, n);
+    // refused BEFORE a copy out of the caller's frames is queued (the rule of oatgpu_track_enqueue): oatgpu_track_batch_dev
+    // checks the same again, but by then stream A would be reading the buffers of a call that fails
+    if (c->ring_count) return fail(c, OATGPU_E_INVALID, "track_batch while enqueued results are outstanding");
+    { const int rc = refuse_pipelined(c, kRefStaging | kRefState); if (rc) return rc; }
     HIPCHK(c, hipSetDevice(c->cfg.device));
     { const int rc = upload_frames(c, frames_host); if (rc) return rc; }
     return oatgpu_track_batch_dev(c, c->frames, lr, out);

@@ -70,16 +70,26 @@ def _components(ys, xs, xe):
     return len({find(i) for i in range(n)})
 
 
+def run_counts(m):
+    """(D, R) of a frame-zeroed 0/1 mask: dirty rows and the runs of the dirty rows, as k_rowscan's rowinfo counts them."""
+    trans = np.count_nonzero(m[:, 1:] != m[:, :-1], axis=1)
+    dirty = m.any(axis=1)
+    return int(dirty.sum()), int(np.where(dirty, 1 + trans, 0).sum())
+
+
+def over_run_capacity(final):
+    """k_blob_lds declines this mask for its rows or runs alone (D > LDS_ROWS or R > LDS_RUNS): the cheap half of
+    blob_load()'s verdict, without the component count -- for callers that ask once a frame at full size."""
+    D, R = run_counts(frame_zeroed(final))
+    return D > LDS_ROWS or R > LDS_RUNS
+
+
 def blob_load(final):
     """Counts and branch choices of k_blob_lds for one final mask (frame zeroed here again; idempotent)."""
     m = frame_zeroed(final)
     H, W = m.shape
     words = (W + 63) // 64
-    trans = np.count_nonzero(m[:, 1:] != m[:, :-1], axis=1)
-    dirty = m.any(axis=1)
-    rowinfo = np.where(dirty, 1 + trans, 0)
-    D = int(dirty.sum())
-    R = int(rowinfo.sum())
+    D, R = run_counts(m)
     NF = (R - D) // 2
     ys, xs, xe = _fg_runs(m)
     assert len(ys) == NF, "a dirty row holds 2 * fg_runs + 1 runs"
