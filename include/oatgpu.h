@@ -42,7 +42,8 @@ extern "C" {
 /* Further additive entries of ABI 9 (detect them by symbol; no existing struct or entry changes): the marker sets --
  * oatgpu_set_markers, oatgpu_set_marker_window, oatgpu_track_markers_dev, oatgpu_track_markers, oatgpu_read_marker_mask,
  * with the structs oatgpu_marker and oatgpu_combined; marker sets on the pipelined path -- oatgpu_set_marker_pipeline,
- * oatgpu_track_collect_markers, oatgpu_track_markers_sequence_dev. */
+ * oatgpu_track_collect_markers, oatgpu_track_markers_sequence_dev; the filter chain behind the combined record --
+ * oatgpu_set_marker_filters, oatgpu_marker_filtered, with the structs oatgpu_region, oatgpu_marker_filters, oatgpu_filtered. */
 
 enum {
     OATGPU_OK = 0,
@@ -341,7 +342,9 @@ typedef struct oatgpu_marker {
  * then the partial sum); with a heading anchor (hx, hy) adds position_m - position_anchor while the running position_valid is
  * still set (an invalid position is (0, 0)) and heading_valid goes 0 otherwise; the sum is then divided by its length --
  * NaN for M = 1 or coincident markers, with heading_valid 1, as the reference.  Without an anchor heading_valid = 0
- * (detectors set no heading); velocity_valid = 0 (no position filter runs on markers).  n_valid: markers found. */
+ * (detectors set no heading); velocity_valid = 0: this record is what `posicom mean` publishes, BEFORE any position filter --
+ * the chain of oatgpu_set_marker_filters leaves it as it is and publishes a record of its own (oatgpu_filtered).
+ * n_valid: markers found. */
 typedef struct oatgpu_combined {
     int32_t position_valid, heading_valid, velocity_valid, n_valid;
     double x, y, hx, hy;
@@ -361,7 +364,9 @@ int oatgpu_set_marker_window(oatgpu_ctx *ctx, int32_t stream, int32_t marker, co
  * camera s (`posidet hsv` number m); mean[n_streams] (or NULL): the combined positions.  With oatgpu_set_track_undistort(1)
  * and / or a ROI mask the markers see the undistorted, masked frame, as the model does.
  * OATGPU_E_INVALID -- before anything has moved -- when results are outstanding (oatgpu_track_enqueue*), markers are not
- * configured, the context's own window is not the non-zero window, or oatgpu_set_kalman / oatgpu_set_homography is on.
+ * configured, the context's own window is not the non-zero window, or oatgpu_set_kalman / oatgpu_set_homography is on (those
+ * two act on the foreground result of the plain track calls; the filters of a marker rig are oatgpu_set_marker_filters, which
+ * runs behind the combined record of this step and of every pipelined form).
  * Two-frame launches, the result ring and the early blob dispatch do not extend to markers. */
 int oatgpu_track_markers_dev(oatgpu_ctx *ctx, const void *frames_dev, double learning_rate, oatgpu_position *fg,
                              oatgpu_position *markers, oatgpu_combined *mean);
@@ -373,9 +378,10 @@ int oatgpu_track_markers(oatgpu_ctx *ctx, const uint8_t *const *frames_host, int
 int oatgpu_read_marker_mask(oatgpu_ctx *ctx, int32_t stream, int32_t marker, int32_t which, uint8_t *out);
 /* Marker sets on the PIPELINED path (default off).  on = 1 is refused -- before anything has moved, with the synchronous step's
  * messages -- when results are outstanding, markers are not configured, the context's own window is not the non-zero window, or
- * oatgpu_set_kalman / oatgpu_set_homography is on.  It allocates everything the path needs (sizes: oatgpu_create's note): per
+ * oatgpu_set_kalman / oatgpu_set_homography is on (the filters of a marker rig are oatgpu_set_marker_filters: allowed with
+ * this switch on or off, in either order).  It allocates everything the path needs (sizes: oatgpu_create's note): per
  * ring slot the M bit planes and every marker's tmp / morph / fin planes, ring_depth host-mapped record sets (M x n_streams result
- * records + n_streams combined records), events, and two back-half scratch sets for M x n_streams planes; an out-of-memory is
+ * records + n_streams combined records + n_streams filtered records), events, and two back-half scratch sets for M x n_streams planes; an out-of-memory is
  * OATGPU_E_NOMEM from THIS call and leaves an ordinary, working context.  on = 0 frees it all (refused while results are
  * outstanding).
  * While it is on, EVERY pipelined entry point (oatgpu_track_enqueue_dev, _enqueue, _stage + _enqueue_staged, the
@@ -397,6 +403,61 @@ int oatgpu_track_collect_markers(oatgpu_ctx *ctx, oatgpu_position *fg, oatgpu_po
  * fg[t * n_streams + s] (or NULL), markers[(t * n_streams + s) * n_markers + m], mean[t * n_streams + s] (or NULL). */
 int oatgpu_track_markers_sequence_dev(oatgpu_ctx *ctx, const void *const *frames_dev, int32_t n_frames, double learning_rate,
                                       oatgpu_position *fg, oatgpu_position *markers, oatgpu_combined *mean);
+
+/* ---- the filter chain behind the combined record: `posifilt kalman` -> `posifilt homography` -> `posifilt region` ----
+ *
+ * What a marker rig's user records: the token `posicom mean` publishes goes through `posifilt kalman` (bridges frames where an
+ * LED is occluded, adds a velocity), `posifilt homography` (metres) and `posifilt region` (which arm of the maze).  The chain
+ * runs on the device, in frame order, in ONE launch behind the combiner -- on the synchronous marker step and on every
+ * pipelined form -- in this fixed order; each member is switched on its own.  Input per camera and frame is the oatgpu_combined
+ * record, which stays as it is; with no chain configured nothing is launched.  oatgpu_set_kalman / oatgpu_set_homography are a
+ * different thing (the foreground result of plain track calls) and stay refused on marker contexts.
+ *
+ * kalman      KalmanFilter2D::filter as oatgpu_set_kalman has it, fed (position_valid, x, y) of the combined record: a
+ *             partial-sum x, y under position_valid == 0 is not a measurement.  position_valid = velocity_valid = found,
+ *             position / velocity = the reported state (6.0 before the first track, the every-sample timeout test, the stale
+ *             measurement, the predicted state: all kept).  The heading passes through.  One filter state per camera stream,
+ *             separate from oatgpu_set_kalman's.
+ * homography  HomographyTransform2D::filter (HomographyTransform2D.cpp:63-106): the position where valid; the velocity and
+ *             the heading where valid through the matrix with its offsets zeroed; the heading is then normalised as
+ *             cv::normalize does a one-element vector -- multiplied by the reciprocal of its length (by 0 where the length is
+ *             not above DBL_EPSILON).  A NaN heading (one marker, coincident markers) becomes (0, 0), heading_valid still 1.
+ * region      RegionFilter2D::filter (RegionFilter2D.cpp:130-152) where position_valid: the position converted as
+ *             (cv::Point) does (cvRound per coordinate, ties to even), every configured vertex converted the same way, then
+ *             cv::pointPolygonTest(contour, pt, false) >= 0 (the boundary counts as inside) in 64-bit integers.  The regions
+ *             are tested IN THE ORDER GIVEN and the first hit wins -- the reference iterates a cpptoml table, an unordered map,
+ *             so its order for overlapping regions is unspecified.  A coordinate that is not finite or beyond int32 after
+ *             rounding matches no region.  At most 16 regions of at most 64 points; a name takes at most 9 bytes (the
+ *             reference's strcpy overruns its 10-byte field with more); a vertex beyond +-32767 after rounding is refused. */
+typedef struct oatgpu_region {
+    char name[10];
+    int32_t n_points;
+    const double *xy;              /* n_points pairs x, y */
+} oatgpu_region;
+typedef struct oatgpu_marker_filters {
+    int32_t kalman;                /* 0: off */
+    double dt, timeout, sigma_accel, sigma_noise;      /* as oatgpu_set_kalman's, same checks */
+    int32_t homography;            /* 0: off */
+    double h[9];                   /* row-major */
+    int32_t n_regions;             /* 0: off */
+    const oatgpu_region *regions;
+} oatgpu_marker_filters;
+typedef struct oatgpu_filtered {
+    int32_t position_valid, velocity_valid, heading_valid, region_valid;
+    int32_t region /* -1: none */, reserved_;
+    double x, y, vx, vy, hx, hy;
+} oatgpu_filtered;
+/* Configures the chain.  f = NULL, or all three members off, switches it off.  A successful call (re)starts every stream's
+ * Kalman state from the reference's initial state.  OATGPU_E_INVALID, with nothing changed, when results are outstanding,
+ * markers are not configured, a limit above is exceeded, a name is too long or a Kalman parameter is out of range.  Allowed
+ * with the marker pipeline on or off, in either order.  Every successful oatgpu_set_markers drops the chain. */
+int oatgpu_set_marker_filters(oatgpu_ctx *ctx, const oatgpu_marker_filters *f);
+/* The filtered records of the frame sets the LATEST marker-result call delivered: one set for oatgpu_track_markers[_dev] and
+ * oatgpu_track_collect_markers, n_frames sets for oatgpu_track_markers_sequence_dev; out[t * n_streams + s].  Returns the
+ * number of sets written; OATGPU_E_INVALID when no chain is configured, no marker result has been delivered since it was, or
+ * max_sets is too small.  Nothing is consumed: the call may be repeated.  The chain advances for every frame whether or not
+ * this is called; oatgpu_track_collect on a marker-pipeline context retires the slot's filtered record with the slot. */
+int oatgpu_marker_filtered(oatgpu_ctx *ctx, oatgpu_filtered *out, int32_t max_sets);
 
 /* Deferred completion of the stage-by-stage operators below (default off).  With on = 1 a frame filter (oatgpu_mog_filter,
  * _bsub_filter, _mask_filter, _thresh_filter, _undistort_filter, _bgr2hsv, _cvt_color) or a detector (oatgpu_detect_hsv / _thresh / _diff)

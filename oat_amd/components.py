@@ -57,12 +57,34 @@ class Combined:
     heading_valid: bool = False
     hx: float = 0.0
     hy: float = 0.0
-    velocity_valid: bool = False   # always False: no position filter runs on markers
+    velocity_valid: bool = False   # always False here: the filter chain publishes its own record (Filtered)
     n_valid: int = 0               # markers found
 
     @staticmethod
     def from_c(p):
         return Combined(bool(p.position_valid), p.x, p.y, bool(p.heading_valid), p.hx, p.hy, bool(p.velocity_valid), p.n_valid)
+
+
+@dataclass
+class Filtered:
+    """The combined record of one camera behind the filter chain of HotPath.set_marker_filters (`posifilt kalman` ->
+    `posifilt homography` -> `posifilt region`): what the camera's oat::Position2D holds behind the three filters."""
+    position_valid: bool = False
+    x: float = 0.0
+    y: float = 0.0
+    velocity_valid: bool = False
+    vx: float = 0.0
+    vy: float = 0.0
+    heading_valid: bool = False
+    hx: float = 0.0
+    hy: float = 0.0
+    region_valid: bool = False
+    region: str = None             # name of the first configured region that holds the position, None: none
+
+    @staticmethod
+    def from_c(p, names):
+        return Filtered(bool(p.position_valid), p.x, p.y, bool(p.velocity_valid), p.vx, p.vy, bool(p.heading_valid), p.hx, p.hy,
+                        bool(p.region_valid), names[p.region] if p.region_valid else None)
 
 
 def _marker(m):
@@ -466,6 +488,50 @@ class HotPath(_Detector):
         self.n_markers = len(ms)
         self._mpos = (ffi.Position * max(self.n_streams * len(ms), 1))()
         self._mean = (ffi.Combined * self.n_streams)()
+        self._region_names = []                            # (every successful oatgpu_set_markers drops the filter chain)
+
+    def set_marker_filters(self, kalman=None, homography=None, regions=None):
+        """oatgpu_set_marker_filters: the chain behind every camera's combined record, in the fixed order kalman -> homography
+        -> region.  kalman = None or a dict with any of dt / timeout / sigma_accel / sigma_noise (set_kalman's defaults);
+        homography = None or a 3x3 matrix; regions = None or a list of (name, points) with points = [(x, y), ...], tested in
+        the order given.  All None switches the chain off.  A successful call restarts every camera's Kalman state."""
+        f = ffi.MarkerFilters()
+        if kalman is not None:
+            k = dict(dt=0.02, timeout=0.0, sigma_accel=5.0, sigma_noise=0.0)
+            unknown = set(kalman) - set(k)
+            if unknown:
+                raise TypeError(f"unknown kalman option(s) {sorted(unknown)}")
+            k.update(kalman)
+            f.kalman, f.dt, f.timeout, f.sigma_accel, f.sigma_noise = 1, k["dt"], k["timeout"], k["sigma_accel"], k["sigma_noise"]
+        if homography is not None:
+            f.homography = 1
+            f.h = (C.c_double * 9)(*np.asarray(homography, np.float64).reshape(9))
+        regions = list(regions or [])
+        arr = (ffi.Region * max(len(regions), 1))()
+        keep, names = [], []
+        for r, (name, points) in zip(arr, regions):
+            raw = name.encode() if isinstance(name, str) else bytes(name)
+            pts = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 2))
+            keep.append(pts)
+            r.name = raw[:10]                              # (10 bytes leave no room for the terminator: the library refuses)
+            r.n_points = len(pts)
+            r.xy = pts.ctypes.data_as(C.POINTER(C.c_double))
+            names.append(raw.decode())
+        f.n_regions = len(regions)
+        f.regions = arr
+        self._chk(self.lib.oatgpu_set_marker_filters(self.ctx, C.byref(f)))
+        self._region_names = names
+
+    def marker_filtered(self):
+        """oatgpu_marker_filtered: the filtered records of the frame sets the latest marker-result call delivered -- a list with
+        one entry per frame set, each a list of n_streams Filtered.  Nothing is consumed."""
+        n, sets = self.n_streams, max(getattr(self, "_mf_sets", 1), 1)
+        out = (ffi.Filtered * (sets * n))()
+        rc = self.lib.oatgpu_marker_filtered(self.ctx, out, sets)
+        if rc < 0:
+            self._chk(rc)
+        names = getattr(self, "_region_names", [])
+        return [[Filtered.from_c(out[t * n + s], names) for s in range(n)] for t in range(rc)]
 
     def set_marker_window(self, stream, marker, h=(0, 256), s=(0, 256), v=(0, 256)):
         """oatgpu_set_marker_window: the colour window of one marker for ONE camera; morphology and area stay per marker."""
@@ -474,6 +540,7 @@ class HotPath(_Detector):
 
     def _markers_out(self):
         M = self.n_markers
+        self._mf_sets = 1                                  # (marker_filtered: one frame set was delivered)
         return (self._out(), [[Position2D.from_c(self._mpos[s * M + m]) for m in range(M)] for s in range(self.n_streams)],
                 [Combined.from_c(p) for p in self._mean])
 
@@ -519,6 +586,7 @@ class HotPath(_Detector):
         mk = (ffi.Position * max(T * n * M, 1))()
         mean = (ffi.Combined * max(T * n, 1))()
         self._chk(self.lib.oatgpu_track_markers_sequence_dev(self.ctx, arr, T, self.learning_coeff_, fg, mk, mean))
+        self._mf_sets = T                                  # (marker_filtered: T frame sets were delivered)
         return [([Position2D.from_c(fg[t * n + s]) for s in range(n)],
                  [[Position2D.from_c(mk[(t * n + s) * M + m]) for m in range(M)] for s in range(n)],
                  [Combined.from_c(mean[t * n + s]) for s in range(n)]) for t in range(T)]

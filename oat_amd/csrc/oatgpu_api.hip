@@ -7,6 +7,7 @@
 // the HIP kernels or fails with an error code.
 #include "../../include/oatgpu.h"
 #include "oatgpu_internal.h"
+#include "posfilt_inline.h"
 
 #include <algorithm>
 #include <atomic>
@@ -236,7 +237,18 @@ struct oatgpu_ctx {
     std::vector<const u64 *> mkp_tap_morph;    // [ring][M] where the MORPH tap of marker m of that slot is
     hipEvent_t mkp_bits_ev = nullptr;          // stream A: the step's k_marker_bits has finished
     int mk_last_slot = -1;                     // ring slot of the frame set collected last on the pipelined path; -1: the synchronous step was later
-    size_t mkp_set_bytes() const { return (size_t)mk_n * cfg.n_streams * sizeof(ResultRec) + (size_t)cfg.n_streams * sizeof(MarkerCombined); }
+    // a record set: M x n result records, n combined records, n filtered records (written only while a chain is configured)
+    size_t mkp_set_bytes() const { return (size_t)mk_n * cfg.n_streams * sizeof(ResultRec) + (size_t)cfg.n_streams * (sizeof(MarkerCombined) + sizeof(MarkerFiltered)); }
+    // the filter chain behind the combined record (oatgpu_set_marker_filters): kalman -> homography -> region in ONE launch
+    // behind k_marker_combine on the same HIP stream.  Made by the setter, dropped with the marker set.
+    bool mf_on = false;
+    MarkerFilterParams *mf_params = nullptr;   // device: the chain's parameters and the region table
+    KalmanState *mf_state = nullptr;           // device: [n] the chain's own filter state, one per camera stream (not c->kal's)
+    MarkerFiltered *mf_out = nullptr;          // device: [n] the synchronous step's filtered records
+    MarkerFiltered *mf_out_host = nullptr;     // ... their page-locked mirror
+    std::vector<oatgpu_filtered> mf_last;      // [sets][n] what the latest marker-result call delivered (oatgpu_marker_filtered)
+    int mf_last_sets = 0;
+    bool mf_append = false;                    // inside oatgpu_track_markers_sequence_dev: every collected set is kept
 };
 
 static int fail(oatgpu_ctx *c, int code, const char *fmt, ...)
@@ -469,9 +481,18 @@ static void free_marker_pipeline(oatgpu_ctx *c)
     c->mkp_on = false;
     c->mk_last_slot = -1;
 }
+static void free_marker_filters(oatgpu_ctx *c)
+{
+    hipFree(c->mf_params); hipFree(c->mf_state); hipFree(c->mf_out);
+    if (c->mf_out_host) hipHostFree(c->mf_out_host);
+    c->mf_params = nullptr; c->mf_state = nullptr; c->mf_out = nullptr; c->mf_out_host = nullptr;
+    c->mf_on = false;
+    c->mf_last.clear(); c->mf_last_sets = 0;
+}
 static void free_markers(oatgpu_ctx *c)
 {
     free_marker_pipeline(c);
+    free_marker_filters(c);
     hipFree(c->mk_win); hipFree(c->mk_planes); hipFree(c->mk_masks); hipFree(c->mk_res);
     if (c->mk_res_host) hipHostFree(c->mk_res_host);
     c->mk_win = nullptr; c->mk_planes = nullptr; c->mk_masks = nullptr; c->mk_res = nullptr; c->mk_res_host = nullptr;
@@ -1005,21 +1026,8 @@ extern "C" int oatgpu_set_kalman(oatgpu_ctx *c, int32_t enable, double dt, doubl
     return OATGPU_OK;
 }
 
-// HomographyTransform2D::filter (HomographyTransform2D.cpp:62-107) on one result: cv::perspectiveTransform of a
-// CV_64FC2 point (OpenCV 3.1.0 core/matmul.cpp perspectiveTransform_<double>: w = x m6 + y m7 + m8; |w| > FLT_EPSILON ->
-// multiply by 1/w, else (0, 0)); the velocity through the same matrix with its offsets zeroed (:79-89).
-static void perspective_point(const double *m, double &px, double &py)
-{
-    const double x = px, y = py;
-    double w = x * m[6] + y * m[7] + m[8];
-    if (fabs(w) > (double)FLT_EPSILON) {
-        w = 1. / w;
-        px = (x * m[0] + y * m[1] + m[2]) * w;
-        py = (x * m[3] + y * m[4] + m[5]) * w;
-    } else {
-        px = py = 0;
-    }
-}
+// HomographyTransform2D::filter (HomographyTransform2D.cpp:62-107) on one result: cv::perspectiveTransform of the position
+// (perspective_point, posfilt_inline.h); the velocity through the same matrix with its offsets zeroed (:79-89).
 static void apply_homography(const oatgpu_ctx *c, oatgpu_position *o)
 {
     if (o->valid) perspective_point(c->homo, o->x, o->y);
@@ -1975,6 +1983,7 @@ static int launch_marker_work(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int 
     const ResultRec *res_c[2] = {};
     ResultRec *res[2] = {}, *rec[2] = {};
     MarkerCombined *comb[2] = {};
+    MarkerFiltered *filt[2] = {};
     for (int i = 0; i < nj; ++i) {
         const int slot = j[i].slot;
         fr[i] = c->ud_track ? c->ud_frames[i] : (const uint8_t *)j[i].frames;
@@ -1986,6 +1995,7 @@ static int launch_marker_work(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int 
         res_c[i] = res[i] = c->mkp_res + (size_t)i * planes;
         rec[i] = (ResultRec *)((char *)c->mkp_rec_dev + (size_t)slot * c->mkp_set_bytes());
         comb[i] = (MarkerCombined *)(rec[i] + planes);
+        filt[i] = (MarkerFiltered *)(comb[i] + n);
         c->mkp_ev_of[(size_t)slot] = j[nj - 1].slot;
     }
     launch_marker_bits_frames(g, fr, c->cfg.channels, z, c->mk_win, M, bits, n, nj, A);
@@ -2012,6 +2022,10 @@ static int launch_marker_work(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int 
     HIPCHK(c, hipGetLastError());
     launch_marker_combine_frames(res_c, M, c->mk_anchor, n, comb, rec, nj, S);
     HIPCHK(c, hipGetLastError());
+    if (c->mf_on) {       // the chain, behind the combiner and before the event: the filtered records are final when it fires
+        launch_marker_filters(c->mf_params, c->mf_state, comb, filt, n, nj, S);
+        HIPCHK(c, hipGetLastError());
+    }
     HIPCHK(c, hipEventRecord(c->mkp_ev[(size_t)j[nj - 1].slot], S));
     return OATGPU_OK;
 }
@@ -2188,6 +2202,17 @@ static hipError_t wait_short(hipEvent_t e)
     }
 }
 
+// the filtered records of a delivered frame set: the latest set, or one more of the running marker sequence
+static void keep_filtered(oatgpu_ctx *c, const MarkerFiltered *f)
+{
+    static_assert(sizeof(oatgpu_filtered) == sizeof(MarkerFiltered), "k_marker_filters writes oatgpu_filtered's layout");
+    const size_t n = (size_t)c->cfg.n_streams;
+    if (!c->mf_append) c->mf_last_sets = 0;
+    c->mf_last.resize((size_t)(c->mf_last_sets + 1) * n);
+    memcpy(c->mf_last.data() + (size_t)c->mf_last_sets * n, f, n * sizeof(oatgpu_filtered));
+    c->mf_last_sets++;
+}
+
 // out: the foreground result (nullptr: not wanted); markers / mean: the marker records of the frame set, [n][M] and [n], from the
 // slot's host-mapped record set (nullptr: not wanted).  With the marker pipeline on the slot's marker work is waited for in
 // any case: the slot's planes and records are free for the next frame set when this returns.
@@ -2228,6 +2253,8 @@ static int collect_frame(oatgpu_ctx *c, oatgpu_position *out, oatgpu_position *m
             for (int s = 0; s < n; ++s)
                 for (int m = 0; m < M; ++m) to_position(mr[(size_t)m * n + s], &markers[(size_t)s * M + m]);
         if (mean) memcpy(mean, mr + (size_t)M * n, (size_t)n * sizeof(oatgpu_combined));
+        if (c->mf_on && markers)             // a marker-result call: what oatgpu_marker_filtered hands out
+            keep_filtered(c, (const MarkerFiltered *)((const MarkerCombined *)(mr + (size_t)M * n) + n));
         c->mk_last_slot = slot;
     }
     for (int s = 0; out && s < c->cfg.n_streams; ++s) {
@@ -2362,7 +2389,12 @@ extern "C" int oatgpu_track_markers_sequence_dev(oatgpu_ctx *c, const void *cons
 {
     if (!c || !markers) return fail(c, OATGPU_E_INVALID, "null argument");
     if (!c->mkp_on) return fail(c, OATGPU_E_INVALID, "the marker pipeline is off (oatgpu_set_marker_pipeline)");
-    return sequence_dev(c, frames_dev, n_frames, lr, fg, nullptr, nullptr, markers, mean);
+    if (c->ring_count) return fail(c, OATGPU_E_INVALID, "track_sequence while enqueued results are outstanding");
+    c->mf_append = true;                 // oatgpu_marker_filtered: the n_frames sets of this call
+    c->mf_last_sets = 0;
+    const int rc = sequence_dev(c, frames_dev, n_frames, lr, fg, nullptr, nullptr, markers, mean);
+    c->mf_append = false;
+    return rc;
 }
 
 extern "C" int oatgpu_track_outstanding(const oatgpu_ctx *c) { return c ? c->ring_count : 0; }
@@ -2613,6 +2645,12 @@ extern "C" int oatgpu_track_markers_dev(oatgpu_ctx *c, const void *frames_dev, d
     MarkerCombined *comb_dev = (MarkerCombined *)(c->mk_res + (size_t)M * n);
     launch_marker_combine(c->mk_res, M, c->mk_anchor, n, comb_dev, A);
     HIPCHK(c, hipGetLastError());
+    if (c->mf_on) {       // the chain, behind the combiner and before the copy back
+        const MarkerCombined *comb_c = comb_dev;
+        launch_marker_filters(c->mf_params, c->mf_state, &comb_c, &c->mf_out, n, 1, A);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->mf_out_host, c->mf_out, (size_t)n * sizeof(MarkerFiltered), hipMemcpyDeviceToHost, A));
+    }
     const size_t res_bytes = (size_t)M * n * sizeof(ResultRec) + (size_t)n * sizeof(MarkerCombined);
     HIPCHK(c, hipMemcpyAsync(c->mk_res_host, c->mk_res, res_bytes, hipMemcpyDeviceToHost, A));
     HIPCHK(c, hipStreamSynchronize(A));
@@ -2620,7 +2658,85 @@ extern "C" int oatgpu_track_markers_dev(oatgpu_ctx *c, const void *frames_dev, d
     for (int s = 0; s < n; ++s)
         for (int m = 0; m < M; ++m) to_position(r[(size_t)m * n + s], &markers[(size_t)s * M + m]);
     if (mean) memcpy(mean, r + (size_t)M * n, (size_t)n * sizeof(oatgpu_combined));
+    if (c->mf_on) keep_filtered(c, c->mf_out_host);
     return OATGPU_OK;
+}
+
+// The filter chain behind the combined record: `posifilt kalman` -> `posifilt homography` -> `posifilt region` (oatgpu.h).
+// Everything is checked before anything changes.
+extern "C" int oatgpu_set_marker_filters(oatgpu_ctx *c, const oatgpu_marker_filters *f)
+{
+    if (!c) return OATGPU_E_INVALID;
+    if (c->ring_count || c->staged_count) return fail(c, OATGPU_E_INVALID, "set_marker_filters while enqueued results are outstanding");
+    if (c->mk_n == 0) return fail(c, OATGPU_E_INVALID, "marker sets are not configured (oatgpu_set_markers)");
+    const bool on = f && (f->kalman || f->homography || f->n_regions > 0);
+    std::vector<MarkerFilterParams> hp(on ? 1 : 0);      // (8 KiB: not on the stack)
+    if (on) {
+        MarkerFilterParams &p = hp[0];
+        memset(&p, 0, sizeof p);
+        if (f->kalman) {
+            if (!(f->dt > 0) || !(f->timeout >= 0) || !(f->sigma_accel >= 0) || !(f->sigma_noise >= 0) || !(f->timeout / f->dt < 2147483647.0))
+                return fail(c, OATGPU_E_INVALID, "kalman: dt must be > 0, timeout / sigma-accel / sigma-noise >= 0");
+            p.kalman = 1;
+            p.dt = f->dt; p.sig_accel = f->sigma_accel; p.sig_noise = f->sigma_noise;
+            p.threshold = (int)(f->timeout / f->dt);                 // KalmanFilter2D.cpp:74-76
+        }
+        if (f->homography) {
+            p.homography = 1;
+            for (int i = 0; i < 9; ++i) p.h[i] = f->h[i];
+        }
+        if (f->n_regions < 0 || f->n_regions > kMaxRegions) return fail(c, OATGPU_E_INVALID, "at most %d regions (got %d)", kMaxRegions, f->n_regions);
+        if (f->n_regions > 0 && !f->regions) return fail(c, OATGPU_E_INVALID, "null argument");
+        p.n_regions = f->n_regions;
+        int at = 0;
+        for (int r = 0; r < f->n_regions; ++r) {
+            const oatgpu_region &g = f->regions[r];
+            if (!memchr(g.name, 0, sizeof g.name))
+                return fail(c, OATGPU_E_INVALID, "region %d: a name takes at most %d bytes", r, (int)sizeof g.name - 1);
+            if (g.n_points < 0 || g.n_points > kMaxRegionPoints)
+                return fail(c, OATGPU_E_INVALID, "region %d (%s): at most %d points (got %d)", r, g.name, kMaxRegionPoints, g.n_points);
+            if (g.n_points > 0 && !g.xy) return fail(c, OATGPU_E_INVALID, "null argument");
+            p.region[r][0] = at; p.region[r][1] = g.n_points;
+            for (int i = 0; i < g.n_points; ++i, ++at)
+                for (int k = 0; k < 2; ++k) {
+                    const double v = nearbyint(g.xy[2 * i + k]);     // (cv::Point)cv::Point2d: cvRound, ties to even
+                    if (!(fabs(v) <= 32767.0)) return fail(c, OATGPU_E_INVALID, "region %d (%s): point %d is beyond +-32767", r, g.name, i);
+                    p.verts[at][k] = (int)v;
+                }
+        }
+    }
+    int rc = open_sync(c);
+    if (rc) return rc;
+    if (!on) { free_marker_filters(c); return OATGPU_OK; }
+    const size_t n = (size_t)c->cfg.n_streams;
+    if (!c->mf_params) {
+        bool ok = hipMalloc((void **)&c->mf_params, sizeof(MarkerFilterParams)) == hipSuccess;
+        ok = ok && hipMalloc((void **)&c->mf_state, n * sizeof(KalmanState)) == hipSuccess;
+        ok = ok && hipMalloc((void **)&c->mf_out, n * sizeof(MarkerFiltered)) == hipSuccess;
+        ok = ok && hipHostMalloc((void **)&c->mf_out_host, n * sizeof(MarkerFiltered), hipHostMallocDefault) == hipSuccess;
+        if (!ok) {
+            const hipError_t e = hipGetLastError();
+            free_marker_filters(c);
+            return fail(c, OATGPU_E_NOMEM, "marker filters: allocation failed: %s", hipGetErrorString(e));
+        }
+    }
+    HIPCHK(c, hipMemcpy(c->mf_params, hp.data(), sizeof(MarkerFilterParams), hipMemcpyHostToDevice));
+    launch_kalman_reset(c->mf_state, (int)n, 0u, c->stream);          // every stream's filter from the reference's initial state
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->mf_on = true;
+    c->mf_last_sets = 0;
+    return OATGPU_OK;
+}
+
+extern "C" int oatgpu_marker_filtered(oatgpu_ctx *c, oatgpu_filtered *out, int32_t max_sets)
+{
+    if (!c || !out) return fail(c, OATGPU_E_INVALID, "null argument");
+    if (!c->mf_on) return fail(c, OATGPU_E_INVALID, "no filter chain is configured (oatgpu_set_marker_filters)");
+    if (c->mf_last_sets == 0) return fail(c, OATGPU_E_INVALID, "no marker result has been delivered since the filter chain was configured");
+    if (max_sets < c->mf_last_sets) return fail(c, OATGPU_E_INVALID, "room for %d frame sets, the latest call delivered %d", max_sets, c->mf_last_sets);
+    memcpy(out, c->mf_last.data(), (size_t)c->mf_last_sets * c->cfg.n_streams * sizeof(oatgpu_filtered));
+    return c->mf_last_sets;
 }
 
 extern "C" int oatgpu_track_markers(oatgpu_ctx *c, const uint8_t *const *frames_host, int32_t n, double lr, oatgpu_position *fg,

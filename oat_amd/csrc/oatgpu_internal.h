@@ -286,4 +286,26 @@ void launch_marker_combine(const ResultRec *results, int M, int anchor, int n_st
 void launch_marker_combine_frames(const ResultRec *const *results, int M, int anchor, int n_streams, MarkerCombined *const *out,
                                   ResultRec *const *copy, int nf, hipStream_t st);
 
+// The filter chain behind the combined record (oatgpu_set_marker_filters): kalman -> homography -> region, every member
+// switched on its own.  MarkerFiltered is oatgpu_filtered's layout.
+constexpr int kMaxRegions = 16, kMaxRegionPoints = 64;
+struct MarkerFiltered {
+    int position_valid, velocity_valid, heading_valid, region_valid;
+    int region, reserved_;       // index of the first region hit, -1: none
+    double x, y, vx, vy, hx, hy;
+};
+struct MarkerFilterParams {      // in DEVICE memory, read uniformly by every lane
+    int kalman, threshold;       // threshold: not_found_count_threshold_ = (int)(timeout / dt)
+    double dt, sig_accel, sig_noise;
+    int homography, n_regions;
+    double h[9];
+    int region[kMaxRegions][2];  // first vertex and number of vertices of each region, in configured order
+    int verts[kMaxRegions * kMaxRegionPoints][2];    // (x, y) after (cv::Point) of the configured point
+};
+// The chain on the nf (1 or 2) frames of a step, IN ORDER in one lane per stream: frame i reads in[i] (k_marker_combine's
+// records, written by an earlier launch on the same HIP stream), writes out[i] (may be host-mapped memory: 64-bit stores) and
+// advances state[s] (the ticket of KalmanState is not used: every launch of a context runs behind the one before)
+void launch_marker_filters(const MarkerFilterParams *params, KalmanState *state, const MarkerCombined *const *in,
+                           MarkerFiltered *const *out, int n_streams, int nf, hipStream_t st);
+
 }  // namespace oatgpu

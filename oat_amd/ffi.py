@@ -67,6 +67,25 @@ class Combined(C.Structure):
                 ("n_valid", C.c_int32), ("x", C.c_double), ("y", C.c_double), ("hx", C.c_double), ("hy", C.c_double)]
 
 
+class Region(C.Structure):
+    """oatgpu_region: one `posifilt region` polygon (name of at most 9 bytes, n_points x/y pairs)."""
+    _fields_ = [("name", C.c_char * 10), ("n_points", C.c_int32), ("xy", C.POINTER(C.c_double))]
+
+
+class MarkerFilters(C.Structure):
+    """oatgpu_marker_filters: the chain kalman -> homography -> region behind the combined record."""
+    _fields_ = [("kalman", C.c_int32), ("dt", C.c_double), ("timeout", C.c_double), ("sigma_accel", C.c_double),
+                ("sigma_noise", C.c_double), ("homography", C.c_int32), ("h", C.c_double * 9), ("n_regions", C.c_int32),
+                ("regions", C.POINTER(Region))]
+
+
+class Filtered(C.Structure):
+    """oatgpu_filtered: the combined record of one camera behind the chain."""
+    _fields_ = [("position_valid", C.c_int32), ("velocity_valid", C.c_int32), ("heading_valid", C.c_int32),
+                ("region_valid", C.c_int32), ("region", C.c_int32), ("reserved_", C.c_int32), ("x", C.c_double), ("y", C.c_double),
+                ("vx", C.c_double), ("vy", C.c_double), ("hx", C.c_double), ("hy", C.c_double)]
+
+
 E_RING_FULL = -4
 E_RING_EMPTY = -5
 ABI_VERSION = 9          # must equal OATGPU_ABI_VERSION of include/oatgpu.h
@@ -117,6 +136,8 @@ SIGNATURES = {
     "oatgpu_track_collect_markers": (C.c_int, [_ctx, C.POINTER(Position), C.POINTER(Position), C.POINTER(Combined)]),
     "oatgpu_track_markers_sequence_dev": (C.c_int, [_ctx, C.POINTER(C.c_void_p), C.c_int32, C.c_double, C.POINTER(Position),
                                                     C.POINTER(Position), C.POINTER(Combined)]),
+    "oatgpu_set_marker_filters": (C.c_int, [_ctx, C.POINTER(MarkerFilters)]),
+    "oatgpu_marker_filtered": (C.c_int, [_ctx, C.POINTER(Filtered), C.c_int32]),
     "oatgpu_mog_apply": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_mog_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_bgr2hsv": (C.c_int, [_ctx, _u8p, _u8p]),

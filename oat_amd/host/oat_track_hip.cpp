@@ -42,6 +42,8 @@
 #include "component.hpp"
 #include "scatter_tracker.hpp"
 #include <chrono>
+#include <cmath>
+#include <cstring>
 #include <deque>
 #include <fstream>
 #include <sched.h>
@@ -170,6 +172,123 @@ static std::vector<oatgpu_marker> read_marker_tables(const std::string &file, co
     return out;
 }
 
+// ---- the filter chain behind the combined record (oatgpu_set_marker_filters): --mean-kalman, --mean-homography, --region ----
+// One `posifilt region` polygon: --region 'NAME=[[x0,y0],[x1,y1],...]' (repeatable, command-line order is region order), or a
+// [[KEY.region]] table of the -c file with name = "NAME" and points = [[x0,y0],...].  The library's limits are checked here,
+// before a device is opened: at most 16 regions of at most 64 points, a name of 1 to 9 bytes (the reference's strcpy overruns its
+// 10-byte field with more), every coordinate within +-32767 once rounded.
+struct RegionDef {
+    std::string name;
+    std::vector<double> xy;
+};
+static std::vector<double> parse_region_points(const std::string &text, const std::string &where)
+{
+    auto bad = [&](const char *what) { return std::runtime_error(where + ": " + what + " in '" + text + "' (expected [[x0,y0],[x1,y1],...])"); };
+    const char *p = text.c_str();
+    auto skip = [&] { while (*p == ' ' || *p == '\t') ++p; };
+    auto number = [&](double &v) {
+        skip();
+        char *end = nullptr;
+        v = strtod(p, &end);
+        if (end == p) throw bad("expected a number");
+        p = end;
+        skip();
+    };
+    std::vector<double> xy;
+    skip();
+    if (*p++ != '[') throw bad("expected '['");
+    skip();
+    while (*p != ']') {
+        if (*p++ != '[') throw bad("a point is a pair [x,y]");
+        double x, y;
+        number(x);
+        if (*p++ != ',') throw bad("a point is a pair [x,y]");
+        number(y);
+        if (*p++ != ']') throw bad("a point is a pair [x,y]");
+        xy.push_back(x); xy.push_back(y);
+        skip();
+        if (*p == ',') { ++p; skip(); if (*p == ']') throw bad("expected a point"); }
+        else if (*p != ']') throw bad("expected ',' or ']'");
+    }
+    ++p;
+    skip();
+    if (*p) throw bad("text behind the closing ']'");
+    return xy;
+}
+static void check_region(const RegionDef &r, const std::string &where)
+{
+    if (r.name.empty()) throw std::runtime_error(where + ": a region needs a name");
+    if (r.name.size() > 9) throw std::runtime_error(where + ": the name '" + r.name + "' is longer than 9 bytes");
+    if (r.xy.size() / 2 > 64) throw std::runtime_error(where + ": region '" + r.name + "' has " + std::to_string(r.xy.size() / 2) + " points, at most 64");
+    for (double v : r.xy)
+        if (!(std::fabs(std::nearbyint(v)) <= 32767.0)) throw std::runtime_error(where + ": region '" + r.name + "' has a coordinate beyond +-32767");
+}
+static RegionDef parse_region(const std::string &text)
+{
+    const size_t eq = text.find('=');
+    if (eq == std::string::npos) throw std::runtime_error("--region: expected NAME=[[x0,y0],[x1,y1],...], got '" + text + "'");
+    RegionDef r;
+    r.name = text.substr(0, eq);
+    r.xy = parse_region_points(text.substr(eq + 1), "--region");
+    check_region(r, "--region");
+    return r;
+}
+// every [[KEY.region]] table of the -c file, in file order; points may span lines
+static std::vector<RegionDef> read_region_tables(const std::string &file, const std::string &key)
+{
+    std::vector<RegionDef> out;
+    std::ifstream in(file);
+    if (!in) return out;
+    auto trim = [](std::string t) {
+        const size_t a = t.find_first_not_of(" \t\r\n"), b = t.find_last_not_of(" \t\r\n");
+        return a == std::string::npos ? std::string() : t.substr(a, b - a + 1);
+    };
+    auto next = [&](std::string &line) {
+        if (!std::getline(in, line)) return false;
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) line = line.substr(0, hash);
+        line = trim(line);
+        return true;
+    };
+    auto depth = [](const std::string &v) { int d = 0; for (char ch : v) d += ch == '[' ? 1 : ch == ']' ? -1 : 0; return d; };
+    const std::string header = "[[" + key + ".region]]", where = header;
+    std::vector<bool> named, pointed;
+    std::string line;
+    bool inside = false;
+    while (next(line)) {
+        if (line.empty()) continue;
+        if (line.front() == '[' && line.find('=') == std::string::npos) {
+            std::string h;
+            for (char ch : line) if (ch != ' ' && ch != '\t') h += ch;
+            inside = h == header;
+            if (inside) { out.emplace_back(); named.push_back(false); pointed.push_back(false); }
+            continue;
+        }
+        if (!inside) continue;
+        const size_t eq = line.find('=');
+        if (eq == std::string::npos) throw std::runtime_error(where + ": expected key = value");
+        const std::string k = trim(line.substr(0, eq));
+        std::string val = trim(line.substr(eq + 1)), more;
+        while (depth(val) > 0 && next(more)) val += " " + more;
+        if (k == "name") {
+            if (val.size() < 2 || (val.front() != '"' && val.front() != '\'') || val.back() != val.front())
+                throw std::runtime_error(where + ": name must be a string, got " + val);
+            out.back().name = val.substr(1, val.size() - 2);
+            named.back() = true;
+        } else if (k == "points") {
+            out.back().xy = parse_region_points(val, where);
+            pointed.back() = true;
+        } else {
+            throw std::runtime_error(where + ": unknown key '" + k + "' (name, points)");
+        }
+    }
+    for (size_t i = 0; i < out.size(); ++i) {
+        if (!named[i] || !pointed[i]) throw std::runtime_error(where + ": a region table holds name and points");
+        check_region(out[i], where);
+    }
+    return out;
+}
+
 class BatchedTracker : public Component {
 public:
     // stream_base / n_total: where this shard's cameras sit in the command line's SOURCE list (model file names)
@@ -214,6 +333,12 @@ public:
     int heading_anchor_{-1};        // --heading-anchor (`posicom mean`), -1: no heading
     int marker_ring_{0};            // --marker-ring D: marker mode through the staged loop and a result ring of D (0: the synchronous step)
     std::vector<std::vector<std::string>> marker_sink_addresses_;
+    // the filter chain behind the combined record (--mean-kalman / --mean-homography / --region): the camera's SINK then carries
+    // the FILTERED Position2D; Kalman parameters are dt_ .. sig_noise_ above
+    bool mean_kalman_{false}, mean_homography_on_{false};
+    double mean_homography_[9]{1, 0, 0, 0, 1, 0, 0, 0, 1};
+    std::vector<RegionDef> regions_;
+    bool chain_on() const { return mean_kalman_ || mean_homography_on_ || !regions_.empty(); }
     ~BatchedTracker() override
     {
         if (!model_file_.empty() && gpu_.ctx)
@@ -313,6 +438,22 @@ protected:
             marker_results_.resize((size_t)n_ * M);
             combined_.resize(n_);
             if (marker_ring_) gpu_.check(oatgpu_set_marker_pipeline(gpu_.ctx, 1));
+            if (chain_on()) {
+                std::vector<oatgpu_region> rs(regions_.size());
+                for (size_t i = 0; i < rs.size(); ++i) {
+                    std::strncpy(rs[i].name, regions_[i].name.c_str(), sizeof rs[i].name);
+                    rs[i].n_points = (int32_t)(regions_[i].xy.size() / 2);
+                    rs[i].xy = regions_[i].xy.data();
+                }
+                oatgpu_marker_filters f{};
+                f.kalman = mean_kalman_; f.dt = dt_; f.timeout = timeout_; f.sigma_accel = sig_accel_; f.sigma_noise = sig_noise_;
+                f.homography = mean_homography_on_;
+                std::copy(mean_homography_, mean_homography_ + 9, f.h);
+                f.n_regions = (int32_t)rs.size();
+                f.regions = rs.data();
+                gpu_.check(oatgpu_set_marker_filters(gpu_.ctx, &f));
+                filtered_.resize(n_);
+            }
         }
         return true;
     }
@@ -347,7 +488,10 @@ protected:
             if (pending_.empty()) return;
             if (only_if_ready && oatgpu_track_ready(gpu_.ctx) != 1) return;
             if (marker_ring_)
+            {
                 gpu_.check(oatgpu_track_collect_markers(gpu_.ctx, results_.data(), marker_results_.data(), combined_.data()));
+                fetch_filtered();
+            }
             else
                 gpu_.check(oatgpu_track_collect(gpu_.ctx, results_.data()));
             pub_samples_ = std::move(pending_.front());
@@ -373,6 +517,13 @@ protected:
         *shared = pos;
         sink.post();
     }
+    // the filtered records of the frame set the marker call before this has just delivered
+    void fetch_filtered()
+    {
+        if (!chain_on()) return;
+        const int got = oatgpu_marker_filtered(gpu_.ctx, filtered_.data(), 1);
+        if (got != 1) gpu_.check(got < 0 ? got : OATGPU_E_INVALID);
+    }
     int process_markers()
     {
         std::vector<Sample> samples(n_);
@@ -388,6 +539,7 @@ protected:
         }
         gpu_.check(oatgpu_track_markers(gpu_.ctx, frame_ptrs_.data(), n_, learning_coeff_, results_.data(), marker_results_.data(),
                                         combined_.data()));
+        fetch_filtered();
         for (int s = 0; s < n_; ++s) frame_sources_[s].post();
         for (int s = 0; s < n_; ++s) publish_markers(s, samples[s]);
         ++rounds_;
@@ -412,6 +564,20 @@ protected:
         pos.position.x = c.x; pos.position.y = c.y;
         pos.heading_valid = c.heading_valid != 0;
         pos.heading.x = c.hx; pos.heading.y = c.hy;
+        if (chain_on()) {                                               // ... behind posifilt kalman / homography / region
+            const oatgpu_filtered &f = filtered_[s];
+            pos.position_valid = f.position_valid != 0;
+            pos.position.x = f.x; pos.position.y = f.y;
+            pos.velocity_valid = f.velocity_valid != 0;
+            pos.velocity.x = f.vx; pos.velocity.y = f.vy;
+            pos.heading_valid = f.heading_valid != 0;
+            pos.heading.x = f.hx; pos.heading.y = f.hy;
+            if (f.region_valid) {                                       // RegionFilter2D.cpp:140-146
+                pos.region_valid = true;
+                std::strncpy(pos.region, regions_[(size_t)f.region].name.c_str(), sizeof pos.region - 1);
+            }
+            if (mean_homography_on_) pos.setCoordSystem(DistanceUnit::WORLD, mean_homography_);   // HomographyTransform2D.cpp:102
+        }
         put(position_sinks_[s], shared_positions_[s], pos);
     }
 
@@ -493,6 +659,7 @@ protected:
     std::vector<Position2D *> marker_shared_;
     std::vector<oatgpu_position> marker_results_;      // [n][M]
     std::vector<oatgpu_combined> combined_;            // [n]
+    std::vector<oatgpu_filtered> filtered_;            // [n] the combined records behind the filter chain
     std::deque<std::vector<Sample>> pending_;  // Samples of the frames whose results are still on the device
     std::vector<Sample> pub_samples_;          // ... and of the result set that is being handed out (publish_some)
     bool collected_{false};
@@ -506,7 +673,7 @@ int main(int argc, char **argv)
         Options o = Options::parse(argc, argv,
             {{"a", "adaptation-coeff"}, {"H", "h-thresh"}, {"S", "s-thresh"}, {"V", "v-thresh"}, {"e", "erode"},
              {"d", "dilate"}, {"T", "timeout"}, {"n", "sigma-noise"}, {"f", "mask"}, {"h", "help"}, {"v", "version"}},
-            {"help", "version", "kalman", "timing", "print-partition"});
+            {"help", "version", "kalman", "timing", "print-partition", "mean-kalman"});
         if (o.has("version")) { std::cout << "oat-track-hip (MI355X drop-in, liboatgpu ABI " << oatgpu_abi_version() << ")\n"; return 0; }
         if (o.has("help") || o.positional.size() != 2) {
             std::cout << "Usage: oat-track-hip SOURCE[,SOURCE..] SINK[,SINK..] [-a coeff] [-H [lo,hi]] [-S ..] [-V ..] [-e n] [-d n] [--area [min,max]]\n"
@@ -529,6 +696,15 @@ int main(int argc, char **argv)
                          "       [--marker-ring D]    (D >= 2; marker-ring in a -c file) marker mode through the pipelined loop: the cameras are\n"
                          "                            staged one by one, two frames a launch, results are published up to D - 1 rounds behind.\n"
                          "                            Without it a marker round is one synchronous step.\n"
+                         "       [--mean-kalman [--dt s] [-T|--timeout s] [--sigma-accel a] [-n|--sigma-noise n]]  [--mean-homography [h11,...,h33]]\n"
+                         "       [--region 'NAME=[[x0,y0],[x1,y1],...]']...\n"
+                         "                            (all three need --marker) the filters of a marker rig, behind posicom mean: posifilt kalman,\n"
+                         "                            posifilt homography and posifilt region on the mean position, in this order, each on its own\n"
+                         "                            switch; the camera's SINK then carries the filtered position: position and velocity from the\n"
+                         "                            Kalman filter, the heading through the homography, the name of the first --region (command-line\n"
+                         "                            order; at most 16 of at most 64 points, names of at most 9 bytes) that holds the position.  With\n"
+                         "                            or without --marker-ring; the per-marker sinks are unchanged.  In a -c file: mean-kalman = true,\n"
+                         "                            mean-homography = [..], and one [[track.region]] table per region with name and points.\n"
                          "N SOURCEs / N SINKs: N cameras batched into one device pass per frame; SOURCE i feeds SINK i.\n"
                          "--gpu-index N0,N1,..: the cameras are split into contiguous blocks, one per listed device (own context and thread).\n"
                          "--ingest-root D0 (with --gpu-index D0,D1,..): all frames are ingested on device D0 and scattered to their devices\n"
@@ -540,8 +716,9 @@ int main(int argc, char **argv)
         if ((o.has("camera-matrix") || o.has("distortion-coeffs")) && o.has("undistort-key")) throw std::runtime_error(ud_exclusive);
         o.apply_config({"adaptation-coeff", "h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "model-file",
                         "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "gpu-index", "ring", "mask", "thresh", "homography", "stage-copy", "timing",
-                        "ingest-root", "print-partition", "camera-matrix", "distortion-coeffs", "undistort-key", "marker-sinks", "heading-anchor", "marker-ring"},
-                       {"kalman", "timing", "print-partition"});
+                        "ingest-root", "print-partition", "camera-matrix", "distortion-coeffs", "undistort-key", "marker-sinks", "heading-anchor", "marker-ring",
+                        "mean-kalman", "mean-homography"},
+                       {"kalman", "timing", "print-partition", "mean-kalman"});
         const std::vector<std::string> sources = split_list(o.positional[0]), sinks = split_list(o.positional[1]);
         if (sources.size() != sinks.size()) throw std::runtime_error("need as many SINKs as SOURCEs");
         // marker sets: --marker (repeatable) or the [[KEY.marker]] tables of the -c file; refused with what the synchronous
@@ -551,7 +728,15 @@ int main(int argc, char **argv)
         else if (!o.config_file.empty()) markers = read_marker_tables(o.config_file, o.config_key);
         std::vector<std::vector<std::string>> marker_sinks;
         int heading_anchor = -1, marker_ring = 0;
+        // the filter chain behind the combined record: --region (repeatable) or the [[KEY.region]] tables of the -c file
+        std::vector<RegionDef> regions;
+        double mean_h[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        bool mean_homography = false;
         if (markers.empty()) {
+            for (const char *k : {"mean-kalman", "mean-homography", "region"})
+                if (o.has(k)) throw std::runtime_error(std::string("--") + k + " filters the mean position of a marker set: it needs at least one --marker");
+            if (!o.config_file.empty() && !read_region_tables(o.config_file, o.config_key).empty())
+                throw std::runtime_error("[[" + o.config_key + ".region]] (--region) filters the mean position of a marker set: it needs at least one --marker");
             if (o.has("marker-sinks") || o.has("heading-anchor")) throw std::runtime_error("--marker-sinks / --heading-anchor need at least one --marker");
             if (o.has("marker-ring")) throw std::runtime_error("--marker-ring needs at least one --marker");
         } else {
@@ -563,11 +748,22 @@ int main(int argc, char **argv)
                 marker_ring = (int)v;
             }
             for (const char *k : {"kalman", "homography", "ingest-root", "thresh"})
-                if (o.has(k)) throw std::runtime_error(std::string("--marker does not go with --") + k);
+                if (o.has(k)) throw std::runtime_error(std::string("--marker does not go with --") + k +
+                                                       (k[0] == 'k' ? " (the filter of a marker rig's mean position is --mean-kalman)"
+                                                        : k[0] == 'h' ? " (the homography of a marker rig's mean position is --mean-homography)" : ""));
             for (const char *k : {"h-thresh", "s-thresh", "v-thresh"})
                 if (o.has(k)) throw std::runtime_error(std::string("--marker does not go with --") + k + ": each marker has its own window (H= S= V= inside --marker)");
             if (o.num("ring", 1, 1, 64) > 1) throw std::runtime_error("--marker does not go with --ring > 1: the ring of marker mode is --marker-ring D (without it the marker step is synchronous, one round of frames at a time)");
             if (markers.size() > 8) throw std::runtime_error("--marker: at most 8 markers");
+            if (o.all.count("region")) for (const std::string &r : o.all["region"]) regions.push_back(parse_region(r));
+            else if (!o.config_file.empty()) regions = read_region_tables(o.config_file, o.config_key);
+            if (regions.size() > 16) throw std::runtime_error("--region: " + std::to_string(regions.size()) + " regions, at most 16");
+            if (o.has("mean-homography")) {
+                Options h;
+                h.kv["--mean-homography"] = o.kv["mean-homography"];
+                mean_homography = h.arr9("--mean-homography", mean_h);
+            }
+            if (o.has("mean-kalman") && !(o.num("dt", 0.02, 0, 1e9) > 0)) throw std::runtime_error("--mean-kalman: --dt must be > 0");
             std::vector<std::string> lists;
             if (o.all.count("marker-sinks")) lists = o.all["marker-sinks"];
             else if (o.has("marker-sinks")) {                              // the -c file: "a,b" or ["a,b", "c,d"]
@@ -693,6 +889,10 @@ int main(int argc, char **argv)
             t->timeout_ = o.num("timeout", 0.0, 0, 1e18);
             t->sig_accel_ = o.num("sigma-accel", 5.0, 0, 1e18);
             t->sig_noise_ = o.num("sigma-noise", 0.0, 0, 1e18);
+            t->mean_kalman_ = o.has("mean-kalman");
+            t->mean_homography_on_ = mean_homography;
+            std::copy(mean_h, mean_h + 9, t->mean_homography_);
+            t->regions_ = regions;
             shards.push_back(std::move(t));
         }
         if (shards.size() == 1) return shards[0]->run();

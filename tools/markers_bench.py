@@ -21,7 +21,12 @@ The PIPELINED legs (oatgpu_set_marker_pipeline), a host clock around calls that 
   (b) the synchronous marker step;  (c) oatgpu_track_markers_sequence_dev;  (d) M plain contexts, each through
   oatgpu_track_sequence_dev, summed;  (e) ONE plain context through oatgpu_track_sequence_dev -- the floor, the marker work
   fully hidden.  With --parent (a library without the pipelined path, e.g. --tree PARENT_CHECKOUT) only the legs it has: the
-  synchronous marker step -- leg (a) -- and (e); its own repeats are the noise floor."""
+  synchronous marker step -- leg (a) -- and (e); its own repeats are the noise floor.
+
+    python tools/markers_bench.py --filters [--pipelined ...]
+The filter chain behind the combined record (oatgpu_set_marker_filters) on every marker leg, synchronous and pipelined: all
+three members on -- posifilt kalman, posifilt homography, posifilt region with two regions (the left and the right half of
+the frame).  The same command without --filters is the chain-off step; profiles/markers_filters_bench.txt has the recipe."""
 import argparse
 import json
 import os
@@ -37,6 +42,15 @@ SHAPES = [("1x4K", 1, 2160, 3840, 7, 7), ("16x1080p", 16, 1080, 1920, 3, 7), ("1
 WINDOWS = [dict(h=(100, 125), s=(150, 256), v=(100, 256)), dict(h=(0, 20), s=(150, 256), v=(100, 256)),
            dict(h=(50, 70), s=(150, 256), v=(100, 256))]
 AREA = (20.0, 1e6)
+
+
+def filters(rows, cols):
+    """HotPath.set_marker_filters keywords of --filters: all three members, two regions"""
+    half = cols // 2
+    return dict(kalman=dict(dt=0.02, timeout=0.2, sigma_accel=5.0, sigma_noise=1.0),
+                homography=[[0.01, 0, -0.005 * cols], [0, 0.01, -0.005 * rows], [0, 0, 1]],
+                regions=[("left", [(0, 0), (half, 0), (half, rows), (0, rows)]),
+                         ("right", [(half, 0), (cols, 0), (cols, rows), (half, rows)])])
 
 
 def ktrace(path, steps_hint=None):
@@ -116,6 +130,8 @@ def pipelined(a):
             markers = [dict(w, erode=ero, dilate=dil, area=AREA) for w in WINDOWS[:M]]
             hp = ctx(dict(h=(0, 256), s=(0, 256), v=(1, 256)))
             hp.set_markers(markers, heading_anchor=0)
+            if a.filters:
+                hp.set_marker_filters(**filters(rows, cols))
 
             def sync_steps():
                 for p_ in ptrs:
@@ -140,7 +156,7 @@ def pipelined(a):
         del pool
         torch.cuda.empty_cache()
     print(json.dumps({"tool": "markers_bench", "mode": "pipelined", "unit": "us a frame set, host clock, one figure a round",
-                      "parent": a.parent, "library": os.path.relpath(oat_amd.lib_path(), os.path.abspath(a.tree)), "shapes": out,
+                      "parent": a.parent, "filters": a.filters, "library": os.path.relpath(oat_amd.lib_path(), os.path.abspath(a.tree)), "shapes": out,
                       "device": torch.cuda.get_device_name(0)}))
 
 
@@ -148,6 +164,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pipelined", action="store_true", help="the pipelined legs (see the module's text)")
     ap.add_argument("--parent", action="store_true", help="with --pipelined: a library without the pipelined marker path")
+    ap.add_argument("--filters", action="store_true", help="the filter chain (kalman, homography, two regions) on every marker leg")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--sets", type=int, default=256, help="frame sets a timed call (--pipelined)")
     ap.add_argument("--steps", type=int, default=200)
@@ -189,6 +206,8 @@ def main():
         for M in (() if a.baseline_only else (1, 2, 3)):
             hp = ctx(dict(h=(0, 256), s=(0, 256), v=(1, 256)))                         # the non-zero window
             hp.set_markers([dict(w, erode=ero, dilate=dil, area=AREA) for w in WINDOWS[:M]], heading_anchor=0)
+            if a.filters:
+                hp.set_marker_filters(**filters(rows, cols))
             st = torch.cuda.ExternalStream(hp.get_stream())
             ev, wall = timed(torch, st, lambda t: hp.track_markers_dev(ptrs[t % frames]), a.steps, a.warmup)
             hp.close()
@@ -207,7 +226,7 @@ def main():
         del pool
         torch.cuda.empty_cache()
     print(json.dumps({"tool": "markers_bench", "entry": "oatgpu_track_markers_dev | oatgpu_track_batch_dev", "unit": "us a step, median",
-                      "library": os.path.relpath(oat_amd.lib_path(), os.path.abspath(a.tree)), "baseline_only": a.baseline_only, "shapes": out, "device": torch.cuda.get_device_name(0)}))
+                      "library": os.path.relpath(oat_amd.lib_path(), os.path.abspath(a.tree)), "baseline_only": a.baseline_only, "filters": a.filters, "shapes": out, "device": torch.cuda.get_device_name(0)}))
 
 
 if __name__ == "__main__":
