@@ -129,12 +129,12 @@ def test_selected_blob_is_the_largest_external_component():
     assert hits > 100
 
 
-@pytest.mark.parametrize("k", [2, 3, 4, 5, 7, 10, 13])
+@pytest.mark.parametrize("k", [2, 3, 4, 5, 7, 10, 13, 31, 32, 33, 62, 63])
 def test_rect_morphology_equals_scipy_window_filters(k):
     """erode / dilate with a k x k rectangle: window [x - k//2, x - k//2 + k - 1] in both directions (anchor k/2,
     the kernel NOT reflected for dilation), outside the image 1 for erosion and 0 for dilation."""
     rng = np.random.default_rng(k)
-    for shape in ((37, 53), (8, 5), (64, 64), (1, 9)):
+    for shape in ((37, 53), (8, 5), (64, 64), (1, 9), (70, 29)):        # (70, 29): W < k from k = 31 on
         img = np.where(rng.random(shape) < 0.55, 255, 0).astype(np.uint8)
         ero = ndimage.minimum_filter(img, size=k, mode="constant", cval=255, origin=0)
         dil = ndimage.maximum_filter(img, size=k, mode="constant", cval=0, origin=0)
