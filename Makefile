@@ -12,7 +12,7 @@ OBJS     = $(CSRC)/kernels_mog.o $(CSRC)/kernels_blob.o $(CSRC)/kernels_kalman.o
 
 all: $(LIB) oracle
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/oatgpu_internal.h $(CSRC)/hsv_inline.h $(CSRC)/posfilt_inline.h include/oatgpu.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/oatgpu_internal.h $(CSRC)/hip_owned.h $(CSRC)/hsv_inline.h $(CSRC)/posfilt_inline.h include/oatgpu.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(LIB): $(OBJS)

@@ -7,6 +7,7 @@
 // the HIP kernels or fails with an error code.
 #include "../../include/oatgpu.h"
 #include "oatgpu_internal.h"
+#include "hip_owned.h"
 #include "posfilt_inline.h"
 
 #include <algorithm>
@@ -42,24 +43,94 @@ static inline const char *measure_env(const char *name)
 #endif
 }
 
-struct ProfStep { hipEvent_t e[5]; int frames = 1; };   // frames: what the K1 launch between e[0] and e[1] covered
+struct ProfStep { Event e[5]; int frames = 1; };   // frames: what the K1 launch between e[0] and e[1] covered
 struct Rate { float alphaT, alpha1, prune; int fresh; };   // A: K1 begin/end; B: back-half begin, after erode, end
 
+namespace { void release_streams(int device); }
+// the context's share of its device's streams (-1: none); declared FIRST in the context, so given back LAST, after every buffer and event
+struct StreamLease { int device = -1; ~StreamLease() { if (device >= 0) release_streams(device); } };
+
+// One scratch set of the back half: owns the 14 arrays tmp .. ready of its BlobBuffers (thr and nopark are the context's, every
+// set points at them).  Kernels take the plain BlobBuffers by value (b).
+struct Scratch {
+    BlobBuffers b{};
+    Scratch() = default;
+    Scratch(Scratch &&o) noexcept : b(std::exchange(o.b, BlobBuffers{})) {}
+    Scratch &operator=(Scratch &&o) noexcept { if (this != &o) { reset(); b = std::exchange(o.b, BlobBuffers{}); } return *this; }
+    ~Scratch() { reset(); }
+    bool alloc(const oatgpu_ctx *c, size_t planes = 0);      // planes: how many (0: one a camera stream)
+    void reset()
+    {
+        void *const own[] = {b.tmp, b.morph, b.fin, b.trans, b.carry, b.parent, b.acc, b.done, b.roots, b.nroots, b.wpre, b.rowinfo, b.lds_ok, b.ready};
+        for (void *p : own) if (p) hipFree(p);
+        b = BlobBuffers{};
+    }
+};
+
+// marker sets (oatgpu_set_markers; kernels_markers.hip): M colour windows per camera behind the one model pass.  Everything
+// below is made by oatgpu_set_markers and used by the synchronous marker step alone, on stream A.
+struct MarkerSet {
+    int n = 0;                                 // M; 0: markers off
+    int anchor = -1;                           // `posicom mean --heading-anchor`, -1: none
+    std::vector<oatgpu_marker> def;            // [M] erode / dilate / area of each marker (and its default window)
+    std::vector<RangeParams> win_host;         // [n][M] normalised colour windows, per camera and marker
+    DevMem<RangeParams> win;                   // ... on the device
+    DevMem<u64> planes;                        // [M][n][Palloc/64] k_marker_bits' output = launch_blob's src_bits
+    DevMem<u64> masks;                         // [M][3][n][Palloc/64] each marker's own tmp / morph / fin planes (the taps)
+    Scratch bb;                                // the rest of one back-half scratch set, shared by the markers (they run one after the other)
+    DevMem<ResultRec> res;                     // device: [M][n] result records, then [n] MarkerCombined
+    HostMem<ResultRec> res_host;               // page-locked mirror: one copy back a step
+    std::vector<const u64 *> tap_morph;        // [M] where marker m's mask after erode / dilate is
+};
+// the pipelined marker path (oatgpu_set_marker_pipeline): everything below is made by the switch, never inside a step.
+// A step's marker work: k_marker_bits on stream A right behind its per-pixel kernel (launch_marker_work), the back half of
+// all M x n planes and the combiner on B2 (a lone frame: on A), results into the slot's host-mapped record set.
+struct MarkerPipeline {
+    bool on = false;
+    bool table = false;                        // the one-launch back half takes this geometry and these markers (else: marker by marker)
+    int max_dil = 0;                           // largest dilation of the set: the row scan's LDS
+    DevMem<u64> planes;                        // [ring][M][n][Palloc/64] k_marker_bits' output, per ring slot
+    DevMem<u64> masks;                         // [ring][3][M][n][Palloc/64] the slot's tmp / morph / fin planes of every marker (the taps)
+    Scratch bb[2];                             // the rest of a back-half scratch set for M x n planes, one for each frame of a step
+    DevMem<BlobTab> tab;                       // [M][n] device table of the one-launch back half
+    DevMem<ResultRec> res;                     // device: [2][M][n] the step's result records, read by k_marker_combine
+    HostMem<ResultRec> rec;                    // host-mapped: [ring] sets of M x n ResultRec + n MarkerCombined, written by k_marker_combine through dev()
+    std::vector<Event> ev;                     // [ring] the marker work whose last frame sits in this slot is done
+    std::vector<int> ev_of;                    // [ring] slot -> the slot whose event covers its marker results
+    std::vector<const u64 *> tap_morph;        // [ring][M] where the MORPH tap of marker m of that slot is
+    Event bits_ev;                             // stream A: the step's k_marker_bits has finished
+    int last_slot = -1;                        // ring slot of the frame set collected last on the pipelined path; -1: the synchronous step was later
+    // a record set: M x n result records, n combined records, n filtered records (written only while a chain is configured)
+    size_t set_bytes = 0;                      // = M n sizeof(ResultRec) + n (sizeof(MarkerCombined) + sizeof(MarkerFiltered))
+};
+// the filter chain behind the combined record (oatgpu_set_marker_filters): kalman -> homography -> region in ONE launch
+// behind k_marker_combine on the same HIP stream.  Made by the setter, dropped with the marker set.
+struct MarkerFilters {
+    bool on = false;
+    DevMem<MarkerFilterParams> params;         // device: the chain's parameters and the region table
+    DevMem<KalmanState> state;                 // device: [n] the chain's own filter state, one per camera stream (not c->kal's)
+    DevMem<MarkerFiltered> out;                // device: [n] the synchronous step's filtered records
+    HostMem<MarkerFiltered> out_host;          // ... their page-locked mirror
+    std::vector<oatgpu_filtered> last;         // [sets][n] what the latest marker-result call delivered (oatgpu_marker_filtered)
+    int last_sets = 0;
+    bool append = false;                       // inside oatgpu_track_markers_sequence_dev: every collected set is kept
+};
+
 struct oatgpu_ctx {
+    StreamLease lease;
     oatgpu_config cfg;
     Geom g;
     hipStream_t stream = nullptr;   // stream A: uploads + the fused per-pixel kernel
-    bool have_shared = false;
     static constexpr int kNB = 3;                // back-half streams B0..B2
     static constexpr int kSets = 5;              // scratch sets of the back half: up to four for frames in flight + one for repairs
     bool b_used[kNB] = {};          // B streams this context has launched on (the only ones it ever has to drain)
     hipStream_t stream_b[kNB] = {}; // streams B0..B2: morphology + blob analysis, on the plain path frame t on B[t % 3]
                                     // (B[t % 2] for host frames), overlapped with later frames' per-pixel kernels and each other
-    hipEvent_t ev_k1[kNB] = {};    // the K1 whose back half runs on B[q] has finished (its threshold bits are ready)
+    Event ev_k1[kNB];            // the K1 whose back half runs on B[q] has finished (its threshold bits are ready)
     unsigned long long enq_total = 0, col_total = 0;  // pipelined frames enqueued / collected so far
     // cache policy of K1's slot-1..4 loads (kernels_mog.hip): streaming on dense models.  Two host-mapped
     // {live modes, samples} pairs filled alternately by k_density_probe; read one probe late, never waited for.
-    unsigned *dens_host = nullptr, *dens_dev = nullptr;
+    HostMem<unsigned> dens;
     unsigned long long dens_probes = 0;
     bool nt_loads = false;
     // back half: frames go through row scan + k_blob_lds ONLY (kBlobSpec) while that keeps working; a frame too busy
@@ -78,17 +149,18 @@ struct oatgpu_ctx {
     std::vector<Slot> slots;        // [ring_slots]
     int ring_slots = 0;                               // internal ring size (= ring_depth); one threshold-bit buffer per slot
     hipStream_t stream_c = nullptr;  // H2D copies of oatgpu_track_enqueue (created on first use)
-    uint8_t *frames_ring = nullptr;  // [ring_slots][n_streams*rows*cols*channels] staging for host frames
-    std::vector<hipEvent_t> copy_ev; // [ring_slots] frames of this slot have arrived
-    std::vector<hipEvent_t> copy_ev_s;   // [ring_slots][n_streams] ... and every single one of them (oatgpu_track_input_consumed_stream)
+    DevMem<uint8_t> frames_ring;     // [ring_slots][n_streams*rows*cols*channels] staging for host frames
+    std::vector<Event> copy_ev;      // [ring_slots] frames of this slot have arrived
+    std::vector<Event> copy_ev_s;        // [ring_slots][n_streams] ... and every single one of them (oatgpu_track_input_consumed_stream)
     hipStream_t stream_c2 = nullptr;     // second copy stream of the camera-by-camera path (shared per device)
-    hipEvent_t ev_c2 = nullptr;          // ... and its "all my copies of this set are done"
+    Event ev_c2;                         // ... and its "all my copies of this set are done"
     std::vector<char> staged;            // [n_streams] oatgpu_track_stage: frame of the NEXT set already on its way
     int staged_count = 0, stage_slot = -1;
     bool per_stream_copy_ev = false;     // recorded from the first per-stream call on
     bool last_copy_per_stream = false;   // the latest enqueue recorded them
     int last_copy_slot = -1;         // slot of the most recent oatgpu_track_enqueue (host frames)
     KalmanLaunch kal{};              // kal.state == nullptr: position filter off
+    DevMem<KalmanState> kal_state;   // ... the owner of kal.state
     bool kal_on = false;
     unsigned kal_ticket = 0;         // ticket of the next enqueued frame
     // Early dispatch of the blob workgroup (kernels_blob.hip): the row scans of a device-frame step go down B0 / B1 by frame
@@ -107,7 +179,7 @@ struct oatgpu_ctx {
                                      // 0 / 1 forced (measurement builds: OATGPU_K1_STOP_EVENT)
     size_t early_min_px = 4000000;   // pixels a step from which the early order is considered (measurement builds: OATGPU_EARLY_MIN_PX)
     int k1_wg_force = 0;             // oatgpu_set_k1_workgroup (64 | 256): the per-pixel kernel's workgroup size whatever the path
-    unsigned *nopark = nullptr;      // device word: a parked blob workgroup of this context has timed out (BlobBuffers::nopark)
+    DevMem<unsigned> nopark;         // device word: a parked blob workgroup of this context has timed out (BlobBuffers::nopark)
     unsigned long long early_timeouts = 0;   // frames whose parked blob workgroup gave up waiting for its row scan (kWaitTicks):
                                      // something serialises kernel dispatches -- the context then stops parking (early_off)
     bool early_off = false;
@@ -124,14 +196,14 @@ struct oatgpu_ctx {
     unsigned pair_steps = 0;         // paired steps so far (their parity picks the B stream and the two scratch sets)
     unsigned bh_ticket[kSets] = {};
     unsigned early_frames = 0;       // frames that took the early path (their parity picks scratch set and row-scan stream)
-    hipEvent_t ev_blob[kSets] = {};  // scratch set q: its latest reader is done
+    Event ev_blob[kSets];            // scratch set q: its latest reader is done
     bool ev_blob_valid[kSets] = {};
     int last_slot = 0;               // ring slot whose threshold bits the latest back half read (oatgpu_read_mask)
     std::string err;
     // Deferred completion of the single-stage calls (oatgpu_set_deferred): the call returns when its INPUT has been read
     // (the H2D copy is done), the result stays on the device until oatgpu_fetch_frame / oatgpu_fetch_position
     bool deferred = false;
-    hipEvent_t ev_h2d = nullptr;
+    Event ev_h2d;
     int defer_kind = 0;              // 0 nothing waiting, 1 a frame (defer_dev, defer_bytes), 2 a position (defer_s)
     const uint8_t *defer_dev = nullptr;
     size_t defer_bytes = 0;
@@ -150,37 +222,37 @@ struct oatgpu_ctx {
     int fuse = 0;                                     // 0: default -- pair where the library owns the frame's lifetime
                                                       // (host frames, track_sequence_dev), not for oatgpu_track_enqueue_dev
     bool in_sequence = false;                         // inside oatgpu_track_sequence_dev: its frames are all in hand
-    hipEvent_t ev_in = nullptr;                       // stream A has read every frame handed over so far (input_consumed)
+    Event ev_in;                                      // stream A has read every frame handed over so far (input_consumed)
     bool dev_unconsumed = false;                      // device frames were enqueued since the last input_consumed
     bool pend_valid = false;
     FrameJob pend;
     unsigned long long launched_total = 0;            // frames whose kernels are out (<= enq_total)
 
     // device memory
-    float *state = nullptr;
-    uint8_t *nmodes = nullptr;
-    uint8_t *frames = nullptr;     // staging [n][H*W*3]
-    uint8_t *aux_a = nullptr;      // [H*W*3]
-    uint8_t *aux_b = nullptr;      // [H*W*3]
-    uint8_t *bsub_bg = nullptr;    // [n][H*W*ch] framefilt bsub background (u8) and its fp32 accumulator
-    float *bsub_f = nullptr;
+    DevMem<float> state;
+    DevMem<uint8_t> nmodes;
+    DevMem<uint8_t> frames;        // staging [n][H*W*3]
+    DevMem<uint8_t> aux_a;         // [H*W*3]
+    DevMem<uint8_t> aux_b;         // [H*W*3]
+    DevMem<uint8_t> bsub_bg;       // [n][H*W*ch] framefilt bsub background (u8) and its fp32 accumulator
+    DevMem<float> bsub_f;
     std::vector<char> bsub_have;
-    uint8_t *diff_last = nullptr;  // [n][H*W] previous GREY frame of posidet diff, allocated on first use
+    DevMem<uint8_t> diff_last;     // [n][H*W] previous GREY frame of posidet diff, allocated on first use
     std::vector<char> diff_have;   // per camera stream
-    u64 *roi = nullptr;            // [n][Palloc/64] ROI bits, allocated on first oatgpu_set_roi_mask
-    uint32_t *ud_map1 = nullptr;   // [n][ud_stride] framefilt undistort maps (sx | sy << 16) and [n][ud_stride] fractions,
-    uint16_t *ud_map2 = nullptr;   //   allocated on first oatgpu_set_undistort (kernels_undistort.hip)
+    DevMem<u64> roi;               // [n][Palloc/64] ROI bits, allocated on first oatgpu_set_roi_mask
+    DevMem<uint32_t> ud_map1;      // [n][ud_stride] framefilt undistort maps (sx | sy << 16) and [n][ud_stride] fractions,
+    DevMem<uint16_t> ud_map2;      //   allocated on first oatgpu_set_undistort (kernels_undistort.hip)
     size_t ud_stride = 0;
     std::vector<char> ud_have;     // per camera stream: has a map
     bool ud_track = false;         // oatgpu_set_track_undistort: the fused track calls remap every frame first (launch_front)
-    uint8_t *ud_frames[2] = {};    // [2][n][H*W*ch] the remapped frames of a step (frame i of a two-frame step in buffer i): K1
+    DevMem<uint8_t> ud_frames[2];  // [2][n][H*W*ch] the remapped frames of a step (frame i of a two-frame step in buffer i): K1
                                    //   reads them in place of the caller's; allocated by oatgpu_set_track_undistort(1)
-    BlobBuffers bb[kSets]{};          // scratch sets (bb[0].thr holds the ring's threshold buffers), all made with the context
+    DevMem<u64> thr;               // [ring_slots][n][Palloc/64] the ring's threshold buffers (BlobBuffers::thr of every scratch set)
+    Scratch bb[kSets];             // scratch sets, all made with the context
     const u64 *last_morph = nullptr;
     const u64 *last_fin = nullptr;
-    ResultRec *res_host = nullptr; // [ring_depth+1][n] pinned + mapped (last slot: single-stage calls)
-    ResultRec *res_dev = nullptr;  // device alias of res_host: kernels store results straight to the host
-    std::vector<hipEvent_t> ring_ev;
+    HostMem<ResultRec> res;        // [ring_depth+1][n] pinned + mapped (last slot: single-stage calls); kernels store results straight to the host through dev()
+    std::vector<Event> ring_ev;
     int ring_count = 0;
 
     std::vector<int> nframes;      // per camera stream
@@ -197,58 +269,16 @@ struct oatgpu_ctx {
     double event_pair_ms = 0.0;
 
     // traffic audit (oatgpu_traffic_audit)
-    unsigned long long *audit_dev = nullptr;   // 8 counters
+    DevMem<unsigned long long> audit_dev;      // 8 counters
 #ifdef OATGPU_RS_TIMING
     unsigned long long *rs_k1_end = nullptr;   // (leaked at destroy: measurement builds only)
 #endif
-    unsigned long long *wild_sink = nullptr;   // 8 counters nobody reads: launches outside div_inrange's operands (kernels_mog.hip)
+    DevMem<unsigned long long> wild_sink;      // 8 counters nobody reads: launches outside div_inrange's operands (kernels_mog.hip)
     std::vector<char> wild_model;              // [n_streams] 1: an imported model with weights no run of the kernel produces
     bool audit_on = false;
     long long audit_launches = 0;
 
-    // marker sets (oatgpu_set_markers; kernels_markers.hip): M colour windows per camera behind the one model pass.  Everything
-    // below is made by oatgpu_set_markers and used by the synchronous marker step alone, on stream A.
-    int mk_n = 0;                              // M; 0: markers off
-    int mk_anchor = -1;                        // `posicom mean --heading-anchor`, -1: none
-    std::vector<oatgpu_marker> mk_def;         // [M] erode / dilate / area of each marker (and its default window)
-    std::vector<RangeParams> mk_win_host;      // [n][M] normalised colour windows, per camera and marker
-    RangeParams *mk_win = nullptr;             // ... on the device
-    u64 *mk_planes = nullptr;                  // [M][n][Palloc/64] k_marker_bits' output = launch_blob's src_bits
-    u64 *mk_masks = nullptr;                   // [M][3][n][Palloc/64] each marker's own tmp / morph / fin planes (the taps)
-    BlobBuffers mk_bb{};                       // the rest of one back-half scratch set, shared by the markers (they run one after the other)
-    ResultRec *mk_res = nullptr;               // device: [M][n] result records, then [n] MarkerCombined
-    void *mk_res_host = nullptr;               // page-locked mirror: one copy back a step
-    std::vector<const u64 *> mk_tap_morph;     // [M] where marker m's mask after erode / dilate is
-    // the pipelined marker path (oatgpu_set_marker_pipeline): everything below is made by the switch, never inside a step.
-    // A step's marker work: k_marker_bits on stream A right behind its per-pixel kernel (launch_marker_work), the back half of
-    // all M x n planes and the combiner on B2 (a lone frame: on A), results into the slot's host-mapped record set.
-    bool mkp_on = false;
-    bool mkp_table = false;                    // the one-launch back half takes this geometry and these markers (else: marker by marker)
-    int mkp_max_dil = 0;                       // largest dilation of the set: the row scan's LDS
-    u64 *mkp_planes = nullptr;                 // [ring][M][n][Palloc/64] k_marker_bits' output, per ring slot
-    u64 *mkp_masks = nullptr;                  // [ring][3][M][n][Palloc/64] the slot's tmp / morph / fin planes of every marker (the taps)
-    BlobBuffers mkp_bb[2]{};                   // the rest of a back-half scratch set for M x n planes, one for each frame of a step
-    BlobTab *mkp_tab = nullptr;                // [M][n] device table of the one-launch back half
-    ResultRec *mkp_res = nullptr;              // device: [2][M][n] the step's result records, read by k_marker_combine
-    ResultRec *mkp_rec_host = nullptr;         // host-mapped: [ring] sets of M x n ResultRec + n MarkerCombined, written by k_marker_combine
-    ResultRec *mkp_rec_dev = nullptr;          // ... its device alias
-    std::vector<hipEvent_t> mkp_ev;            // [ring] the marker work whose last frame sits in this slot is done
-    std::vector<int> mkp_ev_of;                // [ring] slot -> the slot whose event covers its marker results
-    std::vector<const u64 *> mkp_tap_morph;    // [ring][M] where the MORPH tap of marker m of that slot is
-    hipEvent_t mkp_bits_ev = nullptr;          // stream A: the step's k_marker_bits has finished
-    int mk_last_slot = -1;                     // ring slot of the frame set collected last on the pipelined path; -1: the synchronous step was later
-    // a record set: M x n result records, n combined records, n filtered records (written only while a chain is configured)
-    size_t mkp_set_bytes() const { return (size_t)mk_n * cfg.n_streams * sizeof(ResultRec) + (size_t)cfg.n_streams * (sizeof(MarkerCombined) + sizeof(MarkerFiltered)); }
-    // the filter chain behind the combined record (oatgpu_set_marker_filters): kalman -> homography -> region in ONE launch
-    // behind k_marker_combine on the same HIP stream.  Made by the setter, dropped with the marker set.
-    bool mf_on = false;
-    MarkerFilterParams *mf_params = nullptr;   // device: the chain's parameters and the region table
-    KalmanState *mf_state = nullptr;           // device: [n] the chain's own filter state, one per camera stream (not c->kal's)
-    MarkerFiltered *mf_out = nullptr;          // device: [n] the synchronous step's filtered records
-    MarkerFiltered *mf_out_host = nullptr;     // ... their page-locked mirror
-    std::vector<oatgpu_filtered> mf_last;      // [sets][n] what the latest marker-result call delivered (oatgpu_marker_filtered)
-    int mf_last_sets = 0;
-    bool mf_append = false;                    // inside oatgpu_track_markers_sequence_dev: every collected set is kept
+    MarkerSet mk; MarkerPipeline mkp; MarkerFilters mf;      // the optional features: dropping one is assignment (c->mkp = {})
 };
 
 static int fail(oatgpu_ctx *c, int code, const char *fmt, ...)
@@ -441,13 +471,8 @@ void release_streams(int device)
 }  // namespace
 
 namespace {
-struct DevBuf {             // scoped device allocation
-    void *p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
-};
 struct ModelBufs {          // one stream's model in the logical layout of oatgpu_mog_get_state: modes used, weights, variances, means
-    DevBuf mu, w, v, m;
+    DevMem<uint8_t> mu; DevMem<float> w, v, m;
     hipError_t alloc(size_t npx, size_t k, size_t mean_bytes)
     {
         hipError_t e = mu.alloc(npx);
@@ -458,75 +483,6 @@ struct ModelBufs {          // one stream's model in the logical layout of oatgp
     }
 };
 }  // namespace
-
-static void free_scratch(BlobBuffers &b)      // (thr and nopark are the context's: reset with the rest, freed by free_all)
-{
-    hipFree(b.tmp); hipFree(b.morph); hipFree(b.fin); hipFree(b.trans);
-    hipFree(b.carry); hipFree(b.parent); hipFree(b.acc); hipFree(b.done);
-    hipFree(b.roots); hipFree(b.nroots); hipFree(b.wpre); hipFree(b.rowinfo); hipFree(b.lds_ok);
-    hipFree(b.ready);
-    b = BlobBuffers{};
-}
-static void free_marker_pipeline(oatgpu_ctx *c)
-{
-    hipFree(c->mkp_planes); hipFree(c->mkp_masks); hipFree(c->mkp_tab); hipFree(c->mkp_res);
-    if (c->mkp_rec_host) hipHostFree(c->mkp_rec_host);
-    c->mkp_planes = nullptr; c->mkp_masks = nullptr; c->mkp_tab = nullptr; c->mkp_res = nullptr;
-    c->mkp_rec_host = nullptr; c->mkp_rec_dev = nullptr;
-    for (auto &b : c->mkp_bb) free_scratch(b);
-    for (auto e : c->mkp_ev) hipEventDestroy(e);
-    c->mkp_ev.clear(); c->mkp_ev_of.clear(); c->mkp_tap_morph.clear();
-    if (c->mkp_bits_ev) hipEventDestroy(c->mkp_bits_ev);
-    c->mkp_bits_ev = nullptr;
-    c->mkp_on = false;
-    c->mk_last_slot = -1;
-}
-static void free_marker_filters(oatgpu_ctx *c)
-{
-    hipFree(c->mf_params); hipFree(c->mf_state); hipFree(c->mf_out);
-    if (c->mf_out_host) hipHostFree(c->mf_out_host);
-    c->mf_params = nullptr; c->mf_state = nullptr; c->mf_out = nullptr; c->mf_out_host = nullptr;
-    c->mf_on = false;
-    c->mf_last.clear(); c->mf_last_sets = 0;
-}
-static void free_markers(oatgpu_ctx *c)
-{
-    free_marker_pipeline(c);
-    free_marker_filters(c);
-    hipFree(c->mk_win); hipFree(c->mk_planes); hipFree(c->mk_masks); hipFree(c->mk_res);
-    if (c->mk_res_host) hipHostFree(c->mk_res_host);
-    c->mk_win = nullptr; c->mk_planes = nullptr; c->mk_masks = nullptr; c->mk_res = nullptr; c->mk_res_host = nullptr;
-    free_scratch(c->mk_bb);
-    c->mk_n = 0; c->mk_anchor = -1;
-    c->mk_def.clear(); c->mk_win_host.clear(); c->mk_tap_morph.clear();
-}
-
-static void free_all(oatgpu_ctx *c)
-{
-    if (!c) return;
-    free_markers(c);
-    hipFree(c->bsub_bg); hipFree(c->bsub_f); hipFree(c->diff_last); hipFree(c->roi); hipFree(c->ud_map1); hipFree(c->ud_map2); hipFree(c->ud_frames[0]); hipFree(c->ud_frames[1]); hipFree(c->state); hipFree(c->nmodes); hipFree(c->frames); hipFree(c->aux_a); hipFree(c->aux_b);
-    hipFree(c->bb[0].thr);
-    hipFree(c->nopark);
-    hipFree(c->kal.state);
-    hipFree(c->audit_dev);
-    hipFree(c->wild_sink);
-    hipFree(c->frames_ring);
-    if (c->ev_in) hipEventDestroy(c->ev_in);
-    if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
-    if (c->ev_c2) hipEventDestroy(c->ev_c2);
-    for (auto e : c->copy_ev) hipEventDestroy(e);
-    for (auto e : c->copy_ev_s) hipEventDestroy(e);
-    for (auto &b : c->bb) free_scratch(b);
-    if (c->res_host) hipHostFree(c->res_host);
-    if (c->dens_host) hipHostFree(c->dens_host);
-    for (int q = 0; q < oatgpu_ctx::kNB; ++q) if (c->ev_k1[q]) hipEventDestroy(c->ev_k1[q]);
-    for (int q = 0; q < oatgpu_ctx::kSets; ++q) if (c->ev_blob[q]) hipEventDestroy(c->ev_blob[q]);
-    for (auto e : c->ring_ev) hipEventDestroy(e);
-    for (auto &p : c->prof_steps) for (auto e : p.e) hipEventDestroy(e);
-    if (c->have_shared) release_streams(c->cfg.device);
-    delete c;
-}
 
 // Opening the device.  Several processes that open one freshly booted device in the same instant (the ranks of a job, the
 // components of a pipeline started by one script) can see the first runtime calls fail transiently -- no device yet, the
@@ -561,35 +517,44 @@ static hipError_t open_device(int device, int *ndev)
 }
 extern "C" int oatgpu_device_open_retries(void) { return g_open_retries.load(); }
 
+// a table of `count` events: made aside, put in place only when every one of them exists
+static hipError_t make_events(std::vector<Event> &table, size_t count, unsigned flags)
+{
+    std::vector<Event> made(count);
+    for (auto &e : made) { const hipError_t r = e.create(flags); if (r != hipSuccess) return r; }
+    table = std::move(made);
+    return hipSuccess;
+}
+
+template <class T> static bool dev_malloc(T *&p, size_t bytes) { return hipMalloc((void **)&p, bytes) == hipSuccess; }
 // One scratch set of the back half (BlobBuffers; about 30 bytes a pixel and stream), its counters zeroed.  ALL sets a context
 // can come to use are made with it (oatgpu_create): the three of the plain order, the fourth of the early and
 // the paired layout, and the repair set -- 150 bytes a pixel and stream in all.  An allocation in the middle of a pipelined
 // step would stall a camera-paced caller for as long as hipMalloc takes, and its failure would come after the model had
 // moved.
-static bool alloc_scratch(oatgpu_ctx *c, BlobBuffers &b, size_t planes = 0)     // planes: how many (0: one a camera stream)
+bool Scratch::alloc(const oatgpu_ctx *c, size_t planes)
 {
     const Geom &g = c->g;
     const size_t n = planes ? planes : (size_t)c->cfg.n_streams, PA = g.Palloc, NW = PA / 64;
-    bool ok = true;
-    auto A = [&](void **p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) ok = false; };
-    b.thr = c->bb[0].thr;
+    reset();
+    b.thr = c->thr;
     b.nopark = c->nopark;
-    A((void **)&b.tmp, n * NW * 8);
-    A((void **)&b.morph, n * NW * 8);
-    A((void **)&b.fin, n * NW * 8);
-    A((void **)&b.trans, n * NW * 8);
-    A((void **)&b.carry, n * (size_t)g.H * g.words * sizeof(int));
-    A((void **)&b.parent, n * PA * sizeof(int));
-    A((void **)&b.acc, n * PA * 3 * sizeof(long long));
-    A((void **)&b.done, n * sizeof(unsigned));
-    A((void **)&b.roots, n * (PA / 2) * sizeof(int));
-    A((void **)&b.nroots, n * sizeof(unsigned));
-    A((void **)&b.wpre, n * (size_t)g.H * g.words * sizeof(unsigned short));
-    A((void **)&b.rowinfo, n * (size_t)g.H * sizeof(int));
-    A((void **)&b.lds_ok, n * sizeof(unsigned));
-    A((void **)&b.ready, n * sizeof(unsigned));
+    bool ok = dev_malloc(b.tmp, n * NW * 8);
+    ok = ok && dev_malloc(b.morph, n * NW * 8);
+    ok = ok && dev_malloc(b.fin, n * NW * 8);
+    ok = ok && dev_malloc(b.trans, n * NW * 8);
+    ok = ok && dev_malloc(b.carry, n * (size_t)g.H * g.words * sizeof(int));
+    ok = ok && dev_malloc(b.parent, n * PA * sizeof(int));
+    ok = ok && dev_malloc(b.acc, n * PA * 3 * sizeof(long long));
+    ok = ok && dev_malloc(b.done, n * sizeof(unsigned));
+    ok = ok && dev_malloc(b.roots, n * (PA / 2) * sizeof(int));
+    ok = ok && dev_malloc(b.nroots, n * sizeof(unsigned));
+    ok = ok && dev_malloc(b.wpre, n * (size_t)g.H * g.words * sizeof(unsigned short));
+    ok = ok && dev_malloc(b.rowinfo, n * (size_t)g.H * sizeof(int));
+    ok = ok && dev_malloc(b.lds_ok, n * sizeof(unsigned));
+    ok = ok && dev_malloc(b.ready, n * sizeof(unsigned));
     for (unsigned *p : {b.done, b.nroots, b.lds_ok, b.ready})
-        if (ok && hipMemsetAsync(p, 0, n * sizeof(unsigned), c->stream) != hipSuccess) ok = false;
+        ok = ok && hipMemsetAsync(p, 0, n * sizeof(unsigned), c->stream) == hipSuccess;
     return ok;
 }
 
@@ -650,63 +615,53 @@ extern "C" oatgpu_ctx *oatgpu_create(const oatgpu_config *cfg)
     c->bsub_have.assign(n, 0);
     c->ud_have.assign(n, 0);
 
-    bool ok = true;
-    auto A = [&](void **p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) ok = false; };
-    ok = acquire_streams(cfg->device, &c->stream, c->stream_b);
-    c->have_shared = ok;
+    bool ok = acquire_streams(cfg->device, &c->stream, c->stream_b);
+    if (ok) c->lease.device = cfg->device;
     c->ring_slots = cfg->ring_depth;                  // slot = threshold buffer; on the plain path slot % 3 = scratch set / stream
-    for (int q = 0; q < oatgpu_ctx::kNB && ok; ++q)
-        ok = hipEventCreateWithFlags(&c->ev_k1[q], hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
-    for (int q = 0; q < oatgpu_ctx::kSets && ok; ++q)
-        ok = hipEventCreateWithFlags(&c->ev_blob[q], hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
+    for (auto &e : c->ev_k1) ok = ok && e.create(hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
+    for (auto &e : c->ev_blob) ok = ok && e.create(hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
     if (const char *e = measure_env("OATGPU_EARLY_BLOB")) c->early_blob = atoi(e);
     if (const char *e = measure_env("OATGPU_EARLY_MIN_PX")) c->early_min_px = (size_t)atoll(e);
     if (const char *e = measure_env("OATGPU_LONE_PLAIN")) c->lone_plain = atoi(e) != 0;
     if (const char *e = measure_env("OATGPU_PAIR_BACK")) c->pair_back = atoi(e) != 0;
     if (const char *e = measure_env("OATGPU_K1_WG")) { const int v = atoi(e); if (v == 64 || v == 256) c->k1_wg_force = v; }
 
-
     if (const char *e = measure_env("OATGPU_K1_STOP_EVENT")) c->k1_stop_event = atoi(e) != 0 ? 1 : 0;
 
-    A((void **)&c->state, n * mog_stream_floats(g.Palloc) * sizeof(float));
-    A((void **)&c->nmodes, n * PA);
-    A((void **)&c->frames, n * npx * cfg->channels);
-    A((void **)&c->aux_a, npx * 3);
-    A((void **)&c->aux_b, npx * 3);
+    ok = ok && c->state.alloc(n * mog_stream_floats(g.Palloc) * sizeof(float)) == hipSuccess;
+    ok = ok && c->nmodes.alloc(n * PA) == hipSuccess;
+    ok = ok && c->frames.alloc(n * npx * cfg->channels) == hipSuccess;
+    ok = ok && c->aux_a.alloc(npx * 3) == hipSuccess;
+    ok = ok && c->aux_b.alloc(npx * 3) == hipSuccess;
     // One threshold-bit buffer per ring slot: a slot is only reused after its result was collected,
     // i.e. after the back half that read its buffer has finished -- stream A never waits for a B stream.
-    A((void **)&c->bb[0].thr, (size_t)c->ring_slots * n * NW * 8);
-    A((void **)&c->nopark, sizeof(unsigned));
-    if (ok && hipMemsetAsync(c->nopark, 0, sizeof(unsigned), c->stream) != hipSuccess) ok = false;
-    for (int q = 0; q < oatgpu_ctx::kSets && ok; ++q) ok = alloc_scratch(c, c->bb[q]);   // (an out-of-memory shows HERE, as OATGPU_E_NOMEM from oatgpu_create)
+    ok = ok && c->thr.alloc((size_t)c->ring_slots * n * NW * 8) == hipSuccess;
+    ok = ok && c->nopark.alloc(sizeof(unsigned)) == hipSuccess;
+    ok = ok && hipMemsetAsync(c->nopark, 0, sizeof(unsigned), c->stream) == hipSuccess;
+    for (int q = 0; q < oatgpu_ctx::kSets && ok; ++q) ok = c->bb[q].alloc(c);   // (an out-of-memory shows HERE, as OATGPU_E_NOMEM from oatgpu_create)
     const size_t slots = (size_t)c->ring_slots + 1;
-    if (ok && hipHostMalloc((void **)&c->res_host, slots * n * sizeof(ResultRec), hipHostMallocMapped) != hipSuccess)
-        ok = false;
-    if (ok && hipHostGetDevicePointer((void **)&c->res_dev, c->res_host, 0) != hipSuccess) ok = false;
-    if (ok && hipHostMalloc((void **)&c->dens_host, 4 * sizeof(unsigned), hipHostMallocMapped) != hipSuccess) ok = false;
-    if (ok && hipHostGetDevicePointer((void **)&c->dens_dev, c->dens_host, 0) != hipSuccess) ok = false;
-    if (ok) memset(c->dens_host, 0, 4 * sizeof(unsigned));
-    if (ok && hipMalloc((void **)&c->wild_sink, 8 * sizeof(unsigned long long)) != hipSuccess) ok = false;
-    if (ok && hipMemset(c->wild_sink, 0, 8 * sizeof(unsigned long long)) != hipSuccess) ok = false;
+    ok = ok && c->res.alloc(slots * n * sizeof(ResultRec), hipHostMallocMapped) == hipSuccess;
+    ok = ok && c->dens.alloc(4 * sizeof(unsigned), hipHostMallocMapped) == hipSuccess;
+    if (ok) memset(c->dens.host(), 0, 4 * sizeof(unsigned));
+    ok = ok && c->wild_sink.alloc(8 * sizeof(unsigned long long)) == hipSuccess;
+    ok = ok && hipMemset(c->wild_sink, 0, 8 * sizeof(unsigned long long)) == hipSuccess;
     if (ok) {
-        c->ring_ev.resize(c->ring_slots);
         c->slots.assign(c->ring_slots, oatgpu_ctx::Slot{});
         for (int i = 0; i < c->ring_slots; ++i) c->slots[i].ev = i;
-        for (auto &e : c->ring_ev)
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) ok = false;
+        ok = make_events(c->ring_ev, (size_t)c->ring_slots, hipEventDisableTiming) == hipSuccess;
     }
     // the model's mode counters start at zero; everything else is written before it is read
-    if (ok && hipMemsetAsync(c->nmodes, 0, n * PA, c->stream) != hipSuccess) ok = false;
-    if (ok && hipMemsetAsync(c->state, 0, n * mog_stream_floats(g.Palloc) * sizeof(float), c->stream) != hipSuccess) ok = false;
-    if (ok && hipMemsetAsync(c->bb[0].thr, 0, (size_t)c->ring_slots * n * NW * 8, c->stream) != hipSuccess) ok = false;
-    if (ok && hipStreamSynchronize(c->stream) != hipSuccess) ok = false;
+    ok = ok && hipMemsetAsync(c->nmodes, 0, n * PA, c->stream) == hipSuccess;
+    ok = ok && hipMemsetAsync(c->state, 0, n * mog_stream_floats(g.Palloc) * sizeof(float), c->stream) == hipSuccess;
+    ok = ok && hipMemsetAsync(c->thr, 0, (size_t)c->ring_slots * n * NW * 8, c->stream) == hipSuccess;
+    ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
     if (!ok) {
         fail(nullptr, OATGPU_E_NOMEM, "device allocation failed: %s", hipGetErrorString(hipGetLastError()));
-        free_all(c);
+        delete c;
         return nullptr;
     }
-    c->last_morph = c->bb[0].thr;
-    c->last_fin = c->bb[0].fin;
+    c->last_morph = c->thr;
+    c->last_fin = c->bb[0].b.fin;
     return c;
 }
 
@@ -717,7 +672,7 @@ extern "C" void oatgpu_destroy(oatgpu_ctx *c)
     c->pend_valid = false;            // a registered frame nobody collected: nothing to launch for
     if (c->stream) hipStreamSynchronize(c->stream);
     drain_b(c);
-    free_all(c);
+    delete c;           // every member releases what it holds; the stream lease, declared first, goes last
 }
 
 extern "C" const char *oatgpu_last_error(const oatgpu_ctx *c)
@@ -801,8 +756,8 @@ extern "C" int oatgpu_set_early_blob(oatgpu_ctx *c, int32_t on)
 extern "C" __attribute__((visibility("default"))) int oatgpu_debug_addresses(oatgpu_ctx *c, unsigned long long *out4)
 {
     if (!c || !out4) return OATGPU_E_INVALID;
-    out4[0] = (unsigned long long)(uintptr_t)c->state; out4[1] = (unsigned long long)(uintptr_t)c->nmodes;
-    out4[2] = (unsigned long long)(uintptr_t)c->bb[0].thr; out4[3] = (unsigned long long)(mog_stream_floats(c->g.Palloc) * 4);
+    out4[0] = (unsigned long long)(uintptr_t)c->state.get(); out4[1] = (unsigned long long)(uintptr_t)c->nmodes.get();
+    out4[2] = (unsigned long long)(uintptr_t)c->thr.get(); out4[3] = (unsigned long long)(mog_stream_floats(c->g.Palloc) * 4);
     return OATGPU_OK;
 }
 #endif
@@ -844,7 +799,7 @@ extern "C" int oatgpu_set_detector(oatgpu_ctx *c, int32_t h_lo, int32_t h_hi, in
     k.erode = erode; k.dilate = dilate; k.min_area = min_area; k.max_area = max_area;
     int rc = check_detector(c, detector_of(k), k.blur);
     if (rc) return rc;
-    if (c->mkp_on && !own_window_is_nonzero(k))
+    if (c->mkp.on && !own_window_is_nonzero(k))
         return fail(c, OATGPU_E_INVALID, "the marker pipeline is on and needs the non-zero window: oatgpu_set_marker_pipeline(0) first");
     rc = quiesce(c);
     if (rc) return rc;
@@ -875,7 +830,7 @@ static int col_slot(const oatgpu_ctx *c) { return (int)(c->col_total % (unsigned
 
 static u64 *thr_buf(oatgpu_ctx *c, int parity)
 {
-    return c->bb[0].thr + (size_t)parity * c->cfg.n_streams * (c->g.Palloc >> 6);
+    return c->thr + (size_t)parity * c->cfg.n_streams * (c->g.Palloc >> 6);
 }
 
 // The single-stage calls are synchronous and share scratch with the pipelined path:
@@ -939,7 +894,7 @@ static int stage_in(oatgpu_ctx *c, void *dst, const void *src, size_t bytes)
 {
     HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
     if (c->deferred) {
-        if (!c->ev_h2d) HIPCHK(c, hipEventCreateWithFlags(&c->ev_h2d, hipEventDisableTiming | hipEventDisableSystemFence));
+        if (!c->ev_h2d) HIPCHK(c, c->ev_h2d.create(hipEventDisableTiming | hipEventDisableSystemFence));
         HIPCHK(c, hipEventRecord(c->ev_h2d, c->stream));
     }
     return OATGPU_OK;
@@ -1009,14 +964,15 @@ extern "C" int oatgpu_set_kalman(oatgpu_ctx *c, int32_t enable, double dt, doubl
     if (!c) return OATGPU_E_INVALID;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (c->ring_count) return fail(c, OATGPU_E_INVALID, "set_kalman while enqueued results are outstanding");
-    if (enable && c->mkp_on)
+    if (enable && c->mkp.on)
         return fail(c, OATGPU_E_INVALID, "the marker pipeline is on and does not take the position filter: oatgpu_set_marker_pipeline(0) first");
     int rc = quiesce(c);
     if (rc) return rc;
     if (!enable) { c->kal_on = false; return OATGPU_OK; }
     if (!(dt > 0) || !(timeout >= 0) || !(sigma_accel >= 0) || !(sigma_noise >= 0) || !(timeout / dt < 2147483647.0))
         return fail(c, OATGPU_E_INVALID, "kalman: dt must be > 0, timeout / sigma-accel / sigma-noise >= 0");
-    if (!c->kal.state) HIPCHK(c, hipMalloc((void **)&c->kal.state, (size_t)c->cfg.n_streams * sizeof(KalmanState)));
+    if (!c->kal_state) HIPCHK(c, c->kal_state.alloc((size_t)c->cfg.n_streams * sizeof(KalmanState)));
+    c->kal.state = c->kal_state;
     c->kal.dt = dt; c->kal.sig_accel = sigma_accel; c->kal.sig_noise = sigma_noise;
     c->kal.threshold = (int)(timeout / dt);                     // KalmanFilter2D.cpp:74-76
     launch_kalman_reset(c->kal.state, c->cfg.n_streams, c->kal_ticket, c->stream);
@@ -1044,7 +1000,7 @@ extern "C" int oatgpu_set_homography(oatgpu_ctx *c, int32_t enable, const double
     if (!c) return OATGPU_E_INVALID;
     if (enable && !h9) return fail(c, OATGPU_E_INVALID, "null homography");
     if (c->ring_count) return fail(c, OATGPU_E_INVALID, "set_homography while enqueued results are outstanding");
-    if (enable && c->mkp_on)
+    if (enable && c->mkp.on)
         return fail(c, OATGPU_E_INVALID, "the marker pipeline is on and does not take a homography: oatgpu_set_marker_pipeline(0) first");
     c->homo_on = enable != 0;
     if (enable) for (int i = 0; i < 9; ++i) c->homo[i] = h9[i];
@@ -1061,7 +1017,7 @@ extern "C" int oatgpu_set_roi_mask(oatgpu_ctx *c, int32_t s, const uint8_t *roi_
     const size_t NW = g.Palloc >> 6, n = c->cfg.n_streams, npx = (size_t)g.H * g.W;
     if (!c->roi) {
         if (!roi_mask) return OATGPU_OK;                       // nothing to clear
-        HIPCHK(c, hipMalloc((void **)&c->roi, n * NW * 8));
+        HIPCHK(c, c->roi.alloc(n * NW * 8));
         HIPCHK(c, hipMemsetAsync(c->roi, 0xff, n * NW * 8, c->stream));   // other streams keep everything
     }
     if (!roi_mask) {
@@ -1091,8 +1047,10 @@ extern "C" int oatgpu_mog_filter(oatgpu_ctx *c, int32_t s, const uint8_t *bgr_in
 static int ensure_bsub(oatgpu_ctx *c, size_t nb)
 {
     if (c->bsub_bg) return OATGPU_OK;
-    HIPCHK(c, hipMalloc((void **)&c->bsub_bg, (size_t)c->cfg.n_streams * nb));
-    HIPCHK(c, hipMalloc((void **)&c->bsub_f, (size_t)c->cfg.n_streams * nb * sizeof(float)));
+    DevMem<uint8_t> bg; DevMem<float> f;
+    HIPCHK(c, bg.alloc((size_t)c->cfg.n_streams * nb));
+    HIPCHK(c, f.alloc((size_t)c->cfg.n_streams * nb * sizeof(float)));
+    c->bsub_bg = std::move(bg); c->bsub_f = std::move(f);
     return OATGPU_OK;
 }
 
@@ -1213,16 +1171,15 @@ extern "C" int oatgpu_set_undistort(oatgpu_ctx *c, int32_t s, const double K[9],
     undistort_build_map(g.H, g.W, K, dist, n_dist, m1.data(), m2.data());
     rc = open_sync(c);                  // an undistortion still in flight may be reading the old map
     if (rc) return rc;
-    if (!c->ud_map1) {
-        c->ud_stride = undistort_map_stride(g.H, g.W);
-        HIPCHK(c, hipMalloc((void **)&c->ud_map1, n * c->ud_stride * sizeof(uint32_t)));
-        if (hipMalloc((void **)&c->ud_map2, n * c->ud_stride * sizeof(uint16_t)) != hipSuccess) {
-            hipFree(c->ud_map1);
-            c->ud_map1 = nullptr;
+    if (!c->ud_map1) {                  // first use: both maps built aside, moved in when everything worked
+        const size_t stride = undistort_map_stride(g.H, g.W);
+        DevMem<uint32_t> map1; DevMem<uint16_t> map2;
+        HIPCHK(c, map1.alloc(n * stride * sizeof(uint32_t)));
+        if (map2.alloc(n * stride * sizeof(uint16_t)) != hipSuccess)
             return fail(c, OATGPU_E_NOMEM, "device allocation of the undistortion maps failed");
-        }
-        HIPCHK(c, hipMemsetAsync(c->ud_map1, 0, n * c->ud_stride * sizeof(uint32_t), c->stream));   // (the padding is read)
-        HIPCHK(c, hipMemsetAsync(c->ud_map2, 0, n * c->ud_stride * sizeof(uint16_t), c->stream));
+        HIPCHK(c, hipMemsetAsync(map1, 0, n * stride * sizeof(uint32_t), c->stream));   // (the padding is read)
+        HIPCHK(c, hipMemsetAsync(map2, 0, n * stride * sizeof(uint16_t), c->stream));
+        c->ud_stride = stride; c->ud_map1 = std::move(map1); c->ud_map2 = std::move(map2);
     }
     HIPCHK(c, hipMemcpyAsync(c->ud_map1 + (size_t)s * c->ud_stride, m1.data(), npx * sizeof(uint32_t), hipMemcpyHostToDevice,
                              c->stream));
@@ -1244,13 +1201,12 @@ extern "C" int oatgpu_set_track_undistort(oatgpu_ctx *c, int32_t on)
     if (rc) return rc;
     if (on && !c->ud_frames[0]) {       // (allocated here, never in the middle of a step)
         const size_t sb = (size_t)c->g.H * c->g.W * c->cfg.channels * c->cfg.n_streams;
-        for (int i = 0; i < 2; ++i)
-            if (hipMalloc((void **)&c->ud_frames[i], sb) != hipSuccess) {
-                (void)hipGetLastError();
-                hipFree(c->ud_frames[0]);
-                c->ud_frames[0] = c->ud_frames[1] = nullptr;
-                return fail(c, OATGPU_E_NOMEM, "device allocation of the undistorted-frame buffers (2 x %zu bytes) failed", sb);
-            }
+        DevMem<uint8_t> fr[2];
+        if (fr[0].alloc(sb) != hipSuccess || fr[1].alloc(sb) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, OATGPU_E_NOMEM, "device allocation of the undistorted-frame buffers (2 x %zu bytes) failed", sb);
+        }
+        c->ud_frames[0] = std::move(fr[0]); c->ud_frames[1] = std::move(fr[1]);
     }
     c->ud_track = on != 0;
     return OATGPU_OK;
@@ -1398,7 +1354,7 @@ static int back_half(oatgpu_ctx *c, BlobBuffers &bb, const u64 *thr, int s0, int
     if (ev_mid) HIPCHK(c, hipEventRecord(ev_mid, st));
     c->last_morph = m.tap;
     c->last_fin = bb.fin;
-    ResultRec *rd = c->res_dev + (size_t)slot * c->cfg.n_streams;
+    ResultRec *rd = c->res.dev() + (size_t)slot * c->cfg.n_streams;
     launch_blob(g, bb, m.src, m.ero, mp.dil, c->cfg.min_area, c->cfg.max_area, rd, s0, n, st, mode);
     HIPCHK(c, hipGetLastError());
     return OATGPU_OK;
@@ -1409,7 +1365,7 @@ static int back_half(oatgpu_ctx *c, BlobBuffers &bb, const u64 *thr, int s0, int
 static int detect_tail(oatgpu_ctx *c, int s, int erode_k, int dilate_k, oatgpu_position *out)
 {
     const int slot = c->ring_slots;       // the extra slot
-    const int rc = back_half(c, c->bb[0], thr_buf(c, 0), s, 1, slot, c->stream, nullptr, erode_k, dilate_k);
+    const int rc = back_half(c, c->bb[0].b, thr_buf(c, 0), s, 1, slot, c->stream, nullptr, erode_k, dilate_k);
     if (rc) return rc;
     c->last_slot = 0;
     if (c->deferred) {
@@ -1418,7 +1374,7 @@ static int detect_tail(oatgpu_ctx *c, int s, int erode_k, int dilate_k, oatgpu_p
         return OATGPU_OK;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    to_position(c->res_host[(size_t)slot * c->cfg.n_streams + s], out);
+    to_position(c->res.host()[(size_t)slot * c->cfg.n_streams + s], out);
     return OATGPU_OK;
 }
 
@@ -1447,7 +1403,7 @@ extern "C" int oatgpu_detect_diff(oatgpu_ctx *c, int32_t s, const uint8_t *grey_
     if (rc) return rc;
     const Geom &g = c->g;
     const size_t npx = (size_t)g.H * g.W;
-    if (!c->diff_last) HIPCHK(c, hipMalloc((void **)&c->diff_last, (size_t)c->cfg.n_streams * npx));
+    if (!c->diff_last) HIPCHK(c, c->diff_last.alloc((size_t)c->cfg.n_streams * npx));
     rc = stage_in(c, c->aux_a, grey_in, npx);
     if (rc) return rc;
     const int have = c->diff_have[s];
@@ -1474,7 +1430,7 @@ extern "C" int oatgpu_fetch_position(oatgpu_ctx *c, oatgpu_position *out)
     HIPCHK(c, hipSetDevice(c->cfg.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->defer_kind = 0;
-    to_position(c->res_host[(size_t)c->ring_slots * c->cfg.n_streams + c->defer_s], out);
+    to_position(c->res.host()[(size_t)c->ring_slots * c->cfg.n_streams + c->defer_s], out);
     return OATGPU_OK;
 }
 
@@ -1528,18 +1484,18 @@ static int ensure_host_ring(oatgpu_ctx *c)
 {
     if (c->frames_ring) return OATGPU_OK;
     const size_t sb = (size_t)c->g.H * c->g.W * c->cfg.channels * c->cfg.n_streams;
-    c->stream_c = acquire_copy_stream(c->cfg.device);
-    if (!c->stream_c) return fail(c, OATGPU_E_HIP, "could not create the copy stream");
-    HIPCHK(c, hipMalloc((void **)&c->frames_ring, sb * c->ring_slots));
-    c->copy_ev.resize(c->ring_slots);
-    for (auto &e : c->copy_ev) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence));
+    hipStream_t copy = acquire_copy_stream(c->cfg.device);
+    if (!copy) return fail(c, OATGPU_E_HIP, "could not create the copy stream");
+    DevMem<uint8_t> ring;
+    HIPCHK(c, ring.alloc(sb * c->ring_slots));
+    HIPCHK(c, make_events(c->copy_ev, (size_t)c->ring_slots, hipEventDisableTiming | hipEventDisableSystemFence));
+    c->stream_c = copy; c->frames_ring = std::move(ring);
     return OATGPU_OK;
 }
 static int ensure_stream_events(oatgpu_ctx *c)
 {
     if (!c->copy_ev_s.empty()) return OATGPU_OK;
-    c->copy_ev_s.resize((size_t)c->ring_slots * c->cfg.n_streams);
-    for (auto &e : c->copy_ev_s) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence));
+    HIPCHK(c, make_events(c->copy_ev_s, (size_t)c->ring_slots * c->cfg.n_streams, hipEventDisableTiming | hipEventDisableSystemFence));
     return OATGPU_OK;
 }
 
@@ -1582,7 +1538,7 @@ extern "C" int oatgpu_track_stage(oatgpu_ctx *c, int32_t stream_ix, const uint8_
     if (!c->stream_c2 && n > 1) {
         hipStream_t s2 = acquire_copy_stream2(c->cfg.device);
         // (the event first: a context that shows a second copy stream always has the event enqueue_staged records on it)
-        if (s2 && !c->ev_c2) HIPCHK(c, hipEventCreateWithFlags(&c->ev_c2, hipEventDisableTiming | hipEventDisableSystemFence));
+        if (s2 && !c->ev_c2) HIPCHK(c, c->ev_c2.create(hipEventDisableTiming | hipEventDisableSystemFence));
         c->stream_c2 = s2;
     }
     hipStream_t cs = (c->stream_c2 && (c->staged_count & 1)) ? c->stream_c2 : c->stream_c;
@@ -1713,7 +1669,7 @@ static StepPlan plan_step(const oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, in
     // ... and not with the marker pipeline on: its back halves go down B2, where the parked workgroups sit, and nothing may
     // be queued on B2 in front of a row scan they wait for -- marker steps take the paired or the plain order
     p.early = early_wanted && !(lone && c->lone_plain) && !c->early_off && c->lds_spec && !c->kal_on && !j[0].ready && !p.share_b &&
-              lds_geom && step_px >= c->early_min_px && !c->mkp_on;
+              lds_geom && step_px >= c->early_min_px && !c->mkp.on;
     // Threads a K1 workgroup (kernels_mog.hip, k_mog_fused): one wave a workgroup keeps every wave slot filled (K1 -3.5 % on
     // an everyday 4K model, -5.5 % on a dense one) and starves the back half's workgroups of slots.  Taken where that
     // does not come back as a lower frame rate: steps whose blob workgroup is already resident (early), and dense models
@@ -1757,7 +1713,8 @@ static int launch_front(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, co
     const void *fr[2] = {j[0].frames, nj == 2 ? j[1].frames : nullptr};
     if (c->ud_track) {
         const uint8_t *in[2] = {(const uint8_t *)j[0].frames, (const uint8_t *)fr[1]};
-        launch_undistort_frames(in, c->ud_frames, nj, c->ud_map1, c->ud_map2, c->ud_stride, c->g.H, c->g.W, c->cfg.channels, n, A);
+        uint8_t *const out[2] = {c->ud_frames[0], c->ud_frames[1]};
+        launch_undistort_frames(in, out, nj, c->ud_map1, c->ud_map2, c->ud_stride, c->g.H, c->g.W, c->cfg.channels, n, A);
         HIPCHK(c, hipGetLastError());
         fr[0] = c->ud_frames[0];
         fr[1] = c->ud_frames[1];
@@ -1806,9 +1763,9 @@ static int launch_front(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, co
         const unsigned long long t = c->launched_total + (unsigned long long)i;
         if ((t >= 8 && t < 64 && (t & (t - 1)) == 0) || (t >= 64 && (t & 63) == 0)) {
             const int ds = (int)(c->dens_probes & 1);
-            const unsigned *prev = c->dens_host + 2 * (ds ^ 1);
+            const unsigned *prev = c->dens.host() + 2 * (ds ^ 1);
             if (c->dens_probes && prev[1]) c->nt_loads = 2ull * prev[0] >= 5ull * prev[1];      // mean live modes >= 2.5
-            launch_density_probe(c->nmodes, (size_t)n * c->g.Palloc, c->dens_dev + 2 * ds, A);
+            launch_density_probe(c->nmodes, (size_t)n * c->g.Palloc, c->dens.dev() + 2 * ds, A);
             c->dens_probes++;
         }
     }
@@ -1843,9 +1800,9 @@ static int launch_back_paired(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, cons
     c->b_used[p] = true;
     HIPCHK(c, hipStreamWaitEvent(B, plan.k1_done, 0));
     if (ps) { HIPCHK(c, hipEventRecord(ps->e[2], B)); HIPCHK(c, hipEventRecord(ps->e[3], B)); }
-    const BlobBuffers bbs[2] = {c->bb[2 * p], c->bb[2 * p + 1]};
+    const BlobBuffers bbs[2] = {c->bb[2 * p].b, c->bb[2 * p + 1].b};
     const u64 *srcs[2] = {thr_buf(c, j[0].slot), thr_buf(c, j[1].slot)};
-    ResultRec *res[2] = {c->res_dev + (size_t)j[0].slot * n, c->res_dev + (size_t)j[1].slot * n};
+    ResultRec *res[2] = {c->res.dev() + (size_t)j[0].slot * n, c->res.dev() + (size_t)j[1].slot * n};
     launch_blob_pair(c->g, bbs, srcs, plan.ero, plan.dil, c->cfg.min_area, c->cfg.max_area, res, n, B);
     HIPCHK(c, hipGetLastError());
     if (ps) HIPCHK(c, hipEventRecord(ps->e[4], B));
@@ -1884,7 +1841,7 @@ static int launch_back_early(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int n
         qs[i] = q;
         hipStream_t R = c->stream_b[q & 1];
         ProfStep *pb = i == 0 ? ps : nullptr;
-        BlobBuffers &bb = c->bb[q];
+        BlobBuffers &bb = c->bb[q].b;
         // ---- B0 / B1: the frame's row scan, behind the step's per-pixel kernel and the last reader of scratch set q ----
         HIPCHK(c, hipStreamWaitEvent(R, plan.k1_done, 0));
         if (c->ev_blob_valid[q]) HIPCHK(c, hipStreamWaitEvent(R, c->ev_blob[q], 0));
@@ -1896,7 +1853,7 @@ static int launch_back_early(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int n
         unsigned ticket = ++c->bh_ticket[q];
         if (!ticket) ticket = ++c->bh_ticket[q];
         launch_rowscan_signal(g, bb, m.src, m.ero, plan.dil, 0, n, ticket, R);
-        bbs[i] = bb; res[i] = c->res_dev + (size_t)slot * n; tk[i] = ticket;
+        bbs[i] = bb; res[i] = c->res.dev() + (size_t)slot * n; tk[i] = ticket;
         mark_speculative(c, slot);                       // (repaired behind the blob launches on B2)
     }
     // ---- B2: the blob workgroups of the step's frames, ONE launch, dispatched now, started by their row scans' tickets ----
@@ -1936,13 +1893,13 @@ static int launch_back_plain(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int n
         if (plan.spec_plain) mark_speculative(c, slot);
         else c->slots[slot].spec = false;
         // (the position filter is sequential: no repairs behind it)
-        const int rc = back_half(c, c->bb[q], thr_buf(c, slot), 0, n, slot, B, pb ? pb->e[3] : nullptr, -1, -1,
+        const int rc = back_half(c, c->bb[q].b, thr_buf(c, slot), 0, n, slot, B, pb ? pb->e[3] : nullptr, -1, -1,
                                  plan.spec_plain ? kBlobSpec : kBlobFull);
         if (rc) return rc;
         if (c->kal_on) {
             KalmanLaunch kl = c->kal;
             kl.ticket = c->kal_ticket++;
-            launch_kalman(kl, c->res_dev + (size_t)slot * n, n, B);
+            launch_kalman(kl, c->res.dev() + (size_t)slot * n, n, B);
             HIPCHK(c, hipGetLastError());
         }
         c->slots[slot].filtered = c->kal_on;
@@ -1966,14 +1923,14 @@ static int launch_back_plain(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int n
 //     step's remap into the two undistort buffers, the reuse of a host-frame staging slot;
 //   stream B2 behind an event on A (a lone frame: stream A itself, no cross-queue dependency): the back half of all M x n
 //     planes of the step's frames -- launch_blob_table, whose launch count does not depend on M; marker by marker where the
-//     row scan's LDS cannot take the set (mkp_table) -- then k_marker_combine, ONE launch, which writes the frame sets' marker
+//     row scan's LDS cannot take the set (mkp.table) -- then k_marker_combine, ONE launch, which writes the frame sets' marker
 //     records and combined records into the slots' host-mapped record sets; then the slots' marker event.
 // ONE scratch set a frame of the step serves every step: the marker work of consecutive steps runs in order on B2, and a
 // lone frame is launched with nothing outstanding -- every earlier frame set was collected, its marker event waited for.
 static int launch_marker_work(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, const StepPlan &plan)
 {
     const Geom &g = c->g;
-    const int n = c->cfg.n_streams, M = c->mk_n;
+    const int n = c->cfg.n_streams, M = c->mk.n;
     const size_t NW = (size_t)g.Palloc / 64, planes = (size_t)M * n;
     hipStream_t A = c->stream, S = plan.inline_back ? A : c->stream_b[oatgpu_ctx::kNB - 1];
     const uint8_t *fr[2] = {};
@@ -1988,45 +1945,45 @@ static int launch_marker_work(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int 
         const int slot = j[i].slot;
         fr[i] = c->ud_track ? c->ud_frames[i] : (const uint8_t *)j[i].frames;
         z[i] = thr_buf(c, slot);
-        src[i] = bits[i] = c->mkp_planes + (size_t)slot * planes * NW;
-        u64 *own = c->mkp_masks + (size_t)slot * 3 * planes * NW;
-        bbs[i] = c->mkp_bb[i];
+        src[i] = bits[i] = c->mkp.planes + (size_t)slot * planes * NW;
+        u64 *own = c->mkp.masks + (size_t)slot * 3 * planes * NW;
+        bbs[i] = c->mkp.bb[i].b;
         bbs[i].tmp = own; bbs[i].morph = own + planes * NW; bbs[i].fin = own + 2 * planes * NW;
-        res_c[i] = res[i] = c->mkp_res + (size_t)i * planes;
-        rec[i] = (ResultRec *)((char *)c->mkp_rec_dev + (size_t)slot * c->mkp_set_bytes());
+        res_c[i] = res[i] = c->mkp.res + (size_t)i * planes;
+        rec[i] = (ResultRec *)((char *)c->mkp.rec.dev() + (size_t)slot * c->mkp.set_bytes);
         comb[i] = (MarkerCombined *)(rec[i] + planes);
         filt[i] = (MarkerFiltered *)(comb[i] + n);
-        c->mkp_ev_of[(size_t)slot] = j[nj - 1].slot;
+        c->mkp.ev_of[(size_t)slot] = j[nj - 1].slot;
     }
-    launch_marker_bits_frames(g, fr, c->cfg.channels, z, c->mk_win, M, bits, n, nj, A);
+    launch_marker_bits_frames(g, fr, c->cfg.channels, z, c->mk.win, M, bits, n, nj, A);
     HIPCHK(c, hipGetLastError());
     if (S != A) {
-        HIPCHK(c, hipEventRecord(c->mkp_bits_ev, A));
-        HIPCHK(c, hipStreamWaitEvent(S, c->mkp_bits_ev, 0));
+        HIPCHK(c, hipEventRecord(c->mkp.bits_ev, A));
+        HIPCHK(c, hipStreamWaitEvent(S, c->mkp.bits_ev, 0));
         c->b_used[oatgpu_ctx::kNB - 1] = true;
     }
-    if (c->mkp_table) {
-        launch_blob_table(g, bbs, src, c->mkp_tab, c->mkp_max_dil, res, (int)planes, nj, S);
+    if (c->mkp.table) {
+        launch_blob_table(g, bbs, src, c->mkp.tab, c->mkp.max_dil, res, (int)planes, nj, S);
         for (int i = 0; i < nj; ++i)
-            for (int m = 0; m < M; ++m) c->mkp_tap_morph[(size_t)j[i].slot * M + m] = bbs[i].morph + (size_t)m * n * NW;
+            for (int m = 0; m < M; ++m) c->mkp.tap_morph[(size_t)j[i].slot * M + m] = bbs[i].morph + (size_t)m * n * NW;
     } else {
         for (int i = 0; i < nj; ++i)
             for (int m = 0; m < M; ++m) {                     // marker m's planes are "streams" m n .. m n + n - 1 of the set
-                const oatgpu_marker &k = c->mk_def[(size_t)m];
+                const oatgpu_marker &k = c->mk.def[(size_t)m];
                 const MorphPlan mp = plan_morph(g, k.erode, k.dilate);
                 const MorphIssued mi = issue_morph(g, mp, bbs[i], src[i], m * n, n, S);
-                c->mkp_tap_morph[(size_t)j[i].slot * M + m] = mi.tap + (size_t)m * n * NW;
+                c->mkp.tap_morph[(size_t)j[i].slot * M + m] = mi.tap + (size_t)m * n * NW;
                 launch_blob(g, bbs[i], mi.src, mi.ero, mp.dil, k.min_area, k.max_area, res[i], m * n, n, S, kBlobFull);
             }
     }
     HIPCHK(c, hipGetLastError());
-    launch_marker_combine_frames(res_c, M, c->mk_anchor, n, comb, rec, nj, S);
+    launch_marker_combine_frames(res_c, M, c->mk.anchor, n, comb, rec, nj, S);
     HIPCHK(c, hipGetLastError());
-    if (c->mf_on) {       // the chain, behind the combiner and before the event: the filtered records are final when it fires
-        launch_marker_filters(c->mf_params, c->mf_state, comb, filt, n, nj, S);
+    if (c->mf.on) {       // the chain, behind the combiner and before the event: the filtered records are final when it fires
+        launch_marker_filters(c->mf.params, c->mf.state, comb, filt, n, nj, S);
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipEventRecord(c->mkp_ev[(size_t)j[nj - 1].slot], S));
+    HIPCHK(c, hipEventRecord(c->mkp.ev[(size_t)j[nj - 1].slot], S));
     return OATGPU_OK;
 }
 
@@ -2040,8 +1997,8 @@ static int launch_jobs(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, boo
             if (c->prof_steps.size() >= 1024) prof_fold(c);
             else {
                 ProfStep p;
-                for (auto &e : p.e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableSystemFence));   // timing, device-scope fence
-                c->prof_steps.push_back(p);
+                for (auto &e : p.e) HIPCHK(c, e.create(hipEventDisableSystemFence));   // timing, device-scope fence
+                c->prof_steps.push_back(std::move(p));
             }
         }
         ps = &c->prof_steps[c->prof_used++];
@@ -2057,7 +2014,7 @@ static int launch_jobs(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, boo
     c->last_early = path;
     const int brc = plan.paired ? launch_back_paired(c, j, plan, ps) : plan.early ? launch_back_early(c, j, nj, plan, ps)
                                                                                   : launch_back_plain(c, j, nj, plan, ps);
-    if (brc || !c->mkp_on) return brc;
+    if (brc || !c->mkp.on) return brc;
     return launch_marker_work(c, j, nj, plan);
 }
 
@@ -2124,14 +2081,14 @@ static int enqueue_frames(oatgpu_ctx *c, const void *frames_dev, double lr, hipE
 static bool slot_needs_global(const oatgpu_ctx *c, int slot)
 {
     if (!c->slots[slot].spec) return false;
-    const ResultRec *r = c->res_host + (size_t)slot * c->cfg.n_streams;
+    const ResultRec *r = c->res.host() + (size_t)slot * c->cfg.n_streams;
     for (int s = 0; s < c->cfg.n_streams; ++s) if (r[s].valid == kNeedsGlobal) return true;
     return false;
 }
 // ... and did its parked workgroup give up WAITING (path == kPathTimeout) rather than find the frame too busy?
 static bool slot_timed_out(const oatgpu_ctx *c, int slot)
 {
-    const ResultRec *r = c->res_host + (size_t)slot * c->cfg.n_streams;
+    const ResultRec *r = c->res.host() + (size_t)slot * c->cfg.n_streams;
     for (int s = 0; s < c->cfg.n_streams; ++s) if (r[s].valid == kNeedsGlobal && r[s].path == kPathTimeout) return true;
     return false;
 }
@@ -2161,7 +2118,7 @@ static int launch_repair(oatgpu_ctx *c, int slot)
     // repaired frame's own planes are those its speculative back half had made.  tools/fuzz_api.py, seed 1459)
     const auto keep_morph = c->last_morph;
     const auto keep_fin = c->last_fin;
-    const int rc = back_half(c, c->bb[kRepairSet], thr_buf(c, slot), 0, c->cfg.n_streams, slot, B, nullptr, -1, -1, kBlobGlobal);
+    const int rc = back_half(c, c->bb[kRepairSet].b, thr_buf(c, slot), 0, c->cfg.n_streams, slot, B, nullptr, -1, -1, kBlobGlobal);
     c->last_morph = keep_morph;
     c->last_fin = keep_fin;
     if (rc) return rc;
@@ -2207,10 +2164,10 @@ static void keep_filtered(oatgpu_ctx *c, const MarkerFiltered *f)
 {
     static_assert(sizeof(oatgpu_filtered) == sizeof(MarkerFiltered), "k_marker_filters writes oatgpu_filtered's layout");
     const size_t n = (size_t)c->cfg.n_streams;
-    if (!c->mf_append) c->mf_last_sets = 0;
-    c->mf_last.resize((size_t)(c->mf_last_sets + 1) * n);
-    memcpy(c->mf_last.data() + (size_t)c->mf_last_sets * n, f, n * sizeof(oatgpu_filtered));
-    c->mf_last_sets++;
+    if (!c->mf.append) c->mf.last_sets = 0;
+    c->mf.last.resize((size_t)(c->mf.last_sets + 1) * n);
+    memcpy(c->mf.last.data() + (size_t)c->mf.last_sets * n, f, n * sizeof(oatgpu_filtered));
+    c->mf.last_sets++;
 }
 
 // out: the foreground result (nullptr: not wanted); markers / mean: the marker records of the frame set, [n][M] and [n], from the
@@ -2226,7 +2183,7 @@ static int collect_frame(oatgpu_ctx *c, oatgpu_position *out, oatgpu_position *m
     }
     // (polling here, as wait_short does for the copies, made the one-camera latency WORSE: p50 207 -> 257 us free-running)
     HIPCHK(c, hipEventSynchronize(c->ring_ev[c->slots[slot].ev]));
-    const ResultRec *r = c->res_host + (size_t)slot * c->cfg.n_streams;
+    const ResultRec *r = c->res.host() + (size_t)slot * c->cfg.n_streams;
     if (!c->slots[slot].repair && slot_needs_global(c, slot)) {
         const int rc = launch_repair(c, slot);
         if (rc) return rc;
@@ -2245,17 +2202,17 @@ static int collect_frame(oatgpu_ctx *c, oatgpu_position *out, oatgpu_position *m
             c->lds_spec = false;
         }
     }
-    if (c->mkp_on) {
-        HIPCHK(c, hipEventSynchronize(c->mkp_ev[(size_t)c->mkp_ev_of[(size_t)slot]]));
-        const int n = c->cfg.n_streams, M = c->mk_n;
-        const ResultRec *mr = (const ResultRec *)((const char *)c->mkp_rec_host + (size_t)slot * c->mkp_set_bytes());
+    if (c->mkp.on) {
+        HIPCHK(c, hipEventSynchronize(c->mkp.ev[(size_t)c->mkp.ev_of[(size_t)slot]]));
+        const int n = c->cfg.n_streams, M = c->mk.n;
+        const ResultRec *mr = (const ResultRec *)((const char *)c->mkp.rec.host() + (size_t)slot * c->mkp.set_bytes);
         if (markers)
             for (int s = 0; s < n; ++s)
                 for (int m = 0; m < M; ++m) to_position(mr[(size_t)m * n + s], &markers[(size_t)s * M + m]);
         if (mean) memcpy(mean, mr + (size_t)M * n, (size_t)n * sizeof(oatgpu_combined));
-        if (c->mf_on && markers)             // a marker-result call: what oatgpu_marker_filtered hands out
+        if (c->mf.on && markers)             // a marker-result call: what oatgpu_marker_filtered hands out
             keep_filtered(c, (const MarkerFiltered *)((const MarkerCombined *)(mr + (size_t)M * n) + n));
-        c->mk_last_slot = slot;
+        c->mkp.last_slot = slot;
     }
     for (int s = 0; out && s < c->cfg.n_streams; ++s) {
         to_position(r[s], &out[s]);
@@ -2276,7 +2233,7 @@ extern "C" int oatgpu_track_collect(oatgpu_ctx *c, oatgpu_position *out)
 extern "C" int oatgpu_track_collect_markers(oatgpu_ctx *c, oatgpu_position *fg, oatgpu_position *markers, oatgpu_combined *mean)
 {
     if (!c || !markers) return fail(c, OATGPU_E_INVALID, "null argument");
-    if (!c->mkp_on) return fail(c, OATGPU_E_INVALID, "the marker pipeline is off (oatgpu_set_marker_pipeline)");
+    if (!c->mkp.on) return fail(c, OATGPU_E_INVALID, "the marker pipeline is off (oatgpu_set_marker_pipeline)");
     return collect_frame(c, fg, markers, mean);
 }
 
@@ -2287,7 +2244,7 @@ extern "C" int oatgpu_track_input_consumed(oatgpu_ctx *c)
         HIPCHK(c, hipSetDevice(c->cfg.device));
         const int frc = flush_pending(c);
         if (frc) return frc;
-        if (!c->ev_in) HIPCHK(c, hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
+        if (!c->ev_in) HIPCHK(c, c->ev_in.create(hipEventDisableTiming));
         HIPCHK(c, hipEventRecord(c->ev_in, c->stream));
         HIPCHK(c, hipEventSynchronize(c->ev_in));
         c->dev_unconsumed = false;
@@ -2330,8 +2287,8 @@ extern "C" int oatgpu_track_ready(oatgpu_ctx *c)
         const int rc = launch_repair(c, slot);                    // global kernels -- start them, not ready yet
         return rc ? rc : 0;
     }
-    if (c->mkp_on) {                                              // ... and the frame set's marker results
-        const hipError_t me = hipEventQuery(c->mkp_ev[(size_t)c->mkp_ev_of[(size_t)slot]]);
+    if (c->mkp.on) {                                              // ... and the frame set's marker results
+        const hipError_t me = hipEventQuery(c->mkp.ev[(size_t)c->mkp.ev_of[(size_t)slot]]);
         if (me == hipErrorNotReady) return 0;
         if (me != hipSuccess) return fail(c, OATGPU_E_HIP, "hipEventQuery failed: %s", hipGetErrorString(me));
     }
@@ -2348,7 +2305,7 @@ static int sequence_dev(oatgpu_ctx *c, const void *const *frames_dev, int32_t n_
     const auto t0 = std::chrono::steady_clock::now();
     int got = 0, rc = OATGPU_OK;
     auto collect_one = [&]() {
-        const int r = collect_frame(c, out ? out + (size_t)got * n : nullptr, markers ? markers + (size_t)got * n * c->mk_n : nullptr,
+        const int r = collect_frame(c, out ? out + (size_t)got * n : nullptr, markers ? markers + (size_t)got * n * c->mk.n : nullptr,
                                     mean ? mean + (size_t)got * n : nullptr);
         if (!r && done_s) done_s[got] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         ++got;
@@ -2388,12 +2345,12 @@ extern "C" int oatgpu_track_markers_sequence_dev(oatgpu_ctx *c, const void *cons
                                                  oatgpu_position *fg, oatgpu_position *markers, oatgpu_combined *mean)
 {
     if (!c || !markers) return fail(c, OATGPU_E_INVALID, "null argument");
-    if (!c->mkp_on) return fail(c, OATGPU_E_INVALID, "the marker pipeline is off (oatgpu_set_marker_pipeline)");
+    if (!c->mkp.on) return fail(c, OATGPU_E_INVALID, "the marker pipeline is off (oatgpu_set_marker_pipeline)");
     if (c->ring_count) return fail(c, OATGPU_E_INVALID, "track_sequence while enqueued results are outstanding");
-    c->mf_append = true;                 // oatgpu_marker_filtered: the n_frames sets of this call
-    c->mf_last_sets = 0;
+    c->mf.append = true;                 // oatgpu_marker_filtered: the n_frames sets of this call
+    c->mf.last_sets = 0;
     const int rc = sequence_dev(c, frames_dev, n_frames, lr, fg, nullptr, nullptr, markers, mean);
-    c->mf_append = false;
+    c->mf.append = false;
     return rc;
 }
 
@@ -2452,43 +2409,42 @@ extern "C" int oatgpu_set_markers(oatgpu_ctx *c, int32_t n_markers, const oatgpu
     if (n_markers > 0 && (heading_anchor < -1 || heading_anchor >= n_markers))      // MeanPosition.cpp:55-57
         return fail(c, OATGPU_E_INVALID, "heading anchor %d out of range: -1 (none) or a marker index below %d", heading_anchor, n_markers);
     for (int m = 0; m < n_markers; ++m) { const int rc = check_detector(c, defaults[m]); if (rc) return rc; }
-    if (c->mkp_on)       // (its planes, scratch and records are sized by M: refused, like everything that would pull them from under it)
+    if (c->mkp.on)       // (its planes, scratch and records are sized by M: refused, like everything that would pull them from under it)
         return fail(c, OATGPU_E_INVALID, "the marker pipeline is on: oatgpu_set_marker_pipeline(0) before the marker set changes");
     int rc = open_sync(c);
     if (rc) return rc;
-    free_markers(c);
+    c->mkp = {}; c->mf = {}; c->mk = {};      // the old set goes BEFORE the new one is made: peak memory does not double
     if (n_markers == 0) return OATGPU_OK;
 
     const size_t n = c->cfg.n_streams, M = (size_t)n_markers, NW = (size_t)c->g.Palloc / 64;
     const size_t res_bytes = M * n * sizeof(ResultRec) + n * sizeof(MarkerCombined);
-    bool ok = true;
-    auto A = [&](void **p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) ok = false; };
-    A((void **)&c->mk_win, n * M * sizeof(RangeParams));
-    A((void **)&c->mk_planes, M * n * NW * 8);
-    A((void **)&c->mk_masks, M * 3 * n * NW * 8);
-    A((void **)&c->mk_res, res_bytes);
-    if (ok && hipHostMalloc(&c->mk_res_host, res_bytes, hipHostMallocDefault) != hipSuccess) ok = false;
-    if (ok) ok = alloc_scratch(c, c->mk_bb);
+    MarkerSet &mk = c->mk;
+    bool ok = mk.win.alloc(n * M * sizeof(RangeParams)) == hipSuccess;
+    ok = ok && mk.planes.alloc(M * n * NW * 8) == hipSuccess;
+    ok = ok && mk.masks.alloc(M * 3 * n * NW * 8) == hipSuccess;
+    ok = ok && mk.res.alloc(res_bytes) == hipSuccess;
+    ok = ok && mk.res_host.alloc(res_bytes, hipHostMallocDefault) == hipSuccess;
+    ok = ok && mk.bb.alloc(c);
     // (the taps read these before the first step; words beyond the frame are never written by the back half)
-    if (ok && hipMemsetAsync(c->mk_planes, 0, M * n * NW * 8, c->stream) != hipSuccess) ok = false;
-    if (ok && hipMemsetAsync(c->mk_masks, 0, M * 3 * n * NW * 8, c->stream) != hipSuccess) ok = false;
+    ok = ok && hipMemsetAsync(mk.planes, 0, M * n * NW * 8, c->stream) == hipSuccess;
+    ok = ok && hipMemsetAsync(mk.masks, 0, M * 3 * n * NW * 8, c->stream) == hipSuccess;
     if (ok) {
-        c->mk_win_host.resize(n * M);
+        mk.win_host.resize(n * M);
         for (size_t s = 0; s < n; ++s)
-            for (size_t m = 0; m < M; ++m) c->mk_win_host[s * M + m] = range_of(defaults[m]);
-        if (hipMemcpy(c->mk_win, c->mk_win_host.data(), n * M * sizeof(RangeParams), hipMemcpyHostToDevice) != hipSuccess) ok = false;
+            for (size_t m = 0; m < M; ++m) mk.win_host[s * M + m] = range_of(defaults[m]);
+        ok = hipMemcpy(mk.win, mk.win_host.data(), n * M * sizeof(RangeParams), hipMemcpyHostToDevice) == hipSuccess;
     }
-    if (ok && hipStreamSynchronize(c->stream) != hipSuccess) ok = false;
+    ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
     if (!ok) {
         const hipError_t e = hipGetLastError();
-        free_markers(c);
+        mk = {};
         return fail(c, OATGPU_E_NOMEM, "marker sets: device allocation failed: %s", hipGetErrorString(e));
     }
-    c->mk_n = n_markers;
-    c->mk_anchor = heading_anchor;
-    c->mk_def.assign(defaults, defaults + n_markers);
-    c->mk_tap_morph.resize(M);
-    for (size_t m = 0; m < M; ++m) c->mk_tap_morph[m] = c->mk_planes + m * n * NW;
+    mk.n = n_markers;
+    mk.anchor = heading_anchor;
+    mk.def.assign(defaults, defaults + n_markers);
+    mk.tap_morph.resize(M);
+    for (size_t m = 0; m < M; ++m) mk.tap_morph[m] = mk.planes + m * n * NW;
     return OATGPU_OK;
 }
 
@@ -2496,8 +2452,8 @@ static int check_marker_ix(oatgpu_ctx *c, int s, int m)
 {
     const int rc = check_stream_ix(c, s);
     if (rc) return rc;
-    if (c->mk_n == 0) return fail(c, OATGPU_E_INVALID, "marker sets are not configured (oatgpu_set_markers)");
-    if (m < 0 || m >= c->mk_n) return fail(c, OATGPU_E_INVALID, "marker index %d out of range (have %d)", m, c->mk_n);
+    if (c->mk.n == 0) return fail(c, OATGPU_E_INVALID, "marker sets are not configured (oatgpu_set_markers)");
+    if (m < 0 || m >= c->mk.n) return fail(c, OATGPU_E_INVALID, "marker index %d out of range (have %d)", m, c->mk.n);
     return OATGPU_OK;
 }
 
@@ -2506,15 +2462,15 @@ extern "C" int oatgpu_set_marker_window(oatgpu_ctx *c, int32_t s, int32_t marker
     int rc = check_marker_ix(c, s, marker);
     if (rc) return rc;
     if (!m) return fail(c, OATGPU_E_INVALID, "null argument");
-    oatgpu_marker w = c->mk_def[(size_t)marker];      // erode / dilate / area stay the marker's: only the window is checked and taken
+    oatgpu_marker w = c->mk.def[(size_t)marker];      // erode / dilate / area stay the marker's: only the window is checked and taken
     w.h_lo = m->h_lo; w.h_hi = m->h_hi; w.s_lo = m->s_lo; w.s_hi = m->s_hi; w.v_lo = m->v_lo; w.v_hi = m->v_hi;
     rc = check_detector(c, w);
     if (rc) return rc;
     rc = open_sync(c);
     if (rc) return rc;
-    const size_t i = (size_t)s * c->mk_n + marker;
-    c->mk_win_host[i] = range_of(w);
-    HIPCHK(c, hipMemcpy(c->mk_win + i, &c->mk_win_host[i], sizeof(RangeParams), hipMemcpyHostToDevice));
+    const size_t i = (size_t)s * c->mk.n + marker;
+    c->mk.win_host[i] = range_of(w);
+    HIPCHK(c, hipMemcpy(c->mk.win + i, &c->mk.win_host[i], sizeof(RangeParams), hipMemcpyHostToDevice));
     return OATGPU_OK;
 }
 
@@ -2532,7 +2488,7 @@ static int read_plane(oatgpu_ctx *c, const u64 *plane, uint8_t *out)
 static int marker_step_refusals(oatgpu_ctx *c, const char *what = "track_markers")
 {
     if (c->ring_count || c->staged_count) return fail(c, OATGPU_E_INVALID, "%s while enqueued results are outstanding", what);
-    if (c->mk_n == 0) return fail(c, OATGPU_E_INVALID, "marker sets are not configured (oatgpu_set_markers)");
+    if (c->mk.n == 0) return fail(c, OATGPU_E_INVALID, "marker sets are not configured (oatgpu_set_markers)");
     if (!own_window_is_nonzero(c->cfg))
         return fail(c, OATGPU_E_INVALID, "%s needs the context's own window to be the non-zero window: %s", what,
                     c->cfg.channels == 1 ? "intensity [1,256]" : "H [0,256], S [0,256], V [1,256]");
@@ -2547,60 +2503,51 @@ extern "C" int oatgpu_set_marker_pipeline(oatgpu_ctx *c, int32_t on)
 {
     if (!c) return OATGPU_E_INVALID;
     if (!on) {
-        if (!c->mkp_on) return OATGPU_OK;
+        if (!c->mkp.on) return OATGPU_OK;
         if (c->ring_count || c->staged_count)
             return fail(c, OATGPU_E_INVALID, "set_marker_pipeline while enqueued results are outstanding");
         const int rc = open_sync(c);
         if (rc) return rc;
-        free_marker_pipeline(c);
+        c->mkp = {};
         return OATGPU_OK;
     }
     { const int rrc = marker_step_refusals(c, "set_marker_pipeline"); if (rrc) return rrc; }
-    if (c->mkp_on) return OATGPU_OK;
+    if (c->mkp.on) return OATGPU_OK;
     int rc = open_sync(c);
     if (rc) return rc;
     const Geom &g = c->g;
-    const size_t n = c->cfg.n_streams, M = (size_t)c->mk_n, NW = (size_t)g.Palloc / 64, planes = M * n, ring = (size_t)c->ring_slots;
+    const size_t n = c->cfg.n_streams, M = (size_t)c->mk.n, NW = (size_t)g.Palloc / 64, planes = M * n, ring = (size_t)c->ring_slots;
     // the one-launch back half: a geometry the LDS kernel takes, and a row scan whose LDS holds the largest dilation of the set
     std::vector<BlobTab> tab(planes);
     int max_dil = 0;
     for (size_t m = 0; m < M; ++m) {
-        const oatgpu_marker &k = c->mk_def[m];
+        const oatgpu_marker &k = c->mk.def[m];
         const MorphPlan mp = plan_morph(g, k.erode, k.dilate);
         max_dil = std::max(max_dil, mp.dil);
         for (size_t s = 0; s < n; ++s) tab[m * n + s] = BlobTab{mp.ero ? mp.ero : 1, mp.dil, k.min_area, k.max_area};
     }
-    c->mkp_max_dil = max_dil;
-    c->mkp_table = g.H > 2 && g.H <= 16383 && g.W <= 16383 && rowscan_lds_bytes(g, max_dil) <= kRowscanLdsMax;
-    bool ok = true;
-    auto A = [&](void **p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) ok = false; };
-    A((void **)&c->mkp_planes, ring * planes * NW * 8);
-    A((void **)&c->mkp_masks, ring * 3 * planes * NW * 8);
-    A((void **)&c->mkp_tab, planes * sizeof(BlobTab));
-    A((void **)&c->mkp_res, 2 * planes * sizeof(ResultRec));
-    if (ok && hipHostMalloc((void **)&c->mkp_rec_host, ring * c->mkp_set_bytes(), hipHostMallocMapped) != hipSuccess) ok = false;
-    if (ok && hipHostGetDevicePointer((void **)&c->mkp_rec_dev, c->mkp_rec_host, 0) != hipSuccess) ok = false;
-    for (auto &b : c->mkp_bb) if (ok) ok = alloc_scratch(c, b, planes);
+    MarkerPipeline mkp;                  // built aside: the context takes it when everything worked
+    mkp.max_dil = max_dil;
+    mkp.table = g.H > 2 && g.H <= 16383 && g.W <= 16383 && rowscan_lds_bytes(g, max_dil) <= kRowscanLdsMax;
+    mkp.set_bytes = planes * sizeof(ResultRec) + n * (sizeof(MarkerCombined) + sizeof(MarkerFiltered));
+    bool ok = mkp.planes.alloc(ring * planes * NW * 8) == hipSuccess;
+    ok = ok && mkp.masks.alloc(ring * 3 * planes * NW * 8) == hipSuccess;
+    ok = ok && mkp.tab.alloc(planes * sizeof(BlobTab)) == hipSuccess;
+    ok = ok && mkp.res.alloc(2 * planes * sizeof(ResultRec)) == hipSuccess;
+    ok = ok && mkp.rec.alloc(ring * mkp.set_bytes, hipHostMallocMapped) == hipSuccess;
+    for (auto &b : mkp.bb) ok = ok && b.alloc(c, planes);
     // (the taps may be read before a slot's first step; words beyond the frame are never written by the back half)
-    if (ok && hipMemsetAsync(c->mkp_planes, 0, ring * planes * NW * 8, c->stream) != hipSuccess) ok = false;
-    if (ok && hipMemsetAsync(c->mkp_masks, 0, ring * 3 * planes * NW * 8, c->stream) != hipSuccess) ok = false;
-    if (ok && hipMemcpy(c->mkp_tab, tab.data(), planes * sizeof(BlobTab), hipMemcpyHostToDevice) != hipSuccess) ok = false;
-    if (ok) {
-        c->mkp_ev.assign(ring, nullptr);
-        for (auto &e : c->mkp_ev)
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { e = nullptr; ok = false; }
-        if (hipEventCreateWithFlags(&c->mkp_bits_ev, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) ok = false;
-    }
-    if (ok && hipStreamSynchronize(c->stream) != hipSuccess) ok = false;
-    if (!ok) {
-        const hipError_t e = hipGetLastError();
-        c->mkp_ev.erase(std::remove(c->mkp_ev.begin(), c->mkp_ev.end(), (hipEvent_t) nullptr), c->mkp_ev.end());
-        free_marker_pipeline(c);
-        return fail(c, OATGPU_E_NOMEM, "marker pipeline: allocation failed: %s", hipGetErrorString(e));
-    }
-    c->mkp_ev_of.assign(ring, 0);
-    c->mkp_tap_morph.assign(ring * M, nullptr);
-    c->mkp_on = true;
+    ok = ok && hipMemsetAsync(mkp.planes, 0, ring * planes * NW * 8, c->stream) == hipSuccess;
+    ok = ok && hipMemsetAsync(mkp.masks, 0, ring * 3 * planes * NW * 8, c->stream) == hipSuccess;
+    ok = ok && hipMemcpy(mkp.tab, tab.data(), planes * sizeof(BlobTab), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && make_events(mkp.ev, ring, hipEventDisableTiming) == hipSuccess;
+    ok = ok && mkp.bits_ev.create(hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
+    ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
+    if (!ok) return fail(c, OATGPU_E_NOMEM, "marker pipeline: allocation failed: %s", hipGetErrorString(hipGetLastError()));
+    mkp.ev_of.assign(ring, 0);
+    mkp.tap_morph.assign(ring * M, nullptr);
+    mkp.on = true;
+    c->mkp = std::move(mkp);
     return OATGPU_OK;
 }
 
@@ -2613,52 +2560,53 @@ extern "C" int oatgpu_track_markers_dev(oatgpu_ctx *c, const void *frames_dev, d
     // ---- 1. refusals, before anything has moved ----
     { const int rrc = marker_step_refusals(c); if (rrc) return rrc; }
     const Geom &g = c->g;
-    const int n = c->cfg.n_streams, M = c->mk_n;
+    const int n = c->cfg.n_streams, M = c->mk.n;
     const size_t NW = (size_t)g.Palloc / 64;
     // ---- 2. the existing step, unchanged: enqueue + collect ----
     std::vector<oatgpu_position> fg_own;
     if (!fg) { fg_own.resize((size_t)n); fg = fg_own.data(); }
-    const bool pipe = c->mkp_on;          // (the step's own marker work follows: nothing of the pipelined path's for this frame)
-    c->mkp_on = false;
+    const bool pipe = c->mkp.on;          // (the step's own marker work follows: nothing of the pipelined path's for this frame)
+    c->mkp.on = false;
     int rc = oatgpu_track_batch_dev(c, frames_dev, lr, fg);
-    c->mkp_on = pipe;
+    c->mkp.on = pipe;
     if (rc) return rc;
-    c->mk_last_slot = -1;
+    c->mkp.last_slot = -1;
     // ---- 3. every marker's mask from the frames the per-pixel kernel read and the Z plane it has just written ----
     hipStream_t A = c->stream;
     const uint8_t *seen = c->ud_track ? c->ud_frames[0] : (const uint8_t *)frames_dev;
-    launch_marker_bits(g, seen, c->cfg.channels, thr_buf(c, c->last_slot), c->mk_win, M, c->mk_planes, n, A);
+    launch_marker_bits(g, seen, c->cfg.channels, thr_buf(c, c->last_slot), c->mk.win, M, c->mk.planes, n, A);
     HIPCHK(c, hipGetLastError());
     // ---- 4. each marker's back half on its plane, with its erode / dilate / area ----
     for (int m = 0; m < M; ++m) {
-        const oatgpu_marker &k = c->mk_def[(size_t)m];
-        BlobBuffers bb = c->mk_bb;
-        u64 *own = c->mk_masks + (size_t)m * 3 * n * NW;
+        const oatgpu_marker &k = c->mk.def[(size_t)m];
+        BlobBuffers bb = c->mk.bb.b;
+        u64 *own = c->mk.masks + (size_t)m * 3 * n * NW;
         bb.tmp = own; bb.morph = own + (size_t)n * NW; bb.fin = own + 2 * (size_t)n * NW;
         const MorphPlan mp = plan_morph(g, k.erode, k.dilate);
-        const MorphIssued mi = issue_morph(g, mp, bb, c->mk_planes + (size_t)m * n * NW, 0, n, A);
-        c->mk_tap_morph[(size_t)m] = mi.tap;
-        launch_blob(g, bb, mi.src, mi.ero, mp.dil, k.min_area, k.max_area, c->mk_res + (size_t)m * n, 0, n, A, kBlobFull);
+        const MorphIssued mi = issue_morph(g, mp, bb, c->mk.planes + (size_t)m * n * NW, 0, n, A);
+        c->mk.tap_morph[(size_t)m] = mi.tap;
+        launch_blob(g, bb, mi.src, mi.ero, mp.dil, k.min_area, k.max_area, c->mk.res + (size_t)m * n, 0, n, A, kBlobFull);
         HIPCHK(c, hipGetLastError());
     }
     // ---- 5. posicom mean, one copy back, one synchronisation ----
-    MarkerCombined *comb_dev = (MarkerCombined *)(c->mk_res + (size_t)M * n);
-    launch_marker_combine(c->mk_res, M, c->mk_anchor, n, comb_dev, A);
+    MarkerCombined *comb_dev = (MarkerCombined *)(c->mk.res + (size_t)M * n);
+    launch_marker_combine(c->mk.res, M, c->mk.anchor, n, comb_dev, A);
     HIPCHK(c, hipGetLastError());
-    if (c->mf_on) {       // the chain, behind the combiner and before the copy back
+    if (c->mf.on) {       // the chain, behind the combiner and before the copy back
         const MarkerCombined *comb_c = comb_dev;
-        launch_marker_filters(c->mf_params, c->mf_state, &comb_c, &c->mf_out, n, 1, A);
+        MarkerFiltered *filt = c->mf.out;
+        launch_marker_filters(c->mf.params, c->mf.state, &comb_c, &filt, n, 1, A);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->mf_out_host, c->mf_out, (size_t)n * sizeof(MarkerFiltered), hipMemcpyDeviceToHost, A));
+        HIPCHK(c, hipMemcpyAsync(c->mf.out_host.host(), c->mf.out, (size_t)n * sizeof(MarkerFiltered), hipMemcpyDeviceToHost, A));
     }
     const size_t res_bytes = (size_t)M * n * sizeof(ResultRec) + (size_t)n * sizeof(MarkerCombined);
-    HIPCHK(c, hipMemcpyAsync(c->mk_res_host, c->mk_res, res_bytes, hipMemcpyDeviceToHost, A));
+    HIPCHK(c, hipMemcpyAsync(c->mk.res_host.host(), c->mk.res, res_bytes, hipMemcpyDeviceToHost, A));
     HIPCHK(c, hipStreamSynchronize(A));
-    const ResultRec *r = (const ResultRec *)c->mk_res_host;
+    const ResultRec *r = c->mk.res_host.host();
     for (int s = 0; s < n; ++s)
         for (int m = 0; m < M; ++m) to_position(r[(size_t)m * n + s], &markers[(size_t)s * M + m]);
     if (mean) memcpy(mean, r + (size_t)M * n, (size_t)n * sizeof(oatgpu_combined));
-    if (c->mf_on) keep_filtered(c, c->mf_out_host);
+    if (c->mf.on) keep_filtered(c, c->mf.out_host.host());
     return OATGPU_OK;
 }
 
@@ -2668,7 +2616,7 @@ extern "C" int oatgpu_set_marker_filters(oatgpu_ctx *c, const oatgpu_marker_filt
 {
     if (!c) return OATGPU_E_INVALID;
     if (c->ring_count || c->staged_count) return fail(c, OATGPU_E_INVALID, "set_marker_filters while enqueued results are outstanding");
-    if (c->mk_n == 0) return fail(c, OATGPU_E_INVALID, "marker sets are not configured (oatgpu_set_markers)");
+    if (c->mk.n == 0) return fail(c, OATGPU_E_INVALID, "marker sets are not configured (oatgpu_set_markers)");
     const bool on = f && (f->kalman || f->homography || f->n_regions > 0);
     std::vector<MarkerFilterParams> hp(on ? 1 : 0);      // (8 KiB: not on the stack)
     if (on) {
@@ -2707,36 +2655,36 @@ extern "C" int oatgpu_set_marker_filters(oatgpu_ctx *c, const oatgpu_marker_filt
     }
     int rc = open_sync(c);
     if (rc) return rc;
-    if (!on) { free_marker_filters(c); return OATGPU_OK; }
+    if (!on) { c->mf = {}; return OATGPU_OK; }
     const size_t n = (size_t)c->cfg.n_streams;
-    if (!c->mf_params) {
-        bool ok = hipMalloc((void **)&c->mf_params, sizeof(MarkerFilterParams)) == hipSuccess;
-        ok = ok && hipMalloc((void **)&c->mf_state, n * sizeof(KalmanState)) == hipSuccess;
-        ok = ok && hipMalloc((void **)&c->mf_out, n * sizeof(MarkerFiltered)) == hipSuccess;
-        ok = ok && hipHostMalloc((void **)&c->mf_out_host, n * sizeof(MarkerFiltered), hipHostMallocDefault) == hipSuccess;
-        if (!ok) {
-            const hipError_t e = hipGetLastError();
-            free_marker_filters(c);
-            return fail(c, OATGPU_E_NOMEM, "marker filters: allocation failed: %s", hipGetErrorString(e));
-        }
+    MarkerFilters made;                     // first use: built aside, moved in when everything worked
+    const bool first = !c->mf.params;
+    MarkerFilters &mf = first ? made : c->mf;
+    if (first) {
+        bool ok = mf.params.alloc(sizeof(MarkerFilterParams)) == hipSuccess;
+        ok = ok && mf.state.alloc(n * sizeof(KalmanState)) == hipSuccess;
+        ok = ok && mf.out.alloc(n * sizeof(MarkerFiltered)) == hipSuccess;
+        ok = ok && mf.out_host.alloc(n * sizeof(MarkerFiltered), hipHostMallocDefault) == hipSuccess;
+        if (!ok) return fail(c, OATGPU_E_NOMEM, "marker filters: allocation failed: %s", hipGetErrorString(hipGetLastError()));
     }
-    HIPCHK(c, hipMemcpy(c->mf_params, hp.data(), sizeof(MarkerFilterParams), hipMemcpyHostToDevice));
-    launch_kalman_reset(c->mf_state, (int)n, 0u, c->stream);          // every stream's filter from the reference's initial state
+    HIPCHK(c, hipMemcpy(mf.params, hp.data(), sizeof(MarkerFilterParams), hipMemcpyHostToDevice));
+    launch_kalman_reset(mf.state, (int)n, 0u, c->stream);          // every stream's filter from the reference's initial state
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->mf_on = true;
-    c->mf_last_sets = 0;
+    if (first) c->mf = std::move(made);
+    c->mf.on = true;
+    c->mf.last_sets = 0;
     return OATGPU_OK;
 }
 
 extern "C" int oatgpu_marker_filtered(oatgpu_ctx *c, oatgpu_filtered *out, int32_t max_sets)
 {
     if (!c || !out) return fail(c, OATGPU_E_INVALID, "null argument");
-    if (!c->mf_on) return fail(c, OATGPU_E_INVALID, "no filter chain is configured (oatgpu_set_marker_filters)");
-    if (c->mf_last_sets == 0) return fail(c, OATGPU_E_INVALID, "no marker result has been delivered since the filter chain was configured");
-    if (max_sets < c->mf_last_sets) return fail(c, OATGPU_E_INVALID, "room for %d frame sets, the latest call delivered %d", max_sets, c->mf_last_sets);
-    memcpy(out, c->mf_last.data(), (size_t)c->mf_last_sets * c->cfg.n_streams * sizeof(oatgpu_filtered));
-    return c->mf_last_sets;
+    if (!c->mf.on) return fail(c, OATGPU_E_INVALID, "no filter chain is configured (oatgpu_set_marker_filters)");
+    if (c->mf.last_sets == 0) return fail(c, OATGPU_E_INVALID, "no marker result has been delivered since the filter chain was configured");
+    if (max_sets < c->mf.last_sets) return fail(c, OATGPU_E_INVALID, "room for %d frame sets, the latest call delivered %d", max_sets, c->mf.last_sets);
+    memcpy(out, c->mf.last.data(), (size_t)c->mf.last_sets * c->cfg.n_streams * sizeof(oatgpu_filtered));
+    return c->mf.last_sets;
 }
 
 extern "C" int oatgpu_track_markers(oatgpu_ctx *c, const uint8_t *const *frames_host, int32_t n, double lr, oatgpu_position *fg,
@@ -2760,12 +2708,12 @@ extern "C" int oatgpu_read_marker_mask(oatgpu_ctx *c, int32_t s, int32_t marker,
     if (rc) return rc;
     const size_t n = c->cfg.n_streams, NW = (size_t)c->g.Palloc / 64;
     // the planes of the frame set collected last: a ring slot's (the pipelined path), or the synchronous step's
-    const size_t M = (size_t)c->mk_n, slot = (size_t)(c->mk_last_slot < 0 ? 0 : c->mk_last_slot);
-    const bool piped = c->mkp_on && c->mk_last_slot >= 0;
-    const u64 *base = which == OATGPU_TAP_THRESHOLD ? (piped ? c->mkp_planes + (slot * M + marker) * n * NW : c->mk_planes + (size_t)marker * n * NW)
-                    : which == OATGPU_TAP_MORPH ? (piped ? c->mkp_tap_morph[slot * M + marker] : c->mk_tap_morph[(size_t)marker])
-                    : which == OATGPU_TAP_FINAL ? (piped ? c->mkp_masks + ((slot * 3 + 2) * M + marker) * n * NW
-                                                         : c->mk_masks + ((size_t)marker * 3 + 2) * n * NW) : nullptr;
+    const size_t M = (size_t)c->mk.n, slot = (size_t)(c->mkp.last_slot < 0 ? 0 : c->mkp.last_slot);
+    const bool piped = c->mkp.on && c->mkp.last_slot >= 0;
+    const u64 *base = which == OATGPU_TAP_THRESHOLD ? (piped ? c->mkp.planes + (slot * M + marker) * n * NW : c->mk.planes + (size_t)marker * n * NW)
+                    : which == OATGPU_TAP_MORPH ? (piped ? c->mkp.tap_morph[slot * M + marker] : c->mk.tap_morph[(size_t)marker])
+                    : which == OATGPU_TAP_FINAL ? (piped ? c->mkp.masks + ((slot * 3 + 2) * M + marker) * n * NW
+                                                         : c->mk.masks + ((size_t)marker * 3 + 2) * n * NW) : nullptr;
     if (!base) return fail(c, OATGPU_E_INVALID, "unknown tap %d", which);
     return read_plane(c, base + (size_t)s * NW, out);
 }
@@ -2798,7 +2746,7 @@ extern "C" int oatgpu_mog_get_state(oatgpu_ctx *c, int32_t s, uint8_t *modes_use
     const size_t npx = (size_t)g.H * g.W, k = c->cfg.nmixtures, mb = 4 * (size_t)c->cfg.channels;
     ModelBufs b;                         // freed on every return path
     HIPCHK(c, b.alloc(npx, k, mb));
-    uint8_t *d_mu = (uint8_t *)b.mu.p; float *d_w = (float *)b.w.p, *d_v = (float *)b.v.p, *d_m = (float *)b.m.p;
+    uint8_t *d_mu = b.mu; float *d_w = b.w, *d_v = b.v, *d_m = b.m;
     launch_state_export(g, c->state + (size_t)s * mog_stream_floats(g.Palloc), c->nmodes + (size_t)s * g.Palloc, (int)k,
                         c->cfg.channels, d_mu, d_w, d_v, d_m, c->stream);
     hipError_t e = hipGetLastError();
@@ -2825,7 +2773,7 @@ extern "C" int oatgpu_mog_set_state(oatgpu_ctx *c, int32_t s, const uint8_t *mod
     const size_t npx = (size_t)g.H * g.W, k = c->cfg.nmixtures, mb = 4 * (size_t)c->cfg.channels;
     ModelBufs b;                         // freed on every return path
     HIPCHK(c, b.alloc(npx, k, mb));
-    uint8_t *d_mu = (uint8_t *)b.mu.p; float *d_w = (float *)b.w.p, *d_v = (float *)b.v.p, *d_m = (float *)b.m.p;
+    uint8_t *d_mu = b.mu; float *d_w = b.w, *d_v = b.v, *d_m = b.m;
     hipError_t e = hipMemcpyAsync(d_mu, modes_used, npx, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_w, weight, npx * k * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_v, variance, npx * k * 4, hipMemcpyHostToDevice, c->stream);
@@ -2951,16 +2899,15 @@ extern "C" int oatgpu_measure_hbm(oatgpu_ctx *c, size_t bytes, int32_t reps, dou
     int rc = open_sync(c);
     if (rc) return rc;
     const size_t n16 = bytes / 16;
-    void *a = nullptr, *b = nullptr;
-    unsigned *sink = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipMalloc(&a, n16 * 16);
-    if (e == hipSuccess) e = hipMalloc(&b, n16 * 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&sink, 4);
+    DevMem<void> a_own, b_own; DevMem<unsigned> sink_own; Event e0, e1;
+    hipError_t e = a_own.alloc(n16 * 16);
+    if (e == hipSuccess) e = b_own.alloc(n16 * 16);
+    if (e == hipSuccess) e = sink_own.alloc(4);
+    void *a = a_own, *b = b_own; unsigned *sink = sink_own;
     if (e == hipSuccess) e = hipMemsetAsync(a, 0x5a, n16 * 16, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(b, 0, n16 * 16, c->stream);
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = e0.create(hipEventDefault);
+    if (e == hipSuccess) e = e1.create(hipEventDefault);
     double best_r = 0, best_c = 0;
     for (int i = 0; i < reps + 1 && e == hipSuccess; ++i) {          // first iteration warms up
         float ms = 0;
@@ -2977,9 +2924,6 @@ extern "C" int oatgpu_measure_hbm(oatgpu_ctx *c, size_t bytes, int32_t reps, dou
         if (e == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess && i && ms > 0)
             best_c = std::max(best_c, (double)(2 * n16 * 16) / (ms * 1e-3) / 1e9);
     }
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    hipFree(a); hipFree(b); hipFree(sink);
     if (e != hipSuccess) return fail(c, OATGPU_E_HIP, "bandwidth probe failed: %s", hipGetErrorString(e));
     if (read_gbps) *read_gbps = best_r;
     if (copy_gbps) *copy_gbps = best_c;
@@ -2992,7 +2936,7 @@ extern "C" int oatgpu_traffic_audit(oatgpu_ctx *c, int32_t on)
     int rc = open_sync(c);
     if (rc) return rc;
     if (on) {
-        if (!c->audit_dev) HIPCHK(c, hipMalloc((void **)&c->audit_dev, 8 * sizeof(unsigned long long)));
+        if (!c->audit_dev) HIPCHK(c, c->audit_dev.alloc(8 * sizeof(unsigned long long)));
         HIPCHK(c, hipMemsetAsync(c->audit_dev, 0, 8 * sizeof(unsigned long long), c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->audit_launches = 0;
@@ -3026,9 +2970,9 @@ extern "C" int oatgpu_profile_enable(oatgpu_ctx *c, int32_t on)
         // calibrate: what an event pair measures on stream A around a launch that does nothing
         // (event processing + dispatch latency; the empty wave itself runs ~1 us)
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipEvent_t e0, e1;
-        HIPCHK(c, hipEventCreateWithFlags(&e0, hipEventDisableSystemFence));
-        HIPCHK(c, hipEventCreateWithFlags(&e1, hipEventDisableSystemFence));
+        Event e0, e1;
+        HIPCHK(c, e0.create(hipEventDisableSystemFence));
+        HIPCHK(c, e1.create(hipEventDisableSystemFence));
         float best = 1e30f;
         for (int i = 0; i < 16; ++i) {
             HIPCHK(c, hipEventRecord(e0, c->stream));
@@ -3038,7 +2982,6 @@ extern "C" int oatgpu_profile_enable(oatgpu_ctx *c, int32_t on)
             float ms = 0;
             if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess && ms < best) best = ms;
         }
-        hipEventDestroy(e0); hipEventDestroy(e1);
         c->event_pair_ms = best < 1e29f ? best : 0.0;
     }
     c->prof = on != 0;

@@ -133,7 +133,7 @@ def test_density_switch_and_probe_schedule_are_the_sources():
     api = _flat(_function(_src("oatgpu_api.hip"), "static int launch_front("))
     assert "if ((t >= 8 && t < 64 && (t & (t - 1)) == 0) || (t >= 64 && (t & 63) == 0)) {" in api
     assert f"if (c->dens_probes && prev[1]) c->nt_loads = {M.DENSE_DEN}ull * prev[0] >= {M.DENSE_NUM}ull * prev[1];" in api
-    assert "const unsigned *prev = c->dens_host + 2 * (ds ^ 1);" in api           # the previous probe's numbers
+    assert "const unsigned *prev = c->dens.host() + 2 * (ds ^ 1);" in api           # the previous probe's numbers
     assert "c->launched_total += (unsigned long long)nj;" in api
     mog = _src("kernels_mog.hip")
     probe = _flat(_function(mog, "void launch_density_probe("))

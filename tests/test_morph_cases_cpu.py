@@ -55,7 +55,7 @@ def test_route_predicates_are_the_sources():
     assert not M.ero_apart(12, 1 << 14, 1, 63) and M.ero_apart(12, 1 << 14, 2, 63)
     # the fused form is taken from an erosion of 2 on; the marker table and the pair need the LDS kernel's geometry
     assert "if (ero_k > 1) hipLaunchKernelGGL(k_rowscan<true>" in blob
-    assert "c->mkp_table = g.H > 2 && g.H <= 16383 && g.W <= 16383 && rowscan_lds_bytes(g, max_dil) <= kRowscanLdsMax;" in api
+    assert "mkp.table = g.H > 2 && g.H <= 16383 && g.W <= 16383 && rowscan_lds_bytes(g, max_dil) <= kRowscanLdsMax;" in api
     assert "const bool lds_geom = g.H > 2 && g.H <= 16383 && g.W <= 16383;" in api
     # a two-frame step whose erosion is apart is not paired (no public call tells: the GPU file runs both sides alike)
     assert "p.paired = nj == 2 && !p.early && c->pair_back && c->lds_spec && !c->kal_on && lds_geom && !p.ero_apart;" in api
