@@ -8,7 +8,7 @@ ARCH     ?= gfx950
 HIPFLAGS ?= --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fPIC -Wall -Wno-unused-result -Wno-unused-value
 CSRC     = oat_amd/csrc
 LIB      = oat_amd/lib/liboatgpu.so
-OBJS     = $(CSRC)/kernels_mog.o $(CSRC)/kernels_blob.o $(CSRC)/kernels_kalman.o $(CSRC)/kernels_undistort.o $(CSRC)/kernels_markers.o $(CSRC)/oatgpu_api.o
+OBJS     = $(CSRC)/kernels_mog.o $(CSRC)/kernels_blob.o $(CSRC)/kernels_kalman.o $(CSRC)/kernels_undistort.o $(CSRC)/kernels_markers.o $(CSRC)/kernels_diff.o $(CSRC)/oatgpu_api.o
 
 all: $(LIB) oracle
 
@@ -49,7 +49,7 @@ clean:
 # OATGPU_MEASURE_PY=1 OATGPU_LIB=<path> (oat_amd/ffi.py; the tools/*.sh A/B scripts set both).
 variant:
 	@mkdir -p build/$(NAME) build/variants
-	for f in kernels_mog kernels_blob kernels_kalman kernels_undistort kernels_markers oatgpu_api; do $(HIPCC) $(HIPFLAGS) -DOATGPU_MEASURE $(DEFS) -c $(CSRC)/$$f.hip -o build/$(NAME)/$$f.o || exit 1; done
+	for f in kernels_mog kernels_blob kernels_kalman kernels_undistort kernels_markers kernels_diff oatgpu_api; do $(HIPCC) $(HIPFLAGS) -DOATGPU_MEASURE $(DEFS) -c $(CSRC)/$$f.hip -o build/$(NAME)/$$f.o || exit 1; done
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/variants/liboatgpu_$(NAME).so build/$(NAME)/*.o
 clean-variants:
 	rm -rf build/variants oat_amd/lib/liboatgpu_*.so

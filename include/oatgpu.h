@@ -43,7 +43,9 @@ extern "C" {
  * oatgpu_set_markers, oatgpu_set_marker_window, oatgpu_track_markers_dev, oatgpu_track_markers, oatgpu_read_marker_mask,
  * with the structs oatgpu_marker and oatgpu_combined; marker sets on the pipelined path -- oatgpu_set_marker_pipeline,
  * oatgpu_track_collect_markers, oatgpu_track_markers_sequence_dev; the filter chain behind the combined record --
- * oatgpu_set_marker_filters, oatgpu_marker_filtered, with the structs oatgpu_region, oatgpu_marker_filters, oatgpu_filtered. */
+ * oatgpu_set_marker_filters, oatgpu_marker_filtered, with the structs oatgpu_region, oatgpu_marker_filters, oatgpu_filtered;
+ * the motion tracker -- oatgpu_set_diff_tracker, oatgpu_diff_reset, oatgpu_diff_batch_dev, oatgpu_diff_batch,
+ * oatgpu_diff_sequence_dev, oatgpu_read_diff_mask. */
 
 enum {
     OATGPU_OK = 0,
@@ -511,6 +513,42 @@ int oatgpu_detect_thresh(oatgpu_ctx *ctx, int32_t stream_ix, const uint8_t *grey
  * dilation is (away from the outermost ring, which findContours zeroes), so the blur runs as a
  * bit-mask dilation. */
 int oatgpu_detect_diff(oatgpu_ctx *ctx, int32_t stream_ix, const uint8_t *grey_in, oatgpu_position *out);
+
+/* ---- motion tracker: framefilt col -C GREY -> posidet diff for EVERY stream of the context, one front launch a step ----
+ *
+ * Frames are cfg.channels wide: 3 = the chain `framefilt col -C GREY -> posidet diff` (DifferenceDetector.cpp:98-173 behind
+ * ColorConvert), 1 = `posidet diff` alone.  Where a stream has a ROI (oatgpu_set_roi_mask) the frame is masked first
+ * (`framefilt mask` in front of col).  Parameters are the config's diff_threshold, blur and min_area / max_area; erode never.
+ * A stream's first frame is analysed as it is (pixel != 0, no blur), afterwards blur is a dilation -- oatgpu_detect_diff's rules,
+ * and oatgpu_detect_diff's STATE: the last image and the first-frame flag of a stream are shared, a stream advanced by one form
+ * continues in the other.
+ *
+ * oatgpu_set_diff_tracker(1) drains outstanding work and allocates everything a step needs (an out-of-memory is reported here,
+ * as OATGPU_E_NOMEM, never in the middle of a step): the last-image planes if oatgpu_detect_diff has not made them (1 byte a
+ * pixel and stream), four sets of threshold words and of the tracker's own MORPH / FINAL planes (3 bits a pixel and stream a
+ * set: 1.5 bytes in all), four host-mapped result sets and eight events.  The rest of a back half's scratch is the context's own
+ * sets 0..3, used only while nothing else of the context is in flight.  0 frees it all but the last images.
+ *
+ * Every diff call is synchronous: it returns with none of its work in flight and leaves the result ring, the pipelined path's
+ * counters and what oatgpu_read_mask shows untouched.  OATGPU_E_INVALID, with a message naming the cause and before anything is
+ * read or has moved: the tracker is off; results are outstanding (oatgpu_track_enqueue*) or a set is partly staged;
+ * oatgpu_set_kalman, oatgpu_set_homography or oatgpu_set_track_undistort is on; a null argument; n != n_streams;
+ * n_frames < 0.  n_frames == 0 succeeds and does nothing. */
+int oatgpu_set_diff_tracker(oatgpu_ctx *ctx, int32_t on);
+/* Forget the last image of one stream (-1: of every stream): its next frame is a first frame again.  Also for oatgpu_detect_diff. */
+int oatgpu_diff_reset(oatgpu_ctx *ctx, int32_t stream_ix);
+/* One step: frames_dev = n_streams*rows*cols*channels bytes, stream-major (as oatgpu_track_batch_dev); out[n_streams].
+ * Frames and rows of any alignment are taken; 4-byte aligned frames of a width divisible by 4 take the 4-pixels-a-lane kernel. */
+int oatgpu_diff_batch_dev(oatgpu_ctx *ctx, const void *frames_dev, oatgpu_position *out);
+/* The same on host frames: frames_host[i] -> rows*cols*channels bytes of stream i. */
+int oatgpu_diff_batch(oatgpu_ctx *ctx, const uint8_t *const *frames_host, int32_t n, oatgpu_position *out);
+/* A recorded sequence in one call: frames_dev[t] = frame set t, out[n_frames][n_streams].  Up to four frames are in flight, two
+ * consecutive frames share a front launch wherever every stream has a last image; results, masks and the last images are those
+ * of n_frames calls of oatgpu_diff_batch_dev. */
+int oatgpu_diff_sequence_dev(oatgpu_ctx *ctx, const void *const *frames_dev, int32_t n_frames, oatgpu_position *out);
+/* oatgpu_read_mask for the latest diff frame (of a sequence: its last): which = OATGPU_TAP_THRESHOLD (|g - last| > thr),
+ * _MORPH (after the blur-as-dilation), _FINAL; out rows*cols bytes {0, 255}.  OATGPU_E_INVALID before the first diff step. */
+int oatgpu_read_diff_mask(oatgpu_ctx *ctx, int32_t stream_ix, int32_t which, uint8_t *out);
 
 /* ---- fused hot path: mog + setTo + BGR2HSV + inRange + erode + dilate + blob ---- */
 

@@ -386,6 +386,52 @@ class DifferenceDetector(_Detector):
         return _merge(position, p)
 
 
+class MotionTracker(_Detector):
+    """The batched motion tracker: `framefilt col -C GREY` -> `posidet diff` for N camera streams, one front launch a step
+    (oatgpu_set_diff_tracker).  channels = 3: BGR frames (rows, cols, 3); 1: GREY frames (rows, cols).  Options follow
+    DifferenceDetector.cpp:47-64 (-d diff-threshold, -b blur, -a area).  A ROI (set_roi_mask) masks the frame first."""
+
+    def __init__(self, rows, cols, n_streams=1, channels=3, diff_threshold=10, blur=2, area=(0.0, DBL_MAX), device=0, **kw):
+        super().__init__(rows, cols, n_streams=n_streams, channels=channels, diff_threshold=diff_threshold, blur=blur,
+                         erode=0, dilate=0, min_area=area[0], max_area=area[1], device=device, **kw)
+        self._pos = (ffi.Position * n_streams)()
+        self._chk(self.lib.oatgpu_set_diff_tracker(self.ctx, 1))
+
+    def _out(self):
+        return [Position2D.from_c(p) for p in self._pos]
+
+    def track(self, frames):
+        """frames: sequence of n_streams host arrays -> one Position2D per stream (oatgpu_diff_batch)."""
+        fs = [_frame(f, self.frame_shape) for f in frames]
+        ptrs = (ffi._u8p * max(len(fs), 1))(*[ffi.u8(f) for f in fs])
+        self._chk(self.lib.oatgpu_diff_batch(self.ctx, ptrs, len(fs), self._pos))
+        return self._out()
+
+    def track_dev(self, dev_ptr):
+        """dev_ptr: device address of n_streams*rows*cols*channels bytes, stream-major (oatgpu_diff_batch_dev)."""
+        self._chk(self.lib.oatgpu_diff_batch_dev(self.ctx, C.c_void_p(dev_ptr), self._pos))
+        return self._out()
+
+    def track_sequence_dev(self, dev_ptrs):
+        """A recorded sequence in one call (oatgpu_diff_sequence_dev): dev_ptrs[t] = device address of frame set t; returns
+        one list of Position2D per frame set."""
+        T, n = len(dev_ptrs), self.n_streams
+        arr = (C.c_void_p * max(T, 1))(*dev_ptrs)
+        out = (ffi.Position * max(T * n, 1))()
+        self._chk(self.lib.oatgpu_diff_sequence_dev(self.ctx, arr, T, out))
+        return [[Position2D.from_c(out[t * n + s]) for s in range(n)] for t in range(T)]
+
+    def reset(self, stream=None):
+        """Forget the last image of one stream (None: of all): its next frame is a first frame again (oatgpu_diff_reset)."""
+        self._chk(self.lib.oatgpu_diff_reset(self.ctx, -1 if stream is None else int(stream)))
+
+    def read_mask(self, which=ffi.TAP_MORPH, stream=0):
+        """A plane of the latest diff frame (oatgpu_read_diff_mask)."""
+        out = np.empty((self.rows, self.cols), np.uint8)
+        self._chk(self.lib.oatgpu_read_diff_mask(self.ctx, int(stream), which, ffi.u8(out)))
+        return out
+
+
 def _merge(position, p):
     """siftContours only writes x/y when a blob is found (DetectorFunc.cpp:46,58-60)."""
     new = Position2D.from_c(p)

@@ -1,0 +1,183 @@
+// kernels_diff.hip -- the front end of the motion tracker (`framefilt col -C GREY` -> `posidet diff`) for every
+// camera stream of a context in one launch (grid y = stream).
+//
+// Per pixel: g = grey(B, G, R) (3 channels, RGB2Gray<uchar>'s integers) or the pixel itself (1 channel); g = 0 where the
+// stream's ROI bit is 0 (framefilt mask in front of col: grey(0, 0, 0) = 0); bit = have_last ? |g - last| > thr : g != 0
+// (cv::absdiff + cv::threshold(THRESH_BINARY), DifferenceDetector.cpp:156-171); last = g.  With a second frame in the launch
+// (PAIR) the first frame's grey stays in registers: bits2 = |g2 - g| > thr, last = g2.
+//
+// Two instantiations of the lane mapping:
+//   wide   (W % 4 == 0, frame and `last` 4-byte aligned): a lane owns 4 consecutive pixels of one row -- one dword load and one
+//          dword store of `last`, one dword (GREY) or three dwords (BGR, 12 bytes) of the frame.  A wave covers 256 pixels = 4
+//          mask words; bit k of every lane is gathered by one ballot, and lane w < 4 interleaves the four 16-bit fields of its
+//          word out of the four ballots and stores it: every word is stored once, 64 bits a lane.
+//   narrow (everything else): one pixel a lane with byte accesses, the ballot is the word (k_absdiff_bits' mapping).
+// Both write EVERY word of Palloc / 64 (zero bits for x >= W and p >= P): the row scan reads them.
+#include "oatgpu_internal.h"
+
+namespace oatgpu {
+
+namespace {
+
+__device__ __forceinline__ int grey_bgr(unsigned b, unsigned g, unsigned r)
+{
+    return (int)((1868u * b + 9617u * g + 4899u * r + 8192u) >> 14);
+}
+__device__ __forceinline__ bool differs(int a, int b, int thr) { return (a > b ? a - b : b - a) > thr; }
+
+// byte k of three little-endian dwords
+__device__ __forceinline__ unsigned byte_of(const unsigned (&d)[3], int k) { return (d[k >> 2] >> ((k & 3) * 8)) & 255u; }
+
+// the four greys of the 4 pixels at raster index i (a multiple of 4) of one frame, as one little-endian dword
+template <int CH> __device__ __forceinline__ unsigned grey4(const uint8_t *frame, size_t i)
+{
+    if (CH == 1) return *(const unsigned *)(frame + i);
+    const unsigned *q = (const unsigned *)(frame + 3 * i);
+    const unsigned d[3] = {q[0], q[1], q[2]};
+    unsigned g = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) g |= (unsigned)grey_bgr(byte_of(d, 3 * k), byte_of(d, 3 * k + 1), byte_of(d, 3 * k + 2)) << (8 * k);
+    return g;
+}
+
+// bits 0..15 of x to bits 0, 4, 8, .. 60
+__device__ __forceinline__ u64 spread4(u64 x)
+{
+    x = (x | x << 24) & 0x000000ff000000ffull;
+    x = (x | x << 12) & 0x000f000f000f000full;
+    x = (x | x << 6) & 0x0303030303030303ull;
+    x = (x | x << 3) & 0x1111111111111111ull;
+    return x;
+}
+
+// the wave's 4 mask words out of every lane's nibble (bit k = pixel k of the lane): lane w < 4 stores word w
+__device__ __forceinline__ void store_words(unsigned nib, int lane, u64 *dst)
+{
+    const u64 b0 = __ballot(nib & 1u), b1 = __ballot(nib & 2u), b2 = __ballot(nib & 4u), b3 = __ballot(nib & 8u);
+    if (lane < 4) {
+        const int sh = lane * 16;
+        dst[lane] = spread4((b0 >> sh) & 0xffffull) | spread4((b1 >> sh) & 0xffffull) << 1 | spread4((b2 >> sh) & 0xffffull) << 2 |
+                    spread4((b3 >> sh) & 0xffffull) << 3;
+    }
+}
+
+struct DiffArgs {
+    const uint8_t *frames, *frames2;     // [n][H*W*CH] stream-major; frames2: the second frame of a paired launch
+    uint8_t *last;                       // [n][H*W]
+    u64 *bits, *bits2;                   // [n][Palloc/64]
+    const u64 *roi;                      // [n][Palloc/64]
+    u64 have;                            // bit (stream - first_stream): the stream has a last image
+    int thr, first_stream;
+};
+
+template <int CH, bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_diff_wide(Geom g, DiffArgs a)
+{
+    const int s = a.first_stream + (int)blockIdx.y;
+    const bool have = PAIR || ((a.have >> blockIdx.y) & 1ull);      // uniform
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);            // 256 pixels = words 4 * wave .. 4 * wave + 3; Palloc % 1024 == 0
+    const int p0 = wave * 256 + lane * 4;
+    const int y = p0 / g.Wp, x = p0 - y * g.Wp;
+    const size_t npx = (size_t)g.H * g.W, NW = (size_t)(g.Palloc >> 6);
+    unsigned n1 = 0, n2 = 0;
+    if (p0 < g.P && x < g.W) {                                       // W % 4 == 0: the lane's 4 pixels are inside together
+        const size_t i = (size_t)y * g.W + x;
+        unsigned *lp = (unsigned *)(a.last + (size_t)s * npx + i);
+        unsigned keep = 0xffffffffu;
+        if (ROI) {
+            const unsigned r = (((const uint8_t *)(a.roi + (size_t)s * NW))[p0 >> 3] >> (p0 & 4)) & 15u;
+            keep = (r & 1u ? 0xffu : 0u) | (r & 2u ? 0xff00u : 0u) | (r & 4u ? 0xff0000u : 0u) | (r & 8u ? 0xff000000u : 0u);
+        }
+        const unsigned g1 = grey4<CH>(a.frames + (size_t)s * npx * CH, i) & keep;
+        if (have) {
+            const unsigned l = *lp;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) n1 |= differs((g1 >> (8 * k)) & 255u, (l >> (8 * k)) & 255u, a.thr) ? 1u << k : 0u;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) n1 |= ((g1 >> (8 * k)) & 255u) ? 1u << k : 0u;
+        }
+        unsigned out = g1;
+        if (PAIR) {
+            const unsigned g2 = grey4<CH>(a.frames2 + (size_t)s * npx * CH, i) & keep;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) n2 |= differs((g2 >> (8 * k)) & 255u, (g1 >> (8 * k)) & 255u, a.thr) ? 1u << k : 0u;
+            out = g2;
+        }
+        *lp = out;
+    }
+    store_words(n1, lane, a.bits + (size_t)s * NW + (size_t)wave * 4);
+    if (PAIR) store_words(n2, lane, a.bits2 + (size_t)s * NW + (size_t)wave * 4);
+}
+
+template <int CH> __device__ __forceinline__ int grey1(const uint8_t *frame, size_t i)
+{
+    if (CH == 1) return frame[i];
+    return grey_bgr(frame[3 * i], frame[3 * i + 1], frame[3 * i + 2]);
+}
+
+template <int CH, bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_diff_narrow(Geom g, DiffArgs a)
+{
+    const int s = a.first_stream + (int)blockIdx.y;
+    const bool have = PAIR || ((a.have >> blockIdx.y) & 1ull);
+    const int lane = threadIdx.x & 63;
+    const int word = blockIdx.x * 4 + (threadIdx.x >> 6);            // Palloc % 256 == 0: every word of the grid exists
+    const int p = word * 64 + lane;
+    const int y = p / g.Wp, x = p - y * g.Wp;
+    const size_t npx = (size_t)g.H * g.W, NW = (size_t)(g.Palloc >> 6);
+    bool on1 = false, on2 = false;
+    if (p < g.P && x < g.W) {
+        const size_t i = (size_t)y * g.W + x;
+        uint8_t *lp = a.last + (size_t)s * npx + i;
+        const bool keep = !ROI || ((a.roi[(size_t)s * NW + word] >> lane) & 1ull);
+        const int g1 = keep ? grey1<CH>(a.frames + (size_t)s * npx * CH, i) : 0;
+        on1 = have ? differs(g1, *lp, a.thr) : g1 != 0;
+        int out = g1;
+        if (PAIR) {
+            const int g2 = keep ? grey1<CH>(a.frames2 + (size_t)s * npx * CH, i) : 0;
+            on2 = differs(g2, g1, a.thr);
+            out = g2;
+        }
+        *lp = (uint8_t)out;
+    }
+    const u64 w1 = __ballot(on1);
+    if (lane == 0) a.bits[(size_t)s * NW + word] = w1;
+    if (PAIR) {
+        const u64 w2 = __ballot(on2);
+        if (lane == 0) a.bits2[(size_t)s * NW + word] = w2;
+    }
+}
+
+template <int CH, bool ROI, bool PAIR> void launch_one(const Geom &g, const DiffArgs &a, bool wide, int n, hipStream_t st)
+{
+    if (wide) hipLaunchKernelGGL((k_diff_wide<CH, ROI, PAIR>), dim3(g.Palloc / 1024, n), dim3(256), 0, st, g, a);
+    else hipLaunchKernelGGL((k_diff_narrow<CH, ROI, PAIR>), dim3(g.Palloc / 256, n), dim3(256), 0, st, g, a);
+}
+template <int CH> void launch_ch(const Geom &g, const DiffArgs &a, bool wide, int n, hipStream_t st)
+{
+    const bool roi = a.roi != nullptr, pair = a.frames2 != nullptr;
+    if (roi) { if (pair) launch_one<CH, true, true>(g, a, wide, n, st); else launch_one<CH, true, false>(g, a, wide, n, st); }
+    else { if (pair) launch_one<CH, false, true>(g, a, wide, n, st); else launch_one<CH, false, false>(g, a, wide, n, st); }
+}
+
+}  // namespace
+
+bool diff_front_is_wide(const Geom &g, const DiffLaunch &a)
+{
+    const uintptr_t m = (uintptr_t)a.frames | (uintptr_t)a.frames2 | (uintptr_t)a.last;
+    return g.W % 4 == 0 && (m & 3u) == 0;
+}
+
+void launch_diff_front(const Geom &g, const DiffLaunch &a, int n_streams, hipStream_t st)
+{
+    const bool wide = diff_front_is_wide(g, a);
+    for (int s0 = 0; s0 < n_streams; s0 += 64) {         // the have-last mask of a launch is one 64-bit kernel argument
+        const int n = n_streams - s0 < 64 ? n_streams - s0 : 64;
+        DiffArgs k{a.frames, a.frames2, a.last, a.bits, a.bits2, a.roi, 0ull, a.thr, s0};
+        for (int i = 0; i < n; ++i) k.have |= (u64)(a.have_last[s0 + i] != 0) << i;
+        if (a.channels == 3) launch_ch<3>(g, k, wide, n, st);
+        else launch_ch<1>(g, k, wide, n, st);
+    }
+}
+
+}  // namespace oatgpu

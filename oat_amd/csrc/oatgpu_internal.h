@@ -153,6 +153,21 @@ void launch_state_import(const Geom &g, float *state, uint8_t *nmodes, int nmix,
                          const uint8_t *modes_used, const float *weight, const float *variance,
                          const float *mean, hipStream_t st);
 
+// --- kernels_diff.hip --- (the motion tracker's front end: col GREY -> posidet diff's absdiff + threshold)
+struct DiffLaunch {
+    const uint8_t *frames;   // [n][H*W*channels] packed BGR (3) or GREY (1), stream-major
+    const uint8_t *frames2;  // nullptr, or the NEXT frame of every stream: the launch advances two frames (every stream has a last image)
+    int channels;
+    uint8_t *last;           // [n][H*W] previous GREY frame of every stream, refreshed by the launch
+    const char *have_last;   // HOST: [n] 0: the stream's first frame (bit = g != 0)
+    u64 *bits, *bits2;       // [n][Palloc/64] threshold words of the frame(s); every word is written
+    const u64 *roi;          // [n][Palloc/64] region-of-interest bits (framefilt mask in front of col) or nullptr
+    int thr;
+};
+// 4 pixels a lane with dword accesses: W % 4 == 0 and frames / frames2 / last 4-byte aligned; otherwise one pixel a lane
+bool diff_front_is_wide(const Geom &g, const DiffLaunch &a);
+void launch_diff_front(const Geom &g, const DiffLaunch &a, int n_streams, hipStream_t st);
+
 // --- kernels_undistort.hip --- (framefilt undistort, Undistorter.cpp:83-88)
 // 0, or -1 with the reason in *why: 5 to 8 coefficients (the reference's check) and not 6 or 7 (OpenCV 3.1 asserts on those)
 int undistort_check_coeffs(int n_dist, const char **why);

@@ -154,6 +154,12 @@ SIGNATURES = {
     "oatgpu_detect_hsv": (C.c_int, [_ctx, C.c_int32, _u8p, C.POINTER(Position)]),
     "oatgpu_detect_thresh": (C.c_int, [_ctx, C.c_int32, _u8p, C.POINTER(Position)]),
     "oatgpu_detect_diff": (C.c_int, [_ctx, C.c_int32, _u8p, C.POINTER(Position)]),
+    "oatgpu_set_diff_tracker": (C.c_int, [_ctx, C.c_int32]),
+    "oatgpu_diff_reset": (C.c_int, [_ctx, C.c_int32]),
+    "oatgpu_diff_batch_dev": (C.c_int, [_ctx, C.c_void_p, C.POINTER(Position)]),
+    "oatgpu_diff_batch": (C.c_int, [_ctx, C.POINTER(_u8p), C.c_int32, C.POINTER(Position)]),
+    "oatgpu_diff_sequence_dev": (C.c_int, [_ctx, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Position)]),
+    "oatgpu_read_diff_mask": (C.c_int, [_ctx, C.c_int32, C.c_int32, _u8p]),
     "oatgpu_track_batch": (C.c_int, [_ctx, C.POINTER(_u8p), C.c_int32, C.c_double, C.POINTER(Position)]),
     "oatgpu_track_batch_dev": (C.c_int, [_ctx, C.c_void_p, C.c_double, C.POINTER(Position)]),
     "oatgpu_track_enqueue": (C.c_int, [_ctx, C.POINTER(_u8p), C.c_int32, C.c_double]),

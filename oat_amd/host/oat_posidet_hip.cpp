@@ -2,6 +2,7 @@
 //   TYPE  hsv     replacement of `oat posidet hsv`    (src/positiondetector/HSVDetector.cpp)
 //         thresh  replacement of `oat posidet thresh` (src/positiondetector/SimpleThreshold.cpp)
 //         diff    replacement of `oat posidet diff`   (src/positiondetector/DifferenceDetector.cpp)
+//                 diff --bgr: of the chain `oat framefilt col -C GREY` -> `oat posidet diff` on a BGR source (the motion tracker)
 // Same positional arguments and option names as src/positiondetector/main.cpp:85-271.
 #include "component.hpp"
 
@@ -13,10 +14,12 @@ enum class Kind { HSV, THRESH, DIFF };
 
 class GpuDetector : public PositionDetector {
 public:
-    GpuDetector(const std::string &src, const std::string &snk, Kind kind) : PositionDetector(src, snk), kind_(kind)
+    GpuDetector(const std::string &src, const std::string &snk, Kind kind, bool bgr = false)
+        : PositionDetector(src, snk), kind_(kind), bgr_(bgr && kind == Kind::DIFF)
     {
         oatgpu_default_config(&cfg_);
-        if (kind == Kind::HSV) { required_color_ = PIX_HSV; cfg_.erode = 0; cfg_.dilate = 10; }   // HSVDetector.cpp:42-46
+        if (bgr_) { required_color_ = PIX_BGR; cfg_.channels = 3; cfg_.erode = 0; cfg_.dilate = 0; }
+        else if (kind == Kind::HSV) { required_color_ = PIX_HSV; cfg_.erode = 0; cfg_.dilate = 10; }   // HSVDetector.cpp:42-46
         else { required_color_ = PIX_GREY; cfg_.erode = 0; cfg_.dilate = 0; }   // SimpleThreshold.cpp:42-46, DifferenceDetector.cpp:41-44
     }
     oatgpu_config cfg_;
@@ -26,12 +29,14 @@ protected:
     {
         cfg_.rows = (int)p.rows; cfg_.cols = (int)p.cols; cfg_.n_streams = 1;
         gpu_.create(cfg_);
+        if (bgr_) gpu_.check(oatgpu_set_diff_tracker(gpu_.ctx, 1));
     }
     // HSVDetector.cpp:142-173 / SimpleThreshold.cpp:114-134
     // Deferred (oatgpu_set_deferred): the call returns when the frame has left shared memory, PositionDetector::process posts
     // the source, and detect_finish() waits for the kernels and takes the position (PositionDetector.cpp:78-96).
     bool detect_from_shm(const Frame &frame, Position2D &) override
     {
+        if (bgr_) return false;           // the motion tracker's step is synchronous: the frame is copied and the source posted first
         if (!deferred_on_) { gpu_.check(oatgpu_set_deferred(gpu_.ctx, 1)); deferred_on_ = true; }
         gpu_.check(kind_ == Kind::HSV ? oatgpu_detect_hsv(gpu_.ctx, 0, frame.data(), nullptr)
                    : kind_ == Kind::THRESH ? oatgpu_detect_thresh(gpu_.ctx, 0, frame.data(), nullptr)
@@ -48,13 +53,16 @@ protected:
     void detectPosition(Frame &frame, Position2D &position) override
     {
         oatgpu_position r;
-        gpu_.check(kind_ == Kind::HSV ? oatgpu_detect_hsv(gpu_.ctx, 0, frame.data(), &r)
+        const uint8_t *one[1] = {frame.data()};
+        gpu_.check(bgr_ ? oatgpu_diff_batch(gpu_.ctx, one, 1, &r)
+                   : kind_ == Kind::HSV ? oatgpu_detect_hsv(gpu_.ctx, 0, frame.data(), &r)
                    : kind_ == Kind::THRESH ? oatgpu_detect_thresh(gpu_.ctx, 0, frame.data(), &r)
                                            : oatgpu_detect_diff(gpu_.ctx, 0, frame.data(), &r));
         position.position_valid = r.valid != 0;                   // DetectorFunc.cpp:46,58-60
         if (r.valid) { position.position.x = r.x; position.position.y = r.y; }
     }
     Kind kind_;
+    bool bgr_;
     bool deferred_on_{false};
     GpuCtx gpu_;
 };
@@ -63,6 +71,7 @@ static void usage()
 {
     std::cout << "Usage: oat-posidet-hip TYPE SOURCE SINK [CONFIGURATION]\nTYPE\n  hsv | thresh | diff\n"
                  "diff:   -d diff-threshold (default 10)  -b blur (default 2, <= 22)  -a [min,max] area\n"
+                 "        --bgr  the SOURCE is BGR: framefilt col -C GREY is done in front of the detector, in the same kernel\n"
                  "hsv:    -H/-S/-V [min,max] in [0,256]  -e erode  -d dilate (default 10)  -a [min,max] area\n"
                  "thresh: -T [min,max]  -e erode  -d dilate  -a [min,max] area\n"
                  "all:    --gpu-index N  HIP device ordinal (default 0)\n";
@@ -76,7 +85,7 @@ int main(int argc, char **argv)
         Options o = Options::parse(argc, argv,
             {{"H", "h-thresh"}, {"S", "s-thresh"}, {"V", "v-thresh"}, {"T", "thresh"}, {"e", "erode"},
              {"d", is_diff ? "diff-threshold" : "dilate"}, {"b", "blur"}, {"a", "area"}, {"t", "tune"}, {"h", "help"}, {"v", "version"}},
-            {"help", "version", "tune"});
+            {"help", "version", "tune", "bgr"});
         if (o.has("version")) { std::cout << "oat-posidet-hip (MI355X drop-in, liboatgpu ABI " << oatgpu_abi_version() << ")\n"; return 0; }
         if (o.has("help") || o.positional.size() != 3) { usage(); return o.has("help") ? 0 : -1; }
         const std::string type = o.positional[0];
@@ -84,10 +93,11 @@ int main(int argc, char **argv)
         // option names per TYPE: HSVDetector.cpp:49-75, SimpleThreshold.cpp:49-69, DifferenceDetector.cpp:41-62
         if (type == "hsv") o.apply_config({"h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "tune", "gpu-index"}, {"tune"});
         else if (type == "thresh") o.apply_config({"thresh", "erode", "dilate", "area", "tune", "gpu-index"}, {"tune"});
-        else o.apply_config({"diff-threshold", "blur", "area", "tune", "gpu-index"}, {"tune"});
+        else o.apply_config({"diff-threshold", "blur", "area", "tune", "gpu-index", "bgr"}, {"tune", "bgr"});
+        if (o.has("bgr") && type != "diff") throw std::runtime_error("--bgr goes with TYPE diff only");
         if (o.has("tune")) throw std::runtime_error("--tune needs a GUI and is not available in the hip detector");
         auto d = std::make_unique<GpuDetector>(o.positional[1], o.positional[2],
-                                               type == "hsv" ? Kind::HSV : type == "thresh" ? Kind::THRESH : Kind::DIFF);
+                                               type == "hsv" ? Kind::HSV : type == "thresh" ? Kind::THRESH : Kind::DIFF, o.has("bgr"));
         d->cfg_.device = (int)o.num("gpu-index", 0, 0, 64);
         double a, b;
         auto range = [](double x, double y, const char *what) {
