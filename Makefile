@@ -8,12 +8,18 @@ ARCH     ?= gfx950
 HIPFLAGS ?= --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fPIC -Wall -Wno-unused-result -Wno-unused-value
 CSRC     = oat_amd/csrc
 LIB      = oat_amd/lib/liboatgpu.so
-OBJS     = $(CSRC)/kernels_mog.o $(CSRC)/kernels_blob.o $(CSRC)/kernels_kalman.o $(CSRC)/kernels_undistort.o $(CSRC)/kernels_markers.o $(CSRC)/kernels_diff.o $(CSRC)/oatgpu_api.o
+# the units of the library, listed once: the kernels, and the C ABI above them by feature (oatgpu_ctx.h is their shared header)
+KERNELS  = kernels_mog kernels_blob kernels_kalman kernels_undistort kernels_markers kernels_diff
+API      = api_context api_stages api_track api_markers api_diff api_model api_measure
+UNITS    = $(KERNELS) $(API)
+OBJS     = $(UNITS:%=$(CSRC)/%.o)
 
 all: $(LIB) oracle
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/oatgpu_internal.h $(CSRC)/hip_owned.h $(CSRC)/hsv_inline.h $(CSRC)/posfilt_inline.h include/oatgpu.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(API:%=$(CSRC)/%.o): $(CSRC)/oatgpu_ctx.h
 
 $(LIB): $(OBJS)
 	@mkdir -p oat_amd/lib
@@ -49,7 +55,7 @@ clean:
 # OATGPU_MEASURE_PY=1 OATGPU_LIB=<path> (oat_amd/ffi.py; the tools/*.sh A/B scripts set both).
 variant:
 	@mkdir -p build/$(NAME) build/variants
-	for f in kernels_mog kernels_blob kernels_kalman kernels_undistort kernels_markers kernels_diff oatgpu_api; do $(HIPCC) $(HIPFLAGS) -DOATGPU_MEASURE $(DEFS) -c $(CSRC)/$$f.hip -o build/$(NAME)/$$f.o || exit 1; done
+	for f in $(UNITS); do $(HIPCC) $(HIPFLAGS) -DOATGPU_MEASURE $(DEFS) -c $(CSRC)/$$f.hip -o build/$(NAME)/$$f.o || exit 1; done
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/variants/liboatgpu_$(NAME).so build/$(NAME)/*.o
 clean-variants:
 	rm -rf build/variants oat_amd/lib/liboatgpu_*.so

@@ -1,0 +1,397 @@
+// oatgpu_ctx.h -- the context of the C ABI (include/oatgpu.h) and what more than one of its units needs.  Not installed.
+//
+// No CPU fallback for any pixel work: every entry point either runs
+// the HIP kernels or fails with an error code.
+#pragma once
+#include "../../include/oatgpu.h"
+#include "oatgpu_internal.h"
+#include "hip_owned.h"
+#include "posfilt_inline.h"
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cfloat>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+#include <unistd.h>
+
+using namespace oatgpu;
+
+// Measurement switches (OATGPU_A_RESERVE / EARLY_BLOB / EARLY_MIN_PX / LONE_PLAIN / PAIR_BACK / K1_WG /
+// K1_STOP_EVENT, and OATGPU_K1_LDS in kernels_mog.hip) exist only in A/B builds made with -DOATGPU_MEASURE
+// (`make variant`); each overrides one value of a path the product takes.  The product library never reads
+// them, so nothing in the environment can change what it computes or skip work (tests/test_gpu_parity.py::
+// test_measurement_env_is_inert_in_the_product_library).
+static inline const char *measure_env(const char *name)
+{
+#ifdef OATGPU_MEASURE
+    return getenv(name);
+#else
+    (void)name;
+    return nullptr;
+#endif
+}
+
+struct ProfStep { Event e[5]; int frames = 1; };   // frames: what the K1 launch between e[0] and e[1] covered
+struct Rate { float alphaT, alpha1, prune; int fresh; };   // A: K1 begin/end; B: back-half begin, after erode, end
+
+__attribute__((visibility("hidden"))) void release_streams(int device);       // (api_context.hip)
+// the context's share of its device's streams (-1: none); declared FIRST in the context, so given back LAST, after every buffer and event
+struct StreamLease { int device = -1; ~StreamLease() { if (device >= 0) release_streams(device); } };
+
+// One scratch set of the back half: owns the 14 arrays tmp .. ready of its BlobBuffers (thr and nopark are the context's, every
+// set points at them).  Kernels take the plain BlobBuffers by value (b).
+struct Scratch {
+    BlobBuffers b{};
+    Scratch() = default;
+    Scratch(Scratch &&o) noexcept : b(std::exchange(o.b, BlobBuffers{})) {}
+    Scratch &operator=(Scratch &&o) noexcept { if (this != &o) { reset(); b = std::exchange(o.b, BlobBuffers{}); } return *this; }
+    ~Scratch() { reset(); }
+    bool alloc(const oatgpu_ctx *c, size_t planes = 0);      // planes: how many (0: one a camera stream)
+    void reset()
+    {
+        void *const own[] = {b.tmp, b.morph, b.fin, b.trans, b.carry, b.parent, b.acc, b.done, b.roots, b.nroots, b.wpre, b.rowinfo, b.lds_ok, b.ready};
+        for (void *p : own) if (p) hipFree(p);
+        b = BlobBuffers{};
+    }
+};
+
+// marker sets (oatgpu_set_markers; kernels_markers.hip): M colour windows per camera behind the one model pass.  Everything
+// below is made by oatgpu_set_markers and used by the synchronous marker step alone, on stream A.
+struct MarkerSet {
+    int n = 0;                                 // M; 0: markers off
+    int anchor = -1;                           // `posicom mean --heading-anchor`, -1: none
+    std::vector<oatgpu_marker> def;            // [M] erode / dilate / area of each marker (and its default window)
+    std::vector<RangeParams> win_host;         // [n][M] normalised colour windows, per camera and marker
+    DevMem<RangeParams> win;                   // ... on the device
+    DevMem<u64> planes;                        // [M][n][Palloc/64] k_marker_bits' output = launch_blob's src_bits
+    DevMem<u64> masks;                         // [M][3][n][Palloc/64] each marker's own tmp / morph / fin planes (the taps)
+    Scratch bb;                                // the rest of one back-half scratch set, shared by the markers (they run one after the other)
+    DevMem<ResultRec> res;                     // device: [M][n] result records, then [n] MarkerCombined
+    HostMem<ResultRec> res_host;               // page-locked mirror: one copy back a step
+    std::vector<const u64 *> tap_morph;        // [M] where marker m's mask after erode / dilate is
+};
+// the pipelined marker path (oatgpu_set_marker_pipeline): everything below is made by the switch, never inside a step.
+// A step's marker work: k_marker_bits on stream A right behind its per-pixel kernel (launch_marker_work), the back half of
+// all M x n planes and the combiner on B2 (a lone frame: on A), results into the slot's host-mapped record set.
+struct MarkerPipeline {
+    bool on = false;
+    bool table = false;                        // the one-launch back half takes this geometry and these markers (else: marker by marker)
+    int max_dil = 0;                           // largest dilation of the set: the row scan's LDS
+    DevMem<u64> planes;                        // [ring][M][n][Palloc/64] k_marker_bits' output, per ring slot
+    DevMem<u64> masks;                         // [ring][3][M][n][Palloc/64] the slot's tmp / morph / fin planes of every marker (the taps)
+    Scratch bb[2];                             // the rest of a back-half scratch set for M x n planes, one for each frame of a step
+    DevMem<BlobTab> tab;                       // [M][n] device table of the one-launch back half
+    DevMem<ResultRec> res;                     // device: [2][M][n] the step's result records, read by k_marker_combine
+    HostMem<ResultRec> rec;                    // host-mapped: [ring] sets of M x n ResultRec + n MarkerCombined, written by k_marker_combine through dev()
+    std::vector<Event> ev;                     // [ring] the marker work whose last frame sits in this slot is done
+    std::vector<int> ev_of;                    // [ring] slot -> the slot whose event covers its marker results
+    std::vector<const u64 *> tap_morph;        // [ring][M] where the MORPH tap of marker m of that slot is
+    Event bits_ev;                             // stream A: the step's k_marker_bits has finished
+    int last_slot = -1;                        // ring slot of the frame set collected last on the pipelined path; -1: the synchronous step was later
+    // a record set: M x n result records, n combined records, n filtered records (written only while a chain is configured)
+    size_t set_bytes = 0;                      // = M n sizeof(ResultRec) + n (sizeof(MarkerCombined) + sizeof(MarkerFiltered))
+};
+// the filter chain behind the combined record (oatgpu_set_marker_filters): kalman -> homography -> region in ONE launch
+// behind k_marker_combine on the same HIP stream.  Made by the setter, dropped with the marker set.
+struct MarkerFilters {
+    bool on = false;
+    DevMem<MarkerFilterParams> params;         // device: the chain's parameters and the region table
+    DevMem<KalmanState> state;                 // device: [n] the chain's own filter state, one per camera stream (not c->kal's)
+    DevMem<MarkerFiltered> out;                // device: [n] the synchronous step's filtered records
+    HostMem<MarkerFiltered> out_host;          // ... their page-locked mirror
+    std::vector<oatgpu_filtered> last;         // [sets][n] what the latest marker-result call delivered (oatgpu_marker_filtered)
+    int last_sets = 0;
+    bool append = false;                       // inside oatgpu_track_markers_sequence_dev: every collected set is kept
+};
+
+// the motion tracker (oatgpu_set_diff_tracker; kernels_diff.hip): `framefilt col -C GREY` -> `posidet diff` for every
+// camera of the context.  Everything below is made by the switch, never inside a step.  A frame's back half runs in the context's
+// scratch set `slot` (0..3) under open_sync's drain, the way detect_tail uses set 0 -- with the MORPH and FINAL planes replaced by
+// the tracker's own, so that oatgpu_read_diff_mask holds whatever the context's other calls do in between.
+struct DiffTracker {
+    static constexpr int kSlots = 4;           // frames in flight inside oatgpu_diff_sequence_dev
+    bool on = false;
+    DevMem<u64> bits;                          // [kSlots][n][Palloc/64] the front kernel's threshold words
+    DevMem<u64> masks;                         // [kSlots][2][n][Palloc/64] the slot's morph / fin planes (the taps)
+    HostMem<ResultRec> rec;                    // host-mapped: [kSlots][n] result records, written by the blob kernels through dev()
+    Event ev_front[kSlots];                    // stream A: the front launch that wrote this slot's bits has finished
+    Event ev_done[kSlots];                     // the slot's back half has finished
+    int last = -1;                             // slot of the latest diff frame (oatgpu_read_diff_mask); -1: none yet
+    std::vector<char> last_dilated;            // [n] of that frame: the stream's back half dilated (its MORPH tap is the morph plane)
+};
+
+struct oatgpu_ctx {
+    StreamLease lease;
+    oatgpu_config cfg;
+    Geom g;
+    hipStream_t stream = nullptr;   // stream A: uploads + the fused per-pixel kernel
+    static constexpr int kNB = 3;                // back-half streams B0..B2
+    static constexpr int kSets = 5;              // scratch sets of the back half: up to four for frames in flight + one for repairs
+    bool b_used[kNB] = {};          // B streams this context has launched on (the only ones it ever has to drain)
+    hipStream_t stream_b[kNB] = {}; // streams B0..B2: morphology + blob analysis, on the plain path frame t on B[t % 3]
+                                    // (B[t % 2] for host frames), overlapped with later frames' per-pixel kernels and each other
+    Event ev_k1[kNB];            // the K1 whose back half runs on B[q] has finished (its threshold bits are ready)
+    unsigned long long enq_total = 0, col_total = 0;  // pipelined frames enqueued / collected so far
+    // cache policy of K1's slot-1..4 loads (kernels_mog.hip): streaming on dense models.  Two host-mapped
+    // {live modes, samples} pairs filled alternately by k_density_probe; read one probe late, never waited for.
+    HostMem<unsigned> dens;
+    unsigned long long dens_probes = 0;
+    bool nt_loads = false;
+    // back half: frames go through row scan + k_blob_lds ONLY (kBlobSpec) while that keeps working; a frame too busy
+    // for the LDS kernel comes back marked, oatgpu_track_collect then runs the global kernels on its threshold bits
+    // (still in its ring slot) before handing the result out, and the full launch sequence is used until
+    // kSpecAfter frames in a row were taken by the LDS kernel again.
+    bool lds_spec = true;
+    int lds_streak = 0;
+    struct Slot {                   // per ring slot
+        bool spec = false;          // launched speculatively (row scan + LDS kernel alone): redone in the repair set if declined
+        bool filtered = false;      // was the position filter applied to this slot?
+        bool repair = false;        // the global kernels are redoing this frame (ready/quiesce)
+        int ev = 0;                 // the slot whose ring event covers this slot's result (itself, or the second frame of its
+                                    // launch when both back halves share a B stream)
+    };
+    std::vector<Slot> slots;        // [ring_slots]
+    int ring_slots = 0;                               // internal ring size (= ring_depth); one threshold-bit buffer per slot
+    hipStream_t stream_c = nullptr;  // H2D copies of oatgpu_track_enqueue (created on first use)
+    DevMem<uint8_t> frames_ring;     // [ring_slots][n_streams*rows*cols*channels] staging for host frames
+    std::vector<Event> copy_ev;      // [ring_slots] frames of this slot have arrived
+    std::vector<Event> copy_ev_s;        // [ring_slots][n_streams] ... and every single one of them (oatgpu_track_input_consumed_stream)
+    hipStream_t stream_c2 = nullptr;     // second copy stream of the camera-by-camera path (shared per device)
+    Event ev_c2;                         // ... and its "all my copies of this set are done"
+    std::vector<char> staged;            // [n_streams] oatgpu_track_stage: frame of the NEXT set already on its way
+    int staged_count = 0, stage_slot = -1;
+    bool per_stream_copy_ev = false;     // recorded from the first per-stream call on
+    bool last_copy_per_stream = false;   // the latest enqueue recorded them
+    int last_copy_slot = -1;         // slot of the most recent oatgpu_track_enqueue (host frames)
+    KalmanLaunch kal{};              // kal.state == nullptr: position filter off
+    DevMem<KalmanState> kal_state;   // ... the owner of kal.state
+    bool kal_on = false;
+    unsigned kal_ticket = 0;         // ticket of the next enqueued frame
+    // Early dispatch of the blob workgroup (kernels_blob.hip): the row scans of a device-frame step go down B0 / B1 by frame
+    // parity, as on the plain path; the k_blob_lds workgroups of the step's frames are submitted with them as ONE launch on
+    // B2 and wait on the device for their row scans' tickets.  Scratch sets 0 .. 3 by frame index mod 4; repairs of declined
+    // frames use set 4 on B2.
+    int early_blob = -1;             // -1: by shape -- at most THREE streams, 4 MP a step and more, where the per-pixel kernel then runs with one wave
+                                     // a workgroup (k_mog_fused, WG): 4K 18.5 k -> 19.2 k fps, result 245 -> 250 us behind its frame
+                                     // (profiles/r05g_wg64_early_blob_ab.txt).  With 256-thread workgroups the parked workgroup costs
+                                     // the per-pixel kernel 4 % (one at 4K) to 20 % (32 of them, 16 x 1080p) and several streams gain
+                                     // nothing either way (r05h): off there.  0 / 1: oatgpu_set_early_blob
+    bool stage_kernel = false;       // oatgpu_set_stage_copy(1): oatgpu_track_stage copies with a kernel reading the host frame in place
+    int k1_stop_event = -1;          // the step's "K1 done" event rides on the last K1 launch's own completion signal (no marker
+                                     // packet behind it on stream A): -1 by step size (>= 4 MP: +1..2.5 % at 4K; small steps are
+                                     // bound by the host's calls, and hipExtLaunchKernel costs more of those: one 1080p stream -3 %),
+                                     // 0 / 1 forced (measurement builds: OATGPU_K1_STOP_EVENT)
+    size_t early_min_px = 4000000;   // pixels a step from which the early order is considered (measurement builds: OATGPU_EARLY_MIN_PX)
+    int k1_wg_force = 0;             // oatgpu_set_k1_workgroup (64 | 256): the per-pixel kernel's workgroup size whatever the path
+    DevMem<unsigned> nopark;         // device word: a parked blob workgroup of this context has timed out (BlobBuffers::nopark)
+    unsigned long long early_timeouts = 0;   // frames whose parked blob workgroup gave up waiting for its row scan (kWaitTicks):
+                                     // something serialises kernel dispatches -- the context then stops parking (early_off)
+    bool early_off = false;
+    int last_k1_wg = 0;              // what the latest pipelined step used (oatgpu_last_step_shape)
+    bool last_step_early = false;
+    int last_early = -1;             // path of the previous step (-1: none yet; 0 plain, 1 early, 2 paired): a switch drains the B streams first
+    int lone_plain = 1;              // a frame launched with NOTHING else outstanding (a camera-paced caller) takes the plain order even where the early
+                                     // order is the default: no ticket kernel, no parked workgroup to release -- one frame at a time 133.5 -> 129.3 us at
+                                     // 4K, 89.6 -> 85.9 us for two 1080p streams, frame rate unchanged (profiles/r07t_lone_frame_plain_order_ab.txt) --
+                                     // and its back half goes to stream A itself (inline_back in launch_jobs: 4K 131 -> 122 us, one 1080p stream
+                                     // 66 -> 58.5 us, profiles/r07in_lone_frame_inline_ab.txt; measurement builds: OATGPU_LONE_PLAIN=0)
+    int pair_back = 1;               // two-frame steps outside the early order: ONE row-scan launch and ONE blob launch for both frames
+                                     // (measurement builds: OATGPU_PAIR_BACK=0)
+    unsigned pair_steps = 0;         // paired steps so far (their parity picks the B stream and the two scratch sets)
+    unsigned bh_ticket[kSets] = {};
+    unsigned early_frames = 0;       // frames that took the early path (their parity picks scratch set and row-scan stream)
+    Event ev_blob[kSets];            // scratch set q: its latest reader is done
+    bool ev_blob_valid[kSets] = {};
+    int last_slot = 0;               // ring slot whose threshold bits the latest back half read (oatgpu_read_mask)
+    std::string err;
+    // Deferred completion of the single-stage calls (oatgpu_set_deferred): the call returns when its INPUT has been read
+    // (the H2D copy is done), the result stays on the device until oatgpu_fetch_frame / oatgpu_fetch_position
+    bool deferred = false;
+    Event ev_h2d;
+    int defer_kind = 0;              // 0 nothing waiting, 1 a frame (defer_dev, defer_bytes), 2 a position (defer_s)
+    const uint8_t *defer_dev = nullptr;
+    size_t defer_bytes = 0;
+    int defer_s = 0;
+    bool broken = false;             // a launch of the pipelined path failed half-way: the model and its rate schedule are ahead
+                                     // of the results -- every later pipelined call is refused (oatgpu.h "Errors")
+    // Temporal fusion (kernels_mog.hip "Two frames a launch"): with fuse == 2 a pipelined enqueue only REGISTERS its
+    // frame (ring slot, counters); the kernels go out when the next frame is enqueued -- K1 once for both -- or when
+    // somebody needs the frame's result or the model (collect / ready of that very frame, every synchronous entry
+    // point, destroy), then for the one frame alone.  Results, their order and the model are those of one launch a frame.
+    struct FrameJob { const void *frames = nullptr; double lr = 0.0; hipEvent_t ready = nullptr; int slot = 0; };
+    // `posifilt homography` behind the detector / the position filter (oatgpu_set_homography): applied where the
+    // centroid is finished, on the host, in the reference's double arithmetic
+    bool homo_on = false;
+    double homo[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    int fuse = 0;                                     // 0: default -- pair where the library owns the frame's lifetime
+                                                      // (host frames, track_sequence_dev), not for oatgpu_track_enqueue_dev
+    bool in_sequence = false;                         // inside oatgpu_track_sequence_dev: its frames are all in hand
+    Event ev_in;                                      // stream A has read every frame handed over so far (input_consumed)
+    bool dev_unconsumed = false;                      // device frames were enqueued since the last input_consumed
+    bool pend_valid = false;
+    FrameJob pend;
+    unsigned long long launched_total = 0;            // frames whose kernels are out (<= enq_total)
+
+    // device memory
+    DevMem<float> state;
+    DevMem<uint8_t> nmodes;
+    DevMem<uint8_t> frames;        // staging [n][H*W*3]
+    DevMem<uint8_t> aux_a;         // [H*W*3]
+    DevMem<uint8_t> aux_b;         // [H*W*3]
+    DevMem<uint8_t> bsub_bg;       // [n][H*W*ch] framefilt bsub background (u8) and its fp32 accumulator
+    DevMem<float> bsub_f;
+    std::vector<char> bsub_have;
+    DevMem<uint8_t> diff_last;     // [n][H*W] previous GREY frame of posidet diff, allocated on first use
+    std::vector<char> diff_have;   // per camera stream
+    DevMem<u64> roi;               // [n][Palloc/64] ROI bits, allocated on first oatgpu_set_roi_mask
+    DevMem<uint32_t> ud_map1;      // [n][ud_stride] framefilt undistort maps (sx | sy << 16) and [n][ud_stride] fractions,
+    DevMem<uint16_t> ud_map2;      //   allocated on first oatgpu_set_undistort (kernels_undistort.hip)
+    size_t ud_stride = 0;
+    std::vector<char> ud_have;     // per camera stream: has a map
+    bool ud_track = false;         // oatgpu_set_track_undistort: the fused track calls remap every frame first (launch_front)
+    DevMem<uint8_t> ud_frames[2];  // [2][n][H*W*ch] the remapped frames of a step (frame i of a two-frame step in buffer i): K1
+                                   //   reads them in place of the caller's; allocated by oatgpu_set_track_undistort(1)
+    DevMem<u64> thr;               // [ring_slots][n][Palloc/64] the ring's threshold buffers (BlobBuffers::thr of every scratch set)
+    Scratch bb[kSets];             // scratch sets, all made with the context
+    const u64 *last_morph = nullptr;
+    const u64 *last_fin = nullptr;
+    HostMem<ResultRec> res;        // [ring_depth+1][n] pinned + mapped (last slot: single-stage calls); kernels store results straight to the host through dev()
+    std::vector<Event> ring_ev;
+    int ring_count = 0;
+
+    std::vector<int> nframes;      // per camera stream
+    std::vector<Rate> rates_scratch;
+
+    // profiling
+    bool prof = false;
+    int prof_every = 1;            // sample every Nth step (event records cost ~4 us of host time each)
+    unsigned long long prof_tick = 0;
+    std::vector<ProfStep> prof_steps;
+    size_t prof_used = 0;
+    oatgpu_profile prof_sum{};
+    int prof_drop_streak = 0;      // consecutive samples prof_fold took for host stalls
+    double event_pair_ms = 0.0;
+
+    // traffic audit (oatgpu_traffic_audit)
+    DevMem<unsigned long long> audit_dev;      // 8 counters
+#ifdef OATGPU_RS_TIMING
+    unsigned long long *rs_k1_end = nullptr;   // (leaked at destroy: measurement builds only)
+#endif
+    DevMem<unsigned long long> wild_sink;      // 8 counters nobody reads: launches outside div_inrange's operands (kernels_mog.hip)
+    std::vector<char> wild_model;              // [n_streams] 1: an imported model with weights no run of the kernel produces
+    bool audit_on = false;
+    long long audit_launches = 0;
+
+    MarkerSet mk; MarkerPipeline mkp; MarkerFilters mf;      // the optional features: dropping one is assignment (c->mkp = {})
+    DiffTracker df;
+};
+
+// a back half's erosion and dilation, planned and issued (plan_morph, issue_morph: api_track.hip)
+struct MorphPlan {
+    int ero, dil;               // erode / dilate sizes in effect (0: none)
+    bool ero_apart;             // the erosion is a launch of its own, not fused into the row scan
+};
+struct MorphIssued { const u64 *src; int ero; const u64 *tap; };
+
+// What a pipelined step does, decided before anything of it is launched (plan_step)
+struct StepPlan : MorphPlan {  // (the context's erode / dilate: plan_morph)
+    bool share_b, early, inline_back, paired, spec_plain;
+    int k1_wg;                  // threads a K1 workgroup
+    hipEvent_t k1_done;         // the step's "K1 done" event (nullptr: inline_back, nobody waits for it)
+};
+
+#define HIPCHK(c, expr)                                                                         \
+    do {                                                                                        \
+        hipError_t e_ = (expr);                                                                 \
+        if (e_ != hipSuccess)                                                                   \
+            return fail((c), OATGPU_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
+                        __FILE__, __LINE__);                                                    \
+    } while (0)
+
+// What the pipelined entry points refuse, always in this order; `checks` names the ones that apply to the caller.
+enum : unsigned { kRefStaging = 1, kRefState = 2, kRefRingFull = 4 };
+static constexpr int kRepairSet = oatgpu_ctx::kSets - 1, kRepairStream = oatgpu_ctx::kNB - 1;
+
+// Helpers that cross unit boundaries, by the unit that defines them.  Hidden: none of them joins the library's dynamic symbols.
+#pragma GCC visibility push(hidden)
+// api_context.hip
+extern thread_local std::string g_last_error;
+int fail(oatgpu_ctx *c, int code, const char *fmt, ...);
+hipError_t drain_b(oatgpu_ctx *c);
+int check_detector(oatgpu_ctx *c, const oatgpu_marker &k, int blur = 0);
+hipStream_t acquire_copy_stream(int device);
+hipStream_t acquire_copy_stream2(int device);
+hipError_t make_events(std::vector<Event> &table, size_t count, unsigned flags);
+int quiesce(oatgpu_ctx *c);
+int open_sync(oatgpu_ctx *c);
+int check_stream_ix(oatgpu_ctx *c, int s);
+// api_stages.hip
+int read_plane(oatgpu_ctx *c, const u64 *plane, uint8_t *out);
+// api_track.hip
+Rate mog_begin(oatgpu_ctx *c, int s, double learningRate);
+MogLaunch mog_launch_base(oatgpu_ctx *c, const uint8_t *frames, const Rate &r);
+MogLaunchOpts mog_launch_opts(oatgpu_ctx *c, int s0, int s1, int wg);
+void to_position(const ResultRec &r, oatgpu_position *o);
+MorphPlan plan_morph(const Geom &g, int erode, int dilate);
+MorphIssued issue_morph(const Geom &g, const MorphPlan &m, const BlobBuffers &bb, const u64 *thr, int s0, int n, hipStream_t st);
+int back_half(oatgpu_ctx *c, BlobBuffers &bb, const u64 *thr, int s0, int n, int slot, hipStream_t st,
+              hipEvent_t ev_mid, int erode_k = -1, int dilate_k = -1, int mode = kBlobFull);
+int flush_pending(oatgpu_ctx *c);
+int repair_outstanding(oatgpu_ctx *c);
+void keep_filtered(oatgpu_ctx *c, const MarkerFiltered *f);
+int upload_frames(oatgpu_ctx *c, const uint8_t *const *frames_host);
+// api_markers.hip
+bool own_window_is_nonzero(const oatgpu_config &k);
+int launch_marker_work(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, const StepPlan &plan);
+// api_measure.hip
+void prof_fold(oatgpu_ctx *c);
+#pragma GCC visibility pop
+
+// the ten values of a detector: an oatgpu_marker holds a marker's, the context's own come out of its config
+static inline oatgpu_marker detector_of(const oatgpu_config &k)
+{
+    return {k.h_lo, k.h_hi, k.s_lo, k.s_hi, k.v_lo, k.v_hi, k.erode, k.dilate, k.min_area, k.max_area};
+}
+
+// cv::inRange's scalar-bound normalisation for 8U sources
+static inline void norm_range(int lo, int hi, int &l, int &h)
+{
+    if (lo > hi || lo > 255 || hi < 0) { l = 1; h = 0; return; }
+    l = lo < 0 ? 0 : lo;
+    h = hi > 255 ? 255 : hi;
+}
+static inline RangeParams range_of(const oatgpu_marker &k)
+{
+    RangeParams r;
+    norm_range(k.h_lo, k.h_hi, r.lo[0], r.hi[0]);
+    norm_range(k.s_lo, k.s_hi, r.lo[1], r.hi[1]);
+    norm_range(k.v_lo, k.v_hi, r.lo[2], r.hi[2]);
+    return r;
+}
+
+// ring slot of the next frame to be enqueued / collected
+static inline int enq_slot(const oatgpu_ctx *c) { return (int)(c->enq_total % (unsigned long long)c->ring_slots); }
+static inline int col_slot(const oatgpu_ctx *c) { return (int)(c->col_total % (unsigned long long)c->ring_slots); }
+
+static inline u64 *thr_buf(oatgpu_ctx *c, int parity)
+{
+    return c->thr + (size_t)parity * c->cfg.n_streams * (c->g.Palloc >> 6);
+}
+
+// B streams of the plain order for a frame.  Host frames arrive over the copy stream: use one B stream fewer then: the copy
+// stream sits on the last B stream's hardware queue (see acquire_streams)
+static inline int plain_b_streams(const oatgpu_ctx::FrameJob &f) { return f.ready ? 2 : oatgpu_ctx::kNB; }
+
+static inline void mark_speculative(oatgpu_ctx *c, int slot)
+{
+    c->slots[slot].spec = true;
+    c->slots[slot].filtered = false;
+}

@@ -1,6 +1,6 @@
 // posfilt_inline.h -- the arithmetic of `posifilt kalman` and `posifilt homography`, ONE definition for every user:
 // k_kalman (kernels_kalman.hip, the foreground result), k_marker_filters (kernels_markers.hip, the combined record of a marker
-// set) and the host epilogue of oatgpu_api.hip (the homography of a plain track call).
+// set) and the host epilogue of api_track.hip (the homography of a plain track call).
 //
 // Reference: oat::KalmanFilter2D::filter / initializeFilter / initializeStaticMatracies
 // (src/positionfilter/KalmanFilter2D.cpp:95-210) over cv::KalmanFilter(4, 2, 0, CV_64F) (OpenCV 3.1

@@ -1,7 +1,7 @@
 """Random, legal call sequences of the tracker's host API, an oracle-backed model of what every call must return, and the
 driver that runs one against the other (TEST INFRASTRUCTURE, as tests/mog_matrix.py and tests/blob_load.py are).
 
-What is under test is the machinery BETWEEN the kernels in oat_amd/csrc/oatgpu_api.hip: launch orders, scratch sets by
+What is under test is the machinery BETWEEN the kernels in oat_amd/csrc/api_track.hip and api_context.hip: launch orders, scratch sets by
 frame parity, frames that are only registered under oatgpu_set_fusion(2), speculation and repair, staging camera by
 camera, the quiesce() in front of every synchronous call, HIP streams shared by the contexts of a process.
 

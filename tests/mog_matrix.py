@@ -5,7 +5,7 @@ and how the pipelined track path is made to launch it, restated in Python.  No G
     oatgpu_set_fusion, oatgpu_set_k1_workgroup, the rate schedule, the kind of frames and the traffic audit;
   * the launcher's choice, restated: launch_mog_fused / launch_mog_pick / launch_mog_ch / rate_in_range (kernels_mog.hip),
     the workgroup rule of plan_step, the pairing rule of launch_front, frozen_ok of mog_launch_opts, the density switch and
-    the probe schedule of launch_front, what k_density_probe counts (oatgpu_api.hip);
+    the probe schedule of launch_front, what k_density_probe counts (api_track.hip);
   * frame generators for the regimes: sparse (SyntheticStream discs), dense (five well separated levels a pixel, own
     phase: five live modes), mixed (sparse with a tenth of the pixels cycling through six levels: full mixtures that keep
     replacing their last mode, while the mean stays well below the density switch) and shadows (a moving patch at 0.7 x
@@ -98,7 +98,7 @@ INSTANTIATIONS = {sc.inst for sc in SCENARIOS}
 # ------------------------------------------------------------------------------------ the launcher, restated ---
 
 def mog_begin(nframes, lr, history=500, ct=0.05):
-    """BackgroundSubtractorMOG2Impl::apply's prologue (oatgpu_api.hip mog_begin): -> (fresh, nframes after, alphaT, prune)."""
+    """BackgroundSubtractorMOG2Impl::apply's prologue (api_track.hip mog_begin): -> (fresh, nframes after, alphaT, prune)."""
     fresh = nframes == 0 or lr >= 1
     nf = (0 if fresh else nframes) + 1
     lim = 2 * nf if 2 * nf < history else history

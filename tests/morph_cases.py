@@ -2,7 +2,7 @@
 oat_amd/csrc/kernels_blob.hip), shared by tests/test_morph_cases_cpu.py and tests/test_morph_routes_gpu.py.
 
 The kernel's constants are held here once; the CPU file reads them out of the sources and fails when the two disagree.
-rowscan_lds_bytes() and ero_apart() restate the sources' formulas (kernels_blob.hip, plan_morph in oatgpu_api.hip), and
+rowscan_lds_bytes() and ero_apart() restate the sources' formulas (kernels_blob.hip, plan_morph in api_track.hip), and
 every geometry "on an edge" is DERIVED from them:
 
   mechanism                                     one side                          other side
@@ -50,7 +50,7 @@ def rowscan_lds_bytes(H, W, dil):
 
 
 def ero_apart(H, W, ero, dil):
-    """oatgpu_api.hip, plan_morph(): the erosion is a k_morph launch of its own (sizes of 0 and 1 do nothing)."""
+    """api_track.hip, plan_morph(): the erosion is a k_morph launch of its own (sizes of 0 and 1 do nothing)."""
     ero, dil = (ero if ero > 1 else 0), (dil if dil > 1 else 0)
     return bool(ero) and rowscan_lds_bytes(H, W, dil) > ROWSCAN_LDS_MAX
 

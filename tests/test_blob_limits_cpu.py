@@ -47,7 +47,7 @@ def test_kernel_constants_are_the_edge_tables():
 def test_lds_geometry_rule_is_stated_alike_in_both_places():
     rule = re.compile(r"const bool (lds_able|lds_geom) = ([^;]*);")
     found = dict(rule.findall(_src("kernels_blob.hip")))
-    found.update(rule.findall(_src("oatgpu_api.hip")))
+    found.update(rule.findall(_src("api_track.hip")))
     assert set(found) == {"lds_able", "lds_geom"}
     a, g = (" ".join(found[k].split()) for k in ("lds_able", "lds_geom"))
     assert a == g, (a, g)

@@ -130,7 +130,7 @@ def test_restated_launcher_corner_cases():
 # ------------------------------------------------------------------------------- the rules, read from the sources ---
 
 def test_density_switch_and_probe_schedule_are_the_sources():
-    api = _flat(_function(_src("oatgpu_api.hip"), "static int launch_front("))
+    api = _flat(_function(_src("api_track.hip"), "static int launch_front("))
     assert "if ((t >= 8 && t < 64 && (t & (t - 1)) == 0) || (t >= 64 && (t & 63) == 0)) {" in api
     assert f"if (c->dens_probes && prev[1]) c->nt_loads = {M.DENSE_DEN}ull * prev[0] >= {M.DENSE_NUM}ull * prev[1];" in api
     assert "const unsigned *prev = c->dens.host() + 2 * (ds ^ 1);" in api           # the previous probe's numbers
@@ -150,7 +150,7 @@ def test_density_switch_and_probe_schedule_are_the_sources():
 
 
 def test_workgroup_pairing_and_frozen_rules_are_the_sources():
-    api = _flat(_src("oatgpu_api.hip"))
+    api = _flat(_src("api_track.hip"))
     assert ("p.k1_wg = c->k1_wg_force ? c->k1_wg_force : (p.early || c->nt_loads || (lone && c->lone_plain && early_wanted "
             "&& step_px >= c->early_min_px)) ? 64 : 256;") in api
     assert ("const bool pair = nj == 2 && !rates[s0].fresh && !rates[(size_t)n + s0].fresh && "

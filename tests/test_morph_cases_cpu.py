@@ -29,7 +29,7 @@ def _flat(s):
 # ------------------------------------------------------------------------------------- the sources' constants ---
 
 def test_constants_are_the_kernels():
-    blob, api, hdr = _flat(_src("kernels_blob.hip")), _flat(_src("oatgpu_api.hip")), _flat(_src("oatgpu_internal.h"))
+    blob, api, hdr = _flat(_src("kernels_blob.hip")), _flat(_src("api_context.hip")), _flat(_src("oatgpu_internal.h"))
     assert re.search(r"constexpr int kRsWaves = \d+, kRsRows = (\d+);", blob).group(1) == str(M.RS_ROWS)
     m = re.search(r"constexpr size_t kRowscanLdsMax = (\d+) \* (\d+);", hdr)
     assert int(m.group(1)) * int(m.group(2)) == M.ROWSCAN_LDS_MAX
@@ -44,7 +44,8 @@ def test_constants_are_the_kernels():
 
 
 def test_route_predicates_are_the_sources():
-    blob, api = _flat(_src("kernels_blob.hip")), _flat(_src("oatgpu_api.hip"))
+    blob, api = _flat(_src("kernels_blob.hip")), _flat(_src("api_track.hip"))
+    markers, ctx = _flat(_src("api_markers.hip")), _flat(_src("oatgpu_ctx.h"))
     # rowscan_lds_bytes(): (kRsRows + max(dil, 1) - 1) rows of g.words 8-byte words
     assert "return (size_t)(kRsRows + (dil_k > 1 ? dil_k : 1) - 1) * g.words * sizeof(u64);" in blob
     assert M.rowscan_lds_bytes(12, 129, 0) == M.rowscan_lds_bytes(12, 129, 1) == 4 * 3 * 8
@@ -55,11 +56,11 @@ def test_route_predicates_are_the_sources():
     assert not M.ero_apart(12, 1 << 14, 1, 63) and M.ero_apart(12, 1 << 14, 2, 63)
     # the fused form is taken from an erosion of 2 on; the marker table and the pair need the LDS kernel's geometry
     assert "if (ero_k > 1) hipLaunchKernelGGL(k_rowscan<true>" in blob
-    assert "mkp.table = g.H > 2 && g.H <= 16383 && g.W <= 16383 && rowscan_lds_bytes(g, max_dil) <= kRowscanLdsMax;" in api
+    assert "mkp.table = g.H > 2 && g.H <= 16383 && g.W <= 16383 && rowscan_lds_bytes(g, max_dil) <= kRowscanLdsMax;" in markers
     assert "const bool lds_geom = g.H > 2 && g.H <= 16383 && g.W <= 16383;" in api
     # a two-frame step whose erosion is apart is not paired (no public call tells: the GPU file runs both sides alike)
     assert "p.paired = nj == 2 && !p.early && c->pair_back && c->lds_spec && !c->kal_on && lds_geom && !p.ero_apart;" in api
-    assert re.search(r"size_t early_min_px = \d+;", api)
+    assert re.search(r"size_t early_min_px = \d+;", ctx)
     assert not M.lds_able(2, 64) and M.lds_able(3, 64)
     # the row group's LDS rows and the shortcut's source rows, as group_rows() restates them
     assert "const int r0 = grp * ROWS - dk / 2;" in blob and "const int dk = dil_k > 1 ? dil_k : 1;" in blob

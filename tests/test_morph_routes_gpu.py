@@ -249,7 +249,7 @@ def test_fused_tracker_synchronous_and_pipelined(A, pset, ch):
 # ------------------------------------------------------------------------------------------------- early order ---
 
 def _early_min_px():
-    with open(os.path.join(ROOT, "oat_amd", "csrc", "oatgpu_api.hip")) as f:
+    with open(os.path.join(ROOT, "oat_amd", "csrc", "oatgpu_ctx.h")) as f:
         return int(re.search(r"size_t early_min_px = (\d+);", f.read()).group(1))
 
 

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""The library's stream self-check (oatgpu_api.hip settle_streams) against a process that used the device BEFORE its first context:
+"""The library's stream self-check (api_context.hip settle_streams) against a process that used the device BEFORE its first context:
 
     OATGPU_SETTLE_STREAMS=0|1 OATGPU_MEASURE_PY=1 OATGPU_LIB=build/variants/liboatgpu_meas.so python tools/stream_settle_probe.py clean|readback WORKLOAD
 
 readback: `torch.zeros(8, device=...).sum().item()` first -- what cost one 1080p stream 20 % and a 640 x 480 stream 40 % in r07b.
 The self-check itself was measured (profiles/r07v_stream_settle.txt: never anything to replace) and removed: apply
-tools/patches/r07_stream_self_check.diff and `make variant NAME=meas` to run this again; without it the last column reads n/a."""
+tools/patches/r07_stream_self_check.diff (to the tree before the C ABI unit was split by feature) and `make variant NAME=meas` to run this again; without it the last column reads n/a."""
 import os
 import sys
 
