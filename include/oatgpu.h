@@ -45,7 +45,9 @@ extern "C" {
  * oatgpu_track_collect_markers, oatgpu_track_markers_sequence_dev; the filter chain behind the combined record --
  * oatgpu_set_marker_filters, oatgpu_marker_filtered, with the structs oatgpu_region, oatgpu_marker_filters, oatgpu_filtered;
  * the motion tracker -- oatgpu_set_diff_tracker, oatgpu_diff_reset, oatgpu_diff_batch_dev, oatgpu_diff_batch,
- * oatgpu_diff_sequence_dev, oatgpu_read_diff_mask. */
+ * oatgpu_diff_sequence_dev, oatgpu_read_diff_mask; the subtraction tracker -- oatgpu_set_bsub_tracker, oatgpu_bsub_reset,
+ * oatgpu_bsub_track_batch_dev, oatgpu_bsub_track_batch, oatgpu_bsub_track_sequence_dev, oatgpu_bsub_get_state,
+ * oatgpu_read_bsub_mask. */
 
 enum {
     OATGPU_OK = 0,
@@ -549,6 +551,56 @@ int oatgpu_diff_sequence_dev(oatgpu_ctx *ctx, const void *const *frames_dev, int
 /* oatgpu_read_mask for the latest diff frame (of a sequence: its last): which = OATGPU_TAP_THRESHOLD (|g - last| > thr),
  * _MORPH (after the blur-as-dilation), _FINAL; out rows*cols bytes {0, 255}.  OATGPU_E_INVALID before the first diff step. */
 int oatgpu_read_diff_mask(oatgpu_ctx *ctx, int32_t stream_ix, int32_t which, uint8_t *out);
+
+/* ---- subtraction tracker: framefilt bsub -> col -C HSV -> posidet hsv for EVERY stream of the context, one front launch a step ----
+ *
+ * Frames are cfg.channels wide: 3 = the chain `framefilt bsub -> framefilt col -C HSV -> posidet hsv` (BackgroundSubtractor.cpp:
+ * 79-100, ColorConvert.cpp, HSVDetector.cpp:142-173), 1 = `framefilt bsub -> posidet thresh` (SimpleThreshold.cpp:114-134).  Where
+ * a stream has a ROI (oatgpu_set_roi_mask) the frame is masked first (`framefilt mask` in front of bsub, FrameMasker.cpp:71-75):
+ * on a first frame the masked pixels of the background are 0.  alpha is bsub's adaptation coefficient (-a): 0 = the background
+ * stays what the stream's first frame (or oatgpu_bsub_set_background) made it; > 0 = cv::accumulateWeighted in fp32 on every frame,
+ * the first included.  The window is the config's h/s/v (GREY: h_lo / h_hi) on the DIFFERENCE image, then the config's erode,
+ * dilate and min_area / max_area.
+ *
+ * The background is oatgpu_bsub_filter's STATE: the u8 image, the fp32 accumulator and the first-frame flag of a stream are
+ * shared, a stream advanced by one form continues in the other, oatgpu_bsub_set_background serves both.
+ *
+ * oatgpu_set_bsub_tracker(1) drains outstanding work and allocates everything a step needs (an out-of-memory is reported here,
+ * as OATGPU_E_NOMEM, never in the middle of a step): the background planes if oatgpu_bsub_filter has not made them (5 bytes a
+ * pixel, channel and stream), four sets of threshold words and of the tracker's own TMP / MORPH / FINAL planes (4 bits a pixel and
+ * stream a set), four host-mapped result sets and eight events.  The rest of a back half's scratch is the context's own sets 0..3,
+ * used only while nothing else of the context is in flight.  0 frees it all but the background.
+ *
+ * Every call is synchronous: it returns with none of its work in flight and leaves the result ring, the pipelined path's
+ * counters and what oatgpu_read_mask shows untouched.  OATGPU_E_INVALID, with a message naming the cause and before anything is
+ * read or has moved: the tracker is off; results are outstanding (oatgpu_track_enqueue*) or a set is partly staged;
+ * oatgpu_set_kalman, oatgpu_set_homography or oatgpu_set_track_undistort is on; alpha outside [0, 1]; alpha > 0 while a stream's
+ * background came from a file (the message names the stream; BackgroundSubtractor.cpp:63-71 makes no accumulator for it); a null
+ * argument; n != n_streams; n_frames < 0.  n_frames == 0 succeeds and does nothing. */
+int oatgpu_set_bsub_tracker(oatgpu_ctx *ctx, int32_t on);
+/* Forget the background of one stream (-1: of every stream): its next frame is a first frame again (setBackgroundImage,
+ * BackgroundSubtractor.cpp:79-85).  Also for oatgpu_bsub_filter. */
+int oatgpu_bsub_reset(oatgpu_ctx *ctx, int32_t stream_ix);
+/* One step (BackgroundSubtractor.cpp:87-100 -> HSVDetector.cpp:142-173 / SimpleThreshold.cpp:114-134): frames_dev =
+ * n_streams*rows*cols*channels bytes, stream-major (as oatgpu_track_batch_dev); out[n_streams].  Frames and rows of any alignment
+ * are taken; 4-byte aligned frames of a width divisible by 4 take the 4-pixels-a-lane kernel. */
+int oatgpu_bsub_track_batch_dev(oatgpu_ctx *ctx, const void *frames_dev, double alpha, oatgpu_position *out);
+/* The same on host frames (BackgroundSubtractor.cpp:87-100 and the detectors as above): frames_host[i] -> rows*cols*channels bytes
+ * of stream i. */
+int oatgpu_bsub_track_batch(oatgpu_ctx *ctx, const uint8_t *const *frames_host, int32_t n, double alpha, oatgpu_position *out);
+/* A recorded sequence in one call (n_frames runs of BackgroundSubtractor.cpp:87-100 and the detector): frames_dev[t] = frame set
+ * t, out[n_frames][n_streams].  Up to four frames are in flight, two consecutive frames share a front launch wherever a next
+ * frame exists; results, masks and the background are those of n_frames calls of oatgpu_bsub_track_batch_dev. */
+int oatgpu_bsub_track_sequence_dev(oatgpu_ctx *ctx, const void *const *frames_dev, int32_t n_frames, double alpha,
+                                   oatgpu_position *out);
+/* The background of one stream as it stands (background_img_ and its fp32 twin, BackgroundSubtractor.cpp:79-100): bg
+ * rows*cols*channels bytes, acc as many floats; either may be NULL.  OATGPU_E_INVALID while the stream has no background, and for
+ * acc when the background came from a file.  Synchronises.  Also for oatgpu_bsub_filter. */
+int oatgpu_bsub_get_state(oatgpu_ctx *ctx, int32_t stream_ix, uint8_t *bg, float *acc);
+/* oatgpu_read_mask for the latest subtraction-tracker frame (of a sequence: its last; HSVDetector.cpp:146-158's threshold_frame_):
+ * which = OATGPU_TAP_THRESHOLD (the window on the difference), _MORPH (after erode / dilate), _FINAL; out rows*cols bytes {0, 255}.
+ * OATGPU_E_INVALID before the first step. */
+int oatgpu_read_bsub_mask(oatgpu_ctx *ctx, int32_t stream_ix, int32_t which, uint8_t *out);
 
 /* ---- fused hot path: mog + setTo + BGR2HSV + inRange + erode + dilate + blob ---- */
 

@@ -9,9 +9,9 @@ by the tests and the benchmark; there is no CPU fallback -- importing
 """
 from .ffi import OatGpuError, lib_path  # noqa: F401
 from .components import (  # noqa: F401
-    BackgroundSubtractorMOG, BackgroundSubtractor, Threshold, ColorConvert, HSVDetector, SimpleThreshold, DifferenceDetector, HotPath, MotionTracker, Position2D, Combined,
+    BackgroundSubtractorMOG, BackgroundSubtractor, Threshold, ColorConvert, HSVDetector, SimpleThreshold, DifferenceDetector, HotPath, MotionTracker, SubtractionTracker, Position2D, Combined,
     Undistorter, undistort_map,
 )
 
-__all__ = ["BackgroundSubtractorMOG", "BackgroundSubtractor", "Threshold", "ColorConvert", "HSVDetector", "SimpleThreshold", "DifferenceDetector", "HotPath", "MotionTracker",
+__all__ = ["BackgroundSubtractorMOG", "BackgroundSubtractor", "Threshold", "ColorConvert", "HSVDetector", "SimpleThreshold", "DifferenceDetector", "HotPath", "MotionTracker", "SubtractionTracker",
            "Undistorter", "undistort_map", "Position2D", "Combined", "OatGpuError", "lib_path"]

@@ -432,6 +432,72 @@ class MotionTracker(_Detector):
         return out
 
 
+class SubtractionTracker(_Detector):
+    """The batched subtraction tracker: `framefilt bsub` -> `framefilt col -C HSV` -> `posidet hsv` for N camera streams, one front
+    launch a step (oatgpu_set_bsub_tracker).  channels = 3: BGR frames (rows, cols, 3) and the h / s / v window on the difference
+    image; 1: GREY frames (rows, cols), `framefilt bsub` -> `posidet thresh` with `thresh`.  alpha is bsub's -a (0: the background
+    stays the first frame); erode / dilate / area as HSVDetector.cpp:49-75.  A ROI (set_roi_mask) masks the frame first."""
+
+    def __init__(self, rows, cols, n_streams=1, channels=3, alpha=0.0, h_thresh=(0, 256), s_thresh=(0, 256), v_thresh=(0, 256),
+                 thresh=None, erode=0, dilate=10, area=(0.0, DBL_MAX), device=0, **kw):
+        if thresh is not None:
+            h_thresh = thresh
+        super().__init__(rows, cols, n_streams=n_streams, channels=channels, h_lo=h_thresh[0], h_hi=h_thresh[1], s_lo=s_thresh[0],
+                         s_hi=s_thresh[1], v_lo=v_thresh[0], v_hi=v_thresh[1], erode=erode, dilate=dilate, min_area=area[0],
+                         max_area=area[1], device=device, **kw)
+        self.alpha_ = float(alpha)
+        self._pos = (ffi.Position * n_streams)()
+        self._chk(self.lib.oatgpu_set_bsub_tracker(self.ctx, 1))
+
+    def _alpha(self, alpha):
+        return float(getattr(self, "alpha_", 0.0) if alpha is None else alpha)
+
+    def track(self, frames, alpha=None):
+        """frames: sequence of n_streams host arrays -> one Position2D per stream (oatgpu_bsub_track_batch)."""
+        fs = [_frame(f, self.frame_shape) for f in frames]
+        ptrs = (ffi._u8p * max(len(fs), 1))(*[ffi.u8(f) for f in fs])
+        pos = (ffi.Position * self.n_streams)()
+        self._chk(self.lib.oatgpu_bsub_track_batch(self.ctx, ptrs, len(fs), SubtractionTracker._alpha(self, alpha), pos))
+        return [Position2D.from_c(p) for p in pos]
+
+    def track_dev(self, dev_ptr, alpha=None):
+        """dev_ptr: device address of n_streams*rows*cols*channels bytes, stream-major (oatgpu_bsub_track_batch_dev)."""
+        pos = (ffi.Position * self.n_streams)()
+        self._chk(self.lib.oatgpu_bsub_track_batch_dev(self.ctx, C.c_void_p(dev_ptr), SubtractionTracker._alpha(self, alpha), pos))
+        return [Position2D.from_c(p) for p in pos]
+
+    def track_sequence_dev(self, dev_ptrs, alpha=None):
+        """A recorded sequence in one call (oatgpu_bsub_track_sequence_dev): dev_ptrs[t] = device address of frame set t; returns
+        one list of Position2D per frame set."""
+        T, n = len(dev_ptrs), self.n_streams
+        arr = (C.c_void_p * max(T, 1))(*dev_ptrs)
+        out = (ffi.Position * max(T * n, 1))()
+        self._chk(self.lib.oatgpu_bsub_track_sequence_dev(self.ctx, arr, T, SubtractionTracker._alpha(self, alpha), out))
+        return [[Position2D.from_c(out[t * n + s]) for s in range(n)] for t in range(T)]
+
+    def reset(self, stream=None):
+        """Forget the background of one stream (None: of all): its next frame is a first frame again (oatgpu_bsub_reset)."""
+        self._chk(self.lib.oatgpu_bsub_reset(self.ctx, -1 if stream is None else int(stream)))
+
+    def set_background(self, image, stream=0):
+        """`framefilt bsub -f FILE`: the background of one stream from an image; it cannot adapt (oatgpu_bsub_set_background)."""
+        im = _frame(image, self.frame_shape)
+        self._chk(self.lib.oatgpu_bsub_set_background(self.ctx, int(stream), ffi.u8(im)))
+
+    def state(self, stream=0, acc=True):
+        """(background uint8, accumulator float32 or None) of one stream as it stands (oatgpu_bsub_get_state)."""
+        bg = np.empty(self.frame_shape, np.uint8)
+        f = np.empty(self.frame_shape, np.float32) if acc else None
+        self._chk(self.lib.oatgpu_bsub_get_state(self.ctx, int(stream), ffi.u8(bg), ffi.f32(f) if acc else None))
+        return bg, f
+
+    def read_mask(self, which=ffi.TAP_MORPH, stream=0):
+        """A plane of the latest subtraction-tracker frame (oatgpu_read_bsub_mask)."""
+        out = np.empty((self.rows, self.cols), np.uint8)
+        self._chk(self.lib.oatgpu_read_bsub_mask(self.ctx, int(stream), which, ffi.u8(out)))
+        return out
+
+
 def _merge(position, p):
     """siftContours only writes x/y when a blob is found (DetectorFunc.cpp:46,58-60)."""
     new = Position2D.from_c(p)

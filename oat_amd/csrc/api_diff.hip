@@ -160,53 +160,24 @@ extern "C" int oatgpu_diff_sequence_dev(oatgpu_ctx *c, const void *const *frames
     if (n_frames == 0) return OATGPU_OK;
     rc = open_sync(c);
     if (rc) return rc;
-    constexpr int K = DiffTracker::kSlots;
+    static_assert(DiffTracker::kSlots == kSeqSlots, "the sequence loop's slots are the tracker's");
     const int n = c->cfg.n_streams;
-    int got = 0;
-    auto collect_one = [&]() -> int {
-        const int q = got % K;
-        HIPCHK(c, hipEventSynchronize(c->df.ev_done[q]));
-        diff_hand_out(c, q, out + (size_t)got * n);
-        ++got;
-        return OATGPU_OK;
-    };
-    auto back_on_b = [&](int t, const char *have, hipEvent_t front) -> int {
-        const int q = t % K, b = t % oatgpu_ctx::kNB;
-        hipStream_t B = c->stream_b[b];
-        c->b_used[b] = true;
-        HIPCHK(c, hipStreamWaitEvent(B, front, 0));
-        const int r = diff_back(c, q, have, B);
-        if (r) return r;
-        HIPCHK(c, hipEventRecord(c->df.ev_done[q], B));
-        return OATGPU_OK;
-    };
     const std::vector<char> all(c->diff_have.size(), 1);
-    int t = 0;
-    while (t < n_frames && !rc) {
-        const bool every = std::all_of(c->diff_have.begin(), c->diff_have.end(), [](char h) { return h != 0; });
-        const int nf = every && t + 1 < n_frames ? 2 : 1;
-        while (!rc && t + nf - got > K) rc = collect_one();
-        if (rc) break;
-        const std::vector<char> have = c->diff_have;
-        const int q = t % K;
-        rc = diff_front(c, frames_dev[t], nf == 2 ? frames_dev[t + 1] : nullptr, q, (t + 1) % K);
-        if (rc) break;
-        c->diff_have.assign(have.size(), 1);
-        hipError_t e = hipEventRecord(c->df.ev_front[q], c->stream);
-        if (e != hipSuccess) { rc = fail(c, OATGPU_E_HIP, "hipEventRecord failed: %s", hipGetErrorString(e)); break; }
-        rc = back_on_b(t, have.data(), c->df.ev_front[q]);
-        if (!rc && nf == 2) rc = back_on_b(t + 1, all.data(), c->df.ev_front[q]);
-        if (rc) break;
-        t += nf;
-    }
-    if (rc) {                              // nothing of this call stays in flight
-        (void)hipStreamSynchronize(c->stream);
-        (void)drain_b(c);
-        return rc;
-    }
-    while (!rc && got < n_frames) rc = collect_one();
-    if (rc) { (void)hipStreamSynchronize(c->stream); (void)drain_b(c); }
-    return rc;
+    std::vector<char> have;                // the state the launch's first frame met
+    return run_sequence_in_flight(
+        c, n_frames, c->df.ev_front, c->df.ev_done,
+        [&](int t) {
+            const bool every = std::all_of(c->diff_have.begin(), c->diff_have.end(), [](char h) { return h != 0; });
+            return every && t + 1 < n_frames ? 2 : 1;
+        },
+        [&](int t, int nf, int q, int q2) {
+            have = c->diff_have;
+            const int r = diff_front(c, frames_dev[t], nf == 2 ? frames_dev[t + 1] : nullptr, q, q2);
+            if (!r) c->diff_have.assign(have.size(), 1);
+            return r;
+        },
+        [&](int q, int i, hipStream_t B) { return diff_back(c, q, i ? all.data() : have.data(), B); },
+        [&](int q, int frame) { diff_hand_out(c, q, out + (size_t)frame * n); });
 }
 
 extern "C" int oatgpu_read_diff_mask(oatgpu_ctx *c, int32_t s, int32_t which, uint8_t *out)

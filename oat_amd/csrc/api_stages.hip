@@ -135,7 +135,7 @@ extern "C" int oatgpu_mog_filter(oatgpu_ctx *c, int32_t s, const uint8_t *bgr_in
 }
 
 // framefilt bsub's background and its fp32 accumulator, made on first use
-static int ensure_bsub(oatgpu_ctx *c, size_t nb)
+int ensure_bsub(oatgpu_ctx *c, size_t nb)
 {
     if (c->bsub_bg) return OATGPU_OK;
     DevMem<uint8_t> bg; DevMem<float> f;

@@ -1,0 +1,224 @@
+// kernels_bsubtrack.hip -- the front end of the subtraction tracker (`framefilt bsub` -> `framefilt col -C HSV` -> `posidet hsv`
+// for BGR frames, `framefilt bsub` -> `posidet thresh` for GREY ones) for every camera stream of a context in one
+// launch (grid y = stream).
+//
+// Per pixel and channel, in k_bsub's order (BackgroundSubtractor.cpp:79-100): x = the frame byte, 0 where the stream's ROI bit is
+// 0 (framefilt mask in front of bsub); on a stream's first frame acc = (float)x, bg = x; with LEARN acc = x * a + acc * b in
+// separate roundings (cv::accumulateWeighted, the unit is built with -ffp-contract=off) and bg = saturate(round-half-even(acc));
+// d = x > bg ? x - bg : 0.  Then bit = inRange(hsv(d_b, d_g, d_r)) (hsv_inline.h) or lo <= d <= hi (GREY).
+//   LEARN false: acc is neither read nor written and bg only read -- except on a first frame, which makes both.
+//   LEARN true:  bg is not read (it is a function of acc) but written: the state is oatgpu_bsub_filter's.
+//   PAIR:        the stream's next frame in the same launch; acc and bg stay in registers between the two and are stored once.
+//
+// Two instantiations of the lane mapping (kernels_diff.hip's):
+//   wide   (W % 4 == 0, frames and bg 4-byte, acc 16-byte aligned): a lane owns 4 consecutive pixels of one row -- CH dwords of
+//          the frame, CH dwords of bg, CH 16-byte accesses of acc (a wave's 64 * 16 * CH bytes of acc are one contiguous run).
+//          The accumulator leaves in 128-bit stores: each is followed by `s_nop 1` with its data registers live.
+//   narrow (everything else): one pixel a lane with byte and dword accesses, the ballot is the word.
+// Both write EVERY word of Palloc / 64 (zero bits for x >= W and p >= P): the row scan reads them.
+#include "oatgpu_internal.h"
+#include "hsv_inline.h"
+#include "maskwords_inline.h"
+
+namespace oatgpu {
+
+namespace {
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+struct BsubArgs {
+    const uint8_t *frames, *frames2;     // [n][H*W*CH] stream-major; frames2: the second frame of a paired launch
+    uint8_t *bg;                         // [n][H*W*CH]
+    float *acc;                          // [n][H*W*CH]
+    u64 *bits, *bits2;                   // [n][Palloc/64]
+    const u64 *roi;                      // [n][Palloc/64]
+    u64 first;                           // bit (stream - first_stream): this is the stream's first frame
+    RangeParams rp;
+    float a, b;                          // accW_: a = (float)alpha, b = 1 - a
+    int first_stream;
+};
+
+// one channel of one pixel: the state moves on, the saturated difference comes back
+template <bool LEARN> __device__ __forceinline__ int bsub_elem(int x, bool first, int &bg, float &acc, float a, float b)
+{
+    if (first) { acc = (float)x; bg = x; }
+    if (LEARN) {
+        acc = x * a + acc * b;
+        bg = min(255, max(0, __float2int_rn(acc)));
+    }
+    return x > bg ? x - bg : 0;
+}
+
+template <int CH> __device__ __forceinline__ bool window(const int (&d)[CH], const RangeParams &rp)
+{
+    if constexpr (CH == 1) {
+        return d[0] >= rp.lo[0] && d[0] <= rp.hi[0];
+    } else {
+        // V of the triple is its maximum: outside the V window -- every background pixel of a quiet scene -- H and S are not needed
+        const int vmax = max(d[0], max(d[1], d[2]));
+        if (vmax < rp.lo[2] || vmax > rp.hi[2]) return false;
+        int h, s, v;
+        bgr2hsv_inline(d[0], d[1], d[2], h, s, v);
+        return in_range3(h, s, v, rp);
+    }
+}
+
+// 4 pixels of one frame held as CH little-endian dwords: bg (CH dwords) and acc (4 * CH floats) move on; -> the 4 window bits
+template <int CH, bool LEARN>
+__device__ __forceinline__ unsigned frame4(const unsigned (&f)[CH], unsigned keep, bool first, unsigned (&bgw)[CH], float (&acc)[4 * CH],
+                                           const BsubArgs &a)
+{
+    unsigned nib = 0, out[CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) out[j] = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        int d[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const int e = k * CH + c, w = e >> 2, sh = (e & 3) * 8;
+            const int x = (keep >> k) & 1u ? (int)((f[w] >> sh) & 255u) : 0;
+            int bg = (int)((bgw[w] >> sh) & 255u);
+            d[c] = bsub_elem<LEARN>(x, first, bg, acc[e], a.a, a.b);
+            out[w] |= (unsigned)bg << sh;
+        }
+        nib |= window<CH>(d, a.rp) ? 1u << k : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < CH; ++j) bgw[j] = out[j];
+    return nib;
+}
+
+template <int CH, bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(256) void k_bsubtrack_wide(Geom g, BsubArgs a)
+{
+    const int s = a.first_stream + (int)blockIdx.y;
+    const bool first = (a.first >> blockIdx.y) & 1ull;               // uniform
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);            // 256 pixels = words 4 * wave .. 4 * wave + 3; Palloc % 1024 == 0
+    const int p0 = wave * 256 + lane * 4;
+    const int y = p0 / g.Wp, x = p0 - y * g.Wp;
+    const size_t npx = (size_t)g.H * g.W, NW = (size_t)(g.Palloc >> 6);
+    unsigned n1 = 0, n2 = 0;
+    if (p0 < g.P && x < g.W) {                                       // W % 4 == 0: the lane's 4 pixels are inside together
+        const size_t e0 = ((size_t)s * npx + (size_t)y * g.W + x) * CH;          // the lane's first element: a multiple of 4
+        unsigned keep = 15u;
+        if (ROI) keep = (((const uint8_t *)(a.roi + (size_t)s * NW))[p0 >> 3] >> (p0 & 4)) & 15u;
+        unsigned f[CH], bgw[CH];
+        float acc[4 * CH] = {};
+        const unsigned *fp = (const unsigned *)(a.frames + e0);
+        unsigned *bp = (unsigned *)(a.bg + e0);
+        float4 *ap = (float4 *)(a.acc + e0);
+#pragma unroll
+        for (int j = 0; j < CH; ++j) { f[j] = fp[j]; bgw[j] = 0; }
+        if (!first) {
+            if (LEARN) {
+#pragma unroll
+                for (int j = 0; j < CH; ++j) { const float4 q = ap[j]; acc[4 * j] = q.x; acc[4 * j + 1] = q.y; acc[4 * j + 2] = q.z; acc[4 * j + 3] = q.w; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < CH; ++j) bgw[j] = bp[j];
+            }
+        }
+        n1 = frame4<CH, LEARN>(f, keep, first, bgw, acc, a);
+        if (PAIR) {
+            const unsigned *fp2 = (const unsigned *)(a.frames2 + e0);
+#pragma unroll
+            for (int j = 0; j < CH; ++j) f[j] = fp2[j];
+            n2 = frame4<CH, LEARN>(f, keep, false, bgw, acc, a);
+        }
+        if (LEARN || first) {
+#pragma unroll
+            for (int j = 0; j < CH; ++j) bp[j] = bgw[j];
+#pragma unroll
+            for (int j = 0; j < CH; ++j) {
+                u32x4 q;
+                q.x = __float_as_uint(acc[4 * j]); q.y = __float_as_uint(acc[4 * j + 1]);
+                q.z = __float_as_uint(acc[4 * j + 2]); q.w = __float_as_uint(acc[4 * j + 3]);
+                *(u32x4 *)(ap + j) = q;
+                // a store of more than 64 bits reads its data registers after issue: two wait states, the registers live
+                asm volatile("s_nop 1" :: "v"(q) : "memory");
+            }
+        }
+    }
+    store_words(n1, lane, a.bits + (size_t)s * NW + (size_t)wave * 4);
+    if (PAIR) store_words(n2, lane, a.bits2 + (size_t)s * NW + (size_t)wave * 4);
+}
+
+template <int CH, bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(256) void k_bsubtrack_narrow(Geom g, BsubArgs a)
+{
+    const int s = a.first_stream + (int)blockIdx.y;
+    const bool first = (a.first >> blockIdx.y) & 1ull;               // uniform
+    const int lane = threadIdx.x & 63;
+    const int word = blockIdx.x * 4 + (threadIdx.x >> 6);            // Palloc % 256 == 0: every word of the grid exists
+    const int p = word * 64 + lane;
+    const int y = p / g.Wp, x = p - y * g.Wp;
+    const size_t npx = (size_t)g.H * g.W, NW = (size_t)(g.Palloc >> 6);
+    bool on1 = false, on2 = false;
+    if (p < g.P && x < g.W) {
+        const size_t e0 = ((size_t)s * npx + (size_t)y * g.W + x) * CH;
+        const bool keep = !ROI || ((a.roi[(size_t)s * NW + word] >> lane) & 1ull);
+        int bg[CH], d[CH];
+        float acc[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            bg[c] = 0; acc[c] = 0.f;
+            if (!first) { if (LEARN) acc[c] = a.acc[e0 + c]; else bg[c] = a.bg[e0 + c]; }
+            d[c] = bsub_elem<LEARN>(keep ? (int)a.frames[e0 + c] : 0, first, bg[c], acc[c], a.a, a.b);
+        }
+        on1 = window<CH>(d, a.rp);
+        if (PAIR) {
+#pragma unroll
+            for (int c = 0; c < CH; ++c) d[c] = bsub_elem<LEARN>(keep ? (int)a.frames2[e0 + c] : 0, false, bg[c], acc[c], a.a, a.b);
+            on2 = window<CH>(d, a.rp);
+        }
+        if (LEARN || first) {
+#pragma unroll
+            for (int c = 0; c < CH; ++c) { a.bg[e0 + c] = (uint8_t)bg[c]; a.acc[e0 + c] = acc[c]; }
+        }
+    }
+    const u64 w1 = __ballot(on1);
+    if (lane == 0) a.bits[(size_t)s * NW + word] = w1;
+    if (PAIR) {
+        const u64 w2 = __ballot(on2);
+        if (lane == 0) a.bits2[(size_t)s * NW + word] = w2;
+    }
+}
+
+template <int CH, bool ROI, bool PAIR, bool LEARN> void launch_one(const Geom &g, const BsubArgs &a, bool wide, int n, hipStream_t st)
+{
+    if (wide) hipLaunchKernelGGL((k_bsubtrack_wide<CH, ROI, PAIR, LEARN>), dim3(g.Palloc / 1024, n), dim3(256), 0, st, g, a);
+    else hipLaunchKernelGGL((k_bsubtrack_narrow<CH, ROI, PAIR, LEARN>), dim3(g.Palloc / 256, n), dim3(256), 0, st, g, a);
+}
+template <int CH, bool ROI, bool PAIR> void launch_learn(const Geom &g, const BsubArgs &a, bool learn, bool wide, int n, hipStream_t st)
+{
+    if (learn) launch_one<CH, ROI, PAIR, true>(g, a, wide, n, st);
+    else launch_one<CH, ROI, PAIR, false>(g, a, wide, n, st);
+}
+template <int CH> void launch_ch(const Geom &g, const BsubArgs &a, bool learn, bool wide, int n, hipStream_t st)
+{
+    const bool roi = a.roi != nullptr, pair = a.frames2 != nullptr;
+    if (roi) { if (pair) launch_learn<CH, true, true>(g, a, learn, wide, n, st); else launch_learn<CH, true, false>(g, a, learn, wide, n, st); }
+    else { if (pair) launch_learn<CH, false, true>(g, a, learn, wide, n, st); else launch_learn<CH, false, false>(g, a, learn, wide, n, st); }
+}
+
+}  // namespace
+
+bool bsubtrack_front_is_wide(const Geom &g, const BsubLaunch &a)
+{
+    const uintptr_t m = (uintptr_t)a.frames | (uintptr_t)a.frames2 | (uintptr_t)a.bg;
+    return g.W % 4 == 0 && (m & 3u) == 0 && ((uintptr_t)a.acc & 15u) == 0;
+}
+
+void launch_bsubtrack_front(const Geom &g, const BsubLaunch &a, int n_streams, hipStream_t st)
+{
+    const bool wide = bsubtrack_front_is_wide(g, a);
+    for (int s0 = 0; s0 < n_streams; s0 += 64) {         // the first-frame mask of a launch is one 64-bit kernel argument
+        const int n = n_streams - s0 < 64 ? n_streams - s0 : 64;
+        BsubArgs k{a.frames, a.frames2, a.bg, a.acc, a.bits, a.bits2, a.roi, 0ull, a.rp, a.a, a.b, s0};
+        for (int i = 0; i < n; ++i) k.first |= (u64)(a.have[s0 + i] == 0) << i;
+        if (a.channels == 3) launch_ch<3>(g, k, a.learn, wide, n, st);
+        else launch_ch<1>(g, k, a.learn, wide, n, st);
+    }
+}
+
+}  // namespace oatgpu

@@ -14,6 +14,7 @@
 //   narrow (everything else): one pixel a lane with byte accesses, the ballot is the word (k_absdiff_bits' mapping).
 // Both write EVERY word of Palloc / 64 (zero bits for x >= W and p >= P): the row scan reads them.
 #include "oatgpu_internal.h"
+#include "maskwords_inline.h"
 
 namespace oatgpu {
 
@@ -38,27 +39,6 @@ template <int CH> __device__ __forceinline__ unsigned grey4(const uint8_t *frame
 #pragma unroll
     for (int k = 0; k < 4; ++k) g |= (unsigned)grey_bgr(byte_of(d, 3 * k), byte_of(d, 3 * k + 1), byte_of(d, 3 * k + 2)) << (8 * k);
     return g;
-}
-
-// bits 0..15 of x to bits 0, 4, 8, .. 60
-__device__ __forceinline__ u64 spread4(u64 x)
-{
-    x = (x | x << 24) & 0x000000ff000000ffull;
-    x = (x | x << 12) & 0x000f000f000f000full;
-    x = (x | x << 6) & 0x0303030303030303ull;
-    x = (x | x << 3) & 0x1111111111111111ull;
-    return x;
-}
-
-// the wave's 4 mask words out of every lane's nibble (bit k = pixel k of the lane): lane w < 4 stores word w
-__device__ __forceinline__ void store_words(unsigned nib, int lane, u64 *dst)
-{
-    const u64 b0 = __ballot(nib & 1u), b1 = __ballot(nib & 2u), b2 = __ballot(nib & 4u), b3 = __ballot(nib & 8u);
-    if (lane < 4) {
-        const int sh = lane * 16;
-        dst[lane] = spread4((b0 >> sh) & 0xffffull) | spread4((b1 >> sh) & 0xffffull) << 1 | spread4((b2 >> sh) & 0xffffull) << 2 |
-                    spread4((b3 >> sh) & 0xffffull) << 3;
-    }
 }
 
 struct DiffArgs {

@@ -117,7 +117,7 @@ struct MarkerFilters {
 // scratch set `slot` (0..3) under open_sync's drain, the way detect_tail uses set 0 -- with the MORPH and FINAL planes replaced by
 // the tracker's own, so that oatgpu_read_diff_mask holds whatever the context's other calls do in between.
 struct DiffTracker {
-    static constexpr int kSlots = 4;           // frames in flight inside oatgpu_diff_sequence_dev
+    static constexpr int kSlots = 4;           // frames in flight inside oatgpu_diff_sequence_dev (= kSeqSlots)
     bool on = false;
     DevMem<u64> bits;                          // [kSlots][n][Palloc/64] the front kernel's threshold words
     DevMem<u64> masks;                         // [kSlots][2][n][Palloc/64] the slot's morph / fin planes (the taps)
@@ -126,6 +126,23 @@ struct DiffTracker {
     Event ev_done[kSlots];                     // the slot's back half has finished
     int last = -1;                             // slot of the latest diff frame (oatgpu_read_diff_mask); -1: none yet
     std::vector<char> last_dilated;            // [n] of that frame: the stream's back half dilated (its MORPH tap is the morph plane)
+};
+
+// the subtraction tracker (oatgpu_set_bsub_tracker; kernels_bsubtrack.hip): `framefilt bsub` -> `col -C HSV` -> `posidet
+// hsv` (GREY: bsub -> `posidet thresh`) for every camera of the context.  Made by the switch, never inside a step; a frame's back
+// half runs in the context's scratch set `slot` (0..3) under open_sync's drain with the TMP, MORPH and FINAL planes replaced by the
+// tracker's own, so that oatgpu_read_bsub_mask holds whatever the context's other calls do in between.  The background itself --
+// bsub_bg, bsub_f, bsub_have -- is the context's: oatgpu_bsub_filter's.
+struct BsubTracker {
+    static constexpr int kSlots = 4;           // frames in flight inside oatgpu_bsub_track_sequence_dev (= kSeqSlots)
+    bool on = false;
+    DevMem<u64> bits;                          // [kSlots][n][Palloc/64] the front kernel's threshold words
+    DevMem<u64> masks;                         // [kSlots][3][n][Palloc/64] the slot's tmp / morph / fin planes (the taps)
+    HostMem<ResultRec> rec;                    // host-mapped: [kSlots][n] result records, written by the blob kernels through dev()
+    Event ev_front[kSlots];                    // stream A: the front launch that wrote this slot's bits has finished
+    Event ev_done[kSlots];                     // the slot's back half has finished
+    int last = -1;                             // slot of the latest frame (oatgpu_read_bsub_mask); -1: none yet
+    const u64 *last_tap = nullptr;             // of that frame: where the mask after erode / dilate is (the MORPH tap)
 };
 
 struct oatgpu_ctx {
@@ -292,6 +309,7 @@ struct oatgpu_ctx {
 
     MarkerSet mk; MarkerPipeline mkp; MarkerFilters mf;      // the optional features: dropping one is assignment (c->mkp = {})
     DiffTracker df;
+    BsubTracker bs;
 };
 
 // a back half's erosion and dilation, planned and issued (plan_morph, issue_morph: api_track.hip)
@@ -335,6 +353,7 @@ int open_sync(oatgpu_ctx *c);
 int check_stream_ix(oatgpu_ctx *c, int s);
 // api_stages.hip
 int read_plane(oatgpu_ctx *c, const u64 *plane, uint8_t *out);
+int ensure_bsub(oatgpu_ctx *c, size_t nb);
 // api_track.hip
 Rate mog_begin(oatgpu_ctx *c, int s, double learningRate);
 MogLaunch mog_launch_base(oatgpu_ctx *c, const uint8_t *frames, const Rate &r);
@@ -389,6 +408,55 @@ static inline u64 *thr_buf(oatgpu_ctx *c, int parity)
 // B streams of the plain order for a frame.  Host frames arrive over the copy stream: use one B stream fewer then: the copy
 // stream sits on the last B stream's hardware queue (see acquire_streams)
 static inline int plain_b_streams(const oatgpu_ctx::FrameJob &f) { return f.ready ? 2 : oatgpu_ctx::kNB; }
+
+// A recorded sequence of a batched tracker (api_diff.hip, api_bsubtrack.hip) with up to kSeqSlots frames in flight.  Front launches
+// go to stream A, frames_of(t) (1 or 2) frames a launch; front(t, nf, q, q2) issues the one for frames t (.. t + 1) into slots q
+// (and q2); frame t's back half -- back(slot, i, B), i = its place in the front launch -- runs on B[t % 3] behind the front launch's
+// event in slot t % kSeqSlots, and a slot is reused only after hand_out(slot, frame) has collected it.  Everything is collected
+// before the call returns; on an error nothing of the call stays in flight.
+constexpr int kSeqSlots = 4;
+template <class FramesOf, class Front, class Back, class HandOut>
+static int run_sequence_in_flight(oatgpu_ctx *c, int n_frames, Event *ev_front, Event *ev_done, FramesOf frames_of, Front front,
+                                  Back back, HandOut hand_out)
+{
+    constexpr int K = kSeqSlots;
+    int got = 0, rc = OATGPU_OK;
+    auto collect_one = [&]() -> int {
+        const int q = got % K;
+        HIPCHK(c, hipEventSynchronize(ev_done[q]));
+        hand_out(q, got);
+        ++got;
+        return OATGPU_OK;
+    };
+    auto back_on_b = [&](int t, int i, hipEvent_t front_done) -> int {
+        const int q = t % K, b = t % oatgpu_ctx::kNB;
+        hipStream_t B = c->stream_b[b];
+        c->b_used[b] = true;
+        HIPCHK(c, hipStreamWaitEvent(B, front_done, 0));
+        const int r = back(q, i, B);
+        if (r) return r;
+        HIPCHK(c, hipEventRecord(ev_done[q], B));
+        return OATGPU_OK;
+    };
+    int t = 0;
+    while (t < n_frames && !rc) {
+        const int nf = frames_of(t);
+        while (!rc && t + nf - got > K) rc = collect_one();
+        if (rc) break;
+        const int q = t % K;
+        rc = front(t, nf, q, (t + 1) % K);
+        if (rc) break;
+        hipError_t e = hipEventRecord(ev_front[q], c->stream);
+        if (e != hipSuccess) { rc = fail(c, OATGPU_E_HIP, "hipEventRecord failed: %s", hipGetErrorString(e)); break; }
+        rc = back_on_b(t, 0, ev_front[q]);
+        if (!rc && nf == 2) rc = back_on_b(t + 1, 1, ev_front[q]);
+        if (rc) break;
+        t += nf;
+    }
+    while (!rc && got < n_frames) rc = collect_one();
+    if (rc) { (void)hipStreamSynchronize(c->stream); (void)drain_b(c); }       // nothing of this call stays in flight
+    return rc;
+}
 
 static inline void mark_speculative(oatgpu_ctx *c, int slot)
 {

@@ -168,6 +168,24 @@ struct DiffLaunch {
 bool diff_front_is_wide(const Geom &g, const DiffLaunch &a);
 void launch_diff_front(const Geom &g, const DiffLaunch &a, int n_streams, hipStream_t st);
 
+// --- kernels_bsubtrack.hip --- (the subtraction tracker's front end: bsub -> col HSV -> inRange, or bsub -> inRange for GREY)
+struct BsubLaunch {
+    const uint8_t *frames;   // [n][H*W*channels] packed BGR (3) or GREY (1), stream-major
+    const uint8_t *frames2;  // nullptr, or the NEXT frame of every stream: the launch advances two frames
+    int channels;
+    uint8_t *bg;             // [n][H*W*channels] framefilt bsub's background of every stream
+    float *acc;              // [n][H*W*channels] ... and its fp32 accumulator
+    const char *have;        // HOST: [n] 0: the stream's first frame (acc = bg = the masked frame)
+    u64 *bits, *bits2;       // [n][Palloc/64] threshold words of the frame(s); every word is written
+    const u64 *roi;          // [n][Palloc/64] region-of-interest bits (framefilt mask in front of bsub) or nullptr
+    RangeParams rp;          // the window on hsv(difference); GREY: lo[0] <= difference <= hi[0]
+    bool learn;              // alpha > 0: cv::accumulateWeighted with a = (float)alpha, b = 1 - a
+    float a, b;
+};
+// 4 pixels a lane: W % 4 == 0, frames / frames2 / bg 4-byte and acc 16-byte aligned; otherwise one pixel a lane
+bool bsubtrack_front_is_wide(const Geom &g, const BsubLaunch &a);
+void launch_bsubtrack_front(const Geom &g, const BsubLaunch &a, int n_streams, hipStream_t st);
+
 // --- kernels_undistort.hip --- (framefilt undistort, Undistorter.cpp:83-88)
 // 0, or -1 with the reason in *why: 5 to 8 coefficients (the reference's check) and not 6 or 7 (OpenCV 3.1 asserts on those)
 int undistort_check_coeffs(int n_dist, const char **why);

@@ -160,6 +160,13 @@ SIGNATURES = {
     "oatgpu_diff_batch": (C.c_int, [_ctx, C.POINTER(_u8p), C.c_int32, C.POINTER(Position)]),
     "oatgpu_diff_sequence_dev": (C.c_int, [_ctx, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Position)]),
     "oatgpu_read_diff_mask": (C.c_int, [_ctx, C.c_int32, C.c_int32, _u8p]),
+    "oatgpu_set_bsub_tracker": (C.c_int, [_ctx, C.c_int32]),
+    "oatgpu_bsub_reset": (C.c_int, [_ctx, C.c_int32]),
+    "oatgpu_bsub_track_batch_dev": (C.c_int, [_ctx, C.c_void_p, C.c_double, C.POINTER(Position)]),
+    "oatgpu_bsub_track_batch": (C.c_int, [_ctx, C.POINTER(_u8p), C.c_int32, C.c_double, C.POINTER(Position)]),
+    "oatgpu_bsub_track_sequence_dev": (C.c_int, [_ctx, C.POINTER(C.c_void_p), C.c_int32, C.c_double, C.POINTER(Position)]),
+    "oatgpu_bsub_get_state": (C.c_int, [_ctx, C.c_int32, _u8p, _fp]),
+    "oatgpu_read_bsub_mask": (C.c_int, [_ctx, C.c_int32, C.c_int32, _u8p]),
     "oatgpu_track_batch": (C.c_int, [_ctx, C.POINTER(_u8p), C.c_int32, C.c_double, C.POINTER(Position)]),
     "oatgpu_track_batch_dev": (C.c_int, [_ctx, C.c_void_p, C.c_double, C.POINTER(Position)]),
     "oatgpu_track_enqueue": (C.c_int, [_ctx, C.POINTER(_u8p), C.c_int32, C.c_double]),

@@ -290,6 +290,20 @@ inline PnmImage read_pnm(const std::string &path)
     if (im.channels == 3) for (size_t i = 0; i < n; i += 3) std::swap(im.px[i], im.px[i + 2]);    // RGB file -> BGR
     return im;
 }
+// `framefilt bsub -f FILE` (BackgroundSubtractor.cpp:63-71: imread(.., IMREAD_COLOR)) for frames of rows x cols x channels bytes
+inline PnmImage read_background_image(const std::string &path, size_t rows, size_t cols, int channels)
+{
+    PnmImage im = read_pnm(path);
+    if (im.channels == 1 && channels == 3) {         // IMREAD_COLOR turns a grey file into 3 equal channels
+        std::vector<uint8_t> c3(im.px.size() * 3);
+        for (size_t i = 0; i < im.px.size(); ++i) c3[3 * i] = c3[3 * i + 1] = c3[3 * i + 2] = im.px[i];
+        im.px.swap(c3);
+        im.channels = 3;
+    }
+    if (im.rows != rows || im.cols != cols || im.channels != channels)
+        throw std::runtime_error("background image and SOURCE frames differ in size or channels");   // cv::subtract would throw
+    return im;
+}
 struct GreyImage { size_t rows{0}, cols{0}; std::vector<uint8_t> px; };
 // imread(path, IMREAD_GRAYSCALE): colour files go through the same fixed-point BGR->grey as cvtColor
 // ((1868 B + 9617 G + 4899 R + 8192) >> 14, the constants of Threshold.cpp's path as well)

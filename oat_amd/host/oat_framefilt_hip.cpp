@@ -110,15 +110,7 @@ protected:
         cfg.device = gpu_index_; cfg.rows = (int)p.rows; cfg.cols = (int)p.cols; cfg.channels = color_bytes(p.color);
         gpu_.create(cfg);
         if (!background_file_.empty()) {                 // BackgroundSubtractor.cpp:63-71: imread(.., COLOR)
-            PnmImage im = read_pnm(background_file_);
-            if (im.channels == 1 && cfg.channels == 3) {    // IMREAD_COLOR turns a grey file into 3 equal channels
-                std::vector<uint8_t> c3(im.px.size() * 3);
-                for (size_t i = 0; i < im.px.size(); ++i) c3[3 * i] = c3[3 * i + 1] = c3[3 * i + 2] = im.px[i];
-                im.px.swap(c3);
-                im.channels = 3;
-            }
-            if (im.rows != p.rows || im.cols != p.cols || im.channels != cfg.channels)
-                throw std::runtime_error("background image and SOURCE frames differ in size or channels");   // cv::subtract would throw
+            const PnmImage im = read_background_image(background_file_, p.rows, p.cols, cfg.channels);
             gpu_.check(oatgpu_bsub_set_background(gpu_.ctx, 0, im.px.data()));
         }
     }

@@ -3,6 +3,8 @@
 //         thresh  replacement of `oat posidet thresh` (src/positiondetector/SimpleThreshold.cpp)
 //         diff    replacement of `oat posidet diff`   (src/positiondetector/DifferenceDetector.cpp)
 //                 diff --bgr: of the chain `oat framefilt col -C GREY` -> `oat posidet diff` on a BGR source (the motion tracker)
+//                 hsv --bsub: of the chain `oat framefilt bsub` -> `oat framefilt col -C HSV` -> `oat posidet hsv` on a BGR source,
+//                 thresh --bsub: of `oat framefilt bsub` -> `oat posidet thresh` on a GREY source (the subtraction tracker)
 // Same positional arguments and option names as src/positiondetector/main.cpp:85-271.
 #include "component.hpp"
 
@@ -14,15 +16,19 @@ enum class Kind { HSV, THRESH, DIFF };
 
 class GpuDetector : public PositionDetector {
 public:
-    GpuDetector(const std::string &src, const std::string &snk, Kind kind, bool bgr = false)
-        : PositionDetector(src, snk), kind_(kind), bgr_(bgr && kind == Kind::DIFF)
+    GpuDetector(const std::string &src, const std::string &snk, Kind kind, bool bgr = false, bool bsub = false)
+        : PositionDetector(src, snk), kind_(kind), bgr_(bgr && kind == Kind::DIFF), bsub_(bsub && kind != Kind::DIFF)
     {
         oatgpu_default_config(&cfg_);
         if (bgr_) { required_color_ = PIX_BGR; cfg_.channels = 3; cfg_.erode = 0; cfg_.dilate = 0; }
+        else if (bsub_ && kind == Kind::HSV) { required_color_ = PIX_BGR; cfg_.channels = 3; cfg_.erode = 0; cfg_.dilate = 10; }
+        else if (bsub_) { required_color_ = PIX_GREY; cfg_.channels = 1; cfg_.erode = 0; cfg_.dilate = 0; }
         else if (kind == Kind::HSV) { required_color_ = PIX_HSV; cfg_.erode = 0; cfg_.dilate = 10; }   // HSVDetector.cpp:42-46
         else { required_color_ = PIX_GREY; cfg_.erode = 0; cfg_.dilate = 0; }   // SimpleThreshold.cpp:42-46, DifferenceDetector.cpp:41-44
     }
     oatgpu_config cfg_;
+    double bsub_alpha_{0.0};            // --bsub-alpha: framefilt bsub's -a (BackgroundSubtractor.h)
+    std::string bsub_background_;       // --bsub-background: framefilt bsub's -f, PGM/PPM instead of cv::imread's formats
 
 protected:
     void configure_for(const FrameParams &p) override
@@ -30,13 +36,20 @@ protected:
         cfg_.rows = (int)p.rows; cfg_.cols = (int)p.cols; cfg_.n_streams = 1;
         gpu_.create(cfg_);
         if (bgr_) gpu_.check(oatgpu_set_diff_tracker(gpu_.ctx, 1));
+        if (bsub_) {
+            gpu_.check(oatgpu_set_bsub_tracker(gpu_.ctx, 1));
+            if (!bsub_background_.empty()) {                 // BackgroundSubtractor.cpp:63-71: imread(.., COLOR)
+                const PnmImage im = read_background_image(bsub_background_, p.rows, p.cols, cfg_.channels);
+                gpu_.check(oatgpu_bsub_set_background(gpu_.ctx, 0, im.px.data()));
+            }
+        }
     }
     // HSVDetector.cpp:142-173 / SimpleThreshold.cpp:114-134
     // Deferred (oatgpu_set_deferred): the call returns when the frame has left shared memory, PositionDetector::process posts
     // the source, and detect_finish() waits for the kernels and takes the position (PositionDetector.cpp:78-96).
     bool detect_from_shm(const Frame &frame, Position2D &) override
     {
-        if (bgr_) return false;           // the motion tracker's step is synchronous: the frame is copied and the source posted first
+        if (bgr_ || bsub_) return false;  // the batched trackers' step is synchronous: the frame is copied and the source posted first
         if (!deferred_on_) { gpu_.check(oatgpu_set_deferred(gpu_.ctx, 1)); deferred_on_ = true; }
         gpu_.check(kind_ == Kind::HSV ? oatgpu_detect_hsv(gpu_.ctx, 0, frame.data(), nullptr)
                    : kind_ == Kind::THRESH ? oatgpu_detect_thresh(gpu_.ctx, 0, frame.data(), nullptr)
@@ -55,6 +68,7 @@ protected:
         oatgpu_position r;
         const uint8_t *one[1] = {frame.data()};
         gpu_.check(bgr_ ? oatgpu_diff_batch(gpu_.ctx, one, 1, &r)
+                   : bsub_ ? oatgpu_bsub_track_batch(gpu_.ctx, one, 1, bsub_alpha_, &r)
                    : kind_ == Kind::HSV ? oatgpu_detect_hsv(gpu_.ctx, 0, frame.data(), &r)
                    : kind_ == Kind::THRESH ? oatgpu_detect_thresh(gpu_.ctx, 0, frame.data(), &r)
                                            : oatgpu_detect_diff(gpu_.ctx, 0, frame.data(), &r));
@@ -62,7 +76,7 @@ protected:
         if (r.valid) { position.position.x = r.x; position.position.y = r.y; }
     }
     Kind kind_;
-    bool bgr_;
+    bool bgr_, bsub_;
     bool deferred_on_{false};
     GpuCtx gpu_;
 };
@@ -74,6 +88,10 @@ static void usage()
                  "        --bgr  the SOURCE is BGR: framefilt col -C GREY is done in front of the detector, in the same kernel\n"
                  "hsv:    -H/-S/-V [min,max] in [0,256]  -e erode  -d dilate (default 10)  -a [min,max] area\n"
                  "thresh: -T [min,max]  -e erode  -d dilate  -a [min,max] area\n"
+                 "hsv, thresh: --bsub  framefilt bsub (and, for hsv, col -C HSV) is done in front of the detector, in the same kernel:\n"
+                 "        the SOURCE is then BGR for hsv, GREY for thresh\n"
+                 "        --bsub-alpha A  bsub's adaptation coefficient, 0..1 (default 0: the first frame stays the background)\n"
+                 "        --bsub-background FILE.ppm|.pgm  the background image instead of the first frame (it cannot adapt)\n"
                  "all:    --gpu-index N  HIP device ordinal (default 0)\n";
 }
 
@@ -85,19 +103,31 @@ int main(int argc, char **argv)
         Options o = Options::parse(argc, argv,
             {{"H", "h-thresh"}, {"S", "s-thresh"}, {"V", "v-thresh"}, {"T", "thresh"}, {"e", "erode"},
              {"d", is_diff ? "diff-threshold" : "dilate"}, {"b", "blur"}, {"a", "area"}, {"t", "tune"}, {"h", "help"}, {"v", "version"}},
-            {"help", "version", "tune", "bgr"});
+            {"help", "version", "tune", "bgr", "bsub"});
         if (o.has("version")) { std::cout << "oat-posidet-hip (MI355X drop-in, liboatgpu ABI " << oatgpu_abi_version() << ")\n"; return 0; }
         if (o.has("help") || o.positional.size() != 3) { usage(); return o.has("help") ? 0 : -1; }
         const std::string type = o.positional[0];
         if (type != "hsv" && type != "thresh" && type != "diff") throw std::runtime_error("Selected TYPE is invalid.");
         // option names per TYPE: HSVDetector.cpp:49-75, SimpleThreshold.cpp:49-69, DifferenceDetector.cpp:41-62
-        if (type == "hsv") o.apply_config({"h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "tune", "gpu-index"}, {"tune"});
-        else if (type == "thresh") o.apply_config({"thresh", "erode", "dilate", "area", "tune", "gpu-index"}, {"tune"});
+        if (type == "hsv")
+            o.apply_config({"h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background"},
+                           {"tune", "bsub"});
+        else if (type == "thresh")
+            o.apply_config({"thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background"}, {"tune", "bsub"});
         else o.apply_config({"diff-threshold", "blur", "area", "tune", "gpu-index", "bgr"}, {"tune", "bgr"});
         if (o.has("bgr") && type != "diff") throw std::runtime_error("--bgr goes with TYPE diff only");
+        if (type == "diff" && (o.has("bsub") || o.has("bsub-alpha") || o.has("bsub-background")))
+            throw std::runtime_error("--bsub goes with TYPE hsv or thresh only");
+        if (!o.has("bsub") && (o.has("bsub-alpha") || o.has("bsub-background")))
+            throw std::runtime_error("--bsub-alpha and --bsub-background need --bsub");
+        if (o.has("bsub-background") && o.num("bsub-alpha", 0, 0, 1) > 0)
+            throw std::runtime_error("a background image from a file cannot adapt (--bsub-alpha must be 0)");
         if (o.has("tune")) throw std::runtime_error("--tune needs a GUI and is not available in the hip detector");
         auto d = std::make_unique<GpuDetector>(o.positional[1], o.positional[2],
-                                               type == "hsv" ? Kind::HSV : type == "thresh" ? Kind::THRESH : Kind::DIFF, o.has("bgr"));
+                                               type == "hsv" ? Kind::HSV : type == "thresh" ? Kind::THRESH : Kind::DIFF, o.has("bgr"),
+                                               o.has("bsub"));
+        d->bsub_alpha_ = o.num("bsub-alpha", 0, 0, 1);
+        if (o.has("bsub-background")) d->bsub_background_ = o.kv.at("bsub-background");
         d->cfg_.device = (int)o.num("gpu-index", 0, 0, 64);
         double a, b;
         auto range = [](double x, double y, const char *what) {
