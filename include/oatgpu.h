@@ -47,7 +47,8 @@ extern "C" {
  * the motion tracker -- oatgpu_set_diff_tracker, oatgpu_diff_reset, oatgpu_diff_batch_dev, oatgpu_diff_batch,
  * oatgpu_diff_sequence_dev, oatgpu_read_diff_mask; the subtraction tracker -- oatgpu_set_bsub_tracker, oatgpu_bsub_reset,
  * oatgpu_bsub_track_batch_dev, oatgpu_bsub_track_batch, oatgpu_bsub_track_sequence_dev, oatgpu_bsub_get_state,
- * oatgpu_read_bsub_mask. */
+ * oatgpu_read_bsub_mask; Bayer RAW8 ingest -- oatgpu_debayer_filter, oatgpu_debayer_dev, oatgpu_set_track_bayer, with the
+ * OATGPU_BAYER_* pattern values. */
 
 enum {
     OATGPU_OK = 0,
@@ -318,6 +319,39 @@ int oatgpu_undistort_dev(oatgpu_ctx *ctx, const void *frames_dev, void *out_dev)
  * keeps its rule for device frames: it returns once the step's per-pixel kernel has finished, which runs behind the remap
  * that read the caller's frame. */
 int oatgpu_set_track_undistort(oatgpu_ctx *ctx, int32_t on);
+
+/* ---- Bayer RAW8 -> BGR: the frame server's pixel-format conversion (src/frameserver/PointGreyCam.cpp:48-50, :729) ----
+ *
+ * Input rows x cols bytes, one sample a pixel; output rows x cols x 3 bytes BGR.  A pattern is named by the 2 x 2 tile at
+ * image rows 0-1, columns 0-1 read row by row (the camera vendors' convention); OpenCV names the tile at rows 1-2, columns
+ * 1-2, so RGGB is COLOR_BayerBG2BGR, BGGR COLOR_BayerRG2BGR, GRBG COLOR_BayerGB2BGR and GBRG COLOR_BayerGR2BGR.
+ * Interior pixels (1 <= y <= rows - 2, 1 <= x <= cols - 2), 32-bit integer sums: at an R or B site the own colour is the
+ * sample, G = (N + S + W + E + 2) >> 2, the opposite colour = (NW + NE + SW + SE + 2) >> 2; at a G site G is the sample, the
+ * colour of the horizontal neighbours = (W + E + 1) >> 1, of the vertical ones = (N + S + 1) >> 1.  Output (y, x) is the
+ * interior triple of (clamp(y, 1, rows - 2), clamp(x, 1, cols - 2)) with that pixel's own site colours.  rows < 3 or
+ * cols < 3 is refused. */
+#define OATGPU_BAYER_RGGB 1      /* R G / G B */
+#define OATGPU_BAYER_BGGR 2      /* B G / G R */
+#define OATGPU_BAYER_GRBG 3      /* G R / B G */
+#define OATGPU_BAYER_GBRG 4      /* G B / R G */
+/* One host frame, synchronous (deferrable like the other frame filters). */
+int oatgpu_debayer_filter(oatgpu_ctx *ctx, int32_t pattern, const uint8_t *raw_in, uint8_t *bgr_out);
+/* One frame for EVERY stream in device memory, stream-major: n_streams*rows*cols bytes in, n_streams*rows*cols*3 out; one
+ * launch (one per 64 streams) on the context's stream, returns once queued, as oatgpu_undistort_dev.  n_patterns is 1 (one
+ * pattern for all) or n_streams.  bgr_dev must not overlap raw_dev. */
+int oatgpu_debayer_dev(oatgpu_ctx *ctx, const int32_t *patterns, int32_t n_patterns, const void *raw_dev, void *bgr_dev);
+/* Bayer frames INSIDE the fused tracker (default off; NULL / 0 turns it off).  While on, every fused track call
+ * (oatgpu_track_batch, _batch_dev, _enqueue, _enqueue_dev, _stage / _enqueue_staged, _sequence_dev and its _timed / _latency
+ * forms, oatgpu_track_markers[_dev], _markers_sequence_dev and the marker pipeline) takes RAW8 frames -- rows*cols bytes a
+ * stream for host frames, n_streams*rows*cols stream-major for device frames -- and host -> device copies move that many
+ * bytes.  The chain is demosaic -> [undistort] -> ROI mask -> MOG2 -> colour -> detector -> filters: one demosaic launch a
+ * step covers every stream and both frames of a two-frame step, into two BGR buffers of the context that the remap or the
+ * per-pixel kernel then reads.  The call drains outstanding work and allocates those buffers (2 x n_streams*rows*cols*3
+ * bytes) the first time: an out-of-memory is reported here, never in the middle of a step.  Refused (OATGPU_E_INVALID)
+ * before anything has moved: channels != 3, a pattern outside 1..4, n_patterns neither 1 nor n_streams, frames smaller than
+ * 3 x 3, a partly staged frame set.  While it is on the diff and bsub tracker calls are refused; the stage-by-stage calls
+ * never look at it; with it off nothing changes.  oatgpu_track_input_consumed[_stream] keep their rules. */
+int oatgpu_set_track_bayer(oatgpu_ctx *ctx, const int32_t *patterns, int32_t n_patterns);
 
 /* ---- marker sets: several colour windows per camera behind ONE MOG2 pass, `posicom mean` behind them ----
  *

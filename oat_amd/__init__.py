@@ -10,8 +10,8 @@ by the tests and the benchmark; there is no CPU fallback -- importing
 from .ffi import OatGpuError, lib_path  # noqa: F401
 from .components import (  # noqa: F401
     BackgroundSubtractorMOG, BackgroundSubtractor, Threshold, ColorConvert, HSVDetector, SimpleThreshold, DifferenceDetector, HotPath, MotionTracker, SubtractionTracker, Position2D, Combined,
-    Undistorter, undistort_map,
+    Undistorter, undistort_map, Debayer, bayer_pattern,
 )
 
 __all__ = ["BackgroundSubtractorMOG", "BackgroundSubtractor", "Threshold", "ColorConvert", "HSVDetector", "SimpleThreshold", "DifferenceDetector", "HotPath", "MotionTracker", "SubtractionTracker",
-           "Undistorter", "undistort_map", "Position2D", "Combined", "OatGpuError", "lib_path"]
+           "Undistorter", "undistort_map", "Debayer", "bayer_pattern", "Position2D", "Combined", "OatGpuError", "lib_path"]

@@ -310,6 +310,48 @@ class Undistorter(_Context):
         return self.lib.oatgpu_get_stream(self.ctx)
 
 
+_BAYER_NAMES = {"RGGB": ffi.BAYER_RGGB, "BGGR": ffi.BAYER_BGGR, "GRBG": ffi.BAYER_GRBG, "GBRG": ffi.BAYER_GBRG}
+
+
+def bayer_pattern(p):
+    """A Bayer pattern as the library's value: a name ("RGGB": the 2 x 2 tile at rows 0-1, columns 0-1, row by row) or the
+    value itself (1..4; anything else is left for the library to refuse)."""
+    if isinstance(p, str):
+        if p.upper() not in _BAYER_NAMES:
+            raise ValueError(f"unknown Bayer pattern {p!r} (RGGB, BGGR, GRBG or GBRG)")
+        return _BAYER_NAMES[p.upper()]
+    return int(p)
+
+
+def _bayer_patterns(patterns):
+    ps = [patterns] if isinstance(patterns, (str, int, np.integer)) else list(patterns)
+    vals = [bayer_pattern(p) for p in ps]
+    return (C.c_int32 * max(len(vals), 1))(*vals), len(vals)
+
+
+class Debayer(_Context):
+    """Bayer RAW8 -> BGR, the frame server's pixel-format conversion (PointGreyCam.cpp:48-50, :729) as a component:
+    OpenCV 3.1's bilinear demosaic, bit for bit (include/oatgpu.h)."""
+
+    def filter(self, raw, pattern):
+        f = _frame(raw, (self.rows, self.cols))
+        out = np.empty((self.rows, self.cols, 3), np.uint8)
+        self._chk(self.lib.oatgpu_debayer_filter(self.ctx, bayer_pattern(pattern), ffi.u8(f), ffi.u8(out)))
+        return out
+
+    def filter_dev(self, raw_dev, bgr_dev, patterns):
+        """Every stream's frame, device pointers (stream-major: n_streams*rows*cols bytes in, *3 out), one launch on the
+        context's stream (not waited for); patterns: one for all streams, or one a stream."""
+        arr, n = _bayer_patterns(patterns)
+        self._chk(self.lib.oatgpu_debayer_dev(self.ctx, arr, n, C.c_void_p(raw_dev), C.c_void_p(bgr_dev)))
+
+    def synchronize(self):
+        self._chk(self.lib.oatgpu_synchronize(self.ctx))
+
+    def get_stream(self):
+        return self.lib.oatgpu_get_stream(self.ctx)
+
+
 PIX_BINARY, PIX_GREY, PIX_BGR, PIX_HSV = 0, 1, 2, 3      # oat::PixelColor (Color.h:29-34)
 _COLOR_NAMES = {"BINARY": PIX_BINARY, "GREY": PIX_GREY, "BGR": PIX_BGR, "HSV": PIX_HSV}
 
@@ -544,6 +586,18 @@ class HotPath(_Detector):
         """oatgpu_set_track_undistort: every track call remaps each stream's frame with its map before the ROI mask and
         MOG2.  Every stream needs a map (set_undistort) to switch it on."""
         self._chk(self.lib.oatgpu_set_track_undistort(self.ctx, 1 if on else 0))
+
+    def bayer(self, patterns):
+        """oatgpu_set_track_bayer: every track call takes Bayer RAW8 frames (rows, cols) and demosaics them on the device
+        before anything else.  patterns: a name ("RGGB") or value for every stream, a list of n_streams of them, or None to
+        switch it off (frames are BGR again)."""
+        if patterns is None:
+            self._chk(self.lib.oatgpu_set_track_bayer(self.ctx, None, 0))
+            self.frame_shape = (self.rows, self.cols, 3) if self.channels == 3 else (self.rows, self.cols)
+            return
+        arr, n = _bayer_patterns(patterns)
+        self._chk(self.lib.oatgpu_set_track_bayer(self.ctx, arr, n))
+        self.frame_shape = (self.rows, self.cols)
 
     def _out(self):
         return [Position2D.from_c(p) for p in self._pos]

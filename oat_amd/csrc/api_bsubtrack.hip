@@ -57,6 +57,7 @@ static int bsub_refusals(oatgpu_ctx *c, const char *what, double alpha)
     if (c->kal_on) return fail(c, OATGPU_E_INVALID, "%s with the position filter on (oatgpu_set_kalman) is not supported", what);
     if (c->homo_on) return fail(c, OATGPU_E_INVALID, "%s with a homography on (oatgpu_set_homography) is not supported", what);
     if (c->ud_track) return fail(c, OATGPU_E_INVALID, "%s with undistortion on (oatgpu_set_track_undistort) is not supported", what);
+    if (c->by_track) return fail(c, OATGPU_E_INVALID, "%s with Bayer frames on (oatgpu_set_track_bayer) is not supported", what);
     if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(c, OATGPU_E_INVALID, "adaptation-coeff must be in [0,1]");
     if (alpha > 0.0)                    // the reference's accumulateWeighted asserts on its empty fp32 image
         for (int s = 0; s < c->cfg.n_streams; ++s)

@@ -178,7 +178,7 @@ int launch_marker_work(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, con
     MarkerFiltered *filt[2] = {};
     for (int i = 0; i < nj; ++i) {
         const int slot = j[i].slot;
-        fr[i] = c->ud_track ? c->ud_frames[i] : (const uint8_t *)j[i].frames;
+        fr[i] = step_frame(c, i, j[i].frames);
         z[i] = thr_buf(c, slot);
         src[i] = bits[i] = c->mkp.planes + (size_t)slot * planes * NW;
         u64 *own = c->mkp.masks + (size_t)slot * 3 * planes * NW;
@@ -244,7 +244,7 @@ extern "C" int oatgpu_track_markers_dev(oatgpu_ctx *c, const void *frames_dev, d
     c->mkp.last_slot = -1;
     // ---- 3. every marker's mask from the frames the per-pixel kernel read and the Z plane it has just written ----
     hipStream_t A = c->stream;
-    const uint8_t *seen = c->ud_track ? c->ud_frames[0] : (const uint8_t *)frames_dev;
+    const uint8_t *seen = step_frame(c, 0, frames_dev);
     launch_marker_bits(g, seen, c->cfg.channels, thr_buf(c, c->last_slot), c->mk.win, M, c->mk.planes, n, A);
     HIPCHK(c, hipGetLastError());
     // ---- 4. each marker's back half on its plane, with its erode / dilate / area ----

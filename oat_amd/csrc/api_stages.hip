@@ -334,6 +334,86 @@ extern "C" int oatgpu_undistort_dev(oatgpu_ctx *c, const void *frames_dev, void 
     return OATGPU_OK;
 }
 
+// ------------------------------------- Bayer RAW8 -> BGR (the frame server's conversion, PointGreyCam.cpp:48-50, :729) ----
+
+static int check_bayer_args(oatgpu_ctx *c, const int32_t *patterns, int n_patterns)
+{
+    if (c->g.H < 3 || c->g.W < 3) return fail(c, OATGPU_E_INVALID, "demosaicing needs frames of at least 3 x 3 pixels (have %d x %d)", c->g.H, c->g.W);
+    if (!patterns) return fail(c, OATGPU_E_INVALID, "null argument");
+    if (n_patterns != 1 && n_patterns != c->cfg.n_streams)
+        return fail(c, OATGPU_E_INVALID, "%d Bayer patterns for %d streams (give one, or one a stream)", n_patterns, c->cfg.n_streams);
+    for (int i = 0; i < n_patterns; ++i)
+        if (patterns[i] < OATGPU_BAYER_RGGB || patterns[i] > OATGPU_BAYER_GBRG)
+            return fail(c, OATGPU_E_INVALID, "Bayer pattern %d (stream %d) is not one of 1 RGGB, 2 BGGR, 3 GRBG, 4 GBRG", patterns[i], i);
+    return OATGPU_OK;
+}
+
+extern "C" int oatgpu_debayer_filter(oatgpu_ctx *c, int32_t pattern, const uint8_t *raw_in, uint8_t *bgr_out)
+{
+    if (!c) return OATGPU_E_INVALID;
+    if (!raw_in || !bgr_out) return fail(c, OATGPU_E_INVALID, "null argument");
+    int rc = check_bayer_args(c, &pattern, 1);
+    if (rc) return rc;
+    rc = open_sync(c);
+    if (rc) return rc;
+    const size_t npx = (size_t)c->g.H * c->g.W;
+    rc = stage_in(c, c->aux_a, raw_in, npx);
+    if (rc) return rc;
+    const uint8_t *in[1] = {c->aux_a};
+    uint8_t *const out[1] = {c->aux_b};
+    const int pat[1] = {pattern};
+    launch_debayer_frames(in, out, 1, pat, c->g.H, c->g.W, 1, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return finish_frame(c, bgr_out, c->aux_b, npx * 3);
+}
+
+extern "C" int oatgpu_debayer_dev(oatgpu_ctx *c, const int32_t *patterns, int32_t n_patterns, const void *raw_dev, void *bgr_dev)
+{
+    if (!c) return OATGPU_E_INVALID;
+    if (!raw_dev || !bgr_dev) return fail(c, OATGPU_E_INVALID, "null argument");
+    if (raw_dev == bgr_dev) return fail(c, OATGPU_E_INVALID, "debayer_dev cannot work in place");
+    { const int rc = check_bayer_args(c, patterns, n_patterns); if (rc) return rc; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    std::vector<int> pat((size_t)c->cfg.n_streams);
+    for (int s = 0; s < c->cfg.n_streams; ++s) pat[(size_t)s] = patterns[n_patterns == 1 ? 0 : s];
+    const uint8_t *in[1] = {(const uint8_t *)raw_dev};
+    uint8_t *const out[1] = {(uint8_t *)bgr_dev};
+    launch_debayer_frames(in, out, 1, pat.data(), c->g.H, c->g.W, c->cfg.n_streams, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return OATGPU_OK;
+}
+
+extern "C" int oatgpu_set_track_bayer(oatgpu_ctx *c, const int32_t *patterns, int32_t n_patterns)
+{
+    if (!c) return OATGPU_E_INVALID;
+    const bool on = patterns != nullptr || n_patterns != 0;
+    if (on) {
+        if (c->cfg.channels != 3) return fail(c, OATGPU_E_INVALID, "Bayer frames need a BGR context (channels = 3, have %d)", c->cfg.channels);
+        const int rc = check_bayer_args(c, patterns, n_patterns);
+        if (rc) return rc;
+    }
+    // (the staged copies were sized under the old setting)
+    if (c->staged_count)
+        return fail(c, OATGPU_E_INVALID, "a frame set is being staged (oatgpu_track_stage): finish it with oatgpu_track_enqueue_staged or give it up");
+    const int rc = open_sync(c);        // frames registered or in flight were handed over under the old setting
+    if (rc) return rc;
+    if (on && !c->by_frames[0]) {       // (allocated here, never in the middle of a step)
+        const size_t sb = (size_t)c->g.H * c->g.W * 3 * c->cfg.n_streams;
+        DevMem<uint8_t> fr[2];
+        if (fr[0].alloc(sb) != hipSuccess || fr[1].alloc(sb) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, OATGPU_E_NOMEM, "device allocation of the demosaiced-frame buffers (2 x %zu bytes) failed", sb);
+        }
+        c->by_frames[0] = std::move(fr[0]); c->by_frames[1] = std::move(fr[1]);
+    }
+    if (on) {
+        c->by_pat.resize((size_t)c->cfg.n_streams);
+        for (int s = 0; s < c->cfg.n_streams; ++s) c->by_pat[(size_t)s] = patterns[n_patterns == 1 ? 0 : s];
+    }
+    c->by_track = on;
+    return OATGPU_OK;
+}
+
 extern "C" int oatgpu_bgr2hsv(oatgpu_ctx *c, const uint8_t *bgr_in, uint8_t *hsv_out)
 {
     if (!c || !bgr_in || !hsv_out) return fail(c, OATGPU_E_INVALID, "null argument");

@@ -207,8 +207,9 @@ extern "C" int oatgpu_track_stage(oatgpu_ctx *c, int32_t stream_ix, const uint8_
         c->stage_slot = enq_slot(c);
     }
     if (c->staged[(size_t)stream_ix]) return fail(c, OATGPU_E_INVALID, "stream %d is already staged for this frame set", stream_ix);
-    const size_t fb = (size_t)c->g.H * c->g.W * c->cfg.channels;
-    uint8_t *dst = c->frames_ring + (size_t)c->stage_slot * fb * n;
+    // (a staging slot is a BGR / GREY frame set wide; RAW8 sets -- oatgpu_set_track_bayer -- fill the first third, stream-major)
+    const size_t fb = track_in_bytes(c), sb = (size_t)c->g.H * c->g.W * c->cfg.channels * n;
+    uint8_t *dst = c->frames_ring + (size_t)c->stage_slot * sb;
     if (!c->stream_c2 && n > 1) {
         hipStream_t s2 = acquire_copy_stream2(c->cfg.device);
         // (the event first: a context that shows a second copy stream always has the event enqueue_staged records on it)
@@ -291,7 +292,7 @@ extern "C" int oatgpu_track_enqueue(oatgpu_ctx *c, const uint8_t *const *frames_
     { const int rc = refuse_pipelined(c, kRefState | kRefRingFull); if (rc) return rc; }
     for (int s = 0; s < n; ++s) if (!frames_host[s]) return fail(c, OATGPU_E_INVALID, "null frame %d", s);
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    const size_t fb = (size_t)c->g.H * c->g.W * c->cfg.channels, sb = fb * n;
+    const size_t fb = track_in_bytes(c), sb = (size_t)c->g.H * c->g.W * c->cfg.channels * n;
     { const int rc = refuse_pipelined(c, kRefStaging); if (rc) return rc; }
     { const int rc = ensure_host_ring(c); if (rc) return rc; }
     // the slot's staging buffer was last read by the K1 of the frame collected from this slot
@@ -374,8 +375,18 @@ static int launch_front(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, co
     // into the context's buffers, which K1 then reads in place of the caller's.  Two buffers are enough: the next step's
     // remap queues behind this step's K1 on stream A.  (Outside the profile's K1 event pair.)
     const void *fr[2] = {j[0].frames, nj == 2 ? j[1].frames : nullptr};
+    // ... and in front of that the camera's own pixel format (oatgpu_set_track_bayer): the step's RAW8 frames of every stream
+    // demosaiced in ONE launch into the context's BGR buffers, which the remap (or K1) then reads -- the same lifetime rule
+    if (c->by_track) {
+        const uint8_t *in[2] = {(const uint8_t *)fr[0], (const uint8_t *)fr[1]};
+        uint8_t *const out[2] = {c->by_frames[0], c->by_frames[1]};
+        launch_debayer_frames(in, out, nj, c->by_pat.data(), c->g.H, c->g.W, n, A);
+        HIPCHK(c, hipGetLastError());
+        fr[0] = c->by_frames[0];
+        fr[1] = nj == 2 ? (const void *)c->by_frames[1] : nullptr;
+    }
     if (c->ud_track) {
-        const uint8_t *in[2] = {(const uint8_t *)j[0].frames, (const uint8_t *)fr[1]};
+        const uint8_t *in[2] = {(const uint8_t *)fr[0], (const uint8_t *)fr[1]};
         uint8_t *const out[2] = {c->ud_frames[0], c->ud_frames[1]};
         launch_undistort_frames(in, out, nj, c->ud_map1, c->ud_map2, c->ud_stride, c->g.H, c->g.W, c->cfg.channels, n, A);
         HIPCHK(c, hipGetLastError());
@@ -952,7 +963,7 @@ extern "C" int oatgpu_track_batch_dev(oatgpu_ctx *c, const void *frames_dev, dou
 // one host frame per camera stream into the staging buffer of the synchronous steps, on stream A; a null one ends it there
 int upload_frames(oatgpu_ctx *c, const uint8_t *const *frames_host)
 {
-    const size_t fb = (size_t)c->g.H * c->g.W * c->cfg.channels;
+    const size_t fb = track_in_bytes(c);
     for (int s = 0; s < c->cfg.n_streams; ++s) {
         if (!frames_host[s]) return fail(c, OATGPU_E_INVALID, "null frame %d", s);
         HIPCHK(c, hipMemcpyAsync(c->frames + (size_t)s * fb, frames_host[s], fb, hipMemcpyHostToDevice, c->stream));

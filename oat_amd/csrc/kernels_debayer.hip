@@ -1,0 +1,176 @@
+// kernels_debayer.hip -- Bayer RAW8 -> BGR: the frame server's pixel-format conversion of a colour camera
+// (src/frameserver/PointGreyCam.cpp:48-50, :729) as a device stage, for every camera stream (grid y) and both frames of a
+// two-frame step (grid z) in one launch.
+//
+// The arithmetic is OpenCV 3.1's bilinear Bayer2RGB_ in 32-bit integers.  At an R or B site: own colour = the sample,
+// G = (N + S + W + E + 2) >> 2, opposite colour = (NW + NE + SW + SE + 2) >> 2.  At a G site: G = the sample, the colour of the
+// horizontal neighbours = (W + E + 1) >> 1, of the vertical ones = (N + S + 1) >> 1.  Output (y, x) is the triple of
+// (clamp(y, 1, H - 2), clamp(x, 1, W - 2)) with THAT pixel's site colours: first / last column and row repeat their neighbours.
+//
+// The pattern is run-time data: per stream two parity bits, the row and the column of the R sample of the 2 x 2 tile, one bit
+// a stream in two 64-bit kernel arguments (so at most 64 streams a launch).
+//
+// Two lane mappings:
+//   wide   (W % 4 == 0, raw and BGR planes 4-byte aligned): a lane owns 4 pixels x 2 rows at (2 ty, 4 tx), the lanes laid
+//          over the (H + 1) / 2 x W / 4 blocks in raster order.  It reads the dwords at x0 - 4, x0, x0 + 4 of the FOUR raw rows
+//          around its block (the neighbour columns are extra dword loads, served by the vector cache: the lanes left and
+//          right load the same dwords as their centre) and writes 3 dwords (12 bytes) of each of its two BGR rows.
+//   narrow (everything else): one pixel a lane, byte accesses.
+// No LDS, no scratch; nothing wider than a dword is stored (DESIGN.md 3b does not arise).
+#include "oatgpu_internal.h"
+
+namespace oatgpu {
+
+namespace {
+
+constexpr int kDebayerWG = 256;
+
+struct DebayerArgs {
+    const uint8_t *in[2];                // [n][H*W] stream-major, one plane set a frame of the step
+    uint8_t *out[2];                     // [n][H*W*3]
+    u64 r_row, r_col;                    // bit (stream - first_stream): parity of the row / the column of the R sample
+    int H, W, first_stream;
+};
+
+// the five candidate values of a pixel from its 3 x 3 neighbourhood -> (B, G, R) packed as B | G << 8 | R << 16.
+// row_r / col_r: the pixel's row / column holds R samples
+__device__ __forceinline__ unsigned site_bgr(unsigned nw, unsigned n, unsigned ne, unsigned w, unsigned c, unsigned e,
+                                             unsigned sw, unsigned s, unsigned se, bool row_r, bool col_r)
+{
+    const unsigned h = (w + e + 1u) >> 1, v = (n + s + 1u) >> 1;
+    const unsigned p = (n + s + w + e + 2u) >> 2, d = (nw + ne + sw + se + 2u) >> 2;
+    unsigned b, g, r;
+    if (row_r == col_r) {                // an R or a B site
+        g = p;
+        r = row_r ? c : d;
+        b = row_r ? d : c;
+    } else {                             // a G site: in an R row the horizontal neighbours are R, the vertical ones B
+        g = c;
+        r = row_r ? h : v;
+        b = row_r ? v : h;
+    }
+    return b | g << 8 | r << 16;
+}
+
+// bytes x0 - 1 .. x0 + 4 of a raw row as one little-endian 48-bit window (l, c, r: the dwords at x0 - 4, x0, x0 + 4)
+__device__ __forceinline__ u64 window(unsigned l, unsigned c, unsigned r)
+{
+    return (u64)(l >> 24) | (u64)c << 8 | (u64)(r & 255u) << 40;
+}
+__device__ __forceinline__ unsigned wbyte(u64 w, int j) { return (unsigned)(w >> (8 * j)) & 255u; }
+
+// the four BGR triples of one output row of a wide lane from the windows of the raw rows above, at and below it
+__device__ __forceinline__ void row4(u64 up, u64 at, u64 dn, bool row_r, bool col0_r, unsigned px[4])
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i)          // pixel i sits at window byte i + 1; x0 % 4 == 0: its column parity is i & 1
+        px[i] = site_bgr(wbyte(up, i), wbyte(up, i + 1), wbyte(up, i + 2), wbyte(at, i), wbyte(at, i + 1), wbyte(at, i + 2),
+                         wbyte(dn, i), wbyte(dn, i + 1), wbyte(dn, i + 2), row_r, (i & 1) ? !col0_r : col0_r);
+}
+
+// 12 bytes as three dword stores, kept apart: merged into one dwordx3 they would be a wide store
+__device__ __forceinline__ void store4(uint8_t *d, const unsigned px[4])
+{
+    unsigned *q = (unsigned *)d;
+    q[0] = px[0] | px[1] << 24;
+    asm volatile("" ::: "memory");
+    q[1] = px[1] >> 8 | px[2] << 16;
+    asm volatile("" ::: "memory");
+    q[2] = px[2] >> 16 | px[3] << 8;
+}
+
+// grid: x = lanes over the (H + 1) / 2 x W / 4 blocks of one frame, y = stream of the launch, z = frame of the step
+__global__ __launch_bounds__(kDebayerWG) void k_debayer_wide(DebayerArgs a)
+{
+    const int H = a.H, W = a.W, bw = W >> 2;
+    const unsigned id = blockIdx.x * (unsigned)kDebayerWG + threadIdx.x;
+    const unsigned nblk = (unsigned)((H + 1) >> 1) * (unsigned)bw;
+    if (id >= nblk) return;
+    const int ty = (int)(id / (unsigned)bw), tx = (int)(id - (unsigned)ty * (unsigned)bw);
+    const int y0 = ty * 2, x0 = tx * 4;
+    const int s = a.first_stream + (int)blockIdx.y;
+    const bool r_row = (a.r_row >> blockIdx.y) & 1ull, r_col = (a.r_col >> blockIdx.y) & 1ull;      // uniform
+    const size_t npx = (size_t)H * W;
+    const uint8_t *in = (blockIdx.z ? a.in[1] : a.in[0]) + (size_t)s * npx;
+    uint8_t *out = (blockIdx.z ? a.out[1] : a.out[0]) + (size_t)s * npx * 3;
+
+    // the rows whose triples the lane's two output rows take (the same row twice at the top and bottom edges)
+    const int ya = min(max(y0, 1), H - 2), yb = min(max(y0 + 1, 1), H - 2);
+    const int xl = x0 > 0 ? x0 - 4 : x0, xr = x0 + 4 < W ? x0 + 4 : x0;     // clamped: the values they give are not used
+    u64 w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint8_t *row = in + (size_t)min(ya - 1 + k, H - 1) * W;
+        w[k] = window(*(const unsigned *)(row + xl), *(const unsigned *)(row + x0), *(const unsigned *)(row + xr));
+    }
+    const bool col0_r = r_col == false;                  // x0 is even: column x0 holds R samples iff the R column parity is 0
+    unsigned pa[4], pb[4];
+    row4(w[0], w[1], w[2], ((ya & 1) != 0) == r_row, col0_r, pa);
+    row4(w[1], w[2], w[3], (((ya + 1) & 1) != 0) == r_row, col0_r, pb);
+    if (yb == ya) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pb[i] = pa[i];
+    }
+    if (x0 == 0) { pa[0] = pa[1]; pb[0] = pb[1]; }       // first and last column: the neighbour's triple
+    if (x0 + 4 == W) { pa[3] = pa[2]; pb[3] = pb[2]; }
+    store4(out + ((size_t)y0 * W + x0) * 3, pa);
+    if (y0 + 1 < H) store4(out + ((size_t)(y0 + 1) * W + x0) * 3, pb);
+}
+
+// grid: x = pixels of one frame, y = stream of the launch, z = frame of the step
+__global__ __launch_bounds__(kDebayerWG) void k_debayer_narrow(DebayerArgs a)
+{
+    const int H = a.H, W = a.W;
+    const size_t npx = (size_t)H * W;
+    const size_t p = (size_t)blockIdx.x * kDebayerWG + threadIdx.x;
+    if (p >= npx) return;
+    const int y = (int)(p / (size_t)W), x = (int)(p - (size_t)y * W);
+    const int s = a.first_stream + (int)blockIdx.y;
+    const bool r_row = (a.r_row >> blockIdx.y) & 1ull, r_col = (a.r_col >> blockIdx.y) & 1ull;
+    const uint8_t *in = (blockIdx.z ? a.in[1] : a.in[0]) + (size_t)s * npx;
+    uint8_t *out = (blockIdx.z ? a.out[1] : a.out[0]) + (size_t)s * npx * 3;
+    const int cy = min(max(y, 1), H - 2), cx = min(max(x, 1), W - 2);
+    const uint8_t *r0 = in + (size_t)(cy - 1) * W + cx, *r1 = r0 + W, *r2 = r1 + W;
+    const unsigned v = site_bgr(r0[-1], r0[0], r0[1], r1[-1], r1[0], r1[1], r2[-1], r2[0], r2[1], ((cy & 1) != 0) == r_row,
+                                ((cx & 1) != 0) == r_col);
+    uint8_t *d = out + p * 3;
+    d[0] = (uint8_t)v; d[1] = (uint8_t)(v >> 8); d[2] = (uint8_t)(v >> 16);
+}
+
+}  // namespace
+
+bool debayer_is_wide(int W, const uint8_t *const *in, uint8_t *const *out, int n_frames)
+{
+    uintptr_t m = 0;
+    for (int i = 0; i < n_frames; ++i) m |= (uintptr_t)in[i] | (uintptr_t)out[i];
+    return W % 4 == 0 && (m & 3u) == 0;
+}
+
+// patterns[n_streams]: OATGPU_BAYER_* values 1..4 (checked by the caller); H, W >= 3
+void launch_debayer_frames(const uint8_t *const *in, uint8_t *const *out, int n_frames, const int *patterns, int H, int W,
+                           int n_streams, hipStream_t st)
+{
+    const bool wide = debayer_is_wide(W, in, out, n_frames);
+    const size_t lanes = wide ? (size_t)((H + 1) / 2) * (size_t)(W / 4) : (size_t)H * W;
+    const unsigned gx = (unsigned)((lanes + kDebayerWG - 1) / kDebayerWG);
+    for (int s0 = 0; s0 < n_streams; s0 += 64) {         // the parity bits of a launch are two 64-bit kernel arguments
+        const int n = n_streams - s0 < 64 ? n_streams - s0 : 64;
+        DebayerArgs a{};
+        for (int i = 0; i < 2; ++i) {
+            a.in[i] = in[i < n_frames ? i : 0];
+            a.out[i] = out[i < n_frames ? i : 0];
+        }
+        a.H = H; a.W = W; a.first_stream = s0;
+        for (int i = 0; i < n; ++i) {
+            // R sits at (row, column) parity: RGGB (0, 0), BGGR (1, 1), GRBG (0, 1), GBRG (1, 0)
+            const int p = patterns[s0 + i];
+            a.r_row |= (u64)(p == 2 || p == 4) << i;
+            a.r_col |= (u64)(p == 2 || p == 3) << i;
+        }
+        const dim3 grid(gx, (unsigned)n, (unsigned)n_frames);
+        if (wide) hipLaunchKernelGGL(k_debayer_wide, grid, dim3(kDebayerWG), 0, st, a);
+        else hipLaunchKernelGGL(k_debayer_narrow, grid, dim3(kDebayerWG), 0, st, a);
+    }
+}
+
+}  // namespace oatgpu

@@ -276,6 +276,10 @@ struct oatgpu_ctx {
     bool ud_track = false;         // oatgpu_set_track_undistort: the fused track calls remap every frame first (launch_front)
     DevMem<uint8_t> ud_frames[2];  // [2][n][H*W*ch] the remapped frames of a step (frame i of a two-frame step in buffer i): K1
                                    //   reads them in place of the caller's; allocated by oatgpu_set_track_undistort(1)
+    bool by_track = false;         // oatgpu_set_track_bayer: the fused track calls take Bayer RAW8 frames and demosaic them first (launch_front)
+    std::vector<int> by_pat;       // [n] OATGPU_BAYER_* of every camera stream while by_track
+    DevMem<uint8_t> by_frames[2];  // [2][n][H*W*3] the demosaiced frames of a step (ud_frames' lifetime rule): the remap, or K1, reads
+                                   //   them in place of the caller's; allocated by oatgpu_set_track_bayer
     DevMem<u64> thr;               // [ring_slots][n][Palloc/64] the ring's threshold buffers (BlobBuffers::thr of every scratch set)
     Scratch bb[kSets];             // scratch sets, all made with the context
     const u64 *last_morph = nullptr;
@@ -394,6 +398,14 @@ static inline RangeParams range_of(const oatgpu_marker &k)
     norm_range(k.s_lo, k.s_hi, r.lo[1], r.hi[1]);
     norm_range(k.v_lo, k.v_hi, r.lo[2], r.hi[2]);
     return r;
+}
+
+// bytes of one camera's frame as the fused track calls take it: RAW8 with oatgpu_set_track_bayer on
+static inline size_t track_in_bytes(const oatgpu_ctx *c) { return (size_t)c->g.H * c->g.W * (c->by_track ? 1 : c->cfg.channels); }
+// frame i of the step as K1 and the marker kernels see it: remapped, demosaiced, or the caller's own
+static inline const uint8_t *step_frame(const oatgpu_ctx *c, int i, const void *given)
+{
+    return c->ud_track ? (const uint8_t *)c->ud_frames[i] : c->by_track ? (const uint8_t *)c->by_frames[i] : (const uint8_t *)given;
 }
 
 // ring slot of the next frame to be enqueued / collected

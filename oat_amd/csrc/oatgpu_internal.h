@@ -202,6 +202,13 @@ void launch_undistort(const uint8_t *in, uint8_t *out, const uint32_t *map1, con
 void launch_undistort_frames(const uint8_t *const *in, uint8_t *const *out, int n_frames, const uint32_t *map1,
                              const uint16_t *map2, size_t map_stride, int H, int W, int channels, int n_streams, hipStream_t st);
 
+// --- kernels_debayer.hip --- (Bayer RAW8 -> BGR)
+// n_frames (1 or 2) sets of n_streams raw frames (stream-major, H*W bytes each), set i from in[i] into out[i] (H*W*3 bytes a
+// stream), stream s with patterns[s] (OATGPU_BAYER_* 1..4, checked by the caller); H, W >= 3.  One launch per 64 streams.
+bool debayer_is_wide(int W, const uint8_t *const *in, uint8_t *const *out, int n_frames);
+void launch_debayer_frames(const uint8_t *const *in, uint8_t *const *out, int n_frames, const int *patterns, int H, int W,
+                           int n_streams, hipStream_t st);
+
 // --- kernels_blob.hip ---
 struct BlobBuffers {
     u64 *thr;        // [2][n][Palloc/64] inRange output, double-buffered across frames

@@ -90,6 +90,7 @@ E_RING_FULL = -4
 E_RING_EMPTY = -5
 ABI_VERSION = 9          # must equal OATGPU_ABI_VERSION of include/oatgpu.h
 TAP_THRESHOLD, TAP_MORPH, TAP_FINAL = 0, 1, 2
+BAYER_RGGB, BAYER_BGGR, BAYER_GRBG, BAYER_GBRG = 1, 2, 3, 4      # OATGPU_BAYER_*: the tile at rows 0-1, columns 0-1
 
 _u8p = C.POINTER(C.c_uint8)
 _fp = C.POINTER(C.c_float)
@@ -125,6 +126,9 @@ SIGNATURES = {
     "oatgpu_undistort_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p]),
     "oatgpu_undistort_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
     "oatgpu_set_track_undistort": (C.c_int, [_ctx, C.c_int32]),
+    "oatgpu_debayer_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p]),
+    "oatgpu_debayer_dev": (C.c_int, [_ctx, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p]),
+    "oatgpu_set_track_bayer": (C.c_int, [_ctx, C.POINTER(C.c_int32), C.c_int32]),
     "oatgpu_set_markers": (C.c_int, [_ctx, C.c_int32, C.POINTER(Marker), C.c_int32]),
     "oatgpu_set_marker_window": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.POINTER(Marker)]),
     "oatgpu_track_markers_dev": (C.c_int, [_ctx, C.c_void_p, C.c_double, C.POINTER(Position), C.POINTER(Position),

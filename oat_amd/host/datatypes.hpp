@@ -49,6 +49,16 @@ inline PixelColor str_color(const std::string &s)
     throw std::runtime_error("Invalid color.");
 }
 
+// A Bayer pattern by the 2 x 2 tile at image rows 0-1, columns 0-1 (the camera vendors' names) -> OATGPU_BAYER_* (oatgpu.h)
+inline int bayer_pattern(const std::string &s)
+{
+    if (s == "RGGB") return 1;
+    if (s == "BGGR") return 2;
+    if (s == "GRBG") return 3;
+    if (s == "GBRG") return 4;
+    throw std::runtime_error("Invalid Bayer pattern '" + s + "': RGGB, BGGR, GRBG or GBRG.");
+}
+
 // lib/datatypes/Sample.h:35-123
 class Sample {
 public:

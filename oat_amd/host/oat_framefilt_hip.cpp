@@ -4,6 +4,7 @@
 //         bsub  MI355X replacement of `oat framefilt bsub` (src/framefilter/BackgroundSubtractor.cpp)
 //         thresh MI355X replacement of `oat framefilt thresh` (src/framefilter/Threshold.cpp)
 //         undistort MI355X replacement of `oat framefilt undistort` (src/framefilter/Undistorter.cpp)
+//         debayer Bayer RAW8 -> BGR, the reference's frame-server conversion (src/frameserver/PointGreyCam.cpp:48-50, :729) as a component
 // Drop-in: same positional arguments, same option names (src/framefilter/main.cpp:91-296).
 #include "component.hpp"
 #include <unistd.h>
@@ -216,12 +217,53 @@ protected:
     GpuCtx gpu_;
 };
 
+// The pixel-format conversion of the reference's colour cameras (PointGreyCam.cpp:48-50: RAW8 -> BGR, :729 Convert) as a
+// component: SOURCE carries the sensor's samples as a GREY-tagged CV_8UC1 frame (oat::PixelColor has no Bayer value), SINK is BGR.
+class Debayer : public FrameFilter {
+public:
+    using FrameFilter::FrameFilter;
+    int pattern_{OATGPU_BAYER_RGGB};
+    int gpu_index_{0};
+
+protected:
+    PixelColor sink_color(PixelColor in) const override
+    {
+        if (in != PIX_GREY) throw std::runtime_error(std::string("framefilt debayer takes GREY-tagged RAW8 frames, SOURCE carries ") + color_str(in));
+        return PIX_BGR;
+    }
+    void configure_for(const FrameParams &p) override
+    {
+        oatgpu_config cfg;
+        oatgpu_default_config(&cfg);
+        cfg.device = gpu_index_; cfg.rows = (int)p.rows; cfg.cols = (int)p.cols;
+        sink_color(p.color);                             // (refused before a device is opened)
+        gpu_.create(cfg);
+    }
+    // Not in place: the two sides differ in bytes per pixel.
+    void filter(Frame &frame) override
+    {
+        Frame out(frame.rows(), frame.cols(), PIX_BGR);
+        gpu_.check(oatgpu_debayer_filter(gpu_.ctx, pattern_, frame.data(), out.data()));
+        out.sample() = frame.sample();
+        frame = std::move(out);
+    }
+    bool filter_from_shm(const Frame &in, Frame &out) override
+    {
+        gpu_.check(oatgpu_debayer_filter(gpu_.ctx, pattern_, in.data(), out.data()));
+        out.set_color(PIX_BGR);
+        return true;
+    }
+    oatgpu_ctx *deferred_ctx() override { return gpu_.ctx; }
+    GpuCtx gpu_;
+};
+
 static void usage()
 {
     std::cout << "Usage: oat-framefilt-hip TYPE SOURCE SINK [CONFIGURATION]\n"
                  "TYPE\n  mog: MOG2 background segmentation on an MI355X\n  col: colour conversion (BGR -> HSV | GREY, GREY -> BGR, HSV -> BGR) on an MI355X\n"
                  "  bsub | thresh | mask: the other per-pixel filters of oat-framefilt\n"
                  "  undistort: lens-distortion correction (cv::undistort) on an MI355X\n"
+                 "  debayer: Bayer RAW8 (a GREY-tagged frame, as `oat-frameserve-raw -C GREY` serves) -> BGR on an MI355X\n"
                  "all:  --gpu-index N           HIP device ordinal (default 0)\n"
                  "mog:  -a, --adaptation-coeff  0..1, default 0 (no adaptation)\n"
                  "      --model-file FILE    resume the background model from FILE if it exists; checkpoint it there on exit\n"
@@ -231,7 +273,8 @@ static void usage()
                  "mask: -f, --mask FILE         PGM/PPM: pixels where it is 0 are set to 0\n"
                  "thresh: -I, --intensity       [min,max] in [0,256]\n"
                  "undistort: -k, --camera-matrix [K11,K12,...,K33] (required)\n"
-                 "      -d, --distortion-coeffs [k1,k2,p1,p2,k3] or [k1,k2,p1,p2,k3,k4,k5,k6] (required)\n";
+                 "      -d, --distortion-coeffs [k1,k2,p1,p2,k3] or [k1,k2,p1,p2,k3,k4,k5,k6] (required)\n"
+                 "debayer: --pattern RGGB | BGGR | GRBG | GBRG   the 2 x 2 tile at image rows 0-1, columns 0-1 (required)\n";
 }
 
 int main(int argc, char **argv)
@@ -253,6 +296,7 @@ int main(int argc, char **argv)
         else if (type == "thresh") o.apply_config({"intensity", "gpu-index"});
         else if (type == "mask") o.apply_config({"mask", "gpu-index"});
         else if (type == "undistort") o.apply_config({"camera-matrix", "distortion-coeffs", "gpu-index"});   // Undistorter.cpp:43-53
+        else if (type == "debayer") o.apply_config({"pattern", "gpu-index"});
         const int gpu_index = (int)o.num("gpu-index", 0, 0, 64);
         std::unique_ptr<Component> comp;
         if (type == "mog") {
@@ -294,6 +338,12 @@ int main(int argc, char **argv)
             const UndistortCalibration cal = read_undistort_calibration(o);
             std::copy(cal.K, cal.K + 9, f->camera_matrix_);
             f->dist_coeff_ = cal.dist;
+            f->gpu_index_ = gpu_index;
+            comp = std::move(f);
+        } else if (type == "debayer") {
+            auto f = std::make_unique<Debayer>(o.positional[1], o.positional[2]);
+            if (!o.has("pattern")) throw std::runtime_error("Required configuration value 'pattern' was not specified.");
+            f->pattern_ = bayer_pattern(o.kv["pattern"]);
             f->gpu_index_ = gpu_index;
             comp = std::move(f);
         } else {

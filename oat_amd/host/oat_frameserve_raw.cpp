@@ -17,7 +17,8 @@ int main(int argc, char **argv)
     try {
         Options o = Options::parse(argc, argv, {{"f", "file"}, {"n", "num-frames"}, {"r", "fps"}, {"C", "color"}, {"h", "help"}}, {"help"});
         if (o.has("help") || o.positional.size() != 1 || !o.has("file") || !o.has("rows") || !o.has("cols")) {
-            std::cout << "Usage: oat-frameserve-raw SINK -f FILE --rows R --cols C [-C BGR|GREY|HSV] [-n N] [-r fps]\n";
+            std::cout << "Usage: oat-frameserve-raw SINK -f FILE --rows R --cols C [-C BGR|GREY|HSV] [-n N] [-r fps]\n"
+                         "-C GREY also serves Bayer RAW8 frames (one byte a pixel) for `oat-framefilt-hip debayer` and `oat-track-hip --bayer`.\n";
             return o.has("help") ? 0 : -1;
         }
         std::signal(SIGINT, sigHandler);

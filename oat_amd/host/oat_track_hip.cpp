@@ -327,6 +327,7 @@ public:
     bool homography_on_{false};     // --homography: `posifilt homography` behind the detector / the position filter
     double homography_[9]{1, 0, 0, 0, 1, 0, 0, 0, 1};
     std::vector<UndistortCalibration> undistort_;   // one per camera of this shard: `framefilt undistort` fused in front (empty: off)
+    std::vector<int32_t> bayer_;    // --bayer: one OATGPU_BAYER_* per camera of this shard; the SOURCEs carry RAW8 (GREY-tagged) frames
     // marker sets (--marker, repeatable): M `posidet hsv` detectors per camera behind the one model pass and `posicom mean`
     // behind them; marker m of camera s is published on marker_sink_addresses_[s][m], the combined position on SINK s
     std::vector<oatgpu_marker> markers_;
@@ -395,7 +396,7 @@ protected:
         for (int s = 0; s < n_; ++s) frame_sources_[s].touch(source_addresses_[s]);
         FrameParams p0{};
         for (int s = 0; s < n_; ++s) {
-            if (frame_sources_[s].connect(grey_ ? PIX_GREY : PIX_BGR) != SourceState::CONNECTED) return false;
+            if (frame_sources_[s].connect(grey_ || !bayer_.empty() ? PIX_GREY : PIX_BGR) != SourceState::CONNECTED) return false;
             const FrameParams p = frame_sources_[s].parameters();
             if (s == 0) p0 = p;
             else if (p.rows != p0.rows || p.cols != p0.cols)
@@ -405,6 +406,7 @@ protected:
         cfg_.channels = grey_ ? 1 : 3;
         if (cfg_.ring_depth < 2) cfg_.ring_depth = 2;
         gpu_.create(cfg_);
+        if (!bayer_.empty()) gpu_.check(oatgpu_set_track_bayer(gpu_.ctx, bayer_.data(), n_));
         if (!undistort_.empty()) {
             for (int s = 0; s < n_; ++s)
                 gpu_.check(oatgpu_set_undistort(gpu_.ctx, s, undistort_[s].K, undistort_[s].dist.data(), (int32_t)undistort_[s].dist.size()));
@@ -679,6 +681,9 @@ int main(int argc, char **argv)
             std::cout << "Usage: oat-track-hip SOURCE[,SOURCE..] SINK[,SINK..] [-a coeff] [-H [lo,hi]] [-S ..] [-V ..] [-e n] [-d n] [--area [min,max]]\n"
                          "       [--gpu-index N | N0,N1,..] [--ring D] [--model-file FILE] [-f|--mask FILE.pgm] [--stage-copy dma|kernel]\n"
                          "       [--thresh [lo,hi]]   GREY SOURCEs: framefilt mog -> posidet thresh instead of the HSV chain\n"
+                         "       [--bayer P | P0,P1,..]  the SOURCEs carry Bayer RAW8 frames (GREY-tagged, as `oat-frameserve-raw -C GREY` serves): they\n"
+                         "                            are demosaiced on the device in front of the chain; P = RGGB | BGGR | GRBG | GBRG, the 2 x 2 tile\n"
+                         "                            at image rows 0-1, columns 0-1 -- one for all cameras or one per SOURCE.  Not with --thresh.\n"
                          "       [--homography [h11,h12,...,h33]]   posifilt homography fused in (positions in world units)\n"
                          "       [--kalman [--dt s] [-T|--timeout s] [--sigma-accel a] [-n|--sigma-noise n]]   (posifilt kalman fused in)\n"
                          "       [--camera-matrix [K11,...,K33] --distortion-coeffs [k1,k2,p1,p2,k3(,k4,k5,k6)] | --undistort-key T0[,T1,..]]\n"
@@ -717,7 +722,7 @@ int main(int argc, char **argv)
         o.apply_config({"adaptation-coeff", "h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "model-file",
                         "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "gpu-index", "ring", "mask", "thresh", "homography", "stage-copy", "timing",
                         "ingest-root", "print-partition", "camera-matrix", "distortion-coeffs", "undistort-key", "marker-sinks", "heading-anchor", "marker-ring",
-                        "mean-kalman", "mean-homography"},
+                        "mean-kalman", "mean-homography", "bayer"},
                        {"kalman", "timing", "print-partition", "mean-kalman"});
         const std::vector<std::string> sources = split_list(o.positional[0]), sinks = split_list(o.positional[1]);
         if (sources.size() != sinks.size()) throw std::runtime_error("need as many SINKs as SOURCEs");
@@ -834,6 +839,16 @@ int main(int argc, char **argv)
         } else if (o.has("camera-matrix") || o.has("distortion-coeffs")) {
             cals.assign(sources.size(), read_undistort_calibration(o));
         }
+        // --bayer: the SOURCEs' pixel format, one pattern for all cameras or one per SOURCE; checked before any device is opened
+        std::vector<int32_t> bayer;
+        if (o.has("bayer")) {
+            if (o.has("thresh")) throw std::runtime_error("--bayer does not go with --thresh: demosaiced frames are BGR, --thresh selects the GREY chain");
+            for (const std::string &p : split_list(o.kv["bayer"])) bayer.push_back(bayer_pattern(p));
+            if (bayer.size() != 1 && bayer.size() != sources.size())
+                throw std::runtime_error("--bayer: " + std::to_string(bayer.size()) + " patterns for " + std::to_string(sources.size()) +
+                                         " SOURCEs (give one for every camera or one per SOURCE)");
+            if (bayer.size() == 1) bayer.assign(sources.size(), bayer[0]);
+        }
         if (o.has("ingest-root")) {                                       // the stream-to-rank scatter over RCCL (scatter_tracker.hpp)
             for (const char *k : {"kalman", "thresh", "mask", "model-file", "homography", "stage-copy"})
                 if (o.has(k)) throw std::runtime_error(std::string("--ingest-root does not take --") + k);
@@ -849,6 +864,7 @@ int main(int argc, char **argv)
             t.cfg_.ring_depth = (int)o.num("ring", 2, 2, 64);
             t.timing_ = o.has("timing");
             t.undistort_ = cals;
+            t.bayer_ = bayer;
             return t.run();
         }
         const int S = (int)sources.size(), N = (int)devices.size(), per = (S + N - 1) / N;
@@ -883,6 +899,7 @@ int main(int argc, char **argv)
             t->kalman_ = o.has("kalman");
             t->homography_on_ = o.arr9("homography", t->homography_);
             if (!cals.empty()) t->undistort_.assign(cals.begin() + s0, cals.begin() + s1);
+            if (!bayer.empty()) t->bayer_.assign(bayer.begin() + s0, bayer.begin() + s1);
             if (!markers.empty())
                 t->set_markers(markers, heading_anchor, std::vector<std::vector<std::string>>(marker_sinks.begin() + s0, marker_sinks.begin() + s1));
             t->dt_ = o.num("dt", 0.02, 0, 1e9);                        // KalmanFilter2D.cpp:69-85 (lower bound 0)

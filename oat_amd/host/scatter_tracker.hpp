@@ -86,6 +86,8 @@ public:
     double learning_coeff_{0.0};
     bool timing_{false};
     std::vector<UndistortCalibration> undistort_;   // one per SOURCE: `framefilt undistort` fused in front (empty: off)
+    std::vector<int32_t> bayer_;                    // one OATGPU_BAYER_* per SOURCE: the SOURCEs carry RAW8 (GREY-tagged) frames, the
+                                                    // scatter moves those and every shard demosaics its own (empty: BGR SOURCEs)
 
     void print_timing() const
     {
@@ -122,13 +124,13 @@ protected:
         for (int s = 0; s < S_; ++s) frame_sources_[s].touch(source_addresses_[s]);
         FrameParams p0{};
         for (int s = 0; s < S_; ++s) {
-            if (frame_sources_[s].connect(PIX_BGR) != SourceState::CONNECTED) return false;
+            if (frame_sources_[s].connect(bayer_.empty() ? PIX_BGR : PIX_GREY) != SourceState::CONNECTED) return false;
             const FrameParams p = frame_sources_[s].parameters();
             if (s == 0) p0 = p;
             else if (p.rows != p0.rows || p.cols != p0.cols)
                 throw std::runtime_error("all SOURCEs of one scatter tracker must have the same frame geometry");
         }
-        frame_bytes_ = (size_t)p0.rows * p0.cols * 3;
+        frame_bytes_ = (size_t)p0.rows * p0.cols * (bayer_.empty() ? 3 : 1);
         // ---- the communicators: one rank per listed device, this process owns them all ----
         comm_.assign(N_, nullptr);
         OAT_NCCL(ncclCommInitAll(comm_.data(), N_, devices_.data()));
@@ -159,6 +161,7 @@ protected:
             if (c.ring_depth < 2) c.ring_depth = 2;
             gpu_.push_back(std::make_unique<GpuCtx>());
             gpu_.back()->create(c);
+            if (!bayer_.empty()) gpu_.back()->check(oatgpu_set_track_bayer(gpu_.back()->ctx, bayer_.data() + block_begin(k), c.n_streams));
             if (!undistort_.empty()) {                         // each shard's context gets its own cameras' maps
                 GpuCtx &g = *gpu_.back();
                 for (int i = 0; i < c.n_streams; ++i) {
