@@ -48,7 +48,7 @@ extern "C" {
  * oatgpu_diff_sequence_dev, oatgpu_read_diff_mask; the subtraction tracker -- oatgpu_set_bsub_tracker, oatgpu_bsub_reset,
  * oatgpu_bsub_track_batch_dev, oatgpu_bsub_track_batch, oatgpu_bsub_track_sequence_dev, oatgpu_bsub_get_state,
  * oatgpu_read_bsub_mask; Bayer RAW8 ingest -- oatgpu_debayer_filter, oatgpu_debayer_dev, oatgpu_set_track_bayer, with the
- * OATGPU_BAYER_* pattern values. */
+ * OATGPU_BAYER_* pattern values; RAW8 frames for the motion and the subtraction tracker -- oatgpu_set_tracker_bayer. */
 
 enum {
     OATGPU_OK = 0,
@@ -350,8 +350,23 @@ int oatgpu_debayer_dev(oatgpu_ctx *ctx, const int32_t *patterns, int32_t n_patte
  * bytes) the first time: an out-of-memory is reported here, never in the middle of a step.  Refused (OATGPU_E_INVALID)
  * before anything has moved: channels != 3, a pattern outside 1..4, n_patterns neither 1 nor n_streams, frames smaller than
  * 3 x 3, a partly staged frame set.  While it is on the diff and bsub tracker calls are refused; the stage-by-stage calls
- * never look at it; with it off nothing changes.  oatgpu_track_input_consumed[_stream] keep their rules. */
+ * never look at it; with it off nothing changes.  oatgpu_track_input_consumed[_stream] keep their rules.  RAW8 frames for
+ * the diff and bsub trackers are a switch of their own: oatgpu_set_tracker_bayer below. */
 int oatgpu_set_track_bayer(oatgpu_ctx *ctx, const int32_t *patterns, int32_t n_patterns);
+/* Bayer RAW8 frames for the motion and the subtraction tracker of the context (default off; NULL / 0 turns it off).  While
+ * on, oatgpu_diff_batch, _batch_dev, oatgpu_diff_sequence_dev, oatgpu_bsub_track_batch, _batch_dev and
+ * oatgpu_bsub_track_sequence_dev take RAW8 frames -- rows*cols bytes a stream for host frames (that many bytes are
+ * uploaded), n_streams*rows*cols stream-major for device frames.  n_patterns is 1 (one pattern for all) or n_streams.  The
+ * chain is demosaic -> ROI mask -> (col GREY -> diff) or (bsub -> col HSV -> window): the front kernel demosaics its pixels
+ * in registers with exactly the arithmetic above, no BGR frame is written, and the ROI falls on the demosaiced pixel.
+ * Results, taps and state are bit-identical to oatgpu_debayer_dev followed by the BGR call.  The state -- the last grey
+ * image, the BGR background and its fp32 accumulator -- stays in the demosaiced domain and shared with oatgpu_detect_diff,
+ * oatgpu_bsub_filter, oatgpu_bsub_set_background (a BGR image) and oatgpu_bsub_get_state, which never look at the switch;
+ * turning it on or off between steps keeps the state: a stream fed RAW8 on one step and BGR on the next continues as one
+ * stream.  Refused (OATGPU_E_INVALID) with nothing changed: channels != 3, a pattern outside 1..4, n_patterns neither 1
+ * nor n_streams, frames smaller than 3 x 3, results outstanding, a partly staged frame set.  Independent of
+ * oatgpu_set_track_bayer: while THAT is on the diff and bsub calls stay refused.  With it off nothing changes. */
+int oatgpu_set_tracker_bayer(oatgpu_ctx *ctx, const int32_t *patterns, int32_t n_patterns);
 
 /* ---- marker sets: several colour windows per camera behind ONE MOG2 pass, `posicom mean` behind them ----
  *

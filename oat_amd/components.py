@@ -428,16 +428,41 @@ class DifferenceDetector(_Detector):
         return _merge(position, p)
 
 
-class MotionTracker(_Detector):
+def _packed_shape(ctx):
+    """A BGR / GREY frame of the context, whatever its track calls take at the moment."""
+    return (ctx.rows, ctx.cols, 3) if ctx.channels == 3 else (ctx.rows, ctx.cols)
+
+
+class _TrackerBayer:
+    """oatgpu_set_tracker_bayer for the batched trackers (mirrors HotPath.bayer)."""
+
+    def bayer(self, patterns):
+        """oatgpu_set_tracker_bayer: track, track_dev and track_sequence_dev take Bayer RAW8 frames (rows, cols) and the front
+        kernel demosaics them in registers; the state stays in the demosaiced domain.  patterns: a name ("RGGB") or value for
+        every stream, a list of n_streams of them, or None to switch it off (frames are BGR again)."""
+        if patterns is None:
+            self._chk(self.lib.oatgpu_set_tracker_bayer(self.ctx, None, 0))
+            self.frame_shape = _packed_shape(self)
+            return
+        arr, n = _bayer_patterns(patterns)
+        self._chk(self.lib.oatgpu_set_tracker_bayer(self.ctx, arr, n))
+        self.frame_shape = (self.rows, self.cols)
+
+
+class MotionTracker(_Detector, _TrackerBayer):
     """The batched motion tracker: `framefilt col -C GREY` -> `posidet diff` for N camera streams, one front launch a step
     (oatgpu_set_diff_tracker).  channels = 3: BGR frames (rows, cols, 3); 1: GREY frames (rows, cols).  Options follow
-    DifferenceDetector.cpp:47-64 (-d diff-threshold, -b blur, -a area).  A ROI (set_roi_mask) masks the frame first."""
+    DifferenceDetector.cpp:47-64 (-d diff-threshold, -b blur, -a area).  A ROI (set_roi_mask) masks the frame first.
+    bayer: Bayer RAW8 frames (rows, cols) of a BGR tracker, see bayer()."""
 
-    def __init__(self, rows, cols, n_streams=1, channels=3, diff_threshold=10, blur=2, area=(0.0, DBL_MAX), device=0, **kw):
+    def __init__(self, rows, cols, n_streams=1, channels=3, diff_threshold=10, blur=2, area=(0.0, DBL_MAX), device=0, bayer=None,
+                 **kw):
         super().__init__(rows, cols, n_streams=n_streams, channels=channels, diff_threshold=diff_threshold, blur=blur,
                          erode=0, dilate=0, min_area=area[0], max_area=area[1], device=device, **kw)
         self._pos = (ffi.Position * n_streams)()
         self._chk(self.lib.oatgpu_set_diff_tracker(self.ctx, 1))
+        if bayer is not None:
+            self.bayer(bayer)
 
     def _out(self):
         return [Position2D.from_c(p) for p in self._pos]
@@ -474,14 +499,15 @@ class MotionTracker(_Detector):
         return out
 
 
-class SubtractionTracker(_Detector):
+class SubtractionTracker(_Detector, _TrackerBayer):
     """The batched subtraction tracker: `framefilt bsub` -> `framefilt col -C HSV` -> `posidet hsv` for N camera streams, one front
     launch a step (oatgpu_set_bsub_tracker).  channels = 3: BGR frames (rows, cols, 3) and the h / s / v window on the difference
     image; 1: GREY frames (rows, cols), `framefilt bsub` -> `posidet thresh` with `thresh`.  alpha is bsub's -a (0: the background
-    stays the first frame); erode / dilate / area as HSVDetector.cpp:49-75.  A ROI (set_roi_mask) masks the frame first."""
+    stays the first frame); erode / dilate / area as HSVDetector.cpp:49-75.  A ROI (set_roi_mask) masks the frame first.
+    bayer: Bayer RAW8 frames (rows, cols) of a BGR tracker, see bayer(); the background and its state stay BGR."""
 
     def __init__(self, rows, cols, n_streams=1, channels=3, alpha=0.0, h_thresh=(0, 256), s_thresh=(0, 256), v_thresh=(0, 256),
-                 thresh=None, erode=0, dilate=10, area=(0.0, DBL_MAX), device=0, **kw):
+                 thresh=None, erode=0, dilate=10, area=(0.0, DBL_MAX), device=0, bayer=None, **kw):
         if thresh is not None:
             h_thresh = thresh
         super().__init__(rows, cols, n_streams=n_streams, channels=channels, h_lo=h_thresh[0], h_hi=h_thresh[1], s_lo=s_thresh[0],
@@ -490,6 +516,8 @@ class SubtractionTracker(_Detector):
         self.alpha_ = float(alpha)
         self._pos = (ffi.Position * n_streams)()
         self._chk(self.lib.oatgpu_set_bsub_tracker(self.ctx, 1))
+        if bayer is not None:
+            self.bayer(bayer)
 
     def _alpha(self, alpha):
         return float(getattr(self, "alpha_", 0.0) if alpha is None else alpha)
@@ -523,13 +551,13 @@ class SubtractionTracker(_Detector):
 
     def set_background(self, image, stream=0):
         """`framefilt bsub -f FILE`: the background of one stream from an image; it cannot adapt (oatgpu_bsub_set_background)."""
-        im = _frame(image, self.frame_shape)
+        im = _frame(image, _packed_shape(self))
         self._chk(self.lib.oatgpu_bsub_set_background(self.ctx, int(stream), ffi.u8(im)))
 
     def state(self, stream=0, acc=True):
         """(background uint8, accumulator float32 or None) of one stream as it stands (oatgpu_bsub_get_state)."""
-        bg = np.empty(self.frame_shape, np.uint8)
-        f = np.empty(self.frame_shape, np.float32) if acc else None
+        bg = np.empty(_packed_shape(self), np.uint8)
+        f = np.empty(_packed_shape(self), np.float32) if acc else None
         self._chk(self.lib.oatgpu_bsub_get_state(self.ctx, int(stream), ffi.u8(bg), ffi.f32(f) if acc else None))
         return bg, f
 

@@ -78,6 +78,7 @@ static int bsub_front(oatgpu_ctx *c, const void *f1, const void *f2, double alph
     a.bg = c->bsub_bg; a.acc = c->bsub_f; a.have = c->bsub_have.data();
     a.bits = bsub_bits(c, slot); a.bits2 = f2 ? bsub_bits(c, slot2) : nullptr;
     a.roi = c->roi; a.rp = range_of(detector_of(c->cfg));
+    a.bayer = tracker_bayer(c);
     a.learn = alpha > 0.0; a.a = (float)alpha; a.b = 1 - a.a;        // accW_: AT a = (AT)alpha, b = 1 - a
     launch_bsubtrack_front(c->g, a, c->cfg.n_streams, c->stream);
     HIPCHK(c, hipGetLastError());
@@ -143,7 +144,7 @@ extern "C" int oatgpu_bsub_track_batch(oatgpu_ctx *c, const uint8_t *const *fram
     if (rc) return rc;
     rc = open_sync(c);
     if (rc) return rc;
-    rc = upload_frames(c, frames_host);
+    rc = upload_frames(c, frames_host, tracker_in_bytes(c));
     if (rc) return rc;
     return bsub_step(c, c->frames, alpha, out);
 }

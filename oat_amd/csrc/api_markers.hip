@@ -366,7 +366,7 @@ extern "C" int oatgpu_track_markers(oatgpu_ctx *c, const uint8_t *const *frames_
     { const int rrc = marker_step_refusals(c); if (rrc) return rrc; }           // (before the staging buffer is written)
     for (int s = 0; s < n; ++s) if (!frames_host[s]) return fail(c, OATGPU_E_INVALID, "null frame %d", s);
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    { const int rc = upload_frames(c, frames_host); if (rc) return rc; }
+    { const int rc = upload_frames(c, frames_host, track_in_bytes(c)); if (rc) return rc; }
     return oatgpu_track_markers_dev(c, c->frames, lr, fg, markers, mean);
 }
 

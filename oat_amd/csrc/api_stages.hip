@@ -414,6 +414,28 @@ extern "C" int oatgpu_set_track_bayer(oatgpu_ctx *c, const int32_t *patterns, in
     return OATGPU_OK;
 }
 
+// The motion and the subtraction tracker on RAW8 frames (api_diff.hip, api_bsubtrack.hip): their front kernels demosaic in
+// registers, so the switch is the pattern table alone -- no buffer, and the trackers' state stays in the demosaiced domain.
+extern "C" int oatgpu_set_tracker_bayer(oatgpu_ctx *c, const int32_t *patterns, int32_t n_patterns)
+{
+    if (!c) return OATGPU_E_INVALID;
+    const bool on = patterns != nullptr || n_patterns != 0;
+    std::vector<int> pat;               // built aside: the context takes it when nothing was refused
+    if (on) {
+        if (c->cfg.channels != 3) return fail(c, OATGPU_E_INVALID, "Bayer frames need a BGR context (channels = 3, have %d)", c->cfg.channels);
+        const int rc = check_bayer_args(c, patterns, n_patterns);
+        if (rc) return rc;
+        pat.resize((size_t)c->cfg.n_streams);
+        for (int s = 0; s < c->cfg.n_streams; ++s) pat[(size_t)s] = patterns[n_patterns == 1 ? 0 : s];
+    }
+    if (c->ring_count) return fail(c, OATGPU_E_INVALID, "set_tracker_bayer while enqueued results are outstanding");
+    if (c->staged_count)
+        return fail(c, OATGPU_E_INVALID, "set_tracker_bayer while a frame set is being staged (oatgpu_track_stage): finish it with oatgpu_track_enqueue_staged or give it up");
+    c->tb_pat = std::move(pat);
+    c->tb_on = on;
+    return OATGPU_OK;
+}
+
 extern "C" int oatgpu_bgr2hsv(oatgpu_ctx *c, const uint8_t *bgr_in, uint8_t *hsv_out)
 {
     if (!c || !bgr_in || !hsv_out) return fail(c, OATGPU_E_INVALID, "null argument");

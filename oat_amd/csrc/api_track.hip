@@ -961,9 +961,8 @@ extern "C" int oatgpu_track_batch_dev(oatgpu_ctx *c, const void *frames_dev, dou
 }
 
 // one host frame per camera stream into the staging buffer of the synchronous steps, on stream A; a null one ends it there
-int upload_frames(oatgpu_ctx *c, const uint8_t *const *frames_host)
+int upload_frames(oatgpu_ctx *c, const uint8_t *const *frames_host, size_t fb)
 {
-    const size_t fb = track_in_bytes(c);
     for (int s = 0; s < c->cfg.n_streams; ++s) {
         if (!frames_host[s]) return fail(c, OATGPU_E_INVALID, "null frame %d", s);
         HIPCHK(c, hipMemcpyAsync(c->frames + (size_t)s * fb, frames_host[s], fb, hipMemcpyHostToDevice, c->stream));
@@ -981,6 +980,6 @@ extern "C" int oatgpu_track_batch(oatgpu_ctx *c, const uint8_t *const *frames_ho
     if (c->ring_count) return fail(c, OATGPU_E_INVALID, "track_batch while enqueued results are outstanding");
     { const int rc = refuse_pipelined(c, kRefStaging | kRefState); if (rc) return rc; }
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    { const int rc = upload_frames(c, frames_host); if (rc) return rc; }
+    { const int rc = upload_frames(c, frames_host, track_in_bytes(c)); if (rc) return rc; }
     return oatgpu_track_batch_dev(c, c->frames, lr, out);
 }

@@ -16,7 +16,13 @@
 //          The accumulator leaves in 128-bit stores: each is followed by `s_nop 1` with its data registers live.
 //   narrow (everything else): one pixel a lane with byte and dword accesses, the ballot is the word.
 // Both write EVERY word of Palloc / 64 (zero bits for x >= W and p >= P): the row scan reads them.
+//
+// Bayer RAW8 frames (BsubLaunch::bayer): k_bsubtrack_raw_wide / k_bsubtrack_raw_narrow are the BGR lanes with another
+// pixel source -- the lane demosaics its pixels in registers (debayer_inline.h: the dwords at x0 - 4, x0, x0 + 4 of raw rows y - 1,
+// y, y + 1, or 9 byte loads) into the 12 bytes a BGR frame would have held; the ROI falls on the demosaiced pixel, bg and acc are
+// BGR.  The pattern is run-time data, two parity bits a stream in two 64-bit kernel arguments.
 #include "oatgpu_internal.h"
+#include "debayer_inline.h"
 #include "hsv_inline.h"
 #include "maskwords_inline.h"
 
@@ -27,7 +33,7 @@ namespace {
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct BsubArgs {
-    const uint8_t *frames, *frames2;     // [n][H*W*CH] stream-major; frames2: the second frame of a paired launch
+    const uint8_t *frames, *frames2;     // [n][H*W*CH] stream-major (raw kernels: [n][H*W]); frames2: the second frame of a paired launch
     uint8_t *bg;                         // [n][H*W*CH]
     float *acc;                          // [n][H*W*CH]
     u64 *bits, *bits2;                   // [n][Palloc/64]
@@ -89,7 +95,39 @@ __device__ __forceinline__ unsigned frame4(const unsigned (&f)[CH], unsigned kee
     return nib;
 }
 
-template <int CH, bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(256) void k_bsubtrack_wide(Geom g, BsubArgs a)
+// Where a lane's pixels come from: `frames` is a frame set of the launch (stream-major), s the stream, (y, x) the pixel.
+// four: x % 4 == 0, the 4 pixels from x on as CH little-endian dwords; one: the CH bytes of the pixel.
+template <int CH> struct PackedSource {                  // packed BGR (3) or GREY (1) frames
+    __device__ __forceinline__ void four(const uint8_t *frames, const Geom &g, int s, int y, int x, unsigned (&f)[CH]) const
+    {
+        const unsigned *fp = (const unsigned *)(frames + (((size_t)s * g.H + y) * g.W + x) * CH);
+#pragma unroll
+        for (int j = 0; j < CH; ++j) f[j] = fp[j];
+    }
+    __device__ __forceinline__ void one(const uint8_t *frames, const Geom &g, int s, int y, int x, int (&v)[CH]) const
+    {
+        const uint8_t *fp = frames + (((size_t)s * g.H + y) * g.W + x) * CH;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) v[c] = fp[c];
+    }
+};
+struct RawSource {                                       // Bayer RAW8 frames, demosaiced in registers: BGR pixels
+    bool r_row, r_col;                                   // parity of the row / the column of the stream's R sample (uniform)
+    __device__ __forceinline__ void four(const uint8_t *frames, const Geom &g, int s, int y, int x, unsigned (&f)[3]) const
+    {
+        unsigned px[4];
+        debayer_px4(frames + (size_t)s * g.H * g.W, g.H, g.W, y, x, r_row, r_col, px);
+        pack_bgr4(px, f);
+    }
+    __device__ __forceinline__ void one(const uint8_t *frames, const Geom &g, int s, int y, int x, int (&v)[3]) const
+    {
+        const unsigned p = debayer_px1(frames + (size_t)s * g.H * g.W, g.H, g.W, y, x, r_row, r_col);
+        v[0] = p & 255u; v[1] = (p >> 8) & 255u; v[2] = p >> 16;
+    }
+};
+
+template <int CH, bool ROI, bool PAIR, bool LEARN, class SRC>
+__device__ __forceinline__ void bsubtrack_wide(const Geom &g, const BsubArgs &a, const SRC &src)
 {
     const int s = a.first_stream + (int)blockIdx.y;
     const bool first = (a.first >> blockIdx.y) & 1ull;               // uniform
@@ -105,11 +143,11 @@ template <int CH, bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(
         if (ROI) keep = (((const uint8_t *)(a.roi + (size_t)s * NW))[p0 >> 3] >> (p0 & 4)) & 15u;
         unsigned f[CH], bgw[CH];
         float acc[4 * CH] = {};
-        const unsigned *fp = (const unsigned *)(a.frames + e0);
         unsigned *bp = (unsigned *)(a.bg + e0);
         float4 *ap = (float4 *)(a.acc + e0);
+        src.four(a.frames, g, s, y, x, f);
 #pragma unroll
-        for (int j = 0; j < CH; ++j) { f[j] = fp[j]; bgw[j] = 0; }
+        for (int j = 0; j < CH; ++j) bgw[j] = 0;
         if (!first) {
             if (LEARN) {
 #pragma unroll
@@ -121,9 +159,7 @@ template <int CH, bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(
         }
         n1 = frame4<CH, LEARN>(f, keep, first, bgw, acc, a);
         if (PAIR) {
-            const unsigned *fp2 = (const unsigned *)(a.frames2 + e0);
-#pragma unroll
-            for (int j = 0; j < CH; ++j) f[j] = fp2[j];
+            src.four(a.frames2, g, s, y, x, f);
             n2 = frame4<CH, LEARN>(f, keep, false, bgw, acc, a);
         }
         if (LEARN || first) {
@@ -144,7 +180,8 @@ template <int CH, bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(
     if (PAIR) store_words(n2, lane, a.bits2 + (size_t)s * NW + (size_t)wave * 4);
 }
 
-template <int CH, bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(256) void k_bsubtrack_narrow(Geom g, BsubArgs a)
+template <int CH, bool ROI, bool PAIR, bool LEARN, class SRC>
+__device__ __forceinline__ void bsubtrack_narrow(const Geom &g, const BsubArgs &a, const SRC &src)
 {
     const int s = a.first_stream + (int)blockIdx.y;
     const bool first = (a.first >> blockIdx.y) & 1ull;               // uniform
@@ -157,18 +194,22 @@ template <int CH, bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(
     if (p < g.P && x < g.W) {
         const size_t e0 = ((size_t)s * npx + (size_t)y * g.W + x) * CH;
         const bool keep = !ROI || ((a.roi[(size_t)s * NW + word] >> lane) & 1ull);
-        int bg[CH], d[CH];
+        int bg[CH], d[CH], v[CH];
         float acc[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) v[c] = 0;
+        if (keep) src.one(a.frames, g, s, y, x, v);
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
             bg[c] = 0; acc[c] = 0.f;
             if (!first) { if (LEARN) acc[c] = a.acc[e0 + c]; else bg[c] = a.bg[e0 + c]; }
-            d[c] = bsub_elem<LEARN>(keep ? (int)a.frames[e0 + c] : 0, first, bg[c], acc[c], a.a, a.b);
+            d[c] = bsub_elem<LEARN>(v[c], first, bg[c], acc[c], a.a, a.b);
         }
         on1 = window<CH>(d, a.rp);
         if (PAIR) {
+            if (keep) src.one(a.frames2, g, s, y, x, v);
 #pragma unroll
-            for (int c = 0; c < CH; ++c) d[c] = bsub_elem<LEARN>(keep ? (int)a.frames2[e0 + c] : 0, false, bg[c], acc[c], a.a, a.b);
+            for (int c = 0; c < CH; ++c) d[c] = bsub_elem<LEARN>(v[c], false, bg[c], acc[c], a.a, a.b);
             on2 = window<CH>(d, a.rp);
         }
         if (LEARN || first) {
@@ -182,6 +223,24 @@ template <int CH, bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(
         const u64 w2 = __ballot(on2);
         if (lane == 0) a.bits2[(size_t)s * NW + word] = w2;
     }
+}
+
+template <int CH, bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(256) void k_bsubtrack_wide(Geom g, BsubArgs a)
+{
+    bsubtrack_wide<CH, ROI, PAIR, LEARN>(g, a, PackedSource<CH>{});
+}
+template <int CH, bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(256) void k_bsubtrack_narrow(Geom g, BsubArgs a)
+{
+    bsubtrack_narrow<CH, ROI, PAIR, LEARN>(g, a, PackedSource<CH>{});
+}
+// r_row, r_col: bit (stream - first_stream), the parity of the row / the column of the stream's R sample
+template <bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(256) void k_bsubtrack_raw_wide(Geom g, BsubArgs a, u64 r_row, u64 r_col)
+{
+    bsubtrack_wide<3, ROI, PAIR, LEARN>(g, a, RawSource{(bool)((r_row >> blockIdx.y) & 1ull), (bool)((r_col >> blockIdx.y) & 1ull)});
+}
+template <bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(256) void k_bsubtrack_raw_narrow(Geom g, BsubArgs a, u64 r_row, u64 r_col)
+{
+    bsubtrack_narrow<3, ROI, PAIR, LEARN>(g, a, RawSource{(bool)((r_row >> blockIdx.y) & 1ull), (bool)((r_col >> blockIdx.y) & 1ull)});
 }
 
 template <int CH, bool ROI, bool PAIR, bool LEARN> void launch_one(const Geom &g, const BsubArgs &a, bool wide, int n, hipStream_t st)
@@ -201,6 +260,24 @@ template <int CH> void launch_ch(const Geom &g, const BsubArgs &a, bool learn, b
     else { if (pair) launch_learn<CH, false, true>(g, a, learn, wide, n, st); else launch_learn<CH, false, false>(g, a, learn, wide, n, st); }
 }
 
+struct RawBits { u64 r_row, r_col; };
+template <bool ROI, bool PAIR, bool LEARN> void launch_raw_one(const Geom &g, const BsubArgs &a, RawBits r, bool wide, int n, hipStream_t st)
+{
+    if (wide) hipLaunchKernelGGL((k_bsubtrack_raw_wide<ROI, PAIR, LEARN>), dim3(g.Palloc / 1024, n), dim3(256), 0, st, g, a, r.r_row, r.r_col);
+    else hipLaunchKernelGGL((k_bsubtrack_raw_narrow<ROI, PAIR, LEARN>), dim3(g.Palloc / 256, n), dim3(256), 0, st, g, a, r.r_row, r.r_col);
+}
+template <bool ROI, bool PAIR> void launch_raw_learn(const Geom &g, const BsubArgs &a, RawBits r, bool learn, bool wide, int n, hipStream_t st)
+{
+    if (learn) launch_raw_one<ROI, PAIR, true>(g, a, r, wide, n, st);
+    else launch_raw_one<ROI, PAIR, false>(g, a, r, wide, n, st);
+}
+void launch_raw(const Geom &g, const BsubArgs &a, RawBits r, bool learn, bool wide, int n, hipStream_t st)
+{
+    const bool roi = a.roi != nullptr, pair = a.frames2 != nullptr;
+    if (roi) { if (pair) launch_raw_learn<true, true>(g, a, r, learn, wide, n, st); else launch_raw_learn<true, false>(g, a, r, learn, wide, n, st); }
+    else { if (pair) launch_raw_learn<false, true>(g, a, r, learn, wide, n, st); else launch_raw_learn<false, false>(g, a, r, learn, wide, n, st); }
+}
+
 }  // namespace
 
 bool bsubtrack_front_is_wide(const Geom &g, const BsubLaunch &a)
@@ -212,11 +289,15 @@ bool bsubtrack_front_is_wide(const Geom &g, const BsubLaunch &a)
 void launch_bsubtrack_front(const Geom &g, const BsubLaunch &a, int n_streams, hipStream_t st)
 {
     const bool wide = bsubtrack_front_is_wide(g, a);
-    for (int s0 = 0; s0 < n_streams; s0 += 64) {         // the first-frame mask of a launch is one 64-bit kernel argument
+    for (int s0 = 0; s0 < n_streams; s0 += 64) {         // the first-frame mask and the parity bits of a launch are 64-bit kernel arguments
         const int n = n_streams - s0 < 64 ? n_streams - s0 : 64;
         BsubArgs k{a.frames, a.frames2, a.bg, a.acc, a.bits, a.bits2, a.roi, 0ull, a.rp, a.a, a.b, s0};
         for (int i = 0; i < n; ++i) k.first |= (u64)(a.have[s0 + i] == 0) << i;
-        if (a.channels == 3) launch_ch<3>(g, k, a.learn, wide, n, st);
+        if (a.bayer) {
+            RawBits r;
+            bayer_parity_bits(a.bayer + s0, n, r.r_row, r.r_col);
+            launch_raw(g, k, r, a.learn, wide, n, st);
+        } else if (a.channels == 3) launch_ch<3>(g, k, a.learn, wide, n, st);
         else launch_ch<1>(g, k, a.learn, wide, n, st);
     }
 }

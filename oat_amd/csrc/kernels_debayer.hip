@@ -2,10 +2,9 @@
 // (src/frameserver/PointGreyCam.cpp:48-50, :729) as a device stage, for every camera stream (grid y) and both frames of a
 // two-frame step (grid z) in one launch.
 //
-// The arithmetic is OpenCV 3.1's bilinear Bayer2RGB_ in 32-bit integers.  At an R or B site: own colour = the sample,
-// G = (N + S + W + E + 2) >> 2, opposite colour = (NW + NE + SW + SE + 2) >> 2.  At a G site: G = the sample, the colour of the
-// horizontal neighbours = (W + E + 1) >> 1, of the vertical ones = (N + S + 1) >> 1.  Output (y, x) is the triple of
-// (clamp(y, 1, H - 2), clamp(x, 1, W - 2)) with THAT pixel's site colours: first / last column and row repeat their neighbours.
+// The arithmetic is OpenCV 3.1's bilinear Bayer2RGB_ in 32-bit integers (debayer_inline.h, shared with the front kernels that
+// demosaic in registers).  Output (y, x) is the triple of (clamp(y, 1, H - 2), clamp(x, 1, W - 2)) with THAT pixel's site
+// colours: first / last column and row repeat their neighbours.
 //
 // The pattern is run-time data: per stream two parity bits, the row and the column of the R sample of the 2 x 2 tile, one bit
 // a stream in two 64-bit kernel arguments (so at most 64 streams a launch).
@@ -18,6 +17,7 @@
 //   narrow (everything else): one pixel a lane, byte accesses.
 // No LDS, no scratch; nothing wider than a dword is stored (DESIGN.md 3b does not arise).
 #include "oatgpu_internal.h"
+#include "debayer_inline.h"
 
 namespace oatgpu {
 
@@ -31,42 +31,6 @@ struct DebayerArgs {
     u64 r_row, r_col;                    // bit (stream - first_stream): parity of the row / the column of the R sample
     int H, W, first_stream;
 };
-
-// the five candidate values of a pixel from its 3 x 3 neighbourhood -> (B, G, R) packed as B | G << 8 | R << 16.
-// row_r / col_r: the pixel's row / column holds R samples
-__device__ __forceinline__ unsigned site_bgr(unsigned nw, unsigned n, unsigned ne, unsigned w, unsigned c, unsigned e,
-                                             unsigned sw, unsigned s, unsigned se, bool row_r, bool col_r)
-{
-    const unsigned h = (w + e + 1u) >> 1, v = (n + s + 1u) >> 1;
-    const unsigned p = (n + s + w + e + 2u) >> 2, d = (nw + ne + sw + se + 2u) >> 2;
-    unsigned b, g, r;
-    if (row_r == col_r) {                // an R or a B site
-        g = p;
-        r = row_r ? c : d;
-        b = row_r ? d : c;
-    } else {                             // a G site: in an R row the horizontal neighbours are R, the vertical ones B
-        g = c;
-        r = row_r ? h : v;
-        b = row_r ? v : h;
-    }
-    return b | g << 8 | r << 16;
-}
-
-// bytes x0 - 1 .. x0 + 4 of a raw row as one little-endian 48-bit window (l, c, r: the dwords at x0 - 4, x0, x0 + 4)
-__device__ __forceinline__ u64 window(unsigned l, unsigned c, unsigned r)
-{
-    return (u64)(l >> 24) | (u64)c << 8 | (u64)(r & 255u) << 40;
-}
-__device__ __forceinline__ unsigned wbyte(u64 w, int j) { return (unsigned)(w >> (8 * j)) & 255u; }
-
-// the four BGR triples of one output row of a wide lane from the windows of the raw rows above, at and below it
-__device__ __forceinline__ void row4(u64 up, u64 at, u64 dn, bool row_r, bool col0_r, unsigned px[4])
-{
-#pragma unroll
-    for (int i = 0; i < 4; ++i)          // pixel i sits at window byte i + 1; x0 % 4 == 0: its column parity is i & 1
-        px[i] = site_bgr(wbyte(up, i), wbyte(up, i + 1), wbyte(up, i + 2), wbyte(at, i), wbyte(at, i + 1), wbyte(at, i + 2),
-                         wbyte(dn, i), wbyte(dn, i + 1), wbyte(dn, i + 2), row_r, (i & 1) ? !col0_r : col0_r);
-}
 
 // 12 bytes as three dword stores, kept apart: merged into one dwordx3 they would be a wide store
 __device__ __forceinline__ void store4(uint8_t *d, const unsigned px[4])
@@ -129,10 +93,7 @@ __global__ __launch_bounds__(kDebayerWG) void k_debayer_narrow(DebayerArgs a)
     const bool r_row = (a.r_row >> blockIdx.y) & 1ull, r_col = (a.r_col >> blockIdx.y) & 1ull;
     const uint8_t *in = (blockIdx.z ? a.in[1] : a.in[0]) + (size_t)s * npx;
     uint8_t *out = (blockIdx.z ? a.out[1] : a.out[0]) + (size_t)s * npx * 3;
-    const int cy = min(max(y, 1), H - 2), cx = min(max(x, 1), W - 2);
-    const uint8_t *r0 = in + (size_t)(cy - 1) * W + cx, *r1 = r0 + W, *r2 = r1 + W;
-    const unsigned v = site_bgr(r0[-1], r0[0], r0[1], r1[-1], r1[0], r1[1], r2[-1], r2[0], r2[1], ((cy & 1) != 0) == r_row,
-                                ((cx & 1) != 0) == r_col);
+    const unsigned v = debayer_px1(in, H, W, y, x, r_row, r_col);
     uint8_t *d = out + p * 3;
     d[0] = (uint8_t)v; d[1] = (uint8_t)(v >> 8); d[2] = (uint8_t)(v >> 16);
 }
@@ -161,12 +122,7 @@ void launch_debayer_frames(const uint8_t *const *in, uint8_t *const *out, int n_
             a.out[i] = out[i < n_frames ? i : 0];
         }
         a.H = H; a.W = W; a.first_stream = s0;
-        for (int i = 0; i < n; ++i) {
-            // R sits at (row, column) parity: RGGB (0, 0), BGGR (1, 1), GRBG (0, 1), GBRG (1, 0)
-            const int p = patterns[s0 + i];
-            a.r_row |= (u64)(p == 2 || p == 4) << i;
-            a.r_col |= (u64)(p == 2 || p == 3) << i;
-        }
+        bayer_parity_bits(patterns + s0, n, a.r_row, a.r_col);
         const dim3 grid(gx, (unsigned)n, (unsigned)n_frames);
         if (wide) hipLaunchKernelGGL(k_debayer_wide, grid, dim3(kDebayerWG), 0, st, a);
         else hipLaunchKernelGGL(k_debayer_narrow, grid, dim3(kDebayerWG), 0, st, a);

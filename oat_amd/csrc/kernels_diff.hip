@@ -13,7 +13,13 @@
 //          word out of the four ballots and stores it: every word is stored once, 64 bits a lane.
 //   narrow (everything else): one pixel a lane with byte accesses, the ballot is the word (k_absdiff_bits' mapping).
 // Both write EVERY word of Palloc / 64 (zero bits for x >= W and p >= P): the row scan reads them.
+//
+// Bayer RAW8 frames (DiffLaunch::bayer): k_diff_raw_wide / k_diff_raw_narrow are the same lanes with another pixel
+// source -- the lane demosaics its pixels in registers (debayer_inline.h: the dwords at x0 - 4, x0, x0 + 4 of raw rows y - 1, y,
+// y + 1, or 9 byte loads) and takes the grey of the triples; the ROI falls on the demosaiced pixel.  The pattern is run-time
+// data, two parity bits a stream in two 64-bit kernel arguments.
 #include "oatgpu_internal.h"
+#include "debayer_inline.h"
 #include "maskwords_inline.h"
 
 namespace oatgpu {
@@ -40,9 +46,43 @@ template <int CH> __device__ __forceinline__ unsigned grey4(const uint8_t *frame
     for (int k = 0; k < 4; ++k) g |= (unsigned)grey_bgr(byte_of(d, 3 * k), byte_of(d, 3 * k + 1), byte_of(d, 3 * k + 2)) << (8 * k);
     return g;
 }
+template <int CH> __device__ __forceinline__ int grey1(const uint8_t *frame, size_t i)
+{
+    if (CH == 1) return frame[i];
+    return grey_bgr(frame[3 * i], frame[3 * i + 1], frame[3 * i + 2]);
+}
+
+// Where a lane's greys come from: `frames` is a frame set of the launch (stream-major), s the stream, (y, x) the pixel
+// (four4: x % 4 == 0, the four pixels from x on as one little-endian dword).
+template <int CH> struct PackedSource {                  // packed BGR (3) or GREY (1) frames
+    __device__ __forceinline__ unsigned four(const uint8_t *frames, const Geom &g, int s, int y, int x) const
+    {
+        return grey4<CH>(frames + (size_t)s * g.H * g.W * CH, (size_t)y * g.W + x);
+    }
+    __device__ __forceinline__ int one(const uint8_t *frames, const Geom &g, int s, int y, int x) const
+    {
+        return grey1<CH>(frames + (size_t)s * g.H * g.W * CH, (size_t)y * g.W + x);
+    }
+};
+struct RawSource {                                       // Bayer RAW8 frames, demosaiced in registers
+    bool r_row, r_col;                                   // parity of the row / the column of the stream's R sample (uniform)
+    __device__ __forceinline__ unsigned four(const uint8_t *frames, const Geom &g, int s, int y, int x) const
+    {
+        unsigned px[4], v = 0;
+        debayer_px4(frames + (size_t)s * g.H * g.W, g.H, g.W, y, x, r_row, r_col, px);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v |= (unsigned)grey_bgr(px[k] & 255u, (px[k] >> 8) & 255u, px[k] >> 16) << (8 * k);
+        return v;
+    }
+    __device__ __forceinline__ int one(const uint8_t *frames, const Geom &g, int s, int y, int x) const
+    {
+        const unsigned p = debayer_px1(frames + (size_t)s * g.H * g.W, g.H, g.W, y, x, r_row, r_col);
+        return grey_bgr(p & 255u, (p >> 8) & 255u, p >> 16);
+    }
+};
 
 struct DiffArgs {
-    const uint8_t *frames, *frames2;     // [n][H*W*CH] stream-major; frames2: the second frame of a paired launch
+    const uint8_t *frames, *frames2;     // [n][H*W*CH] stream-major (raw kernels: [n][H*W]); frames2: the second frame of a paired launch
     uint8_t *last;                       // [n][H*W]
     u64 *bits, *bits2;                   // [n][Palloc/64]
     const u64 *roi;                      // [n][Palloc/64]
@@ -50,7 +90,7 @@ struct DiffArgs {
     int thr, first_stream;
 };
 
-template <int CH, bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_diff_wide(Geom g, DiffArgs a)
+template <bool ROI, bool PAIR, class SRC> __device__ __forceinline__ void diff_wide(const Geom &g, const DiffArgs &a, const SRC &src)
 {
     const int s = a.first_stream + (int)blockIdx.y;
     const bool have = PAIR || ((a.have >> blockIdx.y) & 1ull);      // uniform
@@ -68,7 +108,7 @@ template <int CH, bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_
             const unsigned r = (((const uint8_t *)(a.roi + (size_t)s * NW))[p0 >> 3] >> (p0 & 4)) & 15u;
             keep = (r & 1u ? 0xffu : 0u) | (r & 2u ? 0xff00u : 0u) | (r & 4u ? 0xff0000u : 0u) | (r & 8u ? 0xff000000u : 0u);
         }
-        const unsigned g1 = grey4<CH>(a.frames + (size_t)s * npx * CH, i) & keep;
+        const unsigned g1 = src.four(a.frames, g, s, y, x) & keep;
         if (have) {
             const unsigned l = *lp;
 #pragma unroll
@@ -79,7 +119,7 @@ template <int CH, bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_
         }
         unsigned out = g1;
         if (PAIR) {
-            const unsigned g2 = grey4<CH>(a.frames2 + (size_t)s * npx * CH, i) & keep;
+            const unsigned g2 = src.four(a.frames2, g, s, y, x) & keep;
 #pragma unroll
             for (int k = 0; k < 4; ++k) n2 |= differs((g2 >> (8 * k)) & 255u, (g1 >> (8 * k)) & 255u, a.thr) ? 1u << k : 0u;
             out = g2;
@@ -90,13 +130,7 @@ template <int CH, bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_
     if (PAIR) store_words(n2, lane, a.bits2 + (size_t)s * NW + (size_t)wave * 4);
 }
 
-template <int CH> __device__ __forceinline__ int grey1(const uint8_t *frame, size_t i)
-{
-    if (CH == 1) return frame[i];
-    return grey_bgr(frame[3 * i], frame[3 * i + 1], frame[3 * i + 2]);
-}
-
-template <int CH, bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_diff_narrow(Geom g, DiffArgs a)
+template <bool ROI, bool PAIR, class SRC> __device__ __forceinline__ void diff_narrow(const Geom &g, const DiffArgs &a, const SRC &src)
 {
     const int s = a.first_stream + (int)blockIdx.y;
     const bool have = PAIR || ((a.have >> blockIdx.y) & 1ull);
@@ -110,11 +144,11 @@ template <int CH, bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_
         const size_t i = (size_t)y * g.W + x;
         uint8_t *lp = a.last + (size_t)s * npx + i;
         const bool keep = !ROI || ((a.roi[(size_t)s * NW + word] >> lane) & 1ull);
-        const int g1 = keep ? grey1<CH>(a.frames + (size_t)s * npx * CH, i) : 0;
+        const int g1 = keep ? src.one(a.frames, g, s, y, x) : 0;
         on1 = have ? differs(g1, *lp, a.thr) : g1 != 0;
         int out = g1;
         if (PAIR) {
-            const int g2 = keep ? grey1<CH>(a.frames2 + (size_t)s * npx * CH, i) : 0;
+            const int g2 = keep ? src.one(a.frames2, g, s, y, x) : 0;
             on2 = differs(g2, g1, a.thr);
             out = g2;
         }
@@ -126,6 +160,24 @@ template <int CH, bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_
         const u64 w2 = __ballot(on2);
         if (lane == 0) a.bits2[(size_t)s * NW + word] = w2;
     }
+}
+
+template <int CH, bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_diff_wide(Geom g, DiffArgs a)
+{
+    diff_wide<ROI, PAIR>(g, a, PackedSource<CH>{});
+}
+template <int CH, bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_diff_narrow(Geom g, DiffArgs a)
+{
+    diff_narrow<ROI, PAIR>(g, a, PackedSource<CH>{});
+}
+// r_row, r_col: bit (stream - first_stream), the parity of the row / the column of the stream's R sample
+template <bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_diff_raw_wide(Geom g, DiffArgs a, u64 r_row, u64 r_col)
+{
+    diff_wide<ROI, PAIR>(g, a, RawSource{(bool)((r_row >> blockIdx.y) & 1ull), (bool)((r_col >> blockIdx.y) & 1ull)});
+}
+template <bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_diff_raw_narrow(Geom g, DiffArgs a, u64 r_row, u64 r_col)
+{
+    diff_narrow<ROI, PAIR>(g, a, RawSource{(bool)((r_row >> blockIdx.y) & 1ull), (bool)((r_col >> blockIdx.y) & 1ull)});
 }
 
 template <int CH, bool ROI, bool PAIR> void launch_one(const Geom &g, const DiffArgs &a, bool wide, int n, hipStream_t st)
@@ -140,6 +192,18 @@ template <int CH> void launch_ch(const Geom &g, const DiffArgs &a, bool wide, in
     else { if (pair) launch_one<CH, false, true>(g, a, wide, n, st); else launch_one<CH, false, false>(g, a, wide, n, st); }
 }
 
+template <bool ROI, bool PAIR> void launch_raw_one(const Geom &g, const DiffArgs &a, u64 r_row, u64 r_col, bool wide, int n, hipStream_t st)
+{
+    if (wide) hipLaunchKernelGGL((k_diff_raw_wide<ROI, PAIR>), dim3(g.Palloc / 1024, n), dim3(256), 0, st, g, a, r_row, r_col);
+    else hipLaunchKernelGGL((k_diff_raw_narrow<ROI, PAIR>), dim3(g.Palloc / 256, n), dim3(256), 0, st, g, a, r_row, r_col);
+}
+void launch_raw(const Geom &g, const DiffArgs &a, u64 r_row, u64 r_col, bool wide, int n, hipStream_t st)
+{
+    const bool roi = a.roi != nullptr, pair = a.frames2 != nullptr;
+    if (roi) { if (pair) launch_raw_one<true, true>(g, a, r_row, r_col, wide, n, st); else launch_raw_one<true, false>(g, a, r_row, r_col, wide, n, st); }
+    else { if (pair) launch_raw_one<false, true>(g, a, r_row, r_col, wide, n, st); else launch_raw_one<false, false>(g, a, r_row, r_col, wide, n, st); }
+}
+
 }  // namespace
 
 bool diff_front_is_wide(const Geom &g, const DiffLaunch &a)
@@ -151,13 +215,18 @@ bool diff_front_is_wide(const Geom &g, const DiffLaunch &a)
 void launch_diff_front(const Geom &g, const DiffLaunch &a, int n_streams, hipStream_t st)
 {
     const bool wide = diff_front_is_wide(g, a);
-    for (int s0 = 0; s0 < n_streams; s0 += 64) {         // the have-last mask of a launch is one 64-bit kernel argument
+    for (int s0 = 0; s0 < n_streams; s0 += 64) {         // the have-last mask and the parity bits of a launch are 64-bit kernel arguments
         const int n = n_streams - s0 < 64 ? n_streams - s0 : 64;
         DiffArgs k{a.frames, a.frames2, a.last, a.bits, a.bits2, a.roi, 0ull, a.thr, s0};
         for (int i = 0; i < n; ++i) k.have |= (u64)(a.have_last[s0 + i] != 0) << i;
-        if (a.channels == 3) launch_ch<3>(g, k, wide, n, st);
+        if (a.bayer) {
+            u64 r_row, r_col;
+            bayer_parity_bits(a.bayer + s0, n, r_row, r_col);
+            launch_raw(g, k, r_row, r_col, wide, n, st);
+        } else if (a.channels == 3) launch_ch<3>(g, k, wide, n, st);
         else launch_ch<1>(g, k, wide, n, st);
     }
 }
 
 }  // namespace oatgpu
+

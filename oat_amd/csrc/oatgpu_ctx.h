@@ -280,6 +280,8 @@ struct oatgpu_ctx {
     std::vector<int> by_pat;       // [n] OATGPU_BAYER_* of every camera stream while by_track
     DevMem<uint8_t> by_frames[2];  // [2][n][H*W*3] the demosaiced frames of a step (ud_frames' lifetime rule): the remap, or K1, reads
                                    //   them in place of the caller's; allocated by oatgpu_set_track_bayer
+    bool tb_on = false;            // oatgpu_set_tracker_bayer: the motion and the subtraction tracker take Bayer RAW8 frames and demosaic
+    std::vector<int> tb_pat;       //   them inside their front kernels; [n] OATGPU_BAYER_* of every camera stream while tb_on
     DevMem<u64> thr;               // [ring_slots][n][Palloc/64] the ring's threshold buffers (BlobBuffers::thr of every scratch set)
     Scratch bb[kSets];             // scratch sets, all made with the context
     const u64 *last_morph = nullptr;
@@ -370,7 +372,7 @@ int back_half(oatgpu_ctx *c, BlobBuffers &bb, const u64 *thr, int s0, int n, int
 int flush_pending(oatgpu_ctx *c);
 int repair_outstanding(oatgpu_ctx *c);
 void keep_filtered(oatgpu_ctx *c, const MarkerFiltered *f);
-int upload_frames(oatgpu_ctx *c, const uint8_t *const *frames_host);
+int upload_frames(oatgpu_ctx *c, const uint8_t *const *frames_host, size_t frame_bytes);
 // api_markers.hip
 bool own_window_is_nonzero(const oatgpu_config &k);
 int launch_marker_work(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, const StepPlan &plan);
@@ -402,6 +404,9 @@ static inline RangeParams range_of(const oatgpu_marker &k)
 
 // bytes of one camera's frame as the fused track calls take it: RAW8 with oatgpu_set_track_bayer on
 static inline size_t track_in_bytes(const oatgpu_ctx *c) { return (size_t)c->g.H * c->g.W * (c->by_track ? 1 : c->cfg.channels); }
+// ... and as the motion and the subtraction tracker take it: RAW8 with oatgpu_set_tracker_bayer on
+static inline size_t tracker_in_bytes(const oatgpu_ctx *c) { return (size_t)c->g.H * c->g.W * (c->tb_on ? 1 : c->cfg.channels); }
+static inline const int *tracker_bayer(const oatgpu_ctx *c) { return c->tb_on ? c->tb_pat.data() : nullptr; }
 // frame i of the step as K1 and the marker kernels see it: remapped, demosaiced, or the caller's own
 static inline const uint8_t *step_frame(const oatgpu_ctx *c, int i, const void *given)
 {

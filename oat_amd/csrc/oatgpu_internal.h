@@ -163,6 +163,8 @@ struct DiffLaunch {
     u64 *bits, *bits2;       // [n][Palloc/64] threshold words of the frame(s); every word is written
     const u64 *roi;          // [n][Palloc/64] region-of-interest bits (framefilt mask in front of col) or nullptr
     int thr;
+    const int *bayer;        // HOST: nullptr, or [n] OATGPU_BAYER_* 1..4 (checked by the caller; channels == 3, H, W >= 3): frames / frames2
+                             // are Bayer RAW8, [n][H*W], demosaiced in registers
 };
 // 4 pixels a lane with dword accesses: W % 4 == 0 and frames / frames2 / last 4-byte aligned; otherwise one pixel a lane
 bool diff_front_is_wide(const Geom &g, const DiffLaunch &a);
@@ -181,6 +183,8 @@ struct BsubLaunch {
     RangeParams rp;          // the window on hsv(difference); GREY: lo[0] <= difference <= hi[0]
     bool learn;              // alpha > 0: cv::accumulateWeighted with a = (float)alpha, b = 1 - a
     float a, b;
+    const int *bayer;        // HOST: nullptr, or [n] OATGPU_BAYER_* 1..4 (checked by the caller; channels == 3, H, W >= 3): frames / frames2
+                             // are Bayer RAW8, [n][H*W], demosaiced in registers; bg and acc stay BGR
 };
 // 4 pixels a lane: W % 4 == 0, frames / frames2 / bg 4-byte and acc 16-byte aligned; otherwise one pixel a lane
 bool bsubtrack_front_is_wide(const Geom &g, const BsubLaunch &a);

@@ -5,6 +5,8 @@
 //                 diff --bgr: of the chain `oat framefilt col -C GREY` -> `oat posidet diff` on a BGR source (the motion tracker)
 //                 hsv --bsub: of the chain `oat framefilt bsub` -> `oat framefilt col -C HSV` -> `oat posidet hsv` on a BGR source,
 //                 thresh --bsub: of `oat framefilt bsub` -> `oat posidet thresh` on a GREY source (the subtraction tracker)
+//                 diff --bayer P, hsv --bsub --bayer P: the two BGR chains on a GREY-tagged Bayer RAW8 source (a colour camera's
+//                 own pixel format, PointGreyCam.cpp:48-50): the demosaic is done in the same kernel (oatgpu_set_tracker_bayer)
 // Same positional arguments and option names as src/positiondetector/main.cpp:85-271.
 #include "component.hpp"
 
@@ -16,8 +18,9 @@ enum class Kind { HSV, THRESH, DIFF };
 
 class GpuDetector : public PositionDetector {
 public:
-    GpuDetector(const std::string &src, const std::string &snk, Kind kind, bool bgr = false, bool bsub = false)
-        : PositionDetector(src, snk), kind_(kind), bgr_(bgr && kind == Kind::DIFF), bsub_(bsub && kind != Kind::DIFF)
+    // bayer: 0, or the OATGPU_BAYER_* pattern of a RAW8 source (GREY-tagged) in front of a BGR chain
+    GpuDetector(const std::string &src, const std::string &snk, Kind kind, bool bgr = false, bool bsub = false, int bayer = 0)
+        : PositionDetector(src, snk), kind_(kind), bgr_(bgr && kind == Kind::DIFF), bsub_(bsub && kind != Kind::DIFF), bayer_(bayer)
     {
         oatgpu_default_config(&cfg_);
         if (bgr_) { required_color_ = PIX_BGR; cfg_.channels = 3; cfg_.erode = 0; cfg_.dilate = 0; }
@@ -25,6 +28,7 @@ public:
         else if (bsub_) { required_color_ = PIX_GREY; cfg_.channels = 1; cfg_.erode = 0; cfg_.dilate = 0; }
         else if (kind == Kind::HSV) { required_color_ = PIX_HSV; cfg_.erode = 0; cfg_.dilate = 10; }   // HSVDetector.cpp:42-46
         else { required_color_ = PIX_GREY; cfg_.erode = 0; cfg_.dilate = 0; }   // SimpleThreshold.cpp:42-46, DifferenceDetector.cpp:41-44
+        if (bayer_) required_color_ = PIX_GREY;          // one sample a pixel, as `oat-frameserve-raw -C GREY` serves RAW8
     }
     oatgpu_config cfg_;
     double bsub_alpha_{0.0};            // --bsub-alpha: framefilt bsub's -a (BackgroundSubtractor.h)
@@ -36,6 +40,7 @@ protected:
         cfg_.rows = (int)p.rows; cfg_.cols = (int)p.cols; cfg_.n_streams = 1;
         gpu_.create(cfg_);
         if (bgr_) gpu_.check(oatgpu_set_diff_tracker(gpu_.ctx, 1));
+        if (bayer_) { const int32_t pat = bayer_; gpu_.check(oatgpu_set_tracker_bayer(gpu_.ctx, &pat, 1)); }
         if (bsub_) {
             gpu_.check(oatgpu_set_bsub_tracker(gpu_.ctx, 1));
             if (!bsub_background_.empty()) {                 // BackgroundSubtractor.cpp:63-71: imread(.., COLOR)
@@ -77,6 +82,7 @@ protected:
     }
     Kind kind_;
     bool bgr_, bsub_;
+    int bayer_;
     bool deferred_on_{false};
     GpuCtx gpu_;
 };
@@ -86,12 +92,16 @@ static void usage()
     std::cout << "Usage: oat-posidet-hip TYPE SOURCE SINK [CONFIGURATION]\nTYPE\n  hsv | thresh | diff\n"
                  "diff:   -d diff-threshold (default 10)  -b blur (default 2, <= 22)  -a [min,max] area\n"
                  "        --bgr  the SOURCE is BGR: framefilt col -C GREY is done in front of the detector, in the same kernel\n"
+                 "        --bayer RGGB|BGGR|GRBG|GBRG  the SOURCE is Bayer RAW8 (GREY-tagged, the 2 x 2 tile at rows 0-1, columns 0-1):\n"
+                 "        demosaic and framefilt col -C GREY are done in front of the detector, in the same kernel (selects the BGR chain)\n"
                  "hsv:    -H/-S/-V [min,max] in [0,256]  -e erode  -d dilate (default 10)  -a [min,max] area\n"
                  "thresh: -T [min,max]  -e erode  -d dilate  -a [min,max] area\n"
                  "hsv, thresh: --bsub  framefilt bsub (and, for hsv, col -C HSV) is done in front of the detector, in the same kernel:\n"
                  "        the SOURCE is then BGR for hsv, GREY for thresh\n"
                  "        --bsub-alpha A  bsub's adaptation coefficient, 0..1 (default 0: the first frame stays the background)\n"
                  "        --bsub-background FILE.ppm|.pgm  the background image instead of the first frame (it cannot adapt)\n"
+                 "        --bayer P  with hsv --bsub: the SOURCE is Bayer RAW8 (GREY-tagged), demosaiced in the same kernel; a background\n"
+                 "        image stays BGR\n"
                  "all:    --gpu-index N  HIP device ordinal (default 0)\n";
 }
 
@@ -110,11 +120,11 @@ int main(int argc, char **argv)
         if (type != "hsv" && type != "thresh" && type != "diff") throw std::runtime_error("Selected TYPE is invalid.");
         // option names per TYPE: HSVDetector.cpp:49-75, SimpleThreshold.cpp:49-69, DifferenceDetector.cpp:41-62
         if (type == "hsv")
-            o.apply_config({"h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background"},
+            o.apply_config({"h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer"},
                            {"tune", "bsub"});
         else if (type == "thresh")
-            o.apply_config({"thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background"}, {"tune", "bsub"});
-        else o.apply_config({"diff-threshold", "blur", "area", "tune", "gpu-index", "bgr"}, {"tune", "bgr"});
+            o.apply_config({"thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer"}, {"tune", "bsub"});
+        else o.apply_config({"diff-threshold", "blur", "area", "tune", "gpu-index", "bgr", "bayer"}, {"tune", "bgr"});
         if (o.has("bgr") && type != "diff") throw std::runtime_error("--bgr goes with TYPE diff only");
         if (type == "diff" && (o.has("bsub") || o.has("bsub-alpha") || o.has("bsub-background")))
             throw std::runtime_error("--bsub goes with TYPE hsv or thresh only");
@@ -122,10 +132,18 @@ int main(int argc, char **argv)
             throw std::runtime_error("--bsub-alpha and --bsub-background need --bsub");
         if (o.has("bsub-background") && o.num("bsub-alpha", 0, 0, 1) > 0)
             throw std::runtime_error("a background image from a file cannot adapt (--bsub-alpha must be 0)");
+        // --bayer: the SOURCE's pixel format; it selects the BGR chain by itself, and is checked before any device is opened
+        int bayer = 0;
+        if (o.has("bayer")) {
+            if (o.has("bgr")) throw std::runtime_error("--bayer and --bgr exclude each other: --bayer selects the BGR chain on a RAW8 source");
+            if (type == "thresh") throw std::runtime_error("--bayer goes with TYPE diff, or with hsv --bsub: thresh is a GREY chain");
+            if (type == "hsv" && !o.has("bsub")) throw std::runtime_error("--bayer with TYPE hsv needs --bsub");
+            bayer = bayer_pattern(o.kv["bayer"]);
+        }
         if (o.has("tune")) throw std::runtime_error("--tune needs a GUI and is not available in the hip detector");
         auto d = std::make_unique<GpuDetector>(o.positional[1], o.positional[2],
-                                               type == "hsv" ? Kind::HSV : type == "thresh" ? Kind::THRESH : Kind::DIFF, o.has("bgr"),
-                                               o.has("bsub"));
+                                               type == "hsv" ? Kind::HSV : type == "thresh" ? Kind::THRESH : Kind::DIFF,
+                                               o.has("bgr") || (bayer && type == "diff"), o.has("bsub"), bayer);
         d->bsub_alpha_ = o.num("bsub-alpha", 0, 0, 1);
         if (o.has("bsub-background")) d->bsub_background_ = o.kv.at("bsub-background");
         d->cfg_.device = (int)o.num("gpu-index", 0, 0, 64);

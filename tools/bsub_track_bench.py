@@ -5,6 +5,7 @@ against the way the same work had to be done before it -- per camera stream `oat
 
     python tools/bsub_track_bench.py [--steps 200] [--warmup 20] [--quick]
     python tools/bsub_track_bench.py --ktrace RESULTS.db      # the kernels of a rocprofv3 --kernel-trace run of --quick
+    python tools/bsub_track_bench.py --bayer [--steps 200] [--warmup 20] [--quick]      # the RAW8 leg: tools/tracker_bayer_legs.py
 
 Shapes: 1 x 4K, 16 x 1080p and 1 x 640x480, BGR frames, alpha 0 and 0.01; the window is V >= 60 on the difference image,
 erode 0, dilate 10 (the reference's default), three moving discs a camera.  Legs, us a frame set:
@@ -60,6 +61,13 @@ def ktrace(path):
                "min_us": round(min(d), 2), "max_us": round(max(d), 2)}
         m = (re.match(r"k_bsubtrack_(wide|narrow)<(\d), (\w+), (\w+), (\w+)>", name)
              or re.search(r"k_bsubtrack_(wide|narrow)ILi(\d)ELb(\d)ELb(\d)ELb(\d)EE", name))      # (a trace may keep the mangled name)
+        raw = (re.match(r"k_bsubtrack_raw_(wide|narrow)<(\w+), (\w+), (\w+)>", name)   # RAW8 frames: 1 byte a pixel in, BGR state
+               or re.search(r"k_bsubtrack_raw_(wide|narrow)ILb(\d)ELb(\d)ELb(\d)EE", name))
+        if raw:
+            roi, pair, learn = (raw.group(i) in ("true", "1") for i in (2, 3, 4))
+            px = gx * (4 if raw.group(1) == "wide" else 1) * gy
+            mb = px * (bytes_a_pixel(3, roi, pair, learn) - 2) * (2 if pair else 1) / 1e6
+            rec.update(model_MB=round(mb, 2), model_TBps=round(mb / rec["median_us"], 3))
         if m:
             ch, roi, pair, learn = int(m.group(2)), m.group(3) in ("true", "1"), m.group(4) in ("true", "1"), m.group(5) in ("true", "1")
             px = gx * (4 if m.group(1) == "wide" else 1) * gy                   # padded pixels of the launch
@@ -87,6 +95,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--quick", action="store_true", help="few steps (a rehearsal or a profiler run)")
     ap.add_argument("--ktrace", help="print the kernels of this rocprofv3 database and exit")
+    ap.add_argument("--bayer", action="store_true", help="the RAW8 leg: demosaic inside the front kernel against oatgpu_debayer_dev + BGR")
     a = ap.parse_args()
     if a.ktrace:
         print(json.dumps(ktrace(a.ktrace)))
@@ -100,6 +109,16 @@ def main():
     from oat_amd.synth import make_pool
     if not torch.cuda.is_available():
         raise SystemExit("bsub_track_bench: no GPU (nothing is measured without one)")
+    if a.bayer:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import tracker_bayer_legs
+        shapes = []
+        for alpha in ALPHAS:
+            shapes += tracker_bayer_legs.run(lambda rows, cols, n: oat_amd.SubtractionTracker(
+                rows, cols, n_streams=n, channels=3, alpha=alpha, erode=0, dilate=10, area=AREA, **WINDOW), a.steps, a.warmup, {"alpha": alpha})
+        print(json.dumps({"tool": "bsub_track_bench --bayer", "unit": "us a frame set, host clock around synchronous calls, median",
+                          "library": os.path.relpath(oat_amd.lib_path(), ROOT), "shapes": shapes, "device": torch.cuda.get_device_name(0)}))
+        return
 
     out = []
     for name, n, rows, cols in SHAPES:
