@@ -6,6 +6,9 @@ FINAL tap = MORPH with the outer ring zeroed; the background and its fp32 accumu
 against the numpy model.  tests/test_bsub_tracker_cpu.py holds that model to the oracle through the subtracted image; the oracle
 does not show its accumulator, so for `acc` the model (independent of the kernel, separate roundings) is the only reference.
 Everything is exact: no tolerance anywhere.
+These cases are about the FRONT kernel and the state: their masks hold a handful of planted pixels and one rectangle, so the back
+half takes its single-workgroup LDS kernel on every frame here and the global union-find never runs.  The back half on frames over
+that kernel's capacity is tested in tests/test_busy_trackers_gpu.py.
 Every frame is under 0.1 MP."""
 import ctypes as C
 import functools

@@ -3,7 +3,9 @@
 after frame[roi == 0] = 0 where a ROI is set, then O.Diff.detect).  Detections as tests/parity_asserts.py compares them; the
 THRESHOLD tap bit for bit against the numpy front end of tests/diff_cases.py, the MORPH tap against the oracle's `thr > 0`
 on [1:-1, 1:-1] (the outer ring is where blur and dilation differ, and findContours zeroes it), the FINAL tap = MORPH with
-that ring zeroed.  Every frame is under 0.1 MP."""
+that ring zeroed.  These cases are about the FRONT kernel: their masks are nearly empty (noise under a third of the threshold),
+so the back half takes its single-workgroup LDS kernel on every frame here and the global union-find never runs.  The back half
+on frames over that kernel's capacity is tested in tests/test_busy_trackers_gpu.py.  Every frame is under 0.1 MP."""
 import ctypes as C
 import functools
 
