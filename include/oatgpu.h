@@ -364,9 +364,29 @@ int oatgpu_set_track_bayer(oatgpu_ctx *ctx, const int32_t *patterns, int32_t n_p
  * oatgpu_bsub_filter, oatgpu_bsub_set_background (a BGR image) and oatgpu_bsub_get_state, which never look at the switch;
  * turning it on or off between steps keeps the state: a stream fed RAW8 on one step and BGR on the next continues as one
  * stream.  Refused (OATGPU_E_INVALID) with nothing changed: channels != 3, a pattern outside 1..4, n_patterns neither 1
- * nor n_streams, frames smaller than 3 x 3, results outstanding, a partly staged frame set.  Independent of
- * oatgpu_set_track_bayer: while THAT is on the diff and bsub calls stay refused.  With it off nothing changes. */
+ * nor n_streams, frames smaller than 3 x 3, results outstanding, a partly staged frame set, oatgpu_set_tracker_undistort
+ * on.  Independent of oatgpu_set_track_bayer: while THAT is on the diff and bsub calls stay refused.  With it off nothing
+ * changes. */
 int oatgpu_set_tracker_bayer(oatgpu_ctx *ctx, const int32_t *patterns, int32_t n_patterns);
+/* framefilt undistort for the motion and the subtraction tracker of the context (default off).  While on, oatgpu_diff_batch,
+ * _batch_dev, oatgpu_diff_sequence_dev, oatgpu_bsub_track_batch, _batch_dev and oatgpu_bsub_track_sequence_dev remap every
+ * stream's frame with that stream's map (oatgpu_set_undistort) INSIDE the front kernel: the lane loads the map entries of its
+ * own pixels -- once for both frames of a paired launch -- and gathers them from the caller's frame; no undistorted frame is
+ * written and nothing is allocated.  The chain is undistort -> ROI mask (the mask is defined on the UNDISTORTED image) ->
+ * (col GREY -> diff) or (bsub -> col HSV -> window): B, G and R are remapped each on its own (INTER_LINEAR, border constant
+ * 0: a pixel whose source lies off the frame is (0, 0, 0)) and the grey, the difference and the window are taken of the
+ * remapped triple.  Results, taps and state are bit-identical to oatgpu_undistort_dev followed by the same call.  The
+ * sequence calls keep their pairing rules and four frames in flight.  The state -- the last grey image, the background and
+ * its fp32 accumulator, the first-frame flags -- stays in the undistorted domain and shared with oatgpu_detect_diff,
+ * oatgpu_bsub_filter, oatgpu_bsub_set_background (an image in undistorted coordinates) and oatgpu_bsub_get_state, which never
+ * look at the switch; turning it on or off between steps keeps the state: steps with the switch on and off continue one
+ * another.  Refused (OATGPU_E_INVALID) with nothing changed: on outside 0 / 1, on = 1 while any stream has no map (naming
+ * the stream) or while oatgpu_set_tracker_bayer is on (RAW8 and undistortion together are not supported: the gather would
+ * demosaic four corners a pixel), results outstanding, a partly staged frame set.  While it is on,
+ * oatgpu_set_undistort(s, ..., n_dist = 0) is refused; a recalibration is allowed, drains outstanding work and takes effect
+ * from the next frame.  Independent of oatgpu_set_track_undistort: while THAT is on the diff and bsub calls stay refused,
+ * as they do with the position filter or a homography on.  With it off nothing changes. */
+int oatgpu_set_tracker_undistort(oatgpu_ctx *ctx, int32_t on);
 
 /* ---- marker sets: several colour windows per camera behind ONE MOG2 pass, `posicom mean` behind them ----
  *

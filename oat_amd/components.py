@@ -449,20 +449,48 @@ class _TrackerBayer:
         self.frame_shape = (self.rows, self.cols)
 
 
-class MotionTracker(_Detector, _TrackerBayer):
+class _TrackerUndistort:
+    """oatgpu_set_tracker_undistort for the batched trackers (mirrors HotPath.set_undistort / HotPath.undistort)."""
+
+    def set_undistort(self, stream, camera_matrix, distortion_coeffs):
+        """The undistortion map of one camera stream (oatgpu_set_undistort): camera_matrix 9 values, distortion_coeffs
+        5 or 8.  Allowed while undistort() is on (a recalibration: it takes effect from the next frame)."""
+        K, D = _calibration(camera_matrix, distortion_coeffs)
+        self._chk(self.lib.oatgpu_set_undistort(self.ctx, int(stream), K.ctypes.data_as(C.POINTER(C.c_double)),
+                                                D.ctypes.data_as(C.POINTER(C.c_double)), D.size))
+
+    def undistort(self, on=True):
+        """oatgpu_set_tracker_undistort: track, track_dev and track_sequence_dev remap each stream's frame with its map inside
+        the front kernel, ahead of the ROI mask; the state stays in the undistorted domain.  Every stream needs a map
+        (set_undistort) to switch it on; not together with bayer()."""
+        self._chk(self.lib.oatgpu_set_tracker_undistort(self.ctx, 1 if on else 0))
+
+    def _undistort_all(self, calibration):
+        """The constructor's undistort=(K, D): one calibration for every stream, switched on."""
+        K, D = calibration
+        for st in range(self.n_streams):
+            self.set_undistort(st, K, D)
+        self.undistort(True)
+
+
+class MotionTracker(_Detector, _TrackerBayer, _TrackerUndistort):
     """The batched motion tracker: `framefilt col -C GREY` -> `posidet diff` for N camera streams, one front launch a step
     (oatgpu_set_diff_tracker).  channels = 3: BGR frames (rows, cols, 3); 1: GREY frames (rows, cols).  Options follow
     DifferenceDetector.cpp:47-64 (-d diff-threshold, -b blur, -a area).  A ROI (set_roi_mask) masks the frame first.
-    bayer: Bayer RAW8 frames (rows, cols) of a BGR tracker, see bayer()."""
+    bayer: Bayer RAW8 frames (rows, cols) of a BGR tracker, see bayer().
+    undistort: a (camera_matrix, distortion_coeffs) tuple -- `framefilt undistort` in front of the chain for every stream, see
+    set_undistort() and undistort()."""
 
     def __init__(self, rows, cols, n_streams=1, channels=3, diff_threshold=10, blur=2, area=(0.0, DBL_MAX), device=0, bayer=None,
-                 **kw):
+                 undistort=None, **kw):
         super().__init__(rows, cols, n_streams=n_streams, channels=channels, diff_threshold=diff_threshold, blur=blur,
                          erode=0, dilate=0, min_area=area[0], max_area=area[1], device=device, **kw)
         self._pos = (ffi.Position * n_streams)()
         self._chk(self.lib.oatgpu_set_diff_tracker(self.ctx, 1))
         if bayer is not None:
             self.bayer(bayer)
+        if undistort is not None:
+            self._undistort_all(undistort)
 
     def _out(self):
         return [Position2D.from_c(p) for p in self._pos]
@@ -499,15 +527,17 @@ class MotionTracker(_Detector, _TrackerBayer):
         return out
 
 
-class SubtractionTracker(_Detector, _TrackerBayer):
+class SubtractionTracker(_Detector, _TrackerBayer, _TrackerUndistort):
     """The batched subtraction tracker: `framefilt bsub` -> `framefilt col -C HSV` -> `posidet hsv` for N camera streams, one front
     launch a step (oatgpu_set_bsub_tracker).  channels = 3: BGR frames (rows, cols, 3) and the h / s / v window on the difference
     image; 1: GREY frames (rows, cols), `framefilt bsub` -> `posidet thresh` with `thresh`.  alpha is bsub's -a (0: the background
     stays the first frame); erode / dilate / area as HSVDetector.cpp:49-75.  A ROI (set_roi_mask) masks the frame first.
-    bayer: Bayer RAW8 frames (rows, cols) of a BGR tracker, see bayer(); the background and its state stay BGR."""
+    bayer: Bayer RAW8 frames (rows, cols) of a BGR tracker, see bayer(); the background and its state stay BGR.
+    undistort: a (camera_matrix, distortion_coeffs) tuple -- `framefilt undistort` in front of the chain for every stream, see
+    set_undistort() and undistort(); the background and its state are images in undistorted coordinates."""
 
     def __init__(self, rows, cols, n_streams=1, channels=3, alpha=0.0, h_thresh=(0, 256), s_thresh=(0, 256), v_thresh=(0, 256),
-                 thresh=None, erode=0, dilate=10, area=(0.0, DBL_MAX), device=0, bayer=None, **kw):
+                 thresh=None, erode=0, dilate=10, area=(0.0, DBL_MAX), device=0, bayer=None, undistort=None, **kw):
         if thresh is not None:
             h_thresh = thresh
         super().__init__(rows, cols, n_streams=n_streams, channels=channels, h_lo=h_thresh[0], h_hi=h_thresh[1], s_lo=s_thresh[0],
@@ -518,6 +548,8 @@ class SubtractionTracker(_Detector, _TrackerBayer):
         self._chk(self.lib.oatgpu_set_bsub_tracker(self.ctx, 1))
         if bayer is not None:
             self.bayer(bayer)
+        if undistort is not None:
+            self._undistort_all(undistort)
 
     def _alpha(self, alpha):
         return float(getattr(self, "alpha_", 0.0) if alpha is None else alpha)

@@ -79,6 +79,7 @@ static int bsub_front(oatgpu_ctx *c, const void *f1, const void *f2, double alph
     a.bits = bsub_bits(c, slot); a.bits2 = f2 ? bsub_bits(c, slot2) : nullptr;
     a.roi = c->roi; a.rp = range_of(detector_of(c->cfg));
     a.bayer = tracker_bayer(c);
+    tracker_undistort(c, a);
     a.learn = alpha > 0.0; a.a = (float)alpha; a.b = 1 - a.a;        // accW_: AT a = (AT)alpha, b = 1 - a
     launch_bsubtrack_front(c->g, a, c->cfg.n_streams, c->stream);
     HIPCHK(c, hipGetLastError());

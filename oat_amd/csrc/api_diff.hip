@@ -71,6 +71,7 @@ static int diff_front(oatgpu_ctx *c, const void *f1, const void *f2, int slot, i
     a.frames = (const uint8_t *)f1; a.frames2 = (const uint8_t *)f2; a.channels = c->cfg.channels; a.last = c->diff_last;
     a.have_last = c->diff_have.data(); a.bits = diff_bits(c, slot); a.bits2 = f2 ? diff_bits(c, slot2) : nullptr;
     a.roi = c->roi; a.thr = c->cfg.diff_threshold; a.bayer = tracker_bayer(c);
+    tracker_undistort(c, a);
     launch_diff_front(c->g, a, c->cfg.n_streams, c->stream);
     HIPCHK(c, hipGetLastError());
     return OATGPU_OK;

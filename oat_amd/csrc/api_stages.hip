@@ -250,6 +250,8 @@ extern "C" int oatgpu_set_undistort(oatgpu_ctx *c, int32_t s, const double K[9],
     if (n_dist == 0) {
         if (c->ud_track)                // (the fused track calls remap every stream: each needs its map while the switch is on)
             return fail(c, OATGPU_E_INVALID, "stream %d: the map cannot be removed while the tracker undistorts (oatgpu_set_track_undistort)", s);
+        if (c->tu_on)                   // (and so do the motion and the subtraction tracker's front kernels)
+            return fail(c, OATGPU_E_INVALID, "stream %d: the map cannot be removed while the diff and bsub trackers undistort (oatgpu_set_tracker_undistort)", s);
         c->ud_have[(size_t)s] = 0;      // (nothing on the device reads a stream without a map)
         return OATGPU_OK;
     }
@@ -300,6 +302,26 @@ extern "C" int oatgpu_set_track_undistort(oatgpu_ctx *c, int32_t on)
         c->ud_frames[0] = std::move(fr[0]); c->ud_frames[1] = std::move(fr[1]);
     }
     c->ud_track = on != 0;
+    return OATGPU_OK;
+}
+
+// The motion and the subtraction tracker on distorted frames (api_diff.hip, api_bsubtrack.hip): their front kernels remap in
+// registers with the maps of oatgpu_set_undistort, so the switch is a flag alone -- no buffer, and the trackers' state stays in
+// the undistorted domain.
+extern "C" int oatgpu_set_tracker_undistort(oatgpu_ctx *c, int32_t on)
+{
+    if (!c) return OATGPU_E_INVALID;
+    if (on != 0 && on != 1) return fail(c, OATGPU_E_INVALID, "tracker undistort must be 0 (off) or 1 (on)");
+    if (on) {
+        for (int s = 0; s < c->cfg.n_streams; ++s)
+            if (!c->ud_have[(size_t)s]) return fail(c, OATGPU_E_INVALID, "stream %d has no undistortion map (oatgpu_set_undistort)", s);
+        if (c->tb_on)
+            return fail(c, OATGPU_E_INVALID, "set_tracker_undistort with Bayer frames on (oatgpu_set_tracker_bayer) is not supported");
+    }
+    if (c->ring_count) return fail(c, OATGPU_E_INVALID, "set_tracker_undistort while enqueued results are outstanding");
+    if (c->staged_count)
+        return fail(c, OATGPU_E_INVALID, "set_tracker_undistort while a frame set is being staged (oatgpu_track_stage): finish it with oatgpu_track_enqueue_staged or give it up");
+    c->tu_on = on != 0;
     return OATGPU_OK;
 }
 
@@ -425,6 +447,8 @@ extern "C" int oatgpu_set_tracker_bayer(oatgpu_ctx *c, const int32_t *patterns, 
         if (c->cfg.channels != 3) return fail(c, OATGPU_E_INVALID, "Bayer frames need a BGR context (channels = 3, have %d)", c->cfg.channels);
         const int rc = check_bayer_args(c, patterns, n_patterns);
         if (rc) return rc;
+        if (c->tu_on)                   // (the gather would demosaic four corners a pixel)
+            return fail(c, OATGPU_E_INVALID, "set_tracker_bayer with undistortion on (oatgpu_set_tracker_undistort) is not supported");
         pat.resize((size_t)c->cfg.n_streams);
         for (int s = 0; s < c->cfg.n_streams; ++s) pat[(size_t)s] = patterns[n_patterns == 1 ? 0 : s];
     }

@@ -21,10 +21,17 @@
 // pixel source -- the lane demosaics its pixels in registers (debayer_inline.h: the dwords at x0 - 4, x0, x0 + 4 of raw rows y - 1,
 // y, y + 1, or 9 byte loads) into the 12 bytes a BGR frame would have held; the ROI falls on the demosaiced pixel, bg and acc are
 // BGR.  The pattern is run-time data, two parity bits a stream in two 64-bit kernel arguments.
+//
+// Lens undistortion (BsubLaunch::ud_map1): k_bsubtrack_remap_wide / k_bsubtrack_remap_narrow are the same lanes with
+// a third pixel source -- the lane loads the map entries of its own pixels (kernels_diff.hip's RemapSource), keeps them in
+// registers for both frames of a paired launch, and gathers each pixel with undistort_inline.h's remap_px into the bytes an
+// undistorted frame would have held: every channel is remapped on its own, then subtracted; the ROI falls on the undistorted
+// pixel, bg and acc are images in undistorted coordinates.
 #include "oatgpu_internal.h"
 #include "debayer_inline.h"
 #include "hsv_inline.h"
 #include "maskwords_inline.h"
+#include "undistort_inline.h"
 
 namespace oatgpu {
 
@@ -96,8 +103,11 @@ __device__ __forceinline__ unsigned frame4(const unsigned (&f)[CH], unsigned kee
 }
 
 // Where a lane's pixels come from: `frames` is a frame set of the launch (stream-major), s the stream, (y, x) the pixel.
-// four: x % 4 == 0, the 4 pixels from x on as CH little-endian dwords; one: the CH bytes of the pixel.
+// four: x % 4 == 0, the 4 pixels from x on as CH little-endian dwords; one: the CH bytes of the pixel.  begin4 / begin1 run once
+// a lane ahead of the first four / one: what the lane keeps for every frame of the launch.
 template <int CH> struct PackedSource {                  // packed BGR (3) or GREY (1) frames
+    __device__ __forceinline__ void begin4(const Geom &, int, int, int) {}
+    __device__ __forceinline__ void begin1(const Geom &, int, int, int) {}
     __device__ __forceinline__ void four(const uint8_t *frames, const Geom &g, int s, int y, int x, unsigned (&f)[CH]) const
     {
         const unsigned *fp = (const unsigned *)(frames + (((size_t)s * g.H + y) * g.W + x) * CH);
@@ -113,6 +123,8 @@ template <int CH> struct PackedSource {                  // packed BGR (3) or GR
 };
 struct RawSource {                                       // Bayer RAW8 frames, demosaiced in registers: BGR pixels
     bool r_row, r_col;                                   // parity of the row / the column of the stream's R sample (uniform)
+    __device__ __forceinline__ void begin4(const Geom &, int, int, int) {}
+    __device__ __forceinline__ void begin1(const Geom &, int, int, int) {}
     __device__ __forceinline__ void four(const uint8_t *frames, const Geom &g, int s, int y, int x, unsigned (&f)[3]) const
     {
         unsigned px[4];
@@ -126,8 +138,41 @@ struct RawSource {                                       // Bayer RAW8 frames, d
     }
 };
 
+template <int CH> struct RemapSource {                   // packed frames seen through the stream's undistortion map
+    const uint32_t *map1;                                // the STREAM's planes (uniform)
+    const uint16_t *map2;
+    uint32_t m1[4], m2[4];                               // the lane's map entries: loaded once, used for every frame of the launch
+    __device__ __forceinline__ void begin4(const Geom &g, int, int y, int x) { load_map4(map1, map2, (size_t)y * g.W + x, m1, m2); }
+    __device__ __forceinline__ void begin1(const Geom &g, int, int y, int x)
+    {
+        const size_t i = (size_t)y * g.W + x;
+        m1[0] = map1[i]; m2[0] = map2[i];
+    }
+    __device__ __forceinline__ void four(const uint8_t *frames, const Geom &g, int s, int, int, unsigned (&f)[CH]) const
+    {
+        const uint8_t *frame = frames + (size_t)s * g.H * g.W * CH;
+        unsigned px[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            uint32_t v[CH];
+            remap_px<CH>(frame, g.H, g.W, m1[k], m2[k], v);
+            if constexpr (CH == 1) px[k] = v[0];
+            else px[k] = v[0] | v[1] << 8 | v[2] << 16;
+        }
+        if constexpr (CH == 1) f[0] = px[0] | px[1] << 8 | px[2] << 16 | px[3] << 24;
+        else pack_bgr4(px, f);
+    }
+    __device__ __forceinline__ void one(const uint8_t *frames, const Geom &g, int s, int, int, int (&v)[CH]) const
+    {
+        uint32_t u[CH];
+        remap_px<CH>(frames + (size_t)s * g.H * g.W * CH, g.H, g.W, m1[0], m2[0], u);
+#pragma unroll
+        for (int c = 0; c < CH; ++c) v[c] = (int)u[c];
+    }
+};
+
 template <int CH, bool ROI, bool PAIR, bool LEARN, class SRC>
-__device__ __forceinline__ void bsubtrack_wide(const Geom &g, const BsubArgs &a, const SRC &src)
+__device__ __forceinline__ void bsubtrack_wide(const Geom &g, const BsubArgs &a, SRC src)
 {
     const int s = a.first_stream + (int)blockIdx.y;
     const bool first = (a.first >> blockIdx.y) & 1ull;               // uniform
@@ -145,6 +190,7 @@ __device__ __forceinline__ void bsubtrack_wide(const Geom &g, const BsubArgs &a,
         float acc[4 * CH] = {};
         unsigned *bp = (unsigned *)(a.bg + e0);
         float4 *ap = (float4 *)(a.acc + e0);
+        src.begin4(g, s, y, x);
         src.four(a.frames, g, s, y, x, f);
 #pragma unroll
         for (int j = 0; j < CH; ++j) bgw[j] = 0;
@@ -181,7 +227,7 @@ __device__ __forceinline__ void bsubtrack_wide(const Geom &g, const BsubArgs &a,
 }
 
 template <int CH, bool ROI, bool PAIR, bool LEARN, class SRC>
-__device__ __forceinline__ void bsubtrack_narrow(const Geom &g, const BsubArgs &a, const SRC &src)
+__device__ __forceinline__ void bsubtrack_narrow(const Geom &g, const BsubArgs &a, SRC src)
 {
     const int s = a.first_stream + (int)blockIdx.y;
     const bool first = (a.first >> blockIdx.y) & 1ull;               // uniform
@@ -198,7 +244,7 @@ __device__ __forceinline__ void bsubtrack_narrow(const Geom &g, const BsubArgs &
         float acc[CH];
 #pragma unroll
         for (int c = 0; c < CH; ++c) v[c] = 0;
-        if (keep) src.one(a.frames, g, s, y, x, v);
+        if (keep) { src.begin1(g, s, y, x); src.one(a.frames, g, s, y, x, v); }
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
             bg[c] = 0; acc[c] = 0.f;
@@ -243,6 +289,20 @@ template <bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(256) voi
     bsubtrack_narrow<3, ROI, PAIR, LEARN>(g, a, RawSource{(bool)((r_row >> blockIdx.y) & 1ull), (bool)((r_col >> blockIdx.y) & 1ull)});
 }
 
+// map1, map2: plane 0 of the context's maps; the stream's planes start map_stride entries a stream further on
+template <int CH, bool ROI, bool PAIR, bool LEARN>
+__global__ __launch_bounds__(256) void k_bsubtrack_remap_wide(Geom g, BsubArgs a, const uint32_t *map1, const uint16_t *map2, size_t map_stride)
+{
+    const size_t off = (size_t)(a.first_stream + (int)blockIdx.y) * map_stride;
+    bsubtrack_wide<CH, ROI, PAIR, LEARN>(g, a, RemapSource<CH>{map1 + off, map2 + off, {}, {}});
+}
+template <int CH, bool ROI, bool PAIR, bool LEARN>
+__global__ __launch_bounds__(256) void k_bsubtrack_remap_narrow(Geom g, BsubArgs a, const uint32_t *map1, const uint16_t *map2, size_t map_stride)
+{
+    const size_t off = (size_t)(a.first_stream + (int)blockIdx.y) * map_stride;
+    bsubtrack_narrow<CH, ROI, PAIR, LEARN>(g, a, RemapSource<CH>{map1 + off, map2 + off, {}, {}});
+}
+
 template <int CH, bool ROI, bool PAIR, bool LEARN> void launch_one(const Geom &g, const BsubArgs &a, bool wide, int n, hipStream_t st)
 {
     if (wide) hipLaunchKernelGGL((k_bsubtrack_wide<CH, ROI, PAIR, LEARN>), dim3(g.Palloc / 1024, n), dim3(256), 0, st, g, a);
@@ -278,11 +338,31 @@ void launch_raw(const Geom &g, const BsubArgs &a, RawBits r, bool learn, bool wi
     else { if (pair) launch_raw_learn<false, true>(g, a, r, learn, wide, n, st); else launch_raw_learn<false, false>(g, a, r, learn, wide, n, st); }
 }
 
+struct MapPlanes { const uint32_t *map1; const uint16_t *map2; size_t stride; };
+template <int CH, bool ROI, bool PAIR, bool LEARN> void launch_remap_one(const Geom &g, const BsubArgs &a, MapPlanes m, bool wide, int n, hipStream_t st)
+{
+    if (wide) hipLaunchKernelGGL((k_bsubtrack_remap_wide<CH, ROI, PAIR, LEARN>), dim3(g.Palloc / 1024, n), dim3(256), 0, st, g, a, m.map1, m.map2, m.stride);
+    else hipLaunchKernelGGL((k_bsubtrack_remap_narrow<CH, ROI, PAIR, LEARN>), dim3(g.Palloc / 256, n), dim3(256), 0, st, g, a, m.map1, m.map2, m.stride);
+}
+template <int CH, bool ROI, bool PAIR> void launch_remap_learn(const Geom &g, const BsubArgs &a, MapPlanes m, bool learn, bool wide, int n, hipStream_t st)
+{
+    if (learn) launch_remap_one<CH, ROI, PAIR, true>(g, a, m, wide, n, st);
+    else launch_remap_one<CH, ROI, PAIR, false>(g, a, m, wide, n, st);
+}
+template <int CH> void launch_remap(const Geom &g, const BsubArgs &a, MapPlanes m, bool learn, bool wide, int n, hipStream_t st)
+{
+    const bool roi = a.roi != nullptr, pair = a.frames2 != nullptr;
+    if (roi) { if (pair) launch_remap_learn<CH, true, true>(g, a, m, learn, wide, n, st); else launch_remap_learn<CH, true, false>(g, a, m, learn, wide, n, st); }
+    else { if (pair) launch_remap_learn<CH, false, true>(g, a, m, learn, wide, n, st); else launch_remap_learn<CH, false, false>(g, a, m, learn, wide, n, st); }
+}
+
 }  // namespace
 
+// With a map (ud_map1) the frames are gathered with unaligned loads, so their own alignment does not count (the rule of
+// diff_front_is_wide): bg, CH dwords a lane, and acc, CH 16-byte accesses a lane, still have to be aligned.
 bool bsubtrack_front_is_wide(const Geom &g, const BsubLaunch &a)
 {
-    const uintptr_t m = (uintptr_t)a.frames | (uintptr_t)a.frames2 | (uintptr_t)a.bg;
+    const uintptr_t m = a.ud_map1 ? (uintptr_t)a.bg : (uintptr_t)a.frames | (uintptr_t)a.frames2 | (uintptr_t)a.bg;
     return g.W % 4 == 0 && (m & 3u) == 0 && ((uintptr_t)a.acc & 15u) == 0;
 }
 
@@ -297,6 +377,10 @@ void launch_bsubtrack_front(const Geom &g, const BsubLaunch &a, int n_streams, h
             RawBits r;
             bayer_parity_bits(a.bayer + s0, n, r.r_row, r.r_col);
             launch_raw(g, k, r, a.learn, wide, n, st);
+        } else if (a.ud_map1) {
+            const MapPlanes m{a.ud_map1, a.ud_map2, a.ud_stride};
+            if (a.channels == 3) launch_remap<3>(g, k, m, a.learn, wide, n, st);
+            else launch_remap<1>(g, k, m, a.learn, wide, n, st);
         } else if (a.channels == 3) launch_ch<3>(g, k, a.learn, wide, n, st);
         else launch_ch<1>(g, k, a.learn, wide, n, st);
     }

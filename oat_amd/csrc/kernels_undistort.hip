@@ -9,6 +9,7 @@
 // -ffp-contract=off (Makefile HIPFLAGS) is a parity requirement of the map builder: a contracted FMA moves u, v and flips
 // 1/32-px cells.
 #include "oatgpu_internal.h"
+#include "undistort_inline.h"
 
 #include <algorithm>
 #include <climits>
@@ -98,53 +99,13 @@ void undistort_build_map(int rows, int cols, const double K[9], const double *di
 //
 // One lane, kPx consecutive output pixels of the raster (one 16-byte map1 load, one 8-byte map2 load, 4 / 12 bytes out).
 // The per-stream map planes are padded to a multiple of kMapAlign entries (undistort_map_stride), so the vector map loads
-// of a stream's last lane stay inside its padded plane and are aligned.  Corner pairs (sx, sx+1) are read as one unaligned
-// dword + ushort (BGR) or one ushort (GREY) per source row when all four corners are inside the frame; border pixels read
-// each corner that is inside byte by byte and take 0 for the others (BORDER_CONSTANT, cval 0).
+// of a stream's last lane stay inside its padded plane and are aligned.  The per-pixel arithmetic -- remap_px, its unaligned
+// corner loads, the inside / partly inside / outside rule (BORDER_CONSTANT, cval 0) -- is undistort_inline.h's, shared with the
+// front kernels of the motion and the subtraction tracker.
 constexpr int kPx = 4;
 constexpr int kUndistortWG = 256;
 
-struct __attribute__((packed)) ua_u32 { uint32_t v; };
-struct __attribute__((packed)) ua_u16 { uint16_t v; };
-
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) { return ((const ua_u32 *)p)->v; }
-__device__ __forceinline__ uint32_t ld_u16(const uint8_t *p) { return ((const ua_u16 *)p)->v; }
 __device__ __forceinline__ void st_u32(uint8_t *p, uint32_t v) { ((ua_u32 *)p)->v = v; }
-
-template <int CH>
-__device__ __forceinline__ void remap_px(const uint8_t *__restrict__ src, int H, int W, uint32_t m1, uint32_t m2, uint32_t out[CH])
-{
-    const int sx = (int)(int16_t)(m1 & 0xffffu), sy = (int)(int16_t)(m1 >> 16);
-    const int fx = (int)(m2 & 31u), fy = (int)((m2 >> 5) & 31u);
-    const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;   // BilinearTab_i / 32
-    uint32_t s00[CH], s01[CH], s10[CH], s11[CH];
-    if ((unsigned)sx < (unsigned)(W - 1) && (unsigned)sy < (unsigned)(H - 1)) {
-        const uint8_t *r0 = src + ((size_t)sy * W + sx) * CH, *r1 = r0 + (size_t)W * CH;
-        if constexpr (CH == 3) {
-            const uint32_t a0 = ld_u32(r0), b0 = ld_u16(r0 + 4), a1 = ld_u32(r1), b1 = ld_u16(r1 + 4);
-            s00[0] = a0 & 255; s00[1] = (a0 >> 8) & 255; s00[2] = (a0 >> 16) & 255;
-            s01[0] = a0 >> 24; s01[1] = b0 & 255;        s01[2] = b0 >> 8;
-            s10[0] = a1 & 255; s10[1] = (a1 >> 8) & 255; s10[2] = (a1 >> 16) & 255;
-            s11[0] = a1 >> 24; s11[1] = b1 & 255;        s11[2] = b1 >> 8;
-        } else {
-            const uint32_t a0 = ld_u16(r0), a1 = ld_u16(r1);
-            s00[0] = a0 & 255; s01[0] = a0 >> 8; s10[0] = a1 & 255; s11[0] = a1 >> 8;
-        }
-    } else if (sx >= W || sx + 1 < 0 || sy >= H || sy + 1 < 0) {
-        for (int c = 0; c < CH; ++c) out[c] = 0;
-        return;
-    } else {
-        const bool x0 = sx >= 0, x1 = sx + 1 < W, y0 = sy >= 0, y1 = sy + 1 < H;
-        for (int c = 0; c < CH; ++c) {
-            s00[c] = (x0 && y0) ? src[((size_t)sy * W + sx) * CH + c] : 0;
-            s01[c] = (x1 && y0) ? src[((size_t)sy * W + sx + 1) * CH + c] : 0;
-            s10[c] = (x0 && y1) ? src[((size_t)(sy + 1) * W + sx) * CH + c] : 0;
-            s11[c] = (x1 && y1) ? src[((size_t)(sy + 1) * W + sx + 1) * CH + c] : 0;
-        }
-    }
-    for (int c = 0; c < CH; ++c)
-        out[c] = (s00[c] * w00 + s01[c] * w01 + s10[c] * w10 + s11[c] * w11 + 512u) >> 10;
-}
 
 // kPx output pixels of one frame from its stream's map planes, starting at raster position p0 (< H*W)
 template <int CH>
@@ -152,10 +113,8 @@ __device__ __forceinline__ void remap_lane(const uint8_t *__restrict__ src, uint
                                            const uint32_t *__restrict__ map1, const uint16_t *__restrict__ map2, size_t p0,
                                            size_t npx, int H, int W)
 {
-    const uint4 m1 = *(const uint4 *)(map1 + p0);
-    const uint2 m2p = *(const uint2 *)(map2 + p0);
-    const uint32_t m1v[kPx] = {m1.x, m1.y, m1.z, m1.w};
-    const uint32_t m2v[kPx] = {m2p.x & 0xffffu, m2p.x >> 16, m2p.y & 0xffffu, m2p.y >> 16};
+    uint32_t m1v[kPx], m2v[kPx];
+    load_map4(map1, map2, p0, m1v, m2v);
     uint32_t v[kPx][CH];
 #pragma unroll
     for (int k = 0; k < kPx; ++k) remap_px<CH>(src, H, W, m1v[k], m2v[k], v[k]);

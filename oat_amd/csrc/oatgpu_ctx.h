@@ -282,6 +282,8 @@ struct oatgpu_ctx {
                                    //   them in place of the caller's; allocated by oatgpu_set_track_bayer
     bool tb_on = false;            // oatgpu_set_tracker_bayer: the motion and the subtraction tracker take Bayer RAW8 frames and demosaic
     std::vector<int> tb_pat;       //   them inside their front kernels; [n] OATGPU_BAYER_* of every camera stream while tb_on
+    bool tu_on = false;            // oatgpu_set_tracker_undistort: the motion and the subtraction tracker remap every stream's frame with
+                                   //   its map (ud_map1 / ud_map2, every ud_have set while on) inside their front kernels
     DevMem<u64> thr;               // [ring_slots][n][Palloc/64] the ring's threshold buffers (BlobBuffers::thr of every scratch set)
     Scratch bb[kSets];             // scratch sets, all made with the context
     const u64 *last_morph = nullptr;
@@ -407,6 +409,12 @@ static inline size_t track_in_bytes(const oatgpu_ctx *c) { return (size_t)c->g.H
 // ... and as the motion and the subtraction tracker take it: RAW8 with oatgpu_set_tracker_bayer on
 static inline size_t tracker_in_bytes(const oatgpu_ctx *c) { return (size_t)c->g.H * c->g.W * (c->tb_on ? 1 : c->cfg.channels); }
 static inline const int *tracker_bayer(const oatgpu_ctx *c) { return c->tb_on ? c->tb_pat.data() : nullptr; }
+// ... and the maps their front kernels remap with: oatgpu_set_tracker_undistort on (a DiffLaunch or a BsubLaunch)
+template <class Launch> static inline void tracker_undistort(const oatgpu_ctx *c, Launch &a)
+{
+    if (!c->tu_on) return;
+    a.ud_map1 = c->ud_map1; a.ud_map2 = c->ud_map2; a.ud_stride = c->ud_stride;
+}
 // frame i of the step as K1 and the marker kernels see it: remapped, demosaiced, or the caller's own
 static inline const uint8_t *step_frame(const oatgpu_ctx *c, int i, const void *given)
 {

@@ -165,8 +165,12 @@ struct DiffLaunch {
     int thr;
     const int *bayer;        // HOST: nullptr, or [n] OATGPU_BAYER_* 1..4 (checked by the caller; channels == 3, H, W >= 3): frames / frames2
                              // are Bayer RAW8, [n][H*W], demosaiced in registers
+    const uint32_t *ud_map1; // nullptr, or the undistortion maps of the n streams (plane 0; stream s at + s * ud_stride entries,
+    const uint16_t *ud_map2; //   ud_stride = undistort_map_stride(H, W)): frames / frames2 are remapped in registers, every stream
+    size_t ud_stride;        //   with its own map; not together with bayer
 };
-// 4 pixels a lane with dword accesses: W % 4 == 0 and frames / frames2 / last 4-byte aligned; otherwise one pixel a lane
+// 4 pixels a lane with dword accesses: W % 4 == 0 and frames / frames2 / last 4-byte aligned (with ud_map1: `last` alone, the
+// frames are gathered with unaligned loads); otherwise one pixel a lane
 bool diff_front_is_wide(const Geom &g, const DiffLaunch &a);
 void launch_diff_front(const Geom &g, const DiffLaunch &a, int n_streams, hipStream_t st);
 
@@ -185,8 +189,12 @@ struct BsubLaunch {
     float a, b;
     const int *bayer;        // HOST: nullptr, or [n] OATGPU_BAYER_* 1..4 (checked by the caller; channels == 3, H, W >= 3): frames / frames2
                              // are Bayer RAW8, [n][H*W], demosaiced in registers; bg and acc stay BGR
+    const uint32_t *ud_map1; // nullptr, or the undistortion maps of the n streams (DiffLaunch's): frames / frames2 are remapped in
+    const uint16_t *ud_map2; //   registers, bg and acc are images in undistorted coordinates; not together with bayer
+    size_t ud_stride;
 };
-// 4 pixels a lane: W % 4 == 0, frames / frames2 / bg 4-byte and acc 16-byte aligned; otherwise one pixel a lane
+// 4 pixels a lane: W % 4 == 0, frames / frames2 / bg 4-byte and acc 16-byte aligned (with ud_map1: bg and acc alone); otherwise
+// one pixel a lane
 bool bsubtrack_front_is_wide(const Geom &g, const BsubLaunch &a);
 void launch_bsubtrack_front(const Geom &g, const BsubLaunch &a, int n_streams, hipStream_t st);
 

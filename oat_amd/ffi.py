@@ -130,6 +130,7 @@ SIGNATURES = {
     "oatgpu_debayer_dev": (C.c_int, [_ctx, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p]),
     "oatgpu_set_track_bayer": (C.c_int, [_ctx, C.POINTER(C.c_int32), C.c_int32]),
     "oatgpu_set_tracker_bayer": (C.c_int, [_ctx, C.POINTER(C.c_int32), C.c_int32]),
+    "oatgpu_set_tracker_undistort": (C.c_int, [_ctx, C.c_int32]),
     "oatgpu_set_markers": (C.c_int, [_ctx, C.c_int32, C.POINTER(Marker), C.c_int32]),
     "oatgpu_set_marker_window": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.POINTER(Marker)]),
     "oatgpu_track_markers_dev": (C.c_int, [_ctx, C.c_void_p, C.c_double, C.POINTER(Position), C.POINTER(Position),

@@ -7,6 +7,9 @@
 //                 thresh --bsub: of `oat framefilt bsub` -> `oat posidet thresh` on a GREY source (the subtraction tracker)
 //                 diff --bayer P, hsv --bsub --bayer P: the two BGR chains on a GREY-tagged Bayer RAW8 source (a colour camera's
 //                 own pixel format, PointGreyCam.cpp:48-50): the demosaic is done in the same kernel (oatgpu_set_tracker_bayer)
+//                 diff [--bgr], hsv --bsub, thresh --bsub with --camera-matrix K --distortion-coeffs D: `oat framefilt undistort`
+//                 (Undistorter.cpp:83-88) in front of the chain, done in the same kernel (oatgpu_set_tracker_undistort); a plain
+//                 `diff` then runs the motion tracker on its GREY source
 // Same positional arguments and option names as src/positiondetector/main.cpp:85-271.
 #include "component.hpp"
 
@@ -19,11 +22,16 @@ enum class Kind { HSV, THRESH, DIFF };
 class GpuDetector : public PositionDetector {
 public:
     // bayer: 0, or the OATGPU_BAYER_* pattern of a RAW8 source (GREY-tagged) in front of a BGR chain
-    GpuDetector(const std::string &src, const std::string &snk, Kind kind, bool bgr = false, bool bsub = false, int bayer = 0)
+    // undistort: the calibration of `framefilt undistort` in front of a batched tracker's chain, or nullptr
+    GpuDetector(const std::string &src, const std::string &snk, Kind kind, bool bgr = false, bool bsub = false, int bayer = 0,
+                const UndistortCalibration *undistort = nullptr)
         : PositionDetector(src, snk), kind_(kind), bgr_(bgr && kind == Kind::DIFF), bsub_(bsub && kind != Kind::DIFF), bayer_(bayer)
     {
         oatgpu_default_config(&cfg_);
+        if (undistort) { undistort_ = *undistort; undistort_on_ = true; }
+        difftrk_ = bgr_ || (kind == Kind::DIFF && undistort_on_);     // the motion tracker: a BGR source, or a remap in front
         if (bgr_) { required_color_ = PIX_BGR; cfg_.channels = 3; cfg_.erode = 0; cfg_.dilate = 0; }
+        else if (difftrk_) { required_color_ = PIX_GREY; cfg_.channels = 1; cfg_.erode = 0; cfg_.dilate = 0; }
         else if (bsub_ && kind == Kind::HSV) { required_color_ = PIX_BGR; cfg_.channels = 3; cfg_.erode = 0; cfg_.dilate = 10; }
         else if (bsub_) { required_color_ = PIX_GREY; cfg_.channels = 1; cfg_.erode = 0; cfg_.dilate = 0; }
         else if (kind == Kind::HSV) { required_color_ = PIX_HSV; cfg_.erode = 0; cfg_.dilate = 10; }   // HSVDetector.cpp:42-46
@@ -39,7 +47,7 @@ protected:
     {
         cfg_.rows = (int)p.rows; cfg_.cols = (int)p.cols; cfg_.n_streams = 1;
         gpu_.create(cfg_);
-        if (bgr_) gpu_.check(oatgpu_set_diff_tracker(gpu_.ctx, 1));
+        if (difftrk_) gpu_.check(oatgpu_set_diff_tracker(gpu_.ctx, 1));
         if (bayer_) { const int32_t pat = bayer_; gpu_.check(oatgpu_set_tracker_bayer(gpu_.ctx, &pat, 1)); }
         if (bsub_) {
             gpu_.check(oatgpu_set_bsub_tracker(gpu_.ctx, 1));
@@ -48,13 +56,17 @@ protected:
                 gpu_.check(oatgpu_bsub_set_background(gpu_.ctx, 0, im.px.data()));
             }
         }
+        if (undistort_on_) {                                 // (a background image is one in undistorted coordinates)
+            gpu_.check(oatgpu_set_undistort(gpu_.ctx, 0, undistort_.K, undistort_.dist.data(), (int32_t)undistort_.dist.size()));
+            gpu_.check(oatgpu_set_tracker_undistort(gpu_.ctx, 1));
+        }
     }
     // HSVDetector.cpp:142-173 / SimpleThreshold.cpp:114-134
     // Deferred (oatgpu_set_deferred): the call returns when the frame has left shared memory, PositionDetector::process posts
     // the source, and detect_finish() waits for the kernels and takes the position (PositionDetector.cpp:78-96).
     bool detect_from_shm(const Frame &frame, Position2D &) override
     {
-        if (bgr_ || bsub_) return false;  // the batched trackers' step is synchronous: the frame is copied and the source posted first
+        if (difftrk_ || bsub_) return false;  // the batched trackers' step is synchronous: the frame is copied and the source posted first
         if (!deferred_on_) { gpu_.check(oatgpu_set_deferred(gpu_.ctx, 1)); deferred_on_ = true; }
         gpu_.check(kind_ == Kind::HSV ? oatgpu_detect_hsv(gpu_.ctx, 0, frame.data(), nullptr)
                    : kind_ == Kind::THRESH ? oatgpu_detect_thresh(gpu_.ctx, 0, frame.data(), nullptr)
@@ -72,7 +84,7 @@ protected:
     {
         oatgpu_position r;
         const uint8_t *one[1] = {frame.data()};
-        gpu_.check(bgr_ ? oatgpu_diff_batch(gpu_.ctx, one, 1, &r)
+        gpu_.check(difftrk_ ? oatgpu_diff_batch(gpu_.ctx, one, 1, &r)
                    : bsub_ ? oatgpu_bsub_track_batch(gpu_.ctx, one, 1, bsub_alpha_, &r)
                    : kind_ == Kind::HSV ? oatgpu_detect_hsv(gpu_.ctx, 0, frame.data(), &r)
                    : kind_ == Kind::THRESH ? oatgpu_detect_thresh(gpu_.ctx, 0, frame.data(), &r)
@@ -83,6 +95,8 @@ protected:
     Kind kind_;
     bool bgr_, bsub_;
     int bayer_;
+    bool difftrk_{false}, undistort_on_{false};
+    UndistortCalibration undistort_{};
     bool deferred_on_{false};
     GpuCtx gpu_;
 };
@@ -102,6 +116,9 @@ static void usage()
                  "        --bsub-background FILE.ppm|.pgm  the background image instead of the first frame (it cannot adapt)\n"
                  "        --bayer P  with hsv --bsub: the SOURCE is Bayer RAW8 (GREY-tagged), demosaiced in the same kernel; a background\n"
                  "        image stays BGR\n"
+                 "diff, hsv --bsub, thresh --bsub:\n"
+                 "        --camera-matrix [K11,K12,...,K33] --distortion-coeffs [k1,k2,p1,p2,k3] or [k1,k2,p1,p2,k3,k4,k5,k6]\n"
+                 "        framefilt undistort is done in front of the chain, in the same kernel (both are needed; not with --bayer)\n"
                  "all:    --gpu-index N  HIP device ordinal (default 0)\n";
 }
 
@@ -120,11 +137,13 @@ int main(int argc, char **argv)
         if (type != "hsv" && type != "thresh" && type != "diff") throw std::runtime_error("Selected TYPE is invalid.");
         // option names per TYPE: HSVDetector.cpp:49-75, SimpleThreshold.cpp:49-69, DifferenceDetector.cpp:41-62
         if (type == "hsv")
-            o.apply_config({"h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer"},
+            o.apply_config({"h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer",
+                            "camera-matrix", "distortion-coeffs"},
                            {"tune", "bsub"});
         else if (type == "thresh")
-            o.apply_config({"thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer"}, {"tune", "bsub"});
-        else o.apply_config({"diff-threshold", "blur", "area", "tune", "gpu-index", "bgr", "bayer"}, {"tune", "bgr"});
+            o.apply_config({"thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer",
+                            "camera-matrix", "distortion-coeffs"}, {"tune", "bsub"});
+        else o.apply_config({"diff-threshold", "blur", "area", "tune", "gpu-index", "bgr", "bayer", "camera-matrix", "distortion-coeffs"}, {"tune", "bgr"});
         if (o.has("bgr") && type != "diff") throw std::runtime_error("--bgr goes with TYPE diff only");
         if (type == "diff" && (o.has("bsub") || o.has("bsub-alpha") || o.has("bsub-background")))
             throw std::runtime_error("--bsub goes with TYPE hsv or thresh only");
@@ -140,10 +159,21 @@ int main(int argc, char **argv)
             if (type == "hsv" && !o.has("bsub")) throw std::runtime_error("--bayer with TYPE hsv needs --bsub");
             bayer = bayer_pattern(o.kv["bayer"]);
         }
+        // --camera-matrix / --distortion-coeffs: framefilt undistort in front of a batched tracker's chain (Undistorter.cpp:57-81),
+        // checked before any device is opened: distortion-coeffs first, then camera-matrix
+        UndistortCalibration cal{};
+        const bool undistort = o.has("camera-matrix") || o.has("distortion-coeffs");
+        if (undistort) {
+            if (bayer) throw std::runtime_error("--camera-matrix / --distortion-coeffs and --bayer exclude each other: a RAW8 source cannot be undistorted in the detector's kernel");
+            if (type != "diff" && !o.has("bsub"))
+                throw std::runtime_error("--camera-matrix / --distortion-coeffs with TYPE hsv or thresh need --bsub");
+            cal = read_undistort_calibration(o);
+        }
         if (o.has("tune")) throw std::runtime_error("--tune needs a GUI and is not available in the hip detector");
         auto d = std::make_unique<GpuDetector>(o.positional[1], o.positional[2],
                                                type == "hsv" ? Kind::HSV : type == "thresh" ? Kind::THRESH : Kind::DIFF,
-                                               o.has("bgr") || (bayer && type == "diff"), o.has("bsub"), bayer);
+                                               o.has("bgr") || (bayer && type == "diff"), o.has("bsub"), bayer,
+                                               undistort ? &cal : nullptr);
         d->bsub_alpha_ = o.num("bsub-alpha", 0, 0, 1);
         if (o.has("bsub-background")) d->bsub_background_ = o.kv.at("bsub-background");
         d->cfg_.device = (int)o.num("gpu-index", 0, 0, 64);
