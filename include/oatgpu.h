@@ -48,7 +48,8 @@ extern "C" {
  * oatgpu_diff_sequence_dev, oatgpu_read_diff_mask; the subtraction tracker -- oatgpu_set_bsub_tracker, oatgpu_bsub_reset,
  * oatgpu_bsub_track_batch_dev, oatgpu_bsub_track_batch, oatgpu_bsub_track_sequence_dev, oatgpu_bsub_get_state,
  * oatgpu_read_bsub_mask; Bayer RAW8 ingest -- oatgpu_debayer_filter, oatgpu_debayer_dev, oatgpu_set_track_bayer, with the
- * OATGPU_BAYER_* pattern values; RAW8 frames for the motion and the subtraction tracker -- oatgpu_set_tracker_bayer. */
+ * OATGPU_BAYER_* pattern values; RAW8 frames for the motion and the subtraction tracker -- oatgpu_set_tracker_bayer; the filter
+ * chain behind the motion and the subtraction tracker -- oatgpu_set_tracker_filters, oatgpu_tracker_filtered. */
 
 enum {
     OATGPU_OK = 0,
@@ -531,6 +532,41 @@ int oatgpu_set_marker_filters(oatgpu_ctx *ctx, const oatgpu_marker_filters *f);
  * max_sets is too small.  Nothing is consumed: the call may be repeated.  The chain advances for every frame whether or not
  * this is called; oatgpu_track_collect on a marker-pipeline context retires the slot's filtered record with the slot. */
 int oatgpu_marker_filtered(oatgpu_ctx *ctx, oatgpu_filtered *out, int32_t max_sets);
+
+/* ---- the same chain behind the motion and the subtraction tracker ----
+ *
+ * What a marker-less rig's user records: `posidet diff` (or `framefilt bsub` -> `posidet hsv`) -> `posifilt kalman` (a velocity,
+ * and the frames bridged where the animal stood still or was hidden) -> `posifilt homography` -> `posifilt region`.  While a
+ * chain is configured, every frame of oatgpu_diff_batch, _batch_dev, oatgpu_diff_sequence_dev, oatgpu_bsub_track_batch,
+ * _batch_dev and oatgpu_bsub_track_sequence_dev advances it by one sample per camera stream, in frame order: one launch a frame
+ * on the device, behind that frame's blob analysis; inside the sequence calls, with four frames in flight on three HIP streams,
+ * the launches of consecutive frames are ordered by events -- nothing waits on the device.  Batch calls and sequence calls,
+ * and the two trackers, continue one another: the chain and its one filter state per camera stream are the CONTEXT's -- not
+ * oatgpu_set_kalman's and not the marker chain's.
+ *
+ * The members, their order, their switches and the limits are those of oatgpu_set_marker_filters above; the input per camera
+ * and frame is the detector's result (valid, and the centroid of the integer sums exactly as oatgpu_position.x / .y).  An
+ * invalid detection is no measurement.  A detector publishes no heading: heading_valid = 0, hx = hy = 0.  With kalman off an
+ * invalid detection gives position_valid = 0, x = y = vx = vy = 0 and no region.
+ *
+ * The oatgpu_position results of those calls, their taps and their state are bit for bit what they are without a chain.
+ * oatgpu_detect_diff, oatgpu_bsub_filter, the MOG2 track calls and the marker calls never look at the chain;
+ * oatgpu_set_tracker_bayer, oatgpu_set_tracker_undistort, oatgpu_diff_reset, oatgpu_bsub_reset and oatgpu_bsub_set_background
+ * do not touch the filter state.  oatgpu_set_kalman / oatgpu_set_homography keep their meaning (the foreground result of plain
+ * track calls), and the tracker calls stay refused while they are on.
+ *
+ * Configures the chain.  f = NULL, or all three members off, switches it off and frees it.  A successful call (re)starts every
+ * stream's Kalman state from the reference's initial state; it drains outstanding work.  Everything the chain needs -- state,
+ * a filtered set for each of the four slots, the ordering events -- is made here, never inside a step: an out-of-memory is
+ * OATGPU_E_NOMEM from this call and leaves a working context.  OATGPU_E_INVALID, with nothing changed, when results are
+ * outstanding, a frame set is partly staged, a limit is exceeded, a name is too long or a Kalman parameter is out of range.
+ * Allowed with either tracker on or off, in either order. */
+int oatgpu_set_tracker_filters(oatgpu_ctx *ctx, const oatgpu_marker_filters *f);
+/* The filtered records of the frame sets the LATEST call of the six above delivered: one set for a batch call, n_frames sets
+ * for a sequence call; out[t * n_streams + s].  Returns the number of sets written; OATGPU_E_INVALID when no chain is
+ * configured, no tracker call has run since it was configured, or max_sets is too small.  Nothing is consumed: the call may
+ * be repeated.  The chain advances for every frame whether or not this is called. */
+int oatgpu_tracker_filtered(oatgpu_ctx *ctx, oatgpu_filtered *out, int32_t max_sets);
 
 /* Deferred completion of the stage-by-stage operators below (default off).  With on = 1 a frame filter (oatgpu_mog_filter,
  * _bsub_filter, _mask_filter, _thresh_filter, _undistort_filter, _bgr2hsv, _cvt_color) or a detector (oatgpu_detect_hsv / _thresh / _diff)

@@ -428,6 +428,38 @@ class DifferenceDetector(_Detector):
         return _merge(position, p)
 
 
+def _filter_chain(kalman, homography, regions):
+    """ffi.MarkerFilters of a chain kalman -> homography -> region (oatgpu_set_marker_filters, oatgpu_set_tracker_filters):
+    kalman = None or a dict with any of dt / timeout / sigma_accel / sigma_noise (set_kalman's defaults); homography = None or a
+    3x3 matrix; regions = None or a list of (name, points) with points = [(x, y), ...].  Returns (struct, region names, what
+    the struct points into: to be kept alive across the call)."""
+    f = ffi.MarkerFilters()
+    if kalman is not None:
+        k = dict(dt=0.02, timeout=0.0, sigma_accel=5.0, sigma_noise=0.0)
+        unknown = set(kalman) - set(k)
+        if unknown:
+            raise TypeError(f"unknown kalman option(s) {sorted(unknown)}")
+        k.update(kalman)
+        f.kalman, f.dt, f.timeout, f.sigma_accel, f.sigma_noise = 1, k["dt"], k["timeout"], k["sigma_accel"], k["sigma_noise"]
+    if homography is not None:
+        f.homography = 1
+        f.h = (C.c_double * 9)(*np.asarray(homography, np.float64).reshape(9))
+    regions = list(regions or [])
+    arr = (ffi.Region * max(len(regions), 1))()
+    keep, names = [], []
+    for r, (name, points) in zip(arr, regions):
+        raw = name.encode() if isinstance(name, str) else bytes(name)
+        pts = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 2))
+        keep.append(pts)
+        r.name = raw[:10]                              # (10 bytes leave no room for the terminator: the library refuses)
+        r.n_points = len(pts)
+        r.xy = pts.ctypes.data_as(C.POINTER(C.c_double))
+        names.append(raw.decode())
+    f.n_regions = len(regions)
+    f.regions = arr
+    return f, names, (arr, keep)
+
+
 def _packed_shape(ctx):
     """A BGR / GREY frame of the context, whatever its track calls take at the moment."""
     return (ctx.rows, ctx.cols, 3) if ctx.channels == 3 else (ctx.rows, ctx.cols)
@@ -473,7 +505,32 @@ class _TrackerUndistort:
         self.undistort(True)
 
 
-class MotionTracker(_Detector, _TrackerBayer, _TrackerUndistort):
+class _TrackerFilters:
+    """oatgpu_set_tracker_filters / oatgpu_tracker_filtered for the batched trackers (mirrors HotPath.set_marker_filters /
+    HotPath.marker_filtered)."""
+
+    def set_filters(self, kalman=None, homography=None, regions=None):
+        """oatgpu_set_tracker_filters: the chain behind every camera's detection, in the fixed order kalman -> homography ->
+        region; arguments as HotPath.set_marker_filters.  All None switches the chain off.  A successful call restarts every
+        camera's Kalman state; track, track_dev and track_sequence_dev then advance it by one sample a frame."""
+        f, names, _keep = _filter_chain(kalman, homography, regions)
+        self._chk(self.lib.oatgpu_set_tracker_filters(self.ctx, C.byref(f)))
+        self._region_names = names
+
+    def filtered(self):
+        """oatgpu_tracker_filtered: the filtered records of the frame sets the latest track call delivered -- a list with one
+        entry per frame set (one for track / track_dev, one per frame for track_sequence_dev), each a list of n_streams
+        Filtered.  Nothing is consumed."""
+        n, sets = self.n_streams, max(getattr(self, "_tf_sets", 1), 1)
+        out = (ffi.Filtered * (sets * n))()
+        rc = self.lib.oatgpu_tracker_filtered(self.ctx, out, sets)
+        if rc < 0:
+            self._chk(rc)
+        names = getattr(self, "_region_names", [])
+        return [[Filtered.from_c(out[t * n + s], names) for s in range(n)] for t in range(rc)]
+
+
+class MotionTracker(_Detector, _TrackerBayer, _TrackerUndistort, _TrackerFilters):
     """The batched motion tracker: `framefilt col -C GREY` -> `posidet diff` for N camera streams, one front launch a step
     (oatgpu_set_diff_tracker).  channels = 3: BGR frames (rows, cols, 3); 1: GREY frames (rows, cols).  Options follow
     DifferenceDetector.cpp:47-64 (-d diff-threshold, -b blur, -a area).  A ROI (set_roi_mask) masks the frame first.
@@ -499,11 +556,13 @@ class MotionTracker(_Detector, _TrackerBayer, _TrackerUndistort):
         """frames: sequence of n_streams host arrays -> one Position2D per stream (oatgpu_diff_batch)."""
         fs = [_frame(f, self.frame_shape) for f in frames]
         ptrs = (ffi._u8p * max(len(fs), 1))(*[ffi.u8(f) for f in fs])
+        self._tf_sets = 1                                  # (filtered: one frame set is delivered)
         self._chk(self.lib.oatgpu_diff_batch(self.ctx, ptrs, len(fs), self._pos))
         return self._out()
 
     def track_dev(self, dev_ptr):
         """dev_ptr: device address of n_streams*rows*cols*channels bytes, stream-major (oatgpu_diff_batch_dev)."""
+        self._tf_sets = 1
         self._chk(self.lib.oatgpu_diff_batch_dev(self.ctx, C.c_void_p(dev_ptr), self._pos))
         return self._out()
 
@@ -513,6 +572,7 @@ class MotionTracker(_Detector, _TrackerBayer, _TrackerUndistort):
         T, n = len(dev_ptrs), self.n_streams
         arr = (C.c_void_p * max(T, 1))(*dev_ptrs)
         out = (ffi.Position * max(T * n, 1))()
+        self._tf_sets = T
         self._chk(self.lib.oatgpu_diff_sequence_dev(self.ctx, arr, T, out))
         return [[Position2D.from_c(out[t * n + s]) for s in range(n)] for t in range(T)]
 
@@ -527,7 +587,7 @@ class MotionTracker(_Detector, _TrackerBayer, _TrackerUndistort):
         return out
 
 
-class SubtractionTracker(_Detector, _TrackerBayer, _TrackerUndistort):
+class SubtractionTracker(_Detector, _TrackerBayer, _TrackerUndistort, _TrackerFilters):
     """The batched subtraction tracker: `framefilt bsub` -> `framefilt col -C HSV` -> `posidet hsv` for N camera streams, one front
     launch a step (oatgpu_set_bsub_tracker).  channels = 3: BGR frames (rows, cols, 3) and the h / s / v window on the difference
     image; 1: GREY frames (rows, cols), `framefilt bsub` -> `posidet thresh` with `thresh`.  alpha is bsub's -a (0: the background
@@ -559,12 +619,14 @@ class SubtractionTracker(_Detector, _TrackerBayer, _TrackerUndistort):
         fs = [_frame(f, self.frame_shape) for f in frames]
         ptrs = (ffi._u8p * max(len(fs), 1))(*[ffi.u8(f) for f in fs])
         pos = (ffi.Position * self.n_streams)()
+        self._tf_sets = 1                                  # (filtered: one frame set is delivered)
         self._chk(self.lib.oatgpu_bsub_track_batch(self.ctx, ptrs, len(fs), SubtractionTracker._alpha(self, alpha), pos))
         return [Position2D.from_c(p) for p in pos]
 
     def track_dev(self, dev_ptr, alpha=None):
         """dev_ptr: device address of n_streams*rows*cols*channels bytes, stream-major (oatgpu_bsub_track_batch_dev)."""
         pos = (ffi.Position * self.n_streams)()
+        self._tf_sets = 1
         self._chk(self.lib.oatgpu_bsub_track_batch_dev(self.ctx, C.c_void_p(dev_ptr), SubtractionTracker._alpha(self, alpha), pos))
         return [Position2D.from_c(p) for p in pos]
 
@@ -574,6 +636,7 @@ class SubtractionTracker(_Detector, _TrackerBayer, _TrackerUndistort):
         T, n = len(dev_ptrs), self.n_streams
         arr = (C.c_void_p * max(T, 1))(*dev_ptrs)
         out = (ffi.Position * max(T * n, 1))()
+        self._tf_sets = T
         self._chk(self.lib.oatgpu_bsub_track_sequence_dev(self.ctx, arr, T, SubtractionTracker._alpha(self, alpha), out))
         return [[Position2D.from_c(out[t * n + s]) for s in range(n)] for t in range(T)]
 
@@ -721,30 +784,7 @@ class HotPath(_Detector):
         -> region.  kalman = None or a dict with any of dt / timeout / sigma_accel / sigma_noise (set_kalman's defaults);
         homography = None or a 3x3 matrix; regions = None or a list of (name, points) with points = [(x, y), ...], tested in
         the order given.  All None switches the chain off.  A successful call restarts every camera's Kalman state."""
-        f = ffi.MarkerFilters()
-        if kalman is not None:
-            k = dict(dt=0.02, timeout=0.0, sigma_accel=5.0, sigma_noise=0.0)
-            unknown = set(kalman) - set(k)
-            if unknown:
-                raise TypeError(f"unknown kalman option(s) {sorted(unknown)}")
-            k.update(kalman)
-            f.kalman, f.dt, f.timeout, f.sigma_accel, f.sigma_noise = 1, k["dt"], k["timeout"], k["sigma_accel"], k["sigma_noise"]
-        if homography is not None:
-            f.homography = 1
-            f.h = (C.c_double * 9)(*np.asarray(homography, np.float64).reshape(9))
-        regions = list(regions or [])
-        arr = (ffi.Region * max(len(regions), 1))()
-        keep, names = [], []
-        for r, (name, points) in zip(arr, regions):
-            raw = name.encode() if isinstance(name, str) else bytes(name)
-            pts = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 2))
-            keep.append(pts)
-            r.name = raw[:10]                              # (10 bytes leave no room for the terminator: the library refuses)
-            r.n_points = len(pts)
-            r.xy = pts.ctypes.data_as(C.POINTER(C.c_double))
-            names.append(raw.decode())
-        f.n_regions = len(regions)
-        f.regions = arr
+        f, names, _keep = _filter_chain(kalman, homography, regions)
         self._chk(self.lib.oatgpu_set_marker_filters(self.ctx, C.byref(f)))
         self._region_names = names
 

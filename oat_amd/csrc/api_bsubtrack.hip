@@ -88,8 +88,9 @@ static int bsub_front(oatgpu_ctx *c, const void *f1, const void *f2, double alph
 }
 
 // The back half of the frame in `slot` on stream st, every stream in one launch sequence: the context's erode / dilate and area
-// window.  Touches neither last_slot nor last_morph / last_fin: those stay with the ordinary calls.
-static int bsub_back(oatgpu_ctx *c, int slot, hipStream_t st)
+// window.  Touches neither last_slot nor last_morph / last_fin: those stay with the ordinary calls.  Behind it the filter chain
+// on the slot's records, where one is configured (prev_slot: tracker_filters_launch).
+static int bsub_back(oatgpu_ctx *c, int slot, hipStream_t st, int prev_slot = -1)
 {
     const Geom &g = c->g;
     const int n = c->cfg.n_streams;
@@ -99,22 +100,25 @@ static int bsub_back(oatgpu_ctx *c, int slot, hipStream_t st)
     bb.fin = bsub_mask(c, slot, 2);
     const MorphPlan mp = plan_morph(g, c->cfg.erode, c->cfg.dilate);
     const MorphIssued m = issue_morph(g, mp, bb, bsub_bits(c, slot), 0, n, st);
-    launch_blob(g, bb, m.src, m.ero, mp.dil, c->cfg.min_area, c->cfg.max_area, c->bs.rec.dev() + (size_t)slot * n, 0, n, st, kBlobFull);
+    ResultRec *rd = c->bs.rec.dev() + (size_t)slot * n;
+    launch_blob(g, bb, m.src, m.ero, mp.dil, c->cfg.min_area, c->cfg.max_area, rd, 0, n, st, kBlobFull);
     HIPCHK(c, hipGetLastError());
     c->bs.last = slot;
     c->bs.last_tap = m.tap;
-    return OATGPU_OK;
+    return tracker_filters_launch(c, rd, slot, prev_slot, st);
 }
 
 static void bsub_hand_out(oatgpu_ctx *c, int slot, oatgpu_position *out)
 {
     const int n = c->cfg.n_streams;
     for (int s = 0; s < n; ++s) to_position(c->bs.rec.host()[(size_t)slot * n + s], out + s);
+    tracker_filters_keep(c, slot);
 }
 
 // one synchronous step on frames in device memory; the context is drained (open_sync)
 static int bsub_step(oatgpu_ctx *c, const void *frames_dev, double alpha, oatgpu_position *out)
 {
+    tracker_filters_begin(c);
     int rc = bsub_front(c, frames_dev, nullptr, alpha, 0, 0);
     if (rc) return rc;
     rc = bsub_back(c, 0, c->stream);
@@ -168,10 +172,12 @@ extern "C" int oatgpu_bsub_track_sequence_dev(oatgpu_ctx *c, const void *const *
     if (rc) return rc;
     static_assert(BsubTracker::kSlots == kSeqSlots, "the sequence loop's slots are the tracker's");
     const int n = c->cfg.n_streams;
+    int prev = -1;                         // slot of the frame before (the filter chain's order)
+    tracker_filters_begin(c);
     return run_sequence_in_flight(
         c, n_frames, c->bs.ev_front, c->bs.ev_done, [&](int t) { return t + 1 < n_frames ? 2 : 1; },
         [&](int t, int nf, int q, int q2) { return bsub_front(c, frames_dev[t], nf == 2 ? frames_dev[t + 1] : nullptr, alpha, q, q2); },
-        [&](int q, int, hipStream_t B) { return bsub_back(c, q, B); },
+        [&](int q, int, hipStream_t B) { return bsub_back(c, q, B, std::exchange(prev, q)); },
         [&](int q, int frame) { bsub_hand_out(c, q, out + (size_t)frame * n); });
 }
 

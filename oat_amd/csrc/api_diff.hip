@@ -79,8 +79,9 @@ static int diff_front(oatgpu_ctx *c, const void *f1, const void *f2, int slot, i
 
 // The back half of the frame in `slot` on stream st: once for each maximal run of consecutive streams in the same first-frame
 // state (have[s] != 0: blur as dilation; 0: the first frame is analysed as it is), erode never.  Touches neither last_slot nor
-// last_morph / last_fin: those stay with the ordinary calls.
-static int diff_back(oatgpu_ctx *c, int slot, const char *have, hipStream_t st)
+// last_morph / last_fin: those stay with the ordinary calls.  Behind it the filter chain on the slot's records, where one is
+// configured (prev_slot: tracker_filters_launch).
+static int diff_back(oatgpu_ctx *c, int slot, const char *have, hipStream_t st, int prev_slot = -1)
 {
     const Geom &g = c->g;
     const int n = c->cfg.n_streams;
@@ -99,19 +100,21 @@ static int diff_back(oatgpu_ctx *c, int slot, const char *have, hipStream_t st)
     }
     HIPCHK(c, hipGetLastError());
     c->df.last = slot;
-    return OATGPU_OK;
+    return tracker_filters_launch(c, rd, slot, prev_slot, st);
 }
 
 static void diff_hand_out(oatgpu_ctx *c, int slot, oatgpu_position *out)
 {
     const int n = c->cfg.n_streams;
     for (int s = 0; s < n; ++s) to_position(c->df.rec.host()[(size_t)slot * n + s], out + s);
+    tracker_filters_keep(c, slot);
 }
 
 // one synchronous step on frames in device memory; the context is drained (open_sync)
 static int diff_step(oatgpu_ctx *c, const void *frames_dev, oatgpu_position *out)
 {
     const std::vector<char> have = c->diff_have;
+    tracker_filters_begin(c);
     int rc = diff_front(c, frames_dev, nullptr, 0, 0);
     if (rc) return rc;
     c->diff_have.assign(have.size(), 1);
@@ -166,6 +169,8 @@ extern "C" int oatgpu_diff_sequence_dev(oatgpu_ctx *c, const void *const *frames
     const int n = c->cfg.n_streams;
     const std::vector<char> all(c->diff_have.size(), 1);
     std::vector<char> have;                // the state the launch's first frame met
+    int prev = -1;                         // slot of the frame before (the filter chain's order)
+    tracker_filters_begin(c);
     return run_sequence_in_flight(
         c, n_frames, c->df.ev_front, c->df.ev_done,
         [&](int t) {
@@ -178,7 +183,7 @@ extern "C" int oatgpu_diff_sequence_dev(oatgpu_ctx *c, const void *const *frames
             if (!r) c->diff_have.assign(have.size(), 1);
             return r;
         },
-        [&](int q, int i, hipStream_t B) { return diff_back(c, q, i ? all.data() : have.data(), B); },
+        [&](int q, int i, hipStream_t B) { return diff_back(c, q, i ? all.data() : have.data(), B, std::exchange(prev, q)); },
         [&](int q, int frame) { diff_hand_out(c, q, out + (size_t)frame * n); });
 }
 

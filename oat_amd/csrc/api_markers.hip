@@ -281,6 +281,44 @@ extern "C" int oatgpu_track_markers_dev(oatgpu_ctx *c, const void *frames_dev, d
     return OATGPU_OK;
 }
 
+// The parameters of a chain kalman -> homography -> region as the kernels take them, checked: oatgpu_set_marker_filters' and
+// oatgpu_set_tracker_filters' limits and messages.  Nothing of the context changes.
+int chain_params(oatgpu_ctx *c, const oatgpu_marker_filters *f, MarkerFilterParams &p)
+{
+    memset(&p, 0, sizeof p);
+    if (f->kalman) {
+        if (!(f->dt > 0) || !(f->timeout >= 0) || !(f->sigma_accel >= 0) || !(f->sigma_noise >= 0) || !(f->timeout / f->dt < 2147483647.0))
+            return fail(c, OATGPU_E_INVALID, "kalman: dt must be > 0, timeout / sigma-accel / sigma-noise >= 0");
+        p.kalman = 1;
+        p.dt = f->dt; p.sig_accel = f->sigma_accel; p.sig_noise = f->sigma_noise;
+        p.threshold = (int)(f->timeout / f->dt);                 // KalmanFilter2D.cpp:74-76
+    }
+    if (f->homography) {
+        p.homography = 1;
+        for (int i = 0; i < 9; ++i) p.h[i] = f->h[i];
+    }
+    if (f->n_regions < 0 || f->n_regions > kMaxRegions) return fail(c, OATGPU_E_INVALID, "at most %d regions (got %d)", kMaxRegions, f->n_regions);
+    if (f->n_regions > 0 && !f->regions) return fail(c, OATGPU_E_INVALID, "null argument");
+    p.n_regions = f->n_regions;
+    int at = 0;
+    for (int r = 0; r < f->n_regions; ++r) {
+        const oatgpu_region &g = f->regions[r];
+        if (!memchr(g.name, 0, sizeof g.name))
+            return fail(c, OATGPU_E_INVALID, "region %d: a name takes at most %d bytes", r, (int)sizeof g.name - 1);
+        if (g.n_points < 0 || g.n_points > kMaxRegionPoints)
+            return fail(c, OATGPU_E_INVALID, "region %d (%s): at most %d points (got %d)", r, g.name, kMaxRegionPoints, g.n_points);
+        if (g.n_points > 0 && !g.xy) return fail(c, OATGPU_E_INVALID, "null argument");
+        p.region[r][0] = at; p.region[r][1] = g.n_points;
+        for (int i = 0; i < g.n_points; ++i, ++at)
+            for (int k = 0; k < 2; ++k) {
+                const double v = nearbyint(g.xy[2 * i + k]);     // (cv::Point)cv::Point2d: cvRound, ties to even
+                if (!(fabs(v) <= 32767.0)) return fail(c, OATGPU_E_INVALID, "region %d (%s): point %d is beyond +-32767", r, g.name, i);
+                p.verts[at][k] = (int)v;
+            }
+    }
+    return OATGPU_OK;
+}
+
 // The filter chain behind the combined record: `posifilt kalman` -> `posifilt homography` -> `posifilt region` (oatgpu.h).
 // Everything is checked before anything changes.
 extern "C" int oatgpu_set_marker_filters(oatgpu_ctx *c, const oatgpu_marker_filters *f)
@@ -291,38 +329,8 @@ extern "C" int oatgpu_set_marker_filters(oatgpu_ctx *c, const oatgpu_marker_filt
     const bool on = f && (f->kalman || f->homography || f->n_regions > 0);
     std::vector<MarkerFilterParams> hp(on ? 1 : 0);      // (8 KiB: not on the stack)
     if (on) {
-        MarkerFilterParams &p = hp[0];
-        memset(&p, 0, sizeof p);
-        if (f->kalman) {
-            if (!(f->dt > 0) || !(f->timeout >= 0) || !(f->sigma_accel >= 0) || !(f->sigma_noise >= 0) || !(f->timeout / f->dt < 2147483647.0))
-                return fail(c, OATGPU_E_INVALID, "kalman: dt must be > 0, timeout / sigma-accel / sigma-noise >= 0");
-            p.kalman = 1;
-            p.dt = f->dt; p.sig_accel = f->sigma_accel; p.sig_noise = f->sigma_noise;
-            p.threshold = (int)(f->timeout / f->dt);                 // KalmanFilter2D.cpp:74-76
-        }
-        if (f->homography) {
-            p.homography = 1;
-            for (int i = 0; i < 9; ++i) p.h[i] = f->h[i];
-        }
-        if (f->n_regions < 0 || f->n_regions > kMaxRegions) return fail(c, OATGPU_E_INVALID, "at most %d regions (got %d)", kMaxRegions, f->n_regions);
-        if (f->n_regions > 0 && !f->regions) return fail(c, OATGPU_E_INVALID, "null argument");
-        p.n_regions = f->n_regions;
-        int at = 0;
-        for (int r = 0; r < f->n_regions; ++r) {
-            const oatgpu_region &g = f->regions[r];
-            if (!memchr(g.name, 0, sizeof g.name))
-                return fail(c, OATGPU_E_INVALID, "region %d: a name takes at most %d bytes", r, (int)sizeof g.name - 1);
-            if (g.n_points < 0 || g.n_points > kMaxRegionPoints)
-                return fail(c, OATGPU_E_INVALID, "region %d (%s): at most %d points (got %d)", r, g.name, kMaxRegionPoints, g.n_points);
-            if (g.n_points > 0 && !g.xy) return fail(c, OATGPU_E_INVALID, "null argument");
-            p.region[r][0] = at; p.region[r][1] = g.n_points;
-            for (int i = 0; i < g.n_points; ++i, ++at)
-                for (int k = 0; k < 2; ++k) {
-                    const double v = nearbyint(g.xy[2 * i + k]);     // (cv::Point)cv::Point2d: cvRound, ties to even
-                    if (!(fabs(v) <= 32767.0)) return fail(c, OATGPU_E_INVALID, "region %d (%s): point %d is beyond +-32767", r, g.name, i);
-                    p.verts[at][k] = (int)v;
-                }
-        }
+        const int prc = chain_params(c, f, hp[0]);
+        if (prc) return prc;
     }
     int rc = open_sync(c);
     if (rc) return rc;

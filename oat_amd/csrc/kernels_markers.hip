@@ -214,120 +214,24 @@ void launch_marker_combine(const ResultRec *results, int M, int anchor, int n_st
 }
 
 // ---- the filter chain behind the combined record: `posifilt kalman` -> `posifilt homography` -> `posifilt region` ----
-namespace {
-
-// a stream's filter state between launches, as k_kalman reads and writes it (there in the kernel's own body: moving it into a
-// function shared with this one changed that kernel's register allocation, which is held to the measured one)
-__device__ inline void load_filter(Filter &f, const KalmanState *ks)
-{
-    for (int i = 0; i < 4; ++i) { f.statePre[i] = ld(&ks->statePre[i]); f.statePost[i] = ld(&ks->statePost[i]); f.reported[i] = ld(&ks->reported[i]); }
-    for (int i = 0; i < 16; ++i) { f.Ppre[i] = ld(&ks->Ppre[i]); f.Ppost[i] = ld(&ks->Ppost[i]); }
-    f.meas[0] = ld(&ks->meas[0]); f.meas[1] = ld(&ks->meas[1]);
-    f.found = __hip_atomic_load(&ks->found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    f.missing = __hip_atomic_load(&ks->missing, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    f.aliased = __hip_atomic_load(&ks->aliased, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ inline void store_filter(const Filter &f, KalmanState *ks)
-{
-    for (int i = 0; i < 4; ++i) { st(&ks->statePre[i], f.statePre[i]); st(&ks->statePost[i], f.statePost[i]); }
-    for (int i = 0; i < 16; ++i) { st(&ks->Ppre[i], f.Ppre[i]); st(&ks->Ppost[i], f.Ppost[i]); }
-    st(&ks->meas[0], f.meas[0]); st(&ks->meas[1], f.meas[1]);
-    __hip_atomic_store(&ks->found, f.found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&ks->missing, f.missing, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&ks->aliased, f.aliased, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// cv::pointPolygonTest(contour, pt, measureDist = false) >= 0 for an integer contour and an integer point: OpenCV 3.1's purely
-// integer branch (modules/imgproc/src/geometry.cpp, [OCV-mem]) in 64-bit integers -- a crossing count over the edges
-// (v0 = previous vertex, v), the boundary counted as inside, an empty contour never hit.  The vertices are read from memory.
-__device__ bool point_in_region(const int (*__restrict__ v)[2], int n, long long px, long long py)
-{
-    if (n <= 0) return false;
-    long long x0 = v[n - 1][0], y0 = v[n - 1][1];
-    int crossings = 0;
-    for (int i = 0; i < n; ++i) {
-        const long long x = v[i][0], y = v[i][1];
-        if ((y0 <= py && y <= py) || (y0 > py && y > py) || (x0 < px && x < px)) {
-            if (py == y && (px == x || (py == y0 && ((x0 <= px && px <= x) || (x <= px && px <= x0))))) return true;
-        } else {
-            long long d = (py - y0) * (x - x0) - (px - x0) * (y - y0);
-            if (d == 0) return true;
-            if (y < y0) d = -d;
-            crossings += d > 0;
-        }
-        x0 = x; y0 = y;
-    }
-    return (crossings & 1) != 0;
-}
-
-}  // namespace
-
 // One lane per camera stream, fp64.  The nf (1 or 2) frames of the step are taken IN ORDER in the lane's own loop: the Kalman
 // recurrence of a paired step is not split over the grid as the combiner's frames are.
-//   kalman      KalmanFilter2D::filter on (position_valid, x, y) of the combined record -- a partial-sum x, y under
-//               position_valid == 0 is no measurement; position_valid = velocity_valid = found, position / velocity = the
-//               reported state (k_kalman's, posfilt_inline.h); the heading passes through
-//   homography  HomographyTransform2D::filter (:63-106): the position where valid, velocity and heading where valid through the
-//               matrix with its offsets zeroed; the heading then through cv::normalize of a one-element vector -- multiplied
-//               by the reciprocal of its length (0 where the length is not above DBL_EPSILON), plus 0.0
-//   region      RegionFilter2D::filter (:130-152) where position_valid: (cv::Point)position = cvRound per coordinate, the
-//               regions in configured order, the first hit wins; a coordinate that is not finite or beyond int32 hits none
+// The chain itself -- chain_step, posfilt_inline.h -- is shared with k_tracker_filters (kernels_trackfilt.hip); its input here is
+// the combined record: a partial-sum x, y under position_valid == 0 is no measurement.
 __global__ __launch_bounds__(64) void k_marker_filters(const MarkerFilterParams *__restrict__ p, KalmanState *state,
                                                        const MarkerCombined *in0, const MarkerCombined *in1, MarkerFiltered *out0,
                                                        MarkerFiltered *out1, int nf, int n_streams)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_streams) return;
-    const bool kalman = p->kalman != 0, homography = p->homography != 0;
-    const int n_regions = p->n_regions;
-    KalmanLaunch k;
-    k.state = state; k.dt = p->dt; k.sig_accel = p->sig_accel; k.sig_noise = p->sig_noise; k.threshold = p->threshold; k.ticket = 0u;
+    const bool kalman = p->kalman != 0;
+    const KalmanLaunch k = chain_kalman(p, state);
     Filter f;
     if (kalman) load_filter(f, state + s);
 #pragma unroll 1
     for (int t = 0; t < nf; ++t) {
         const MarkerCombined *in = (t ? in1 : in0) + s;
-        int position_valid = in->position_valid, velocity_valid = 0;
-        const int heading_valid = in->heading_valid;
-        double x = in->x, y = in->y, vx = 0.0, vy = 0.0, hx = in->hx, hy = in->hy;
-        if (kalman) {
-            filter_step(f, k, position_valid != 0, x, y);
-            const double *rep = f.aliased ? f.statePre : f.reported;
-            x = rep[0]; vx = rep[1]; y = rep[2]; vy = rep[3];
-            position_valid = velocity_valid = f.found;
-        }
-        if (homography) {
-            if (position_valid) perspective_point(p->h, x, y);
-            if (velocity_valid) perspective_point(p->h, vx, vy, false);
-            if (heading_valid) {
-                perspective_point(p->h, hx, hy, false);
-                const double len = sqrt(hx * hx + hy * hy);
-                const double scale = len > DBL_EPSILON ? 1.0 / len : 0.0;
-                hx = hx * scale + 0.0;
-                hy = hy * scale + 0.0;
-            }
-        }
-        int region = -1;
-        if (n_regions > 0 && position_valid) {
-            const double rx = rint(x), ry = rint(y);               // cvRound: to nearest, ties to even
-            if (rx >= -2147483648.0 && rx <= 2147483647.0 && ry >= -2147483648.0 && ry <= 2147483647.0) {
-                const long long px = (long long)rx, py = (long long)ry;
-                for (int r = 0; r < n_regions && region < 0; ++r)
-                    if (point_in_region(p->verts + p->region[r][0], p->region[r][1], px, py)) region = r;
-            }
-        }
-        // 64-bit stores, one field (or pair of flags) each (nothing wider than 64 bits)
-        u64 *o = reinterpret_cast<u64 *>((t ? out1 : out0) + s);
-        auto put = [&](int i, u64 v) { __hip_atomic_store(o + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-        put(0, (u64)(unsigned)position_valid | (u64)(unsigned)velocity_valid << 32);
-        put(1, (u64)(unsigned)heading_valid | (u64)(unsigned)(region >= 0) << 32);
-        put(2, (u64)(unsigned)region);
-        put(3, (u64)__double_as_longlong(x));
-        put(4, (u64)__double_as_longlong(y));
-        put(5, (u64)__double_as_longlong(vx));
-        put(6, (u64)__double_as_longlong(vy));
-        put(7, (u64)__double_as_longlong(hx));
-        put(8, (u64)__double_as_longlong(hy));
+        chain_step(p, k, f, in->position_valid, in->heading_valid, in->x, in->y, in->hx, in->hy, (t ? out1 : out0) + s);
     }
     if (kalman) store_filter(f, state + s);
 }

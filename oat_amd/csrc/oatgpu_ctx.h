@@ -145,6 +145,21 @@ struct BsubTracker {
     const u64 *last_tap = nullptr;             // of that frame: where the mask after erode / dilate is (the MORPH tap)
 };
 
+// the filter chain behind the two batched trackers (oatgpu_set_tracker_filters; kernels_trackfilt.hip): kalman ->
+// homography -> region on the result records of a slot, one launch a frame behind the slot's back half.  One chain and one filter
+// state per camera stream for the context -- both trackers advance it; not c->kal's and not the marker chain's.  Everything below
+// is made by the setter, never inside a step.
+struct TrackerFilters {
+    static constexpr int kSlots = 4;           // = DiffTracker::kSlots = BsubTracker::kSlots
+    bool on = false;
+    DevMem<MarkerFilterParams> params;         // device: the chain's parameters and the region table
+    DevMem<KalmanState> state;                 // device: [n] the chain's own filter state
+    HostMem<MarkerFiltered> out;               // host-mapped: [kSlots][n] the slot's filtered set, written by k_tracker_filters through dev()
+    Event ev[kSlots];                          // the slot's filter launch has finished: frame t's launch waits for frame t - 1's
+    std::vector<oatgpu_filtered> last;         // [sets][n] what the latest tracker call delivered (oatgpu_tracker_filtered)
+    int last_sets = 0;
+};
+
 struct oatgpu_ctx {
     StreamLease lease;
     oatgpu_config cfg;
@@ -318,6 +333,7 @@ struct oatgpu_ctx {
     MarkerSet mk; MarkerPipeline mkp; MarkerFilters mf;      // the optional features: dropping one is assignment (c->mkp = {})
     DiffTracker df;
     BsubTracker bs;
+    TrackerFilters tf;
 };
 
 // a back half's erosion and dilation, planned and issued (plan_morph, issue_morph: api_track.hip)
@@ -378,6 +394,11 @@ int upload_frames(oatgpu_ctx *c, const uint8_t *const *frames_host, size_t frame
 // api_markers.hip
 bool own_window_is_nonzero(const oatgpu_config &k);
 int launch_marker_work(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, const StepPlan &plan);
+int chain_params(oatgpu_ctx *c, const oatgpu_marker_filters *f, MarkerFilterParams &p);
+// api_trackfilt.hip
+int tracker_filters_launch(oatgpu_ctx *c, const ResultRec *rec_dev, int slot, int prev_slot, hipStream_t st);
+void tracker_filters_begin(oatgpu_ctx *c);
+void tracker_filters_keep(oatgpu_ctx *c, int slot);
 // api_measure.hip
 void prof_fold(oatgpu_ctx *c);
 #pragma GCC visibility pop

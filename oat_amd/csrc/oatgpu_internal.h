@@ -359,5 +359,11 @@ struct MarkerFilterParams {      // in DEVICE memory, read uniformly by every la
 // advances state[s] (the ticket of KalmanState is not used: every launch of a context runs behind the one before)
 void launch_marker_filters(const MarkerFilterParams *params, KalmanState *state, const MarkerCombined *const *in,
                            MarkerFiltered *const *out, int n_streams, int nf, hipStream_t st);
+// The same chain behind the motion and the subtraction tracker (oatgpu_set_tracker_filters; kernels_trackfilt.hip): ONE frame a
+// launch, one lane per stream.  in[n_streams]: the tracker's result records of the frame's slot, written by the blob kernels
+// earlier on the same HIP stream; out[n_streams] may be host-mapped memory (64-bit stores).  A detector has no heading.  The
+// caller orders the launches of consecutive frames (events): nothing waits on the device.
+void launch_tracker_filters(const MarkerFilterParams *params, KalmanState *state, const ResultRec *in, MarkerFiltered *out,
+                            int n_streams, hipStream_t st);
 
 }  // namespace oatgpu

@@ -144,6 +144,8 @@ SIGNATURES = {
                                                     C.POINTER(Position), C.POINTER(Combined)]),
     "oatgpu_set_marker_filters": (C.c_int, [_ctx, C.POINTER(MarkerFilters)]),
     "oatgpu_marker_filtered": (C.c_int, [_ctx, C.POINTER(Filtered), C.c_int32]),
+    "oatgpu_set_tracker_filters": (C.c_int, [_ctx, C.POINTER(MarkerFilters)]),
+    "oatgpu_tracker_filtered": (C.c_int, [_ctx, C.POINTER(Filtered), C.c_int32]),
     "oatgpu_mog_apply": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_mog_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_bgr2hsv": (C.c_int, [_ctx, _u8p, _u8p]),

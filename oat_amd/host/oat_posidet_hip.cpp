@@ -10,8 +10,13 @@
 //                 diff [--bgr], hsv --bsub, thresh --bsub with --camera-matrix K --distortion-coeffs D: `oat framefilt undistort`
 //                 (Undistorter.cpp:83-88) in front of the chain, done in the same kernel (oatgpu_set_tracker_undistort); a plain
 //                 `diff` then runs the motion tracker on its GREY source
+//                 diff [--bgr|--bayer P], hsv --bsub, thresh --bsub with --kalman / --homography H / --region R: `oat posifilt
+//                 kalman` -> `oat posifilt homography` -> `oat posifilt region` behind the detector, on the device in the same step
+//                 (oatgpu_set_tracker_filters): the SINK carries the filtered Position2D; a plain `diff` then runs the motion
+//                 tracker on its GREY source
 // Same positional arguments and option names as src/positiondetector/main.cpp:85-271.
 #include "component.hpp"
+#include "filter_chain.hpp"
 
 #include <cfloat>
 
@@ -23,13 +28,15 @@ class GpuDetector : public PositionDetector {
 public:
     // bayer: 0, or the OATGPU_BAYER_* pattern of a RAW8 source (GREY-tagged) in front of a BGR chain
     // undistort: the calibration of `framefilt undistort` in front of a batched tracker's chain, or nullptr
+    // filters: a filter chain behind the detector (kalman_ / homography_on_ / regions_ below): the batched trackers have one
     GpuDetector(const std::string &src, const std::string &snk, Kind kind, bool bgr = false, bool bsub = false, int bayer = 0,
-                const UndistortCalibration *undistort = nullptr)
+                const UndistortCalibration *undistort = nullptr, bool filters = false)
         : PositionDetector(src, snk), kind_(kind), bgr_(bgr && kind == Kind::DIFF), bsub_(bsub && kind != Kind::DIFF), bayer_(bayer)
     {
         oatgpu_default_config(&cfg_);
         if (undistort) { undistort_ = *undistort; undistort_on_ = true; }
-        difftrk_ = bgr_ || (kind == Kind::DIFF && undistort_on_);     // the motion tracker: a BGR source, or a remap in front
+        // the motion tracker: a BGR source, a remap in front, or a filter chain behind
+        difftrk_ = bgr_ || (kind == Kind::DIFF && (undistort_on_ || filters));
         if (bgr_) { required_color_ = PIX_BGR; cfg_.channels = 3; cfg_.erode = 0; cfg_.dilate = 0; }
         else if (difftrk_) { required_color_ = PIX_GREY; cfg_.channels = 1; cfg_.erode = 0; cfg_.dilate = 0; }
         else if (bsub_ && kind == Kind::HSV) { required_color_ = PIX_BGR; cfg_.channels = 3; cfg_.erode = 0; cfg_.dilate = 10; }
@@ -41,6 +48,12 @@ public:
     oatgpu_config cfg_;
     double bsub_alpha_{0.0};            // --bsub-alpha: framefilt bsub's -a (BackgroundSubtractor.h)
     std::string bsub_background_;       // --bsub-background: framefilt bsub's -f, PGM/PPM instead of cv::imread's formats
+    // the filter chain behind a batched tracker (--kalman / --homography / --region): the SINK then carries the filtered Position2D
+    bool kalman_{false}, homography_on_{false};
+    double dt_{0.02}, timeout_{0.0}, sig_accel_{5.0}, sig_noise_{0.0};      // KalmanFilter2D.cpp:69-85
+    double homography_[9]{1, 0, 0, 0, 1, 0, 0, 0, 1};
+    std::vector<RegionDef> regions_;
+    bool chain_on() const { return kalman_ || homography_on_ || !regions_.empty(); }
 
 protected:
     void configure_for(const FrameParams &p) override
@@ -59,6 +72,14 @@ protected:
         if (undistort_on_) {                                 // (a background image is one in undistorted coordinates)
             gpu_.check(oatgpu_set_undistort(gpu_.ctx, 0, undistort_.K, undistort_.dist.data(), (int32_t)undistort_.dist.size()));
             gpu_.check(oatgpu_set_tracker_undistort(gpu_.ctx, 1));
+        }
+        if (chain_on()) {
+            std::vector<oatgpu_region> rs;
+            oatgpu_marker_filters f = chain_filters(regions_, rs);
+            f.kalman = kalman_; f.dt = dt_; f.timeout = timeout_; f.sigma_accel = sig_accel_; f.sigma_noise = sig_noise_;
+            f.homography = homography_on_;
+            std::copy(homography_, homography_ + 9, f.h);
+            gpu_.check(oatgpu_set_tracker_filters(gpu_.ctx, &f));
         }
     }
     // HSVDetector.cpp:142-173 / SimpleThreshold.cpp:114-134
@@ -91,6 +112,11 @@ protected:
                                            : oatgpu_detect_diff(gpu_.ctx, 0, frame.data(), &r));
         position.position_valid = r.valid != 0;                   // DetectorFunc.cpp:46,58-60
         if (r.valid) { position.position.x = r.x; position.position.y = r.y; }
+        if (chain_on()) {                                         // ... behind posifilt kalman / homography / region
+            oatgpu_filtered f;
+            if (oatgpu_tracker_filtered(gpu_.ctx, &f, 1) != 1) gpu_.check(OATGPU_E_INVALID);
+            publish_filtered(position, f, regions_, homography_on_ ? homography_ : nullptr);
+        }
     }
     Kind kind_;
     bool bgr_, bsub_;
@@ -119,6 +145,14 @@ static void usage()
                  "diff, hsv --bsub, thresh --bsub:\n"
                  "        --camera-matrix [K11,K12,...,K33] --distortion-coeffs [k1,k2,p1,p2,k3] or [k1,k2,p1,p2,k3,k4,k5,k6]\n"
                  "        framefilt undistort is done in front of the chain, in the same kernel (both are needed; not with --bayer)\n"
+                 "        --kalman [--dt s] [--timeout s] [--sigma-accel a] [--sigma-noise n]  --homography [h11,h12,...,h33]\n"
+                 "        --region 'NAME=[[x0,y0],[x1,y1],...]' (repeatable; at most 16 regions of 64 points, a name of at most 9 bytes)\n"
+                 "        posifilt kalman, posifilt homography and posifilt region behind the detector, in this order, each on its own, on\n"
+                 "        the device in the same step: the SINK carries the filtered position -- position and velocity of the Kalman\n"
+                 "        filter (defaults dt 0.02, timeout 0, sigma-accel 5, sigma-noise 0), WORLD units with the matrix, the name of\n"
+                 "        the first region (command-line order) that holds the position.  In a -c file: kalman = true, dt = .., homography\n"
+                 "        = [..] and one [[KEY.region]] table per region with name and points.  Long names only (-T is thresh's window).\n"
+                 "        hsv and thresh need --bsub for them; a plain diff runs the motion tracker on its GREY source.\n"
                  "all:    --gpu-index N  HIP device ordinal (default 0)\n";
 }
 
@@ -130,7 +164,7 @@ int main(int argc, char **argv)
         Options o = Options::parse(argc, argv,
             {{"H", "h-thresh"}, {"S", "s-thresh"}, {"V", "v-thresh"}, {"T", "thresh"}, {"e", "erode"},
              {"d", is_diff ? "diff-threshold" : "dilate"}, {"b", "blur"}, {"a", "area"}, {"t", "tune"}, {"h", "help"}, {"v", "version"}},
-            {"help", "version", "tune", "bgr", "bsub"});
+            {"help", "version", "tune", "bgr", "bsub", "kalman"});
         if (o.has("version")) { std::cout << "oat-posidet-hip (MI355X drop-in, liboatgpu ABI " << oatgpu_abi_version() << ")\n"; return 0; }
         if (o.has("help") || o.positional.size() != 3) { usage(); return o.has("help") ? 0 : -1; }
         const std::string type = o.positional[0];
@@ -138,12 +172,14 @@ int main(int argc, char **argv)
         // option names per TYPE: HSVDetector.cpp:49-75, SimpleThreshold.cpp:49-69, DifferenceDetector.cpp:41-62
         if (type == "hsv")
             o.apply_config({"h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer",
-                            "camera-matrix", "distortion-coeffs"},
-                           {"tune", "bsub"});
+                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography"},
+                           {"tune", "bsub", "kalman"});
         else if (type == "thresh")
             o.apply_config({"thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer",
-                            "camera-matrix", "distortion-coeffs"}, {"tune", "bsub"});
-        else o.apply_config({"diff-threshold", "blur", "area", "tune", "gpu-index", "bgr", "bayer", "camera-matrix", "distortion-coeffs"}, {"tune", "bgr"});
+                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography"},
+                           {"tune", "bsub", "kalman"});
+        else o.apply_config({"diff-threshold", "blur", "area", "tune", "gpu-index", "bgr", "bayer", "camera-matrix", "distortion-coeffs",
+                             "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography"}, {"tune", "bgr", "kalman"});
         if (o.has("bgr") && type != "diff") throw std::runtime_error("--bgr goes with TYPE diff only");
         if (type == "diff" && (o.has("bsub") || o.has("bsub-alpha") || o.has("bsub-background")))
             throw std::runtime_error("--bsub goes with TYPE hsv or thresh only");
@@ -169,11 +205,36 @@ int main(int argc, char **argv)
                 throw std::runtime_error("--camera-matrix / --distortion-coeffs with TYPE hsv or thresh need --bsub");
             cal = read_undistort_calibration(o);
         }
+        // --kalman / --homography / --region (or the [[KEY.region]] tables of the -c file): the filter chain behind a batched tracker,
+        // checked before any device is opened
+        std::vector<RegionDef> regions;
+        if (o.all.count("region")) for (const std::string &r : o.all["region"]) regions.push_back(parse_region(r));
+        else if (!o.config_file.empty()) regions = read_region_tables(o.config_file, o.config_key);
+        double homography[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        const bool filters = o.has("kalman") || o.has("homography") || !regions.empty();
+        for (const char *k : {"dt", "timeout", "sigma-accel", "sigma-noise"})
+            if (o.has(k) && !o.has("kalman")) throw std::runtime_error(std::string("--") + k + " is a parameter of --kalman");
+        if (filters) {
+            if (type != "diff" && !o.has("bsub"))
+                throw std::runtime_error("--kalman / --homography / --region with TYPE " + type + " need --bsub: the filter chain runs behind "
+                                         "the batched trackers (diff, hsv --bsub, thresh --bsub), not behind the single-stage detector");
+            if (regions.size() > 16) throw std::runtime_error("--region: " + std::to_string(regions.size()) + " regions, at most 16");
+            if (o.has("kalman") && !(o.num("dt", 0.02, 0, 1e9) > 0)) throw std::runtime_error("--kalman: --dt must be > 0");
+        }
+        const bool homography_on = o.arr9("homography", homography);
         if (o.has("tune")) throw std::runtime_error("--tune needs a GUI and is not available in the hip detector");
         auto d = std::make_unique<GpuDetector>(o.positional[1], o.positional[2],
                                                type == "hsv" ? Kind::HSV : type == "thresh" ? Kind::THRESH : Kind::DIFF,
                                                o.has("bgr") || (bayer && type == "diff"), o.has("bsub"), bayer,
-                                               undistort ? &cal : nullptr);
+                                               undistort ? &cal : nullptr, filters);
+        d->kalman_ = o.has("kalman");
+        d->dt_ = o.num("dt", 0.02, 0, 1e9);                         // KalmanFilter2D.cpp:69-85 (lower bound 0)
+        d->timeout_ = o.num("timeout", 0.0, 0, 1e18);
+        d->sig_accel_ = o.num("sigma-accel", 5.0, 0, 1e18);
+        d->sig_noise_ = o.num("sigma-noise", 0.0, 0, 1e18);
+        d->homography_on_ = homography_on;
+        std::copy(homography, homography + 9, d->homography_);
+        d->regions_ = regions;
         d->bsub_alpha_ = o.num("bsub-alpha", 0, 0, 1);
         if (o.has("bsub-background")) d->bsub_background_ = o.kv.at("bsub-background");
         d->cfg_.device = (int)o.num("gpu-index", 0, 0, 64);

@@ -40,6 +40,7 @@
 // frames (a mono camera or `framefilt col -C GREY`; SimpleThreshold.cpp:46 requires them), the one-channel model
 // and the intensity window of SimpleThreshold.cpp:171-174 in the same fused launches.
 #include "component.hpp"
+#include "filter_chain.hpp"
 #include "scatter_tracker.hpp"
 #include <chrono>
 #include <cmath>
@@ -173,121 +174,7 @@ static std::vector<oatgpu_marker> read_marker_tables(const std::string &file, co
 }
 
 // ---- the filter chain behind the combined record (oatgpu_set_marker_filters): --mean-kalman, --mean-homography, --region ----
-// One `posifilt region` polygon: --region 'NAME=[[x0,y0],[x1,y1],...]' (repeatable, command-line order is region order), or a
-// [[KEY.region]] table of the -c file with name = "NAME" and points = [[x0,y0],...].  The library's limits are checked here,
-// before a device is opened: at most 16 regions of at most 64 points, a name of 1 to 9 bytes (the reference's strcpy overruns its
-// 10-byte field with more), every coordinate within +-32767 once rounded.
-struct RegionDef {
-    std::string name;
-    std::vector<double> xy;
-};
-static std::vector<double> parse_region_points(const std::string &text, const std::string &where)
-{
-    auto bad = [&](const char *what) { return std::runtime_error(where + ": " + what + " in '" + text + "' (expected [[x0,y0],[x1,y1],...])"); };
-    const char *p = text.c_str();
-    auto skip = [&] { while (*p == ' ' || *p == '\t') ++p; };
-    auto number = [&](double &v) {
-        skip();
-        char *end = nullptr;
-        v = strtod(p, &end);
-        if (end == p) throw bad("expected a number");
-        p = end;
-        skip();
-    };
-    std::vector<double> xy;
-    skip();
-    if (*p++ != '[') throw bad("expected '['");
-    skip();
-    while (*p != ']') {
-        if (*p++ != '[') throw bad("a point is a pair [x,y]");
-        double x, y;
-        number(x);
-        if (*p++ != ',') throw bad("a point is a pair [x,y]");
-        number(y);
-        if (*p++ != ']') throw bad("a point is a pair [x,y]");
-        xy.push_back(x); xy.push_back(y);
-        skip();
-        if (*p == ',') { ++p; skip(); if (*p == ']') throw bad("expected a point"); }
-        else if (*p != ']') throw bad("expected ',' or ']'");
-    }
-    ++p;
-    skip();
-    if (*p) throw bad("text behind the closing ']'");
-    return xy;
-}
-static void check_region(const RegionDef &r, const std::string &where)
-{
-    if (r.name.empty()) throw std::runtime_error(where + ": a region needs a name");
-    if (r.name.size() > 9) throw std::runtime_error(where + ": the name '" + r.name + "' is longer than 9 bytes");
-    if (r.xy.size() / 2 > 64) throw std::runtime_error(where + ": region '" + r.name + "' has " + std::to_string(r.xy.size() / 2) + " points, at most 64");
-    for (double v : r.xy)
-        if (!(std::fabs(std::nearbyint(v)) <= 32767.0)) throw std::runtime_error(where + ": region '" + r.name + "' has a coordinate beyond +-32767");
-}
-static RegionDef parse_region(const std::string &text)
-{
-    const size_t eq = text.find('=');
-    if (eq == std::string::npos) throw std::runtime_error("--region: expected NAME=[[x0,y0],[x1,y1],...], got '" + text + "'");
-    RegionDef r;
-    r.name = text.substr(0, eq);
-    r.xy = parse_region_points(text.substr(eq + 1), "--region");
-    check_region(r, "--region");
-    return r;
-}
-// every [[KEY.region]] table of the -c file, in file order; points may span lines
-static std::vector<RegionDef> read_region_tables(const std::string &file, const std::string &key)
-{
-    std::vector<RegionDef> out;
-    std::ifstream in(file);
-    if (!in) return out;
-    auto trim = [](std::string t) {
-        const size_t a = t.find_first_not_of(" \t\r\n"), b = t.find_last_not_of(" \t\r\n");
-        return a == std::string::npos ? std::string() : t.substr(a, b - a + 1);
-    };
-    auto next = [&](std::string &line) {
-        if (!std::getline(in, line)) return false;
-        const size_t hash = line.find('#');
-        if (hash != std::string::npos) line = line.substr(0, hash);
-        line = trim(line);
-        return true;
-    };
-    auto depth = [](const std::string &v) { int d = 0; for (char ch : v) d += ch == '[' ? 1 : ch == ']' ? -1 : 0; return d; };
-    const std::string header = "[[" + key + ".region]]", where = header;
-    std::vector<bool> named, pointed;
-    std::string line;
-    bool inside = false;
-    while (next(line)) {
-        if (line.empty()) continue;
-        if (line.front() == '[' && line.find('=') == std::string::npos) {
-            std::string h;
-            for (char ch : line) if (ch != ' ' && ch != '\t') h += ch;
-            inside = h == header;
-            if (inside) { out.emplace_back(); named.push_back(false); pointed.push_back(false); }
-            continue;
-        }
-        if (!inside) continue;
-        const size_t eq = line.find('=');
-        if (eq == std::string::npos) throw std::runtime_error(where + ": expected key = value");
-        const std::string k = trim(line.substr(0, eq));
-        std::string val = trim(line.substr(eq + 1)), more;
-        while (depth(val) > 0 && next(more)) val += " " + more;
-        if (k == "name") {
-            if (val.size() < 2 || (val.front() != '"' && val.front() != '\'') || val.back() != val.front())
-                throw std::runtime_error(where + ": name must be a string, got " + val);
-            out.back().name = val.substr(1, val.size() - 2);
-            named.back() = true;
-        } else if (k == "points") {
-            out.back().xy = parse_region_points(val, where);
-            pointed.back() = true;
-        } else {
-            throw std::runtime_error(where + ": unknown key '" + k + "' (name, points)");
-        }
-    }
-    for (size_t i = 0; i < out.size(); ++i) {
-        if (!named[i] || !pointed[i]) throw std::runtime_error(where + ": a region table holds name and points");
-        check_region(out[i], where);
-    }
-    return out;
-}
+// (--region and the [[KEY.region]] tables: parse_region, check_region, read_region_tables of filter_chain.hpp)
 
 class BatchedTracker : public Component {
 public:
@@ -441,18 +328,11 @@ protected:
             combined_.resize(n_);
             if (marker_ring_) gpu_.check(oatgpu_set_marker_pipeline(gpu_.ctx, 1));
             if (chain_on()) {
-                std::vector<oatgpu_region> rs(regions_.size());
-                for (size_t i = 0; i < rs.size(); ++i) {
-                    std::strncpy(rs[i].name, regions_[i].name.c_str(), sizeof rs[i].name);
-                    rs[i].n_points = (int32_t)(regions_[i].xy.size() / 2);
-                    rs[i].xy = regions_[i].xy.data();
-                }
-                oatgpu_marker_filters f{};
+                std::vector<oatgpu_region> rs;
+                oatgpu_marker_filters f = chain_filters(regions_, rs);
                 f.kalman = mean_kalman_; f.dt = dt_; f.timeout = timeout_; f.sigma_accel = sig_accel_; f.sigma_noise = sig_noise_;
                 f.homography = mean_homography_on_;
                 std::copy(mean_homography_, mean_homography_ + 9, f.h);
-                f.n_regions = (int32_t)rs.size();
-                f.regions = rs.data();
                 gpu_.check(oatgpu_set_marker_filters(gpu_.ctx, &f));
                 filtered_.resize(n_);
             }
@@ -567,18 +447,7 @@ protected:
         pos.heading_valid = c.heading_valid != 0;
         pos.heading.x = c.hx; pos.heading.y = c.hy;
         if (chain_on()) {                                               // ... behind posifilt kalman / homography / region
-            const oatgpu_filtered &f = filtered_[s];
-            pos.position_valid = f.position_valid != 0;
-            pos.position.x = f.x; pos.position.y = f.y;
-            pos.velocity_valid = f.velocity_valid != 0;
-            pos.velocity.x = f.vx; pos.velocity.y = f.vy;
-            pos.heading_valid = f.heading_valid != 0;
-            pos.heading.x = f.hx; pos.heading.y = f.hy;
-            if (f.region_valid) {                                       // RegionFilter2D.cpp:140-146
-                pos.region_valid = true;
-                std::strncpy(pos.region, regions_[(size_t)f.region].name.c_str(), sizeof pos.region - 1);
-            }
-            if (mean_homography_on_) pos.setCoordSystem(DistanceUnit::WORLD, mean_homography_);   // HomographyTransform2D.cpp:102
+            publish_filtered(pos, filtered_[s], regions_, mean_homography_on_ ? mean_homography_ : nullptr);
         }
         put(position_sinks_[s], shared_positions_[s], pos);
     }

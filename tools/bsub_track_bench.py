@@ -7,6 +7,7 @@ against the way the same work had to be done before it -- per camera stream `oat
     python tools/bsub_track_bench.py --ktrace RESULTS.db      # the kernels of a rocprofv3 --kernel-trace run of --quick
     python tools/bsub_track_bench.py --bayer [--steps 200] [--warmup 20] [--quick]      # the RAW8 leg: tools/tracker_bayer_legs.py
     python tools/bsub_track_bench.py --undistort [--steps 200] [--warmup 20] [--quick]  # the lens leg: tools/tracker_undistort_legs.py
+    python tools/bsub_track_bench.py --filters [--steps 200] [--warmup 20] [--quick]    # the filter chain: tools/tracker_filters_legs.py
 
 Shapes: 1 x 4K, 16 x 1080p and 1 x 640x480, BGR frames, alpha 0 and 0.01; the window is V >= 60 on the difference image,
 erode 0, dilate 10 (the reference's default), three moving discs a camera.  Legs, us a frame set:
@@ -99,6 +100,7 @@ def main():
     ap.add_argument("--bayer", action="store_true", help="the RAW8 leg: demosaic inside the front kernel against oatgpu_debayer_dev + BGR")
     ap.add_argument("--undistort", action="store_true",
                     help="the lens leg: remap inside the front kernel against oatgpu_undistort_dev + the packed call")
+    ap.add_argument("--filters", action="store_true", help="the filter chain behind the tracker (kalman, homography, regions) on and off")
     a = ap.parse_args()
     if a.ktrace:
         print(json.dumps(ktrace(a.ktrace)))
@@ -120,6 +122,15 @@ def main():
             shapes += tracker_bayer_legs.run(lambda rows, cols, n: oat_amd.SubtractionTracker(
                 rows, cols, n_streams=n, channels=3, alpha=alpha, erode=0, dilate=10, area=AREA, **WINDOW), a.steps, a.warmup, {"alpha": alpha})
         print(json.dumps({"tool": "bsub_track_bench --bayer", "unit": "us a frame set, host clock around synchronous calls, median",
+                          "library": os.path.relpath(oat_amd.lib_path(), ROOT), "shapes": shapes, "device": torch.cuda.get_device_name(0)}))
+        return
+    if a.filters:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import tracker_filters_legs
+        maker = lambda alpha: lambda rows, cols, n: oat_amd.SubtractionTracker(  # noqa: E731
+            rows, cols, n_streams=n, channels=3, alpha=alpha, erode=0, dilate=10, area=AREA, **WINDOW)
+        shapes = tracker_filters_legs.run([({"alpha": alpha}, maker(alpha)) for alpha in ALPHAS], a.steps, a.warmup)
+        print(json.dumps({"tool": "bsub_track_bench --filters", "unit": "us a frame set, host clock around synchronous calls, median",
                           "library": os.path.relpath(oat_amd.lib_path(), ROOT), "shapes": shapes, "device": torch.cuda.get_device_name(0)}))
         return
     if a.undistort:

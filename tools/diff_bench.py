@@ -6,6 +6,7 @@ same work had to be done before it: per camera stream `oatgpu_cvt_color` BGR -> 
     python tools/diff_bench.py [--steps 200] [--warmup 20] [--quick]
     python tools/diff_bench.py --bayer [--steps 200] [--warmup 20] [--quick]      # the RAW8 leg: tools/tracker_bayer_legs.py
     python tools/diff_bench.py --undistort [--steps 200] [--warmup 20] [--quick]  # the lens leg: tools/tracker_undistort_legs.py
+    python tools/diff_bench.py --filters [--steps 200] [--warmup 20] [--quick]    # the filter chain: tools/tracker_filters_legs.py
 
 Shapes: 1 x 4K, 16 x 1080p and 1 x 640x480, each with BGR and with GREY frames; diff_threshold 10, blur 2, three moving discs a
 camera.  Legs, us a frame set:
@@ -57,12 +58,23 @@ def main():
     ap.add_argument("--bayer", action="store_true", help="the RAW8 leg: demosaic inside the front kernel against oatgpu_debayer_dev + BGR")
     ap.add_argument("--undistort", action="store_true",
                     help="the lens leg: remap inside the front kernel against oatgpu_undistort_dev + the packed call")
+    ap.add_argument("--filters", action="store_true", help="the filter chain behind the tracker (kalman, homography, regions) on and off")
     a = ap.parse_args()
     if a.quick:
         a.steps, a.warmup = 16, 4
     import numpy as np
     import torch
     import oat_amd
+    if a.filters:
+        if not torch.cuda.is_available():
+            raise SystemExit("diff_bench: no GPU (nothing is measured without one)")
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import tracker_filters_legs
+        make = lambda rows, cols, n: oat_amd.MotionTracker(rows, cols, n_streams=n, channels=3, diff_threshold=10, blur=2, area=AREA)  # noqa: E731
+        shapes = tracker_filters_legs.run([({}, make)], a.steps, a.warmup)
+        print(json.dumps({"tool": "diff_bench --filters", "unit": "us a frame set, host clock around synchronous calls, median",
+                          "library": os.path.relpath(oat_amd.lib_path(), ROOT), "shapes": shapes, "device": torch.cuda.get_device_name(0)}))
+        return
     if a.bayer:
         if not torch.cuda.is_available():
             raise SystemExit("diff_bench: no GPU (nothing is measured without one)")
