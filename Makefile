@@ -16,7 +16,7 @@ OBJS     = $(UNITS:%=$(CSRC)/%.o)
 
 all: $(LIB) oracle
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/oatgpu_internal.h $(CSRC)/hip_owned.h $(CSRC)/hsv_inline.h $(CSRC)/debayer_inline.h $(CSRC)/undistort_inline.h $(CSRC)/maskwords_inline.h $(CSRC)/posfilt_inline.h include/oatgpu.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/oatgpu_internal.h $(CSRC)/hip_owned.h $(CSRC)/hsv_inline.h $(CSRC)/debayer_inline.h $(CSRC)/undistort_inline.h $(CSRC)/pixel_source_inline.h $(CSRC)/maskwords_inline.h $(CSRC)/posfilt_inline.h include/oatgpu.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(API:%=$(CSRC)/%.o): $(CSRC)/oatgpu_ctx.h

@@ -6,72 +6,30 @@
 extern "C" int oatgpu_set_diff_tracker(oatgpu_ctx *c, int32_t on)
 {
     if (!c) return OATGPU_E_INVALID;
-    if (c->ring_count || c->staged_count) return fail(c, OATGPU_E_INVALID, "set_diff_tracker while enqueued results are outstanding");
-    if (!on) {
-        if (!c->df.on) return OATGPU_OK;
-        const int rc = open_sync(c);
-        if (rc) return rc;
-        c->df = {};
+    const size_t n = c->cfg.n_streams, npx = (size_t)c->g.H * c->g.W;
+    DevMem<uint8_t> last;                // built aside like the tracker; diff_last stays the context's: it outlives the tracker
+    const int rc = set_batched_tracker(c, c->df, on, "diff", [&](DiffTracker &df, bool &ok) {
+        ok = c->diff_last || last.alloc(n * npx) == hipSuccess;
+        df.last_dilated.assign(n, 0);
         return OATGPU_OK;
-    }
-    if (c->df.on) return OATGPU_OK;
-    const int rc = open_sync(c);
-    if (rc) return rc;
-    const Geom &g = c->g;
-    const size_t n = c->cfg.n_streams, NW = (size_t)g.Palloc / 64, K = DiffTracker::kSlots, npx = (size_t)g.H * g.W;
-    DiffTracker df;                      // built aside: the context takes it when everything worked
-    DevMem<uint8_t> last;
-    bool ok = c->diff_last || last.alloc(n * npx) == hipSuccess;
-    ok = ok && df.bits.alloc(K * n * NW * 8) == hipSuccess;
-    ok = ok && df.masks.alloc(K * 2 * n * NW * 8) == hipSuccess;
-    ok = ok && df.rec.alloc(K * n * sizeof(ResultRec), hipHostMallocMapped) == hipSuccess;
-    // (the taps: words beyond the frame are never written by the back half)
-    ok = ok && hipMemsetAsync(df.bits, 0, K * n * NW * 8, c->stream) == hipSuccess;
-    ok = ok && hipMemsetAsync(df.masks, 0, K * 2 * n * NW * 8, c->stream) == hipSuccess;
-    for (auto &e : df.ev_front) ok = ok && e.create(hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
-    for (auto &e : df.ev_done) ok = ok && e.create(hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
-    if (!ok) return fail(c, OATGPU_E_NOMEM, "diff tracker: allocation failed: %s", hipGetErrorString(hipGetLastError()));
-    df.last_dilated.assign(n, 0);
-    df.on = true;
-    if (!c->diff_last) c->diff_last = std::move(last);
-    c->df = std::move(df);
-    return OATGPU_OK;
+    });
+    if (!rc && last) c->diff_last = std::move(last);
+    return rc;
 }
 
 extern "C" int oatgpu_diff_reset(oatgpu_ctx *c, int32_t s)
 {
     if (!c) return OATGPU_E_INVALID;
-    if (s < -1 || s >= c->cfg.n_streams) return fail(c, OATGPU_E_INVALID, "stream index %d out of range", s);
-    if (s < 0) c->diff_have.assign((size_t)c->cfg.n_streams, 0);
-    else c->diff_have[(size_t)s] = 0;
-    return OATGPU_OK;
+    return reset_have(c, c->diff_have, s);
 }
-
-// what a diff step refuses, checked before anything is read or has moved
-static int diff_refusals(oatgpu_ctx *c, const char *what)
-{
-    if (!c->df.on) return fail(c, OATGPU_E_INVALID, "the diff tracker is off (oatgpu_set_diff_tracker)");
-    if (c->ring_count || c->staged_count) return fail(c, OATGPU_E_INVALID, "%s while enqueued results are outstanding", what);
-    if (c->kal_on) return fail(c, OATGPU_E_INVALID, "%s with the position filter on (oatgpu_set_kalman) is not supported", what);
-    if (c->homo_on) return fail(c, OATGPU_E_INVALID, "%s with a homography on (oatgpu_set_homography) is not supported", what);
-    if (c->ud_track) return fail(c, OATGPU_E_INVALID, "%s with undistortion on (oatgpu_set_track_undistort) is not supported", what);
-    if (c->by_track) return fail(c, OATGPU_E_INVALID, "%s with Bayer frames on (oatgpu_set_track_bayer) is not supported", what);
-    return OATGPU_OK;
-}
-
-static u64 *diff_bits(oatgpu_ctx *c, int slot) { return c->df.bits + (size_t)slot * c->cfg.n_streams * (c->g.Palloc >> 6); }
-static u64 *diff_mask(oatgpu_ctx *c, int slot, int which) { return c->df.masks + ((size_t)slot * 2 + which) * c->cfg.n_streams * (c->g.Palloc >> 6); }
 
 // The front kernel of one frame set (f2: and the next, every stream has a last image) on stream A into the bits of `slot`
 // (and slot2).  have[] is the state the frame(s) met; diff_have moves on.
 static int diff_front(oatgpu_ctx *c, const void *f1, const void *f2, int slot, int slot2)
 {
     DiffLaunch a{};
-    a.frames = (const uint8_t *)f1; a.frames2 = (const uint8_t *)f2; a.channels = c->cfg.channels; a.last = c->diff_last;
-    a.have_last = c->diff_have.data(); a.bits = diff_bits(c, slot); a.bits2 = f2 ? diff_bits(c, slot2) : nullptr;
-    a.roi = c->roi; a.thr = c->cfg.diff_threshold; a.bayer = tracker_bayer(c);
-    tracker_undistort(c, a);
+    tracker_front(c, c->df, f1, f2, slot, slot2, a);
+    a.last = c->diff_last; a.have_last = c->diff_have.data(); a.thr = c->cfg.diff_threshold;
     launch_diff_front(c->g, a, c->cfg.n_streams, c->stream);
     HIPCHK(c, hipGetLastError());
     return OATGPU_OK;
@@ -86,10 +44,10 @@ static int diff_back(oatgpu_ctx *c, int slot, const char *have, hipStream_t st, 
     const Geom &g = c->g;
     const int n = c->cfg.n_streams;
     BlobBuffers bb = c->bb[slot].b;
-    bb.morph = diff_mask(c, slot, 0);
-    bb.fin = diff_mask(c, slot, 1);
-    const u64 *src = diff_bits(c, slot);
-    ResultRec *rd = c->df.rec.dev() + (size_t)slot * n;
+    bb.morph = c->df.mask(slot, 0);
+    bb.fin = c->df.mask(slot, 1);
+    const u64 *src = c->df.bits_of(slot);
+    ResultRec *rd = c->df.rec_dev(slot);
     for (int s0 = 0; s0 < n;) {
         int s1 = s0 + 1;
         while (s1 < n && (have[s1] != 0) == (have[s0] != 0)) ++s1;
@@ -103,13 +61,6 @@ static int diff_back(oatgpu_ctx *c, int slot, const char *have, hipStream_t st, 
     return tracker_filters_launch(c, rd, slot, prev_slot, st);
 }
 
-static void diff_hand_out(oatgpu_ctx *c, int slot, oatgpu_position *out)
-{
-    const int n = c->cfg.n_streams;
-    for (int s = 0; s < n; ++s) to_position(c->df.rec.host()[(size_t)slot * n + s], out + s);
-    tracker_filters_keep(c, slot);
-}
-
 // one synchronous step on frames in device memory; the context is drained (open_sync)
 static int diff_step(oatgpu_ctx *c, const void *frames_dev, oatgpu_position *out)
 {
@@ -121,15 +72,15 @@ static int diff_step(oatgpu_ctx *c, const void *frames_dev, oatgpu_position *out
     rc = diff_back(c, 0, have.data(), c->stream);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    diff_hand_out(c, 0, out);
+    tracker_hand_out(c, c->df, 0, out);
     return OATGPU_OK;
 }
 
 extern "C" int oatgpu_diff_batch_dev(oatgpu_ctx *c, const void *frames_dev, oatgpu_position *out)
 {
-    if (!c) return OATGPU_E_INVALID;
-    if (!frames_dev || !out) return fail(c, OATGPU_E_INVALID, "null argument");
-    int rc = diff_refusals(c, "diff_batch");
+    int rc = check_batch_dev(c, frames_dev, out);
+    if (rc) return rc;
+    rc = tracker_refusals(c, c->df, "diff", "diff_batch");
     if (rc) return rc;
     rc = open_sync(c);
     if (rc) return rc;
@@ -138,11 +89,9 @@ extern "C" int oatgpu_diff_batch_dev(oatgpu_ctx *c, const void *frames_dev, oatg
 
 extern "C" int oatgpu_diff_batch(oatgpu_ctx *c, const uint8_t *const *frames_host, int32_t n, oatgpu_position *out)
 {
-    if (!c) return OATGPU_E_INVALID;
-    if (!frames_host || !out) return fail(c, OATGPU_E_INVALID, "null argument");
-    if (n != c->cfg.n_streams) return fail(c, OATGPU_E_INVALID, "expected %d frames, got %d", c->cfg.n_streams, n);
-    for (int s = 0; s < n; ++s) if (!frames_host[s]) return fail(c, OATGPU_E_INVALID, "null frame %d", s);
-    int rc = diff_refusals(c, "diff_batch");
+    int rc = check_batch(c, frames_host, n, out);
+    if (rc) return rc;
+    rc = tracker_refusals(c, c->df, "diff", "diff_batch");
     if (rc) return rc;
     rc = open_sync(c);
     if (rc) return rc;
@@ -156,16 +105,13 @@ extern "C" int oatgpu_diff_batch(oatgpu_ctx *c, const uint8_t *const *frames_hos
 // a slot is reused only after its result has been collected.  Everything is collected before the call returns.
 extern "C" int oatgpu_diff_sequence_dev(oatgpu_ctx *c, const void *const *frames_dev, int32_t n_frames, oatgpu_position *out)
 {
-    if (!c) return OATGPU_E_INVALID;
-    if (n_frames < 0) return fail(c, OATGPU_E_INVALID, "n_frames must be >= 0");
-    if (!frames_dev || (!out && n_frames > 0)) return fail(c, OATGPU_E_INVALID, "null argument");
-    for (int t = 0; t < n_frames; ++t) if (!frames_dev[t]) return fail(c, OATGPU_E_INVALID, "null frame set %d", t);
-    int rc = diff_refusals(c, "diff_sequence");
+    int rc = check_sequence_dev(c, frames_dev, n_frames, out);
+    if (rc) return rc;
+    rc = tracker_refusals(c, c->df, "diff", "diff_sequence");
     if (rc) return rc;
     if (n_frames == 0) return OATGPU_OK;
     rc = open_sync(c);
     if (rc) return rc;
-    static_assert(DiffTracker::kSlots == kSeqSlots, "the sequence loop's slots are the tracker's");
     const int n = c->cfg.n_streams;
     const std::vector<char> all(c->diff_have.size(), 1);
     std::vector<char> have;                // the state the launch's first frame met
@@ -184,22 +130,16 @@ extern "C" int oatgpu_diff_sequence_dev(oatgpu_ctx *c, const void *const *frames
             return r;
         },
         [&](int q, int i, hipStream_t B) { return diff_back(c, q, i ? all.data() : have.data(), B, std::exchange(prev, q)); },
-        [&](int q, int frame) { diff_hand_out(c, q, out + (size_t)frame * n); });
+        [&](int q, int frame) { tracker_hand_out(c, c->df, q, out + (size_t)frame * n); });
 }
 
 extern "C" int oatgpu_read_diff_mask(oatgpu_ctx *c, int32_t s, int32_t which, uint8_t *out)
 {
-    int rc = check_stream_ix(c, s);
-    if (rc) return rc;
-    if (!out) return fail(c, OATGPU_E_INVALID, "null argument");
-    if (!c->df.on) return fail(c, OATGPU_E_INVALID, "the diff tracker is off (oatgpu_set_diff_tracker)");
-    if (c->df.last < 0) return fail(c, OATGPU_E_INVALID, "no diff step has run yet");
-    if (which != OATGPU_TAP_THRESHOLD && which != OATGPU_TAP_MORPH && which != OATGPU_TAP_FINAL)
-        return fail(c, OATGPU_E_INVALID, "unknown tap %d", which);
-    rc = open_sync(c);
+    if (!c) return OATGPU_E_INVALID;
+    const int rc = open_tap(c, c->df, "diff", "no diff step has run yet", s, which, out);
     if (rc) return rc;
     const int q = c->df.last;
-    const u64 *base = which == OATGPU_TAP_FINAL ? diff_mask(c, q, 1)
-                    : which == OATGPU_TAP_MORPH && c->df.last_dilated[(size_t)s] ? diff_mask(c, q, 0) : diff_bits(c, q);
+    const u64 *base = which == OATGPU_TAP_FINAL ? c->df.mask(q, 1)
+                    : which == OATGPU_TAP_MORPH && c->df.last_dilated[(size_t)s] ? c->df.mask(q, 0) : c->df.bits_of(q);
     return read_plane(c, base + (size_t)s * (c->g.Palloc >> 6), out);
 }

@@ -1,11 +1,96 @@
-// api_trackfilt.hip -- the filter chain behind the motion and the subtraction tracker.
+// api_trackfilt.hip -- what the motion and the subtraction tracker share on the host, and the filter chain behind them.
 // `posifilt kalman` -> `posifilt homography` -> `posifilt region` on the trackers' own result records (kernels_trackfilt.hip,
 // DESIGN.md 9h): one launch a frame behind the slot's back half, in frame order.  api_diff.hip and api_bsubtrack.hip call the
 // three helpers below from their steps; with no chain configured they do nothing.
 #include "oatgpu_ctx.h"
 
-static_assert(TrackerFilters::kSlots == kSeqSlots && TrackerFilters::kSlots == DiffTracker::kSlots &&
-              TrackerFilters::kSlots == BsubTracker::kSlots, "a filtered set for every slot of the trackers");
+// --- what the two trackers' entry points have in common (BatchedTrackerState, oatgpu_ctx.h) ---
+
+bool BatchedTrackerState::alloc(const oatgpu_ctx *c)
+{
+    n = (size_t)c->cfg.n_streams;
+    words = n * ((size_t)c->g.Palloc / 64);
+    const size_t K = kSeqSlots;
+    bool ok = bits.alloc(K * words * 8) == hipSuccess;
+    ok = ok && masks.alloc(K * planes * words * 8) == hipSuccess;
+    ok = ok && rec.alloc(K * n * sizeof(ResultRec), hipHostMallocMapped) == hipSuccess;
+    // (the taps: words beyond the frame are never written by the back half)
+    ok = ok && hipMemsetAsync(bits, 0, K * words * 8, c->stream) == hipSuccess;
+    ok = ok && hipMemsetAsync(masks, 0, K * planes * words * 8, c->stream) == hipSuccess;
+    for (auto &e : ev_front) ok = ok && e.create(hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
+    for (auto &e : ev_done) ok = ok && e.create(hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
+    on = ok;
+    return ok;
+}
+
+// what a step of either tracker refuses, checked before anything is read or has moved
+int tracker_refusals(oatgpu_ctx *c, const BatchedTrackerState &bt, const char *name, const char *what)
+{
+    if (!bt.on) return fail(c, OATGPU_E_INVALID, "the %s tracker is off (oatgpu_set_%s_tracker)", name, name);
+    if (c->ring_count || c->staged_count) return fail(c, OATGPU_E_INVALID, "%s while enqueued results are outstanding", what);
+    if (c->kal_on) return fail(c, OATGPU_E_INVALID, "%s with the position filter on (oatgpu_set_kalman) is not supported", what);
+    if (c->homo_on) return fail(c, OATGPU_E_INVALID, "%s with a homography on (oatgpu_set_homography) is not supported", what);
+    if (c->ud_track) return fail(c, OATGPU_E_INVALID, "%s with undistortion on (oatgpu_set_track_undistort) is not supported", what);
+    if (c->by_track) return fail(c, OATGPU_E_INVALID, "%s with Bayer frames on (oatgpu_set_track_bayer) is not supported", what);
+    return OATGPU_OK;
+}
+
+// the arguments of the *_batch_dev, *_batch and *_sequence_dev entry points
+int check_batch_dev(oatgpu_ctx *c, const void *frames_dev, const oatgpu_position *out)
+{
+    if (!c) return OATGPU_E_INVALID;
+    if (!frames_dev || !out) return fail(c, OATGPU_E_INVALID, "null argument");
+    return OATGPU_OK;
+}
+int check_batch(oatgpu_ctx *c, const uint8_t *const *frames_host, int n, const oatgpu_position *out)
+{
+    if (!c) return OATGPU_E_INVALID;
+    if (!frames_host || !out) return fail(c, OATGPU_E_INVALID, "null argument");
+    if (n != c->cfg.n_streams) return fail(c, OATGPU_E_INVALID, "expected %d frames, got %d", c->cfg.n_streams, n);
+    for (int s = 0; s < n; ++s) if (!frames_host[s]) return fail(c, OATGPU_E_INVALID, "null frame %d", s);
+    return OATGPU_OK;
+}
+int check_sequence_dev(oatgpu_ctx *c, const void *const *frames_dev, int n_frames, const oatgpu_position *out)
+{
+    if (!c) return OATGPU_E_INVALID;
+    if (n_frames < 0) return fail(c, OATGPU_E_INVALID, "n_frames must be >= 0");
+    if (!frames_dev || (!out && n_frames > 0)) return fail(c, OATGPU_E_INVALID, "null argument");
+    for (int t = 0; t < n_frames; ++t) if (!frames_dev[t]) return fail(c, OATGPU_E_INVALID, "null frame set %d", t);
+    return OATGPU_OK;
+}
+
+// oatgpu_read_diff_mask / oatgpu_read_bsub_mask up to the read itself: the arguments, a frame to read from (none_yet: the text
+// where there is none), the context drained
+int open_tap(oatgpu_ctx *c, const BatchedTrackerState &bt, const char *name, const char *none_yet, int s, int which, const uint8_t *out)
+{
+    const int rc = check_stream_ix(c, s);
+    if (rc) return rc;
+    if (!out) return fail(c, OATGPU_E_INVALID, "null argument");
+    if (!bt.on) return fail(c, OATGPU_E_INVALID, "the %s tracker is off (oatgpu_set_%s_tracker)", name, name);
+    if (bt.last < 0) return fail(c, OATGPU_E_INVALID, "%s", none_yet);
+    if (which != OATGPU_TAP_THRESHOLD && which != OATGPU_TAP_MORPH && which != OATGPU_TAP_FINAL)
+        return fail(c, OATGPU_E_INVALID, "unknown tap %d", which);
+    return open_sync(c);
+}
+
+// oatgpu_diff_reset / oatgpu_bsub_reset: stream s (-1: every stream) starts over with its next frame
+int reset_have(oatgpu_ctx *c, std::vector<char> &have, int s)
+{
+    if (s < -1 || s >= c->cfg.n_streams) return fail(c, OATGPU_E_INVALID, "stream index %d out of range", s);
+    if (s < 0) have.assign((size_t)c->cfg.n_streams, 0);
+    else have[(size_t)s] = 0;
+    return OATGPU_OK;
+}
+
+// the finished frame in `slot` to the caller: its records as positions, its filtered set into the call's
+void tracker_hand_out(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, oatgpu_position *out)
+{
+    for (size_t s = 0; s < bt.n; ++s) to_position(bt.rec.host()[(size_t)slot * bt.n + s], out + s);
+    tracker_filters_keep(c, slot);
+}
+
+// --- the filter chain ---
 
 // The chain on the frame whose result records are rec_dev (the tracker's slot `slot`), on stream st right behind that frame's
 // back half.  Inside a sequence call (st is a B stream) consecutive frames sit on different HIP streams: the launch waits for
@@ -63,7 +148,7 @@ extern "C" int oatgpu_set_tracker_filters(oatgpu_ctx *c, const oatgpu_marker_fil
     if (first) {
         bool ok = tf.params.alloc(sizeof(MarkerFilterParams)) == hipSuccess;
         ok = ok && tf.state.alloc(n * sizeof(KalmanState)) == hipSuccess;
-        ok = ok && tf.out.alloc(TrackerFilters::kSlots * n * sizeof(MarkerFiltered), hipHostMallocMapped) == hipSuccess;
+        ok = ok && tf.out.alloc(kSeqSlots * n * sizeof(MarkerFiltered), hipHostMallocMapped) == hipSuccess;
         for (auto &e : tf.ev) ok = ok && e.create(hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
         if (!ok) return fail(c, OATGPU_E_NOMEM, "tracker filters: allocation failed: %s", hipGetErrorString(hipGetLastError()));
         tf.last.reserve(n);

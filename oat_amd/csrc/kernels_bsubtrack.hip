@@ -17,21 +17,15 @@
 //   narrow (everything else): one pixel a lane with byte and dword accesses, the ballot is the word.
 // Both write EVERY word of Palloc / 64 (zero bits for x >= W and p >= P): the row scan reads them.
 //
-// Bayer RAW8 frames (BsubLaunch::bayer): k_bsubtrack_raw_wide / k_bsubtrack_raw_narrow are the BGR lanes with another
-// pixel source -- the lane demosaics its pixels in registers (debayer_inline.h: the dwords at x0 - 4, x0, x0 + 4 of raw rows y - 1,
-// y, y + 1, or 9 byte loads) into the 12 bytes a BGR frame would have held; the ROI falls on the demosaiced pixel, bg and acc are
-// BGR.  The pattern is run-time data, two parity bits a stream in two 64-bit kernel arguments.
-//
-// Lens undistortion (BsubLaunch::ud_map1): k_bsubtrack_remap_wide / k_bsubtrack_remap_narrow are the same lanes with
-// a third pixel source -- the lane loads the map entries of its own pixels (kernels_diff.hip's RemapSource), keeps them in
-// registers for both frames of a paired launch, and gathers each pixel with undistort_inline.h's remap_px into the bytes an
-// undistorted frame would have held: every channel is remapped on its own, then subtracted; the ROI falls on the undistorted
-// pixel, bg and acc are images in undistorted coordinates.
+// Where the pixels come from is a template argument of the lane code (pixel_source_inline.h): packed frames (k_bsubtrack_wide /
+// k_bsubtrack_narrow), Bayer RAW8 demosaiced in registers into the 12 bytes a BGR frame would have held (FrontLaunch::bayer,
+// k_bsubtrack_raw_*, the BGR lanes) or packed frames remapped in registers with the stream's undistortion map into
+// the bytes an undistorted frame would have held (FrontLaunch::ud_map1, DESIGN.md 9g: k_bsubtrack_remap_*).  The ROI falls on the
+// pixel the source hands back; bg and acc are BGR images, with a map in undistorted coordinates.
 #include "oatgpu_internal.h"
-#include "debayer_inline.h"
 #include "hsv_inline.h"
 #include "maskwords_inline.h"
-#include "undistort_inline.h"
+#include "pixel_source_inline.h"
 
 namespace oatgpu {
 
@@ -101,75 +95,6 @@ __device__ __forceinline__ unsigned frame4(const unsigned (&f)[CH], unsigned kee
     for (int j = 0; j < CH; ++j) bgw[j] = out[j];
     return nib;
 }
-
-// Where a lane's pixels come from: `frames` is a frame set of the launch (stream-major), s the stream, (y, x) the pixel.
-// four: x % 4 == 0, the 4 pixels from x on as CH little-endian dwords; one: the CH bytes of the pixel.  begin4 / begin1 run once
-// a lane ahead of the first four / one: what the lane keeps for every frame of the launch.
-template <int CH> struct PackedSource {                  // packed BGR (3) or GREY (1) frames
-    __device__ __forceinline__ void begin4(const Geom &, int, int, int) {}
-    __device__ __forceinline__ void begin1(const Geom &, int, int, int) {}
-    __device__ __forceinline__ void four(const uint8_t *frames, const Geom &g, int s, int y, int x, unsigned (&f)[CH]) const
-    {
-        const unsigned *fp = (const unsigned *)(frames + (((size_t)s * g.H + y) * g.W + x) * CH);
-#pragma unroll
-        for (int j = 0; j < CH; ++j) f[j] = fp[j];
-    }
-    __device__ __forceinline__ void one(const uint8_t *frames, const Geom &g, int s, int y, int x, int (&v)[CH]) const
-    {
-        const uint8_t *fp = frames + (((size_t)s * g.H + y) * g.W + x) * CH;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) v[c] = fp[c];
-    }
-};
-struct RawSource {                                       // Bayer RAW8 frames, demosaiced in registers: BGR pixels
-    bool r_row, r_col;                                   // parity of the row / the column of the stream's R sample (uniform)
-    __device__ __forceinline__ void begin4(const Geom &, int, int, int) {}
-    __device__ __forceinline__ void begin1(const Geom &, int, int, int) {}
-    __device__ __forceinline__ void four(const uint8_t *frames, const Geom &g, int s, int y, int x, unsigned (&f)[3]) const
-    {
-        unsigned px[4];
-        debayer_px4(frames + (size_t)s * g.H * g.W, g.H, g.W, y, x, r_row, r_col, px);
-        pack_bgr4(px, f);
-    }
-    __device__ __forceinline__ void one(const uint8_t *frames, const Geom &g, int s, int y, int x, int (&v)[3]) const
-    {
-        const unsigned p = debayer_px1(frames + (size_t)s * g.H * g.W, g.H, g.W, y, x, r_row, r_col);
-        v[0] = p & 255u; v[1] = (p >> 8) & 255u; v[2] = p >> 16;
-    }
-};
-
-template <int CH> struct RemapSource {                   // packed frames seen through the stream's undistortion map
-    const uint32_t *map1;                                // the STREAM's planes (uniform)
-    const uint16_t *map2;
-    uint32_t m1[4], m2[4];                               // the lane's map entries: loaded once, used for every frame of the launch
-    __device__ __forceinline__ void begin4(const Geom &g, int, int y, int x) { load_map4(map1, map2, (size_t)y * g.W + x, m1, m2); }
-    __device__ __forceinline__ void begin1(const Geom &g, int, int y, int x)
-    {
-        const size_t i = (size_t)y * g.W + x;
-        m1[0] = map1[i]; m2[0] = map2[i];
-    }
-    __device__ __forceinline__ void four(const uint8_t *frames, const Geom &g, int s, int, int, unsigned (&f)[CH]) const
-    {
-        const uint8_t *frame = frames + (size_t)s * g.H * g.W * CH;
-        unsigned px[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            uint32_t v[CH];
-            remap_px<CH>(frame, g.H, g.W, m1[k], m2[k], v);
-            if constexpr (CH == 1) px[k] = v[0];
-            else px[k] = v[0] | v[1] << 8 | v[2] << 16;
-        }
-        if constexpr (CH == 1) f[0] = px[0] | px[1] << 8 | px[2] << 16 | px[3] << 24;
-        else pack_bgr4(px, f);
-    }
-    __device__ __forceinline__ void one(const uint8_t *frames, const Geom &g, int s, int, int, int (&v)[CH]) const
-    {
-        uint32_t u[CH];
-        remap_px<CH>(frames + (size_t)s * g.H * g.W * CH, g.H, g.W, m1[0], m2[0], u);
-#pragma unroll
-        for (int c = 0; c < CH; ++c) v[c] = (int)u[c];
-    }
-};
 
 template <int CH, bool ROI, bool PAIR, bool LEARN, class SRC>
 __device__ __forceinline__ void bsubtrack_wide(const Geom &g, const BsubArgs &a, SRC src)
@@ -271,89 +196,32 @@ __device__ __forceinline__ void bsubtrack_narrow(const Geom &g, const BsubArgs &
     }
 }
 
+// One kernel name a source and lane mapping; the raw and the remap kernels take what their source is built from
 template <int CH, bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(256) void k_bsubtrack_wide(Geom g, BsubArgs a)
 {
-    bsubtrack_wide<CH, ROI, PAIR, LEARN>(g, a, PackedSource<CH>{});
+    bsubtrack_wide<CH, ROI, PAIR, LEARN>(g, a, PackedSource<CH, true>{});
 }
 template <int CH, bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(256) void k_bsubtrack_narrow(Geom g, BsubArgs a)
 {
-    bsubtrack_narrow<CH, ROI, PAIR, LEARN>(g, a, PackedSource<CH>{});
+    bsubtrack_narrow<CH, ROI, PAIR, LEARN>(g, a, PackedSource<CH, true>{});
 }
-// r_row, r_col: bit (stream - first_stream), the parity of the row / the column of the stream's R sample
 template <bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(256) void k_bsubtrack_raw_wide(Geom g, BsubArgs a, u64 r_row, u64 r_col)
 {
-    bsubtrack_wide<3, ROI, PAIR, LEARN>(g, a, RawSource{(bool)((r_row >> blockIdx.y) & 1ull), (bool)((r_col >> blockIdx.y) & 1ull)});
+    bsubtrack_wide<3, ROI, PAIR, LEARN>(g, a, RawSource(r_row, r_col));
 }
 template <bool ROI, bool PAIR, bool LEARN> __global__ __launch_bounds__(256) void k_bsubtrack_raw_narrow(Geom g, BsubArgs a, u64 r_row, u64 r_col)
 {
-    bsubtrack_narrow<3, ROI, PAIR, LEARN>(g, a, RawSource{(bool)((r_row >> blockIdx.y) & 1ull), (bool)((r_col >> blockIdx.y) & 1ull)});
+    bsubtrack_narrow<3, ROI, PAIR, LEARN>(g, a, RawSource(r_row, r_col));
 }
-
-// map1, map2: plane 0 of the context's maps; the stream's planes start map_stride entries a stream further on
 template <int CH, bool ROI, bool PAIR, bool LEARN>
 __global__ __launch_bounds__(256) void k_bsubtrack_remap_wide(Geom g, BsubArgs a, const uint32_t *map1, const uint16_t *map2, size_t map_stride)
 {
-    const size_t off = (size_t)(a.first_stream + (int)blockIdx.y) * map_stride;
-    bsubtrack_wide<CH, ROI, PAIR, LEARN>(g, a, RemapSource<CH>{map1 + off, map2 + off, {}, {}});
+    bsubtrack_wide<CH, ROI, PAIR, LEARN>(g, a, RemapSource<CH>(a.first_stream, map1, map2, map_stride));
 }
 template <int CH, bool ROI, bool PAIR, bool LEARN>
 __global__ __launch_bounds__(256) void k_bsubtrack_remap_narrow(Geom g, BsubArgs a, const uint32_t *map1, const uint16_t *map2, size_t map_stride)
 {
-    const size_t off = (size_t)(a.first_stream + (int)blockIdx.y) * map_stride;
-    bsubtrack_narrow<CH, ROI, PAIR, LEARN>(g, a, RemapSource<CH>{map1 + off, map2 + off, {}, {}});
-}
-
-template <int CH, bool ROI, bool PAIR, bool LEARN> void launch_one(const Geom &g, const BsubArgs &a, bool wide, int n, hipStream_t st)
-{
-    if (wide) hipLaunchKernelGGL((k_bsubtrack_wide<CH, ROI, PAIR, LEARN>), dim3(g.Palloc / 1024, n), dim3(256), 0, st, g, a);
-    else hipLaunchKernelGGL((k_bsubtrack_narrow<CH, ROI, PAIR, LEARN>), dim3(g.Palloc / 256, n), dim3(256), 0, st, g, a);
-}
-template <int CH, bool ROI, bool PAIR> void launch_learn(const Geom &g, const BsubArgs &a, bool learn, bool wide, int n, hipStream_t st)
-{
-    if (learn) launch_one<CH, ROI, PAIR, true>(g, a, wide, n, st);
-    else launch_one<CH, ROI, PAIR, false>(g, a, wide, n, st);
-}
-template <int CH> void launch_ch(const Geom &g, const BsubArgs &a, bool learn, bool wide, int n, hipStream_t st)
-{
-    const bool roi = a.roi != nullptr, pair = a.frames2 != nullptr;
-    if (roi) { if (pair) launch_learn<CH, true, true>(g, a, learn, wide, n, st); else launch_learn<CH, true, false>(g, a, learn, wide, n, st); }
-    else { if (pair) launch_learn<CH, false, true>(g, a, learn, wide, n, st); else launch_learn<CH, false, false>(g, a, learn, wide, n, st); }
-}
-
-struct RawBits { u64 r_row, r_col; };
-template <bool ROI, bool PAIR, bool LEARN> void launch_raw_one(const Geom &g, const BsubArgs &a, RawBits r, bool wide, int n, hipStream_t st)
-{
-    if (wide) hipLaunchKernelGGL((k_bsubtrack_raw_wide<ROI, PAIR, LEARN>), dim3(g.Palloc / 1024, n), dim3(256), 0, st, g, a, r.r_row, r.r_col);
-    else hipLaunchKernelGGL((k_bsubtrack_raw_narrow<ROI, PAIR, LEARN>), dim3(g.Palloc / 256, n), dim3(256), 0, st, g, a, r.r_row, r.r_col);
-}
-template <bool ROI, bool PAIR> void launch_raw_learn(const Geom &g, const BsubArgs &a, RawBits r, bool learn, bool wide, int n, hipStream_t st)
-{
-    if (learn) launch_raw_one<ROI, PAIR, true>(g, a, r, wide, n, st);
-    else launch_raw_one<ROI, PAIR, false>(g, a, r, wide, n, st);
-}
-void launch_raw(const Geom &g, const BsubArgs &a, RawBits r, bool learn, bool wide, int n, hipStream_t st)
-{
-    const bool roi = a.roi != nullptr, pair = a.frames2 != nullptr;
-    if (roi) { if (pair) launch_raw_learn<true, true>(g, a, r, learn, wide, n, st); else launch_raw_learn<true, false>(g, a, r, learn, wide, n, st); }
-    else { if (pair) launch_raw_learn<false, true>(g, a, r, learn, wide, n, st); else launch_raw_learn<false, false>(g, a, r, learn, wide, n, st); }
-}
-
-struct MapPlanes { const uint32_t *map1; const uint16_t *map2; size_t stride; };
-template <int CH, bool ROI, bool PAIR, bool LEARN> void launch_remap_one(const Geom &g, const BsubArgs &a, MapPlanes m, bool wide, int n, hipStream_t st)
-{
-    if (wide) hipLaunchKernelGGL((k_bsubtrack_remap_wide<CH, ROI, PAIR, LEARN>), dim3(g.Palloc / 1024, n), dim3(256), 0, st, g, a, m.map1, m.map2, m.stride);
-    else hipLaunchKernelGGL((k_bsubtrack_remap_narrow<CH, ROI, PAIR, LEARN>), dim3(g.Palloc / 256, n), dim3(256), 0, st, g, a, m.map1, m.map2, m.stride);
-}
-template <int CH, bool ROI, bool PAIR> void launch_remap_learn(const Geom &g, const BsubArgs &a, MapPlanes m, bool learn, bool wide, int n, hipStream_t st)
-{
-    if (learn) launch_remap_one<CH, ROI, PAIR, true>(g, a, m, wide, n, st);
-    else launch_remap_one<CH, ROI, PAIR, false>(g, a, m, wide, n, st);
-}
-template <int CH> void launch_remap(const Geom &g, const BsubArgs &a, MapPlanes m, bool learn, bool wide, int n, hipStream_t st)
-{
-    const bool roi = a.roi != nullptr, pair = a.frames2 != nullptr;
-    if (roi) { if (pair) launch_remap_learn<CH, true, true>(g, a, m, learn, wide, n, st); else launch_remap_learn<CH, true, false>(g, a, m, learn, wide, n, st); }
-    else { if (pair) launch_remap_learn<CH, false, true>(g, a, m, learn, wide, n, st); else launch_remap_learn<CH, false, false>(g, a, m, learn, wide, n, st); }
+    bsubtrack_narrow<CH, ROI, PAIR, LEARN>(g, a, RemapSource<CH>(a.first_stream, map1, map2, map_stride));
 }
 
 }  // namespace
@@ -373,16 +241,27 @@ void launch_bsubtrack_front(const Geom &g, const BsubLaunch &a, int n_streams, h
         const int n = n_streams - s0 < 64 ? n_streams - s0 : 64;
         BsubArgs k{a.frames, a.frames2, a.bg, a.acc, a.bits, a.bits2, a.roi, 0ull, a.rp, a.a, a.b, s0};
         for (int i = 0; i < n; ++i) k.first |= (u64)(a.have[s0 + i] == 0) << i;
+        // the source, then CH, ROI, PAIR and LEARN pick the kernel pair; `wide` picks of the pair and sets the grid
+        auto launch = [&](auto *k_wide, auto *k_narrow, auto... source_args) {
+            hipLaunchKernelGGL(wide ? k_wide : k_narrow, dim3(g.Palloc / (wide ? 1024 : 256), n), dim3(256), 0, st, g, k, source_args...);
+        };
+        const bool ch3 = a.channels == 3, roi = a.roi != nullptr, pair = a.frames2 != nullptr;
         if (a.bayer) {
-            RawBits r;
-            bayer_parity_bits(a.bayer + s0, n, r.r_row, r.r_col);
-            launch_raw(g, k, r, a.learn, wide, n, st);
+            u64 r_row, r_col;
+            bayer_parity_bits(a.bayer + s0, n, r_row, r_col);
+            lift_bools([&](auto ROI, auto PAIR, auto LEARN) {
+                launch(k_bsubtrack_raw_wide<ROI, PAIR, LEARN>, k_bsubtrack_raw_narrow<ROI, PAIR, LEARN>, r_row, r_col);
+            }, roi, pair, a.learn);
         } else if (a.ud_map1) {
-            const MapPlanes m{a.ud_map1, a.ud_map2, a.ud_stride};
-            if (a.channels == 3) launch_remap<3>(g, k, m, a.learn, wide, n, st);
-            else launch_remap<1>(g, k, m, a.learn, wide, n, st);
-        } else if (a.channels == 3) launch_ch<3>(g, k, a.learn, wide, n, st);
-        else launch_ch<1>(g, k, a.learn, wide, n, st);
+            lift_bools([&](auto CH3, auto ROI, auto PAIR, auto LEARN) {
+                launch(k_bsubtrack_remap_wide<CH3 ? 3 : 1, ROI, PAIR, LEARN>, k_bsubtrack_remap_narrow<CH3 ? 3 : 1, ROI, PAIR, LEARN>,
+                       a.ud_map1, a.ud_map2, a.ud_stride);
+            }, ch3, roi, pair, a.learn);
+        } else {
+            lift_bools([&](auto CH3, auto ROI, auto PAIR, auto LEARN) {
+                launch(k_bsubtrack_wide<CH3 ? 3 : 1, ROI, PAIR, LEARN>, k_bsubtrack_narrow<CH3 ? 3 : 1, ROI, PAIR, LEARN>);
+            }, ch3, roi, pair, a.learn);
+        }
     }
 }
 

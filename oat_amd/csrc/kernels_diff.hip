@@ -14,21 +14,14 @@
 //   narrow (everything else): one pixel a lane with byte accesses, the ballot is the word (k_absdiff_bits' mapping).
 // Both write EVERY word of Palloc / 64 (zero bits for x >= W and p >= P): the row scan reads them.
 //
-// Bayer RAW8 frames (DiffLaunch::bayer): k_diff_raw_wide / k_diff_raw_narrow are the same lanes with another pixel
-// source -- the lane demosaics its pixels in registers (debayer_inline.h: the dwords at x0 - 4, x0, x0 + 4 of raw rows y - 1, y,
-// y + 1, or 9 byte loads) and takes the grey of the triples; the ROI falls on the demosaiced pixel.  The pattern is run-time
-// data, two parity bits a stream in two 64-bit kernel arguments.
-//
-// Lens undistortion (DiffLaunch::ud_map1): k_diff_remap_wide / k_diff_remap_narrow are the same lanes with a third
-// pixel source -- the lane loads the map entries of its own pixels (raster index y * W + x of the stream's planes: one 16-byte
-// and one 8-byte load for 4 pixels, or one entry of each plane), keeps them in registers for both frames of a paired launch, and
-// gathers each pixel's 2 x 2 neighbourhood from the caller's frame with undistort_inline.h's remap_px.  B, G and R are remapped
-// each on its own and the grey is taken of the remapped triple (the chain's order: undistort, mask, col GREY); the ROI falls on
-// the undistorted pixel.
+// Where the pixels come from is a template argument of the lane code (pixel_source_inline.h): packed frames (k_diff_wide /
+// k_diff_narrow), Bayer RAW8 demosaiced in registers (FrontLaunch::bayer, DESIGN.md 9f: k_diff_raw_*) or packed frames remapped in
+// registers with the stream's undistortion map (FrontLaunch::ud_map1, DESIGN.md 9g: k_diff_remap_*).  The grey is taken of what
+// the source hands back -- of the demosaiced or the remapped triple, the chain's order: undistort, mask, col GREY -- and the ROI
+// falls on that pixel.
 #include "oatgpu_internal.h"
-#include "debayer_inline.h"
 #include "maskwords_inline.h"
-#include "undistort_inline.h"
+#include "pixel_source_inline.h"
 
 namespace oatgpu {
 
@@ -40,90 +33,25 @@ __device__ __forceinline__ int grey_bgr(unsigned b, unsigned g, unsigned r)
 }
 __device__ __forceinline__ bool differs(int a, int b, int thr) { return (a > b ? a - b : b - a) > thr; }
 
-// byte k of three little-endian dwords
-__device__ __forceinline__ unsigned byte_of(const unsigned (&d)[3], int k) { return (d[k >> 2] >> ((k & 3) * 8)) & 255u; }
-
-// the four greys of the 4 pixels at raster index i (a multiple of 4) of one frame, as one little-endian dword
-template <int CH> __device__ __forceinline__ unsigned grey4(const uint8_t *frame, size_t i)
+// col GREY of one pixel's values
+template <class T, int CH> __device__ __forceinline__ int grey_of(const T (&v)[CH])
 {
-    if (CH == 1) return *(const unsigned *)(frame + i);
-    const unsigned *q = (const unsigned *)(frame + 3 * i);
-    const unsigned d[3] = {q[0], q[1], q[2]};
-    unsigned g = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) g |= (unsigned)grey_bgr(byte_of(d, 3 * k), byte_of(d, 3 * k + 1), byte_of(d, 3 * k + 2)) << (8 * k);
-    return g;
+    if constexpr (CH == 1) return (int)v[0];
+    else return grey_bgr(v[0], v[1], v[2]);
 }
-template <int CH> __device__ __forceinline__ int grey1(const uint8_t *frame, size_t i)
+// the greys of a source's 4 pixels from (y, x) on as one little-endian dword, and the grey of its pixel (y, x)
+template <class SRC> __device__ __forceinline__ unsigned grey4(const SRC &src, const uint8_t *frames, const Geom &g, int s, int y, int x)
 {
-    if (CH == 1) return frame[i];
-    return grey_bgr(frame[3 * i], frame[3 * i + 1], frame[3 * i + 2]);
+    unsigned gr = 0;
+    src.each4(frames, g, s, y, x, [&](int k, const unsigned (&v)[SRC::kCH]) { gr |= (unsigned)grey_of(v) << (8 * k); });
+    return gr;
 }
-
-// Where a lane's greys come from: `frames` is a frame set of the launch (stream-major), s the stream, (y, x) the pixel
-// (four: x % 4 == 0, the four pixels from x on as one little-endian dword).  begin4 / begin1 run once a lane ahead of the
-// first four / one: what the lane keeps for every frame of the launch.
-template <int CH> struct PackedSource {                  // packed BGR (3) or GREY (1) frames
-    __device__ __forceinline__ void begin4(const Geom &, int, int, int) {}
-    __device__ __forceinline__ void begin1(const Geom &, int, int, int) {}
-    __device__ __forceinline__ unsigned four(const uint8_t *frames, const Geom &g, int s, int y, int x) const
-    {
-        return grey4<CH>(frames + (size_t)s * g.H * g.W * CH, (size_t)y * g.W + x);
-    }
-    __device__ __forceinline__ int one(const uint8_t *frames, const Geom &g, int s, int y, int x) const
-    {
-        return grey1<CH>(frames + (size_t)s * g.H * g.W * CH, (size_t)y * g.W + x);
-    }
-};
-struct RawSource {                                       // Bayer RAW8 frames, demosaiced in registers
-    bool r_row, r_col;                                   // parity of the row / the column of the stream's R sample (uniform)
-    __device__ __forceinline__ void begin4(const Geom &, int, int, int) {}
-    __device__ __forceinline__ void begin1(const Geom &, int, int, int) {}
-    __device__ __forceinline__ unsigned four(const uint8_t *frames, const Geom &g, int s, int y, int x) const
-    {
-        unsigned px[4], v = 0;
-        debayer_px4(frames + (size_t)s * g.H * g.W, g.H, g.W, y, x, r_row, r_col, px);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v |= (unsigned)grey_bgr(px[k] & 255u, (px[k] >> 8) & 255u, px[k] >> 16) << (8 * k);
-        return v;
-    }
-    __device__ __forceinline__ int one(const uint8_t *frames, const Geom &g, int s, int y, int x) const
-    {
-        const unsigned p = debayer_px1(frames + (size_t)s * g.H * g.W, g.H, g.W, y, x, r_row, r_col);
-        return grey_bgr(p & 255u, (p >> 8) & 255u, p >> 16);
-    }
-};
-
-template <int CH> struct RemapSource {                   // packed frames seen through the stream's undistortion map
-    const uint32_t *map1;                                // the STREAM's planes (uniform)
-    const uint16_t *map2;
-    uint32_t m1[4], m2[4];                               // the lane's map entries: loaded once, used for every frame of the launch
-    __device__ __forceinline__ void begin4(const Geom &g, int, int y, int x) { load_map4(map1, map2, (size_t)y * g.W + x, m1, m2); }
-    __device__ __forceinline__ void begin1(const Geom &g, int, int y, int x)
-    {
-        const size_t i = (size_t)y * g.W + x;
-        m1[0] = map1[i]; m2[0] = map2[i];
-    }
-    __device__ __forceinline__ int grey(const uint8_t *frame, const Geom &g, int k) const
-    {
-        uint32_t v[CH];
-        remap_px<CH>(frame, g.H, g.W, m1[k], m2[k], v);
-        if constexpr (CH == 1) return (int)v[0];
-        else return grey_bgr(v[0], v[1], v[2]);
-    }
-    __device__ __forceinline__ unsigned four(const uint8_t *frames, const Geom &g, int s, int, int) const
-    {
-        const uint8_t *frame = frames + (size_t)s * g.H * g.W * CH;
-        unsigned v = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v |= (unsigned)grey(frame, g, k) << (8 * k);
-        return v;
-    }
-    __device__ __forceinline__ int one(const uint8_t *frames, const Geom &g, int s, int, int) const
-    {
-        return grey(frames + (size_t)s * g.H * g.W * CH, g, 0);
-    }
-};
+template <class SRC> __device__ __forceinline__ int grey1(const SRC &src, const uint8_t *frames, const Geom &g, int s, int y, int x)
+{
+    int v[SRC::kCH];
+    src.one(frames, g, s, y, x, v);
+    return grey_of(v);
+}
 
 struct DiffArgs {
     const uint8_t *frames, *frames2;     // [n][H*W*CH] stream-major (raw kernels: [n][H*W]); frames2: the second frame of a paired launch
@@ -153,7 +81,7 @@ template <bool ROI, bool PAIR, class SRC> __device__ __forceinline__ void diff_w
             keep = (r & 1u ? 0xffu : 0u) | (r & 2u ? 0xff00u : 0u) | (r & 4u ? 0xff0000u : 0u) | (r & 8u ? 0xff000000u : 0u);
         }
         src.begin4(g, s, y, x);
-        const unsigned g1 = src.four(a.frames, g, s, y, x) & keep;
+        const unsigned g1 = grey4(src, a.frames, g, s, y, x) & keep;
         if (have) {
             const unsigned l = *lp;
 #pragma unroll
@@ -164,7 +92,7 @@ template <bool ROI, bool PAIR, class SRC> __device__ __forceinline__ void diff_w
         }
         unsigned out = g1;
         if (PAIR) {
-            const unsigned g2 = src.four(a.frames2, g, s, y, x) & keep;
+            const unsigned g2 = grey4(src, a.frames2, g, s, y, x) & keep;
 #pragma unroll
             for (int k = 0; k < 4; ++k) n2 |= differs((g2 >> (8 * k)) & 255u, (g1 >> (8 * k)) & 255u, a.thr) ? 1u << k : 0u;
             out = g2;
@@ -190,11 +118,11 @@ template <bool ROI, bool PAIR, class SRC> __device__ __forceinline__ void diff_n
         uint8_t *lp = a.last + (size_t)s * npx + i;
         const bool keep = !ROI || ((a.roi[(size_t)s * NW + word] >> lane) & 1ull);
         if (keep) src.begin1(g, s, y, x);
-        const int g1 = keep ? src.one(a.frames, g, s, y, x) : 0;
+        const int g1 = keep ? grey1(src, a.frames, g, s, y, x) : 0;
         on1 = have ? differs(g1, *lp, a.thr) : g1 != 0;
         int out = g1;
         if (PAIR) {
-            const int g2 = keep ? src.one(a.frames2, g, s, y, x) : 0;
+            const int g2 = keep ? grey1(src, a.frames2, g, s, y, x) : 0;
             on2 = differs(g2, g1, a.thr);
             out = g2;
         }
@@ -208,6 +136,7 @@ template <bool ROI, bool PAIR, class SRC> __device__ __forceinline__ void diff_n
     }
 }
 
+// One kernel name a source and lane mapping; the raw and the remap kernels take what their source is built from
 template <int CH, bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_diff_wide(Geom g, DiffArgs a)
 {
     diff_wide<ROI, PAIR>(g, a, PackedSource<CH>{});
@@ -216,65 +145,23 @@ template <int CH, bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_
 {
     diff_narrow<ROI, PAIR>(g, a, PackedSource<CH>{});
 }
-// r_row, r_col: bit (stream - first_stream), the parity of the row / the column of the stream's R sample
 template <bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_diff_raw_wide(Geom g, DiffArgs a, u64 r_row, u64 r_col)
 {
-    diff_wide<ROI, PAIR>(g, a, RawSource{(bool)((r_row >> blockIdx.y) & 1ull), (bool)((r_col >> blockIdx.y) & 1ull)});
+    diff_wide<ROI, PAIR>(g, a, RawSource(r_row, r_col));
 }
 template <bool ROI, bool PAIR> __global__ __launch_bounds__(256) void k_diff_raw_narrow(Geom g, DiffArgs a, u64 r_row, u64 r_col)
 {
-    diff_narrow<ROI, PAIR>(g, a, RawSource{(bool)((r_row >> blockIdx.y) & 1ull), (bool)((r_col >> blockIdx.y) & 1ull)});
+    diff_narrow<ROI, PAIR>(g, a, RawSource(r_row, r_col));
 }
-
-// map1, map2: plane 0 of the context's maps; the stream's planes start map_stride entries a stream further on
 template <int CH, bool ROI, bool PAIR>
 __global__ __launch_bounds__(256) void k_diff_remap_wide(Geom g, DiffArgs a, const uint32_t *map1, const uint16_t *map2, size_t map_stride)
 {
-    const size_t off = (size_t)(a.first_stream + (int)blockIdx.y) * map_stride;
-    diff_wide<ROI, PAIR>(g, a, RemapSource<CH>{map1 + off, map2 + off, {}, {}});
+    diff_wide<ROI, PAIR>(g, a, RemapSource<CH>(a.first_stream, map1, map2, map_stride));
 }
 template <int CH, bool ROI, bool PAIR>
 __global__ __launch_bounds__(256) void k_diff_remap_narrow(Geom g, DiffArgs a, const uint32_t *map1, const uint16_t *map2, size_t map_stride)
 {
-    const size_t off = (size_t)(a.first_stream + (int)blockIdx.y) * map_stride;
-    diff_narrow<ROI, PAIR>(g, a, RemapSource<CH>{map1 + off, map2 + off, {}, {}});
-}
-
-template <int CH, bool ROI, bool PAIR> void launch_one(const Geom &g, const DiffArgs &a, bool wide, int n, hipStream_t st)
-{
-    if (wide) hipLaunchKernelGGL((k_diff_wide<CH, ROI, PAIR>), dim3(g.Palloc / 1024, n), dim3(256), 0, st, g, a);
-    else hipLaunchKernelGGL((k_diff_narrow<CH, ROI, PAIR>), dim3(g.Palloc / 256, n), dim3(256), 0, st, g, a);
-}
-template <int CH> void launch_ch(const Geom &g, const DiffArgs &a, bool wide, int n, hipStream_t st)
-{
-    const bool roi = a.roi != nullptr, pair = a.frames2 != nullptr;
-    if (roi) { if (pair) launch_one<CH, true, true>(g, a, wide, n, st); else launch_one<CH, true, false>(g, a, wide, n, st); }
-    else { if (pair) launch_one<CH, false, true>(g, a, wide, n, st); else launch_one<CH, false, false>(g, a, wide, n, st); }
-}
-
-template <bool ROI, bool PAIR> void launch_raw_one(const Geom &g, const DiffArgs &a, u64 r_row, u64 r_col, bool wide, int n, hipStream_t st)
-{
-    if (wide) hipLaunchKernelGGL((k_diff_raw_wide<ROI, PAIR>), dim3(g.Palloc / 1024, n), dim3(256), 0, st, g, a, r_row, r_col);
-    else hipLaunchKernelGGL((k_diff_raw_narrow<ROI, PAIR>), dim3(g.Palloc / 256, n), dim3(256), 0, st, g, a, r_row, r_col);
-}
-void launch_raw(const Geom &g, const DiffArgs &a, u64 r_row, u64 r_col, bool wide, int n, hipStream_t st)
-{
-    const bool roi = a.roi != nullptr, pair = a.frames2 != nullptr;
-    if (roi) { if (pair) launch_raw_one<true, true>(g, a, r_row, r_col, wide, n, st); else launch_raw_one<true, false>(g, a, r_row, r_col, wide, n, st); }
-    else { if (pair) launch_raw_one<false, true>(g, a, r_row, r_col, wide, n, st); else launch_raw_one<false, false>(g, a, r_row, r_col, wide, n, st); }
-}
-
-struct MapPlanes { const uint32_t *map1; const uint16_t *map2; size_t stride; };
-template <int CH, bool ROI, bool PAIR> void launch_remap_one(const Geom &g, const DiffArgs &a, MapPlanes m, bool wide, int n, hipStream_t st)
-{
-    if (wide) hipLaunchKernelGGL((k_diff_remap_wide<CH, ROI, PAIR>), dim3(g.Palloc / 1024, n), dim3(256), 0, st, g, a, m.map1, m.map2, m.stride);
-    else hipLaunchKernelGGL((k_diff_remap_narrow<CH, ROI, PAIR>), dim3(g.Palloc / 256, n), dim3(256), 0, st, g, a, m.map1, m.map2, m.stride);
-}
-template <int CH> void launch_remap(const Geom &g, const DiffArgs &a, MapPlanes m, bool wide, int n, hipStream_t st)
-{
-    const bool roi = a.roi != nullptr, pair = a.frames2 != nullptr;
-    if (roi) { if (pair) launch_remap_one<CH, true, true>(g, a, m, wide, n, st); else launch_remap_one<CH, true, false>(g, a, m, wide, n, st); }
-    else { if (pair) launch_remap_one<CH, false, true>(g, a, m, wide, n, st); else launch_remap_one<CH, false, false>(g, a, m, wide, n, st); }
+    diff_narrow<ROI, PAIR>(g, a, RemapSource<CH>(a.first_stream, map1, map2, map_stride));
 }
 
 }  // namespace
@@ -294,16 +181,22 @@ void launch_diff_front(const Geom &g, const DiffLaunch &a, int n_streams, hipStr
         const int n = n_streams - s0 < 64 ? n_streams - s0 : 64;
         DiffArgs k{a.frames, a.frames2, a.last, a.bits, a.bits2, a.roi, 0ull, a.thr, s0};
         for (int i = 0; i < n; ++i) k.have |= (u64)(a.have_last[s0 + i] != 0) << i;
+        // the source, then CH, ROI and PAIR pick the kernel pair; `wide` picks of the pair and sets the grid
+        auto launch = [&](auto *k_wide, auto *k_narrow, auto... source_args) {
+            hipLaunchKernelGGL(wide ? k_wide : k_narrow, dim3(g.Palloc / (wide ? 1024 : 256), n), dim3(256), 0, st, g, k, source_args...);
+        };
+        const bool ch3 = a.channels == 3, roi = a.roi != nullptr, pair = a.frames2 != nullptr;
         if (a.bayer) {
             u64 r_row, r_col;
             bayer_parity_bits(a.bayer + s0, n, r_row, r_col);
-            launch_raw(g, k, r_row, r_col, wide, n, st);
+            lift_bools([&](auto ROI, auto PAIR) { launch(k_diff_raw_wide<ROI, PAIR>, k_diff_raw_narrow<ROI, PAIR>, r_row, r_col); }, roi, pair);
         } else if (a.ud_map1) {
-            const MapPlanes m{a.ud_map1, a.ud_map2, a.ud_stride};
-            if (a.channels == 3) launch_remap<3>(g, k, m, wide, n, st);
-            else launch_remap<1>(g, k, m, wide, n, st);
-        } else if (a.channels == 3) launch_ch<3>(g, k, wide, n, st);
-        else launch_ch<1>(g, k, wide, n, st);
+            lift_bools([&](auto CH3, auto ROI, auto PAIR) {
+                launch(k_diff_remap_wide<CH3 ? 3 : 1, ROI, PAIR>, k_diff_remap_narrow<CH3 ? 3 : 1, ROI, PAIR>, a.ud_map1, a.ud_map2, a.ud_stride);
+            }, ch3, roi, pair);
+        } else {
+            lift_bools([&](auto CH3, auto ROI, auto PAIR) { launch(k_diff_wide<CH3 ? 3 : 1, ROI, PAIR>, k_diff_narrow<CH3 ? 3 : 1, ROI, PAIR>); }, ch3, roi, pair);
+        }
     }
 }
 

@@ -112,37 +112,43 @@ struct MarkerFilters {
     bool append = false;                       // inside oatgpu_track_markers_sequence_dev: every collected set is kept
 };
 
-// the motion tracker (oatgpu_set_diff_tracker; kernels_diff.hip): `framefilt col -C GREY` -> `posidet diff` for every
-// camera of the context.  Everything below is made by the switch, never inside a step.  A frame's back half runs in the context's
-// scratch set `slot` (0..3) under open_sync's drain, the way detect_tail uses set 0 -- with the MORPH and FINAL planes replaced by
-// the tracker's own, so that oatgpu_read_diff_mask holds whatever the context's other calls do in between.
-struct DiffTracker {
-    static constexpr int kSlots = 4;           // frames in flight inside oatgpu_diff_sequence_dev (= kSeqSlots)
-    bool on = false;
-    DevMem<u64> bits;                          // [kSlots][n][Palloc/64] the front kernel's threshold words
-    DevMem<u64> masks;                         // [kSlots][2][n][Palloc/64] the slot's morph / fin planes (the taps)
-    HostMem<ResultRec> rec;                    // host-mapped: [kSlots][n] result records, written by the blob kernels through dev()
-    Event ev_front[kSlots];                    // stream A: the front launch that wrote this slot's bits has finished
-    Event ev_done[kSlots];                     // the slot's back half has finished
-    int last = -1;                             // slot of the latest diff frame (oatgpu_read_diff_mask); -1: none yet
-    std::vector<char> last_dilated;            // [n] of that frame: the stream's back half dilated (its MORPH tap is the morph plane)
-};
+// frames a batched tracker has in flight inside its sequence call (run_sequence_in_flight); each sits in a slot of its own
+constexpr int kSeqSlots = 4;
 
-// the subtraction tracker (oatgpu_set_bsub_tracker; kernels_bsubtrack.hip): `framefilt bsub` -> `col -C HSV` -> `posidet
-// hsv` (GREY: bsub -> `posidet thresh`) for every camera of the context.  Made by the switch, never inside a step; a frame's back
-// half runs in the context's scratch set `slot` (0..3) under open_sync's drain with the TMP, MORPH and FINAL planes replaced by the
-// tracker's own, so that oatgpu_read_bsub_mask holds whatever the context's other calls do in between.  The background itself --
-// bsub_bg, bsub_f, bsub_have -- is the context's: oatgpu_bsub_filter's.
-struct BsubTracker {
-    static constexpr int kSlots = 4;           // frames in flight inside oatgpu_bsub_track_sequence_dev (= kSeqSlots)
+// What a batched tracker keeps for every camera of the context.  Everything below is made by the tracker's switch (alloc), never
+// inside a step.  A frame's back half runs in the context's scratch set `slot` (0..3) under open_sync's drain, the way detect_tail
+// uses set 0 -- with the planes behind the taps replaced by the tracker's own, so that oatgpu_read_diff_mask / oatgpu_read_bsub_mask
+// hold whatever the context's other calls do in between.
+// (Not `BatchedTracker`: oat-track-hip has a class of that name, and the structs of this header are global -- the program's
+// destructor would stand in for the library's: tests/test_abi_exports.py::test_no_cxx_symbol_is_shared_with_a_host_program.)
+struct BatchedTrackerState {
+    int planes;                                // mask planes a slot
     bool on = false;
-    DevMem<u64> bits;                          // [kSlots][n][Palloc/64] the front kernel's threshold words
-    DevMem<u64> masks;                         // [kSlots][3][n][Palloc/64] the slot's tmp / morph / fin planes (the taps)
-    HostMem<ResultRec> rec;                    // host-mapped: [kSlots][n] result records, written by the blob kernels through dev()
-    Event ev_front[kSlots];                    // stream A: the front launch that wrote this slot's bits has finished
-    Event ev_done[kSlots];                     // the slot's back half has finished
-    int last = -1;                             // slot of the latest frame (oatgpu_read_bsub_mask); -1: none yet
-    const u64 *last_tap = nullptr;             // of that frame: where the mask after erode / dilate is (the MORPH tap)
+    size_t n = 0, words = 0;                   // camera streams, and the words of one plane of all of them: n * Palloc / 64
+    DevMem<u64> bits;                          // [kSeqSlots][n][Palloc/64] the front kernel's threshold words
+    DevMem<u64> masks;                         // [kSeqSlots][planes][n][Palloc/64] the slot's planes (the taps)
+    HostMem<ResultRec> rec;                    // host-mapped: [kSeqSlots][n] result records, written by the blob kernels through dev()
+    Event ev_front[kSeqSlots];                 // stream A: the front launch that wrote this slot's bits has finished
+    Event ev_done[kSeqSlots];                  // the slot's back half has finished
+    int last = -1;                             // slot of the tracker's latest frame (oatgpu_read_*_mask); -1: none yet
+    explicit BatchedTrackerState(int planes) : planes(planes) {}
+    bool alloc(const oatgpu_ctx *c);           // all of the above, planes zeroed, `on` set; false: hipGetLastError() has the reason
+    u64 *bits_of(int slot) const { return bits + (size_t)slot * words; }
+    u64 *mask(int slot, int which) const { return masks + ((size_t)slot * planes + which) * words; }
+    ResultRec *rec_dev(int slot) const { return rec.dev() + (size_t)slot * n; }
+};
+// the motion tracker (oatgpu_set_diff_tracker; kernels_diff.hip): `framefilt col -C GREY` -> `posidet diff`.
+// Planes: morph, fin.
+struct DiffTracker : BatchedTrackerState {
+    DiffTracker() : BatchedTrackerState(2) {}
+    std::vector<char> last_dilated;            // [n] of the latest frame: the stream's back half dilated (its MORPH tap is the morph plane)
+};
+// the subtraction tracker (oatgpu_set_bsub_tracker; kernels_bsubtrack.hip): `framefilt bsub` -> `col -C HSV` ->
+// `posidet hsv` (GREY: bsub -> `posidet thresh`).  Planes: tmp, morph, fin.  The background itself -- bsub_bg, bsub_f, bsub_have --
+// is the context's: oatgpu_bsub_filter's.
+struct BsubTracker : BatchedTrackerState {
+    BsubTracker() : BatchedTrackerState(3) {}
+    const u64 *last_tap = nullptr;             // of the latest frame: where the mask after erode / dilate is (the MORPH tap)
 };
 
 // the filter chain behind the two batched trackers (oatgpu_set_tracker_filters; kernels_trackfilt.hip): kalman ->
@@ -150,12 +156,11 @@ struct BsubTracker {
 // state per camera stream for the context -- both trackers advance it; not c->kal's and not the marker chain's.  Everything below
 // is made by the setter, never inside a step.
 struct TrackerFilters {
-    static constexpr int kSlots = 4;           // = DiffTracker::kSlots = BsubTracker::kSlots
     bool on = false;
     DevMem<MarkerFilterParams> params;         // device: the chain's parameters and the region table
     DevMem<KalmanState> state;                 // device: [n] the chain's own filter state
-    HostMem<MarkerFiltered> out;               // host-mapped: [kSlots][n] the slot's filtered set, written by k_tracker_filters through dev()
-    Event ev[kSlots];                          // the slot's filter launch has finished: frame t's launch waits for frame t - 1's
+    HostMem<MarkerFiltered> out;               // host-mapped: [kSeqSlots][n] the slot's filtered set, written by k_tracker_filters through dev()
+    Event ev[kSeqSlots];                       // the slot's filter launch has finished: frame t's launch waits for frame t - 1's
     std::vector<oatgpu_filtered> last;         // [sets][n] what the latest tracker call delivered (oatgpu_tracker_filtered)
     int last_sets = 0;
 };
@@ -399,6 +404,14 @@ int chain_params(oatgpu_ctx *c, const oatgpu_marker_filters *f, MarkerFilterPara
 int tracker_filters_launch(oatgpu_ctx *c, const ResultRec *rec_dev, int slot, int prev_slot, hipStream_t st);
 void tracker_filters_begin(oatgpu_ctx *c);
 void tracker_filters_keep(oatgpu_ctx *c, int slot);
+// ... and what the two batched trackers share; `name` is "diff" or "bsub", `what` the call's name in a refusal
+int tracker_refusals(oatgpu_ctx *c, const BatchedTrackerState &bt, const char *name, const char *what);
+int check_batch_dev(oatgpu_ctx *c, const void *frames_dev, const oatgpu_position *out);
+int check_batch(oatgpu_ctx *c, const uint8_t *const *frames_host, int n, const oatgpu_position *out);
+int check_sequence_dev(oatgpu_ctx *c, const void *const *frames_dev, int n_frames, const oatgpu_position *out);
+int open_tap(oatgpu_ctx *c, const BatchedTrackerState &bt, const char *name, const char *none_yet, int s, int which, const uint8_t *out);
+int reset_have(oatgpu_ctx *c, std::vector<char> &have, int s);
+void tracker_hand_out(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, oatgpu_position *out);
 // api_measure.hip
 void prof_fold(oatgpu_ctx *c);
 #pragma GCC visibility pop
@@ -429,12 +442,15 @@ static inline RangeParams range_of(const oatgpu_marker &k)
 static inline size_t track_in_bytes(const oatgpu_ctx *c) { return (size_t)c->g.H * c->g.W * (c->by_track ? 1 : c->cfg.channels); }
 // ... and as the motion and the subtraction tracker take it: RAW8 with oatgpu_set_tracker_bayer on
 static inline size_t tracker_in_bytes(const oatgpu_ctx *c) { return (size_t)c->g.H * c->g.W * (c->tb_on ? 1 : c->cfg.channels); }
-static inline const int *tracker_bayer(const oatgpu_ctx *c) { return c->tb_on ? c->tb_pat.data() : nullptr; }
-// ... and the maps their front kernels remap with: oatgpu_set_tracker_undistort on (a DiffLaunch or a BsubLaunch)
-template <class Launch> static inline void tracker_undistort(const oatgpu_ctx *c, Launch &a)
+// ... and what the front launch of either takes from the context: frame set f1 (f2: and the next) into the bits of `slot` (and
+// slot2), the ROI, the Bayer patterns with oatgpu_set_tracker_bayer on, the streams' maps with oatgpu_set_tracker_undistort on
+static inline void tracker_front(const oatgpu_ctx *c, const BatchedTrackerState &bt, const void *f1, const void *f2, int slot, int slot2, FrontLaunch &a)
 {
-    if (!c->tu_on) return;
-    a.ud_map1 = c->ud_map1; a.ud_map2 = c->ud_map2; a.ud_stride = c->ud_stride;
+    a.frames = (const uint8_t *)f1; a.frames2 = (const uint8_t *)f2; a.channels = c->cfg.channels;
+    a.bits = bt.bits_of(slot); a.bits2 = f2 ? bt.bits_of(slot2) : nullptr;
+    a.roi = c->roi;
+    a.bayer = c->tb_on ? c->tb_pat.data() : nullptr;
+    if (c->tu_on) { a.ud_map1 = c->ud_map1; a.ud_map2 = c->ud_map2; a.ud_stride = c->ud_stride; }
 }
 // frame i of the step as K1 and the marker kernels see it: remapped, demosaiced, or the caller's own
 static inline const uint8_t *step_frame(const oatgpu_ctx *c, int i, const void *given)
@@ -455,12 +471,30 @@ static inline u64 *thr_buf(oatgpu_ctx *c, int parity)
 // stream sits on the last B stream's hardware queue (see acquire_streams)
 static inline int plain_b_streams(const oatgpu_ctx::FrameJob &f) { return f.ready ? 2 : oatgpu_ctx::kNB; }
 
+// The switch of a batched tracker (oatgpu_set_diff_tracker, oatgpu_set_bsub_tracker; c is not null).  Off: the tracker is dropped.
+// On: a new one is built aside -- extra(made, ok) first: what this tracker needs besides, an error code or ok = false for a failed
+// allocation -- and the context takes it when everything worked.
+template <class Tracker, class Extra> static int set_batched_tracker(oatgpu_ctx *c, Tracker &cur, int on, const char *name, Extra extra)
+{
+    if (c->ring_count || c->staged_count) return fail(c, OATGPU_E_INVALID, "set_%s_tracker while enqueued results are outstanding", name);
+    if (!on == !cur.on) return OATGPU_OK;
+    int rc = open_sync(c);
+    if (rc) return rc;
+    if (!on) { cur = Tracker{}; return OATGPU_OK; }
+    Tracker made;
+    bool ok = true;
+    rc = extra(made, ok);
+    if (rc) return rc;
+    if (!ok || !made.alloc(c)) return fail(c, OATGPU_E_NOMEM, "%s tracker: allocation failed: %s", name, hipGetErrorString(hipGetLastError()));
+    cur = std::move(made);
+    return OATGPU_OK;
+}
+
 // A recorded sequence of a batched tracker (api_diff.hip, api_bsubtrack.hip) with up to kSeqSlots frames in flight.  Front launches
 // go to stream A, frames_of(t) (1 or 2) frames a launch; front(t, nf, q, q2) issues the one for frames t (.. t + 1) into slots q
 // (and q2); frame t's back half -- back(slot, i, B), i = its place in the front launch -- runs on B[t % 3] behind the front launch's
 // event in slot t % kSeqSlots, and a slot is reused only after hand_out(slot, frame) has collected it.  Everything is collected
 // before the call returns; on an error nothing of the call stays in flight.
-constexpr int kSeqSlots = 4;
 template <class FramesOf, class Front, class Back, class HandOut>
 static int run_sequence_in_flight(oatgpu_ctx *c, int n_frames, Event *ev_front, Event *ev_done, FramesOf frames_of, Front front,
                                   Back back, HandOut hand_out)

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace oatgpu {
 
@@ -153,45 +154,48 @@ void launch_state_import(const Geom &g, float *state, uint8_t *nmodes, int nmix,
                          const uint8_t *modes_used, const float *weight, const float *variance,
                          const float *mean, hipStream_t st);
 
-// --- kernels_diff.hip --- (the motion tracker's front end: col GREY -> posidet diff's absdiff + threshold)
-struct DiffLaunch {
+// --- kernels_diff.hip, kernels_bsubtrack.hip --- (the front ends of the two batched trackers)
+// what both front launches take: the frames, where the threshold words go, and the frames' form
+struct FrontLaunch {
     const uint8_t *frames;   // [n][H*W*channels] packed BGR (3) or GREY (1), stream-major
-    const uint8_t *frames2;  // nullptr, or the NEXT frame of every stream: the launch advances two frames (every stream has a last image)
+    const uint8_t *frames2;  // nullptr, or the NEXT frame of every stream: the launch advances two frames
     int channels;
-    uint8_t *last;           // [n][H*W] previous GREY frame of every stream, refreshed by the launch
-    const char *have_last;   // HOST: [n] 0: the stream's first frame (bit = g != 0)
     u64 *bits, *bits2;       // [n][Palloc/64] threshold words of the frame(s); every word is written
-    const u64 *roi;          // [n][Palloc/64] region-of-interest bits (framefilt mask in front of col) or nullptr
-    int thr;
+    const u64 *roi;          // [n][Palloc/64] region-of-interest bits (framefilt mask in front of everything else) or nullptr
     const int *bayer;        // HOST: nullptr, or [n] OATGPU_BAYER_* 1..4 (checked by the caller; channels == 3, H, W >= 3): frames / frames2
-                             // are Bayer RAW8, [n][H*W], demosaiced in registers
+                             // are Bayer RAW8, [n][H*W], demosaiced in registers; the tracker's own images stay BGR
     const uint32_t *ud_map1; // nullptr, or the undistortion maps of the n streams (plane 0; stream s at + s * ud_stride entries,
     const uint16_t *ud_map2; //   ud_stride = undistort_map_stride(H, W)): frames / frames2 are remapped in registers, every stream
-    size_t ud_stride;        //   with its own map; not together with bayer
+    size_t ud_stride;        //   with its own map, the tracker's own images are in undistorted coordinates; not together with bayer
+};
+// Run-time switches as template arguments: f(std::bool_constant<b>{}...) for the bools given, in their order.  The front
+// launches pick their kernel instantiation with it.
+template <class F> void lift_bools(F &&f) { f(); }
+template <class F, class... Rest> void lift_bools(F &&f, bool b, Rest... rest)
+{
+    if (b) lift_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else lift_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+// the motion tracker's front end: col GREY -> posidet diff's absdiff + threshold, DESIGN.md 9c
+struct DiffLaunch : FrontLaunch {   // (frames2: every stream has a last image)
+    uint8_t *last;           // [n][H*W] previous GREY frame of every stream, refreshed by the launch
+    const char *have_last;   // HOST: [n] 0: the stream's first frame (bit = g != 0)
+    int thr;
 };
 // 4 pixels a lane with dword accesses: W % 4 == 0 and frames / frames2 / last 4-byte aligned (with ud_map1: `last` alone, the
 // frames are gathered with unaligned loads); otherwise one pixel a lane
 bool diff_front_is_wide(const Geom &g, const DiffLaunch &a);
 void launch_diff_front(const Geom &g, const DiffLaunch &a, int n_streams, hipStream_t st);
 
-// --- kernels_bsubtrack.hip --- (the subtraction tracker's front end: bsub -> col HSV -> inRange, or bsub -> inRange for GREY)
-struct BsubLaunch {
-    const uint8_t *frames;   // [n][H*W*channels] packed BGR (3) or GREY (1), stream-major
-    const uint8_t *frames2;  // nullptr, or the NEXT frame of every stream: the launch advances two frames
-    int channels;
+// the subtraction tracker's front end: bsub -> col HSV -> inRange, or bsub -> inRange for GREY, DESIGN.md 9d
+struct BsubLaunch : FrontLaunch {
     uint8_t *bg;             // [n][H*W*channels] framefilt bsub's background of every stream
     float *acc;              // [n][H*W*channels] ... and its fp32 accumulator
     const char *have;        // HOST: [n] 0: the stream's first frame (acc = bg = the masked frame)
-    u64 *bits, *bits2;       // [n][Palloc/64] threshold words of the frame(s); every word is written
-    const u64 *roi;          // [n][Palloc/64] region-of-interest bits (framefilt mask in front of bsub) or nullptr
     RangeParams rp;          // the window on hsv(difference); GREY: lo[0] <= difference <= hi[0]
     bool learn;              // alpha > 0: cv::accumulateWeighted with a = (float)alpha, b = 1 - a
     float a, b;
-    const int *bayer;        // HOST: nullptr, or [n] OATGPU_BAYER_* 1..4 (checked by the caller; channels == 3, H, W >= 3): frames / frames2
-                             // are Bayer RAW8, [n][H*W], demosaiced in registers; bg and acc stay BGR
-    const uint32_t *ud_map1; // nullptr, or the undistortion maps of the n streams (DiffLaunch's): frames / frames2 are remapped in
-    const uint16_t *ud_map2; //   registers, bg and acc are images in undistorted coordinates; not together with bayer
-    size_t ud_stride;
 };
 // 4 pixels a lane: W % 4 == 0, frames / frames2 / bg 4-byte and acc 16-byte aligned (with ud_map1: bg and acc alone); otherwise
 // one pixel a lane

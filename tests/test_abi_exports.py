@@ -102,3 +102,24 @@ def test_only_the_product_library_sits_beside_the_binding():
     """A/B builds live under build/variants (make variant): nothing but liboatgpu.so in oat_amd/lib."""
     libdir = os.path.join(ROOT, "oat_amd", "lib")
     assert sorted(f for f in os.listdir(libdir) if f.endswith(".so")) == ["liboatgpu.so"]
+
+
+def test_no_cxx_symbol_is_shared_with_a_host_program(lib):
+    """The library's internal structs are global C++ types and their inline members are exported weak; a host program that
+    defines a member of the same name is searched first, so the library would run the PROGRAM's code on its own objects (a
+    struct named like oat-track-hip's BatchedTracker once had the program's destructor run at oatgpu_destroy).  No C++ symbol
+    may be defined by both; the standard library's templates, one definition wherever they are instantiated, are exempt."""
+    subprocess.check_call(["make", "-s", "-j4", "-C", ROOT, "host"])
+
+    def defined(path):
+        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True)
+        return {l.split()[-1] for l in out.stdout.splitlines() if l.split()} if out.returncode == 0 else set()
+
+    ours = {s for s in defined(os.path.join(ROOT, "oat_amd", "lib", "liboatgpu.so")) if s.startswith("_Z")}
+    assert ours
+    bins = os.path.join(ROOT, "build", "bin")
+    programs = [b for b in sorted(os.listdir(bins)) if b.startswith("oat-")]
+    assert "oat-track-hip" in programs
+    for b in programs:
+        both = {s for s in ours & defined(os.path.join(bins, b)) if not re.match(r"_ZNK?St|_ZSt|_ZNK?9__gnu_cxx", s)}
+        assert not both, (b, sorted(both))
