@@ -224,6 +224,46 @@ __device__ __forceinline__ void mog2_mode(PxModel<CH, TUP> &s, PxLoop &c, float 
     }
 }
 
+// Iteration 0 of the mode loop as the two-frame default-policy BGR kernel that learns runs it (k_mog_fused, kPair): the same
+// numbers as mog2_mode<3, 0, true, 0> on a loop that starts (background = fits = false, total = 0), written for what all 64
+// lanes of a wave issue -- nearly every wave holds lanes that fit mode 0 and a lane that does not, so it walks both sides of
+// every branch.  No branch round the update: every lane computes it (a lane that does not fit: numbers nobody keeps) and a
+// fitting lane keeps it, one select a register -- as a branch the compiler copied the record tuple out and back, zeroed and
+// moved what the branch merges, and turned 0/1 registers back into lane masks (SQ_INSTS_VALU of the 4K launch: 439.7 ->
+// 426.0 a wave for both frames, profiles/r09_k1_allanes.md).  `total` starts from the
+// weight itself: 0.f + weight is weight but for a -0.f, which only a frame at rate 0 can produce -- that frame keeps the
+// addition, by a scalar branch.  Mode 0 has nowhere to bubble to.  valid: the lane holds a pixel.
+__device__ __forceinline__ void mog2_mode0_pair(PxModel<3, true> &s, PxLoop &c, bool valid, float x0, float x1, float x2,
+                                                const MogParams &P, float alphaT, float alpha1, float prune, unsigned &dvm)
+{
+    const bool live = valid && c.nmodes > 0;
+    const float w1 = alpha1 * s.w[0] + prune;
+    const float var = s.r[0][0], o0 = s.r[0][1], o1 = s.r[0][2], o2 = s.r[0][3];
+    float d0 = o0 - x0, d1 = o1 - x1, d2 = o2 - x2;
+    // (each difference through an opaque register: paired into packed fp32 the means are first copied out of their
+    // odd-aligned place in the record tuple, and back)
+    asm volatile("" : "+v"(d0)); asm volatile("" : "+v"(d1)); asm volatile("" : "+v"(d2));
+    const float dist2 = d0 * d0 + d1 * d1 + d2 * d2;
+    c.background = live && 0.f < P.TB && dist2 < P.Tb * var;
+    c.fits = live && dist2 < P.Tg * var;
+    const float weight = w1 + alphaT;
+    const float k = rate_over_weight<0>(alphaT, weight);
+    float n0 = o0 - k * d0, n1 = o1 - k * d1, n2 = o2 - k * d2;
+    asm volatile("" : "+v"(n0)); asm volatile("" : "+v"(n1)); asm volatile("" : "+v"(n2));
+    float varnew = var + k * (dist2 - var);
+    varnew = __builtin_elementwise_maximum(varnew, P.varMin);         // (NaN-propagating, like OpenCV's macros: mog2_mode)
+    varnew = __builtin_elementwise_minimum(varnew, P.varMax);
+    s.r[0][0] = c.fits ? varnew : var; s.r[0][1] = c.fits ? n0 : o0; s.r[0][2] = c.fits ? n1 : o1; s.r[0][3] = c.fits ? n2 : o2;
+    if (c.fits) dvm |= 1u;
+    const bool pruned = live && !c.fits && w1 < -prune;
+    const float wmiss = pruned ? 0.f : w1;
+    if (live) s.w[0] = c.fits ? weight : wmiss;
+    if (pruned) c.nmodes--;
+    float total = live ? s.w[0] : 0.f;
+    if (alphaT == 0.f) total = 0.f + total;
+    c.total = total;
+}
+
 // Everything behind the mode loop: renormalisation, `nmodes = nNewModes;`, the new mode, the mask.
 // nentry: mode count at entry (the reference's nNewModes).  Returns the foreground-mask value
 // {0, shadowVal, 255}; nmodes_out: the count to store; wchg: weights may differ from what was loaded
@@ -491,6 +531,9 @@ __global__ __launch_bounds__(WG, (k1_waves<CH, AUDIT, NTLD, NF>())) void k_mog_f
     // (late arguments: the product two-frame BGR instantiation only -- the others are not bound by their instruction count
     // or were left as compiled)
     constexpr bool kLate = !NTLD && !AUDIT && CH == 3;
+    // ... and of those the one the everyday pipelined path lives on: its pixels come as one dword each, and its mode-0 iteration is
+    // mog2_mode0_pair -- measured together (neither pays alone: profiles/r09_k1_allanes.md)
+    constexpr bool kPair = kLate && NF == 2 && !FROZEN;
     KArgs ka = (KArgs)((KBytes)__builtin_amdgcn_kernarg_segment_ptr() + kMogLaunchArgOffset);
     // Nothing here spends vector instructions on what the scalar unit or the address path can do (the kernel was
     // 79 % VALU-busy at 370 VALU instructions per wave before, profiles/r02_k1_sq_counters_before.md): every plane
@@ -655,14 +698,34 @@ __global__ __launch_bounds__(WG, (k1_waves<CH, AUDIT, NTLD, NF>())) void k_mog_f
         AU_REC(active, false);
     }
     // no branch around the pixel loads either (lanes beyond the image read pixel 0 and ignore it)
-    {
+    unsigned px1 = 0;                             // kPair: the first frame's pixel, packed like px2 below
+    unsigned px2 = 0;                             // NF == 2: the second frame's pixel, packed b | g << 8 | r << 16
+    if constexpr (kPair) {
+        // One dword a pixel: the three bytes of a BGR pixel are contiguous, an unaligned 32-bit load at byte fi brings them and
+        // the byte behind them, which nothing reads (bits 24..31 of px1 / px2 are never looked at).  The load must stay inside
+        // the caller's buffer: a lane of pixel i reads bytes 3i .. 3i + 3 of its stream, inside the stream's 3 * H * W bytes for
+        // every pixel but the last (3 (H W - 2) + 3 < 3 H W), and a lane without a pixel reads bytes 0 .. 3 (as long as the stream
+        // has two pixels).  Only the lane of a stream's LAST pixel would read one byte past its stream -- past the buffer, if the
+        // stream is the buffer's last.  The wave that holds that pixel, and the waves behind it (no pixels: they are what a
+        // one-pixel stream has besides), keep the byte loads, in EVERY stream: a scalar comparison of the wave's word index, no
+        // per-lane clamp, and nothing to know about where the caller's buffer ends.
+        const unsigned fj = valid ? fi : 0u;
+        const uint8_t *frame2 = a.frames2 + (size_t)s * npx * CH;
+        const unsigned last_word = (unsigned)(g.H - 1) * (unsigned)g.words + ((unsigned)(g.W - 1) >> 6);
+        if (__builtin_amdgcn_readfirstlane(widx) >= last_word) {
+            px1 = (unsigned)frame[fj] | (unsigned)frame[fj + 1] << 8 | (unsigned)frame[fj + 2] << 16;
+            px2 = (unsigned)frame2[fj] | (unsigned)frame2[fj + 1] << 8 | (unsigned)frame2[fj + 2] << 16;
+        } else {
+            __builtin_memcpy(&px1, frame + fj, 4);
+            __builtin_memcpy(&px2, frame2 + fj, 4);
+        }
+    } else {
         const unsigned fj = valid ? fi : 0u;
         b = frame[fj];
         if (CH == 3) { gg = frame[fj + 1]; r = frame[fj + 2]; }
         au.run(valid, CH, false);
     }
-    unsigned px2 = 0;                             // NF == 2: the second frame's pixel, packed b | g << 8 | r << 16
-    if (NF == 2) {
+    if (NF == 2 && !kPair) {
         const uint8_t *frame2 = a.frames2 + (size_t)s * npx * CH;
         const unsigned fj = valid ? fi : 0u;
         px2 = frame2[fj];
@@ -675,15 +738,17 @@ __global__ __launch_bounds__(WG, (k1_waves<CH, AUDIT, NTLD, NF>())) void k_mog_f
     // one bit per pixel, one word per wave.
     if (a.roi_bits) {
         const u64 rw = a.roi_bits[(size_t)s * nwords + widx];
-        if (!((rw >> lpos) & 1ull)) { b = 0; gg = 0; r = 0; px2 = 0; }
+        if (!((rw >> lpos) & 1ull)) { b = 0; gg = 0; r = 0; px1 = 0; px2 = 0; }
     }
 
     const int nold = cnt & kCountMask;
-    const float x0 = (float)b, x1 = (float)gg, x2 = (float)r;
+    const float x0 = kPair ? (float)(px1 & 255u) : (float)b, x1 = kPair ? (float)((px1 >> 8) & 255u) : (float)gg,
+                x2 = kPair ? (float)((px1 >> 16) & 255u) : (float)r;
     PxLoop lp{false, false, nold, 0.f};
     unsigned dvm = 0;           // modes whose variance/mean changed
     bool wchg = false;          // weights changed
-    if (valid) mog2_mode<CH, 0, TUP, kFrozenMode>(pm, lp, x0, x1, x2, a.mp, a.alphaT, a.alpha1, a.prune, dvm, audit_frz);
+    if constexpr (kPair) mog2_mode0_pair(pm, lp, valid, x0, x1, x2, a.mp, a.alphaT, a.alpha1, a.prune, dvm);
+    else if (valid) mog2_mode<CH, 0, TUP, kFrozenMode>(pm, lp, x0, x1, x2, a.mp, a.alphaT, a.alpha1, a.prune, dvm, audit_frz);
     // A pixel that matched mode 0 as background never looks at another mode's variance/mean again this
     // frame (no fit test once fits is set, no shadow test on background, no new mode): what is left for
     // slots >= 1 is the weight decay of the live ones.  Everybody else is "full".
@@ -706,7 +771,7 @@ __global__ __launch_bounds__(WG, (k1_waves<CH, AUDIT, NTLD, NF>())) void k_mog_f
     bool want2 = false;
     constexpr bool kEarly2 = NF == 2 && !NTLD;
     if (kEarly2) {
-        const float z0 = (float)(px2 & 255u), z1 = (float)((px2 >> 8) & 255u), z2 = (float)(px2 >> 16);
+        const float z0 = (float)(px2 & 255u), z1 = (float)((px2 >> 8) & 255u), z2 = (float)((px2 >> 16) & 255u);
         const float var = rv(pm, 0);
         const float e0 = rm<0>(pm, 0) - z0;
         const float e1 = CH == 3 ? rm<1>(pm, 0) - z1 : 0.f;
@@ -771,6 +836,12 @@ __global__ __launch_bounds__(WG, (k1_waves<CH, AUDIT, NTLD, NF>())) void k_mog_f
 
     // frame.setTo(0, mask == 0): shadows (127) stay foreground
     if (mask == 0) { b = 0; gg = 0; r = 0; }
+    // (kPair: the integers only where somebody needs them, a foreground lane's HSV conversion -- through an opaque copy inside
+    // that branch, or the compiler unpacks on every lane in front of it)
+    auto unpack = [&](unsigned q) {
+        asm volatile("" : "+v"(q));
+        b = (int)(q & 255u); gg = (int)((q >> 8) & 255u); r = (int)((q >> 16) & 255u);
+    };
     if (kSingle && work && a.out_mask) a.out_mask[(size_t)(s - a.out_base) * npx + (size_t)y * g.W + x] = (uint8_t)mask;
     if (kSingle && work && a.out_bgr) {
         uint8_t *o = a.out_bgr + (size_t)(s - a.out_base) * npx * CH + fi;
@@ -788,6 +859,7 @@ __global__ __launch_bounds__(WG, (k1_waves<CH, AUDIT, NTLD, NF>())) void k_mog_f
                 KRELOAD(kb);
                 const RangeParams rp = karg_rp(kb);
                 int hh, ss, vv;
+                if (kPair) unpack(px1);
                 bgr2hsv_inline(b, gg, r, hh, ss, vv);
                 thr = work && in_range3(hh, ss, vv, rp);
             }
@@ -814,12 +886,13 @@ __global__ __launch_bounds__(WG, (k1_waves<CH, AUDIT, NTLD, NF>())) void k_mog_f
         au.run(thr1 && lane == 0, 8, true);
         const MogParams mp2 = kLate ? karg_mp(ka) : a.mp;
         const float aT2 = kLate ? ka->alphaT2 : a.alphaT2, a12 = kLate ? ka->alpha12 : a.alpha12, pr2 = kLate ? ka->prune2 : a.prune2;
-        b = (int)(px2 & 255u); gg = (int)((px2 >> 8) & 255u); r = (int)(px2 >> 16);
+        if (!kPair) { b = (int)(px2 & 255u); gg = (int)((px2 >> 8) & 255u); r = (int)((px2 >> 16) & 255u); }
         const int nold2 = nnew;
-        const float y0 = (float)b, y1 = (float)gg, y2 = (float)r;
+        const float y0 = (float)(px2 & 255u), y1 = (float)((px2 >> 8) & 255u), y2 = (float)((px2 >> 16) & 255u);
         PxLoop lq{false, false, nold2, 0.f};
         bool wchg2 = false;
-        if (valid) mog2_mode<CH, 0, TUP, kFrozenMode>(pm, lq, y0, y1, y2, mp2, aT2, a12, pr2, dvm, audit_frz);
+        if constexpr (kPair) mog2_mode0_pair(pm, lq, valid, y0, y1, y2, mp2, aT2, a12, pr2, dvm);
+        else if (valid) mog2_mode<CH, 0, TUP, kFrozenMode>(pm, lq, y0, y1, y2, mp2, aT2, a12, pr2, dvm, audit_frz);
         const bool full2 = valid && !(lq.fits && lq.background);
         if (!kEarly2) {
             // records this lane has not seen yet: it was not full in frame 1 (so its slots >= 1 are as in memory)
@@ -851,6 +924,7 @@ __global__ __launch_bounds__(WG, (k1_waves<CH, AUDIT, NTLD, NF>())) void k_mog_f
                     KRELOAD(kb);
                     const RangeParams rp = karg_rp(kb);
                     int hh, ss, vv;
+                    if (kPair) unpack(px2);
                     bgr2hsv_inline(b, gg, r, hh, ss, vv);
                     thr = work && in_range3(hh, ss, vv, rp);
                 }
