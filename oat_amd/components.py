@@ -460,29 +460,53 @@ def _filter_chain(kalman, homography, regions):
     return f, names, (arr, keep)
 
 
+def _set_chain(ctx, entry, kalman, homography, regions):
+    """A chain through `entry` (oatgpu_set_marker_filters, oatgpu_set_tracker_filters); the context remembers its region names."""
+    f, names, _keep = _filter_chain(kalman, homography, regions)
+    ctx._chk(entry(ctx.ctx, C.byref(f)))
+    ctx._region_names = names
+
+
+def _read_chain(ctx, entry, sets):
+    """The filtered sets of the latest delivering call through `entry` (oatgpu_marker_filtered, oatgpu_tracker_filtered), with
+    room for `sets` of them: a list with one list of n_streams Filtered per frame set."""
+    n, sets = ctx.n_streams, max(sets, 1)
+    out = (ffi.Filtered * (sets * n))()
+    rc = entry(ctx.ctx, out, sets)
+    if rc < 0:
+        ctx._chk(rc)
+    names = getattr(ctx, "_region_names", [])
+    return [[Filtered.from_c(out[t * n + s], names) for s in range(n)] for t in range(rc)]
+
+
 def _packed_shape(ctx):
     """A BGR / GREY frame of the context, whatever its track calls take at the moment."""
     return (ctx.rows, ctx.cols, 3) if ctx.channels == 3 else (ctx.rows, ctx.cols)
 
 
+def _set_bayer(ctx, entry, patterns):
+    """Bayer RAW8 ingest through `entry` (oatgpu_set_track_bayer, oatgpu_set_tracker_bayer), and the frames the track calls take."""
+    if patterns is None:
+        ctx._chk(entry(ctx.ctx, None, 0))
+        ctx.frame_shape = _packed_shape(ctx)
+        return
+    arr, n = _bayer_patterns(patterns)
+    ctx._chk(entry(ctx.ctx, arr, n))
+    ctx.frame_shape = (ctx.rows, ctx.cols)
+
+
 class _TrackerBayer:
-    """oatgpu_set_tracker_bayer for the batched trackers (mirrors HotPath.bayer)."""
+    """oatgpu_set_tracker_bayer for the batched trackers (HotPath.bayer is the same body, _set_bayer, on its own entry point)."""
 
     def bayer(self, patterns):
         """oatgpu_set_tracker_bayer: track, track_dev and track_sequence_dev take Bayer RAW8 frames (rows, cols) and the front
         kernel demosaics them in registers; the state stays in the demosaiced domain.  patterns: a name ("RGGB") or value for
         every stream, a list of n_streams of them, or None to switch it off (frames are BGR again)."""
-        if patterns is None:
-            self._chk(self.lib.oatgpu_set_tracker_bayer(self.ctx, None, 0))
-            self.frame_shape = _packed_shape(self)
-            return
-        arr, n = _bayer_patterns(patterns)
-        self._chk(self.lib.oatgpu_set_tracker_bayer(self.ctx, arr, n))
-        self.frame_shape = (self.rows, self.cols)
+        _set_bayer(self, self.lib.oatgpu_set_tracker_bayer, patterns)
 
 
 class _TrackerUndistort:
-    """oatgpu_set_tracker_undistort for the batched trackers (mirrors HotPath.set_undistort / HotPath.undistort)."""
+    """oatgpu_set_tracker_undistort for the batched trackers (mirrors HotPath.undistort; set_undistort is HotPath's too)."""
 
     def set_undistort(self, stream, camera_matrix, distortion_coeffs):
         """The undistortion map of one camera stream (oatgpu_set_undistort): camera_matrix 9 values, distortion_coeffs
@@ -506,28 +530,20 @@ class _TrackerUndistort:
 
 
 class _TrackerFilters:
-    """oatgpu_set_tracker_filters / oatgpu_tracker_filtered for the batched trackers (mirrors HotPath.set_marker_filters /
-    HotPath.marker_filtered)."""
+    """oatgpu_set_tracker_filters / oatgpu_tracker_filtered for the batched trackers (HotPath.set_marker_filters / marker_filtered
+    are the same bodies, _set_chain / _read_chain, on their own entry points)."""
 
     def set_filters(self, kalman=None, homography=None, regions=None):
         """oatgpu_set_tracker_filters: the chain behind every camera's detection, in the fixed order kalman -> homography ->
         region; arguments as HotPath.set_marker_filters.  All None switches the chain off.  A successful call restarts every
         camera's Kalman state; track, track_dev and track_sequence_dev then advance it by one sample a frame."""
-        f, names, _keep = _filter_chain(kalman, homography, regions)
-        self._chk(self.lib.oatgpu_set_tracker_filters(self.ctx, C.byref(f)))
-        self._region_names = names
+        _set_chain(self, self.lib.oatgpu_set_tracker_filters, kalman, homography, regions)
 
     def filtered(self):
         """oatgpu_tracker_filtered: the filtered records of the frame sets the latest track call delivered -- a list with one
         entry per frame set (one for track / track_dev, one per frame for track_sequence_dev), each a list of n_streams
         Filtered.  Nothing is consumed."""
-        n, sets = self.n_streams, max(getattr(self, "_tf_sets", 1), 1)
-        out = (ffi.Filtered * (sets * n))()
-        rc = self.lib.oatgpu_tracker_filtered(self.ctx, out, sets)
-        if rc < 0:
-            self._chk(rc)
-        names = getattr(self, "_region_names", [])
-        return [[Filtered.from_c(out[t * n + s], names) for s in range(n)] for t in range(rc)]
+        return _read_chain(self, self.lib.oatgpu_tracker_filtered, getattr(self, "_tf_sets", 1))
 
 
 class MotionTracker(_Detector, _TrackerBayer, _TrackerUndistort, _TrackerFilters):
@@ -698,12 +714,7 @@ class HotPath(_Detector):
                 self.set_undistort(st, K, D)
             self.undistort(True)
 
-    def set_undistort(self, stream, camera_matrix, distortion_coeffs):
-        """The undistortion map of one camera stream (oatgpu_set_undistort): camera_matrix 9 values, distortion_coeffs
-        5 or 8.  Allowed while undistort() is on (a recalibration: it takes effect from the next frame)."""
-        K, D = _calibration(camera_matrix, distortion_coeffs)
-        self._chk(self.lib.oatgpu_set_undistort(self.ctx, int(stream), K.ctypes.data_as(C.POINTER(C.c_double)),
-                                                D.ctypes.data_as(C.POINTER(C.c_double)), D.size))
+    set_undistort = _TrackerUndistort.set_undistort        # (oatgpu_set_undistort: a stream's one map, whichever tracker reads it)
 
     def undistort(self, on=True):
         """oatgpu_set_track_undistort: every track call remaps each stream's frame with its map before the ROI mask and
@@ -714,13 +725,7 @@ class HotPath(_Detector):
         """oatgpu_set_track_bayer: every track call takes Bayer RAW8 frames (rows, cols) and demosaics them on the device
         before anything else.  patterns: a name ("RGGB") or value for every stream, a list of n_streams of them, or None to
         switch it off (frames are BGR again)."""
-        if patterns is None:
-            self._chk(self.lib.oatgpu_set_track_bayer(self.ctx, None, 0))
-            self.frame_shape = (self.rows, self.cols, 3) if self.channels == 3 else (self.rows, self.cols)
-            return
-        arr, n = _bayer_patterns(patterns)
-        self._chk(self.lib.oatgpu_set_track_bayer(self.ctx, arr, n))
-        self.frame_shape = (self.rows, self.cols)
+        _set_bayer(self, self.lib.oatgpu_set_track_bayer, patterns)
 
     def _out(self):
         return [Position2D.from_c(p) for p in self._pos]
@@ -784,20 +789,12 @@ class HotPath(_Detector):
         -> region.  kalman = None or a dict with any of dt / timeout / sigma_accel / sigma_noise (set_kalman's defaults);
         homography = None or a 3x3 matrix; regions = None or a list of (name, points) with points = [(x, y), ...], tested in
         the order given.  All None switches the chain off.  A successful call restarts every camera's Kalman state."""
-        f, names, _keep = _filter_chain(kalman, homography, regions)
-        self._chk(self.lib.oatgpu_set_marker_filters(self.ctx, C.byref(f)))
-        self._region_names = names
+        _set_chain(self, self.lib.oatgpu_set_marker_filters, kalman, homography, regions)
 
     def marker_filtered(self):
         """oatgpu_marker_filtered: the filtered records of the frame sets the latest marker-result call delivered -- a list with
         one entry per frame set, each a list of n_streams Filtered.  Nothing is consumed."""
-        n, sets = self.n_streams, max(getattr(self, "_mf_sets", 1), 1)
-        out = (ffi.Filtered * (sets * n))()
-        rc = self.lib.oatgpu_marker_filtered(self.ctx, out, sets)
-        if rc < 0:
-            self._chk(rc)
-        names = getattr(self, "_region_names", [])
-        return [[Filtered.from_c(out[t * n + s], names) for s in range(n)] for t in range(rc)]
+        return _read_chain(self, self.lib.oatgpu_marker_filtered, getattr(self, "_mf_sets", 1))
 
     def set_marker_window(self, stream, marker, h=(0, 256), s=(0, 256), v=(0, 256)):
         """oatgpu_set_marker_window: the colour window of one marker for ONE camera; morphology and area stay per marker."""

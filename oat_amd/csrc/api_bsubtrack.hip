@@ -71,7 +71,7 @@ static int bsub_back(oatgpu_ctx *c, int slot, hipStream_t st, int prev_slot = -1
 // one synchronous step on frames in device memory; the context is drained (open_sync)
 static int bsub_step(oatgpu_ctx *c, const void *frames_dev, double alpha, oatgpu_position *out)
 {
-    tracker_filters_begin(c);
+    chain_begin(c->tf);
     int rc = bsub_front(c, frames_dev, nullptr, alpha, 0, 0);
     if (rc) return rc;
     rc = bsub_back(c, 0, c->stream);
@@ -121,7 +121,7 @@ extern "C" int oatgpu_bsub_track_sequence_dev(oatgpu_ctx *c, const void *const *
     if (rc) return rc;
     const int n = c->cfg.n_streams;
     int prev = -1;                         // slot of the frame before (the filter chain's order)
-    tracker_filters_begin(c);
+    chain_begin(c->tf);
     return run_sequence_in_flight(
         c, n_frames, c->bs.ev_front, c->bs.ev_done, [&](int t) { return t + 1 < n_frames ? 2 : 1; },
         [&](int t, int nf, int q, int q2) { return bsub_front(c, frames_dev[t], nf == 2 ? frames_dev[t + 1] : nullptr, alpha, q, q2); },

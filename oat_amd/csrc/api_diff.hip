@@ -65,7 +65,7 @@ static int diff_back(oatgpu_ctx *c, int slot, const char *have, hipStream_t st, 
 static int diff_step(oatgpu_ctx *c, const void *frames_dev, oatgpu_position *out)
 {
     const std::vector<char> have = c->diff_have;
-    tracker_filters_begin(c);
+    chain_begin(c->tf);
     int rc = diff_front(c, frames_dev, nullptr, 0, 0);
     if (rc) return rc;
     c->diff_have.assign(have.size(), 1);
@@ -116,7 +116,7 @@ extern "C" int oatgpu_diff_sequence_dev(oatgpu_ctx *c, const void *const *frames
     const std::vector<char> all(c->diff_have.size(), 1);
     std::vector<char> have;                // the state the launch's first frame met
     int prev = -1;                         // slot of the frame before (the filter chain's order)
-    tracker_filters_begin(c);
+    chain_begin(c->tf);
     return run_sequence_in_flight(
         c, n_frames, c->df.ev_front, c->df.ev_done,
         [&](int t) {

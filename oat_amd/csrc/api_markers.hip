@@ -277,93 +277,27 @@ extern "C" int oatgpu_track_markers_dev(oatgpu_ctx *c, const void *frames_dev, d
     for (int s = 0; s < n; ++s)
         for (int m = 0; m < M; ++m) to_position(r[(size_t)m * n + s], &markers[(size_t)s * M + m]);
     if (mean) memcpy(mean, r + (size_t)M * n, (size_t)n * sizeof(oatgpu_combined));
-    if (c->mf.on) keep_filtered(c, c->mf.out_host.host());
+    if (c->mf.on) { chain_begin(c->mf); chain_keep(c, c->mf, c->mf.out_host.host()); }
     return OATGPU_OK;
 }
 
-// The parameters of a chain kalman -> homography -> region as the kernels take them, checked: oatgpu_set_marker_filters' and
-// oatgpu_set_tracker_filters' limits and messages.  Nothing of the context changes.
-int chain_params(oatgpu_ctx *c, const oatgpu_marker_filters *f, MarkerFilterParams &p)
-{
-    memset(&p, 0, sizeof p);
-    if (f->kalman) {
-        if (!(f->dt > 0) || !(f->timeout >= 0) || !(f->sigma_accel >= 0) || !(f->sigma_noise >= 0) || !(f->timeout / f->dt < 2147483647.0))
-            return fail(c, OATGPU_E_INVALID, "kalman: dt must be > 0, timeout / sigma-accel / sigma-noise >= 0");
-        p.kalman = 1;
-        p.dt = f->dt; p.sig_accel = f->sigma_accel; p.sig_noise = f->sigma_noise;
-        p.threshold = (int)(f->timeout / f->dt);                 // KalmanFilter2D.cpp:74-76
-    }
-    if (f->homography) {
-        p.homography = 1;
-        for (int i = 0; i < 9; ++i) p.h[i] = f->h[i];
-    }
-    if (f->n_regions < 0 || f->n_regions > kMaxRegions) return fail(c, OATGPU_E_INVALID, "at most %d regions (got %d)", kMaxRegions, f->n_regions);
-    if (f->n_regions > 0 && !f->regions) return fail(c, OATGPU_E_INVALID, "null argument");
-    p.n_regions = f->n_regions;
-    int at = 0;
-    for (int r = 0; r < f->n_regions; ++r) {
-        const oatgpu_region &g = f->regions[r];
-        if (!memchr(g.name, 0, sizeof g.name))
-            return fail(c, OATGPU_E_INVALID, "region %d: a name takes at most %d bytes", r, (int)sizeof g.name - 1);
-        if (g.n_points < 0 || g.n_points > kMaxRegionPoints)
-            return fail(c, OATGPU_E_INVALID, "region %d (%s): at most %d points (got %d)", r, g.name, kMaxRegionPoints, g.n_points);
-        if (g.n_points > 0 && !g.xy) return fail(c, OATGPU_E_INVALID, "null argument");
-        p.region[r][0] = at; p.region[r][1] = g.n_points;
-        for (int i = 0; i < g.n_points; ++i, ++at)
-            for (int k = 0; k < 2; ++k) {
-                const double v = nearbyint(g.xy[2 * i + k]);     // (cv::Point)cv::Point2d: cvRound, ties to even
-                if (!(fabs(v) <= 32767.0)) return fail(c, OATGPU_E_INVALID, "region %d (%s): point %d is beyond +-32767", r, g.name, i);
-                p.verts[at][k] = (int)v;
-            }
-    }
-    return OATGPU_OK;
-}
-
-// The filter chain behind the combined record: `posifilt kalman` -> `posifilt homography` -> `posifilt region` (oatgpu.h).
-// Everything is checked before anything changes.
+// The filter chain behind the combined record: `posifilt kalman` -> `posifilt homography` -> `posifilt region` (oatgpu.h).  The
+// chain's host side is api_trackfilt.hip's and configure_chain's (oatgpu_ctx.h); the marker chain's own: its precondition, the
+// synchronous step's output buffers, its texts.
 extern "C" int oatgpu_set_marker_filters(oatgpu_ctx *c, const oatgpu_marker_filters *f)
 {
     if (!c) return OATGPU_E_INVALID;
-    if (c->ring_count || c->staged_count) return fail(c, OATGPU_E_INVALID, "set_marker_filters while enqueued results are outstanding");
-    if (c->mk.n == 0) return fail(c, OATGPU_E_INVALID, "marker sets are not configured (oatgpu_set_markers)");
-    const bool on = f && (f->kalman || f->homography || f->n_regions > 0);
-    std::vector<MarkerFilterParams> hp(on ? 1 : 0);      // (8 KiB: not on the stack)
-    if (on) {
-        const int prc = chain_params(c, f, hp[0]);
-        if (prc) return prc;
-    }
-    int rc = open_sync(c);
-    if (rc) return rc;
-    if (!on) { c->mf = {}; return OATGPU_OK; }
-    const size_t n = (size_t)c->cfg.n_streams;
-    MarkerFilters made;                     // first use: built aside, moved in when everything worked
-    const bool first = !c->mf.params;
-    MarkerFilters &mf = first ? made : c->mf;
-    if (first) {
-        bool ok = mf.params.alloc(sizeof(MarkerFilterParams)) == hipSuccess;
-        ok = ok && mf.state.alloc(n * sizeof(KalmanState)) == hipSuccess;
-        ok = ok && mf.out.alloc(n * sizeof(MarkerFiltered)) == hipSuccess;
-        ok = ok && mf.out_host.alloc(n * sizeof(MarkerFiltered), hipHostMallocDefault) == hipSuccess;
-        if (!ok) return fail(c, OATGPU_E_NOMEM, "marker filters: allocation failed: %s", hipGetErrorString(hipGetLastError()));
-    }
-    HIPCHK(c, hipMemcpy(mf.params, hp.data(), sizeof(MarkerFilterParams), hipMemcpyHostToDevice));
-    launch_kalman_reset(mf.state, (int)n, 0u, c->stream);          // every stream's filter from the reference's initial state
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (first) c->mf = std::move(made);
-    c->mf.on = true;
-    c->mf.last_sets = 0;
-    return OATGPU_OK;
+    const char *refused = c->mk.n == 0 ? "marker sets are not configured (oatgpu_set_markers)" : nullptr;
+    return configure_chain(c, c->mf, f, "marker", refused, [](MarkerFilters &mf, size_t n) {
+        return mf.out.alloc(n * sizeof(MarkerFiltered)) == hipSuccess &&
+               mf.out_host.alloc(n * sizeof(MarkerFiltered), hipHostMallocDefault) == hipSuccess;
+    });
 }
 
 extern "C" int oatgpu_marker_filtered(oatgpu_ctx *c, oatgpu_filtered *out, int32_t max_sets)
 {
     if (!c || !out) return fail(c, OATGPU_E_INVALID, "null argument");
-    if (!c->mf.on) return fail(c, OATGPU_E_INVALID, "no filter chain is configured (oatgpu_set_marker_filters)");
-    if (c->mf.last_sets == 0) return fail(c, OATGPU_E_INVALID, "no marker result has been delivered since the filter chain was configured");
-    if (max_sets < c->mf.last_sets) return fail(c, OATGPU_E_INVALID, "room for %d frame sets, the latest call delivered %d", max_sets, c->mf.last_sets);
-    memcpy(out, c->mf.last.data(), (size_t)c->mf.last_sets * c->cfg.n_streams * sizeof(oatgpu_filtered));
-    return c->mf.last_sets;
+    return chain_hand_out(c, c->mf, "marker", "no marker result has been delivered since the filter chain was configured", out, max_sets);
 }
 
 extern "C" int oatgpu_track_markers(oatgpu_ctx *c, const uint8_t *const *frames_host, int32_t n, double lr, oatgpu_position *fg,

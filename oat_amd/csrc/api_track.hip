@@ -74,23 +74,14 @@ static void apply_homography(const oatgpu_ctx *c, oatgpu_position *o)
     }
 }
 
-// contourMoments' epilogue (imgproc/moments.cpp) + siftContours' centroid
-// (DetectorFunc.cpp:54-62) on the exact integer sums.
+// a result record as the position the caller gets: posidet's centroid and area (centroid_of, posfilt_inline.h) and the integer sums
 void to_position(const ResultRec &r, oatgpu_position *o)
 {
     memset(o, 0, sizeof *o);
     o->first_pixel = -1;
-    if (!r.valid) return;
-    const double a00 = (double)r.a00, a10 = (double)r.a10, a01 = (double)r.a01;
-    double db1_2, db1_6;
-    if (a00 > 0) { db1_2 = 0.5; db1_6 = 0.16666666666666666666666666666667; }
-    else { db1_2 = -0.5; db1_6 = -0.16666666666666666666666666666667; }
-    const double m00 = a00 * db1_2, m10 = a10 * db1_6, m01 = a01 * db1_6;
+    if (!centroid_of(r, o->x, o->y, &o->area)) return;
     o->valid = 1;
     o->first_pixel = r.first_pixel;
-    o->x = m10 / m00;
-    o->y = m01 / m00;
-    o->area = m00;
     o->a00 = r.a00; o->a10 = r.a10; o->a01 = r.a01;
     o->raw_valid = 1; o->raw_x = o->x; o->raw_y = o->y;
 }
@@ -754,17 +745,6 @@ static hipError_t wait_short(hipEvent_t e)
     }
 }
 
-// the filtered records of a delivered frame set: the latest set, or one more of the running marker sequence
-void keep_filtered(oatgpu_ctx *c, const MarkerFiltered *f)
-{
-    static_assert(sizeof(oatgpu_filtered) == sizeof(MarkerFiltered), "k_marker_filters writes oatgpu_filtered's layout");
-    const size_t n = (size_t)c->cfg.n_streams;
-    if (!c->mf.append) c->mf.last_sets = 0;
-    c->mf.last.resize((size_t)(c->mf.last_sets + 1) * n);
-    memcpy(c->mf.last.data() + (size_t)c->mf.last_sets * n, f, n * sizeof(oatgpu_filtered));
-    c->mf.last_sets++;
-}
-
 // out: the foreground result (nullptr: not wanted); markers / mean: the marker records of the frame set, [n][M] and [n], from the
 // slot's host-mapped record set (nullptr: not wanted).  With the marker pipeline on the slot's marker work is waited for in
 // any case: the slot's planes and records are free for the next frame set when this returns.
@@ -805,8 +785,10 @@ static int collect_frame(oatgpu_ctx *c, oatgpu_position *out, oatgpu_position *m
             for (int s = 0; s < n; ++s)
                 for (int m = 0; m < M; ++m) to_position(mr[(size_t)m * n + s], &markers[(size_t)s * M + m]);
         if (mean) memcpy(mean, mr + (size_t)M * n, (size_t)n * sizeof(oatgpu_combined));
-        if (c->mf.on && markers)             // a marker-result call: what oatgpu_marker_filtered hands out
-            keep_filtered(c, (const MarkerFiltered *)((const MarkerCombined *)(mr + (size_t)M * n) + n));
+        if (c->mf.on && markers) {           // a marker-result call: what oatgpu_marker_filtered hands out -- this set, or one more
+            if (!c->mf.append) chain_begin(c->mf);          // of oatgpu_track_markers_sequence_dev's
+            chain_keep(c, c->mf, (const MarkerFiltered *)((const MarkerCombined *)(mr + (size_t)M * n) + n));
+        }
         c->mkp.last_slot = slot;
     }
     for (int s = 0; out && s < c->cfg.n_streams; ++s) {
@@ -943,7 +925,7 @@ extern "C" int oatgpu_track_markers_sequence_dev(oatgpu_ctx *c, const void *cons
     if (!c->mkp.on) return fail(c, OATGPU_E_INVALID, "the marker pipeline is off (oatgpu_set_marker_pipeline)");
     if (c->ring_count) return fail(c, OATGPU_E_INVALID, "track_sequence while enqueued results are outstanding");
     c->mf.append = true;                 // oatgpu_marker_filtered: the n_frames sets of this call
-    c->mf.last_sets = 0;
+    chain_begin(c->mf);
     const int rc = sequence_dev(c, frames_dev, n_frames, lr, fg, nullptr, nullptr, markers, mean);
     c->mf.append = false;
     return rc;

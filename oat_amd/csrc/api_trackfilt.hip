@@ -1,7 +1,10 @@
-// api_trackfilt.hip -- what the motion and the subtraction tracker share on the host, and the filter chain behind them.
-// `posifilt kalman` -> `posifilt homography` -> `posifilt region` on the trackers' own result records (kernels_trackfilt.hip,
-// DESIGN.md 9h): one launch a frame behind the slot's back half, in frame order.  api_diff.hip and api_bsubtrack.hip call the
-// three helpers below from their steps; with no chain configured they do nothing.
+// api_trackfilt.hip -- what the motion and the subtraction tracker share on the host, and the filter chain on the host.
+// `posifilt kalman` -> `posifilt homography` -> `posifilt region` has ONE owner here for both of its users, the marker sets'
+// combined record (api_markers.hip) and the trackers' own result records: the checked parameters (chain_params),
+// the list a delivering call keeps (chain_begin, chain_keep) and its hand-out (chain_hand_out); the setters' body is
+// configure_chain (oatgpu_ctx.h).  The trackers' chain runs one launch a frame behind the slot's back half, in frame order
+// (kernels_trackfilt.hip); api_diff.hip and api_bsubtrack.hip call tracker_filters_launch, chain_begin and tracker_hand_out from
+// their steps.
 #include "oatgpu_ctx.h"
 
 // --- what the two trackers' entry points have in common (BatchedTrackerState, oatgpu_ctx.h) ---
@@ -87,10 +90,10 @@ int reset_have(oatgpu_ctx *c, std::vector<char> &have, int s)
 void tracker_hand_out(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, oatgpu_position *out)
 {
     for (size_t s = 0; s < bt.n; ++s) to_position(bt.rec.host()[(size_t)slot * bt.n + s], out + s);
-    tracker_filters_keep(c, slot);
+    if (c->tf.on) chain_keep(c, c->tf, c->tf.out.host() + (size_t)slot * bt.n);
 }
 
-// --- the filter chain ---
+// --- the trackers' launch of the filter chain ---
 
 // The chain on the frame whose result records are rec_dev (the tracker's slot `slot`), on stream st right behind that frame's
 // back half.  Inside a sequence call (st is a B stream) consecutive frames sit on different HIP streams: the launch waits for
@@ -109,66 +112,80 @@ int tracker_filters_launch(oatgpu_ctx *c, const ResultRec *rec_dev, int slot, in
     return OATGPU_OK;
 }
 
-// a tracker call starts: what oatgpu_tracker_filtered hands out is this call's
-void tracker_filters_begin(oatgpu_ctx *c)
+// --- the filter chain, for the marker sets and the trackers alike ---
+
+// The parameters of a chain kalman -> homography -> region as the kernels take them, checked: oatgpu_set_marker_filters' and
+// oatgpu_set_tracker_filters' limits and messages.  Nothing of the context changes.
+int chain_params(oatgpu_ctx *c, const oatgpu_marker_filters *f, MarkerFilterParams &p)
 {
-    if (c->tf.on) c->tf.last_sets = 0;
+    memset(&p, 0, sizeof p);
+    if (f->kalman) {
+        if (!(f->dt > 0) || !(f->timeout >= 0) || !(f->sigma_accel >= 0) || !(f->sigma_noise >= 0) || !(f->timeout / f->dt < 2147483647.0))
+            return fail(c, OATGPU_E_INVALID, "kalman: dt must be > 0, timeout / sigma-accel / sigma-noise >= 0");
+        p.kalman = 1;
+        p.dt = f->dt; p.sig_accel = f->sigma_accel; p.sig_noise = f->sigma_noise;
+        p.threshold = (int)(f->timeout / f->dt);                 // KalmanFilter2D.cpp:74-76
+    }
+    if (f->homography) {
+        p.homography = 1;
+        for (int i = 0; i < 9; ++i) p.h[i] = f->h[i];
+    }
+    if (f->n_regions < 0 || f->n_regions > kMaxRegions) return fail(c, OATGPU_E_INVALID, "at most %d regions (got %d)", kMaxRegions, f->n_regions);
+    if (f->n_regions > 0 && !f->regions) return fail(c, OATGPU_E_INVALID, "null argument");
+    p.n_regions = f->n_regions;
+    int at = 0;
+    for (int r = 0; r < f->n_regions; ++r) {
+        const oatgpu_region &g = f->regions[r];
+        if (!memchr(g.name, 0, sizeof g.name))
+            return fail(c, OATGPU_E_INVALID, "region %d: a name takes at most %d bytes", r, (int)sizeof g.name - 1);
+        if (g.n_points < 0 || g.n_points > kMaxRegionPoints)
+            return fail(c, OATGPU_E_INVALID, "region %d (%s): at most %d points (got %d)", r, g.name, kMaxRegionPoints, g.n_points);
+        if (g.n_points > 0 && !g.xy) return fail(c, OATGPU_E_INVALID, "null argument");
+        p.region[r][0] = at; p.region[r][1] = g.n_points;
+        for (int i = 0; i < g.n_points; ++i, ++at)
+            for (int k = 0; k < 2; ++k) {
+                const double v = nearbyint(g.xy[2 * i + k]);     // (cv::Point)cv::Point2d: cvRound, ties to even
+                if (!(fabs(v) <= 32767.0)) return fail(c, OATGPU_E_INVALID, "region %d (%s): point %d is beyond +-32767", r, g.name, i);
+                p.verts[at][k] = (int)v;
+            }
+    }
+    return OATGPU_OK;
 }
 
-// the frame in `slot` has finished: its filtered set joins the call's
-void tracker_filters_keep(oatgpu_ctx *c, int slot)
+// What oatgpu_marker_filtered / oatgpu_tracker_filtered hand out is the list of the latest delivering call.  ONE convention: the
+// call starts the list over where it begins to deliver (chain_begin), every set it delivers joins the list (chain_keep).
+void chain_begin(PosfiltChain &ch) { ch.last_sets = 0; }
+void chain_keep(oatgpu_ctx *c, PosfiltChain &ch, const MarkerFiltered *set)
 {
-    static_assert(sizeof(oatgpu_filtered) == sizeof(MarkerFiltered), "k_tracker_filters writes oatgpu_filtered's layout");
-    TrackerFilters &tf = c->tf;
-    if (!tf.on) return;
+    static_assert(sizeof(oatgpu_filtered) == sizeof(MarkerFiltered), "k_marker_filters and k_tracker_filters write oatgpu_filtered's layout");
     const size_t n = (size_t)c->cfg.n_streams;
-    tf.last.resize((size_t)(tf.last_sets + 1) * n);
-    memcpy(tf.last.data() + (size_t)tf.last_sets * n, tf.out.host() + (size_t)slot * n, n * sizeof(oatgpu_filtered));
-    tf.last_sets++;
+    ch.last.resize((size_t)(ch.last_sets + 1) * n);
+    memcpy(ch.last.data() + (size_t)ch.last_sets * n, set, n * sizeof(oatgpu_filtered));
+    ch.last_sets++;
 }
 
-// Everything is checked before anything changes.
+// oatgpu_marker_filtered / oatgpu_tracker_filtered behind their null checks; none_yet: the text where nothing was delivered yet
+int chain_hand_out(oatgpu_ctx *c, const PosfiltChain &ch, const char *who, const char *none_yet, oatgpu_filtered *out, int max_sets)
+{
+    if (!ch.on) return fail(c, OATGPU_E_INVALID, "no filter chain is configured (oatgpu_set_%s_filters)", who);
+    if (ch.last_sets == 0) return fail(c, OATGPU_E_INVALID, "%s", none_yet);
+    if (max_sets < ch.last_sets) return fail(c, OATGPU_E_INVALID, "room for %d frame sets, the latest call delivered %d", max_sets, ch.last_sets);
+    memcpy(out, ch.last.data(), (size_t)ch.last_sets * c->cfg.n_streams * sizeof(oatgpu_filtered));
+    return ch.last_sets;
+}
+
 extern "C" int oatgpu_set_tracker_filters(oatgpu_ctx *c, const oatgpu_marker_filters *f)
 {
     if (!c) return OATGPU_E_INVALID;
-    if (c->ring_count || c->staged_count) return fail(c, OATGPU_E_INVALID, "set_tracker_filters while enqueued results are outstanding");
-    const bool on = f && (f->kalman || f->homography || f->n_regions > 0);
-    std::vector<MarkerFilterParams> hp(on ? 1 : 0);      // (8 KiB: not on the stack)
-    if (on) {
-        const int prc = chain_params(c, f, hp[0]);
-        if (prc) return prc;
-    }
-    int rc = open_sync(c);
-    if (rc) return rc;
-    if (!on) { c->tf = {}; return OATGPU_OK; }
-    const size_t n = (size_t)c->cfg.n_streams;
-    TrackerFilters made;                    // first use: built aside, moved in when everything worked
-    const bool first = !c->tf.params;
-    TrackerFilters &tf = first ? made : c->tf;
-    if (first) {
-        bool ok = tf.params.alloc(sizeof(MarkerFilterParams)) == hipSuccess;
-        ok = ok && tf.state.alloc(n * sizeof(KalmanState)) == hipSuccess;
-        ok = ok && tf.out.alloc(kSeqSlots * n * sizeof(MarkerFiltered), hipHostMallocMapped) == hipSuccess;
+    return configure_chain(c, c->tf, f, "tracker", nullptr, [](TrackerFilters &tf, size_t n) {
+        bool ok = tf.out.alloc(kSeqSlots * n * sizeof(MarkerFiltered), hipHostMallocMapped) == hipSuccess;
         for (auto &e : tf.ev) ok = ok && e.create(hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
-        if (!ok) return fail(c, OATGPU_E_NOMEM, "tracker filters: allocation failed: %s", hipGetErrorString(hipGetLastError()));
-        tf.last.reserve(n);
-    }
-    HIPCHK(c, hipMemcpy(tf.params, hp.data(), sizeof(MarkerFilterParams), hipMemcpyHostToDevice));
-    launch_kalman_reset(tf.state, (int)n, 0u, c->stream);          // every stream's filter from the reference's initial state
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (first) c->tf = std::move(made);
-    c->tf.on = true;
-    c->tf.last_sets = 0;
-    return OATGPU_OK;
+        return ok;
+    });
 }
 
 extern "C" int oatgpu_tracker_filtered(oatgpu_ctx *c, oatgpu_filtered *out, int32_t max_sets)
 {
     if (!c || !out) return fail(c, OATGPU_E_INVALID, "null argument");
-    if (!c->tf.on) return fail(c, OATGPU_E_INVALID, "no filter chain is configured (oatgpu_set_tracker_filters)");
-    if (c->tf.last_sets == 0) return fail(c, OATGPU_E_INVALID, "no tracker call has run since the filter chain was configured");
-    if (max_sets < c->tf.last_sets) return fail(c, OATGPU_E_INVALID, "room for %d frame sets, the latest call delivered %d", max_sets, c->tf.last_sets);
-    memcpy(out, c->tf.last.data(), (size_t)c->tf.last_sets * c->cfg.n_streams * sizeof(oatgpu_filtered));
-    return c->tf.last_sets;
+    return chain_hand_out(c, c->tf, "tracker", "no tracker call has run since the filter chain was configured", out, max_sets);
 }

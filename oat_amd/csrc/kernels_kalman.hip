@@ -13,7 +13,7 @@
 // equals n.  State and ticket are only touched with agent-scope atomics (coherent across XCDs
 // without cache write-backs); the ticket is bumped after the state stores have drained.
 #include "oatgpu_internal.h"
-#include "posfilt_inline.h"     // Filter / filter_step / static_matrices: shared with k_marker_filters
+#include "posfilt_inline.h"     // Filter / filter_step / static_matrices / centroid_of: shared with the chain kernels
 
 namespace oatgpu {
 
@@ -33,18 +33,9 @@ __global__ __launch_bounds__(64) void k_kalman(KalmanLaunch k, ResultRec *result
     f.missing = __hip_atomic_load(&ks->missing, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     f.aliased = __hip_atomic_load(&ks->aliased, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
-    // posidet's centroid, exactly as the host epilogue derives it from the integer sums
     ResultRec &r = results[s];
-    double x = 0.0, y = 0.0;
-    const bool valid = r.valid != 0;
-    if (valid) {
-        const double a00 = (double)r.a00, a10 = (double)r.a10, a01 = (double)r.a01;
-        const double db1_2 = a00 > 0 ? 0.5 : -0.5;
-        const double db1_6 = a00 > 0 ? 0.16666666666666666666666666666667 : -0.16666666666666666666666666666667;
-        const double m00 = a00 * db1_2;
-        x = (a10 * db1_6) / m00;
-        y = (a01 * db1_6) / m00;
-    }
+    double x, y;
+    const bool valid = centroid_of(r, x, y);       // posidet's centroid: the host epilogue's (posfilt_inline.h)
     filter_step(f, k, valid, x, y);
 
     const double *rep = f.aliased ? f.statePre : f.reported;

@@ -146,20 +146,8 @@ __global__ __launch_bounds__(64) void k_marker_combine(const ResultRec *__restri
                 __hip_atomic_store(dst + i, src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-    // posidet's centroid of marker m, exactly as the host epilogue (to_position) and k_kalman derive it from the integer sums;
-    // an invalid Position2D keeps its initial (0, 0)
-    auto centroid = [&](int m, double &x, double &y) -> bool {
-        const ResultRec &r = results[(size_t)m * n_streams + s];
-        x = 0.0; y = 0.0;
-        if (!r.valid) return false;
-        const double a00 = (double)r.a00, a10 = (double)r.a10, a01 = (double)r.a01;
-        const double db1_2 = a00 > 0 ? 0.5 : -0.5;
-        const double db1_6 = a00 > 0 ? 0.16666666666666666666666666666667 : -0.16666666666666666666666666666667;
-        const double m00 = a00 * db1_2;
-        x = (a10 * db1_6) / m00;
-        y = (a01 * db1_6) / m00;
-        return true;
-    };
+    // posidet's centroid of marker m: the host epilogue's and k_kalman's (centroid_of, posfilt_inline.h)
+    auto centroid = [&](int m, double &x, double &y) { return centroid_of(results[(size_t)m * n_streams + s], x, y); };
     const double mean_denom = 1.0 / (double)M;
     double px = 0.0, py = 0.0, hx = 0.0, hy = 0.0, ax = 0.0, ay = 0.0;
     int position_valid = 1, heading_valid = 1, n_valid = 0;
@@ -211,38 +199,6 @@ void launch_marker_combine(const ResultRec *results, int M, int anchor, int n_st
 {
     ResultRec *const none = nullptr;
     launch_marker_combine_frames(&results, M, anchor, n_streams, &out, &none, 1, st);
-}
-
-// ---- the filter chain behind the combined record: `posifilt kalman` -> `posifilt homography` -> `posifilt region` ----
-// One lane per camera stream, fp64.  The nf (1 or 2) frames of the step are taken IN ORDER in the lane's own loop: the Kalman
-// recurrence of a paired step is not split over the grid as the combiner's frames are.
-// The chain itself -- chain_step, posfilt_inline.h -- is shared with k_tracker_filters (kernels_trackfilt.hip); its input here is
-// the combined record: a partial-sum x, y under position_valid == 0 is no measurement.
-__global__ __launch_bounds__(64) void k_marker_filters(const MarkerFilterParams *__restrict__ p, KalmanState *state,
-                                                       const MarkerCombined *in0, const MarkerCombined *in1, MarkerFiltered *out0,
-                                                       MarkerFiltered *out1, int nf, int n_streams)
-{
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n_streams) return;
-    const bool kalman = p->kalman != 0;
-    const KalmanLaunch k = chain_kalman(p, state);
-    Filter f;
-    if (kalman) load_filter(f, state + s);
-#pragma unroll 1
-    for (int t = 0; t < nf; ++t) {
-        const MarkerCombined *in = (t ? in1 : in0) + s;
-        chain_step(p, k, f, in->position_valid, in->heading_valid, in->x, in->y, in->hx, in->hy, (t ? out1 : out0) + s);
-    }
-    if (kalman) store_filter(f, state + s);
-}
-
-void launch_marker_filters(const MarkerFilterParams *params, KalmanState *state, const MarkerCombined *const *in,
-                           MarkerFiltered *const *out, int n_streams, int nf, hipStream_t st)
-{
-    static_assert(sizeof(MarkerFiltered) == 72, "nine 64-bit words");
-    const int k = nf > 1 ? 1 : 0;
-    hipLaunchKernelGGL(k_marker_filters, dim3((n_streams + 63) / 64), dim3(64), 0, st, params, state, in[0], in[k], out[0], out[k],
-                       nf, n_streams);
 }
 
 }  // namespace oatgpu

@@ -99,16 +99,21 @@ struct MarkerPipeline {
     // a record set: M x n result records, n combined records, n filtered records (written only while a chain is configured)
     size_t set_bytes = 0;                      // = M n sizeof(ResultRec) + n (sizeof(MarkerCombined) + sizeof(MarkerFiltered))
 };
-// the filter chain behind the combined record (oatgpu_set_marker_filters): kalman -> homography -> region in ONE launch
-// behind k_marker_combine on the same HIP stream.  Made by the setter, dropped with the marker set.
-struct MarkerFilters {
+// A filter chain kalman -> homography -> region (chain_step, posfilt_inline.h) as the host keeps it: what the marker chain and the
+// trackers' chain have in common.  api_trackfilt.hip configures it (configure_chain), keeps what a call delivered (chain_begin,
+// chain_keep) and hands that out (chain_hand_out); the owners below add the buffers their kernels write.
+struct PosfiltChain {
     bool on = false;
     DevMem<MarkerFilterParams> params;         // device: the chain's parameters and the region table
     DevMem<KalmanState> state;                 // device: [n] the chain's own filter state, one per camera stream (not c->kal's)
+    std::vector<oatgpu_filtered> last;         // [sets][n] what the latest delivering call delivered (oatgpu_*_filtered)
+    int last_sets = 0;
+};
+// the filter chain behind the combined record (oatgpu_set_marker_filters): ONE launch behind k_marker_combine on the same HIP
+// stream.  Made by the setter, dropped with the marker set.
+struct MarkerFilters : PosfiltChain {
     DevMem<MarkerFiltered> out;                // device: [n] the synchronous step's filtered records
     HostMem<MarkerFiltered> out_host;          // ... their page-locked mirror
-    std::vector<oatgpu_filtered> last;         // [sets][n] what the latest marker-result call delivered (oatgpu_marker_filtered)
-    int last_sets = 0;
     bool append = false;                       // inside oatgpu_track_markers_sequence_dev: every collected set is kept
 };
 
@@ -155,14 +160,9 @@ struct BsubTracker : BatchedTrackerState {
 // homography -> region on the result records of a slot, one launch a frame behind the slot's back half.  One chain and one filter
 // state per camera stream for the context -- both trackers advance it; not c->kal's and not the marker chain's.  Everything below
 // is made by the setter, never inside a step.
-struct TrackerFilters {
-    bool on = false;
-    DevMem<MarkerFilterParams> params;         // device: the chain's parameters and the region table
-    DevMem<KalmanState> state;                 // device: [n] the chain's own filter state
+struct TrackerFilters : PosfiltChain {
     HostMem<MarkerFiltered> out;               // host-mapped: [kSeqSlots][n] the slot's filtered set, written by k_tracker_filters through dev()
     Event ev[kSeqSlots];                       // the slot's filter launch has finished: frame t's launch waits for frame t - 1's
-    std::vector<oatgpu_filtered> last;         // [sets][n] what the latest tracker call delivered (oatgpu_tracker_filtered)
-    int last_sets = 0;
 };
 
 struct oatgpu_ctx {
@@ -394,16 +394,18 @@ int back_half(oatgpu_ctx *c, BlobBuffers &bb, const u64 *thr, int s0, int n, int
               hipEvent_t ev_mid, int erode_k = -1, int dilate_k = -1, int mode = kBlobFull);
 int flush_pending(oatgpu_ctx *c);
 int repair_outstanding(oatgpu_ctx *c);
-void keep_filtered(oatgpu_ctx *c, const MarkerFiltered *f);
 int upload_frames(oatgpu_ctx *c, const uint8_t *const *frames_host, size_t frame_bytes);
 // api_markers.hip
 bool own_window_is_nonzero(const oatgpu_config &k);
 int launch_marker_work(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, const StepPlan &plan);
-int chain_params(oatgpu_ctx *c, const oatgpu_marker_filters *f, MarkerFilterParams &p);
 // api_trackfilt.hip
 int tracker_filters_launch(oatgpu_ctx *c, const ResultRec *rec_dev, int slot, int prev_slot, hipStream_t st);
-void tracker_filters_begin(oatgpu_ctx *c);
-void tracker_filters_keep(oatgpu_ctx *c, int slot);
+// ... and the chain as both of its owners use it (who: "marker" or "tracker", in the messages): the checked parameters for
+// configure_chain below, the list a delivering call keeps, and that list to the caller
+int chain_params(oatgpu_ctx *c, const oatgpu_marker_filters *f, MarkerFilterParams &p);
+void chain_begin(PosfiltChain &ch);
+void chain_keep(oatgpu_ctx *c, PosfiltChain &ch, const MarkerFiltered *set);
+int chain_hand_out(oatgpu_ctx *c, const PosfiltChain &ch, const char *who, const char *none_yet, oatgpu_filtered *out, int max_sets);
 // ... and what the two batched trackers share; `name` is "diff" or "bsub", `what` the call's name in a refusal
 int tracker_refusals(oatgpu_ctx *c, const BatchedTrackerState &bt, const char *name, const char *what);
 int check_batch_dev(oatgpu_ctx *c, const void *frames_dev, const oatgpu_position *out);
@@ -487,6 +489,46 @@ template <class Tracker, class Extra> static int set_batched_tracker(oatgpu_ctx 
     if (rc) return rc;
     if (!ok || !made.alloc(c)) return fail(c, OATGPU_E_NOMEM, "%s tracker: allocation failed: %s", name, hipGetErrorString(hipGetLastError()));
     cur = std::move(made);
+    return OATGPU_OK;
+}
+
+// The body of oatgpu_set_marker_filters and oatgpu_set_tracker_filters (c is not null).  Everything is checked before anything
+// changes: results outstanding; `refused`, the text of the owner's own precondition where it does not hold (nullptr: it holds);
+// the parameters (chain_params).  Nothing asked for: the chain is dropped.  First use: a chain is built aside -- extra(made, n):
+// the owner's own buffers, false for a failed allocation -- and the context takes it when everything worked.  Then the parameters
+// go up and every stream's filter starts from the reference's initial state.
+template <class Chain, class Extra>
+static int configure_chain(oatgpu_ctx *c, Chain &cur, const oatgpu_marker_filters *f, const char *who, const char *refused, Extra extra)
+{
+    if (c->ring_count || c->staged_count) return fail(c, OATGPU_E_INVALID, "set_%s_filters while enqueued results are outstanding", who);
+    if (refused) return fail(c, OATGPU_E_INVALID, "%s", refused);
+    const bool on = f && (f->kalman || f->homography || f->n_regions > 0);
+    std::vector<MarkerFilterParams> hp(on ? 1 : 0);      // (8 KiB: not on the stack)
+    if (on) {
+        const int prc = chain_params(c, f, hp[0]);
+        if (prc) return prc;
+    }
+    int rc = open_sync(c);
+    if (rc) return rc;
+    if (!on) { cur = {}; return OATGPU_OK; }
+    const size_t n = (size_t)c->cfg.n_streams;
+    Chain made;
+    const bool first = !cur.params;
+    Chain &ch = first ? made : cur;
+    if (first) {
+        bool ok = ch.params.alloc(sizeof(MarkerFilterParams)) == hipSuccess;
+        ok = ok && ch.state.alloc(n * sizeof(KalmanState)) == hipSuccess;
+        ok = ok && extra(ch, n);
+        if (!ok) return fail(c, OATGPU_E_NOMEM, "%s filters: allocation failed: %s", who, hipGetErrorString(hipGetLastError()));
+        ch.last.reserve(n);
+    }
+    HIPCHK(c, hipMemcpy(ch.params, hp.data(), sizeof(MarkerFilterParams), hipMemcpyHostToDevice));
+    launch_kalman_reset(ch.state, (int)n, 0u, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (first) cur = std::move(made);
+    cur.on = true;
+    cur.last_sets = 0;
     return OATGPU_OK;
 }
 

@@ -358,12 +358,12 @@ struct MarkerFilterParams {      // in DEVICE memory, read uniformly by every la
     int region[kMaxRegions][2];  // first vertex and number of vertices of each region, in configured order
     int verts[kMaxRegions * kMaxRegionPoints][2];    // (x, y) after (cv::Point) of the configured point
 };
-// The chain on the nf (1 or 2) frames of a step, IN ORDER in one lane per stream: frame i reads in[i] (k_marker_combine's
+// The chain (both launches: kernels_trackfilt.hip) on the nf (1 or 2) frames of a step, IN ORDER in one lane per stream: frame i reads in[i] (k_marker_combine's
 // records, written by an earlier launch on the same HIP stream), writes out[i] (may be host-mapped memory: 64-bit stores) and
 // advances state[s] (the ticket of KalmanState is not used: every launch of a context runs behind the one before)
 void launch_marker_filters(const MarkerFilterParams *params, KalmanState *state, const MarkerCombined *const *in,
                            MarkerFiltered *const *out, int n_streams, int nf, hipStream_t st);
-// The same chain behind the motion and the subtraction tracker (oatgpu_set_tracker_filters; kernels_trackfilt.hip): ONE frame a
+// The same chain behind the motion and the subtraction tracker (oatgpu_set_tracker_filters): ONE frame a
 // launch, one lane per stream.  in[n_streams]: the tracker's result records of the frame's slot, written by the blob kernels
 // earlier on the same HIP stream; out[n_streams] may be host-mapped memory (64-bit stores).  A detector has no heading.  The
 // caller orders the launches of consecutive frames (events): nothing waits on the device.

@@ -1,8 +1,8 @@
-// posfilt_inline.h -- the arithmetic of `posifilt kalman` and `posifilt homography`, ONE definition for every user:
-// k_kalman (kernels_kalman.hip, the foreground result), k_marker_filters (kernels_markers.hip, the combined record of a marker
-// set), k_tracker_filters (kernels_trackfilt.hip, the result record of the motion and the subtraction tracker) and the host
-// epilogue of api_track.hip (the homography of a plain track call).  The chain kalman -> homography -> region of the two filter
-// kernels is chain_step below.
+// posfilt_inline.h -- the arithmetic of `posifilt kalman` and `posifilt homography`, and posidet's centroid in front of them
+// (centroid_of), ONE definition for every user: k_kalman (kernels_kalman.hip, the foreground result), k_marker_filters and
+// k_tracker_filters (kernels_trackfilt.hip: the combined record of a marker set, the result record of the motion and the
+// subtraction tracker), k_marker_combine (kernels_markers.hip, the centroid) and the host epilogue of api_track.hip (to_position;
+// the homography of a plain track call).  The chain kalman -> homography -> region of the two filter kernels is chain_step below.
 //
 // Reference: oat::KalmanFilter2D::filter / initializeFilter / initializeStaticMatracies
 // (src/positionfilter/KalmanFilter2D.cpp:95-210) over cv::KalmanFilter(4, 2, 0, CV_64F) (OpenCV 3.1
@@ -27,6 +27,25 @@ __host__ __device__ inline void mul4(const double *a, int n, const double *b, in
             for (int q = 0; q < 4; ++q) s += a[i * 4 + q] * (b_transposed ? b[j * 4 + q] : b[q * m + j]);
             d[i * m + j] = c ? s + c[i * m + j] : s;
         }
+}
+
+// posidet's centroid of a result record from its exact integer sums: contourMoments' epilogue (imgproc/moments.cpp: m00 = a00 *
+// db1_2, m10 = a10 * db1_6, m01 = a01 * db1_6) and siftContours' centroid m10 / m00, m01 / m00 (DetectorFunc.cpp:54-62).  An
+// invalid record gives false and the (0, 0) an invalid Position2D keeps.  ONE definition for the position the host hands out
+// (to_position, api_track.hip; area: where m00 goes, the position's area) and for what k_kalman, k_marker_combine and
+// k_tracker_filters take as their measurement: a position and its filtered record agree to the bit.
+__host__ __device__ inline bool centroid_of(const ResultRec &r, double &x, double &y, double *area = nullptr)
+{
+    x = 0.0; y = 0.0;
+    if (!r.valid) return false;
+    const double a00 = (double)r.a00, a10 = (double)r.a10, a01 = (double)r.a01;
+    const double db1_2 = a00 > 0 ? 0.5 : -0.5;
+    const double db1_6 = a00 > 0 ? 0.16666666666666666666666666666667 : -0.16666666666666666666666666666667;
+    const double m00 = a00 * db1_2;
+    x = (a10 * db1_6) / m00;
+    y = (a01 * db1_6) / m00;
+    if (area) *area = m00;
+    return true;
 }
 
 struct Filter {     // registers copy of one stream's KalmanState

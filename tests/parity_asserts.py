@@ -1,6 +1,8 @@
-"""The three assertions every parity test shares (TEST INFRASTRUCTURE): a Position2D against an oracle detection, a MOG2
-model against the oracle's, bit for bit.  They lived in test_gpu_parity.py; tests/api_sequences.py needs them without a
-GPU, so they have a module of their own.  What they assert is unchanged."""
+"""The assertions the parity tests share (TEST INFRASTRUCTURE): a Position2D against an oracle detection, a MOG2
+model against the oracle's, bit for bit, and two doubles of a filtered record.  They lived in test_gpu_parity.py;
+tests/api_sequences.py needs them without a GPU, so they have a module of their own.  What they assert is unchanged."""
+import math
+
 import numpy as np
 
 CENTROID_TOL = 1e-4     # px, from BASELINE.json north_star
@@ -14,6 +16,11 @@ def _same_detection(got, want, tag=""):
         assert got.first_pixel == want["first_pixel"], (tag, got, want)
         assert abs(got.x - want["x"]) <= CENTROID_TOL and abs(got.y - want["y"]) <= CENTROID_TOL, (tag, got, want)
         assert got.x == want["x"] and got.y == want["y"], (tag, got, want)
+
+
+def _same_double(a, b):
+    """Equal as doubles, a NaN matched by a NaN (the filter chain's records: test_marker_filters_gpu, test_tracker_filters_gpu)."""
+    return math.isnan(a) if math.isnan(b) else a == b
 
 
 def _eq(a, b):

@@ -1,5 +1,5 @@
 """GPU tests of the filter chain behind a marker set's combined record (oatgpu_set_marker_filters, oatgpu_marker_filtered;
-HotPath.set_marker_filters / .marker_filtered; k_marker_filters in kernels_markers.hip): `posifilt kalman` -> `posifilt
+HotPath.set_marker_filters / .marker_filtered; k_marker_filters in kernels_trackfilt.hip): `posifilt kalman` -> `posifilt
 homography` -> `posifilt region` on the record `posicom mean` publishes, on the synchronous marker step and on every
 pipelined form.
 
@@ -24,6 +24,7 @@ import marker_filters_ref as R
 import markers_ref as MR
 import oracle_lib as O
 import posfilt_cases as P
+from parity_asserts import _same_double
 
 pytestmark = pytest.mark.gpu
 
@@ -47,11 +48,8 @@ def _hp(A, shape, ring=4, chain=None):
     return hp
 
 
-def _same_double(a, b):
-    return math.isnan(a) if math.isnan(b) else a == b
-
-
 def _same_filtered(got, want, tag):
+    """(Not test_tracker_filters_gpu's: every member is compared with the expected record, the heading included.)"""
     assert (got.position_valid, got.velocity_valid, got.heading_valid, got.region_valid, got.region) == \
         (want["position_valid"], want["velocity_valid"], want["heading_valid"], want["region_valid"], want["region"]), (tag, got, want)
     for k in DOUBLES:
@@ -251,11 +249,18 @@ def test_chain_leaves_everything_else_bit_identical(A, form):
 
 # ------------------------------------------------------------------------------------------- 5: life cycle ---
 
-def _refused(fn, word):
+def _refused(fn, text):
+    """text: the complete message, as the source before the setters and getters had one body printed it"""
     from oat_amd import ffi
     with pytest.raises(ffi.OatGpuError) as e:
         fn()
-    assert e.value.code == -1 and word in str(e.value), str(e.value)
+    assert e.value.code == -1 and str(e.value) == f"oatgpu error -1: {text}", str(e.value)
+
+
+NO_CHAIN = "no filter chain is configured (oatgpu_set_marker_filters)"
+NO_RESULT = "no marker result has been delivered since the filter chain was configured"
+OUTSTANDING = "set_marker_filters while enqueued results are outstanding"
+BAD_KALMAN = "kalman: dt must be > 0, timeout / sigma-accel / sigma-noise >= 0"
 
 
 def test_life_cycle(A):
@@ -269,14 +274,14 @@ def test_life_cycle(A):
     assert want[cut:] != _want(shape, name)[cut:]              # the restart shows
     hp = A.HotPath(rows, cols, n_streams=n, ring_depth=4, **K.OWN)
     try:
-        _refused(lambda: hp.set_marker_filters(**chain), "not configured")            # no markers yet
+        _refused(lambda: hp.set_marker_filters(**chain), "marker sets are not configured (oatgpu_set_markers)")            # no markers yet
         hp.set_markers(K.MARKERS[:M], heading_anchor=0)
-        _refused(hp.marker_filtered, "no filter chain")                               # the chain is off
+        _refused(hp.marker_filtered, NO_CHAIN)                               # the chain is off
         hp.track_markers(list(fr[0]))                                                 # (a chain-off step: no record is kept)
-        _refused(hp.marker_filtered, "no filter chain")
+        _refused(hp.marker_filtered, NO_CHAIN)
         hp.close()
         hp = _hp(A, shape, 4, chain)
-        _refused(hp.marker_filtered, "no marker result")                              # before any result
+        _refused(hp.marker_filtered, NO_RESULT)                              # before any result
         t = 0
 
         def sync_step():
@@ -293,12 +298,14 @@ def test_life_cycle(A):
             sync_step()
         # refused with nothing changed: limits, names, parameters -- the filter goes on where it was
         sq = [(0, 0), (10, 0), (10, 10), (0, 10)]
-        _refused(lambda: hp.set_marker_filters(regions=[(f"r{i}", sq) for i in range(17)]), "at most 16 regions")
-        _refused(lambda: hp.set_marker_filters(regions=[("a", [(i, i * i % 7) for i in range(65)])]), "at most 64 points")
-        _refused(lambda: hp.set_marker_filters(regions=[("tenletters", sq)]), "at most 9 bytes")
-        _refused(lambda: hp.set_marker_filters(regions=[("a", [(0, 0), (40000, 0), (5, 5)])]), "32767")
-        _refused(lambda: hp.set_marker_filters(kalman=dict(dt=0.0)), "dt must be > 0")
-        _refused(lambda: hp.set_marker_filters(kalman=dict(sigma_noise=-1.0)), "kalman")
+        _refused(lambda: hp.set_marker_filters(regions=[(f"r{i}", sq) for i in range(17)]), "at most 16 regions (got 17)")
+        _refused(lambda: hp.set_marker_filters(regions=[("a", [(i, i * i % 7) for i in range(65)])]),
+                 "region 0 (a): at most 64 points (got 65)")
+        _refused(lambda: hp.set_marker_filters(regions=[("tenletters", sq)]), "region 0: a name takes at most 9 bytes")
+        _refused(lambda: hp.set_marker_filters(regions=[("a", [(0, 0), (40000, 0), (5, 5)])]),
+                 "region 0 (a): point 1 is beyond +-32767")
+        _refused(lambda: hp.set_marker_filters(kalman=dict(dt=0.0)), BAD_KALMAN)
+        _refused(lambda: hp.set_marker_filters(kalman=dict(sigma_noise=-1.0)), BAD_KALMAN)
         for _ in range(2):
             sync_step()
         hp.set_marker_filters(regions=[("ninebytes", sq)] + [(f"r{i}", sq) for i in range(15)])     # the limits themselves pass
@@ -313,8 +320,8 @@ def test_life_cycle(A):
         while t < 7:                                          # pipelined, one set in flight
             hp.enqueue(list(fr[t]))
             if t == 3:                                        # refused with results outstanding: state and results unaffected
-                _refused(lambda: hp.set_marker_filters(**chain), "outstanding")
-                _refused(lambda: hp.set_marker_filters(), "outstanding")
+                _refused(lambda: hp.set_marker_filters(**chain), OUTSTANDING)
+                _refused(lambda: hp.set_marker_filters(), OUTSTANDING)
             got = hp.collect_markers()
             _same_front(got, shape, t, "pipe")
             sets = hp.marker_filtered()
@@ -348,7 +355,7 @@ def test_life_cycle(A):
         t = cut
         # ... and the chain after the pipeline: set_marker_filters again restarts the filter (expected: a fresh O.Kalman)
         hp.set_marker_filters(**chain)
-        _refused(hp.marker_filtered, "no marker result")
+        _refused(hp.marker_filtered, NO_RESULT)
         bufs = _device(fr[t:])
         hp.set_fusion(2)
         hp.track_markers_sequence_dev([b.data_ptr() for b in bufs])
@@ -359,16 +366,17 @@ def test_life_cycle(A):
                 _same_filtered(sets[i][s], want[t + i][s], ("restarted", t + i, s))
         # switching the chain off; set_markers drops it
         hp.set_marker_filters()
-        _refused(hp.marker_filtered, "no filter chain")
+        _refused(hp.marker_filtered, NO_CHAIN)
         hp.set_marker_filters(**chain)
         hp.marker_pipeline(False)
         hp.set_markers(K.MARKERS[:M], heading_anchor=0)
-        _refused(hp.marker_filtered, "no filter chain")
+        _refused(hp.marker_filtered, NO_CHAIN)
         hp.track_markers(list(fr[0]))
-        _refused(hp.marker_filtered, "no filter chain")
+        _refused(hp.marker_filtered, NO_CHAIN)
         # the foreground filters stay refused on marker contexts
         hp.set_kalman(True, dt=0.02, timeout=1.0)
-        _refused(lambda: hp.track_markers(list(fr[0])), "oatgpu_set_kalman")
+        _refused(lambda: hp.track_markers(list(fr[0])),
+                 "track_markers with the position filter on (oatgpu_set_kalman) is not supported")
         hp.set_kalman(False)
     finally:
         hp.close()

@@ -8,7 +8,6 @@ marker_filters_ref.chain with one oracle_lib.Kalman per stream.  Every filtered 
 flags and region name equal, x / y / vx / vy equal as doubles (==), hx = hy = 0; the sign of a zero is not pinned.  The detections
 in front of the chain are held to the oracle too.  Every frame is under 0.01 MP."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
@@ -18,7 +17,7 @@ import debayer_ref as DR
 import diff_cases as DC
 import tracker_filters_cases as K
 import undistort_ref as UR
-from parity_asserts import _same_detection
+from parity_asserts import _same_detection, _same_double
 
 pytestmark = pytest.mark.gpu
 
@@ -45,11 +44,9 @@ def _tracker(A, kind, rows, cols, ch, n, **kw):
     return A.SubtractionTracker(rows, cols, **K.bsub_case(rows, cols, ch, n).tracker_args(), **kw)
 
 
-def _same_double(a, b):
-    return math.isnan(a) if math.isnan(b) else a == b
-
-
 def _same_filtered(got, want, tag):
+    """(Not test_marker_filters_gpu's: a detector publishes no heading, so heading_valid, hx and hy are held to False, 0, 0
+    whatever the expected record says, where the marker chain's are compared with it.)"""
     assert (got.position_valid, got.velocity_valid, got.heading_valid, got.region_valid, got.region) == \
         (want["position_valid"], want["velocity_valid"], False, want["region_valid"], want["region"]), (tag, got, want)
     for k in ("x", "y", "vx", "vy"):
@@ -262,19 +259,20 @@ def test_refusals_leave_the_context_and_the_chain_as_they_were(A):
     bufs = [_dev(f) for f in fr]
     out, filt = (ffi.Position * n)(), (ffi.Filtered * (4 * n))()
 
-    def refused(rc, *needles):
+    def refused(rc, text, whole=True):
+        """whole: the complete message, as the source before the setters and getters had one body printed it"""
         assert rc == E_INVALID
         msg = lib.oatgpu_last_error(ctx).decode()
-        assert all(k in msg for k in needles), msg
+        assert msg == text if whole else text in msg, msg
 
     def chain(**kw):
         return C.byref(A.components._filter_chain(kw.get("kalman"), kw.get("homography"), kw.get("regions"))[0])
 
     sq = [(0, 0), (10, 0), (10, 10), (0, 10)]
     try:
-        refused(lib.oatgpu_tracker_filtered(ctx, filt, 4), "no filter chain is configured")
+        refused(lib.oatgpu_tracker_filtered(ctx, filt, 4), "no filter chain is configured (oatgpu_set_tracker_filters)")
         M.set_filters(hp, **cfg)
-        refused(lib.oatgpu_tracker_filtered(ctx, filt, 4), "no tracker call has run")
+        refused(lib.oatgpu_tracker_filtered(ctx, filt, 4), "no tracker call has run since the filter chain was configured")
         for t in range(3):
             _same_front(M.track_dev(hp, bufs[t].data_ptr()), det[t], t)
             _same_set(M.filtered(hp)[0], want[t], t)
@@ -282,30 +280,30 @@ def test_refusals_leave_the_context_and_the_chain_as_they_were(A):
         for bad in (dict(kalman=dict(dt=0.0)), dict(kalman=dict(dt=0.02, timeout=-1.0)), dict(kalman=dict(sigma_accel=-1.0)),
                     dict(kalman=dict(sigma_noise=float("nan")))):
             f, _, keep = A.components._filter_chain(bad["kalman"], None, None)
-            refused(lib.oatgpu_set_tracker_filters(ctx, C.byref(f)), "kalman", "dt must be > 0")
-        for regions, needle in (([(f"r{i}", sq) for i in range(17)], "at most 16 regions"),
-                                ([("a", [(i, i * i % 7) for i in range(65)])], "at most 64 points"),
-                                ([("tenletters", sq)], "at most 9 bytes"),
-                                ([("a", [(0, 0), (40000, 0), (10, 10)])], "beyond +-32767")):
+            refused(lib.oatgpu_set_tracker_filters(ctx, C.byref(f)), "kalman: dt must be > 0, timeout / sigma-accel / sigma-noise >= 0")
+        for regions, text in (([(f"r{i}", sq) for i in range(17)], "at most 16 regions (got 17)"),
+                              ([("a", [(i, i * i % 7) for i in range(65)])], "region 0 (a): at most 64 points (got 65)"),
+                              ([("tenletters", sq)], "region 0: a name takes at most 9 bytes"),
+                              ([("a", [(0, 0), (40000, 0), (10, 10)])], "region 0 (a): point 1 is beyond +-32767")):
             f, _, keep = A.components._filter_chain(None, None, regions)
-            refused(lib.oatgpu_set_tracker_filters(ctx, C.byref(f)), needle)
+            refused(lib.oatgpu_set_tracker_filters(ctx, C.byref(f)), text)
         f, _, keep = A.components._filter_chain(cfg["kalman"], None, None)
         hp.enqueue_dev(bufs[0].data_ptr(), keepalive=bufs[0])
-        refused(lib.oatgpu_set_tracker_filters(ctx, C.byref(f)), "outstanding")
-        refused(lib.oatgpu_set_tracker_filters(ctx, None), "outstanding")
+        refused(lib.oatgpu_set_tracker_filters(ctx, C.byref(f)), "set_tracker_filters while enqueued results are outstanding")
+        refused(lib.oatgpu_set_tracker_filters(ctx, None), "set_tracker_filters while enqueued results are outstanding")
         hp.collect()
         hp.stage(0, fr[0][0])
-        refused(lib.oatgpu_set_tracker_filters(ctx, C.byref(f)), "outstanding")
+        refused(lib.oatgpu_set_tracker_filters(ctx, C.byref(f)), "set_tracker_filters while enqueued results are outstanding")
         hp.stage_abort()
         # oatgpu_set_kalman / oatgpu_set_homography keep their meaning: the tracker calls stay refused while they are on
         arr = (C.c_void_p * 1)(bufs[3].data_ptr())
         hp.set_kalman(True)
-        refused(lib.oatgpu_diff_batch_dev(ctx, C.c_void_p(bufs[3].data_ptr()), out), "oatgpu_set_kalman")
-        refused(lib.oatgpu_diff_sequence_dev(ctx, arr, 1, out), "oatgpu_set_kalman")
-        refused(lib.oatgpu_bsub_track_batch_dev(ctx, C.c_void_p(bufs[3].data_ptr()), 0.0, out), "oatgpu_set_kalman")
+        refused(lib.oatgpu_diff_batch_dev(ctx, C.c_void_p(bufs[3].data_ptr()), out), "oatgpu_set_kalman", whole=False)
+        refused(lib.oatgpu_diff_sequence_dev(ctx, arr, 1, out), "oatgpu_set_kalman", whole=False)
+        refused(lib.oatgpu_bsub_track_batch_dev(ctx, C.c_void_p(bufs[3].data_ptr()), 0.0, out), "oatgpu_set_kalman", whole=False)
         hp.set_kalman(False)
         hp.set_homography(K.HOMOGRAPHIES["h_affine"])
-        refused(lib.oatgpu_diff_batch_dev(ctx, C.c_void_p(bufs[3].data_ptr()), out), "oatgpu_set_homography")
+        refused(lib.oatgpu_diff_batch_dev(ctx, C.c_void_p(bufs[3].data_ptr()), out), "oatgpu_set_homography", whole=False)
         hp.set_homography(None)
         # the latest sets are still frame 2's; too little room is refused, nothing is consumed
         assert lib.oatgpu_tracker_filtered(ctx, filt, 1) == 1
@@ -313,13 +311,13 @@ def test_refusals_leave_the_context_and_the_chain_as_they_were(A):
         _same_set(M.filtered(hp)[0], want[2], "kept")
         seq = M.track_sequence_dev(hp, [b.data_ptr() for b in bufs[3:7]])
         _same_front(seq[3], det[6], 6)
-        refused(lib.oatgpu_tracker_filtered(ctx, filt, 3), "room for 3 frame sets", "delivered 4")
+        refused(lib.oatgpu_tracker_filtered(ctx, filt, 3), "room for 3 frame sets, the latest call delivered 4")
         sets = M.filtered(hp)
         for i in range(4):
             _same_set(sets[i], want[3 + i], ("through the refusals", 3 + i))  # the chain went through every refusal untouched
         # switched off: freed, and the getter says so; the tracker goes on
         M.set_filters(hp)
-        refused(lib.oatgpu_tracker_filtered(ctx, filt, 4), "no filter chain is configured")
+        refused(lib.oatgpu_tracker_filtered(ctx, filt, 4), "no filter chain is configured (oatgpu_set_tracker_filters)")
         assert lib.oatgpu_set_tracker_filters(ctx, None) == 0
         _same_front(M.track_dev(hp, bufs[7].data_ptr()), det[7], 7)
     finally:
