@@ -9,17 +9,16 @@ HIPFLAGS ?= --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fPIC -Wall 
 CSRC     = oat_amd/csrc
 LIB      = oat_amd/lib/liboatgpu.so
 # the units of the library, listed once: the kernels, and the C ABI above them by feature (oatgpu_ctx.h is their shared header)
-KERNELS  = kernels_mog kernels_blob kernels_kalman kernels_undistort kernels_debayer kernels_markers kernels_diff kernels_bsubtrack kernels_trackfilt
+KERNELS  = kernels_mog kernels_stages kernels_measure kernels_blob kernels_kalman kernels_undistort kernels_debayer kernels_markers kernels_diff kernels_bsubtrack kernels_trackfilt
 API      = api_context api_stages api_track api_markers api_diff api_bsubtrack api_trackfilt api_model api_measure
 UNITS    = $(KERNELS) $(API)
 OBJS     = $(UNITS:%=$(CSRC)/%.o)
 
 all: $(LIB) oracle
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/oatgpu_internal.h $(CSRC)/hip_owned.h $(CSRC)/hsv_inline.h $(CSRC)/debayer_inline.h $(CSRC)/undistort_inline.h $(CSRC)/pixel_source_inline.h $(CSRC)/maskwords_inline.h $(CSRC)/posfilt_inline.h include/oatgpu.h
+# every unit depends on every header of the directory: a new header is a dependency without being listed
+$(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/oatgpu.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(API:%=$(CSRC)/%.o): $(CSRC)/oatgpu_ctx.h
 
 $(LIB): $(OBJS)
 	@mkdir -p oat_amd/lib

@@ -1,19 +1,22 @@
-// hsv_inline.h -- BGR -> HSV of ONE pixel and the inRange test, shared by the per-pixel MOG2 kernel (kernels_mog.hip) and the
-// marker-set kernel (kernels_markers.hip): both must produce the same HSV triple for the same pixel, bit for bit.
+// hsv_inline.h -- BGR -> HSV of ONE pixel and the inRange test, the one implementation of every kernel that converts: the
+// per-pixel MOG2 kernel (kernels_mog.hip), the marker sets (kernels_markers.hip), the subtraction tracker (kernels_bsubtrack.hip)
+// and the single stage k_bgr2hsv (kernels_stages.hip) produce the same HSV triple for the same pixel, bit for bit.
 #pragma once
 
 #include "oatgpu_internal.h"
 
 namespace oatgpu {
 
-// The same table entries computed on the spot (hsv_tables_init's exact fp32 quotients): K1 needs two entries per
-// FOREGROUND pixel, and building both 256-entry tables per 256-pixel workgroup costs every pixel two quotients
-// plus LDS traffic and a barrier -- the inline form costs foreground pixels the same and background pixels nothing.
+// RGB2HSV_b's table entries sdiv[i] = cvRound((255<<12)/i), hdiv[i] = cvRound((180<<12)/(6 i)), computed on the spot: a pixel
+// needs two of them, K1 for FOREGROUND pixels only, and 256-entry tables in LDS would cost every workgroup 512 quotients and a
+// barrier.  Neither quotient ever lands on .5 (255<<12 = 2^12*255, 180<<12/6 = 2^13*15), so round-half-even == floor(q + 1/2)
+// == floor((2n + i) / (2i)).  The quotient is taken in fp32: numerator < 2^22 and denominator <= 510 are exact floats, and the
+// exact quotient is at least 1/(2i) away from the next integer, so floor() of an fp32 quotient good to a few ulp is exact.
 // (r05) the quotient as numerator * v_rcp_f32(denominator), 2 vector instructions instead of the 11 of an IEEE division:
 // v_rcp_f32 is good to 1 ulp and the product rounds once more, so the result is within 1.5 * 2^-23 of the exact quotient
 // q <= 2^20 / i + 1/2, i.e. off by < 0.19 / i, while q lies at least 1 / (2i) away from the next integer (above): floor()
 // still lands on the same integer.  tests/test_abi_exports.py checks every entry with the reciprocal off by one ulp either
-// way, test_bgr2hsv_exhaustive_256cubed runs all 2^24 colours through tables built with these very functions.
+// way, test_bgr2hsv_exhaustive_256cubed runs all 2^24 colours through k_bgr2hsv, that is through these very functions.
 __device__ __forceinline__ int hsv_sdiv(int i) { return i ? (int)floorf((float)(2 * (255 << 12) + i) * __builtin_amdgcn_rcpf((float)(2 * i))) : 0; }
 __device__ __forceinline__ int hsv_hdiv(int i) { return i ? (int)floorf((float)(2 * ((180 << 12) / 6) + i) * __builtin_amdgcn_rcpf((float)(2 * i))) : 0; }
 __device__ __forceinline__ void bgr2hsv_inline(int b, int g, int r, int &h, int &s, int &v)

@@ -2,7 +2,7 @@
 // for BGR frames, `framefilt bsub` -> `posidet thresh` for GREY ones) for every camera stream of a context in one
 // launch (grid y = stream).
 //
-// Per pixel and channel, in k_bsub's order (BackgroundSubtractor.cpp:79-100): x = the frame byte, 0 where the stream's ROI bit is
+// Per pixel and channel bsub_elem, k_bsub's rule (BackgroundSubtractor.cpp:79-100): x = the frame byte, 0 where the stream's ROI bit is
 // 0 (framefilt mask in front of bsub); on a stream's first frame acc = (float)x, bg = x; with LEARN acc = x * a + acc * b in
 // separate roundings (cv::accumulateWeighted, the unit is built with -ffp-contract=off) and bg = saturate(round-half-even(acc));
 // d = x > bg ? x - bg : 0.  Then bit = inRange(hsv(d_b, d_g, d_r)) (hsv_inline.h) or lo <= d <= hi (GREY).
@@ -25,6 +25,7 @@
 #include "oatgpu_internal.h"
 #include "hsv_inline.h"
 #include "maskwords_inline.h"
+#include "pixel_rules_inline.h"
 #include "pixel_source_inline.h"
 
 namespace oatgpu {
@@ -44,17 +45,6 @@ struct BsubArgs {
     float a, b;                          // accW_: a = (float)alpha, b = 1 - a
     int first_stream;
 };
-
-// one channel of one pixel: the state moves on, the saturated difference comes back
-template <bool LEARN> __device__ __forceinline__ int bsub_elem(int x, bool first, int &bg, float &acc, float a, float b)
-{
-    if (first) { acc = (float)x; bg = x; }
-    if (LEARN) {
-        acc = x * a + acc * b;
-        bg = min(255, max(0, __float2int_rn(acc)));
-    }
-    return x > bg ? x - bg : 0;
-}
 
 template <int CH> __device__ __forceinline__ bool window(const int (&d)[CH], const RangeParams &rp)
 {
@@ -101,16 +91,14 @@ __device__ __forceinline__ void bsubtrack_wide(const Geom &g, const BsubArgs &a,
 {
     const int s = a.first_stream + (int)blockIdx.y;
     const bool first = (a.first >> blockIdx.y) & 1ull;               // uniform
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);            // 256 pixels = words 4 * wave .. 4 * wave + 3; Palloc % 1024 == 0
-    const int p0 = wave * 256 + lane * 4;
-    const int y = p0 / g.Wp, x = p0 - y * g.Wp;
+    const QuadLane ql(g);
+    const int y = ql.y, x = ql.x;
     const size_t npx = (size_t)g.H * g.W, NW = (size_t)(g.Palloc >> 6);
     unsigned n1 = 0, n2 = 0;
-    if (p0 < g.P && x < g.W) {                                       // W % 4 == 0: the lane's 4 pixels are inside together
+    if (ql.inside(g)) {
         const size_t e0 = ((size_t)s * npx + (size_t)y * g.W + x) * CH;          // the lane's first element: a multiple of 4
         unsigned keep = 15u;
-        if (ROI) keep = (((const uint8_t *)(a.roi + (size_t)s * NW))[p0 >> 3] >> (p0 & 4)) & 15u;
+        if (ROI) keep = ql.nibble(a.roi + (size_t)s * NW);
         unsigned f[CH], bgw[CH];
         float acc[4 * CH] = {};
         unsigned *bp = (unsigned *)(a.bg + e0);
@@ -147,8 +135,8 @@ __device__ __forceinline__ void bsubtrack_wide(const Geom &g, const BsubArgs &a,
             }
         }
     }
-    store_words(n1, lane, a.bits + (size_t)s * NW + (size_t)wave * 4);
-    if (PAIR) store_words(n2, lane, a.bits2 + (size_t)s * NW + (size_t)wave * 4);
+    store_words(n1, ql.lane, a.bits + (size_t)s * NW + (size_t)ql.wave * 4);
+    if (PAIR) store_words(n2, ql.lane, a.bits2 + (size_t)s * NW + (size_t)ql.wave * 4);
 }
 
 template <int CH, bool ROI, bool PAIR, bool LEARN, class SRC>
@@ -156,15 +144,13 @@ __device__ __forceinline__ void bsubtrack_narrow(const Geom &g, const BsubArgs &
 {
     const int s = a.first_stream + (int)blockIdx.y;
     const bool first = (a.first >> blockIdx.y) & 1ull;               // uniform
-    const int lane = threadIdx.x & 63;
-    const int word = blockIdx.x * 4 + (threadIdx.x >> 6);            // Palloc % 256 == 0: every word of the grid exists
-    const int p = word * 64 + lane;
-    const int y = p / g.Wp, x = p - y * g.Wp;
+    const WordLane l(g);                                             // Palloc % 256 == 0: every word of the grid exists
+    const int y = l.y, x = l.x;
     const size_t npx = (size_t)g.H * g.W, NW = (size_t)(g.Palloc >> 6);
     bool on1 = false, on2 = false;
-    if (p < g.P && x < g.W) {
+    if (l.inside(g)) {
         const size_t e0 = ((size_t)s * npx + (size_t)y * g.W + x) * CH;
-        const bool keep = !ROI || ((a.roi[(size_t)s * NW + word] >> lane) & 1ull);
+        const bool keep = !ROI || ((a.roi[(size_t)s * NW + l.word] >> l.lane) & 1ull);
         int bg[CH], d[CH], v[CH];
         float acc[CH];
 #pragma unroll
@@ -188,12 +174,8 @@ __device__ __forceinline__ void bsubtrack_narrow(const Geom &g, const BsubArgs &
             for (int c = 0; c < CH; ++c) { a.bg[e0 + c] = (uint8_t)bg[c]; a.acc[e0 + c] = acc[c]; }
         }
     }
-    const u64 w1 = __ballot(on1);
-    if (lane == 0) a.bits[(size_t)s * NW + word] = w1;
-    if (PAIR) {
-        const u64 w2 = __ballot(on2);
-        if (lane == 0) a.bits2[(size_t)s * NW + word] = w2;
-    }
+    store_word(on1, l.lane, a.bits, (size_t)s * NW + l.word);
+    if (PAIR) store_word(on2, l.lane, a.bits2, (size_t)s * NW + l.word);
 }
 
 // One kernel name a source and lane mapping; the raw and the remap kernels take what their source is built from

@@ -21,23 +21,18 @@
 // falls on that pixel.
 #include "oatgpu_internal.h"
 #include "maskwords_inline.h"
+#include "pixel_rules_inline.h"
 #include "pixel_source_inline.h"
 
 namespace oatgpu {
 
 namespace {
 
-__device__ __forceinline__ int grey_bgr(unsigned b, unsigned g, unsigned r)
-{
-    return (int)((1868u * b + 9617u * g + 4899u * r + 8192u) >> 14);
-}
-__device__ __forceinline__ bool differs(int a, int b, int thr) { return (a > b ? a - b : b - a) > thr; }
-
 // col GREY of one pixel's values
 template <class T, int CH> __device__ __forceinline__ int grey_of(const T (&v)[CH])
 {
     if constexpr (CH == 1) return (int)v[0];
-    else return grey_bgr(v[0], v[1], v[2]);
+    else return (int)grey_bgr(v[0], v[1], v[2]);
 }
 // the greys of a source's 4 pixels from (y, x) on as one little-endian dword, and the grey of its pixel (y, x)
 template <class SRC> __device__ __forceinline__ unsigned grey4(const SRC &src, const uint8_t *frames, const Geom &g, int s, int y, int x)
@@ -66,29 +61,27 @@ template <bool ROI, bool PAIR, class SRC> __device__ __forceinline__ void diff_w
 {
     const int s = a.first_stream + (int)blockIdx.y;
     const bool have = PAIR || ((a.have >> blockIdx.y) & 1ull);      // uniform
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);            // 256 pixels = words 4 * wave .. 4 * wave + 3; Palloc % 1024 == 0
-    const int p0 = wave * 256 + lane * 4;
-    const int y = p0 / g.Wp, x = p0 - y * g.Wp;
+    const QuadLane ql(g);
+    const int y = ql.y, x = ql.x;
     const size_t npx = (size_t)g.H * g.W, NW = (size_t)(g.Palloc >> 6);
     unsigned n1 = 0, n2 = 0;
-    if (p0 < g.P && x < g.W) {                                       // W % 4 == 0: the lane's 4 pixels are inside together
+    if (ql.inside(g)) {
         const size_t i = (size_t)y * g.W + x;
         unsigned *lp = (unsigned *)(a.last + (size_t)s * npx + i);
         unsigned keep = 0xffffffffu;
         if (ROI) {
-            const unsigned r = (((const uint8_t *)(a.roi + (size_t)s * NW))[p0 >> 3] >> (p0 & 4)) & 15u;
+            const unsigned r = ql.nibble(a.roi + (size_t)s * NW);
             keep = (r & 1u ? 0xffu : 0u) | (r & 2u ? 0xff00u : 0u) | (r & 4u ? 0xff0000u : 0u) | (r & 8u ? 0xff000000u : 0u);
         }
         src.begin4(g, s, y, x);
         const unsigned g1 = grey4(src, a.frames, g, s, y, x) & keep;
-        if (have) {
+        if (have) {                                                  // (uniform: one branch, not one a pixel)
             const unsigned l = *lp;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) n1 |= differs((g1 >> (8 * k)) & 255u, (l >> (8 * k)) & 255u, a.thr) ? 1u << k : 0u;
+            for (int k = 0; k < 4; ++k) n1 |= motion_bit((g1 >> (8 * k)) & 255u, (l >> (8 * k)) & 255u, true, a.thr) ? 1u << k : 0u;
         } else {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) n1 |= ((g1 >> (8 * k)) & 255u) ? 1u << k : 0u;
+            for (int k = 0; k < 4; ++k) n1 |= motion_bit((g1 >> (8 * k)) & 255u, 0, false, a.thr) ? 1u << k : 0u;
         }
         unsigned out = g1;
         if (PAIR) {
@@ -99,27 +92,25 @@ template <bool ROI, bool PAIR, class SRC> __device__ __forceinline__ void diff_w
         }
         *lp = out;
     }
-    store_words(n1, lane, a.bits + (size_t)s * NW + (size_t)wave * 4);
-    if (PAIR) store_words(n2, lane, a.bits2 + (size_t)s * NW + (size_t)wave * 4);
+    store_words(n1, ql.lane, a.bits + (size_t)s * NW + (size_t)ql.wave * 4);
+    if (PAIR) store_words(n2, ql.lane, a.bits2 + (size_t)s * NW + (size_t)ql.wave * 4);
 }
 
 template <bool ROI, bool PAIR, class SRC> __device__ __forceinline__ void diff_narrow(const Geom &g, const DiffArgs &a, SRC src)
 {
     const int s = a.first_stream + (int)blockIdx.y;
     const bool have = PAIR || ((a.have >> blockIdx.y) & 1ull);
-    const int lane = threadIdx.x & 63;
-    const int word = blockIdx.x * 4 + (threadIdx.x >> 6);            // Palloc % 256 == 0: every word of the grid exists
-    const int p = word * 64 + lane;
-    const int y = p / g.Wp, x = p - y * g.Wp;
+    const WordLane l(g);                                             // Palloc % 256 == 0: every word of the grid exists
+    const int y = l.y, x = l.x;
     const size_t npx = (size_t)g.H * g.W, NW = (size_t)(g.Palloc >> 6);
     bool on1 = false, on2 = false;
-    if (p < g.P && x < g.W) {
+    if (l.inside(g)) {
         const size_t i = (size_t)y * g.W + x;
         uint8_t *lp = a.last + (size_t)s * npx + i;
-        const bool keep = !ROI || ((a.roi[(size_t)s * NW + word] >> lane) & 1ull);
+        const bool keep = !ROI || ((a.roi[(size_t)s * NW + l.word] >> l.lane) & 1ull);
         if (keep) src.begin1(g, s, y, x);
         const int g1 = keep ? grey1(src, a.frames, g, s, y, x) : 0;
-        on1 = have ? differs(g1, *lp, a.thr) : g1 != 0;
+        on1 = motion_bit(g1, have ? *lp : 0, have, a.thr);
         int out = g1;
         if (PAIR) {
             const int g2 = keep ? grey1(src, a.frames2, g, s, y, x) : 0;
@@ -128,12 +119,8 @@ template <bool ROI, bool PAIR, class SRC> __device__ __forceinline__ void diff_n
         }
         *lp = (uint8_t)out;
     }
-    const u64 w1 = __ballot(on1);
-    if (lane == 0) a.bits[(size_t)s * NW + word] = w1;
-    if (PAIR) {
-        const u64 w2 = __ballot(on2);
-        if (lane == 0) a.bits2[(size_t)s * NW + word] = w2;
-    }
+    store_word(on1, l.lane, a.bits, (size_t)s * NW + l.word);
+    if (PAIR) store_word(on2, l.lane, a.bits2, (size_t)s * NW + l.word);
 }
 
 // One kernel name a source and lane mapping; the raw and the remap kernels take what their source is built from

@@ -15,8 +15,7 @@
 //     reference's x86-64 build); the mixture lives in registers with fully
 //     unrolled, statically indexed mode loops (no scratch).
 //   * BGR->HSV uses RGB2HSV_b's integer quotients, taken on the spot by foreground lanes only
-//     (a zeroed pixel is HSV (0,0,0): one uniform window test); the stand-alone conversion
-//     kernel builds the two tables once per block in LDS.
+//     (a zeroed pixel is HSV (0,0,0): one uniform window test).
 //   * what nothing on the fused path can observe is not computed (detectShadowGMM: mog2_finish),
 //     what did not change is not stored (a frozen model is read-only: FROZEN), and what is
 //     only needed late is loaded late (kernel arguments: KRELOAD).
@@ -28,10 +27,11 @@
 //     they can test, revive or overwrite a later mode).  Stores go
 //     out only for planes whose bits changed.  The state in HBM stays bit-identical to
 //     updating all of it (state-parity tests).
+// The checkpoint kernels (k_state_export / k_state_import, at the end) stay in this unit because they are the only other code
+// that reads K1's model layout and its counter byte.
 #include "oatgpu_internal.h"
 #include "hsv_inline.h"
 #include <hip/hip_ext.h>
-#include <algorithm>
 #ifdef OATGPU_MEASURE
 #include <stdlib.h>
 #endif
@@ -347,33 +347,6 @@ __device__ __forceinline__ int mog2_finish(PxModel<CH, TUP> &s, PxLoop &c, int n
         }
     }
     return mask;
-}
-
-// RGB2HSV_b tables: sdiv[i] = cvRound((255<<12)/i), hdiv[i] = cvRound((180<<12)/(6 i)).
-// Neither quotient ever lands on .5 (255<<12 = 2^12*255, 180<<12/6 = 2^13*15), so
-// round-half-even == floor(q + 1/2) == floor((2n + i) / (2i)).  The quotient is taken in fp32:
-// numerator < 2^22 and denominator <= 510 are exact floats, and the exact quotient is at least 1/(2i) away from
-// the next integer, so floor() of an fp32 quotient that is good to a few ulp is exact (hsv_sdiv / hsv_hdiv in hsv_inline.h;
-// checked against the integer form for all 255 entries in tests/test_abi_exports.py).
-__device__ __forceinline__ void hsv_tables_init(int *sdiv, int *hdiv)
-{
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) {
-        sdiv[i] = hsv_sdiv(i);
-        hdiv[i] = hsv_hdiv(i);
-    }
-}
-
-__device__ __forceinline__ void bgr2hsv_px(int b, int g, int r, const int *sdiv, const int *hdiv,
-                                           int &h, int &s, int &v)
-{
-    v = max(b, max(g, r));
-    const int vmin = min(b, min(g, r));
-    const int diff = v - vmin;
-    s = (diff * sdiv[v] + (1 << 11)) >> 12;
-    int hh = (v == r) ? (g - b) : (v == g) ? (b - r + 2 * diff) : (r - g + 4 * diff);
-    hh = (hh * hdiv[diff] + (1 << 11)) >> 12;   // arithmetic shift, as the reference
-    hh += hh < 0 ? 180 : 0;
-    h = hh;
 }
 
 // Traffic audit (oatgpu_traffic_audit): the SAME kernel with every load / store predicate also counted --
@@ -990,60 +963,6 @@ __global__ __launch_bounds__(WG, (k1_waves<CH, AUDIT, NTLD, NF>())) void k_mog_f
 #undef AU_B
 }
 
-// ---- achievable-bandwidth probes: the best plain streaming kernels found on this chip ----
-// (tools/k1_lab.hip, profiles/r02_k1_lab.txt: one 16-byte element per thread on a FULL grid with the
-// streaming cache policy copies at 6.6 TB/s; the usual 2048-block grid-stride loop reaches 5.0)
-typedef unsigned nv4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void k_stream_read(const uint4 *src, size_t n, unsigned *sink)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const nv4 v = __builtin_nontemporal_load((const nv4 *)src + i);
-    if ((v.x ^ v.y ^ v.z ^ v.w) == 0x9e3779b9u) *sink = v.x;      // keeps the load alive, practically never taken
-}
-__global__ __launch_bounds__(256) void k_stream_copy(const uint4 *src, uint4 *dst, size_t n)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    __builtin_nontemporal_store(__builtin_nontemporal_load((const nv4 *)src + i), (nv4 *)dst + i);
-}
-void launch_stream_read(const void *src, size_t n16, unsigned *sink, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_stream_read, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, st, (const uint4 *)src, n16, sink);
-}
-void launch_stream_copy(const void *src, void *dst, size_t n16, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_stream_copy, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, st, (const uint4 *)src, (uint4 *)dst, n16);
-}
-
-// One camera's frame out of page-locked HOST memory (a registered shared-memory segment: every load is a PCIe read) into
-// its staging slot, by a kernel instead of a DMA copy (oatgpu_set_stage_copy): a launch costs the host ~5 us where a
-// hipMemcpyAsync costs ~20 us of set-up per 6 MB frame.  A small grid -- the waves do nothing but wait for the link, and
-// the per-pixel kernel wants the slots: 4 x 16 bytes in flight per lane, 128 workgroups = 2 MB in flight.
-__global__ __launch_bounds__(256) void k_stage_copy(const nv4 *src, nv4 *dst, size_t n16, const uint8_t *src_tail, uint8_t *dst_tail, int tail)
-{
-    const size_t stride = (size_t)gridDim.x * 1024;
-    for (size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x; i < n16; i += stride) {
-        nv4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) if (i + (size_t)u * 256 < n16) v[u] = __builtin_nontemporal_load(src + i + (size_t)u * 256);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) if (i + (size_t)u * 256 < n16) __builtin_nontemporal_store(v[u], dst + i + (size_t)u * 256);
-    }
-    if (blockIdx.x == 0 && (int)threadIdx.x < tail) dst_tail[threadIdx.x] = src_tail[threadIdx.x];
-}
-void launch_stage_copy(const void *src_dev_visible, void *dst, size_t bytes, hipStream_t st)
-{
-    const size_t n16 = bytes / 16;
-    const int tail = (int)(bytes - n16 * 16);
-    const unsigned blocks = (unsigned)std::min<size_t>(128, (n16 + 1023) / 1024 ? (n16 + 1023) / 1024 : 1);
-    hipLaunchKernelGGL(k_stage_copy, dim3(blocks), dim3(256), 0, st, (const nv4 *)src_dev_visible, (nv4 *)dst, n16,
-                       (const uint8_t *)src_dev_visible + n16 * 16, (uint8_t *)dst + n16 * 16, tail);
-}
-
-__global__ void k_nop() {}
-void launch_nop(hipStream_t st) { hipLaunchKernelGGL(k_nop, dim3(1), dim3(64), 0, st); }
-
 template <int CH, bool AUDIT, bool NTLD, int NF, bool FROZEN, int WG>
 static void launch_mog_wg(const Geom &g, const MogLaunch &a, int first_stream, int n_streams, hipStream_t st, hipEvent_t stop)
 {
@@ -1162,276 +1081,6 @@ void launch_density_probe(const uint8_t *nmodes, size_t total, unsigned *out, hi
     const size_t samples = 16384;
     const size_t stride = total > samples ? total / samples : 1;
     hipLaunchKernelGGL(k_density_probe, dim3(1), dim3(1024), 0, st, nmodes, total, stride, out);
-}
-
-// ------------------------------------------------------------ small kernels --
-
-__global__ __launch_bounds__(256) void k_bgr2hsv(const uint8_t *bgr, uint8_t *hsv, size_t npx)
-{
-    __shared__ int sdiv[256];
-    __shared__ int hdiv[256];
-    hsv_tables_init(sdiv, hdiv);
-    __syncthreads();
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += (size_t)gridDim.x * blockDim.x) {
-        int h, s, v;
-        bgr2hsv_px(bgr[3 * i], bgr[3 * i + 1], bgr[3 * i + 2], sdiv, hdiv, h, s, v);
-        hsv[3 * i] = (uint8_t)h; hsv[3 * i + 1] = (uint8_t)s; hsv[3 * i + 2] = (uint8_t)v;
-    }
-}
-
-void launch_bgr2hsv(const uint8_t *bgr, uint8_t *hsv, size_t npx, hipStream_t st)
-{
-    int blocks = (int)((npx + 255) / 256);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_bgr2hsv, dim3(blocks), dim3(256), 0, st, bgr, hsv, npx);
-}
-
-// ---- the other entries of oat::color_conv_table (Color.h:45-51) behind ColorConvert::filter (ColorConvert.cpp:101-107) ----
-// Four pixels a thread, every access a dword (4 px x 3 B = three dwords; 4 grey px = one); the last npx % 4 pixels
-// are done byte-wise by the thread behind the last full group.
-
-// COLOR_BGR2GRAY on 8U: RGB2Gray<uchar>'s table sums = (1868 B + 9617 G + 4899 R + 2^13) >> 14
-__device__ __forceinline__ unsigned grey_of(unsigned b, unsigned g, unsigned r)
-{
-    return (1868u * b + 9617u * g + 4899u * r + (1u << 13)) >> 14;
-}
-
-// COLOR_HSV2BGR on 8U, OpenCV 3.1.0: HSV2RGB_b over HSV2RGB_f(hrange 180) -- fp32, every operation rounded on its own
-// (-ffp-contract=off), cvRound (nearest even) + saturation on the way out.  h <= 255 -> h * (6/180) < 8.5: the
-// reference's "do h -= 6 while (h >= 6)" runs once at most and the sector is always one of 0..5.
-__device__ __forceinline__ void hsv2bgr_px(unsigned hh, unsigned ss, unsigned vv, unsigned &b, unsigned &g, unsigned &r)
-{
-    float h = (float)hh;
-    const float s = (float)ss * (1.f / 255.f), v = (float)vv * (1.f / 255.f);
-    float fb, fg, fr;
-    if (s == 0.f) fb = fg = fr = v;
-    else {
-        h *= 6.f / 180.f;
-        if (h >= 6.f) h -= 6.f;
-        const int sector = (int)floorf(h);
-        h -= (float)sector;
-        const float t0 = v, t1 = v * (1.f - s), t2 = v * (1.f - s * h), t3 = v * (1.f - s * (1.f - h));
-        switch (sector) {                       // sector_data[][3] of HSV2RGB_f, (b, g, r)
-        case 0:  fb = t1; fg = t3; fr = t0; break;
-        case 1:  fb = t1; fg = t0; fr = t2; break;
-        case 2:  fb = t3; fg = t0; fr = t1; break;
-        case 3:  fb = t0; fg = t2; fr = t1; break;
-        case 4:  fb = t0; fg = t1; fr = t3; break;
-        default: fb = t2; fg = t1; fr = t0; break;
-        }
-    }
-    b = (unsigned)min(max(__float2int_rn(fb * 255.f), 0), 255);
-    g = (unsigned)min(max(__float2int_rn(fg * 255.f), 0), 255);
-    r = (unsigned)min(max(__float2int_rn(fr * 255.f), 0), 255);
-}
-
-template <int kCode>   // 0: BGR -> GREY, 1: GREY -> BGR, 2: HSV -> BGR
-__global__ __launch_bounds__(256) void k_cvt_color(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, size_t npx)
-{
-    const size_t groups = npx >> 2;
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < groups) {
-        if (kCode == 1) {
-            const unsigned q = ((const unsigned *)in)[t];
-            const unsigned p0 = q & 255u, p1 = (q >> 8) & 255u, p2 = (q >> 16) & 255u, p3 = q >> 24;
-            unsigned *o = (unsigned *)out + 3 * t;
-            o[0] = p0 * 0x010101u | p1 << 24;
-            o[1] = p1 * 0x0101u | p2 * 0x01010000u;
-            o[2] = p2 | p3 * 0x01010100u;
-        } else {
-            const unsigned *w = (const unsigned *)in + 3 * t;
-            const unsigned w0 = w[0], w1 = w[1], w2 = w[2];
-            // channel c of pixel k is byte 3k + c of the twelve
-            const unsigned a0 = w0 & 255u, a1 = (w0 >> 8) & 255u, a2 = (w0 >> 16) & 255u;
-            const unsigned b0 = w0 >> 24, b1 = w1 & 255u, b2 = (w1 >> 8) & 255u;
-            const unsigned c0 = (w1 >> 16) & 255u, c1 = w1 >> 24, c2 = w2 & 255u;
-            const unsigned d0 = (w2 >> 8) & 255u, d1 = (w2 >> 16) & 255u, d2 = w2 >> 24;
-            if (kCode == 0) {
-                ((unsigned *)out)[t] = grey_of(a0, a1, a2) | grey_of(b0, b1, b2) << 8 | grey_of(c0, c1, c2) << 16 |
-                                       grey_of(d0, d1, d2) << 24;
-            } else {
-                unsigned pb[4], pg[4], pr[4];
-                hsv2bgr_px(a0, a1, a2, pb[0], pg[0], pr[0]);
-                hsv2bgr_px(b0, b1, b2, pb[1], pg[1], pr[1]);
-                hsv2bgr_px(c0, c1, c2, pb[2], pg[2], pr[2]);
-                hsv2bgr_px(d0, d1, d2, pb[3], pg[3], pr[3]);
-                unsigned *o = (unsigned *)out + 3 * t;
-                o[0] = pb[0] | pg[0] << 8 | pr[0] << 16 | pb[1] << 24;
-                o[1] = pg[1] | pr[1] << 8 | pb[2] << 16 | pg[2] << 24;
-                o[2] = pr[2] | pb[3] << 8 | pg[3] << 16 | pr[3] << 24;
-            }
-        }
-    } else if (t == groups) {
-        for (size_t i = groups << 2; i < npx; ++i) {
-            if (kCode == 0) out[i] = (uint8_t)grey_of(in[3 * i], in[3 * i + 1], in[3 * i + 2]);
-            else if (kCode == 1) out[3 * i] = out[3 * i + 1] = out[3 * i + 2] = in[i];
-            else {
-                unsigned b, g, r;
-                hsv2bgr_px(in[3 * i], in[3 * i + 1], in[3 * i + 2], b, g, r);
-                out[3 * i] = (uint8_t)b; out[3 * i + 1] = (uint8_t)g; out[3 * i + 2] = (uint8_t)r;
-            }
-        }
-    }
-}
-
-void launch_cvt_color(int code, const uint8_t *in, uint8_t *out, size_t npx, hipStream_t st)
-{
-    const unsigned blocks = (unsigned)(((npx >> 2) + 1 + 255) / 256);
-    if (code == 0) hipLaunchKernelGGL(k_cvt_color<0>, dim3(blocks), dim3(256), 0, st, in, out, npx);
-    else if (code == 1) hipLaunchKernelGGL(k_cvt_color<1>, dim3(blocks), dim3(256), 0, st, in, out, npx);
-    else hipLaunchKernelGGL(k_cvt_color<2>, dim3(blocks), dim3(256), 0, st, in, out, npx);
-}
-
-// one wave = one mask word (64 pixels of one row)
-__global__ __launch_bounds__(256) void k_inrange_bits(Geom g, const uint8_t *frame, int channels,
-                                                      RangeParams rp, u64 *bits)
-{
-    const int lane = threadIdx.x & 63;
-    const int word = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (word >= (g.Palloc >> 6)) return;
-    const int p = word * 64 + lane;
-    const int y = p / g.Wp, x = p - y * g.Wp;
-    const bool valid = p < g.P && x < g.W;
-    bool thr = false;
-    if (valid) {
-        const size_t i = (size_t)y * g.W + x;
-        if (channels == 3) thr = in_range3(frame[3 * i], frame[3 * i + 1], frame[3 * i + 2], rp);
-        else { const int v = frame[i]; thr = v >= rp.lo[0] && v <= rp.hi[0]; }
-    }
-    const u64 w = __ballot(thr);
-    if (lane == 0) bits[word] = w;
-}
-
-void launch_inrange_bits(const Geom &g, const uint8_t *frame, int channels, const RangeParams &rp,
-                         u64 *bits, hipStream_t st)
-{
-    const int nwords = g.Palloc >> 6;
-    hipLaunchKernelGGL(k_inrange_bits, dim3((nwords + 3) / 4), dim3(256), 0, st, g, frame, channels, rp, bits);
-}
-
-// framefilt bsub: first frame -> background; alpha > 0: cv::accumulateWeighted in fp32
-// (src*a + bg*b, a = (float)alpha, b = 1 - a) and convertTo(CV_8U) (round half even, saturate);
-// then frame - background, saturating (BackgroundSubtractor.cpp:87-100).
-__global__ __launch_bounds__(256) void k_bsub(const uint8_t *in, uint8_t *out, uint8_t *bg, float *bg_f, size_t n,
-                                              float a, float b, int first, int learn)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int v = in[i];
-        float f = first ? (float)v : bg_f[i];
-        int g = first ? v : bg[i];
-        if (learn) {
-            f = v * a + f * b;
-            g = min(255, max(0, __float2int_rn(f)));
-        }
-        if (first || learn) { bg_f[i] = f; bg[i] = (uint8_t)g; }
-        out[i] = (uint8_t)(v > g ? v - g : 0);
-    }
-}
-
-void launch_bsub(const uint8_t *in, uint8_t *out, uint8_t *bg, float *bg_f, size_t n, float a, float b, int first,
-                 int learn, hipStream_t st)
-{
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_bsub, dim3(blocks), dim3(256), 0, st, in, out, bg, bg_f, n, a, b, first, learn);
-}
-
-// framefilt mask: frame.setTo(0, roi_mask == 0) (FrameMasker.cpp:71-75) with the 1-bit ROI plane
-__global__ __launch_bounds__(256) void k_apply_roi(Geom g, const uint8_t *in, uint8_t *out, int ch, const u64 *roi)
-{
-    const size_t npx = (size_t)g.H * g.W;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += (size_t)gridDim.x * blockDim.x) {
-        const int y = (int)(i / g.W), x = (int)(i - (size_t)y * g.W);
-        const int p = y * g.Wp + x;
-        const bool keep = (roi[p >> 6] >> (p & 63)) & 1ull;
-        for (int c = 0; c < ch; ++c) out[i * ch + c] = keep ? in[i * ch + c] : 0;
-    }
-}
-void launch_apply_roi(const Geom &g, const uint8_t *in, uint8_t *out, int channels, const u64 *roi, hipStream_t st)
-{
-    const size_t npx = (size_t)g.H * g.W;
-    int blocks = (int)((npx + 255) / 256);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_apply_roi, dim3(blocks), dim3(256), 0, st, g, in, out, channels, roi);
-}
-
-// framefilt thresh: RGB2Gray<uchar> ((1868 B + 9617 G + 4899 R + 8192) >> 14), inRange, setTo(0)
-__global__ __launch_bounds__(256) void k_thresh_filter(const uint8_t *in, uint8_t *out, size_t npx, int ch, int lo,
-                                                       int hi)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += (size_t)gridDim.x * blockDim.x) {
-        if (ch == 3) {
-            const int b = in[3 * i], g = in[3 * i + 1], r = in[3 * i + 2];
-            const int y = (1868 * b + 9617 * g + 4899 * r + (1 << 13)) >> 14;
-            const bool keep = y >= lo && y <= hi;
-            out[3 * i] = keep ? b : 0; out[3 * i + 1] = keep ? g : 0; out[3 * i + 2] = keep ? r : 0;
-        } else {
-            const int y = in[i];
-            out[i] = (y >= lo && y <= hi) ? y : 0;
-        }
-    }
-}
-
-void launch_thresh_filter(const uint8_t *in, uint8_t *out, size_t npx, int channels, int lo, int hi, hipStream_t st)
-{
-    int blocks = (int)((npx + 255) / 256);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_thresh_filter, dim3(blocks), dim3(256), 0, st, in, out, npx, channels, lo, hi);
-}
-
-// posidet diff: cv::absdiff + cv::threshold(THRESH_BINARY) of a GREY frame against the previous one
-// (DifferenceDetector.cpp:156-161), one wave = one mask word; also refreshes the previous frame.
-__global__ __launch_bounds__(256) void k_absdiff_bits(Geom g, const uint8_t *frame, uint8_t *last, int thr,
-                                                      int have_last, u64 *bits)
-{
-    const int lane = threadIdx.x & 63;
-    const int word = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (word >= (g.Palloc >> 6)) return;
-    const int p = word * 64 + lane;
-    const int y = p / g.Wp, x = p - y * g.Wp;
-    const bool valid = p < g.P && x < g.W;
-    bool on = false;
-    if (valid) {
-        const size_t i = (size_t)y * g.W + x;
-        const int v = frame[i];
-        if (have_last) { const int l = last[i]; on = (v > l ? v - l : l - v) > thr; }
-        else on = v != 0;                       // first frame: threshold_frame_ = frame.clone()
-        last[i] = (uint8_t)v;
-    }
-    const u64 w = __ballot(on);
-    if (lane == 0) bits[word] = w;
-}
-
-void launch_absdiff_bits(const Geom &g, const uint8_t *frame, uint8_t *last, int thr, int have_last, u64 *bits,
-                         hipStream_t st)
-{
-    const int nwords = g.Palloc >> 6;
-    hipLaunchKernelGGL(k_absdiff_bits, dim3((nwords + 3) / 4), dim3(256), 0, st, g, frame, last, thr, have_last, bits);
-}
-
-__global__ __launch_bounds__(256) void k_unpack_bits(Geom g, const u64 *bits, uint8_t *out)
-{
-    const size_t npx = (size_t)g.H * g.W;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += (size_t)gridDim.x * blockDim.x) {
-        const int y = (int)(i / g.W), x = (int)(i - (size_t)y * g.W);
-        const int p = y * g.Wp + x;
-        out[i] = ((bits[p >> 6] >> (p & 63)) & 1ull) ? 255 : 0;
-    }
-}
-
-void launch_pack_bits(const Geom &g, const uint8_t *in, u64 *bits, hipStream_t st)
-{
-    RangeParams rp;
-    rp.lo[0] = 1; rp.hi[0] = 255; rp.lo[1] = rp.lo[2] = 0; rp.hi[1] = rp.hi[2] = 255;
-    launch_inrange_bits(g, in, 1, rp, bits, st);     // nonzero == in [1,255]
-}
-
-void launch_unpack_bits(const Geom &g, const u64 *bits, uint8_t *out, hipStream_t st)
-{
-    size_t npx = (size_t)g.H * g.W;
-    int blocks = (int)((npx + 255) / 256);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_unpack_bits, dim3(blocks), dim3(256), 0, st, g, bits, out);
 }
 
 // ---- model checkpoint: device layout <-> OpenCV's logical AoS order ----

@@ -1,10 +1,38 @@
-// maskwords_inline.h -- a wave's mask words out of four pixels a lane, shared by the front kernels that own 4 consecutive pixels
-// of a row per lane (kernels_diff.hip, kernels_bsubtrack.hip).
+// maskwords_inline.h -- which pixels of the padded index space a lane owns and how a wave's mask words leave it, shared by the
+// kernels that write a bit plane with 256 threads a workgroup and blockIdx.x along the plane: one pixel a lane (kernels_stages.hip,
+// the narrow front kernels) or 4 consecutive pixels of a row a lane (the wide front kernels; kernels_diff.hip, kernels_bsubtrack.hip).
 #pragma once
 
 #include "oatgpu_internal.h"
 
 namespace oatgpu {
+
+// one wave = one mask word: pixel p = y * Wp + x of word `word` is this lane's; inside(): it is a pixel of the frame
+struct WordLane {
+    int lane, word, p, y, x;
+    // the wave's word alone, for a kernel that leaves before anything else when its grid may overshoot the plane
+    static __device__ __forceinline__ int this_word() { return blockIdx.x * 4 + (threadIdx.x >> 6); }
+    __device__ __forceinline__ explicit WordLane(const Geom &g)
+        : lane(threadIdx.x & 63), word(this_word()), p(word * 64 + lane), y(p / g.Wp), x(p - y * g.Wp) {}
+    __device__ __forceinline__ bool inside(const Geom &g) const { return p < g.P && x < g.W; }
+};
+
+// the wave's word out of every lane's bit: lane 0 stores it as words[index]
+__device__ __forceinline__ void store_word(bool on, int lane, u64 *words, size_t index)
+{
+    const u64 w = __ballot(on);
+    if (lane == 0) words[index] = w;
+}
+
+// four pixels a lane: p0 .. p0 + 3 from (y, x) on, of words 4 * wave .. 4 * wave + 3 (Palloc % 1024 == 0); W % 4 == 0: inside together
+struct QuadLane {
+    int lane, wave, p0, y, x;
+    __device__ __forceinline__ explicit QuadLane(const Geom &g)
+        : lane(threadIdx.x & 63), wave(blockIdx.x * 4 + (threadIdx.x >> 6)), p0(wave * 256 + lane * 4), y(p0 / g.Wp), x(p0 - y * g.Wp) {}
+    __device__ __forceinline__ bool inside(const Geom &g) const { return p0 < g.P && x < g.W; }
+    // the 4 pixels' bits of a stream's bit plane (bit k = pixel k of the lane)
+    __device__ __forceinline__ unsigned nibble(const u64 *plane) const { return (((const uint8_t *)plane)[p0 >> 3] >> (p0 & 4)) & 15u; }
+};
 
 // bits 0..15 of x to bits 0, 4, 8, .. 60
 __device__ __forceinline__ u64 spread4(u64 x)

@@ -120,11 +120,24 @@ struct MogLaunchOpts {
 };
 void launch_mog_fused(const Geom &g, const MogLaunch &a, int first_stream, int n_streams, hipStream_t st, hipEvent_t stop,
                       const MogLaunchOpts &o);
+void launch_density_probe(const uint8_t *nmodes, size_t total, unsigned *out, hipStream_t st);   // out = {live modes, samples}
+// model checkpoint: logical (OpenCV AoS) <-> device planes
+// state / nmodes point at ONE stream's model
+void launch_state_export(const Geom &g, float *state, uint8_t *nmodes, int nmix, int channels,
+                         uint8_t *modes_used, float *weight, float *variance, float *mean, hipStream_t st);
+void launch_state_import(const Geom &g, float *state, uint8_t *nmodes, int nmix, int channels,
+                         const uint8_t *modes_used, const float *weight, const float *variance,
+                         const float *mean, hipStream_t st);
+
+// --- kernels_measure.hip ---
 // plain streaming kernels for the achievable-bandwidth measurement (n16 = number of 16-byte elements)
 void launch_stream_read(const void *src, size_t n16, unsigned *sink, hipStream_t st);
 void launch_stream_copy(const void *src, void *dst, size_t n16, hipStream_t st);
-void launch_density_probe(const uint8_t *nmodes, size_t total, unsigned *out, hipStream_t st);   // out = {live modes, samples}
 void launch_nop(hipStream_t st);   // one empty wave: calibrates what an event pair adds around a launch
+
+// --- kernels_stages.hip --- (one component on one frame a launch)
+// workgroups of 256 threads for a grid-stride loop over n elements: one thread an element up to a cap
+inline unsigned grid_stride_blocks(size_t n) { const size_t blocks = (n + 255) / 256; return blocks > 8192 ? 8192u : (unsigned)blocks; }
 // bytes from device-visible (page-locked, mapped) host memory to device memory by a kernel; both 16-byte aligned
 void launch_stage_copy(const void *src_dev_visible, void *dst, size_t bytes, hipStream_t st);
 void launch_bgr2hsv(const uint8_t *bgr, uint8_t *hsv, size_t npx, hipStream_t st);
@@ -146,13 +159,6 @@ void launch_absdiff_bits(const Geom &g, const uint8_t *frame, uint8_t *last, int
 void launch_unpack_bits(const Geom &g, const u64 *bits, uint8_t *out, hipStream_t st);
 // rows*cols bytes (nonzero = keep) -> bit mask of one stream
 void launch_pack_bits(const Geom &g, const uint8_t *in, u64 *bits, hipStream_t st);
-// model checkpoint: logical (OpenCV AoS) <-> device planes
-// state / nmodes point at ONE stream's model
-void launch_state_export(const Geom &g, float *state, uint8_t *nmodes, int nmix, int channels,
-                         uint8_t *modes_used, float *weight, float *variance, float *mean, hipStream_t st);
-void launch_state_import(const Geom &g, float *state, uint8_t *nmodes, int nmix, int channels,
-                         const uint8_t *modes_used, const float *weight, const float *variance,
-                         const float *mean, hipStream_t st);
 
 // --- kernels_diff.hip, kernels_bsubtrack.hip --- (the front ends of the two batched trackers)
 // what both front launches take: the frames, where the threshold words go, and the frames' form

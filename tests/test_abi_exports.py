@@ -69,7 +69,7 @@ def test_create_without_gpu_fails_loudly_not_silently(lib):
 
 
 def test_hsv_table_integer_formula_equals_cvround():
-    """The kernel builds RGB2HSV_b's tables as floor(fp32((2n+i) / (2i))): check that this equals the
+    """The kernels take RGB2HSV_b's table entries as floor(fp32((2n+i) / (2i))): check that this equals the
     integer form and cvRound(n/i) for every entry (the fp32 quotient is exact enough for floor())."""
     import numpy as np
     for i in range(1, 256):
