@@ -48,7 +48,7 @@ clean:
 
 # A/B variant builds: make variant NAME=px2 DEFS="-DOATGPU_PX=2"  -> build/variants/liboatgpu_px2.so
 # Only these builds (-DOATGPU_MEASURE) read the OATGPU_A_RESERVE / EARLY_BLOB / EARLY_MIN_PX / LONE_PLAIN / PAIR_BACK /
-# K1_WG / K1_STOP_EVENT / K1_LDS measurement switches from the environment; the product library ignores them.
+# K1_WG / K1_STOP_EVENT / K1_LDS / RS_DEEP_ROWS measurement switches from the environment; the product library ignores them.
 # They live under build/ (git-ignored, but they travel to the GPU box):
 # oat_amd/lib/ holds the product library and nothing else, and the Python binding loads another library only with
 # OATGPU_MEASURE_PY=1 OATGPU_LIB=<path> (oat_amd/ffi.py; the tools/*.sh A/B scripts set both).

@@ -232,6 +232,17 @@ int oatgpu_set_k1_workgroup(oatgpu_ctx *ctx, int32_t threads);
 /* How the latest pipelined step was launched: threads of a per-pixel workgroup (0 before the first step) and whether its
  * blob workgroup was dispatched early.  Either pointer may be NULL. */
 int oatgpu_last_step_shape(const oatgpu_ctx *ctx, int32_t *k1_workgroup, int32_t *early_blob);
+/* Image rows a workgroup of the row scan takes on the pipelined path.  4 rows deliver a frame's result soonest; 16 rows are
+ * fewer, longer workgroups beside the per-pixel kernel, which then runs ~3 % faster at 4K, and a result that comes up to
+ * ~85 us later (4K; ~28 us at 1080p).  rows = 0 (the default): by pipeline depth -- 16 on a step launched while at least four
+ * earlier frames are still uncollected (results are collected in order: nobody can be waiting for that step's), 4 otherwise;
+ * a caller that keeps a ring of 2 or 4, or one frame at a time, always gets 4.  rows = 4 / 16: that height on every eligible
+ * step whatever the depth.  Eligible: a step of the early or the paired order whose fused erosion fits the row scan's LDS at
+ * 16 rows ((16 + max(dilate, 1) - 1) x 8-byte words of a row <= 64 KiB); every other step takes 4.  Other values are refused.
+ * Results are identical either way. */
+int oatgpu_set_rowscan_rows(oatgpu_ctx *ctx, int32_t rows);
+/* Rows a row-scan workgroup of the latest pipelined step took (0 before the first step). */
+int oatgpu_last_step_rowscan_rows(const oatgpu_ctx *ctx);
 
 /* Re-configure the detector between frames (what the reference's tuning GUI
  * mutates: HSVDetector.cpp:175-251). */

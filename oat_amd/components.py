@@ -969,6 +969,15 @@ class HotPath(_Detector):
         self._chk(self.lib.oatgpu_last_step_shape(self.ctx, C.byref(wg), C.byref(early)))
         return wg.value, bool(early.value)
 
+    def set_rowscan_rows(self, rows=0):
+        """oatgpu_set_rowscan_rows: image rows a row-scan workgroup takes on the pipelined path, 0 = by pipeline depth
+        (default: 16 with four and more frames ahead in the ring, else 4), 4 or 16 = on every eligible step."""
+        self._chk(self.lib.oatgpu_set_rowscan_rows(self.ctx, int(rows)))
+
+    def last_step_rowscan_rows(self):
+        """Rows a row-scan workgroup of the latest pipelined step took (oatgpu_last_step_rowscan_rows)."""
+        return int(self.lib.oatgpu_last_step_rowscan_rows(self.ctx))
+
     def early_blob_timeouts(self):
         """Frames whose parked blob workgroup gave up waiting for its row scan (oatgpu_early_blob_timeouts)."""
         return int(self.lib.oatgpu_early_blob_timeouts(self.ctx))

@@ -290,6 +290,7 @@ extern "C" oatgpu_ctx *oatgpu_create(const oatgpu_config *cfg)
     if (const char *e = measure_env("OATGPU_EARLY_MIN_PX")) c->early_min_px = (size_t)atoll(e);
     if (const char *e = measure_env("OATGPU_LONE_PLAIN")) c->lone_plain = atoi(e) != 0;
     if (const char *e = measure_env("OATGPU_PAIR_BACK")) c->pair_back = atoi(e) != 0;
+    if (const char *e = measure_env("OATGPU_RS_DEEP_ROWS")) { const int v = atoi(e); if (v == kRsRowsDeep || v == kRsRowsDeepAlt) c->rs_rows_deep = v; }
     if (const char *e = measure_env("OATGPU_K1_WG")) { const int v = atoi(e); if (v == 64 || v == 256) c->k1_wg_force = v; }
 
     if (const char *e = measure_env("OATGPU_K1_STOP_EVENT")) c->k1_stop_event = atoi(e) != 0 ? 1 : 0;
@@ -442,6 +443,16 @@ extern "C" int oatgpu_last_step_shape(const oatgpu_ctx *c, int32_t *k1_workgroup
     if (early_blob) *early_blob = c->last_step_early ? 1 : 0;
     return OATGPU_OK;
 }
+
+extern "C" int oatgpu_set_rowscan_rows(oatgpu_ctx *c, int32_t rows)
+{
+    if (!c || (rows != 0 && rows != kRsRowsNarrow && rows != c->rs_rows_deep))
+        return fail(c, OATGPU_E_INVALID, "row-scan rows must be 0 (by pipeline depth), %d or %d", kRsRowsNarrow, c ? c->rs_rows_deep : kRsRowsDeep);
+    c->rs_rows_force = rows;
+    return OATGPU_OK;
+}
+
+extern "C" int oatgpu_last_step_rowscan_rows(const oatgpu_ctx *c) { return c ? c->last_rs_rows : 0; }
 
 extern "C" int64_t oatgpu_early_blob_timeouts(const oatgpu_ctx *c) { return c ? (int64_t)c->early_timeouts : 0; }
 

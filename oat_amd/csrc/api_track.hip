@@ -302,7 +302,8 @@ extern "C" int oatgpu_track_enqueue(oatgpu_ctx *c, const uint8_t *const *frames_
 }
 
 // The decisions of a step of one frame (nj == 1) or two consecutive frames (nj == 2).  No HIP calls, no context fields written.
-static StepPlan plan_step(const oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, bool lone)
+// ahead: frames launched earlier and not collected yet.
+static StepPlan plan_step(const oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, bool lone, int ahead)
 {
     const Geom &g = c->g;
     const size_t step_px = (size_t)c->cfg.n_streams * (size_t)g.P;
@@ -348,6 +349,18 @@ static StepPlan plan_step(const oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, in
     p.paired = nj == 2 && !p.early && c->pair_back && c->lds_spec && !c->kal_on && lds_geom && !p.ero_apart;
     // the plain order, speculative (row scan + LDS kernel alone) unless the position filter is on or a frame was declined
     p.spec_plain = !p.early && !p.paired && c->lds_spec && !c->kal_on;
+    // Rows a row-scan workgroup (kernels_blob.hip "Rows a workgroup").  The wide form takes fewer wave slots from the per-pixel
+    // kernel beside it and delivers the frame later: up to ~85 us at 4K, ~28 us at 1080p (profiles/r07y_rowscan_rows_per_workgroup_ab.txt).
+    // A step is DEEP when kDeepAhead frames launched earlier are still uncollected: results are collected in order, so nobody can
+    // ask for this step's before those -- two launch periods, ~100 us at 4K; both sides scale with the frame.  Rings of 2 and 4
+    // (oat-track-hip) never get there, a ring of 8 kept full has 6 ahead at every launch, and a lone frame is never deep.
+    // Early and paired order only (the plain order, repairs, the single stage and the marker table stay narrow), and only where the
+    // fused erosion's LDS at that height fits: otherwise narrow, with the routes and the ero_apart decision above unchanged.
+    // (No floor on the frame size: small frames did not lose in profiles/rowscan_deep_rows.txt.)
+    constexpr int kDeepAhead = 4;
+    const bool wide_fits = rowscan_lds_bytes_rows(g, p.dil, c->rs_rows_deep) <= kRowscanLdsMax;
+    const bool deep = c->rs_rows_force ? c->rs_rows_force != kRsRowsNarrow : ahead >= kDeepAhead;
+    p.rs_rows = deep && (p.early || p.paired) && wide_fits ? c->rs_rows_deep : kRsRowsNarrow;
     return p;
 }
 
@@ -461,7 +474,7 @@ static int launch_back_paired(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, cons
     const BlobBuffers bbs[2] = {c->bb[2 * p].b, c->bb[2 * p + 1].b};
     const u64 *srcs[2] = {thr_buf(c, j[0].slot), thr_buf(c, j[1].slot)};
     ResultRec *res[2] = {c->res.dev() + (size_t)j[0].slot * n, c->res.dev() + (size_t)j[1].slot * n};
-    launch_blob_pair(c->g, bbs, srcs, plan.ero, plan.dil, c->cfg.min_area, c->cfg.max_area, res, n, B);
+    launch_blob_pair(c->g, bbs, srcs, plan.ero, plan.dil, c->cfg.min_area, c->cfg.max_area, res, n, B, plan.rs_rows);
     HIPCHK(c, hipGetLastError());
     if (ps) HIPCHK(c, hipEventRecord(ps->e[4], B));
     for (int i = 0; i < 2; ++i) {
@@ -510,7 +523,7 @@ static int launch_back_early(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int n
         c->last_fin = bb.fin;
         unsigned ticket = ++c->bh_ticket[q];
         if (!ticket) ticket = ++c->bh_ticket[q];
-        launch_rowscan_signal(g, bb, m.src, m.ero, plan.dil, 0, n, ticket, R);
+        launch_rowscan_signal(g, bb, m.src, m.ero, plan.dil, 0, n, ticket, R, plan.rs_rows);
         bbs[i] = bb; res[i] = c->res.dev() + (size_t)slot * n; tk[i] = ticket;
         mark_speculative(c, slot);                       // (repaired behind the blob launches on B2)
     }
@@ -575,7 +588,8 @@ static int launch_back_plain(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int n
 
 // The kernels of one frame (nj == 1) or of two consecutive frames (nj == 2: K1 once for both where the streams'
 // learning-rate schedules allow, then the back halves in the layout plan_step picked).
-static int launch_jobs(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, bool lone = false)
+// ahead: frames launched earlier that are still uncollected (the ring's count less the frames of this step)
+static int launch_jobs(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, int ahead, bool lone = false)
 {
     ProfStep *ps = nullptr;
     if (c->prof && (c->prof_tick++ % (unsigned long long)c->prof_every) == 0) {
@@ -590,8 +604,9 @@ static int launch_jobs(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, boo
         ps = &c->prof_steps[c->prof_used++];
         ps->frames = nj;
     }
-    const StepPlan plan = plan_step(c, j, nj, lone);
+    const StepPlan plan = plan_step(c, j, nj, lone, ahead);
     c->last_k1_wg = plan.k1_wg;
+    c->last_rs_rows = plan.rs_rows;
     c->last_step_early = plan.early;
     { const int rc = launch_front(c, j, nj, plan, ps); if (rc) return rc; }
     const int path = plan.early ? 1 : plan.paired ? 2 : 0;
@@ -610,7 +625,7 @@ int flush_pending(oatgpu_ctx *c)
     if (!c->pend_valid) return OATGPU_OK;
     c->pend_valid = false;
     int rc = hipSetDevice(c->cfg.device) == hipSuccess ? OATGPU_OK : fail(c, OATGPU_E_HIP, "hipSetDevice(%d) failed", c->cfg.device);
-    if (!rc) rc = launch_jobs(c, &c->pend, 1, c->ring_count == 1);        // (lone: nothing else is outstanding)
+    if (!rc) rc = launch_jobs(c, &c->pend, 1, c->ring_count - 1, c->ring_count == 1);        // (lone: nothing else is outstanding)
     if (rc) {
         // the same rule as in enqueue_frames: mog_begin has advanced the frame counts and the rate schedule, the model may
         // have moved -- fatal for the context.  The registered frame is no longer outstanding: without this a later collect
@@ -638,7 +653,7 @@ static int enqueue_frames(oatgpu_ctx *c, const void *frames_dev, double lr, hipE
     if (c->pend_valid) {
         const oatgpu_ctx::FrameJob two[2] = {c->pend, cur};
         c->pend_valid = false;
-        rc = launch_jobs(c, two, 2);
+        rc = launch_jobs(c, two, 2, c->ring_count - 1);       // (ring_count holds the registered frame, not yet this one)
         if (rc) {                         // the registered frame went down with this one: it is no longer outstanding
             c->enq_total--;
             c->ring_count--;
@@ -648,7 +663,7 @@ static int enqueue_frames(oatgpu_ctx *c, const void *frames_dev, double lr, hipE
         c->pend = cur;
         c->pend_valid = true;
     } else {
-        rc = launch_jobs(c, &cur, 1, c->ring_count == 0);
+        rc = launch_jobs(c, &cur, 1, c->ring_count, c->ring_count == 0);
     }
     if (rc) {
         // launch_jobs had advanced the streams' frame counts and rate schedules (mog_begin) and may have updated the

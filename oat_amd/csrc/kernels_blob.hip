@@ -171,11 +171,17 @@ __device__ __forceinline__ u64 dilate_word_lds(const Geom &g, const u64 *er, int
 // say where the 55-60 us of this kernel beside the per-pixel kernel go: a workgroup RUNS 7 us (9 p90), the 540 workgroups of a 4K
 // frame START over 35 us -- the dispatcher hands this queue ~15 workgroups a microsecond while the per-pixel launch streams
 // 1 300 a microsecond through the other.
-// (Rows a workgroup: 8 / 16 instead of 4 -- fewer workgroups beside K1, a longer loop in each -- is a trade, not a gain: 4K
-// 19.0 k -> 19.3 k / 19.6 k fps and one 1080p stream 56.2 k -> 56.8 k / 58.9 k, because K1 is disturbed less, but a frame's
-// result comes 40 / 83 us later (gpu_total 242 -> 282 / 325 us) and one frame at a time takes 127 -> 131 / 141 us:
-// profiles/r07y_rowscan_rows_per_workgroup_ab.txt.  Oat is a real-time tracker: four rows.)
+// Rows a workgroup (ROWS, a template parameter: the loop over rows is the same at any height, and nothing a row writes depends on
+// it, so steps of either height follow each other on the same scratch sets): 8 / 16 instead of 4 -- fewer workgroups beside K1, a
+// longer loop in each -- disturbs K1 less: 4K 19.0 k -> 19.3 k / 19.6 k fps and one 1080p stream 56.2 k -> 56.8 k / 58.9 k; but a
+// frame's result comes 40 / 83 us later (gpu_total 242 -> 282 / 325 us) and one frame at a time takes 127 -> 131 / 141 us:
+// profiles/r07y_rowscan_rows_per_workgroup_ab.txt.  Where somebody waits for the frame that is a loss, and Oat is a real-time
+// tracker: kRsRows = 4 is the default and what every single-stage call, the plain order, repairs and the marker table take.
+// Where nobody can -- a step launched with four and more frames ahead of it in the ring, whose results are collected first --
+// the later result costs nothing and the shorter period shortens the ring's latency too: such a step of the early or the
+// paired order takes kRsRowsDeep (plan_step, api_track.hip; profiles/rowscan_deep_rows.txt).
 constexpr int kRsWaves = 4, kRsRows = 4;
+static_assert(kRsRows == kRsRowsNarrow && kRsRowsDeep % kRsWaves == 0, "oatgpu_internal.h names the same heights");
 
 #ifdef OATGPU_RS_TIMING             // measurement builds only (make variant DEFS=-DOATGPU_RS_TIMING, tools/rowscan_probe.py)
 constexpr unsigned kRsTkRing = 1u << 16;
@@ -205,14 +211,14 @@ extern "C" __attribute__((visibility("default"))) int oatgpu_debug_rs_timing(lon
 // workgroup, so the values arrive by scalar loads.  Always the ERODE form: an erosion of size 1 is the identity (a plane
 // without erosion shares the launch with ones that have it; the LDS is sized by the launch's largest dilation), and the
 // mask after erode / dilate is always written to b.morph.
-template <bool ERODE, bool TAB = false>
+template <bool ERODE, bool TAB = false, int ROWS = kRsRows>
 __global__ __launch_bounds__(64 * kRsWaves) void k_rowscan(Geom g, const u64 *src0, const u64 *src1, int ero_k, int dil_k, BlobBuffers b0,
                                                         BlobBuffers b1, int first_stream, int clear_lds_ok, unsigned tag,
                                                         const BlobTab *__restrict__ tab)
 {
     static_assert(ERODE || !TAB, "the table form erodes through LDS (size 1: the identity)");
     extern __shared__ u64 er[];
-    constexpr int WAVES = kRsWaves, ROWS = kRsRows;
+    constexpr int WAVES = kRsWaves;
     const bool second = blockIdx.z != 0;
     const BlobBuffers &b = second ? b1 : b0;
     const u64 *src_all = second ? src1 : src0;
@@ -374,10 +380,36 @@ size_t rowscan_lds_bytes(const Geom &g, int dil_k)
     return (size_t)(kRsRows + (dil_k > 1 ? dil_k : 1) - 1) * g.words * sizeof(u64);
 }
 
-// src / b: nf (1 or 2) frames' source masks and scratch sets
-static void launch_rowscan(const Geom &g, const u64 *const *src, int ero_k, int dil_k, const BlobBuffers *b, int nf, int first_stream,
-                           int n_streams, int clear, hipStream_t st, unsigned tag = 0u)
+// ... and of a row scan of `rows` rows a workgroup (the rule a step must meet to take kRsRowsDeep: plan_step)
+size_t rowscan_lds_bytes_rows(const Geom &g, int dil_k, int rows)
 {
+    return (size_t)(rows + (dil_k > 1 ? dil_k : 1) - 1) * g.words * sizeof(u64);
+}
+
+// the launch at a height other than kRsRows
+template <int ROWS>
+static void launch_rowscan_tall(const Geom &g, const u64 *const *src, int ero_k, int dil_k, const BlobBuffers *b, int nf, int first_stream,
+                                int n_streams, int clear, hipStream_t st, unsigned tag)
+{
+    const int k = nf > 1 ? 1 : 0;
+    const dim3 grid((g.H + ROWS - 1) / ROWS, n_streams, nf), block(64 * kRsWaves);
+    if (ero_k > 1)
+        hipLaunchKernelGGL((k_rowscan<true, false, ROWS>), grid, block, rowscan_lds_bytes_rows(g, dil_k, ROWS), st, g, src[0], src[k], ero_k,
+                           dil_k, b[0], b[k], first_stream, clear, tag, nullptr);
+    else
+        hipLaunchKernelGGL((k_rowscan<false, false, ROWS>), grid, block, 0, st, g, src[0], src[k], 0, dil_k, b[0], b[k], first_stream, clear,
+                           tag, nullptr);
+}
+
+// src / b: nf (1 or 2) frames' source masks and scratch sets; rows: kRsRows, or kRsRowsDeep where the caller has checked
+// rowscan_lds_bytes_rows() against kRowscanLdsMax
+static void launch_rowscan(const Geom &g, const u64 *const *src, int ero_k, int dil_k, const BlobBuffers *b, int nf, int first_stream,
+                           int n_streams, int clear, hipStream_t st, unsigned tag = 0u, int rows = kRsRows)
+{
+    if (rows == kRsRowsDeep) return launch_rowscan_tall<kRsRowsDeep>(g, src, ero_k, dil_k, b, nf, first_stream, n_streams, clear, st, tag);
+#ifdef OATGPU_MEASURE               // the other candidate height of the A/B (OATGPU_RS_DEEP_ROWS, api_context.hip)
+    if (rows == kRsRowsDeepAlt) return launch_rowscan_tall<kRsRowsDeepAlt>(g, src, ero_k, dil_k, b, nf, first_stream, n_streams, clear, st, tag);
+#endif
     const int k = nf > 1 ? 1 : 0;
     const dim3 grid((g.H + kRsRows - 1) / kRsRows, n_streams, nf), block(64 * kRsWaves);
     if (ero_k > 1)
@@ -1264,9 +1296,9 @@ __global__ void k_publish_ticket(unsigned *ready, int first_stream, unsigned tic
     __hip_atomic_store(&ready[first_stream + threadIdx.x], ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 void launch_rowscan_signal(const Geom &g, const BlobBuffers &b, const u64 *src_bits, int ero_k, int dil_k, int first_stream,
-                           int n_streams, unsigned ticket, hipStream_t st)
+                           int n_streams, unsigned ticket, hipStream_t st, int rows)
 {
-    launch_rowscan(g, &src_bits, ero_k, dil_k, &b, 1, first_stream, n_streams, 0, st, ticket);
+    launch_rowscan(g, &src_bits, ero_k, dil_k, &b, 1, first_stream, n_streams, 0, st, ticket, rows);
     for (int s0 = 0; s0 < n_streams; s0 += 1024)
         hipLaunchKernelGGL(k_publish_ticket, dim3(1), dim3(n_streams - s0 < 1024 ? n_streams - s0 : 1024), 0, st, b.ready,
                            first_stream + s0, ticket);
@@ -1275,9 +1307,9 @@ void launch_rowscan_signal(const Geom &g, const BlobBuffers &b, const u64 *src_b
 // The back halves of the TWO frames of a step as two launches instead of four (speculative mode: row scan + the LDS
 // kernel; a declined frame comes back marked kNeedsGlobal): frame i reads src[i] and scratch set b[i], writes results[i].
 void launch_blob_pair(const Geom &g, const BlobBuffers *b, const u64 *const *src, int ero_k, int dil_k, double min_area,
-                      double max_area, ResultRec *const *results, int n_streams, hipStream_t st)
+                      double max_area, ResultRec *const *results, int n_streams, hipStream_t st, int rows)
 {
-    launch_rowscan(g, src, ero_k, dil_k, b, 2, 0, n_streams, 0, st);
+    launch_rowscan(g, src, ero_k, dil_k, b, 2, 0, n_streams, 0, st, 0u, rows);
     hipLaunchKernelGGL(k_blob_lds<false>, dim3(1, n_streams, 2), dim3(kLdsBlock), 0, st, g, b[0], b[1], min_area, max_area, results[0],
                        results[1], 0, 1, 0u, 0u, nullptr);
 }

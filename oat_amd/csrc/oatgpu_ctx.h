@@ -25,7 +25,7 @@
 using namespace oatgpu;
 
 // Measurement switches (OATGPU_A_RESERVE / EARLY_BLOB / EARLY_MIN_PX / LONE_PLAIN / PAIR_BACK / K1_WG /
-// K1_STOP_EVENT, and OATGPU_K1_LDS in kernels_mog.hip) exist only in A/B builds made with -DOATGPU_MEASURE
+// K1_STOP_EVENT / RS_DEEP_ROWS, and OATGPU_K1_LDS in kernels_mog.hip) exist only in A/B builds made with -DOATGPU_MEASURE
 // (`make variant`); each overrides one value of a path the product takes.  The product library never reads
 // them, so nothing in the environment can change what it computes or skip work (tests/test_gpu_parity.py::
 // test_measurement_env_is_inert_in_the_product_library).
@@ -234,6 +234,9 @@ struct oatgpu_ctx {
     bool early_off = false;
     int last_k1_wg = 0;              // what the latest pipelined step used (oatgpu_last_step_shape)
     bool last_step_early = false;
+    int rs_rows_force = 0;           // oatgpu_set_rowscan_rows: 0 by pipeline depth (plan_step), kRsRowsNarrow / kRsRowsDeep on every eligible step
+    int rs_rows_deep = kRsRowsDeep;  // the wide height (measurement builds: OATGPU_RS_DEEP_ROWS = 16 | 32)
+    int last_rs_rows = 0;            // rows a row-scan workgroup of the latest pipelined step (oatgpu_last_step_rowscan_rows)
     int last_early = -1;             // path of the previous step (-1: none yet; 0 plain, 1 early, 2 paired): a switch drains the B streams first
     int lone_plain = 1;              // a frame launched with NOTHING else outstanding (a camera-paced caller) takes the plain order even where the early
                                      // order is the default: no ticket kernel, no parked workgroup to release -- one frame at a time 133.5 -> 129.3 us at
@@ -352,6 +355,7 @@ struct MorphIssued { const u64 *src; int ero; const u64 *tap; };
 struct StepPlan : MorphPlan {  // (the context's erode / dilate: plan_morph)
     bool share_b, early, inline_back, paired, spec_plain;
     int k1_wg;                  // threads a K1 workgroup
+    int rs_rows;                // rows a row-scan workgroup (kRsRowsNarrow, or the wide height on a step deep in the pipeline)
     hipEvent_t k1_done;         // the step's "K1 done" event (nullptr: inline_back, nobody waits for it)
 };
 

@@ -294,6 +294,11 @@ void launch_morph(const Geom &g, const u64 *src, u64 *dst, int k, bool is_erode,
 // results: device-visible (host-mapped) array indexed by stream.
 constexpr size_t kRowscanLdsMax = 64 * 1024;
 size_t rowscan_lds_bytes(const Geom &g, int dil_k);
+// Rows a row-scan workgroup takes where a step is launched deep in the pipeline (kernels_blob.hip "Rows a workgroup"; the default
+// height, kRsRows, stays with the kernel).  A step takes it only if rowscan_lds_bytes_rows(g, dil_k, kRsRowsDeep) <= kRowscanLdsMax.
+constexpr int kRsRowsNarrow = 4, kRsRowsDeep = 16;
+constexpr int kRsRowsDeepAlt = 32;      // (measurement builds: the other height of profiles/rowscan_deep_rows.txt)
+size_t rowscan_lds_bytes_rows(const Geom &g, int dil_k, int rows);
 // mode: kBlobFull  = row scan + k_blob_lds + k_merge + k_green_select (the last two stand down when the LDS
 //                     kernel took the frame);
 //       kBlobSpec  = row scan + k_blob_lds only: a frame too busy for it comes back with valid == kNeedsGlobal and
@@ -309,10 +314,10 @@ void launch_blob(const Geom &g, const BlobBuffers &b, const u64 *src_bits, int e
 // it that publishes `ticket`, and everything behind the row scan, whose k_blob_lds workgroup may be dispatched long before
 // the row scan has run and waits for `ticket` on the device.  ticket != 0.
 void launch_rowscan_signal(const Geom &g, const BlobBuffers &b, const u64 *src_bits, int ero_k, int dil_k, int first_stream,
-                           int n_streams, unsigned ticket, hipStream_t st);
+                           int n_streams, unsigned ticket, hipStream_t st, int rows = kRsRowsNarrow);
 // both frames of a two-frame step: ONE row-scan launch and ONE k_blob_lds launch (speculative mode), lds-able geometries only
 void launch_blob_pair(const Geom &g, const BlobBuffers *b, const u64 *const *src, int ero_k, int dil_k, double min_area,
-                      double max_area, ResultRec *const *results, int n_streams, hipStream_t st);
+                      double max_area, ResultRec *const *results, int n_streams, hipStream_t st, int rows = kRsRowsNarrow);
 // the blob workgroups of the nf (1 or 2) frames of a step in ONE launch (speculative mode): arrays of nf scratch sets,
 // result records and tickets
 void launch_blob_tail2(const Geom &g, const BlobBuffers *b, double min_area, double max_area, ResultRec *const *results,

@@ -158,6 +158,8 @@ SIGNATURES = {
     "oatgpu_early_blob_timeouts": (C.c_int64, [_ctx]),
     "oatgpu_set_k1_workgroup": (C.c_int, [_ctx, C.c_int32]),
     "oatgpu_last_step_shape": (C.c_int, [_ctx, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "oatgpu_set_rowscan_rows": (C.c_int, [_ctx, C.c_int32]),
+    "oatgpu_last_step_rowscan_rows": (C.c_int, [_ctx]),
     "oatgpu_set_homography": (C.c_int, [_ctx, C.c_int32, C.POINTER(C.c_double)]),
     "oatgpu_detect_hsv": (C.c_int, [_ctx, C.c_int32, _u8p, C.POINTER(Position)]),
     "oatgpu_detect_thresh": (C.c_int, [_ctx, C.c_int32, _u8p, C.POINTER(Position)]),
