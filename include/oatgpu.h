@@ -579,6 +579,43 @@ int oatgpu_set_tracker_filters(oatgpu_ctx *ctx, const oatgpu_marker_filters *f);
  * be repeated.  The chain advances for every frame whether or not this is called. */
 int oatgpu_tracker_filtered(oatgpu_ctx *ctx, oatgpu_filtered *out, int32_t max_sets);
 
+/* ---- multi-target detection: the K largest blobs of every camera, ranked ----
+ * Every detector publishes one object a camera: the largest contour inside the area window.  With targets on, every call that
+ * delivers a foreground result -- oatgpu_track_batch[_dev], oatgpu_track_enqueue* / _collect, oatgpu_track_stage /
+ * _enqueue_staged, the three oatgpu_track_sequence_dev calls, oatgpu_detect_hsv / _thresh / _diff, and the batch and sequence
+ * calls of the motion and the subtraction tracker -- also ranks the K best candidates of every camera and frame.
+ *
+ * For one camera and one frame, on the mask after erode / dilate and the one-pixel frame zeroing:
+ *   candidates  its external contours with m00 > 0 and min_area <= m00 < max_area -- the contours the ordinary selection
+ *               considers; a blob inside another blob's hole is not one;
+ *   ranking     area descending; among equal areas the LATER first pixel in raster order comes first (the rule by which the
+ *               ordinary selection picks its winner);
+ *   rank 0      is therefore bit for bit the ordinary result (before oatgpu_set_kalman / oatgpu_set_homography);
+ *   rank j      is invalid (valid = 0, first_pixel = -1) when fewer than j + 1 candidates exist;
+ *   n_found     is the number of candidates and may exceed K.
+ * Ranks carry no identity from frame to frame.  Targets are raw detections: oatgpu_set_kalman, oatgpu_set_homography and both
+ * filter chains keep acting on the ordinary result only.  The ordinary results, the taps, the models and every state are bit
+ * for bit what they are with targets off.
+ *
+ * Cost: a step with targets on takes the global blob kernels -- not the single-workgroup LDS kernel -- with one small ranking
+ * kernel (k_blob_rank) behind them, and the fused tracker launches it in the plain order: no early dispatch, no paired back
+ * half (oatgpu_last_step_shape reports early_blob 0).  With targets off every call does exactly what it did before.
+ *
+ * oatgpu_set_targets(k): 0 switches targets off (the default), 1..OATGPU_MAX_TARGETS on.  Drains outstanding work.  Everything
+ * is allocated here, never in a step -- a target set for every ring slot and the synchronous detectors' extra slot, and for the
+ * four slots of each batched tracker that is on (one switched on later allocates its own): an out-of-memory is OATGPU_E_NOMEM
+ * from this call and leaves a working context.  OATGPU_E_INVALID, with nothing changed, when k is out of range, results are
+ * outstanding or a frame set is partly staged, oatgpu_set_deferred is on, or marker sets are configured;
+ * oatgpu_set_markers(n > 0) and oatgpu_set_deferred(1) are refused while targets are on. */
+#define OATGPU_MAX_TARGETS 8
+int oatgpu_set_targets(oatgpu_ctx *ctx, int32_t k);          /* 0: off (default) */
+/* The target sets of the frame sets the LATEST result-delivering call handed out: one set for a batch call, a collect or a
+ * single-stage detector, n_frames sets for a sequence call.  out[(t * n_streams + s) * K + j] is rank j of camera s of set t,
+ * n_found[t * n_streams + s] its candidate count.  A single-stage detector analyses one stream: the other streams of its set
+ * come back invalid with n_found 0.  Returns the number of sets written; nothing is consumed.  OATGPU_E_INVALID when targets
+ * are off, no such call has run since oatgpu_set_targets, or max_sets is too small. */
+int oatgpu_targets(oatgpu_ctx *ctx, oatgpu_position *out, int32_t *n_found, int32_t max_sets);
+
 /* Deferred completion of the stage-by-stage operators below (default off).  With on = 1 a frame filter (oatgpu_mog_filter,
  * _bsub_filter, _mask_filter, _thresh_filter, _undistort_filter, _bgr2hsv, _cvt_color) or a detector (oatgpu_detect_hsv / _thresh / _diff)
  * returns as soon as its INPUT frame has been read -- the point where the reference posts its SOURCE, right after its

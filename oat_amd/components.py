@@ -14,6 +14,7 @@ All pixel work happens in liboatgpu.so on the GPU.
 """
 import ctypes as C
 import os
+import re
 from dataclasses import dataclass
 
 import numpy as np
@@ -382,6 +383,35 @@ class _Detector(_Context):
             setattr(c, k, v)
         self._chk(self.lib.oatgpu_set_detector(self.ctx, c.h_lo, c.h_hi, c.s_lo, c.s_hi, c.v_lo, c.v_hi,
                                                c.erode, c.dilate, c.min_area, c.max_area))
+
+    # -- multi-target detection (oatgpu_set_targets / oatgpu_targets) --
+    def set_targets(self, k):
+        """The k largest blobs of every camera, ranked, beside the ordinary result of every detecting call; 0 switches it off
+        (the default), at most ffi.MAX_TARGETS.  A step with targets on takes the global blob kernels and, in HotPath, the plain
+        launch order."""
+        self._chk(self.lib.oatgpu_set_targets(self.ctx, int(k)))
+        self._targets_k = int(k)
+
+    def targets(self):
+        """oatgpu_targets: the target sets of the frame sets the latest result-delivering call handed out -- a list with one
+        entry per frame set (one for a track / collect / detectPosition call, one per frame for a sequence call), each a list
+        with one (ranks, n_found) pair per camera: ranks is k Position2D, area descending, ties to the later first pixel, rank
+        0 the ordinary result, invalid where fewer candidates exist; n_found is the number of candidates (it may exceed k).
+        Nothing is consumed."""
+        n, k, sets = self.n_streams, getattr(self, "_targets_k", 0), 1
+        while True:
+            out = (ffi.Position * (sets * n * max(k, 1)))()
+            found = (C.c_int32 * (sets * n))()
+            rc = self.lib.oatgpu_targets(self.ctx, out, found, sets)
+            if rc >= 0:
+                break
+            text = (self.lib.oatgpu_last_error(self.ctx) or b"").decode()
+            m = re.search(r"the latest call delivered (\d+)", text)
+            if not m or int(m.group(1)) <= sets:
+                self._chk(rc)
+            sets = int(m.group(1))           # a sequence call delivered more sets than there was room for
+        return [[([Position2D.from_c(out[(t * n + s) * k + j]) for j in range(k)], int(found[t * n + s])) for s in range(n)]
+                for t in range(rc)]
 
 
 class HSVDetector(_Detector):

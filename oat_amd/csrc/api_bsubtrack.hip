@@ -61,10 +61,11 @@ static int bsub_back(oatgpu_ctx *c, int slot, hipStream_t st, int prev_slot = -1
     const MorphPlan mp = plan_morph(g, c->cfg.erode, c->cfg.dilate);
     const MorphIssued m = issue_morph(g, mp, bb, c->bs.bits_of(slot), 0, n, st);
     ResultRec *rd = c->bs.rec_dev(slot);
-    launch_blob(g, bb, m.src, m.ero, mp.dil, c->cfg.min_area, c->cfg.max_area, rd, 0, n, st, kBlobFull);
+    launch_blob(g, bb, m.src, m.ero, mp.dil, c->cfg.min_area, c->cfg.max_area, rd, 0, n, st, c->tg.k ? kBlobGlobal : kBlobFull);
     HIPCHK(c, hipGetLastError());
     c->bs.last = slot;
     c->bs.last_tap = m.tap;
+    { const int rc = targets_launch(c, bb, c->bs.tgt, slot, 0, n, st); if (rc) return rc; }
     return tracker_filters_launch(c, rd, slot, prev_slot, st);
 }
 
@@ -72,6 +73,7 @@ static int bsub_back(oatgpu_ctx *c, int slot, hipStream_t st, int prev_slot = -1
 static int bsub_step(oatgpu_ctx *c, const void *frames_dev, double alpha, oatgpu_position *out)
 {
     chain_begin(c->tf);
+    targets_begin(c);
     int rc = bsub_front(c, frames_dev, nullptr, alpha, 0, 0);
     if (rc) return rc;
     rc = bsub_back(c, 0, c->stream);
@@ -122,6 +124,7 @@ extern "C" int oatgpu_bsub_track_sequence_dev(oatgpu_ctx *c, const void *const *
     const int n = c->cfg.n_streams;
     int prev = -1;                         // slot of the frame before (the filter chain's order)
     chain_begin(c->tf);
+    targets_begin(c);
     return run_sequence_in_flight(
         c, n_frames, c->bs.ev_front, c->bs.ev_done, [&](int t) { return t + 1 < n_frames ? 2 : 1; },
         [&](int t, int nf, int q, int q2) { return bsub_front(c, frames_dev[t], nf == 2 ? frames_dev[t + 1] : nullptr, alpha, q, q2); },

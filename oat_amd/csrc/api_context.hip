@@ -516,6 +516,7 @@ extern "C" int oatgpu_set_deferred(oatgpu_ctx *c, int32_t on)
 {
     if (!c) return OATGPU_E_INVALID;
     if (c->defer_kind) return fail(c, OATGPU_E_INVALID, "a deferred result is waiting: fetch it first");
+    if (on && c->tg.k) return fail(c, OATGPU_E_INVALID, "set_deferred with targets on (oatgpu_set_targets) is not supported");
     c->deferred = on != 0;
     return OATGPU_OK;
 }

@@ -38,7 +38,8 @@ static int diff_front(oatgpu_ctx *c, const void *f1, const void *f2, int slot, i
 // The back half of the frame in `slot` on stream st: once for each maximal run of consecutive streams in the same first-frame
 // state (have[s] != 0: blur as dilation; 0: the first frame is analysed as it is), erode never.  Touches neither last_slot nor
 // last_morph / last_fin: those stay with the ordinary calls.  Behind it the filter chain on the slot's records, where one is
-// configured (prev_slot: tracker_filters_launch).
+// configured (prev_slot: tracker_filters_launch).  With targets on every run takes the global route and ONE k_blob_rank launch
+// behind the last of them ranks all streams into the slot's target set.
 static int diff_back(oatgpu_ctx *c, int slot, const char *have, hipStream_t st, int prev_slot = -1)
 {
     const Geom &g = c->g;
@@ -52,12 +53,13 @@ static int diff_back(oatgpu_ctx *c, int slot, const char *have, hipStream_t st, 
         int s1 = s0 + 1;
         while (s1 < n && (have[s1] != 0) == (have[s0] != 0)) ++s1;
         const MorphPlan mp = plan_morph(g, 0, have[s0] ? c->cfg.blur : 0);
-        launch_blob(g, bb, src, 0, mp.dil, c->cfg.min_area, c->cfg.max_area, rd, s0, s1 - s0, st, kBlobFull);
+        launch_blob(g, bb, src, 0, mp.dil, c->cfg.min_area, c->cfg.max_area, rd, s0, s1 - s0, st, c->tg.k ? kBlobGlobal : kBlobFull);
         for (int s = s0; s < s1; ++s) c->df.last_dilated[(size_t)s] = mp.dil != 0;
         s0 = s1;
     }
     HIPCHK(c, hipGetLastError());
     c->df.last = slot;
+    { const int rc = targets_launch(c, bb, c->df.tgt, slot, 0, n, st); if (rc) return rc; }      // (every stream's roots and sums are still in the set)
     return tracker_filters_launch(c, rd, slot, prev_slot, st);
 }
 
@@ -66,6 +68,7 @@ static int diff_step(oatgpu_ctx *c, const void *frames_dev, oatgpu_position *out
 {
     const std::vector<char> have = c->diff_have;
     chain_begin(c->tf);
+    targets_begin(c);
     int rc = diff_front(c, frames_dev, nullptr, 0, 0);
     if (rc) return rc;
     c->diff_have.assign(have.size(), 1);
@@ -117,6 +120,7 @@ extern "C" int oatgpu_diff_sequence_dev(oatgpu_ctx *c, const void *const *frames
     std::vector<char> have;                // the state the launch's first frame met
     int prev = -1;                         // slot of the frame before (the filter chain's order)
     chain_begin(c->tf);
+    targets_begin(c);
     return run_sequence_in_flight(
         c, n_frames, c->df.ev_front, c->df.ev_done,
         [&](int t) {

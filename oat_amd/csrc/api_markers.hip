@@ -18,6 +18,7 @@ extern "C" int oatgpu_set_markers(oatgpu_ctx *c, int32_t n_markers, const oatgpu
     if (n_markers > 0 && (heading_anchor < -1 || heading_anchor >= n_markers))      // MeanPosition.cpp:55-57
         return fail(c, OATGPU_E_INVALID, "heading anchor %d out of range: -1 (none) or a marker index below %d", heading_anchor, n_markers);
     for (int m = 0; m < n_markers; ++m) { const int rc = check_detector(c, defaults[m]); if (rc) return rc; }
+    if (n_markers > 0 && c->tg.k) return fail(c, OATGPU_E_INVALID, "set_markers with targets on (oatgpu_set_targets) is not supported");
     if (c->mkp.on)       // (its planes, scratch and records are sized by M: refused, like everything that would pull them from under it)
         return fail(c, OATGPU_E_INVALID, "the marker pipeline is on: oatgpu_set_marker_pipeline(0) before the marker set changes");
     int rc = open_sync(c);

@@ -515,6 +515,8 @@ static int detect_tail(oatgpu_ctx *c, int s, int erode_k, int dilate_k, oatgpu_p
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     to_position(c->res.host()[(size_t)slot * c->cfg.n_streams + s], out);
+    targets_begin(c);
+    targets_keep(c, c->tg.ring, slot, s);
     return OATGPU_OK;
 }
 

@@ -119,7 +119,8 @@ MorphIssued issue_morph(const Geom &g, const MorphPlan &m, const BlobBuffers &bb
 }
 
 // erode -> (dilate fused into the row scan) -> blob for camera streams [s0, s0+n), reading
-// the threshold bits `thr`; results land in host-mapped slot `slot`.  All on HIP stream st.
+// the threshold bits `thr`; results land in host-mapped slot `slot` (with targets on: and the ranked blobs in the slot's target
+// set).  All on HIP stream st.
 int back_half(oatgpu_ctx *c, BlobBuffers &bb, const u64 *thr, int s0, int n, int slot, hipStream_t st,
               hipEvent_t ev_mid, int erode_k, int dilate_k, int mode)
 {
@@ -132,9 +133,10 @@ int back_half(oatgpu_ctx *c, BlobBuffers &bb, const u64 *thr, int s0, int n, int
     c->last_morph = m.tap;
     c->last_fin = bb.fin;
     ResultRec *rd = c->res.dev() + (size_t)slot * c->cfg.n_streams;
-    launch_blob(g, bb, m.src, m.ero, mp.dil, c->cfg.min_area, c->cfg.max_area, rd, s0, n, st, mode);
+    // targets on (oatgpu_set_targets): the global route, whose root list and sums k_blob_rank then ranks into the slot's target set
+    launch_blob(g, bb, m.src, m.ero, mp.dil, c->cfg.min_area, c->cfg.max_area, rd, s0, n, st, c->tg.k ? kBlobGlobal : mode);
     HIPCHK(c, hipGetLastError());
-    return OATGPU_OK;
+    return targets_launch(c, bb, c->tg.ring, slot, s0, n, st);
 }
 
 static int enqueue_frames(oatgpu_ctx *c, const void *frames_dev, double lr, hipEvent_t frames_ready);
@@ -325,7 +327,7 @@ static StepPlan plan_step(const oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, in
     // ... and not with the marker pipeline on: its back halves go down B2, where the parked workgroups sit, and nothing may
     // be queued on B2 in front of a row scan they wait for -- marker steps take the paired or the plain order
     p.early = early_wanted && !(lone && c->lone_plain) && !c->early_off && c->lds_spec && !c->kal_on && !j[0].ready && !p.share_b &&
-              lds_geom && step_px >= c->early_min_px && !c->mkp.on;
+              lds_geom && step_px >= c->early_min_px && !c->mkp.on && !c->tg.k;
     // Threads a K1 workgroup (kernels_mog.hip, k_mog_fused): one wave a workgroup keeps every wave slot filled (K1 -3.5 % on
     // an everyday 4K model, -5.5 % on a dense one) and starves the back half's workgroups of slots.  Taken where that
     // does not come back as a lower frame rate: steps whose blob workgroup is already resident (early), and dense models
@@ -349,6 +351,9 @@ static StepPlan plan_step(const oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, in
     p.paired = nj == 2 && !p.early && c->pair_back && c->lds_spec && !c->kal_on && lds_geom && !p.ero_apart;
     // the plain order, speculative (row scan + LDS kernel alone) unless the position filter is on or a frame was declined
     p.spec_plain = !p.early && !p.paired && c->lds_spec && !c->kal_on;
+    // targets on (oatgpu_set_targets): every frame takes back_half's global route with k_blob_rank behind it -- the plain order,
+    // nothing paired, nothing speculative (and not early: above)
+    if (c->tg.k) p.paired = p.spec_plain = false;
     // Rows a row-scan workgroup (kernels_blob.hip "Rows a workgroup").  The wide form takes fewer wave slots from the per-pixel
     // kernel beside it and delivers the frame later: up to ~85 us at 4K, ~28 us at 1080p (profiles/r07y_rowscan_rows_per_workgroup_ab.txt).
     // A step is DEEP when kDeepAhead frames launched earlier are still uncollected: results are collected in order, so nobody can
@@ -781,7 +786,7 @@ static int collect_frame(oatgpu_ctx *c, oatgpu_position *out, oatgpu_position *m
     if (c->slots[slot].repair) {                            // (launched here, by oatgpu_track_ready or by a quiesce())
         HIPCHK(c, hipEventSynchronize(c->ring_ev[slot]));
         c->slots[slot].repair = false;
-    } else {
+    } else if (!c->tg.k) {                                   // (a targets step took the global route by rule, not because a frame was busy)
         constexpr int kSpecAfter = 16;
         bool all_lds = true;
         for (int s = 0; s < c->cfg.n_streams; ++s) if (r[s].path != 1) all_lds = false;
@@ -805,6 +810,10 @@ static int collect_frame(oatgpu_ctx *c, oatgpu_position *out, oatgpu_position *m
             chain_keep(c, c->mf, (const MarkerFiltered *)((const MarkerCombined *)(mr + (size_t)M * n) + n));
         }
         c->mkp.last_slot = slot;
+    }
+    if (c->tg.k) {                           // what oatgpu_targets hands out -- this set, or one more of oatgpu_track_sequence_dev's
+        if (!c->tg.append) targets_begin(c);
+        targets_keep(c, c->tg.ring, slot);
     }
     for (int s = 0; out && s < c->cfg.n_streams; ++s) {
         to_position(r[s], &out[s]);
@@ -904,6 +913,8 @@ static int sequence_dev(oatgpu_ctx *c, const void *const *frames_dev, int32_t n_
         return r;
     };
     c->in_sequence = true;               // every frame of the sequence is in hand: pairing is safe (oatgpu_set_fusion)
+    c->tg.append = true;                 // oatgpu_targets: the n_frames sets of this call
+    targets_begin(c);
     for (int t = 0; t < n_frames && !rc; ++t) {
         if (c->ring_count == c->cfg.ring_depth) rc = collect_one();
         if (!rc && enq_s) enq_s[t] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -911,6 +922,7 @@ static int sequence_dev(oatgpu_ctx *c, const void *const *frames_dev, int32_t n_
     }
     c->in_sequence = false;
     while (!rc && c->ring_count) rc = collect_one();
+    c->tg.append = false;
     c->dev_unconsumed = false;           // all collected: every frame was read
     return rc;
 }

@@ -17,6 +17,7 @@ bool BatchedTrackerState::alloc(const oatgpu_ctx *c)
     bool ok = bits.alloc(K * words * 8) == hipSuccess;
     ok = ok && masks.alloc(K * planes * words * 8) == hipSuccess;
     ok = ok && rec.alloc(K * n * sizeof(ResultRec), hipHostMallocMapped) == hipSuccess;
+    ok = ok && (!c->tg.k || tgt.alloc(K, n, c->tg.k));
     // (the taps: words beyond the frame are never written by the back half)
     ok = ok && hipMemsetAsync(bits, 0, K * words * 8, c->stream) == hipSuccess;
     ok = ok && hipMemsetAsync(masks, 0, K * planes * words * 8, c->stream) == hipSuccess;
@@ -86,11 +87,12 @@ int reset_have(oatgpu_ctx *c, std::vector<char> &have, int s)
     return OATGPU_OK;
 }
 
-// the finished frame in `slot` to the caller: its records as positions, its filtered set into the call's
+// the finished frame in `slot` to the caller: its records as positions, its filtered set and its target set into the call's
 void tracker_hand_out(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, oatgpu_position *out)
 {
     for (size_t s = 0; s < bt.n; ++s) to_position(bt.rec.host()[(size_t)slot * bt.n + s], out + s);
     if (c->tf.on) chain_keep(c, c->tf, c->tf.out.host() + (size_t)slot * bt.n);
+    targets_keep(c, bt.tgt, slot);
 }
 
 // --- the trackers' launch of the filter chain ---

@@ -1346,4 +1346,116 @@ void launch_blob_table(const Geom &g, const BlobBuffers *b, const u64 *const *sr
     }
 }
 
+// ------------------------------------------------------------ multi-target: the K largest blobs, ranked ----
+// k_blob_rank runs on the HIP stream of a kBlobGlobal back half, directly behind it, on the same scratch set: k_green_select
+// has left the first pixel of every foreground root in roots[0 .. nroots) and the Green sums of every one of them in acc
+// (both stay until the set's next row scan), and has handed out only the maximum.  One workgroup a stream.
+//   Candidates: roots with a00 != 0 (a blob inside another blob's hole never faces the outside background: its sums stay 0)
+//     and min_area <= |a00| / 2 < max_area -- k_green_select's test, word for word.
+//   Ranking: key = |a00| << 32 | first pixel (padded index: raster order), larger first -- the selection's own key, so rank 0
+//     is bit for bit the step's ordinary record and ties go to the later first pixel.
+//   One pass over the root list: every lane keeps the KC largest keys it has met, sorted, in registers (insertion by a
+//     compare-exchange chain with constant indices).  Then k rounds of a workgroup maximum (wave shuffle, one LDS word a wave):
+//     the lane whose head won pops it.  Keys are distinct (the first pixel is), so exactly one lane pops a round.  The order of
+//     the root list differs from run to run; the ranking does not depend on it.
+//   Output: k records a stream and the candidate count (which may exceed k), by 64-bit stores -- the target set
+//     may be host-mapped memory.
+constexpr int kRankBlock = 256;
+template <int KC>
+__global__ __launch_bounds__(kRankBlock) void k_blob_rank(Geom g, BlobBuffers b, double min_area, double max_area, int k,
+                                                          TargetRec *__restrict__ recs, long long *__restrict__ found, int first_stream)
+{
+    static_assert(KC >= 1 && KC <= kMaxTargets, "a lane keeps at most kMaxTargets keys");
+    __shared__ u64 red[kRankBlock / 64];
+    __shared__ u64 win[kMaxTargets];
+    __shared__ unsigned cnt[kRankBlock / 64];
+    const int s = first_stream + blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long *acc = b.acc + (size_t)s * g.Palloc * 3;
+    const int *roots = b.roots + (size_t)s * (g.Palloc >> 1);
+    const unsigned nr = b.nroots[s];
+
+    u64 top[KC];
+#pragma unroll
+    for (int i = 0; i < KC; ++i) top[i] = 0ull;
+    unsigned mine = 0;
+    for (unsigned i = threadIdx.x; i < nr; i += kRankBlock) {
+        const int h = roots[i];
+        const long long a00 = acc[(size_t)h * 3];
+        if (a00 == 0) continue;
+        const u64 mag = (u64)(a00 < 0 ? -a00 : a00);
+        const double area = (double)mag * 0.5;            // m00 = a00 * (+-0.5), exact
+        if (!(area >= min_area && area < max_area)) continue;
+        ++mine;
+        u64 v = (mag << 32) | (u64)(unsigned)h;
+#pragma unroll
+        for (int q = 0; q < KC; ++q) {                    // top[] stays sorted, v leaves as the smallest of the KC + 1
+            const u64 t = top[q];
+            const bool up = v > t;
+            top[q] = up ? v : t;
+            v = up ? t : v;
+        }
+    }
+    // the candidate count
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
+    if (lane == 0) cnt[wave] = mine;
+
+    for (int j = 0; j < k; ++j) {
+        u64 best = top[0];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const u64 v = __shfl_xor(best, o);
+            best = v > best ? v : best;
+        }
+        if (lane == 0) red[wave] = best;
+        __syncthreads();
+        u64 key = red[0];
+#pragma unroll
+        for (int w = 1; w < kRankBlock / 64; ++w) key = red[w] > key ? red[w] : key;
+        if (key != 0ull && top[0] == key) {
+#pragma unroll
+            for (int q = 0; q + 1 < KC; ++q) top[q] = top[q + 1];
+            top[KC - 1] = 0ull;
+        }
+        if (threadIdx.x == 0) win[j] = key;
+        __syncthreads();                                   // red[] is free for the next round, win[j] is visible
+    }
+    if (k == 0) __syncthreads();                           // cnt[]
+
+    if ((int)threadIdx.x < k) {
+        const u64 key = win[threadIdx.x];
+        long long a00 = 0, a10 = 0, a01 = 0;
+        int first_pixel = -1, valid = 0;
+        if (key) {
+            const int h = (int)(key & 0xffffffffull);
+            a00 = acc[(size_t)h * 3]; a10 = acc[(size_t)h * 3 + 1]; a01 = acc[(size_t)h * 3 + 2];
+            const int yy = h / g.Wp, xx = h - yy * g.Wp;
+            first_pixel = yy * g.W + xx;
+            valid = 1;
+        }
+        static_assert(sizeof(TargetRec) == 32, "a target record is four 64-bit words");
+        u64 *o = reinterpret_cast<u64 *>(recs + (size_t)s * k + threadIdx.x);
+        auto put = [&](int i, u64 v) { __hip_atomic_store(o + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+        put(0, (u64)a00);
+        put(1, (u64)a10);
+        put(2, (u64)a01);
+        put(3, (u64)(unsigned)first_pixel | (u64)(unsigned)valid << 32);
+    }
+    if (threadIdx.x == 0) {
+        unsigned total = 0;
+        for (int w = 0; w < kRankBlock / 64; ++w) total += cnt[w];
+        __hip_atomic_store(found + s, (long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+void launch_blob_rank(const Geom &g, const BlobBuffers &b, double min_area, double max_area, int k, TargetRec *recs,
+                      long long *found, int first_stream, int n_streams, hipStream_t st)
+{
+    const dim3 grid(1, n_streams), block(kRankBlock);
+    if (k <= 1) hipLaunchKernelGGL(k_blob_rank<1>, grid, block, 0, st, g, b, min_area, max_area, k, recs, found, first_stream);
+    else if (k <= 4) hipLaunchKernelGGL(k_blob_rank<4>, grid, block, 0, st, g, b, min_area, max_area, k, recs, found, first_stream);
+    else hipLaunchKernelGGL(k_blob_rank<kMaxTargets>, grid, block, 0, st, g, b, min_area, max_area, k, recs, found, first_stream);
+}
+
 }  // namespace oatgpu

@@ -117,6 +117,27 @@ struct MarkerFilters : PosfiltChain {
     bool append = false;                       // inside oatgpu_track_markers_sequence_dev: every collected set is kept
 };
 
+// Multi-target detection (oatgpu_set_targets; api_targets.hip).  A target set is what k_blob_rank writes for one
+// frame set: [n][k] TargetRec, then [n] candidate counts.  TargetSets owns one for each slot of a result ring, host-mapped;
+// everything is made by oatgpu_set_targets (or by a batched tracker switched on while targets are on), never inside a step.
+struct TargetSets {
+    HostMem<char> mem;
+    size_t n = 0, k = 0, set_bytes = 0;
+    bool alloc(size_t slots, size_t n_streams, int k_);        // false: hipGetLastError() has the reason
+    TargetRec *rec_dev(int slot) const { return (TargetRec *)(mem.dev() + (size_t)slot * set_bytes); }
+    long long *found_dev(int slot) const { return (long long *)(rec_dev(slot) + n * k); }
+    const TargetRec *rec_host(int slot) const { return (const TargetRec *)(mem.host() + (size_t)slot * set_bytes); }
+    const long long *found_host(int slot) const { return (const long long *)(rec_host(slot) + n * k); }
+};
+struct Targets {
+    int k = 0;                                 // K; 0: targets off
+    TargetSets ring;                           // [ring_slots + 1] beside oatgpu_ctx::res: the ring's slots and the synchronous detectors' extra one
+    std::vector<oatgpu_position> last;         // [sets][n][k] what the latest delivering call delivered (oatgpu_targets)
+    std::vector<int32_t> last_found;           // [sets][n]
+    int last_sets = 0;
+    bool append = false;                       // inside oatgpu_track_sequence_dev: every collected set is kept
+};
+
 // frames a batched tracker has in flight inside its sequence call (run_sequence_in_flight); each sits in a slot of its own
 constexpr int kSeqSlots = 4;
 
@@ -133,6 +154,7 @@ struct BatchedTrackerState {
     DevMem<u64> bits;                          // [kSeqSlots][n][Palloc/64] the front kernel's threshold words
     DevMem<u64> masks;                         // [kSeqSlots][planes][n][Palloc/64] the slot's planes (the taps)
     HostMem<ResultRec> rec;                    // host-mapped: [kSeqSlots][n] result records, written by the blob kernels through dev()
+    TargetSets tgt;                            // [kSeqSlots] target sets beside rec, while targets are on (oatgpu_set_targets)
     Event ev_front[kSeqSlots];                 // stream A: the front launch that wrote this slot's bits has finished
     Event ev_done[kSeqSlots];                  // the slot's back half has finished
     int last = -1;                             // slot of the tracker's latest frame (oatgpu_read_*_mask); -1: none yet
@@ -342,6 +364,7 @@ struct oatgpu_ctx {
     DiffTracker df;
     BsubTracker bs;
     TrackerFilters tf;
+    Targets tg;
 };
 
 // a back half's erosion and dilation, planned and issued (plan_morph, issue_morph: api_track.hip)
@@ -418,6 +441,12 @@ int check_sequence_dev(oatgpu_ctx *c, const void *const *frames_dev, int n_frame
 int open_tap(oatgpu_ctx *c, const BatchedTrackerState &bt, const char *name, const char *none_yet, int s, int which, const uint8_t *out);
 int reset_have(oatgpu_ctx *c, std::vector<char> &have, int s);
 void tracker_hand_out(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, oatgpu_position *out);
+// api_targets.hip: k_blob_rank behind a kBlobGlobal back half of scratch set bb on st, for streams [s0, s0 + n), into `slot` of ts;
+// the list a delivering call keeps (targets_begin where it starts to deliver, targets_keep for every set; only: the one stream a
+// single-stage detector analysed, -1: all) -- both do nothing while targets are off
+int targets_launch(oatgpu_ctx *c, const BlobBuffers &bb, const TargetSets &ts, int slot, int s0, int n, hipStream_t st);
+void targets_begin(oatgpu_ctx *c);
+void targets_keep(oatgpu_ctx *c, const TargetSets &ts, int slot, int only = -1);
 // api_measure.hip
 void prof_fold(oatgpu_ctx *c);
 #pragma GCC visibility pop

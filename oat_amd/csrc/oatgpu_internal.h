@@ -332,6 +332,19 @@ struct BlobTab {
 void launch_blob_table(const Geom &g, const BlobBuffers *b, const u64 *const *src, const BlobTab *tab, int max_dil,
                        ResultRec *const *results, int n_planes, int nf, hipStream_t st);
 
+// Multi-target detection (oatgpu_set_targets; kernels_blob.hip, k_blob_rank): the k largest candidates of every
+// stream, ranked, out of what a kBlobGlobal back half has left in its scratch set b -- launched on the same HIP stream directly
+// behind launch_blob(..., kBlobGlobal) or k_green_select's other launchers, before the set's next row scan.  recs[n][k]
+// (stream first_stream + i at recs + (first_stream + i) * k) and found[n] may be host-mapped memory: 64-bit stores.  1 <= k <= kMaxTargets.
+constexpr int kMaxTargets = 8;
+struct TargetRec {   // one ranked blob: ResultRec's first four fields
+    long long a00, a10, a01;
+    int first_pixel;
+    int valid;
+};
+void launch_blob_rank(const Geom &g, const BlobBuffers &b, double min_area, double max_area, int k, TargetRec *recs,
+                      long long *found, int first_stream, int n_streams, hipStream_t st);
+
 // --- kernels_markers.hip --- (marker sets: M colour windows per camera behind one MOG2 pass, `posicom mean`)
 constexpr int kMaxMarkers = 8;
 struct MarkerCombined {   // device-side record of k_marker_combine, one per stream per step: oatgpu_combined's layout

@@ -89,6 +89,7 @@ class Filtered(C.Structure):
 E_RING_FULL = -4
 E_RING_EMPTY = -5
 ABI_VERSION = 9          # must equal OATGPU_ABI_VERSION of include/oatgpu.h
+MAX_TARGETS = 8          # OATGPU_MAX_TARGETS
 TAP_THRESHOLD, TAP_MORPH, TAP_FINAL = 0, 1, 2
 BAYER_RGGB, BAYER_BGGR, BAYER_GRBG, BAYER_GBRG = 1, 2, 3, 4      # OATGPU_BAYER_*: the tile at rows 0-1, columns 0-1
 
@@ -146,6 +147,8 @@ SIGNATURES = {
     "oatgpu_marker_filtered": (C.c_int, [_ctx, C.POINTER(Filtered), C.c_int32]),
     "oatgpu_set_tracker_filters": (C.c_int, [_ctx, C.POINTER(MarkerFilters)]),
     "oatgpu_tracker_filtered": (C.c_int, [_ctx, C.POINTER(Filtered), C.c_int32]),
+    "oatgpu_set_targets": (C.c_int, [_ctx, C.c_int32]),
+    "oatgpu_targets": (C.c_int, [_ctx, C.POINTER(Position), C.POINTER(C.c_int32), C.c_int32]),
     "oatgpu_mog_apply": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_mog_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_bgr2hsv": (C.c_int, [_ctx, _u8p, _u8p]),

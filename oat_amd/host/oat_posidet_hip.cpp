@@ -14,9 +14,13 @@
 //                 kalman` -> `oat posifilt homography` -> `oat posifilt region` behind the detector, on the device in the same step
 //                 (oatgpu_set_tracker_filters): the SINK carries the filtered Position2D; a plain `diff` then runs the motion
 //                 tracker on its GREY source
+//                 every TYPE and form with --target-sinks T0,T1,..: the K largest blobs of the frame, ranked (oatgpu_set_targets):
+//                 sink j receives rank j as a Position2D with the frame's Sample on every frame, invalid where the rank is empty;
+//                 the SINK carries what it carries without the option
 // Same positional arguments and option names as src/positiondetector/main.cpp:85-271.
 #include "component.hpp"
 #include "filter_chain.hpp"
+#include "target_sinks.hpp"
 
 #include <cfloat>
 
@@ -54,8 +58,46 @@ public:
     double homography_[9]{1, 0, 0, 0, 1, 0, 0, 0, 1};
     std::vector<RegionDef> regions_;
     bool chain_on() const { return kalman_ || homography_on_ || !regions_.empty(); }
+    std::vector<std::string> target_sink_addresses_;     // --target-sinks: rank j of every frame on the j-th address
 
 protected:
+    // (a detector that fails while connecting still binds its target sinks, so that its destructor sets them END)
+    bool connectToNode() override
+    {
+        try {
+            return PositionDetector::connectToNode();
+        } catch (...) {
+            bind_target_sinks(false);
+            throw;
+        }
+    }
+    void bind_target_sinks(bool loud)
+    {
+        if (target_sinks_.empty()) target_sinks_ = std::vector<Sink<Position2D>>(target_sink_addresses_.size());
+        for (size_t j = target_shared_.size(); j < target_sinks_.size(); ++j) {
+            try {
+                target_sinks_[j].bind(target_sink_addresses_[j], target_sink_addresses_[j]);
+                target_shared_.push_back(target_sinks_[j].retrieve());
+            } catch (...) {
+                if (loud) throw;
+                return;
+            }
+        }
+    }
+    // the frame's ranks to their sinks, every one with the frame's Sample
+    void publish_targets(const Position2D &position)
+    {
+        const size_t K = target_sink_addresses_.size();
+        if (!K) return;
+        oatgpu_position ranks[OATGPU_MAX_TARGETS];
+        int32_t found = 0;
+        if (oatgpu_targets(gpu_.ctx, ranks, &found, 1) != 1) gpu_.check(OATGPU_E_INVALID);
+        for (size_t j = 0; j < K; ++j) {
+            target_sinks_[j].wait();
+            *target_shared_[j] = target_position(ranks[j], position.sample());
+            target_sinks_[j].post();
+        }
+    }
     void configure_for(const FrameParams &p) override
     {
         cfg_.rows = (int)p.rows; cfg_.cols = (int)p.cols; cfg_.n_streams = 1;
@@ -81,6 +123,10 @@ protected:
             std::copy(homography_, homography_ + 9, f.h);
             gpu_.check(oatgpu_set_tracker_filters(gpu_.ctx, &f));
         }
+        if (!target_sink_addresses_.empty()) {
+            gpu_.check(oatgpu_set_targets(gpu_.ctx, (int32_t)target_sink_addresses_.size()));
+            bind_target_sinks(true);
+        }
     }
     // HSVDetector.cpp:142-173 / SimpleThreshold.cpp:114-134
     // Deferred (oatgpu_set_deferred): the call returns when the frame has left shared memory, PositionDetector::process posts
@@ -88,6 +134,7 @@ protected:
     bool detect_from_shm(const Frame &frame, Position2D &) override
     {
         if (difftrk_ || bsub_) return false;  // the batched trackers' step is synchronous: the frame is copied and the source posted first
+        if (!target_sink_addresses_.empty()) return false;       // (targets do not go with deferred completion: the synchronous call)
         if (!deferred_on_) { gpu_.check(oatgpu_set_deferred(gpu_.ctx, 1)); deferred_on_ = true; }
         gpu_.check(kind_ == Kind::HSV ? oatgpu_detect_hsv(gpu_.ctx, 0, frame.data(), nullptr)
                    : kind_ == Kind::THRESH ? oatgpu_detect_thresh(gpu_.ctx, 0, frame.data(), nullptr)
@@ -117,6 +164,7 @@ protected:
             if (oatgpu_tracker_filtered(gpu_.ctx, &f, 1) != 1) gpu_.check(OATGPU_E_INVALID);
             publish_filtered(position, f, regions_, homography_on_ ? homography_ : nullptr);
         }
+        publish_targets(position);
     }
     Kind kind_;
     bool bgr_, bsub_;
@@ -125,6 +173,8 @@ protected:
     UndistortCalibration undistort_{};
     bool deferred_on_{false};
     GpuCtx gpu_;
+    std::vector<Sink<Position2D>> target_sinks_;         // [K] (after gpu_: the sinks go END before the context is destroyed)
+    std::vector<Position2D *> target_shared_;
 };
 
 static void usage()
@@ -153,7 +203,12 @@ static void usage()
                  "        the first region (command-line order) that holds the position.  In a -c file: kalman = true, dt = .., homography\n"
                  "        = [..] and one [[KEY.region]] table per region with name and points.  Long names only (-T is thresh's window).\n"
                  "        hsv and thresh need --bsub for them; a plain diff runs the motion tracker on its GREY source.\n"
-                 "all:    --gpu-index N  HIP device ordinal (default 0)\n";
+                 "all:    --gpu-index N  HIP device ordinal (default 0)\n"
+                 "        --target-sinks T0,T1,..  (at most 8 names; target-sinks = \"T0,T1\" in a -c file) multi-target detection: the K\n"
+                 "        largest blobs inside the area window, ranked by area (ties: the later first pixel first); rank j of every frame\n"
+                 "        goes to sink Tj as a Position2D with the frame's sample, invalid where fewer than j + 1 blobs exist.  Rank 0 is\n"
+                 "        the detector's own result; the SINK carries what it carries without the option.  Targets are raw detections:\n"
+                 "        a filter chain acts on the SINK only.\n";
 }
 
 int main(int argc, char **argv)
@@ -172,14 +227,14 @@ int main(int argc, char **argv)
         // option names per TYPE: HSVDetector.cpp:49-75, SimpleThreshold.cpp:49-69, DifferenceDetector.cpp:41-62
         if (type == "hsv")
             o.apply_config({"h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer",
-                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography"},
+                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks"},
                            {"tune", "bsub", "kalman"});
         else if (type == "thresh")
             o.apply_config({"thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer",
-                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography"},
+                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks"},
                            {"tune", "bsub", "kalman"});
         else o.apply_config({"diff-threshold", "blur", "area", "tune", "gpu-index", "bgr", "bayer", "camera-matrix", "distortion-coeffs",
-                             "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography"}, {"tune", "bgr", "kalman"});
+                             "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks"}, {"tune", "bgr", "kalman"});
         if (o.has("bgr") && type != "diff") throw std::runtime_error("--bgr goes with TYPE diff only");
         if (type == "diff" && (o.has("bsub") || o.has("bsub-alpha") || o.has("bsub-background")))
             throw std::runtime_error("--bsub goes with TYPE hsv or thresh only");
@@ -222,6 +277,13 @@ int main(int argc, char **argv)
             if (o.has("kalman") && !(o.num("dt", 0.02, 0, 1e9) > 0)) throw std::runtime_error("--kalman: --dt must be > 0");
         }
         const bool homography_on = o.arr9("homography", homography);
+        // --target-sinks: the K ranked blobs of every frame, checked before any device is opened
+        std::vector<std::string> target_sinks;
+        if (o.has("target-sinks")) {
+            if (o.has("marker")) throw std::runtime_error("--target-sinks does not go with --marker");
+            const std::vector<std::string> lists = o.all.count("target-sinks") ? o.all["target-sinks"] : target_sink_lists_of_config(o.kv["target-sinks"]);
+            target_sinks = check_target_sinks(lists, {o.positional[2]}, false)[0];
+        }
         if (o.has("tune")) throw std::runtime_error("--tune needs a GUI and is not available in the hip detector");
         auto d = std::make_unique<GpuDetector>(o.positional[1], o.positional[2],
                                                type == "hsv" ? Kind::HSV : type == "thresh" ? Kind::THRESH : Kind::DIFF,
@@ -235,6 +297,7 @@ int main(int argc, char **argv)
         d->homography_on_ = homography_on;
         std::copy(homography, homography + 9, d->homography_);
         d->regions_ = regions;
+        d->target_sink_addresses_ = target_sinks;
         d->bsub_alpha_ = o.num("bsub-alpha", 0, 0, 1);
         if (o.has("bsub-background")) d->bsub_background_ = o.kv.at("bsub-background");
         d->cfg_.device = (int)o.num("gpu-index", 0, 0, 64);

@@ -41,6 +41,7 @@
 // and the intensity window of SimpleThreshold.cpp:171-174 in the same fused launches.
 #include "component.hpp"
 #include "filter_chain.hpp"
+#include "target_sinks.hpp"
 #include "scatter_tracker.hpp"
 #include <chrono>
 #include <cmath>
@@ -202,6 +203,13 @@ public:
         marker_sinks_ = std::vector<Sink<Position2D>>((size_t)n_ * markers.size());
         cfg_.h_lo = 0; cfg_.h_hi = 256; cfg_.s_lo = 0; cfg_.s_hi = 256; cfg_.v_lo = 1; cfg_.v_hi = 256;
     }
+    // --target-sinks: multi-target detection (oatgpu_set_targets); sinks[s][j] = address of rank j of camera s
+    void set_targets(const std::vector<std::vector<std::string>> &sinks)
+    {
+        target_sink_addresses_ = sinks;
+        targets_k_ = sinks.empty() ? 0 : (int)sinks[0].size();
+        target_sinks_ = std::vector<Sink<Position2D>>((size_t)n_ * targets_k_);
+    }
     oatgpu_config cfg_;
     double learning_coeff_{0.0};
     bool kalman_{false};            // --kalman: `posifilt kalman` fused behind the detector
@@ -221,6 +229,8 @@ public:
     int heading_anchor_{-1};        // --heading-anchor (`posicom mean`), -1: no heading
     int marker_ring_{0};            // --marker-ring D: marker mode through the staged loop and a result ring of D (0: the synchronous step)
     std::vector<std::vector<std::string>> marker_sink_addresses_;
+    std::vector<std::vector<std::string>> target_sink_addresses_;
+    int targets_k_{0};              // K of --target-sinks (0: off)
     // the filter chain behind the combined record (--mean-kalman / --mean-homography / --region): the camera's SINK then carries
     // the FILTERED Position2D; Kalman parameters are dt_ .. sig_noise_ above
     bool mean_kalman_{false}, mean_homography_on_{false};
@@ -274,6 +284,10 @@ protected:
                 const std::string &a = marker_sink_addresses_[i / markers_.size()][i % markers_.size()];
                 try { marker_sinks_[i].bind(a, a); } catch (...) {}
             }
+            for (size_t i = target_shared_.size(); i < target_sinks_.size(); ++i) {
+                const std::string &a = target_sink_addresses_[i / targets_k_][i % targets_k_];
+                try { target_sinks_[i].bind(a, a); } catch (...) {}
+            }
             throw;
         }
     }
@@ -316,6 +330,16 @@ protected:
         }
         frame_ptrs_.resize(n_);
         results_.resize(n_);
+        if (targets_k_) {
+            gpu_.check(oatgpu_set_targets(gpu_.ctx, targets_k_));
+            for (size_t i = 0; i < target_sinks_.size(); ++i) {
+                const std::string &a = target_sink_addresses_[i / targets_k_][i % targets_k_];
+                target_sinks_[i].bind(a, a);
+                target_shared_.push_back(target_sinks_[i].retrieve());
+            }
+            target_results_.resize((size_t)n_ * targets_k_);
+            target_found_.resize(n_);
+        }
         if (!markers_.empty()) {
             const int M = (int)markers_.size();
             gpu_.check(oatgpu_set_markers(gpu_.ctx, M, markers_.data(), heading_anchor_));
@@ -363,6 +387,9 @@ protected:
         position_sinks_[s].wait();
         *shared_positions_[s] = pos;
         position_sinks_[s].post();
+        for (int j = 0; j < targets_k_; ++j)                         // rank j of camera s, raw, with the frame's Sample
+            put(target_sinks_[(size_t)s * targets_k_ + j], target_shared_[(size_t)s * targets_k_ + j],
+                target_position(target_results_[(size_t)s * targets_k_ + j], pub_samples_[s]));
     }
     void publish_some(int max_sinks, bool only_if_ready)
     {
@@ -376,6 +403,8 @@ protected:
             }
             else
                 gpu_.check(oatgpu_track_collect(gpu_.ctx, results_.data()));
+            if (targets_k_ && oatgpu_targets(gpu_.ctx, target_results_.data(), target_found_.data(), 1) != 1)    // the set just collected
+                gpu_.check(OATGPU_E_INVALID);
             pub_samples_ = std::move(pending_.front());
             pending_.pop_front();
             collected_ = true;
@@ -531,6 +560,10 @@ protected:
     std::vector<oatgpu_position> marker_results_;      // [n][M]
     std::vector<oatgpu_combined> combined_;            // [n]
     std::vector<oatgpu_filtered> filtered_;            // [n] the combined records behind the filter chain
+    std::vector<Sink<Position2D>> target_sinks_;       // [n][K]
+    std::vector<Position2D *> target_shared_;
+    std::vector<oatgpu_position> target_results_;      // [n][K] of the result set that is being handed out
+    std::vector<int32_t> target_found_;                // [n]
     std::deque<std::vector<Sample>> pending_;  // Samples of the frames whose results are still on the device
     std::vector<Sample> pub_samples_;          // ... and of the result set that is being handed out (publish_some)
     bool collected_{false};
@@ -579,6 +612,13 @@ int main(int argc, char **argv)
                          "                            order; at most 16 of at most 64 points, names of at most 9 bytes) that holds the position.  With\n"
                          "                            or without --marker-ring; the per-marker sinks are unchanged.  In a -c file: mean-kalman = true,\n"
                          "                            mean-homography = [..], and one [[track.region]] table per region with name and points.\n"
+                         "       [--target-sinks T0,T1,..]...   multi-target detection: the K largest blobs of every camera's mask inside the area\n"
+                         "                            window, ranked by area (ties: the later first pixel first).  One comma list per camera (repeat\n"
+                         "                            the option), every list of the same length K <= 8; rank j of a camera's frame goes to the j-th\n"
+                         "                            address of its list as a Position2D with the frame's sample, invalid where fewer than j + 1 blobs\n"
+                         "                            exist.  Rank 0 is the detector's own result; the SINK carries what it carries without the option\n"
+                         "                            (--kalman / --homography act on the SINK only).  With or without --ring.  In a -c file:\n"
+                         "                            target-sinks = [\"a,b\", \"c,d\"].  Not with --marker or --ingest-root.\n"
                          "N SOURCEs / N SINKs: N cameras batched into one device pass per frame; SOURCE i feeds SINK i.\n"
                          "--gpu-index N0,N1,..: the cameras are split into contiguous blocks, one per listed device (own context and thread).\n"
                          "--ingest-root D0 (with --gpu-index D0,D1,..): all frames are ingested on device D0 and scattered to their devices\n"
@@ -591,7 +631,7 @@ int main(int argc, char **argv)
         o.apply_config({"adaptation-coeff", "h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "model-file",
                         "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "gpu-index", "ring", "mask", "thresh", "homography", "stage-copy", "timing",
                         "ingest-root", "print-partition", "camera-matrix", "distortion-coeffs", "undistort-key", "marker-sinks", "heading-anchor", "marker-ring",
-                        "mean-kalman", "mean-homography", "bayer"},
+                        "mean-kalman", "mean-homography", "bayer", "target-sinks"},
                        {"kalman", "timing", "print-partition", "mean-kalman"});
         const std::vector<std::string> sources = split_list(o.positional[0]), sinks = split_list(o.positional[1]);
         if (sources.size() != sinks.size()) throw std::runtime_error("need as many SINKs as SOURCEs");
@@ -667,6 +707,13 @@ int main(int argc, char **argv)
                     throw std::runtime_error("--heading-anchor: expected a marker index in 0.." + std::to_string(markers.size() - 1));
                 heading_anchor = (int)v;
             }
+        }
+        // --target-sinks: one list per camera, all of one length; checked before any device is opened
+        std::vector<std::vector<std::string>> target_sinks;
+        if (o.has("target-sinks")) {
+            if (o.has("ingest-root")) throw std::runtime_error("--ingest-root does not take --target-sinks");
+            target_sinks = check_target_sinks(o.all.count("target-sinks") ? o.all["target-sinks"] : target_sink_lists_of_config(o.kv["target-sinks"]),
+                                              sinks, !markers.empty());
         }
         // --gpu-index N | N0,N1,...: one shard of the SOURCE list per listed device (contiguous blocks)
         std::vector<int> devices;
@@ -769,6 +816,8 @@ int main(int argc, char **argv)
             t->homography_on_ = o.arr9("homography", t->homography_);
             if (!cals.empty()) t->undistort_.assign(cals.begin() + s0, cals.begin() + s1);
             if (!bayer.empty()) t->bayer_.assign(bayer.begin() + s0, bayer.begin() + s1);
+            if (!target_sinks.empty())
+                t->set_targets(std::vector<std::vector<std::string>>(target_sinks.begin() + s0, target_sinks.begin() + s1));
             if (!markers.empty())
                 t->set_markers(markers, heading_anchor, std::vector<std::vector<std::string>>(marker_sinks.begin() + s0, marker_sinks.begin() + s1));
             t->dt_ = o.num("dt", 0.02, 0, 1e9);                        // KalmanFilter2D.cpp:69-85 (lower bound 0)

@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""What multi-target detection costs (oatgpu_set_targets): a step with targets on gives up the single-workgroup LDS
+blob kernel and, in the fused tracker, the early / paired launch orders, for the global blob kernels with k_blob_rank behind them.
+
+    python tools/targets_bench.py [--steps 200] [--warmup 20] [--quick]
+    python tools/targets_bench.py --off-only --tree DIR      # the off legs alone with the package of another checkout (the parent)
+
+Shapes: 1 x 4K, 16 x 1080p and 1 x 640x480, BGR frames in device memory; the fused tracker (HotPath, bench.py's detector) and the
+motion tracker (diff_threshold 16, blur 2); frames with ONE blob a camera and with TWELVE (squares of the disc colour, 8 .. 30
+pixels wide, moving a few pixels a frame over synth.py's gradient with its +-6 noise and WITHOUT its flickering pixels: every
+64th pixel flickering by 110 levels is a foreground dot of the motion tracker on every frame, 130 k of them at 4K, far over the
+LDS blob kernel's capacity -- the step would take the global kernels with targets off as well and there would be nothing to
+compare).  --shapes / --trackers / --blobs pick a part.  Legs, us a frame set:
+  sync      track_dev: the median of `steps` calls after `warmup` calls;
+  sequence  track_sequence_dev over the 8 frame sets of the pool in one call, divided by 8: the median of `steps` calls after 2.
+Each with targets off, off once more (the same process, a new context: the run-to-run spread beside the differences), then K =
+1, 4, 8.  Every timed call ends in a device synchronisation, so a host clock around it is the step.  --off-only runs the two off
+legs and nothing that needs the new entry points, so that the same file measures the parent commit's step from its own tree
+(--tree): the off legs of the two trees should differ by no more than the two off legs of one tree do.  Prints one JSON line;
+the recipe and the figures' place are in profiles/targets_bench.txt.  Without a GPU the tool fails (no fallback)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+SHAPES = [("1x4K", 1, 2160, 3840), ("16x1080p", 16, 1080, 1920), ("1x640x480", 1, 480, 640)]
+AREA = (20.0, 1e6)
+BLOCK = (255, 64, 0)                 # synth.DISC_BGR[0]: inside disc_hsv_window()
+POOL = 8
+
+
+def median_us(call, steps, warmup):
+    for t in range(warmup):
+        call(t)
+    d = []
+    for t in range(steps):
+        t0 = time.perf_counter()
+        call(warmup + t)
+        d.append(time.perf_counter() - t0)
+    return round(statistics.median(d) * 1e6, 1)
+
+
+def paint(pool, blobs):
+    """a copy of the pool [POOL][n, rows, cols, 3] with `blobs` squares a camera, each on its own cell of a 4 x 3 grid"""
+    import numpy as np                      # (here and not at the top: --help needs nothing)
+    out = np.stack(pool).copy()
+    _, n, rows, cols, _ = out.shape
+    ch, cw = rows // 3, cols // 4
+    for t in range(out.shape[0]):
+        for s in range(n):
+            for b in range(blobs):
+                side = min(8 + 2 * b, ch // 3, cw // 3)
+                y = (b // 4) * ch + ch // 4 + (3 * t + s) % (ch // 4)
+                x = (b % 4) * cw + cw // 4 + (5 * t + 2 * s) % (cw // 4)
+                out[t, s, y:y + side, x:x + side] = BLOCK
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--quick", action="store_true", help="few steps (a rehearsal)")
+    ap.add_argument("--off-only", action="store_true", help="the two off legs alone: nothing that needs oatgpu_set_targets")
+    ap.add_argument("--shapes", default="", help="comma list of shape names (default: all)")
+    ap.add_argument("--trackers", default="", help="fused, motion or both (default)")
+    ap.add_argument("--blobs", default="1,12", help="blobs a camera, comma list")
+    ap.add_argument("--tree", default=ROOT, help="the checkout whose oat_amd package and library are measured (default: this one)")
+    a = ap.parse_args()
+    if a.quick:
+        a.steps, a.warmup = 16, 4
+    tree = os.path.abspath(a.tree)
+    sys.path.insert(0, tree)
+    import torch
+    import oat_amd
+    import numpy as np
+    from oat_amd.synth import SyntheticStream, disc_hsv_window
+    if not torch.cuda.is_available():
+        raise SystemExit("targets_bench: no GPU (nothing is measured without one)")
+    assert os.path.abspath(oat_amd.__file__).startswith(tree + os.sep), (oat_amd.__file__, tree)
+
+    def fused(rows, cols, n):
+        return oat_amd.HotPath(rows, cols, n_streams=n, adaptation_coeff=0.01, erode=3, dilate=7, area=AREA, ring_depth=8,
+                               **disc_hsv_window())
+
+    def motion(rows, cols, n):
+        return oat_amd.MotionTracker(rows, cols, n_streams=n, channels=3, diff_threshold=16, blur=2, area=AREA)
+
+    legs = [("off", 0), ("off_again", 0)] + ([] if a.off_only else [("k1", 1), ("k4", 4), ("k8", 8)])
+    out = []
+    for name, n, rows, cols in SHAPES:
+        if a.shapes and name not in a.shapes.split(","):
+            continue
+        streams = [SyntheticStream(rows, cols, s, n_discs=0, flicker=False) for s in range(n)]
+        bare = [np.stack([st.frame(t) for st in streams]) for t in range(POOL)]
+        for blobs in [int(b) for b in a.blobs.split(",")]:
+            dev = torch.from_numpy(paint(bare, blobs)).cuda()
+            torch.cuda.synchronize()
+            ptrs = [dev[t].data_ptr() for t in range(POOL)]
+            for tracker, make in (("fused", fused), ("motion", motion)):
+                if a.trackers and tracker not in a.trackers.split(","):
+                    continue
+                rec = {"shape": name, "streams": n, "rows": rows, "cols": cols, "tracker": tracker, "blobs": blobs,
+                       "steps": a.steps, "warmup": a.warmup}
+                for leg, k in legs:
+                    tr = make(rows, cols, n)
+                    if k:
+                        tr.set_targets(k)
+                    for t in range(POOL):                                   # the model and the last images settle on the pool
+                        tr.track_dev(ptrs[t])
+                    rec[f"sync_us_{leg}"] = median_us(lambda t: tr.track_dev(ptrs[t % POOL]), a.steps, a.warmup)
+                    rec[f"sequence_us_{leg}"] = round(median_us(lambda t: tr.track_sequence_dev(ptrs), a.steps, 2) / POOL, 1)
+                    if k:
+                        (tset,) = tr.targets()[-1:]
+                        rec[f"n_found_{leg}"] = [f for _, f in tset][:4]
+                    tr.close()
+                out.append(rec)
+            del dev
+            torch.cuda.empty_cache()
+    print(json.dumps({"tool": "targets_bench" + (" --off-only" if a.off_only else ""),
+                      "unit": "us a frame set, host clock around synchronous calls, median",
+                      "tree": os.path.relpath(tree, ROOT), "library": os.path.relpath(oat_amd.lib_path(), tree), "shapes": out,
+                      "device": torch.cuda.get_device_name(0)}))
+
+
+if __name__ == "__main__":
+    main()
