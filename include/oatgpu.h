@@ -49,7 +49,8 @@ extern "C" {
  * oatgpu_bsub_track_batch_dev, oatgpu_bsub_track_batch, oatgpu_bsub_track_sequence_dev, oatgpu_bsub_get_state,
  * oatgpu_read_bsub_mask; Bayer RAW8 ingest -- oatgpu_debayer_filter, oatgpu_debayer_dev, oatgpu_set_track_bayer, with the
  * OATGPU_BAYER_* pattern values; RAW8 frames for the motion and the subtraction tracker -- oatgpu_set_tracker_bayer; the filter
- * chain behind the motion and the subtraction tracker -- oatgpu_set_tracker_filters, oatgpu_tracker_filtered. */
+ * chain behind the motion and the subtraction tracker -- oatgpu_set_tracker_filters, oatgpu_tracker_filtered; target tracks --
+ * oatgpu_set_tracks, oatgpu_tracks, oatgpu_tracks_update, with the struct oatgpu_track. */
 
 enum {
     OATGPU_OK = 0,
@@ -615,6 +616,82 @@ int oatgpu_set_targets(oatgpu_ctx *ctx, int32_t k);          /* 0: off (default)
  * come back invalid with n_found 0.  Returns the number of sets written; nothing is consumed.  OATGPU_E_INVALID when targets
  * are off, no such call has run since oatgpu_set_targets, or max_sets is too small. */
 int oatgpu_targets(oatgpu_ctx *ctx, oatgpu_position *out, int32_t *n_found, int32_t max_sets);
+
+/* ---- target tracks: identity across frames for the K ranked blobs ----
+ * Rank is not identity: two animals of similar size swap ranks from frame to frame.  With tracks on, every frame of the motion
+ * and the subtraction tracker (oatgpu_diff_batch[_dev], oatgpu_diff_sequence_dev, oatgpu_bsub_track_batch[_dev],
+ * oatgpu_bsub_track_sequence_dev) also assigns its ranked detections to K persistent track slots per camera, runs one Kalman
+ * filter per slot and publishes each slot's filtered record with an identity: one launch a frame on the device
+ * (k_target_tracks) behind the frame's ranking, in frame order; inside the sequence calls the launches of consecutive frames are
+ * ordered by events on the host -- nothing waits on the device.  Batch calls, sequence calls, oatgpu_tracks_update and the two
+ * trackers continue one another.  The reference has nothing like this (every posidet publishes one object): the semantics are
+ * this project's own.
+ *
+ * Per camera stream the context owns K track slots (K = the K of oatgpu_set_targets).  Each slot holds
+ *   - one Kalman filter: a KalmanState, started from the reference's initial state by oatgpu_set_tracks and never re-created
+ *     afterwards;
+ *   - id (int64, 0 = empty), age and missed.
+ * Per camera there is next_id, starting at 1.  A reborn slot therefore carries the covariance filter_step leaves behind: that
+ * is exactly what `posifilt kalman` does after its own timeout, and it is kept.
+ *
+ * Parameters: the chain parameters of oatgpu_marker_filters, with kalman required on and homography and regions optional;
+ * gate, in pixels: gate >= 0, or +inf for no gate; NaN or a negative value is refused.
+ *
+ * One frame of one camera takes the frame's target set.  Rank j is valid for j < D, with centroid (cx_j, cy_j) exactly as
+ * oatgpu_position.x / .y give it.  All arithmetic is fp64, one rounding per operation, no contraction.
+ *   1. Live slots.  Slot i is live if its Kalman output of the previous frame had position_valid = 1 (found).
+ *   2. Prediction.  The predicted position of slot i is px = x + dt * vx, py = y + dt * vy, from that previous Kalman output in
+ *      pixels, before any homography.
+ *   3. Cost.  c(i, j) = dx * dx + dy * dy with dx = cx_j - px_i, dy = cy_j - py_i.  A pair is admissible iff slot i is live,
+ *      rank j is valid and c <= gate * gate.  A NaN cost is inadmissible.
+ *   4. Assignment.  Greedy global nearest neighbour.  Repeat until no pair is left: among admissible pairs whose slot and rank
+ *      are both unassigned, take the smallest c; break equal costs by the smaller slot index, then by the smaller rank; assign
+ *      the pair.
+ *   5. Births.  Valid ranks still unassigned take, in rank order, the slots that were NOT LIVE AT THE START OF THIS FRAME, in
+ *      ascending slot index.  A slot taken this way gets id = next_id++ and age = 0.  A rank with no such slot left is dropped.
+ *   6. One sample per slot.  Every slot takes exactly one sample this frame: assigned or born slots take
+ *      filter_step(valid, cx, cy); every other slot takes an invalid sample.  The slot then runs homography -> region, as the
+ *      trackers' chain does, with no heading.
+ *   7. The slot's output: the nine-word filtered record, i.e. oatgpu_filtered, bit for bit what the chain gives for that sample
+ *      stream; id, which is 0 if the slot is not live AFTER the step (the slot's id is then cleared); rank, the rank it took
+ *      this frame, or -1; age, the number of frames since birth; missed, the number of consecutive frames without a
+ *      measurement, 0 on a measured frame.  A slot that is not live reports id 0, rank -1, age 0, missed 0.
+ * Ids are never reused until the next oatgpu_set_tracks.  The assignment is greedy on purpose: exactly specifiable, K <= 8.
+ *
+ * Tracks act on the raw ranked detections.  The ordinary result, oatgpu_targets, the trackers' own filter chain
+ * (oatgpu_set_tracker_filters, a separate state), taps, models and tracker state stay bit for bit what they are without tracks.
+ * oatgpu_diff_reset, oatgpu_bsub_reset, RAW8 and undistortion switches never touch track state.  The fused tracker's own calls
+ * (oatgpu_track_*) and the single-stage detectors do NOT advance tracks: with tracks on they behave as with tracks off; their
+ * users, and any outside detector, go through oatgpu_tracks_update.
+ *
+ * Left out: tracks advanced inside the fused tracker's own batch, ring and sequence calls; an optimal (Hungarian) assignment;
+ * tracks on marker planes; merging and splitting of blobs; several GPUs. */
+typedef struct oatgpu_track {
+    oatgpu_filtered filtered;      /* the slot's record behind kalman -> homography -> region; no heading */
+    int64_t id;                    /* 0: the slot is not live */
+    int32_t rank;                  /* the rank the slot took this frame, -1: none */
+    int32_t age;                   /* frames since birth */
+    int32_t missed;                /* consecutive frames without a measurement */
+    int32_t reserved_;
+} oatgpu_track;                    /* 96 bytes */
+/* f = NULL switches tracks off and frees everything.  Otherwise: requires targets on, checks its parameters as
+ * oatgpu_set_tracker_filters does and drains outstanding work; (re)starts every slot and every camera's next_id.  Everything is
+ * allocated here, never in a step -- state, a track set for the four slots of each batched tracker that is on (one switched on
+ * later allocates its own), an extra set for oatgpu_tracks_update, one ordering event per slot: an out-of-memory is
+ * OATGPU_E_NOMEM and leaves a working context.  OATGPU_E_INVALID, with nothing changed, when targets are off, f->kalman == 0,
+ * the gate is NaN or negative, a limit is exceeded or results are outstanding.  While tracks are on, oatgpu_set_targets is
+ * refused (switch tracks off first). */
+int oatgpu_set_tracks(oatgpu_ctx *ctx, const oatgpu_marker_filters *f, double gate);
+/* The track sets of the frame sets the LATEST delivering call handed out (the six tracker calls above: one set for a batch
+ * call, n_frames for a sequence call; oatgpu_tracks_update: its one set), in the convention of oatgpu_targets:
+ * out[(t * n_streams + s) * K + i] is slot i of camera s of set t.  Returns the number of sets written; nothing is consumed.
+ * OATGPU_E_INVALID when tracks are off, no such call has run since oatgpu_set_tracks, or max_sets is too small. */
+int oatgpu_tracks(oatgpu_ctx *ctx, oatgpu_track *out, int32_t max_sets);
+/* One synchronous association step, on the device, for one frame set of n_streams x K positions: exactly what oatgpu_targets
+ * returns for one set; valid, x and y are used.  Advances the same track state; out[s * K + i] receives slot i of camera s.
+ * This is how the fused tracker, the single-stage detectors and any outside detector reach tracks.  Refused while results are
+ * outstanding. */
+int oatgpu_tracks_update(oatgpu_ctx *ctx, const oatgpu_position *targets, oatgpu_track *out);
 
 /* Deferred completion of the stage-by-stage operators below (default off).  With on = 1 a frame filter (oatgpu_mog_filter,
  * _bsub_filter, _mask_filter, _thresh_filter, _undistort_filter, _bgr2hsv, _cvt_color) or a detector (oatgpu_detect_hsv / _thresh / _diff)

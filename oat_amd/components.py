@@ -88,6 +88,20 @@ class Filtered:
                         bool(p.region_valid), names[p.region] if p.region_valid else None)
 
 
+@dataclass
+class Track(Filtered):
+    """One track slot of one camera (set_tracks): the slot's record behind kalman -> homography -> region, and its identity."""
+    id: int = 0                    # 0: the slot is not live
+    rank: int = -1                 # the rank the slot took this frame, -1: none
+    age: int = 0                   # frames since birth
+    missed: int = 0                # consecutive frames without a measurement
+
+    @staticmethod
+    def from_c(t, names):
+        f = Filtered.from_c(t.filtered, names)
+        return Track(**f.__dict__, id=int(t.id), rank=int(t.rank), age=int(t.age), missed=int(t.missed))
+
+
 def _marker(m):
     """dict(h=(lo,hi), s=(lo,hi), v=(lo,hi), erode=K, dilate=K, area=(a,b)) -- every key optional, the defaults are
     HSVDetector's (all-pass window, erode off, dilate 10, area [0, DBL_MAX)); GREY contexts: h is the intensity window --
@@ -412,6 +426,59 @@ class _Detector(_Context):
             sets = int(m.group(1))           # a sequence call delivered more sets than there was room for
         return [[([Position2D.from_c(out[(t * n + s) * k + j]) for j in range(k)], int(found[t * n + s])) for s in range(n)]
                 for t in range(rc)]
+
+    # -- target tracks (oatgpu_set_tracks / oatgpu_tracks / oatgpu_tracks_update) --
+    def set_tracks(self, kalman=None, gate=float("inf"), homography=None, regions=None):
+        """oatgpu_set_tracks: k persistent track slots per camera (k of set_targets, which must be on) behind the ranked
+        detections -- greedy nearest-neighbour assignment inside `gate` pixels, one Kalman filter a slot (kalman: a dict as
+        set_filters takes it, required), then homography and regions where given.  kalman=None switches tracks off.  A
+        successful call restarts every slot and the ids.  The batched trackers advance tracks with every frame; every other
+        detector goes through update_tracks."""
+        if kalman is None:
+            self._chk(self.lib.oatgpu_set_tracks(self.ctx, None, float(gate)))
+            return
+        f, names, _keep = _filter_chain(kalman, homography, regions)
+        self._chk(self.lib.oatgpu_set_tracks(self.ctx, C.byref(f), float(gate)))
+        self._track_region_names = names
+
+    def _tracks_out(self, out, sets):
+        n, k, names = self.n_streams, getattr(self, "_targets_k", 0), getattr(self, "_track_region_names", [])
+        return [[[Track.from_c(out[(t * n + s) * k + i], names) for i in range(k)] for s in range(n)] for t in range(sets)]
+
+    def tracks(self):
+        """oatgpu_tracks: the track sets of the frame sets the latest delivering call handed out -- a list with one entry per
+        frame set, each a list with one list of k Track (slot order) per camera.  Nothing is consumed."""
+        n, k, sets = self.n_streams, getattr(self, "_targets_k", 0), 1
+        while True:
+            out = (ffi.Track * (sets * n * max(k, 1)))()
+            rc = self.lib.oatgpu_tracks(self.ctx, out, sets)
+            if rc >= 0:
+                break
+            text = (self.lib.oatgpu_last_error(self.ctx) or b"").decode()
+            m = re.search(r"the latest call delivered (\d+)", text)
+            if not m or int(m.group(1)) <= sets:
+                self._chk(rc)
+            sets = int(m.group(1))
+        return self._tracks_out(out, rc)
+
+    def update_tracks(self, targets):
+        """oatgpu_tracks_update: one association step on one frame set of detections -- targets: one entry of targets(), or a
+        list with one list of k Position2D (or (valid, x, y)) per camera.  Returns one list of k Track per camera."""
+        n, k = self.n_streams, getattr(self, "_targets_k", 0)
+        if len(targets) != n:
+            raise ValueError(f"expected detections of {n} cameras, got {len(targets)}")
+        arr = (ffi.Position * (n * max(k, 1)))()
+        for s, cam in enumerate(targets):
+            ranks = cam[0] if isinstance(cam, tuple) and len(cam) == 2 and isinstance(cam[1], (int, np.integer)) else cam
+            if len(ranks) != k:
+                raise ValueError(f"expected {k} detections a camera, got {len(ranks)}")
+            for j, p in enumerate(ranks):
+                valid, x, y = (p.position_valid, p.x, p.y) if isinstance(p, Position2D) else p
+                a = arr[s * k + j]
+                a.valid, a.x, a.y = int(bool(valid)), float(x), float(y)
+        out = (ffi.Track * (n * max(k, 1)))()
+        self._chk(self.lib.oatgpu_tracks_update(self.ctx, arr, out))
+        return self._tracks_out(out, 1)[0]
 
 
 class HSVDetector(_Detector):

@@ -66,6 +66,7 @@ static int bsub_back(oatgpu_ctx *c, int slot, hipStream_t st, int prev_slot = -1
     c->bs.last = slot;
     c->bs.last_tap = m.tap;
     { const int rc = targets_launch(c, bb, c->bs.tgt, slot, 0, n, st); if (rc) return rc; }
+    { const int rc = tracks_launch(c, c->bs.tgt.rec_dev(slot), c->bs.trk.dev(), slot, prev_slot, st); if (rc) return rc; }
     return tracker_filters_launch(c, rd, slot, prev_slot, st);
 }
 
@@ -74,6 +75,7 @@ static int bsub_step(oatgpu_ctx *c, const void *frames_dev, double alpha, oatgpu
 {
     chain_begin(c->tf);
     targets_begin(c);
+    tracks_begin(c);
     int rc = bsub_front(c, frames_dev, nullptr, alpha, 0, 0);
     if (rc) return rc;
     rc = bsub_back(c, 0, c->stream);
@@ -125,6 +127,7 @@ extern "C" int oatgpu_bsub_track_sequence_dev(oatgpu_ctx *c, const void *const *
     int prev = -1;                         // slot of the frame before (the filter chain's order)
     chain_begin(c->tf);
     targets_begin(c);
+    tracks_begin(c);
     return run_sequence_in_flight(
         c, n_frames, c->bs.ev_front, c->bs.ev_done, [&](int t) { return t + 1 < n_frames ? 2 : 1; },
         [&](int t, int nf, int q, int q2) { return bsub_front(c, frames_dev[t], nf == 2 ? frames_dev[t + 1] : nullptr, alpha, q, q2); },

@@ -60,6 +60,7 @@ static int diff_back(oatgpu_ctx *c, int slot, const char *have, hipStream_t st, 
     HIPCHK(c, hipGetLastError());
     c->df.last = slot;
     { const int rc = targets_launch(c, bb, c->df.tgt, slot, 0, n, st); if (rc) return rc; }      // (every stream's roots and sums are still in the set)
+    { const int rc = tracks_launch(c, c->df.tgt.rec_dev(slot), c->df.trk.dev(), slot, prev_slot, st); if (rc) return rc; }
     return tracker_filters_launch(c, rd, slot, prev_slot, st);
 }
 
@@ -69,6 +70,7 @@ static int diff_step(oatgpu_ctx *c, const void *frames_dev, oatgpu_position *out
     const std::vector<char> have = c->diff_have;
     chain_begin(c->tf);
     targets_begin(c);
+    tracks_begin(c);
     int rc = diff_front(c, frames_dev, nullptr, 0, 0);
     if (rc) return rc;
     c->diff_have.assign(have.size(), 1);
@@ -121,6 +123,7 @@ extern "C" int oatgpu_diff_sequence_dev(oatgpu_ctx *c, const void *const *frames
     int prev = -1;                         // slot of the frame before (the filter chain's order)
     chain_begin(c->tf);
     targets_begin(c);
+    tracks_begin(c);
     return run_sequence_in_flight(
         c, n_frames, c->df.ev_front, c->df.ev_done,
         [&](int t) {

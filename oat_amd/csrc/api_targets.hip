@@ -54,6 +54,7 @@ extern "C" int oatgpu_set_targets(oatgpu_ctx *c, int32_t k)
     if (!c) return OATGPU_E_INVALID;
     if (k < 0 || k > kMaxTargets) return fail(c, OATGPU_E_INVALID, "targets must be in 0..%d", kMaxTargets);
     if (c->ring_count || c->staged_count) return fail(c, OATGPU_E_INVALID, "set_targets while enqueued results are outstanding");
+    if (c->tk.on) return fail(c, OATGPU_E_INVALID, "set_targets while tracks are on: switch tracks off first (oatgpu_set_tracks)");
     if (k > 0 && c->deferred) return fail(c, OATGPU_E_INVALID, "set_targets with deferred completion on (oatgpu_set_deferred) is not supported");
     if (k > 0 && c->mk.n) return fail(c, OATGPU_E_INVALID, "set_targets with marker sets configured (oatgpu_set_markers) is not supported");
     int rc = open_sync(c);

@@ -18,6 +18,7 @@ bool BatchedTrackerState::alloc(const oatgpu_ctx *c)
     ok = ok && masks.alloc(K * planes * words * 8) == hipSuccess;
     ok = ok && rec.alloc(K * n * sizeof(ResultRec), hipHostMallocMapped) == hipSuccess;
     ok = ok && (!c->tg.k || tgt.alloc(K, n, c->tg.k));
+    ok = ok && (!c->tk.on || tracks_alloc_sets(c, trk, c->tk.k));
     // (the taps: words beyond the frame are never written by the back half)
     ok = ok && hipMemsetAsync(bits, 0, K * words * 8, c->stream) == hipSuccess;
     ok = ok && hipMemsetAsync(masks, 0, K * planes * words * 8, c->stream) == hipSuccess;
@@ -93,6 +94,7 @@ void tracker_hand_out(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, oa
     for (size_t s = 0; s < bt.n; ++s) to_position(bt.rec.host()[(size_t)slot * bt.n + s], out + s);
     if (c->tf.on) chain_keep(c, c->tf, c->tf.out.host() + (size_t)slot * bt.n);
     targets_keep(c, bt.tgt, slot);
+    if (c->tk.on) tracks_keep(c, bt.trk.host() + (size_t)slot * bt.n * (size_t)c->tk.k);
 }
 
 // --- the trackers' launch of the filter chain ---

@@ -155,6 +155,7 @@ struct BatchedTrackerState {
     DevMem<u64> masks;                         // [kSeqSlots][planes][n][Palloc/64] the slot's planes (the taps)
     HostMem<ResultRec> rec;                    // host-mapped: [kSeqSlots][n] result records, written by the blob kernels through dev()
     TargetSets tgt;                            // [kSeqSlots] target sets beside rec, while targets are on (oatgpu_set_targets)
+    HostMem<TrackRec> trk;                     // host-mapped: [kSeqSlots][n][K] track sets beside tgt, while tracks are on (oatgpu_set_tracks)
     Event ev_front[kSeqSlots];                 // stream A: the front launch that wrote this slot's bits has finished
     Event ev_done[kSeqSlots];                  // the slot's back half has finished
     int last = -1;                             // slot of the tracker's latest frame (oatgpu_read_*_mask); -1: none yet
@@ -185,6 +186,26 @@ struct BsubTracker : BatchedTrackerState {
 struct TrackerFilters : PosfiltChain {
     HostMem<MarkerFiltered> out;               // host-mapped: [kSeqSlots][n] the slot's filtered set, written by k_tracker_filters through dev()
     Event ev[kSeqSlots];                       // the slot's filter launch has finished: frame t's launch waits for frame t - 1's
+};
+
+// Target tracks (oatgpu_set_tracks; api_tracks.hip, kernels_tracks.hip): K persistent track slots per camera
+// stream behind the ranked detections of the motion and the subtraction tracker, one k_target_tracks launch a frame behind the
+// slot's k_blob_rank, in frame order.  One state for the context -- both trackers and oatgpu_tracks_update advance it.  Everything
+// below, and BatchedTrackerState::trk, is made by the setter (or by a batched tracker switched on later), never inside a step.
+struct Tracks {
+    bool on = false;
+    int k = 0;                                 // K of oatgpu_set_targets when tracks were switched on
+    double gate2 = 0.0;                        // gate * gate
+    DevMem<MarkerFilterParams> params;         // device: the chain's parameters and the region table
+    DevMem<KalmanState> state;                 // device: [n][K] one filter a slot
+    DevMem<TrackMeta> meta;                    // device: [n][K] id, age, missed of every slot
+    DevMem<long long> next_id;                 // device: [n]
+    HostMem<TrackTriple> upd_in;               // host-mapped: [n][K] the detections of oatgpu_tracks_update
+    HostMem<TrackRec> upd_out;                 // host-mapped: [n][K] ... and its track set
+    Event ev[kSeqSlots];                       // the slot's track launch has finished: frame t's launch waits for frame t - 1's
+    std::vector<oatgpu_track> last;            // [sets][n][K] what the latest delivering call delivered (oatgpu_tracks)
+    int last_sets = 0;
+    TrackLaunch launch() const { return {params, state, meta, next_id, gate2, k}; }
 };
 
 struct oatgpu_ctx {
@@ -365,6 +386,7 @@ struct oatgpu_ctx {
     BsubTracker bs;
     TrackerFilters tf;
     Targets tg;
+    Tracks tk;
 };
 
 // a back half's erosion and dilation, planned and issued (plan_morph, issue_morph: api_track.hip)
@@ -447,6 +469,13 @@ void tracker_hand_out(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, oa
 int targets_launch(oatgpu_ctx *c, const BlobBuffers &bb, const TargetSets &ts, int slot, int s0, int n, hipStream_t st);
 void targets_begin(oatgpu_ctx *c);
 void targets_keep(oatgpu_ctx *c, const TargetSets &ts, int slot, int only = -1);
+// api_tracks.hip: k_target_tracks on the target set recs of the tracker's slot `slot`, on st right behind its k_blob_rank, into the
+// slot's track set `set`; prev_slot as tracker_filters_launch's.  The list a delivering call keeps (tracks_begin, tracks_keep) and a
+// batched tracker's own track sets (false: hipGetLastError() has the reason).  All do nothing while tracks are off.
+int tracks_launch(oatgpu_ctx *c, const TargetRec *recs, TrackRec *set, int slot, int prev_slot, hipStream_t st);
+void tracks_begin(oatgpu_ctx *c);
+void tracks_keep(oatgpu_ctx *c, const TrackRec *set);
+bool tracks_alloc_sets(const oatgpu_ctx *c, HostMem<TrackRec> &sets, int k);
 // api_measure.hip
 void prof_fold(oatgpu_ctx *c);
 #pragma GCC visibility pop

@@ -394,4 +394,27 @@ void launch_marker_filters(const MarkerFilterParams *params, KalmanState *state,
 void launch_tracker_filters(const MarkerFilterParams *params, KalmanState *state, const ResultRec *in, MarkerFiltered *out,
                             int n_streams, hipStream_t st);
 
+// --- kernels_tracks.hip --- (target tracks: identity across frames for the k ranked blobs, oatgpu_set_tracks)
+struct TrackRec {                // one slot's output, twelve 64-bit words: oatgpu_track's layout
+    MarkerFiltered f;
+    long long id;                // 0: the slot is not live
+    int rank, age;               // rank taken this frame (-1: none), frames since birth
+    int missed, reserved_;       // consecutive frames without a measurement
+};
+struct TrackMeta { long long id; int age, missed; };     // a slot's identity between launches, beside its KalmanState
+struct TrackTriple { long long valid; double x, y; };    // one detection as oatgpu_tracks_update hands it over
+struct TrackLaunch {
+    const MarkerFilterParams *params;    // the chain's parameters (kalman on), in DEVICE memory
+    KalmanState *state;                  // [n_streams][k] one filter a slot
+    TrackMeta *meta;                     // [n_streams][k]
+    long long *next_id;                  // [n_streams]
+    double gate2;                        // gate * gate (+inf: no gate)
+    int k;                               // slots a camera = ranks a camera, 1..kMaxTargets
+};
+// One association step for every camera stream: one wave a stream.  The frame's detections are recs[n_streams][k] (a target set,
+// written by k_blob_rank earlier on the same HIP stream) or, where recs is null, tri[n_streams][k]; out[n_streams][k] may be
+// host-mapped memory (64-bit stores).  The caller orders the launches of consecutive frames (events): nothing waits on the device.
+void launch_target_tracks(const TrackLaunch &a, const TargetRec *recs, const TrackTriple *tri, TrackRec *out, int n_streams,
+                          hipStream_t st);
+
 }  // namespace oatgpu

@@ -86,6 +86,12 @@ class Filtered(C.Structure):
                 ("vx", C.c_double), ("vy", C.c_double), ("hx", C.c_double), ("hy", C.c_double)]
 
 
+class Track(C.Structure):
+    """oatgpu_track: one track slot of one camera (oatgpu_set_tracks), 96 bytes."""
+    _fields_ = [("filtered", Filtered), ("id", C.c_int64), ("rank", C.c_int32), ("age", C.c_int32), ("missed", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
 E_RING_FULL = -4
 E_RING_EMPTY = -5
 ABI_VERSION = 9          # must equal OATGPU_ABI_VERSION of include/oatgpu.h
@@ -149,6 +155,9 @@ SIGNATURES = {
     "oatgpu_tracker_filtered": (C.c_int, [_ctx, C.POINTER(Filtered), C.c_int32]),
     "oatgpu_set_targets": (C.c_int, [_ctx, C.c_int32]),
     "oatgpu_targets": (C.c_int, [_ctx, C.POINTER(Position), C.POINTER(C.c_int32), C.c_int32]),
+    "oatgpu_set_tracks": (C.c_int, [_ctx, C.POINTER(MarkerFilters), C.c_double]),
+    "oatgpu_tracks": (C.c_int, [_ctx, C.POINTER(Track), C.c_int32]),
+    "oatgpu_tracks_update": (C.c_int, [_ctx, C.POINTER(Position), C.POINTER(Track)]),
     "oatgpu_mog_apply": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_mog_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_bgr2hsv": (C.c_int, [_ctx, _u8p, _u8p]),

@@ -17,6 +17,9 @@
 //                 every TYPE and form with --target-sinks T0,T1,..: the K largest blobs of the frame, ranked (oatgpu_set_targets):
 //                 sink j receives rank j as a Position2D with the frame's Sample on every frame, invalid where the rank is empty;
 //                 the SINK carries what it carries without the option
+//                 diff [--bgr|--bayer P], hsv --bsub, thresh --bsub with --track-sinks T0,T1,.. --kalman ..: target tracks
+//                 (oatgpu_set_tracks): K = the list's length persistent track slots behind the K ranked blobs; sink i carries slot
+//                 i's filtered Position2D on every frame, invalid while the slot is empty -- the slot is the identity on the wire
 // Same positional arguments and option names as src/positiondetector/main.cpp:85-271.
 #include "component.hpp"
 #include "filter_chain.hpp"
@@ -59,6 +62,15 @@ public:
     std::vector<RegionDef> regions_;
     bool chain_on() const { return kalman_ || homography_on_ || !regions_.empty(); }
     std::vector<std::string> target_sink_addresses_;     // --target-sinks: rank j of every frame on the j-th address
+    std::vector<std::string> track_sink_addresses_;      // --track-sinks: track slot i of every frame on the i-th address
+    double track_gate_{HUGE_VAL};                        // --track-gate: pixels (default: no gate)
+    // the sinks beside the SINK: the target sinks, then the track sinks
+    std::vector<std::string> extra_sink_addresses() const
+    {
+        std::vector<std::string> v = target_sink_addresses_;
+        v.insert(v.end(), track_sink_addresses_.begin(), track_sink_addresses_.end());
+        return v;
+    }
 
 protected:
     // (a detector that fails while connecting still binds its target sinks, so that its destructor sets them END)
@@ -73,10 +85,11 @@ protected:
     }
     void bind_target_sinks(bool loud)
     {
-        if (target_sinks_.empty()) target_sinks_ = std::vector<Sink<Position2D>>(target_sink_addresses_.size());
+        const std::vector<std::string> names = extra_sink_addresses();
+        if (target_sinks_.empty()) target_sinks_ = std::vector<Sink<Position2D>>(names.size());
         for (size_t j = target_shared_.size(); j < target_sinks_.size(); ++j) {
             try {
-                target_sinks_[j].bind(target_sink_addresses_[j], target_sink_addresses_[j]);
+                target_sinks_[j].bind(names[j], names[j]);
                 target_shared_.push_back(target_sinks_[j].retrieve());
             } catch (...) {
                 if (loud) throw;
@@ -98,6 +111,30 @@ protected:
             target_sinks_[j].post();
         }
     }
+    // the frame's track slots to their sinks (behind the target sinks in target_sinks_), every one with the frame's Sample
+    void publish_tracks(const Position2D &position)
+    {
+        const size_t K = track_sink_addresses_.size(), first = target_sink_addresses_.size();
+        if (!K) return;
+        oatgpu_track slots[OATGPU_MAX_TARGETS];
+        if (oatgpu_tracks(gpu_.ctx, slots, 1) != 1) gpu_.check(OATGPU_E_INVALID);
+        for (size_t i = 0; i < K; ++i) {
+            Position2D pos("");
+            pos.set_sample(position.sample());
+            publish_filtered(pos, slots[i].filtered, regions_, homography_on_ ? homography_ : nullptr);
+            target_sinks_[first + i].wait();
+            *target_shared_[first + i] = pos;
+            target_sinks_[first + i].post();
+        }
+    }
+    oatgpu_marker_filters chain_of(std::vector<oatgpu_region> &rs) const
+    {
+        oatgpu_marker_filters f = chain_filters(regions_, rs);
+        f.kalman = kalman_; f.dt = dt_; f.timeout = timeout_; f.sigma_accel = sig_accel_; f.sigma_noise = sig_noise_;
+        f.homography = homography_on_;
+        std::copy(homography_, homography_ + 9, f.h);
+        return f;
+    }
     void configure_for(const FrameParams &p) override
     {
         cfg_.rows = (int)p.rows; cfg_.cols = (int)p.cols; cfg_.n_streams = 1;
@@ -117,16 +154,17 @@ protected:
         }
         if (chain_on()) {
             std::vector<oatgpu_region> rs;
-            oatgpu_marker_filters f = chain_filters(regions_, rs);
-            f.kalman = kalman_; f.dt = dt_; f.timeout = timeout_; f.sigma_accel = sig_accel_; f.sigma_noise = sig_noise_;
-            f.homography = homography_on_;
-            std::copy(homography_, homography_ + 9, f.h);
+            const oatgpu_marker_filters f = chain_of(rs);
             gpu_.check(oatgpu_set_tracker_filters(gpu_.ctx, &f));
         }
-        if (!target_sink_addresses_.empty()) {
-            gpu_.check(oatgpu_set_targets(gpu_.ctx, (int32_t)target_sink_addresses_.size()));
-            bind_target_sinks(true);
+        const size_t n_targets = std::max(target_sink_addresses_.size(), track_sink_addresses_.size());      // (equal where both are given)
+        if (n_targets) gpu_.check(oatgpu_set_targets(gpu_.ctx, (int32_t)n_targets));
+        if (!track_sink_addresses_.empty()) {                // the chain options describe the tracks too
+            std::vector<oatgpu_region> rs;
+            const oatgpu_marker_filters f = chain_of(rs);
+            gpu_.check(oatgpu_set_tracks(gpu_.ctx, &f, track_gate_));
         }
+        if (n_targets) bind_target_sinks(true);
     }
     // HSVDetector.cpp:142-173 / SimpleThreshold.cpp:114-134
     // Deferred (oatgpu_set_deferred): the call returns when the frame has left shared memory, PositionDetector::process posts
@@ -134,7 +172,7 @@ protected:
     bool detect_from_shm(const Frame &frame, Position2D &) override
     {
         if (difftrk_ || bsub_) return false;  // the batched trackers' step is synchronous: the frame is copied and the source posted first
-        if (!target_sink_addresses_.empty()) return false;       // (targets do not go with deferred completion: the synchronous call)
+        if (!extra_sink_addresses().empty()) return false;       // (targets do not go with deferred completion: the synchronous call)
         if (!deferred_on_) { gpu_.check(oatgpu_set_deferred(gpu_.ctx, 1)); deferred_on_ = true; }
         gpu_.check(kind_ == Kind::HSV ? oatgpu_detect_hsv(gpu_.ctx, 0, frame.data(), nullptr)
                    : kind_ == Kind::THRESH ? oatgpu_detect_thresh(gpu_.ctx, 0, frame.data(), nullptr)
@@ -165,6 +203,7 @@ protected:
             publish_filtered(position, f, regions_, homography_on_ ? homography_ : nullptr);
         }
         publish_targets(position);
+        publish_tracks(position);
     }
     Kind kind_;
     bool bgr_, bsub_;
@@ -208,7 +247,15 @@ static void usage()
                  "        largest blobs inside the area window, ranked by area (ties: the later first pixel first); rank j of every frame\n"
                  "        goes to sink Tj as a Position2D with the frame's sample, invalid where fewer than j + 1 blobs exist.  Rank 0 is\n"
                  "        the detector's own result; the SINK carries what it carries without the option.  Targets are raw detections:\n"
-                 "        a filter chain acts on the SINK only.\n";
+                 "        a filter chain acts on the SINK only.\n"
+                 "diff, hsv --bsub, thresh --bsub:\n"
+                 "        --track-sinks T0,T1,.. [--track-gate PX] --kalman [..] [--homography ..] [--region ..]  (at most 8 names) target\n"
+                 "        tracks: K = the number of names persistent track slots behind the K ranked blobs -- each frame's blobs are\n"
+                 "        assigned to the slots by greedy nearest neighbour inside PX pixels (default: no gate) of where the slot's\n"
+                 "        Kalman filter expects its object, new objects take free slots.  Sink Ti carries slot i's filtered Position2D\n"
+                 "        with the frame's sample on every frame (position, velocity, region, WORLD units under a homography), invalid\n"
+                 "        while the slot is empty: the slot is the identity.  Switches targets on itself; the chain options describe\n"
+                 "        both the SINK's chain and the tracks.  With --target-sinks too, both lists have the same length.\n";
 }
 
 int main(int argc, char **argv)
@@ -227,14 +274,14 @@ int main(int argc, char **argv)
         // option names per TYPE: HSVDetector.cpp:49-75, SimpleThreshold.cpp:49-69, DifferenceDetector.cpp:41-62
         if (type == "hsv")
             o.apply_config({"h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer",
-                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks"},
+                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "track-sinks", "track-gate"},
                            {"tune", "bsub", "kalman"});
         else if (type == "thresh")
             o.apply_config({"thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer",
-                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks"},
+                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "track-sinks", "track-gate"},
                            {"tune", "bsub", "kalman"});
         else o.apply_config({"diff-threshold", "blur", "area", "tune", "gpu-index", "bgr", "bayer", "camera-matrix", "distortion-coeffs",
-                             "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks"}, {"tune", "bgr", "kalman"});
+                             "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "track-sinks", "track-gate"}, {"tune", "bgr", "kalman"});
         if (o.has("bgr") && type != "diff") throw std::runtime_error("--bgr goes with TYPE diff only");
         if (type == "diff" && (o.has("bsub") || o.has("bsub-alpha") || o.has("bsub-background")))
             throw std::runtime_error("--bsub goes with TYPE hsv or thresh only");
@@ -284,11 +331,26 @@ int main(int argc, char **argv)
             const std::vector<std::string> lists = o.all.count("target-sinks") ? o.all["target-sinks"] : target_sink_lists_of_config(o.kv["target-sinks"]);
             target_sinks = check_target_sinks(lists, {o.positional[2]}, false)[0];
         }
+        // --track-sinks: the K track slots of every frame, checked before any device is opened
+        std::vector<std::string> track_sinks;
+        if (o.has("track-gate") && !o.has("track-sinks")) throw std::runtime_error("--track-gate is a parameter of --track-sinks");
+        if (o.has("track-sinks")) {
+            if (o.has("marker")) throw std::runtime_error("--track-sinks does not go with --marker");
+            if (type != "diff" && !o.has("bsub"))
+                throw std::runtime_error("--track-sinks with TYPE " + type + " needs --bsub: tracks run behind the batched trackers (diff, hsv "
+                                         "--bsub, thresh --bsub), not behind the single-stage detector");
+            if (!o.has("kalman")) throw std::runtime_error("--track-sinks needs --kalman: every track slot runs a Kalman filter");
+            const std::vector<std::string> lists = o.all.count("track-sinks") ? o.all["track-sinks"] : target_sink_lists_of_config(o.kv["track-sinks"]);
+            track_sinks = check_target_sinks(lists, {o.positional[2]}, false, "--track-sinks", target_sinks)[0];
+            if (!target_sinks.empty() && target_sinks.size() != track_sinks.size())
+                throw std::runtime_error("--track-sinks names " + std::to_string(track_sinks.size()) + " sinks, --target-sinks " +
+                                         std::to_string(target_sinks.size()) + ": K is one number");
+        }
         if (o.has("tune")) throw std::runtime_error("--tune needs a GUI and is not available in the hip detector");
         auto d = std::make_unique<GpuDetector>(o.positional[1], o.positional[2],
                                                type == "hsv" ? Kind::HSV : type == "thresh" ? Kind::THRESH : Kind::DIFF,
                                                o.has("bgr") || (bayer && type == "diff"), o.has("bsub"), bayer,
-                                               undistort ? &cal : nullptr, filters);
+                                               undistort ? &cal : nullptr, filters || !track_sinks.empty());
         d->kalman_ = o.has("kalman");
         d->dt_ = o.num("dt", 0.02, 0, 1e9);                         // KalmanFilter2D.cpp:69-85 (lower bound 0)
         d->timeout_ = o.num("timeout", 0.0, 0, 1e18);
@@ -298,6 +360,14 @@ int main(int argc, char **argv)
         std::copy(homography, homography + 9, d->homography_);
         d->regions_ = regions;
         d->target_sink_addresses_ = target_sinks;
+        d->track_sink_addresses_ = track_sinks;
+        if (o.has("track-gate")) {
+            char *end = nullptr;
+            const std::string g = o.kv.at("track-gate");
+            const double v = strtod(g.c_str(), &end);
+            if (end == g.c_str() || *end || !(v >= 0)) throw std::runtime_error("--track-gate: expected pixels >= 0 (or inf), got '" + g + "'");
+            d->track_gate_ = v;
+        }
         d->bsub_alpha_ = o.num("bsub-alpha", 0, 0, 1);
         if (o.has("bsub-background")) d->bsub_background_ = o.kv.at("bsub-background");
         d->cfg_.device = (int)o.num("gpu-index", 0, 0, 64);

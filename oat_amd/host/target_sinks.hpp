@@ -36,28 +36,31 @@ inline std::vector<std::string> target_sink_lists_of_config(const std::string &v
     return lists;
 }
 
-// lists: one per camera; sinks: the cameras' ordinary SINKs (a target sink may not repeat one of them either)
+// lists: one per camera; sinks: the cameras' ordinary SINKs (a target sink may not repeat one of them either); taken: names that
+// are in use besides (--track-sinks: the target sinks); option: the option the lists came from, for the messages
 inline std::vector<std::vector<std::string>> check_target_sinks(const std::vector<std::string> &lists, const std::vector<std::string> &sinks,
-                                                                bool markers)
+                                                                bool markers, const std::string &option = "--target-sinks",
+                                                                const std::vector<std::string> &taken = {})
 {
     if (markers)
-        throw std::runtime_error("--target-sinks does not go with --marker: targets rank the blobs of one mask, a marker set has one mask a marker");
+        throw std::runtime_error(option + " does not go with --marker: targets rank the blobs of one mask, a marker set has one mask a marker");
     if (lists.size() != sinks.size())
-        throw std::runtime_error("--target-sinks: " + std::to_string(lists.size()) + " lists for " + std::to_string(sinks.size()) +
+        throw std::runtime_error(option + ": " + std::to_string(lists.size()) + " lists for " + std::to_string(sinks.size()) +
                                  " SOURCEs (one comma list per camera: repeat the option)");
     std::vector<std::vector<std::string>> out;
     std::set<std::string> seen(sinks.begin(), sinks.end());
+    seen.insert(taken.begin(), taken.end());
     for (const std::string &l : lists) {
         out.push_back(target_sink_names(l));
         if (out.back().size() > OATGPU_MAX_TARGETS)
-            throw std::runtime_error("--target-sinks: '" + l + "' names " + std::to_string(out.back().size()) + " sinks, at most " +
+            throw std::runtime_error(option + ": '" + l + "' names " + std::to_string(out.back().size()) + " sinks, at most " +
                                      std::to_string(OATGPU_MAX_TARGETS));
         if (out.back().size() != out.front().size())
-            throw std::runtime_error("--target-sinks: lists of different lengths (" + std::to_string(out.front().size()) + " and " +
+            throw std::runtime_error(option + ": lists of different lengths (" + std::to_string(out.front().size()) + " and " +
                                      std::to_string(out.back().size()) + "): K is the same for every camera");
         for (const std::string &name : out.back()) {
-            if (name.empty()) throw std::runtime_error("--target-sinks: an empty sink name in '" + l + "'");
-            if (!seen.insert(name).second) throw std::runtime_error("--target-sinks: sink '" + name + "' is named twice");
+            if (name.empty()) throw std::runtime_error(option + ": an empty sink name in '" + l + "'");
+            if (!seen.insert(name).second) throw std::runtime_error(option + ": sink '" + name + "' is named twice");
         }
     }
     return out;

@@ -4,6 +4,7 @@ blob kernel and, in the fused tracker, the early / paired launch orders, for the
 
     python tools/targets_bench.py [--steps 200] [--warmup 20] [--quick]
     python tools/targets_bench.py --off-only --tree DIR      # the off legs alone with the package of another checkout (the parent)
+    python tools/targets_bench.py --tracks [--off-only --tree DIR]      # what target tracks cost on top of targets
 
 Shapes: 1 x 4K, 16 x 1080p and 1 x 640x480, BGR frames in device memory; the fused tracker (HotPath, bench.py's detector) and the
 motion tracker (diff_threshold 16, blur 2); frames with ONE blob a camera and with TWELVE (squares of the disc colour, 8 .. 30
@@ -17,7 +18,15 @@ Each with targets off, off once more (the same process, a new context: the run-t
 1, 4, 8.  Every timed call ends in a device synchronisation, so a host clock around it is the step.  --off-only runs the two off
 legs and nothing that needs the new entry points, so that the same file measures the parent commit's step from its own tree
 (--tree): the off legs of the two trees should differ by no more than the two off legs of one tree do.  Prints one JSON line;
-the recipe and the figures' place are in profiles/targets_bench.txt.  Without a GPU the tool fails (no fallback)."""
+the recipe and the figures' place are in profiles/targets_bench.txt.
+
+--tracks measures target tracks (oatgpu_set_tracks) instead: the motion and the subtraction tracker (alpha 0, a window on the
+brightness of the difference), the same shapes and legs; per K = 4 and 8: targets on with tracks off, off once more (a new
+context), then tracks on (kalman dt 0.02 timeout 0.1 sigma-accel 300 sigma-noise 0.5, gate 40 pixels).  The added us a frame
+set is tracks minus off.  With --off-only the tracks-off legs alone: they need nothing newer than oatgpu_set_targets, so the
+parent commit's tree (--tree) runs them.  The recipe and the figures' place are in profiles/tracks_bench.txt.
+
+Without a GPU the tool fails (no fallback)."""
 import argparse
 import json
 import os
@@ -66,6 +75,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--quick", action="store_true", help="few steps (a rehearsal)")
     ap.add_argument("--off-only", action="store_true", help="the two off legs alone: nothing that needs oatgpu_set_targets")
+    ap.add_argument("--tracks", action="store_true", help="target tracks on top of targets K = 4, 8 (motion and subtraction tracker)")
     ap.add_argument("--shapes", default="", help="comma list of shape names (default: all)")
     ap.add_argument("--trackers", default="", help="fused, motion or both (default)")
     ap.add_argument("--blobs", default="1,12", help="blobs a camera, comma list")
@@ -90,7 +100,15 @@ def main():
     def motion(rows, cols, n):
         return oat_amd.MotionTracker(rows, cols, n_streams=n, channels=3, diff_threshold=16, blur=2, area=AREA)
 
-    legs = [("off", 0), ("off_again", 0)] + ([] if a.off_only else [("k1", 1), ("k4", 4), ("k8", 8)])
+    def subtraction(rows, cols, n):
+        return oat_amd.SubtractionTracker(rows, cols, n_streams=n, channels=3, alpha=0.0, v_thresh=(60, 256), erode=0, dilate=3, area=AREA)
+
+    # (leg, K, tracks on)
+    legs = [("off", 0, False), ("off_again", 0, False)] + ([] if a.off_only else [("k1", 1, False), ("k4", 4, False), ("k8", 8, False)])
+    trackers = (("fused", fused), ("motion", motion))
+    if a.tracks:
+        legs = [(f"k{k}_{leg}", k, leg == "tracks") for k in (4, 8) for leg in ("off", "off_again") + (() if a.off_only else ("tracks",))]
+        trackers = (("motion", motion), ("subtraction", subtraction))
     out = []
     for name, n, rows, cols in SHAPES:
         if a.shapes and name not in a.shapes.split(","):
@@ -101,15 +119,17 @@ def main():
             dev = torch.from_numpy(paint(bare, blobs)).cuda()
             torch.cuda.synchronize()
             ptrs = [dev[t].data_ptr() for t in range(POOL)]
-            for tracker, make in (("fused", fused), ("motion", motion)):
+            for tracker, make in trackers:
                 if a.trackers and tracker not in a.trackers.split(","):
                     continue
                 rec = {"shape": name, "streams": n, "rows": rows, "cols": cols, "tracker": tracker, "blobs": blobs,
                        "steps": a.steps, "warmup": a.warmup}
-                for leg, k in legs:
+                for leg, k, tracks in legs:
                     tr = make(rows, cols, n)
                     if k:
                         tr.set_targets(k)
+                    if tracks:
+                        tr.set_tracks(kalman=dict(dt=0.02, timeout=0.1, sigma_accel=300.0, sigma_noise=0.5), gate=40.0)
                     for t in range(POOL):                                   # the model and the last images settle on the pool
                         tr.track_dev(ptrs[t])
                     rec[f"sync_us_{leg}"] = median_us(lambda t: tr.track_dev(ptrs[t % POOL]), a.steps, a.warmup)
@@ -117,11 +137,13 @@ def main():
                     if k:
                         (tset,) = tr.targets()[-1:]
                         rec[f"n_found_{leg}"] = [f for _, f in tset][:4]
+                    if tracks:
+                        rec[f"ids_{leg}"] = [[r.id for r in cam] for cam in tr.tracks()[-1]][:2]
                     tr.close()
                 out.append(rec)
             del dev
             torch.cuda.empty_cache()
-    print(json.dumps({"tool": "targets_bench" + (" --off-only" if a.off_only else ""),
+    print(json.dumps({"tool": "targets_bench" + (" --tracks" if a.tracks else "") + (" --off-only" if a.off_only else ""),
                       "unit": "us a frame set, host clock around synchronous calls, median",
                       "tree": os.path.relpath(tree, ROOT), "library": os.path.relpath(oat_amd.lib_path(), tree), "shapes": out,
                       "device": torch.cuda.get_device_name(0)}))
