@@ -50,7 +50,8 @@ extern "C" {
  * oatgpu_read_bsub_mask; Bayer RAW8 ingest -- oatgpu_debayer_filter, oatgpu_debayer_dev, oatgpu_set_track_bayer, with the
  * OATGPU_BAYER_* pattern values; RAW8 frames for the motion and the subtraction tracker -- oatgpu_set_tracker_bayer; the filter
  * chain behind the motion and the subtraction tracker -- oatgpu_set_tracker_filters, oatgpu_tracker_filtered; target tracks --
- * oatgpu_set_tracks, oatgpu_tracks, oatgpu_tracks_update, with the struct oatgpu_track. */
+ * oatgpu_set_tracks, oatgpu_tracks, oatgpu_tracks_update, with the struct oatgpu_track; target shapes --
+ * oatgpu_set_target_shapes, oatgpu_target_shapes, with the struct oatgpu_shape. */
 
 enum {
     OATGPU_OK = 0,
@@ -607,7 +608,8 @@ int oatgpu_tracker_filtered(oatgpu_ctx *ctx, oatgpu_filtered *out, int32_t max_s
  * four slots of each batched tracker that is on (one switched on later allocates its own): an out-of-memory is OATGPU_E_NOMEM
  * from this call and leaves a working context.  OATGPU_E_INVALID, with nothing changed, when k is out of range, results are
  * outstanding or a frame set is partly staged, oatgpu_set_deferred is on, or marker sets are configured;
- * oatgpu_set_markers(n > 0) and oatgpu_set_deferred(1) are refused while targets are on. */
+ * oatgpu_set_markers(n > 0) and oatgpu_set_deferred(1) are refused while targets are on.  oatgpu_set_targets itself is refused
+ * while tracks (oatgpu_set_tracks) or target shapes (oatgpu_set_target_shapes) are on: switch them off first. */
 #define OATGPU_MAX_TARGETS 8
 int oatgpu_set_targets(oatgpu_ctx *ctx, int32_t k);          /* 0: off (default) */
 /* The target sets of the frame sets the LATEST result-delivering call handed out: one set for a batch call, a collect or a
@@ -692,6 +694,70 @@ int oatgpu_tracks(oatgpu_ctx *ctx, oatgpu_track *out, int32_t max_sets);
  * This is how the fused tracker, the single-stage detectors and any outside detector reach tracks.  Refused while results are
  * outstanding. */
 int oatgpu_tracks_update(oatgpu_ctx *ctx, const oatgpu_position *targets, oatgpu_track *out);
+
+/* ---- target shapes: second moments, extents and body axis of the K ranked blobs ----
+ * A target is a centroid and an area.  With shapes on, every call that delivers target sets (the list at oatgpu_set_targets)
+ * also delivers, for every rank, the blob's order-2 moments, its bounding box and its orientation axis: one more kernel
+ * (k_blob_shape) behind the frame's ranking, launched only while shapes are on.  The reference keeps m00, m10 and m01 of a
+ * contour only (siftContours); what follows is cv::moments' next three fields and cv::boundingRect of the same contour.
+ *
+ * For every valid rank j of a target set, over the directed edges (x0, y0) -> (x1, y1) of the blob's EXTERNAL contour -- exactly
+ * the edges whose order-0 and order-1 sums are a00, a10 and a01: the unit steps between neighbouring border pixels, one per side
+ * of a pixel that faces the outside background; an edge facing a hole is not one -- with d = x0 * y1 - x1 * y0, in int64:
+ *   a20 += d * (x0 * (x0 + x1) + x1 * x1)
+ *   a11 += d * (x0 * ((y0 + y1) + y0) + x1 * ((y0 + y1) + y1))
+ *   a02 += d * (y0 * (y0 + y1) + y1 * y1)
+ * This is contourMoments of OpenCV 3.1 (imgproc/moments.cpp) over the contour's CHAIN_APPROX_SIMPLE points (the sums over a
+ * straight piece equal the sums over its unit steps), exact in integers; it equals the double sums there wherever those stay
+ * below 2^53.
+ * x_min, y_min, x_max, y_max are the extremes of the contour's pixels; cv::boundingRect is (x_min, y_min, x_max - x_min + 1,
+ * y_max - y_min + 1).
+ *
+ * The derived fields are fp64, use + - * / and sqrt only, one rounding per operation, no contraction.  With sg the sign of a00:
+ *   m00 = a00 * sg 0.5,  m10 = a10 * sg 0.16666666666666666666666666666667,  m01 likewise from a01 (as oatgpu_position forms them)
+ *   m20 = a20 * sg 0.083333333333333333333333333333333
+ *   m11 = a11 * sg 0.041666666666666666666666666666667
+ *   m02 = a02 * sg 0.083333333333333333333333333333333        (multiplications by these constants, as the source has them)
+ *   inv = 1.0 / m00,  cx = m10 * inv,  cy = m01 * inv
+ *   mu20 = m20 - m10 * cx,  mu11 = m11 - m10 * cy,  mu02 = m02 - m01 * cy            (completeMomentState)
+ *   a = mu20 * inv,  b = mu11 * inv,  c = mu02 * inv                                 (the covariance of the blob's area)
+ *   h = (a - c) * 0.5,  r = sqrt(h * h + b * b)
+ *   l1 = (a + c) * 0.5 + r,  l2 = (a + c) * 0.5 - r                                  (its eigenvalues)
+ *   major = 2 * sqrt(max(l1, 0)),  minor = 2 * sqrt(max(l2, 0))                      (max(l, 0): l where l > 0, else +0)
+ * The body axis, the eigenvector of l1:
+ *   v = (h + r, b) if h >= 0, else (b, r - h);  n = sqrt(vx * vx + vy * vy);  axis_valid = n > 0
+ *   axis = (vx / n, vy / n), both components negated if vx < 0, or if vx == 0 and vy < 0.
+ * An axis has no front: the sign rule only makes it unique (axis_x >= 0), it says nothing about where the head is.  A blob
+ * whose covariance is isotropic (a square, a disc) has no axis: axis_valid = 0 and axis = (0, 0).  An invalid rank is all zeros.
+ *
+ * Shapes are read-only passengers: the ordinary results, oatgpu_targets, oatgpu_tracks, both filter chains, taps, models and
+ * every state are bit for bit what they are with shapes off; integer sums make two runs bit-alike.  oatgpu_tracks_update
+ * delivers no shapes.  With tracks on, oatgpu_track.rank indexes the frame's shape set: shapes[(t * n_streams + s) * K +
+ * track.rank] is the shape of the identified animal -- the way to an identity's body axis.
+ *
+ * Left out: a heading inside oatgpu_track with the sign taken from the velocity; shapes on marker planes; third-order and Hu
+ * moments; several GPUs. */
+typedef struct oatgpu_shape {
+    int32_t valid;                 /* the rank's position_valid */
+    int32_t axis_valid;
+    int64_t a20, a11, a02;         /* the exact order-2 sums */
+    int32_t x_min, y_min, x_max, y_max;
+    double mu20, mu11, mu02;       /* central moments */
+    double axis_x, axis_y;         /* unit vector along the body, axis_x >= 0 */
+    double major, minor;           /* 2 * sqrt(eigenvalue): the semi-axes' doubles of the equivalent ellipse, in pixels */
+} oatgpu_shape;                    /* 104 bytes */
+/* on = 1: requires targets on; drains outstanding work; allocates everything here, never in a step -- a shape set and a device
+ * accumulator for every slot that has a target set (the ring's slots and the synchronous detectors' extra one, the four slots of
+ * each batched tracker that is on; one switched on later allocates its own): an out-of-memory is OATGPU_E_NOMEM and leaves a
+ * working context.  A successful call starts the delivered lists over (oatgpu_targets included).  on = 0 frees everything.
+ * OATGPU_E_INVALID, with nothing changed, while results are outstanding or a frame set is partly staged, or targets are off.
+ * While shapes are on, oatgpu_set_targets is refused (switch shapes off first). */
+int oatgpu_set_target_shapes(oatgpu_ctx *ctx, int32_t on);
+/* The shape sets of the frame sets the LATEST result-delivering call handed out, in oatgpu_targets' convention:
+ * out[(t * n_streams + s) * K + j] is rank j of camera s of set t (a single-stage detector: the other streams are invalid).
+ * Returns the number of sets written; nothing is consumed.  OATGPU_E_INVALID when shapes are off, no such call has run since
+ * oatgpu_set_target_shapes, or max_sets is too small. */
+int oatgpu_target_shapes(oatgpu_ctx *ctx, oatgpu_shape *out, int32_t max_sets);
 
 /* Deferred completion of the stage-by-stage operators below (default off).  With on = 1 a frame filter (oatgpu_mog_filter,
  * _bsub_filter, _mask_filter, _thresh_filter, _undistort_filter, _bgr2hsv, _cvt_color) or a detector (oatgpu_detect_hsv / _thresh / _diff)

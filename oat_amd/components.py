@@ -102,6 +102,34 @@ class Track(Filtered):
         return Track(**f.__dict__, id=int(t.id), rank=int(t.rank), age=int(t.age), missed=int(t.missed))
 
 
+@dataclass
+class Shape:
+    """One ranked blob's shape (set_target_shapes; oatgpu_shape in include/oatgpu.h has the exact definitions): the exact order-2
+    sums of its external contour, its bounding box (cv::boundingRect: x_min, y_min, x_max - x_min + 1, y_max - y_min + 1), the
+    central moments, the unit vector along the body (axis_x >= 0: an axis has no front) and the axes of the equivalent ellipse."""
+    valid: bool = False
+    a20: int = 0
+    a11: int = 0
+    a02: int = 0
+    x_min: int = 0
+    y_min: int = 0
+    x_max: int = 0
+    y_max: int = 0
+    mu20: float = 0.0
+    mu11: float = 0.0
+    mu02: float = 0.0
+    axis_valid: bool = False
+    axis_x: float = 0.0
+    axis_y: float = 0.0
+    major: float = 0.0
+    minor: float = 0.0
+
+    @staticmethod
+    def from_c(p):
+        return Shape(bool(p.valid), int(p.a20), int(p.a11), int(p.a02), int(p.x_min), int(p.y_min), int(p.x_max), int(p.y_max),
+                     p.mu20, p.mu11, p.mu02, bool(p.axis_valid), p.axis_x, p.axis_y, p.major, p.minor)
+
+
 def _marker(m):
     """dict(h=(lo,hi), s=(lo,hi), v=(lo,hi), erode=K, dilate=K, area=(a,b)) -- every key optional, the defaults are
     HSVDetector's (all-pass window, erode off, dilate 10, area [0, DBL_MAX)); GREY contexts: h is the intensity window --
@@ -426,6 +454,29 @@ class _Detector(_Context):
             sets = int(m.group(1))           # a sequence call delivered more sets than there was room for
         return [[([Position2D.from_c(out[(t * n + s) * k + j]) for j in range(k)], int(found[t * n + s])) for s in range(n)]
                 for t in range(rc)]
+
+    # -- target shapes (oatgpu_set_target_shapes / oatgpu_target_shapes) --
+    def set_target_shapes(self, on=True):
+        """Second moments, bounding box and body axis of every ranked blob beside every target set (set_targets must be on): one
+        more kernel behind the ranking.  A successful call starts the delivered lists over, targets() included."""
+        self._chk(self.lib.oatgpu_set_target_shapes(self.ctx, 1 if on else 0))
+
+    def target_shapes(self):
+        """oatgpu_target_shapes: the shape sets of the frame sets the latest result-delivering call handed out -- a list with one
+        entry per frame set, each a list with one list of k Shape (rank order, as targets()) per camera.  With tracks on,
+        shapes[track.rank] is the shape of an identified animal.  Nothing is consumed."""
+        n, k, sets = self.n_streams, getattr(self, "_targets_k", 0), 1
+        while True:
+            out = (ffi.Shape * (sets * n * max(k, 1)))()
+            rc = self.lib.oatgpu_target_shapes(self.ctx, out, sets)
+            if rc >= 0:
+                break
+            text = (self.lib.oatgpu_last_error(self.ctx) or b"").decode()
+            m = re.search(r"the latest call delivered (\d+)", text)
+            if not m or int(m.group(1)) <= sets:
+                self._chk(rc)
+            sets = int(m.group(1))
+        return [[[Shape.from_c(out[(t * n + s) * k + j]) for j in range(k)] for s in range(n)] for t in range(rc)]
 
     # -- target tracks (oatgpu_set_tracks / oatgpu_tracks / oatgpu_tracks_update, DESIGN.md 9j) --
     def set_tracks(self, kalman=None, gate=float("inf"), homography=None, regions=None):

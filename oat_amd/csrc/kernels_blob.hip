@@ -1458,4 +1458,223 @@ void launch_blob_rank(const Geom &g, const BlobBuffers &b, double min_area, doub
     else hipLaunchKernelGGL(k_blob_rank<kMaxTargets>, grid, block, 0, st, g, b, min_area, max_area, k, recs, found, first_stream);
 }
 
+// ------------------------------------------------------------ target shapes: order-2 sums and extents of the K ranked blobs ----
+// k_blob_shape runs on the HIP stream of a kBlobGlobal back half directly behind its k_blob_rank, on the same scratch set: one more
+// pass over the border pixels, for the K ranked roots only, launched only while shapes are on (oatgpu_set_target_shapes).
+// What it relies on, and why that still holds the frame's data: fin, trans and carry are written by k_rowscan alone (k_morph,
+//   k_merge, k_green_select, k_blob_lds, k_blob_rank and k_target_tracks only read them); parent is written by k_rowscan (run heads)
+//   and by k_merge's unions and path halving, k_green_select walks it with plain loads (uf_root) and nothing behind k_merge writes
+//   it; every launcher of this file issues these kernels on ONE HIP stream in the order row scan, merge, selection, and the host
+//   launches the ranking and this kernel on that very stream before the set's next row scan (targets_launch, api_targets.hip).  So
+//   all four hold the frame's final data from the end of k_merge until the set's next row scan -- as roots / acc do for k_blob_rank.
+// The edges are k_green_select's, word for word: one directed edge (x0, y0) -> (x1, y1) per side of a foreground pixel that faces
+//   OUTSIDE background (root 0); an edge facing a hole is not one.  With d = x0 y1 - x1 y0, per ranked root, exact in int64:
+//     a20 += d (x0 (x0 + x1) + x1 x1)     a11 += d (x0 ((y0 + y1) + y0) + x1 ((y0 + y1) + y1))     a02 += d (y0 (y0 + y1) + y1 y1)
+//   (contourMoments, imgproc/moments.cpp; the products are formed in 64 bits: a term passes 2^31 from x ~ 900 on), and the extents
+//   are the extremes over the pixels that have a side facing outside.
+// Grid: k_green_select's -- kGreenChunks threads a mask word, blockIdx.y = stream.  A workgroup none of whose chunks holds a border
+//   bit goes straight to the arrival.  Otherwise the K ranked roots (padded indices, from TargetRec.first_pixel) are loaded
+//   once a workgroup, a lane a rank, and read back uniformly from LDS; a border pixel's root is resolved first (the memoised uf_root) and the pixel is skipped unless it is one of the K;
+//   only then are its four sides tested.  Running sums a thread, flushed on a label change into the workgroup's LDS accumulators
+//   (64-bit LDS adds; the extents as unsigned maxima: INT_MAX - min), then ONE round of global atomics a touched rank into
+//   accum[s][k][kShapeAccWords].  The last workgroup of the stream to arrive (k_green_select's arrival pattern: each wave drains
+//   vmcnt before arriving, the accumulator is written and read with agent-scope atomics) writes the stream's k ShapeRec by 64-bit
+//   stores (the shape set may be host-mapped memory) and re-zeroes the accumulator and the counter for the slot's
+//   next launch.  Integer sums and maxima: the result does not depend on the order of arrival.
+static_assert(sizeof(ShapeRec) == 48, "a shape record is six 64-bit words");
+template <int KC>
+__global__ __launch_bounds__(kGreenBlock) void k_blob_shape(Geom g, BlobBuffers b, int k, const TargetRec *__restrict__ recs,
+                                                            u64 *__restrict__ accum, unsigned *__restrict__ arrived,
+                                                            ShapeRec *__restrict__ out, int first_stream)
+{
+    static_assert(KC >= 1 && KC <= kMaxTargets, "at most kMaxTargets ranks");
+    __shared__ int is_last;
+    __shared__ u64 lsum[kMaxTargets * 3];
+    __shared__ unsigned lext[kMaxTargets * 4];
+    __shared__ int lroot[kMaxTargets];
+    const int tt = blockIdx.x * blockDim.x + threadIdx.x;
+    const int t = tt / kGreenChunks;
+    const u64 chunk_bits = (kGreenChunks == 1 ? ~0ull : ((1ull << (64 / kGreenChunks)) - 1ull)) << ((tt % kGreenChunks) * (64 / kGreenChunks));
+    const int s = first_stream + blockIdx.y;
+    const size_t soff = (size_t)s * (g.Palloc >> 6);
+    const u64 *fin = b.fin + soff;
+    const u64 *trans = b.trans + soff;
+    const int *carry = b.carry + (size_t)s * g.H * g.words;
+    const int *parent = b.parent + (size_t)s * g.Palloc;
+    const TargetRec *tr = recs + (size_t)s * k;
+    u64 *gacc = accum + (size_t)s * k * kShapeAccWords;
+
+    if (threadIdx.x < kMaxTargets * 3) lsum[threadIdx.x] = 0ull;
+    if (threadIdx.x < kMaxTargets * 4) lext[threadIdx.x] = 0u;
+
+    u64 cur = 0ull, L = 0ull, R = 0ull, U = 0ull, D = 0ull;
+    int y = 0, w = 0;
+    if (t < (g.H - 2) * g.words) {
+        y = 1 + t / g.words; w = t % g.words;
+        cur = fin[(size_t)y * g.words + w];
+    }
+    u64 cand = 0ull;
+    if ((cur & chunk_bits) != 0ull) {
+        const size_t rc = (size_t)y * g.words;
+        const u64 curP = w > 0 ? fin[rc + w - 1] : 0ull, curN = w + 1 < g.words ? fin[rc + w + 1] : 0ull;
+        U = fin[rc - g.words + w]; D = fin[rc + g.words + w];
+        L = (cur << 1) | (curP >> 63); R = (cur >> 1) | (curN << 63);
+        cand = cur & ~(L & R & U & D) & chunk_bits;
+    }
+    if (__syncthreads_or(cand != 0ull)) {            // (uniform; also the barrier behind the LDS clears)
+        // the K ranked roots: lane j fetches rank j -- the target set may be host-mapped memory, and K loads of one lane, one behind
+        // the other, were K round trips over the link (profiles/shapes_bench.txt) -- and the workgroup reads them back uniformly
+        if (threadIdx.x < kMaxTargets) {
+            int r = -1;
+            if ((int)threadIdx.x < k && tr[threadIdx.x].valid) {
+                const int fp = tr[threadIdx.x].first_pixel, yy = fp / g.W;
+                r = yy * g.Wp + (fp - yy * g.W);
+            }
+            lroot[threadIdx.x] = r;
+        }
+        __syncthreads();
+        int root[KC];
+#pragma unroll
+        for (int j = 0; j < KC; ++j) root[j] = lroot[j];
+        if (cand != 0ull && root[0] >= 0) {
+            const size_t rc = (size_t)y * g.words, ru = rc - g.words, rd = rc + g.words;
+            const bool hp = w > 0, hn = w + 1 < g.words;
+            const u64 upP = hp ? fin[ru + w - 1] : 0ull, upN = hn ? fin[ru + w + 1] : 0ull;
+            const u64 dnP = hp ? fin[rd + w - 1] : 0ull, dnN = hn ? fin[rd + w + 1] : 0ull;
+            const u64 UL = (U << 1) | (upP >> 63), UR = (U >> 1) | (upN << 63);
+            const u64 DL = (D << 1) | (dnP >> 63), DR = (D >> 1) | (dnN << 63);
+            const u64 Tc = trans[rc + w], Tu = trans[ru + w], Td = trans[rd + w];
+            const int cc = carry[rc + w], cu = carry[ru + w], cd = carry[rd + w];
+
+            struct Memo { int head, root; };
+            Memo mo{-1, 0}, ml{-1, 0}, mb{-1, 0}, mr{-1, 0}, mt{-1, 0};
+            auto root_of = [&](Memo &m, int head) -> int {
+                if (head != m.head) { m.head = head; m.root = uf_root(parent, head); }
+                return m.root;
+            };
+            int label = -1, rank = -1;
+            long long s20 = 0, s11 = 0, s02 = 0;
+            int x_lo = 0x7fffffff, x_hi = 0, y_hit = 0;
+            auto flush = [&]() {
+                if (rank >= 0 && y_hit) {
+                    if (s20) atomicAdd((unsigned long long *)&lsum[rank * 3], (unsigned long long)s20);
+                    if (s11) atomicAdd((unsigned long long *)&lsum[rank * 3 + 1], (unsigned long long)s11);
+                    if (s02) atomicAdd((unsigned long long *)&lsum[rank * 3 + 2], (unsigned long long)s02);
+                    atomicMax(&lext[rank * 4], 0x7fffffffu - (unsigned)x_lo);
+                    atomicMax(&lext[rank * 4 + 1], 0x7fffffffu - (unsigned)y);
+                    atomicMax(&lext[rank * 4 + 2], (unsigned)x_hi);
+                    atomicMax(&lext[rank * 4 + 3], (unsigned)y);
+                }
+            };
+            while (cand) {
+                const int i = lsb64(cand);
+                cand &= cand - 1;
+                const int x = w * 64 + i;
+                const u64 bit = 1ull << i;
+                const int lab = root_of(mo, run_head_w(g, Tc, cc, y, w, i));
+                if (lab != label) {
+                    flush();
+                    label = lab; rank = -1;
+#pragma unroll
+                    for (int j = 0; j < KC; ++j) if (lab == root[j]) rank = j;
+                    s20 = s11 = s02 = 0; x_lo = 0x7fffffff; x_hi = 0; y_hit = 0;
+                }
+                if (rank < 0) continue;
+                int qx, qy;
+                bool e, outside = false;
+#define OAT_EDGE2()                                                                                             \
+                if (e) {                                                                                        \
+                    const long long d = (long long)(x * qy - qx * y), sy = y + qy;                              \
+                    s20 += d * ((long long)x * (x + qx) + (long long)qx * qx);                                  \
+                    s11 += d * ((long long)x * (sy + y) + (long long)qx * (sy + qy));                           \
+                    s02 += d * ((long long)y * (y + qy) + (long long)qy * qy);                                  \
+                }
+                if (!(L & bit)) {                                                             // left
+                    const int h = i > 0 ? run_head_w(g, Tc, cc, y, w, i - 1) : run_head(g, trans, carry, y, x - 1);
+                    if (root_of(ml, h) == 0) {
+                        outside = true; e = true;
+                        if (DL & bit) { qx = x - 1; qy = y + 1; } else if (D & bit) { qx = x; qy = y + 1; } else e = false;
+                        OAT_EDGE2()
+                    }
+                }
+                if (!(D & bit) && root_of(mb, run_head_w(g, Td, cd, y + 1, w, i)) == 0) {    // bottom
+                    outside = true; e = true;
+                    if (DR & bit) { qx = x + 1; qy = y + 1; } else if (R & bit) { qx = x + 1; qy = y; } else e = false;
+                    OAT_EDGE2()
+                }
+                if (!(R & bit)) {                                                             // right
+                    const int h = i < 63 ? run_head_w(g, Tc, cc, y, w, i + 1) : run_head(g, trans, carry, y, x + 1);
+                    if (root_of(mr, h) == 0) {
+                        outside = true; e = true;
+                        if (UR & bit) { qx = x + 1; qy = y - 1; } else if (U & bit) { qx = x; qy = y - 1; } else e = false;
+                        OAT_EDGE2()
+                    }
+                }
+                if (!(U & bit) && root_of(mt, run_head_w(g, Tu, cu, y - 1, w, i)) == 0) {    // top
+                    outside = true; e = true;
+                    if (UL & bit) { qx = x - 1; qy = y - 1; } else if (L & bit) { qx = x - 1; qy = y; } else e = false;
+                    OAT_EDGE2()
+                }
+#undef OAT_EDGE2
+                if (outside) { y_hit = 1; x_lo = x < x_lo ? x : x_lo; x_hi = x > x_hi ? x : x_hi; }
+            }
+            flush();
+        }
+        __syncthreads();
+        // one round of global atomics a touched rank
+        if ((int)threadIdx.x < k * 3) {
+            const u64 v = lsum[threadIdx.x];
+            const int j = threadIdx.x / 3, q = threadIdx.x - j * 3;
+            if (v) __hip_atomic_fetch_add(gacc + j * kShapeAccWords + q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else if (threadIdx.x >= 64 && (int)threadIdx.x - 64 < k * 4) {
+            const int i = threadIdx.x - 64, j = i >> 2, q = i & 3;
+            const unsigned v = lext[i];
+            if (v) __hip_atomic_fetch_max(reinterpret_cast<unsigned *>(gacc + j * kShapeAccWords + 3) + q, v, __ATOMIC_RELAXED,
+                                          __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+
+    // ---- arrival; the last workgroup of this stream writes the records ----
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned prev = __hip_atomic_fetch_add(&arrived[s], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        is_last = (prev == gridDim.x - 1) ? 1 : 0;
+    }
+    __syncthreads();
+    if (!is_last) return;
+
+    if ((int)threadIdx.x < k) {
+        const int j = threadIdx.x;
+        u64 *a = gacc + j * kShapeAccWords;
+        u64 v[kShapeAccWords];
+#pragma unroll
+        for (int q = 0; q < kShapeAccWords; ++q) {
+            v[q] = __hip_atomic_load(a + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a + q, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        const bool valid = v[4] != 0ull;      // (a ranked blob has a pixel facing outside, x_max >= 1; an empty rank matched no pixel)
+        u64 *o = reinterpret_cast<u64 *>(out + (size_t)s * k + j);
+        auto put = [&](int i, u64 x) { __hip_atomic_store(o + i, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+        const u64 lim = 0x7fffffffull;
+        put(0, valid ? v[0] : 0ull);
+        put(1, valid ? v[1] : 0ull);
+        put(2, valid ? v[2] : 0ull);
+        put(3, valid ? (lim - (v[3] & 0xffffffffull)) | (lim - (v[3] >> 32)) << 32 : 0ull);      // x_min | y_min << 32
+        put(4, valid ? v[4] : 0ull);                                                              // x_max | y_max << 32
+        put(5, valid ? 1ull : 0ull);
+    }
+    if (threadIdx.x == 0) __hip_atomic_store(&arrived[s], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+void launch_blob_shape(const Geom &g, const BlobBuffers &b, int k, const TargetRec *recs, u64 *accum, unsigned *arrived,
+                       ShapeRec *out, int first_stream, int n_streams, hipStream_t st)
+{
+    const int nw = (g.H > 2 ? (g.H - 2) * g.words : 1) * kGreenChunks;
+    const dim3 grid((nw + kGreenBlock - 1) / kGreenBlock, n_streams), block(kGreenBlock);
+    if (k <= 1) hipLaunchKernelGGL(k_blob_shape<1>, grid, block, 0, st, g, b, k, recs, accum, arrived, out, first_stream);
+    else if (k <= 4) hipLaunchKernelGGL(k_blob_shape<4>, grid, block, 0, st, g, b, k, recs, accum, arrived, out, first_stream);
+    else hipLaunchKernelGGL(k_blob_shape<kMaxTargets>, grid, block, 0, st, g, b, k, recs, accum, arrived, out, first_stream);
+}
+
 }  // namespace oatgpu

@@ -117,11 +117,27 @@ struct MarkerFilters : PosfiltChain {
     bool append = false;                       // inside oatgpu_track_markers_sequence_dev: every collected set is kept
 };
 
+// Target shapes (oatgpu_set_target_shapes; api_shapes.hip).  A shape set is what k_blob_shape writes for one frame
+// set: [n][k] ShapeRec, host-mapped.  ShapeSets owns one for each slot of the TargetSets it stands beside, and the slot's device
+// accumulator and arrival counter (frames in flight sit in different slots, so no two launches share them); everything is made by
+// oatgpu_set_target_shapes (or by a batched tracker switched on while shapes are on), never inside a step.  Empty while shapes are off.
+struct ShapeSets {
+    HostMem<ShapeRec> mem;                     // [slots][n][k]
+    DevMem<u64> accum;                         // [slots][n][k][kShapeAccWords], all zero between launches
+    DevMem<unsigned> arrived;                  // [slots][n], likewise
+    size_t n = 0, k = 0;
+    bool alloc(size_t slots, size_t n_streams, int k_);        // false: hipGetLastError() has the reason
+    ShapeRec *rec_dev(int slot) const { return mem.dev() + (size_t)slot * n * k; }
+    const ShapeRec *rec_host(int slot) const { return mem.host() + (size_t)slot * n * k; }
+    u64 *accum_of(int slot) const { return accum + (size_t)slot * n * k * kShapeAccWords; }
+    unsigned *arrived_of(int slot) const { return arrived + (size_t)slot * n; }
+};
 // Multi-target detection (oatgpu_set_targets; api_targets.hip).  A target set is what k_blob_rank writes for one
 // frame set: [n][k] TargetRec, then [n] candidate counts.  TargetSets owns one for each slot of a result ring, host-mapped;
 // everything is made by oatgpu_set_targets (or by a batched tracker switched on while targets are on), never inside a step.
 struct TargetSets {
     HostMem<char> mem;
+    ShapeSets shp;                             // the shape sets beside the target sets, slot for slot, while shapes are on
     size_t n = 0, k = 0, set_bytes = 0;
     bool alloc(size_t slots, size_t n_streams, int k_);        // false: hipGetLastError() has the reason
     TargetRec *rec_dev(int slot) const { return (TargetRec *)(mem.dev() + (size_t)slot * set_bytes); }
@@ -136,6 +152,8 @@ struct Targets {
     std::vector<int32_t> last_found;           // [sets][n]
     int last_sets = 0;
     bool append = false;                       // inside oatgpu_track_sequence_dev: every collected set is kept
+    bool shapes = false;                       // oatgpu_set_target_shapes: every TargetSets of the context has its ShapeSets
+    std::vector<oatgpu_shape> last_shapes;     // [sets][n][k] beside last, while shapes are on (oatgpu_target_shapes)
 };
 
 // frames a batched tracker has in flight inside its sequence call (run_sequence_in_flight); each sits in a slot of its own
@@ -469,6 +487,12 @@ void tracker_hand_out(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, oa
 int targets_launch(oatgpu_ctx *c, const BlobBuffers &bb, const TargetSets &ts, int slot, int s0, int n, hipStream_t st);
 void targets_begin(oatgpu_ctx *c);
 void targets_keep(oatgpu_ctx *c, const TargetSets &ts, int slot, int only = -1);
+// api_shapes.hip: k_blob_shape behind targets_launch's k_blob_rank into `slot` of ts.shp (called from targets_launch alone), and the
+// shapes' share of the list a delivering call keeps (called from targets_begin / targets_keep, so that every call that delivers
+// targets delivers shapes) -- all do nothing while shapes are off
+int shapes_launch(oatgpu_ctx *c, const BlobBuffers &bb, const TargetSets &ts, int slot, int s0, int n, hipStream_t st);
+void shapes_begin(oatgpu_ctx *c);
+void shapes_keep(oatgpu_ctx *c, const TargetSets &ts, int slot, int only);
 // api_tracks.hip: k_target_tracks on the target set recs of the tracker's slot `slot`, on st right behind its k_blob_rank, into the
 // slot's track set `set`; prev_slot as tracker_filters_launch's.  The list a delivering call keeps (tracks_begin, tracks_keep) and a
 // batched tracker's own track sets (false: hipGetLastError() has the reason).  All do nothing while tracks are off.

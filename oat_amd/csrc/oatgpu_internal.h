@@ -345,6 +345,20 @@ struct TargetRec {   // one ranked blob: ResultRec's first four fields
 void launch_blob_rank(const Geom &g, const BlobBuffers &b, double min_area, double max_area, int k, TargetRec *recs,
                       long long *found, int first_stream, int n_streams, hipStream_t st);
 
+// Target shapes (oatgpu_set_target_shapes; kernels_blob.hip, k_blob_shape): the order-2 Green sums and the extents of
+// the k ranked blobs of every stream -- launched on the same HIP stream directly behind launch_blob_rank, on the same scratch set b
+// and the target set recs it has just written.  out[n][k] may be host-mapped memory (64-bit stores).  accum[n][k][kShapeAccWords]
+// and arrived[n] are device memory that is all zero before the first launch and left all zero by every launch; launches that may
+// run at the same time (frames in flight on several HIP streams) take an accumulator and a counter each.
+constexpr int kShapeAccWords = 5;       // a20, a11, a02, {INT_MAX - x_min, INT_MAX - y_min}, {x_max, y_max}
+struct ShapeRec {    // one ranked blob's raw shape, six 64-bit words
+    long long a20, a11, a02;
+    int x_min, y_min, x_max, y_max;
+    int valid, reserved_;
+};
+void launch_blob_shape(const Geom &g, const BlobBuffers &b, int k, const TargetRec *recs, u64 *accum, unsigned *arrived,
+                       ShapeRec *out, int first_stream, int n_streams, hipStream_t st);
+
 // --- kernels_markers.hip --- (marker sets: M colour windows per camera behind one MOG2 pass, `posicom mean`)
 constexpr int kMaxMarkers = 8;
 struct MarkerCombined {   // device-side record of k_marker_combine, one per stream per step: oatgpu_combined's layout

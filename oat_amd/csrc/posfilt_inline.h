@@ -48,6 +48,47 @@ __host__ __device__ inline bool centroid_of(const ResultRec &r, double &x, doubl
     return true;
 }
 
+// A ranked blob's shape from its exact integer sums (oatgpu_shape, include/oatgpu.h "target shapes": the text there is the
+// contract, this is its one implementation): contourMoments' epilogue for the order-2 moments (m20 = a20 * db1_12, m11 = a11 *
+// db1_24, m02 = a02 * db1_12), completeMomentState's central moments (cx = m10 * inv_m00, mu20 = m20 - m10 * cx, ...), then the
+// covariance's eigenvalues and the eigenvector of the larger one in closed form.  fp64, + - * / sqrt only, one rounding each.
+struct ShapeDerived {
+    double mu20, mu11, mu02, axis_x, axis_y, major, minor;
+    int axis_valid;
+};
+__host__ __device__ inline void shape_of(long long a00_, long long a10_, long long a01_, long long a20_, long long a11_,
+                                         long long a02_, ShapeDerived &o)
+{
+    const double a00 = (double)a00_, a10 = (double)a10_, a01 = (double)a01_;
+    const double a20 = (double)a20_, a11 = (double)a11_, a02 = (double)a02_;
+    const double db1_2 = a00 > 0 ? 0.5 : -0.5;
+    const double db1_6 = a00 > 0 ? 0.16666666666666666666666666666667 : -0.16666666666666666666666666666667;
+    const double db1_12 = a00 > 0 ? 0.083333333333333333333333333333333 : -0.083333333333333333333333333333333;
+    const double db1_24 = a00 > 0 ? 0.041666666666666666666666666666667 : -0.041666666666666666666666666666667;
+    const double m00 = a00 * db1_2, m10 = a10 * db1_6, m01 = a01 * db1_6;
+    const double m20 = a20 * db1_12, m11 = a11 * db1_24, m02 = a02 * db1_12;
+    const double inv = 1.0 / m00;
+    const double cx = m10 * inv, cy = m01 * inv;
+    o.mu20 = m20 - m10 * cx;
+    o.mu11 = m11 - m10 * cy;
+    o.mu02 = m02 - m01 * cy;
+    const double a = o.mu20 * inv, b = o.mu11 * inv, c = o.mu02 * inv;
+    const double h = (a - c) * 0.5;
+    const double r = sqrt(h * h + b * b);
+    const double l1 = (a + c) * 0.5 + r, l2 = (a + c) * 0.5 - r;
+    o.major = 2.0 * sqrt(l1 > 0.0 ? l1 : 0.0);
+    o.minor = 2.0 * sqrt(l2 > 0.0 ? l2 : 0.0);
+    double vx, vy;
+    if (h >= 0.0) { vx = h + r; vy = b; } else { vx = b; vy = r - h; }
+    const double n = sqrt(vx * vx + vy * vy);
+    o.axis_valid = n > 0.0 ? 1 : 0;
+    o.axis_x = 0.0; o.axis_y = 0.0;
+    if (o.axis_valid) {
+        o.axis_x = vx / n; o.axis_y = vy / n;
+        if (vx < 0.0 || (vx == 0.0 && vy < 0.0)) { o.axis_x = -o.axis_x; o.axis_y = -o.axis_y; }
+    }
+}
+
 struct Filter {     // registers copy of one stream's KalmanState
     double statePre[4], statePost[4], Ppre[16], Ppost[16], meas[2], reported[4];
     int found, missing, aliased;

@@ -92,6 +92,14 @@ class Track(C.Structure):
                 ("reserved_", C.c_int32)]
 
 
+class Shape(C.Structure):
+    """oatgpu_shape: second moments, extents and body axis of one ranked blob (oatgpu_set_target_shapes), 104 bytes."""
+    _fields_ = [("valid", C.c_int32), ("axis_valid", C.c_int32), ("a20", C.c_int64), ("a11", C.c_int64), ("a02", C.c_int64),
+                ("x_min", C.c_int32), ("y_min", C.c_int32), ("x_max", C.c_int32), ("y_max", C.c_int32), ("mu20", C.c_double),
+                ("mu11", C.c_double), ("mu02", C.c_double), ("axis_x", C.c_double), ("axis_y", C.c_double), ("major", C.c_double),
+                ("minor", C.c_double)]
+
+
 E_RING_FULL = -4
 E_RING_EMPTY = -5
 ABI_VERSION = 9          # must equal OATGPU_ABI_VERSION of include/oatgpu.h
@@ -158,6 +166,8 @@ SIGNATURES = {
     "oatgpu_set_tracks": (C.c_int, [_ctx, C.POINTER(MarkerFilters), C.c_double]),
     "oatgpu_tracks": (C.c_int, [_ctx, C.POINTER(Track), C.c_int32]),
     "oatgpu_tracks_update": (C.c_int, [_ctx, C.POINTER(Position), C.POINTER(Track)]),
+    "oatgpu_set_target_shapes": (C.c_int, [_ctx, C.c_int32]),
+    "oatgpu_target_shapes": (C.c_int, [_ctx, C.POINTER(Shape), C.c_int32]),
     "oatgpu_mog_apply": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_mog_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_bgr2hsv": (C.c_int, [_ctx, _u8p, _u8p]),

@@ -62,6 +62,7 @@ public:
     std::vector<RegionDef> regions_;
     bool chain_on() const { return kalman_ || homography_on_ || !regions_.empty(); }
     std::vector<std::string> target_sink_addresses_;     // --target-sinks: rank j of every frame on the j-th address
+    bool target_shape_{false};                           // --target-shape: rank j's token carries the blob's body axis as its heading
     std::vector<std::string> track_sink_addresses_;      // --track-sinks: track slot i of every frame on the i-th address
     double track_gate_{HUGE_VAL};                        // --track-gate: pixels (default: no gate)
     // the sinks beside the SINK: the target sinks, then the track sinks
@@ -105,9 +106,11 @@ protected:
         oatgpu_position ranks[OATGPU_MAX_TARGETS];
         int32_t found = 0;
         if (oatgpu_targets(gpu_.ctx, ranks, &found, 1) != 1) gpu_.check(OATGPU_E_INVALID);
+        oatgpu_shape shapes[OATGPU_MAX_TARGETS];
+        if (target_shape_ && oatgpu_target_shapes(gpu_.ctx, shapes, 1) != 1) gpu_.check(OATGPU_E_INVALID);
         for (size_t j = 0; j < K; ++j) {
             target_sinks_[j].wait();
-            *target_shared_[j] = target_position(ranks[j], position.sample());
+            *target_shared_[j] = target_position(ranks[j], position.sample(), target_shape_ ? &shapes[j] : nullptr);
             target_sinks_[j].post();
         }
     }
@@ -159,6 +162,7 @@ protected:
         }
         const size_t n_targets = std::max(target_sink_addresses_.size(), track_sink_addresses_.size());      // (equal where both are given)
         if (n_targets) gpu_.check(oatgpu_set_targets(gpu_.ctx, (int32_t)n_targets));
+        if (target_shape_) gpu_.check(oatgpu_set_target_shapes(gpu_.ctx, 1));
         if (!track_sink_addresses_.empty()) {                // the chain options describe the tracks too
             std::vector<oatgpu_region> rs;
             const oatgpu_marker_filters f = chain_of(rs);
@@ -248,6 +252,9 @@ static void usage()
                  "        goes to sink Tj as a Position2D with the frame's sample, invalid where fewer than j + 1 blobs exist.  Rank 0 is\n"
                  "        the detector's own result; the SINK carries what it carries without the option.  Targets are raw detections:\n"
                  "        a filter chain acts on the SINK only.\n"
+                 "        --target-shape  (with --target-sinks; target-shape = true in a -c file) target shapes: rank j's Position2D also\n"
+                 "        carries the blob's body axis -- the major axis of its second moments, a unit vector with x >= 0: an axis has no\n"
+                 "        front -- as its heading; no heading where the blob has no axis (a square, a disc).\n"
                  "diff, hsv --bsub, thresh --bsub:\n"
                  "        --track-sinks T0,T1,.. [--track-gate PX] --kalman [..] [--homography ..] [--region ..]  (at most 8 names) target\n"
                  "        tracks: K = the number of names persistent track slots behind the K ranked blobs -- each frame's blobs are\n"
@@ -266,7 +273,7 @@ int main(int argc, char **argv)
         Options o = Options::parse(argc, argv,
             {{"H", "h-thresh"}, {"S", "s-thresh"}, {"V", "v-thresh"}, {"T", "thresh"}, {"e", "erode"},
              {"d", is_diff ? "diff-threshold" : "dilate"}, {"b", "blur"}, {"a", "area"}, {"t", "tune"}, {"h", "help"}, {"v", "version"}},
-            {"help", "version", "tune", "bgr", "bsub", "kalman"});
+            {"help", "version", "tune", "bgr", "bsub", "kalman", "target-shape"});
         if (o.has("version")) { std::cout << "oat-posidet-hip (MI355X drop-in, liboatgpu ABI " << oatgpu_abi_version() << ")\n"; return 0; }
         if (o.has("help") || o.positional.size() != 3) { usage(); return o.has("help") ? 0 : -1; }
         const std::string type = o.positional[0];
@@ -274,14 +281,14 @@ int main(int argc, char **argv)
         // option names per TYPE: HSVDetector.cpp:49-75, SimpleThreshold.cpp:49-69, DifferenceDetector.cpp:41-62
         if (type == "hsv")
             o.apply_config({"h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer",
-                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "track-sinks", "track-gate"},
-                           {"tune", "bsub", "kalman"});
+                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "target-shape", "track-sinks", "track-gate"},
+                           {"tune", "bsub", "kalman", "target-shape"});
         else if (type == "thresh")
             o.apply_config({"thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer",
-                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "track-sinks", "track-gate"},
-                           {"tune", "bsub", "kalman"});
+                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "target-shape", "track-sinks", "track-gate"},
+                           {"tune", "bsub", "kalman", "target-shape"});
         else o.apply_config({"diff-threshold", "blur", "area", "tune", "gpu-index", "bgr", "bayer", "camera-matrix", "distortion-coeffs",
-                             "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "track-sinks", "track-gate"}, {"tune", "bgr", "kalman"});
+                             "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "target-shape", "track-sinks", "track-gate"}, {"tune", "bgr", "kalman", "target-shape"});
         if (o.has("bgr") && type != "diff") throw std::runtime_error("--bgr goes with TYPE diff only");
         if (type == "diff" && (o.has("bsub") || o.has("bsub-alpha") || o.has("bsub-background")))
             throw std::runtime_error("--bsub goes with TYPE hsv or thresh only");
@@ -331,6 +338,7 @@ int main(int argc, char **argv)
             const std::vector<std::string> lists = o.all.count("target-sinks") ? o.all["target-sinks"] : target_sink_lists_of_config(o.kv["target-sinks"]);
             target_sinks = check_target_sinks(lists, {o.positional[2]}, false)[0];
         }
+        check_target_shape(o.has("target-shape"), !target_sinks.empty());
         // --track-sinks: the K track slots of every frame, checked before any device is opened
         std::vector<std::string> track_sinks;
         if (o.has("track-gate") && !o.has("track-sinks")) throw std::runtime_error("--track-gate is a parameter of --track-sinks");
@@ -360,6 +368,7 @@ int main(int argc, char **argv)
         std::copy(homography, homography + 9, d->homography_);
         d->regions_ = regions;
         d->target_sink_addresses_ = target_sinks;
+        d->target_shape_ = o.has("target-shape");
         d->track_sink_addresses_ = track_sinks;
         if (o.has("track-gate")) {
             char *end = nullptr;

@@ -204,8 +204,10 @@ public:
         cfg_.h_lo = 0; cfg_.h_hi = 256; cfg_.s_lo = 0; cfg_.s_hi = 256; cfg_.v_lo = 1; cfg_.v_hi = 256;
     }
     // --target-sinks: multi-target detection (oatgpu_set_targets); sinks[s][j] = address of rank j of camera s
-    void set_targets(const std::vector<std::vector<std::string>> &sinks)
+    // shape: --target-shape, rank j's token carries the blob's body axis as its heading (oatgpu_set_target_shapes)
+    void set_targets(const std::vector<std::vector<std::string>> &sinks, bool shape = false)
     {
+        target_shape_ = shape;
         target_sink_addresses_ = sinks;
         targets_k_ = sinks.empty() ? 0 : (int)sinks[0].size();
         target_sinks_ = std::vector<Sink<Position2D>>((size_t)n_ * targets_k_);
@@ -231,6 +233,7 @@ public:
     std::vector<std::vector<std::string>> marker_sink_addresses_;
     std::vector<std::vector<std::string>> target_sink_addresses_;
     int targets_k_{0};              // K of --target-sinks (0: off)
+    bool target_shape_{false};      // --target-shape
     // the filter chain behind the combined record (--mean-kalman / --mean-homography / --region): the camera's SINK then carries
     // the FILTERED Position2D; Kalman parameters are dt_ .. sig_noise_ above
     bool mean_kalman_{false}, mean_homography_on_{false};
@@ -339,6 +342,10 @@ protected:
             }
             target_results_.resize((size_t)n_ * targets_k_);
             target_found_.resize(n_);
+            if (target_shape_) {
+                gpu_.check(oatgpu_set_target_shapes(gpu_.ctx, 1));
+                target_shapes_.resize((size_t)n_ * targets_k_);
+            }
         }
         if (!markers_.empty()) {
             const int M = (int)markers_.size();
@@ -389,7 +396,8 @@ protected:
         position_sinks_[s].post();
         for (int j = 0; j < targets_k_; ++j)                         // rank j of camera s, raw, with the frame's Sample
             put(target_sinks_[(size_t)s * targets_k_ + j], target_shared_[(size_t)s * targets_k_ + j],
-                target_position(target_results_[(size_t)s * targets_k_ + j], pub_samples_[s]));
+                target_position(target_results_[(size_t)s * targets_k_ + j], pub_samples_[s],
+                                target_shape_ ? &target_shapes_[(size_t)s * targets_k_ + j] : nullptr));
     }
     void publish_some(int max_sinks, bool only_if_ready)
     {
@@ -405,6 +413,7 @@ protected:
                 gpu_.check(oatgpu_track_collect(gpu_.ctx, results_.data()));
             if (targets_k_ && oatgpu_targets(gpu_.ctx, target_results_.data(), target_found_.data(), 1) != 1)    // the set just collected
                 gpu_.check(OATGPU_E_INVALID);
+            if (target_shape_ && oatgpu_target_shapes(gpu_.ctx, target_shapes_.data(), 1) != 1) gpu_.check(OATGPU_E_INVALID);
             pub_samples_ = std::move(pending_.front());
             pending_.pop_front();
             collected_ = true;
@@ -564,6 +573,7 @@ protected:
     std::vector<Position2D *> target_shared_;
     std::vector<oatgpu_position> target_results_;      // [n][K] of the result set that is being handed out
     std::vector<int32_t> target_found_;                // [n]
+    std::vector<oatgpu_shape> target_shapes_;          // [n][K] beside target_results_ with --target-shape
     std::deque<std::vector<Sample>> pending_;  // Samples of the frames whose results are still on the device
     std::vector<Sample> pub_samples_;          // ... and of the result set that is being handed out (publish_some)
     bool collected_{false};
@@ -577,7 +587,7 @@ int main(int argc, char **argv)
         Options o = Options::parse(argc, argv,
             {{"a", "adaptation-coeff"}, {"H", "h-thresh"}, {"S", "s-thresh"}, {"V", "v-thresh"}, {"e", "erode"},
              {"d", "dilate"}, {"T", "timeout"}, {"n", "sigma-noise"}, {"f", "mask"}, {"h", "help"}, {"v", "version"}},
-            {"help", "version", "kalman", "timing", "print-partition", "mean-kalman"});
+            {"help", "version", "kalman", "timing", "print-partition", "mean-kalman", "target-shape"});
         if (o.has("version")) { std::cout << "oat-track-hip (MI355X drop-in, liboatgpu ABI " << oatgpu_abi_version() << ")\n"; return 0; }
         if (o.has("help") || o.positional.size() != 2) {
             std::cout << "Usage: oat-track-hip SOURCE[,SOURCE..] SINK[,SINK..] [-a coeff] [-H [lo,hi]] [-S ..] [-V ..] [-e n] [-d n] [--area [min,max]]\n"
@@ -619,6 +629,9 @@ int main(int argc, char **argv)
                          "                            exist.  Rank 0 is the detector's own result; the SINK carries what it carries without the option\n"
                          "                            (--kalman / --homography act on the SINK only).  With or without --ring.  In a -c file:\n"
                          "                            target-sinks = [\"a,b\", \"c,d\"].  Not with --marker or --ingest-root.\n"
+                         "       [--target-shape]     (with --target-sinks; target-shape = true in a -c file) target shapes: rank j's Position2D also\n"
+                         "                            carries the blob's body axis -- the major axis of its second moments, a unit vector with x >= 0:\n"
+                         "                            an axis has no front -- as its heading; no heading where the blob has no axis.\n"
                          "N SOURCEs / N SINKs: N cameras batched into one device pass per frame; SOURCE i feeds SINK i.\n"
                          "--gpu-index N0,N1,..: the cameras are split into contiguous blocks, one per listed device (own context and thread).\n"
                          "--ingest-root D0 (with --gpu-index D0,D1,..): all frames are ingested on device D0 and scattered to their devices\n"
@@ -631,8 +644,8 @@ int main(int argc, char **argv)
         o.apply_config({"adaptation-coeff", "h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "model-file",
                         "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "gpu-index", "ring", "mask", "thresh", "homography", "stage-copy", "timing",
                         "ingest-root", "print-partition", "camera-matrix", "distortion-coeffs", "undistort-key", "marker-sinks", "heading-anchor", "marker-ring",
-                        "mean-kalman", "mean-homography", "bayer", "target-sinks"},
-                       {"kalman", "timing", "print-partition", "mean-kalman"});
+                        "mean-kalman", "mean-homography", "bayer", "target-sinks", "target-shape"},
+                       {"kalman", "timing", "print-partition", "mean-kalman", "target-shape"});
         const std::vector<std::string> sources = split_list(o.positional[0]), sinks = split_list(o.positional[1]);
         if (sources.size() != sinks.size()) throw std::runtime_error("need as many SINKs as SOURCEs");
         // marker sets: --marker (repeatable) or the [[KEY.marker]] tables of the -c file; refused with what the synchronous
@@ -715,6 +728,7 @@ int main(int argc, char **argv)
             target_sinks = check_target_sinks(o.all.count("target-sinks") ? o.all["target-sinks"] : target_sink_lists_of_config(o.kv["target-sinks"]),
                                               sinks, !markers.empty());
         }
+        check_target_shape(o.has("target-shape"), !target_sinks.empty());
         // --gpu-index N | N0,N1,...: one shard of the SOURCE list per listed device (contiguous blocks)
         std::vector<int> devices;
         for (const std::string &d : split_list(o.has("gpu-index") ? o.kv["gpu-index"] : std::string("0"))) {
@@ -817,7 +831,7 @@ int main(int argc, char **argv)
             if (!cals.empty()) t->undistort_.assign(cals.begin() + s0, cals.begin() + s1);
             if (!bayer.empty()) t->bayer_.assign(bayer.begin() + s0, bayer.begin() + s1);
             if (!target_sinks.empty())
-                t->set_targets(std::vector<std::vector<std::string>>(target_sinks.begin() + s0, target_sinks.begin() + s1));
+                t->set_targets(std::vector<std::vector<std::string>>(target_sinks.begin() + s0, target_sinks.begin() + s1), o.has("target-shape"));
             if (!markers.empty())
                 t->set_markers(markers, heading_anchor, std::vector<std::vector<std::string>>(marker_sinks.begin() + s0, marker_sinks.begin() + s1));
             t->dt_ = o.num("dt", 0.02, 0, 1e9);                        // KalmanFilter2D.cpp:69-85 (lower bound 0)

@@ -1,6 +1,7 @@
 // target_sinks.hpp -- `--target-sinks T0,T1,..` of oat-posidet-hip and oat-track-hip (multi-target detection, oatgpu_set_targets):
 // one comma list per camera, K = the list's length, the same for every camera; sink j receives rank j of its camera on every
-// frame.  Everything is checked at start-up, before a device is opened.
+// frame.  With `--target-shape` (target shapes, oatgpu_set_target_shapes) rank j's Position2D also carries the blob's body axis as
+// its heading.  Everything is checked at start-up, before a device is opened.
 #pragma once
 #include "component.hpp"
 
@@ -66,13 +67,26 @@ inline std::vector<std::vector<std::string>> check_target_sinks(const std::vecto
     return out;
 }
 
-// rank j of a camera as the Position2D its sink receives: a detector's token (DetectorFunc.cpp:46,58-60), invalid where the rank is empty
-inline Position2D target_position(const oatgpu_position &r, const Sample &sample)
+// --target-shape without --target-sinks is refused at start-up
+inline void check_target_shape(bool shape, bool have_target_sinks)
+{
+    if (shape && !have_target_sinks)
+        throw std::runtime_error("--target-shape needs --target-sinks: the body axis travels as the heading of the ranked blobs' tokens");
+}
+
+// rank j of a camera as the Position2D its sink receives: a detector's token (DetectorFunc.cpp:46,58-60), invalid where the rank is
+// empty; shape (--target-shape): the rank's oatgpu_shape, whose body axis becomes the token's heading -- an axis has no front, its
+// sign is oatgpu_shape's rule
+inline Position2D target_position(const oatgpu_position &r, const Sample &sample, const oatgpu_shape *shape = nullptr)
 {
     Position2D pos("");
     pos.set_sample(sample);
     pos.position_valid = r.valid != 0;
     if (r.valid) { pos.position.x = r.x; pos.position.y = r.y; }
+    if (shape && shape->valid && shape->axis_valid) {
+        pos.heading_valid = true;
+        pos.heading.x = shape->axis_x; pos.heading.y = shape->axis_y;
+    }
     return pos;
 }
 

@@ -5,6 +5,7 @@ blob kernel and, in the fused tracker, the early / paired launch orders, for the
     python tools/targets_bench.py [--steps 200] [--warmup 20] [--quick]
     python tools/targets_bench.py --off-only --tree DIR      # the off legs alone with the package of another checkout (the parent)
     python tools/targets_bench.py --tracks [--off-only --tree DIR]      # what target tracks cost on top of targets
+    python tools/targets_bench.py --target-shapes [--off-only --tree DIR]      # what target shapes cost on top of targets
 
 Shapes: 1 x 4K, 16 x 1080p and 1 x 640x480, BGR frames in device memory; the fused tracker (HotPath, bench.py's detector) and the
 motion tracker (diff_threshold 16, blur 2); frames with ONE blob a camera and with TWELVE (squares of the disc colour, 8 .. 30
@@ -25,6 +26,11 @@ brightness of the difference), the same shapes and legs; per K = 4 and 8: target
 context), then tracks on (kalman dt 0.02 timeout 0.1 sigma-accel 300 sigma-noise 0.5, gate 40 pixels).  The added us a frame
 set is tracks minus off.  With --off-only the tracks-off legs alone: they need nothing newer than oatgpu_set_targets, so the
 parent commit's tree (--tree) runs them.  The recipe and the figures' place are in profiles/tracks_bench.txt.
+
+--target-shapes measures target shapes (oatgpu_set_target_shapes) instead: the fused and the motion tracker, the same shapes,
+blobs and legs; per K = 4 and 8: targets on with shapes off, off once more (a new context), then shapes on.  The added us a frame
+set is shapes minus off.  With --off-only the shapes-off legs alone, which the parent commit's tree (--tree) runs too.  (--shapes
+is the list of frame shapes.)  The recipe and the figures' place are in profiles/shapes_bench.txt.
 
 Without a GPU the tool fails (no fallback)."""
 import argparse
@@ -76,6 +82,7 @@ def main():
     ap.add_argument("--quick", action="store_true", help="few steps (a rehearsal)")
     ap.add_argument("--off-only", action="store_true", help="the two off legs alone: nothing that needs oatgpu_set_targets")
     ap.add_argument("--tracks", action="store_true", help="target tracks on top of targets K = 4, 8 (motion and subtraction tracker)")
+    ap.add_argument("--target-shapes", action="store_true", help="target shapes on top of targets K = 4, 8 (fused and motion tracker)")
     ap.add_argument("--shapes", default="", help="comma list of shape names (default: all)")
     ap.add_argument("--trackers", default="", help="fused, motion or both (default)")
     ap.add_argument("--blobs", default="1,12", help="blobs a camera, comma list")
@@ -103,12 +110,14 @@ def main():
     def subtraction(rows, cols, n):
         return oat_amd.SubtractionTracker(rows, cols, n_streams=n, channels=3, alpha=0.0, v_thresh=(60, 256), erode=0, dilate=3, area=AREA)
 
-    # (leg, K, tracks on)
+    # (leg, K, tracks or shapes on)
     legs = [("off", 0, False), ("off_again", 0, False)] + ([] if a.off_only else [("k1", 1, False), ("k4", 4, False), ("k8", 8, False)])
     trackers = (("fused", fused), ("motion", motion))
     if a.tracks:
         legs = [(f"k{k}_{leg}", k, leg == "tracks") for k in (4, 8) for leg in ("off", "off_again") + (() if a.off_only else ("tracks",))]
         trackers = (("motion", motion), ("subtraction", subtraction))
+    if a.target_shapes:
+        legs = [(f"k{k}_{leg}", k, leg == "shapes") for k in (4, 8) for leg in ("off", "off_again") + (() if a.off_only else ("shapes",))]
     out = []
     for name, n, rows, cols in SHAPES:
         if a.shapes and name not in a.shapes.split(","):
@@ -124,10 +133,13 @@ def main():
                     continue
                 rec = {"shape": name, "streams": n, "rows": rows, "cols": cols, "tracker": tracker, "blobs": blobs,
                        "steps": a.steps, "warmup": a.warmup}
-                for leg, k, tracks in legs:
+                for leg, k, extra in legs:
+                    tracks, shapes = extra and a.tracks, extra and a.target_shapes
                     tr = make(rows, cols, n)
                     if k:
                         tr.set_targets(k)
+                    if shapes:
+                        tr.set_target_shapes()
                     if tracks:
                         tr.set_tracks(kalman=dict(dt=0.02, timeout=0.1, sigma_accel=300.0, sigma_noise=0.5), gate=40.0)
                     for t in range(POOL):                                   # the model and the last images settle on the pool
@@ -137,13 +149,15 @@ def main():
                     if k:
                         (tset,) = tr.targets()[-1:]
                         rec[f"n_found_{leg}"] = [f for _, f in tset][:4]
+                    if shapes:
+                        rec[f"axes_{leg}"] = [sum(r.axis_valid for r in cam) for cam in tr.target_shapes()[-1]][:4]
                     if tracks:
                         rec[f"ids_{leg}"] = [[r.id for r in cam] for cam in tr.tracks()[-1]][:2]
                     tr.close()
                 out.append(rec)
             del dev
             torch.cuda.empty_cache()
-    print(json.dumps({"tool": "targets_bench" + (" --tracks" if a.tracks else "") + (" --off-only" if a.off_only else ""),
+    print(json.dumps({"tool": "targets_bench" + (" --tracks" if a.tracks else "") + (" --target-shapes" if a.target_shapes else "") + (" --off-only" if a.off_only else ""),
                       "unit": "us a frame set, host clock around synchronous calls, median",
                       "tree": os.path.relpath(tree, ROOT), "library": os.path.relpath(oat_amd.lib_path(), tree), "shapes": out,
                       "device": torch.cuda.get_device_name(0)}))
