@@ -51,7 +51,8 @@ extern "C" {
  * OATGPU_BAYER_* pattern values; RAW8 frames for the motion and the subtraction tracker -- oatgpu_set_tracker_bayer; the filter
  * chain behind the motion and the subtraction tracker -- oatgpu_set_tracker_filters, oatgpu_tracker_filtered; target tracks --
  * oatgpu_set_tracks, oatgpu_tracks, oatgpu_tracks_update, with the struct oatgpu_track; target shapes --
- * oatgpu_set_target_shapes, oatgpu_target_shapes, with the struct oatgpu_shape. */
+ * oatgpu_set_target_shapes, oatgpu_target_shapes, with the struct oatgpu_shape; target crops -- oatgpu_set_target_crops,
+ * oatgpu_target_crops, oatgpu_crop_windows_dev, with the struct oatgpu_crop_window and the OATGPU_CROP_* modes. */
 
 enum {
     OATGPU_OK = 0,
@@ -758,6 +759,78 @@ int oatgpu_set_target_shapes(oatgpu_ctx *ctx, int32_t on);
  * Returns the number of sets written; nothing is consumed.  OATGPU_E_INVALID when shapes are off, no such call has run since
  * oatgpu_set_target_shapes, or max_sets is too small. */
 int oatgpu_target_shapes(oatgpu_ctx *ctx, oatgpu_shape *out, int32_t max_sets);
+
+/* ---- target crops: a frame window around every ranked blob, upright or turned to the body axis ----
+ * Targets, tracks and shapes deliver numbers.  With crops on, the batch and sequence calls of the motion and the subtraction
+ * tracker (the six calls that advance tracks) also deliver an h x w window of the INPUT frame for every rank of every camera
+ * and frame: one more kernel (k_target_crops) behind the frame's ranking (and k_blob_shape), launched only while crops are on.
+ * A 64 x 64 window per animal can follow its result to the host at rates a whole frame cannot.  oatgpu_crop_windows_dev cuts
+ * windows at caller-given centres and axes; it is how the fused tracker, the single-stage detectors and any outside detector
+ * reach crops.  The reference has nothing like this: the semantics are this project's own.
+ *
+ * Window geometry.  A window is (valid, cx, cy, ax, ay, upright) over an H x W frame of C interleaved channels (C = 1 or 3, the
+ * context's channels).  Output pixel (i, j) -- row i of h, column j of w -- uses u = (double)(j - w / 2) and
+ * v = (double)(i - h / 2), with integer division.
+ *   Upright:  X0 = (int)rint(cx) - w / 2,  Y0 = (int)rint(cy) - h / 2   (rint rounds half to even, as cvRound does)
+ *             out(i, j) = frame(Y0 + i, X0 + j); every pixel outside the frame is 0.
+ *   Axis:     all fp64, one rounding per operation, no contraction:
+ *             X = (cx + u * ax) - v * ay,   Y = (cy + u * ay) + v * ax
+ *             qx = (int)rint(X * 32.0),  sx = qx >> 5 (arithmetic shift),  fx = qx & 31;  qy, sy, fy likewise from Y
+ *             out(i, j) = (sum S * p + 512) >> 10 over the four corners (sx, sy), (sx + 1, sy), (sx, sy + 1), (sx + 1, sy + 1)
+ *             with the weights (32 - fx)(32 - fy), fx (32 - fy), (32 - fx) fy, fx fy -- `framefilt undistort`'s pixel rule
+ *             (INTER_LINEAR in OpenCV's fixed point); corners outside the frame are 0 (BORDER_CONSTANT 0); each channel on its
+ *             own.  A position that is not finite, or whose |rint(X * 32.0)| or |rint(Y * 32.0)| reaches 2^30, lies outside
+ *             every frame: the pixel is 0.
+ *   Invalid:  h * w * C zeros.  Every byte of every window is written by every launch: a stale crop never survives in a slot.
+ * A window whose centre or axis is NaN or infinite, or whose |cx| or |cy| exceeds 1e6, is invalid (qx cannot overflow).
+ *
+ * In the trackers the window of rank j has valid = the rank's valid; (cx, cy) exactly what oatgpu_position.x / .y carry for the
+ * rank; in axis mode (ax, ay) = oatgpu_shape.axis_x / .axis_y where the rank's shape has axis_valid = 1 -- the body axis lies
+ * along the window's +x; axis_x >= 0, so a window is never turned by more than 90 degrees either way, and the axis still has no
+ * front.  A rank without an axis (a square) takes the upright rule as it stands.  Crops are cut from the frame as the caller gave
+ * it, before the ROI mask and before anything the front kernel does to it.  With tracks on, oatgpu_track.rank indexes the
+ * frame's crop set exactly as it indexes the shape set: the way to one small video per identified animal.
+ *
+ * Crops are read-only passengers: the ordinary results, oatgpu_targets, oatgpu_target_shapes, oatgpu_tracks, both filter chains,
+ * taps, models and every state are bit for bit what they are with crops off.  The fused tracker's own calls and the single-stage
+ * detectors deliver no crops: with crops on they behave as with crops off, exactly as they do for tracks.
+ *
+ * Left out: crops inside the fused tracker's own batch, ring and sequence calls and in oat-track-hip (ring frames may be
+ * overwritten after oatgpu_track_input_consumed); crops from RAW8 or undistorted front ends; crops delivered into device memory
+ * or a torch tensor; crops on marker planes; scaling, or a window turned by the velocity's sign; several GPUs. */
+#define OATGPU_CROP_OFF 0
+#define OATGPU_CROP_UPRIGHT 1
+#define OATGPU_CROP_AXIS 2
+#define OATGPU_CROP_MAX_SIDE 256
+#define OATGPU_CROP_MAX_WINDOWS 8      /* per_stream of oatgpu_crop_windows_dev */
+/* mode OATGPU_CROP_OFF switches crops off (the default) and frees everything; h and w are not looked at.  Otherwise:
+ * 1 <= h <= 256, 4 <= w <= 256, w % 4 == 0; requires targets on, OATGPU_CROP_AXIS requires target shapes on; drains outstanding
+ * work; allocates everything here, never in a step -- a crop set beside every target set of each batched tracker that is on
+ * (one switched on later allocates its own), in page-locked host-mapped memory: an out-of-memory is OATGPU_E_NOMEM and leaves a
+ * working context.  A successful call starts the delivered lists over, as oatgpu_set_target_shapes does.  OATGPU_E_INVALID, with
+ * nothing changed, when a parameter is out of range, results are outstanding or a frame set is partly staged, targets (or, for
+ * OATGPU_CROP_AXIS, shapes) are off, or oatgpu_set_tracker_bayer or oatgpu_set_tracker_undistort is on.  While crops are on,
+ * those two switches and oatgpu_set_targets are refused, and oatgpu_set_target_shapes(0) is refused in axis mode. */
+int oatgpu_set_target_crops(oatgpu_ctx *ctx, int32_t mode, int32_t h, int32_t w);
+/* The crop sets of the frame sets the LATEST delivering call handed out (one set for a batch call, n_frames for a sequence
+ * call), in oatgpu_targets' convention: out[(((t * n_streams + s) * K + j) * h + i) * w * C + x * C + c] is channel c of pixel
+ * (i, x) of rank j of camera s of set t.  Returns the number of sets written; nothing is consumed.  OATGPU_E_INVALID when crops
+ * are off, no such call has run since oatgpu_set_target_crops (or the latest delivering call was not one of the six), or
+ * max_sets is too small. */
+int oatgpu_target_crops(oatgpu_ctx *ctx, uint8_t *out, int32_t max_sets);
+typedef struct oatgpu_crop_window {
+    int32_t valid;                 /* 0: the window is h * w * C zeros */
+    int32_t upright;               /* != 0: the upright rule, (ax, ay) is not used (but must be finite) */
+    double cx, cy;                 /* the centre, in frame pixels */
+    double ax, ay;                 /* the direction of the window's +x; used as given, not normalised */
+} oatgpu_crop_window;              /* 40 bytes */
+/* One synchronous step: per_stream (1..OATGPU_CROP_MAX_WINDOWS) windows for each of the context's n_streams frames.  frames_dev:
+ * n_streams * rows * cols * channels bytes in device memory, stream-major, any alignment; win[s * per_stream + q] and
+ * out[((s * per_stream + q) * h + i) * w * C + ...] are on the host.  The size limits of oatgpu_set_target_crops; needs no
+ * switch and touches nothing a switch owns (its buffers are made, and grown, by the call: OATGPU_E_NOMEM).  Refused while
+ * results are outstanding. */
+int oatgpu_crop_windows_dev(oatgpu_ctx *ctx, const void *frames_dev, const oatgpu_crop_window *win, int32_t per_stream,
+                            int32_t h, int32_t w, uint8_t *out);
 
 /* Deferred completion of the stage-by-stage operators below (default off).  With on = 1 a frame filter (oatgpu_mog_filter,
  * _bsub_filter, _mask_filter, _thresh_filter, _undistort_filter, _bgr2hsv, _cvt_color) or a detector (oatgpu_detect_hsv / _thresh / _diff)

@@ -478,6 +478,64 @@ class _Detector(_Context):
             sets = int(m.group(1))
         return [[[Shape.from_c(out[(t * n + s) * k + j]) for j in range(k)] for s in range(n)] for t in range(rc)]
 
+    # -- target crops (oatgpu_set_target_crops / oatgpu_target_crops / oatgpu_crop_windows_dev) --
+    def _crop_shape(self, *lead):
+        return lead + ((3,) if self.channels == 3 else ())
+
+    def set_target_crops(self, h, w=None, axis=False):
+        """An h x w window of the input frame around every ranked blob beside every target set of the motion and the subtraction
+        tracker (set_targets must be on; axis=True turns each window so that the blob's body axis lies along its +x and needs
+        set_target_shapes).  set_target_crops(None) switches crops off.  1 <= h <= 256, 4 <= w <= 256, w a multiple of 4.  A
+        successful call starts the delivered lists over, targets() and target_shapes() included."""
+        if h is None:
+            self._chk(self.lib.oatgpu_set_target_crops(self.ctx, ffi.CROP_OFF, 0, 0))
+            self._crop_hw = None
+            return
+        w = h if w is None else w
+        self._chk(self.lib.oatgpu_set_target_crops(self.ctx, ffi.CROP_AXIS if axis else ffi.CROP_UPRIGHT, int(h), int(w)))
+        self._crop_hw = (int(h), int(w))
+
+    def target_crops(self):
+        """oatgpu_target_crops: the crop sets of the frame sets the latest track / track_dev / track_sequence_dev call of a
+        batched tracker handed out -- a uint8 array [sets, n_streams, k, h, w] (GREY) or [sets, n_streams, k, h, w, 3]; rank
+        order as targets(), zeros where a rank is empty.  With tracks on, crops[t, s, track.rank] is the window of an
+        identified animal.  Nothing is consumed."""
+        n, k, sets = self.n_streams, getattr(self, "_targets_k", 0), 1
+        h, w = getattr(self, "_crop_hw", None) or (1, 4)
+        while True:
+            out = np.empty(self._crop_shape(sets, n, max(k, 1), h, w), np.uint8)
+            rc = self.lib.oatgpu_target_crops(self.ctx, ffi.u8(out), sets)
+            if rc >= 0:
+                break
+            text = (self.lib.oatgpu_last_error(self.ctx) or b"").decode()
+            m = re.search(r"the latest call delivered (\d+)", text)
+            if not m or int(m.group(1)) <= sets:
+                self._chk(rc)
+            sets = int(m.group(1))
+        return out[:rc]
+
+    def crop_windows(self, frames_dev, windows, h, w):
+        """oatgpu_crop_windows_dev: h x w windows at given centres and axes from one frame set in device memory (frames_dev: the
+        device address of n_streams * rows * cols * channels bytes, stream-major, any alignment).  windows: one list per camera,
+        all of one length 1..8, of ffi.CropWindow or (valid, upright, cx, cy, ax, ay).  Returns a uint8 array
+        [n_streams, per_stream, h, w] or [..., 3]; an invalid window is zeros."""
+        n = self.n_streams
+        if len(windows) != n:
+            raise ValueError(f"expected windows of {n} cameras, got {len(windows)}")
+        per = len(windows[0])
+        if any(len(cam) != per for cam in windows):
+            raise ValueError("every camera takes the same number of windows")
+        arr = (ffi.CropWindow * max(n * per, 1))()
+        for s, cam in enumerate(windows):
+            for q, win in enumerate(cam):
+                if not isinstance(win, ffi.CropWindow):
+                    valid, upright, cx, cy, ax, ay = win
+                    win = ffi.CropWindow(int(bool(valid)), int(bool(upright)), float(cx), float(cy), float(ax), float(ay))
+                arr[s * per + q] = win
+        out = np.empty(self._crop_shape(n, max(per, 1), max(int(h), 1), max(int(w), 1)), np.uint8)
+        self._chk(self.lib.oatgpu_crop_windows_dev(self.ctx, C.c_void_p(frames_dev), arr, per, int(h), int(w), ffi.u8(out)))
+        return out
+
     # -- target tracks (oatgpu_set_tracks / oatgpu_tracks / oatgpu_tracks_update, DESIGN.md 9j) --
     def set_tracks(self, kalman=None, gate=float("inf"), homography=None, regions=None):
         """oatgpu_set_tracks: k persistent track slots per camera (k of set_targets, which must be on) behind the ranked

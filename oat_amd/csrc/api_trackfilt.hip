@@ -19,6 +19,7 @@ bool BatchedTrackerState::alloc(const oatgpu_ctx *c)
     ok = ok && rec.alloc(K * n * sizeof(ResultRec), hipHostMallocMapped) == hipSuccess;
     ok = ok && (!c->tg.k || tgt.alloc(K, n, c->tg.k));
     ok = ok && (!c->tg.shapes || tgt.shp.alloc(K, n, c->tg.k));
+    ok = ok && (!c->tg.crop_mode || tgt.crp.alloc(K, n, c->tg.k, c->tg.crop_h, c->tg.crop_w, c->cfg.channels));
     ok = ok && (!c->tk.on || tracks_alloc_sets(c, trk, c->tk.k));
     // (the taps: words beyond the frame are never written by the back half)
     ok = ok && hipMemsetAsync(bits, 0, K * words * 8, c->stream) == hipSuccess;

@@ -132,12 +132,27 @@ struct ShapeSets {
     u64 *accum_of(int slot) const { return accum + (size_t)slot * n * k * kShapeAccWords; }
     unsigned *arrived_of(int slot) const { return arrived + (size_t)slot * n; }
 };
+// Target crops (oatgpu_set_target_crops; api_crops.hip).  A crop set is what k_target_crops writes for one frame set:
+// [n][k][h][w][channels] bytes, host-mapped.  CropSets owns one for each slot of the TargetSets it stands beside -- a batched
+// tracker's: the fused tracker and the single-stage detectors deliver no crops, their target sets have none -- and remembers the
+// frame set each slot's front launch read (tracker_front).  Everything is made by oatgpu_set_target_crops (or by a batched tracker
+// switched on while crops are on), never inside a step.  Empty while crops are off.
+struct CropSets {
+    HostMem<uint8_t> mem;                      // [slots][n][k][h][w][channels]
+    size_t set_bytes = 0;
+    const uint8_t *frame[4] = {};              // [kSeqSlots] the frame set of the slot, as the caller gave it
+    bool alloc(size_t slots, size_t n_streams, int k, int h, int w, int channels);     // false: hipGetLastError() has the reason
+    bool on() const { return mem.host() != nullptr; }
+    uint8_t *set_dev(int slot) const { return mem.dev() + (size_t)slot * set_bytes; }
+    const uint8_t *set_host(int slot) const { return mem.host() + (size_t)slot * set_bytes; }
+};
 // Multi-target detection (oatgpu_set_targets; api_targets.hip).  A target set is what k_blob_rank writes for one
 // frame set: [n][k] TargetRec, then [n] candidate counts.  TargetSets owns one for each slot of a result ring, host-mapped;
 // everything is made by oatgpu_set_targets (or by a batched tracker switched on while targets are on), never inside a step.
 struct TargetSets {
     HostMem<char> mem;
     ShapeSets shp;                             // the shape sets beside the target sets, slot for slot, while shapes are on
+    CropSets crp;                              // the crop sets beside them, while crops are on (a batched tracker's sets only)
     size_t n = 0, k = 0, set_bytes = 0;
     bool alloc(size_t slots, size_t n_streams, int k_);        // false: hipGetLastError() has the reason
     TargetRec *rec_dev(int slot) const { return (TargetRec *)(mem.dev() + (size_t)slot * set_bytes); }
@@ -154,6 +169,12 @@ struct Targets {
     bool append = false;                       // inside oatgpu_track_sequence_dev: every collected set is kept
     bool shapes = false;                       // oatgpu_set_target_shapes: every TargetSets of the context has its ShapeSets
     std::vector<oatgpu_shape> last_shapes;     // [sets][n][k] beside last, while shapes are on (oatgpu_target_shapes)
+    int crop_mode = 0, crop_h = 0, crop_w = 0; // oatgpu_set_target_crops: OATGPU_CROP_*, the window
+    std::vector<uint8_t> last_crops;           // [crop_sets][n][k][h][w][channels] what the latest delivering call delivered (oatgpu_target_crops)
+    int last_crop_sets = 0;                    // (a call of the fused tracker or a single-stage detector delivers none)
+    HostMem<CropWin> cw_win;                   // host-mapped: [n][kCropMaxWindows] the table of oatgpu_crop_windows_dev ...
+    HostMem<uint8_t> cw_out;                   // ... and its windows, [cw_bytes]; made and grown by that call
+    size_t cw_bytes = 0;
 };
 
 // frames a batched tracker has in flight inside its sequence call (run_sequence_in_flight); each sits in a slot of its own
@@ -493,6 +514,12 @@ void targets_keep(oatgpu_ctx *c, const TargetSets &ts, int slot, int only = -1);
 int shapes_launch(oatgpu_ctx *c, const BlobBuffers &bb, const TargetSets &ts, int slot, int s0, int n, hipStream_t st);
 void shapes_begin(oatgpu_ctx *c);
 void shapes_keep(oatgpu_ctx *c, const TargetSets &ts, int slot, int only);
+// api_crops.hip: k_target_crops behind shapes_launch into `slot` of ts.crp, from the frame set the slot remembers (called from
+// targets_launch alone), and the crops' share of the list a delivering call keeps (called from targets_begin / targets_keep) -- all
+// do nothing while crops are off or for a target set without crop sets
+int crops_launch(oatgpu_ctx *c, const TargetSets &ts, int slot, int s0, int n, hipStream_t st);
+void crops_begin(oatgpu_ctx *c);
+void crops_keep(oatgpu_ctx *c, const TargetSets &ts, int slot);
 // api_tracks.hip: k_target_tracks on the target set recs of the tracker's slot `slot`, on st right behind its k_blob_rank, into the
 // slot's track set `set`; prev_slot as tracker_filters_launch's.  The list a delivering call keeps (tracks_begin, tracks_keep) and a
 // batched tracker's own track sets (false: hipGetLastError() has the reason).  All do nothing while tracks are off.
@@ -532,9 +559,12 @@ static inline size_t track_in_bytes(const oatgpu_ctx *c) { return (size_t)c->g.H
 static inline size_t tracker_in_bytes(const oatgpu_ctx *c) { return (size_t)c->g.H * c->g.W * (c->tb_on ? 1 : c->cfg.channels); }
 // ... and what the front launch of either takes from the context: frame set f1 (f2: and the next) into the bits of `slot` (and
 // slot2), the ROI, the Bayer patterns with oatgpu_set_tracker_bayer on, the streams' maps with oatgpu_set_tracker_undistort on
-static inline void tracker_front(const oatgpu_ctx *c, const BatchedTrackerState &bt, const void *f1, const void *f2, int slot, int slot2, FrontLaunch &a)
+// (the slots' crop sets remember their frame set here: k_target_crops cuts from it behind the slot's ranking)
+static inline void tracker_front(const oatgpu_ctx *c, BatchedTrackerState &bt, const void *f1, const void *f2, int slot, int slot2, FrontLaunch &a)
 {
     a.frames = (const uint8_t *)f1; a.frames2 = (const uint8_t *)f2; a.channels = c->cfg.channels;
+    bt.tgt.crp.frame[slot] = a.frames;
+    if (f2) bt.tgt.crp.frame[slot2] = a.frames2;
     a.bits = bt.bits_of(slot); a.bits2 = f2 ? bt.bits_of(slot2) : nullptr;
     a.roi = c->roi;
     a.bayer = c->tb_on ? c->tb_pat.data() : nullptr;

@@ -359,6 +359,25 @@ struct ShapeRec {    // one ranked blob's raw shape, six 64-bit words
 void launch_blob_shape(const Geom &g, const BlobBuffers &b, int k, const TargetRec *recs, u64 *accum, unsigned *arrived,
                        ShapeRec *out, int first_stream, int n_streams, hipStream_t st);
 
+// --- kernels_crops.hip --- (target crops: a frame window around every ranked blob, oatgpu_set_target_crops)
+constexpr int kCropMaxSide = 256;      // 1 <= h <= 256, 4 <= w <= 256, w % 4 == 0
+constexpr int kCropMaxWindows = 8;     // windows a stream of oatgpu_crop_windows_dev
+struct CropWin { int valid, upright; double cx, cy, ax, ay; };      // one explicit window, five 64-bit words: oatgpu_crop_window's layout
+struct CropLaunch {
+    const uint8_t *frames;   // [n_streams][H*W*channels] packed BGR (3) or GREY (1), stream-major; any alignment
+    int channels;
+    int h, w;                // the window
+    int k;                   // windows a stream
+    int axis;                // records: 1 turns the window of a rank that has a body axis (shp is not null)
+    const TargetRec *recs;   // [n_streams][k] a target set (may be host-mapped memory) ...
+    const ShapeRec *shp;     // ... with the shape set beside it, or nullptr
+    const CropWin *win;      // recs == nullptr: [n_streams][k] explicit windows (may be host-mapped memory)
+    uint8_t *out;            // [n_streams][k][h][w][channels], 4-byte aligned (may be host-mapped memory: 32-bit stores)
+};
+// One launch for every window of every stream: workgroups over (row block, window, stream), a lane 4 output pixels of one row.
+// A window's record is fetched once a workgroup; every byte of every window is written, zeros where the window is invalid.
+void launch_target_crops(const Geom &g, const CropLaunch &a, int n_streams, hipStream_t st);
+
 // --- kernels_markers.hip --- (marker sets: M colour windows per camera behind one MOG2 pass, `posicom mean`)
 constexpr int kMaxMarkers = 8;
 struct MarkerCombined {   // device-side record of k_marker_combine, one per stream per step: oatgpu_combined's layout

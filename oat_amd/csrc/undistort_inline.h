@@ -19,12 +19,12 @@ struct __attribute__((packed)) ua_u16 { uint16_t v; };
 __device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) { return ((const ua_u32 *)p)->v; }
 __device__ __forceinline__ uint32_t ld_u16(const uint8_t *p) { return ((const ua_u16 *)p)->v; }
 
-// one output pixel of an H x W frame of CH interleaved channels from its map entry (m1, m2)
+// one output pixel of an H x W frame of CH interleaved channels from the source corner (sx, sy) and the fractions (fx, fy) in
+// 1/32 px, 0..31: the rule itself, for remap_px below and for k_target_crops (kernels_crops.hip), whose windows compute their
+// own source positions
 template <int CH>
-__device__ __forceinline__ void remap_px(const uint8_t *__restrict__ src, int H, int W, uint32_t m1, uint32_t m2, uint32_t out[CH])
+__device__ __forceinline__ void remap_core(const uint8_t *__restrict__ src, int H, int W, int sx, int sy, int fx, int fy, uint32_t out[CH])
 {
-    const int sx = (int)(int16_t)(m1 & 0xffffu), sy = (int)(int16_t)(m1 >> 16);
-    const int fx = (int)(m2 & 31u), fy = (int)((m2 >> 5) & 31u);
     const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;   // BilinearTab_i / 32
     uint32_t s00[CH], s01[CH], s10[CH], s11[CH];
     if ((unsigned)sx < (unsigned)(W - 1) && (unsigned)sy < (unsigned)(H - 1)) {
@@ -53,6 +53,13 @@ __device__ __forceinline__ void remap_px(const uint8_t *__restrict__ src, int H,
     }
     for (int c = 0; c < CH; ++c)
         out[c] = (s00[c] * w00 + s01[c] * w01 + s10[c] * w10 + s11[c] * w11 + 512u) >> 10;
+}
+
+// ... from its map entry (m1, m2)
+template <int CH>
+__device__ __forceinline__ void remap_px(const uint8_t *__restrict__ src, int H, int W, uint32_t m1, uint32_t m2, uint32_t out[CH])
+{
+    remap_core<CH>(src, H, W, (int)(int16_t)(m1 & 0xffffu), (int)(int16_t)(m1 >> 16), (int)(m2 & 31u), (int)((m2 >> 5) & 31u), out);
 }
 
 // The map entries of the 4 output pixels from raster position i on: one 16-byte and one 8-byte load.  i % 4 == 0; the planes

@@ -100,10 +100,18 @@ class Shape(C.Structure):
                 ("minor", C.c_double)]
 
 
+class CropWindow(C.Structure):
+    """oatgpu_crop_window: one window of oatgpu_crop_windows_dev -- centre, direction of the window's +x, upright or not; 40 bytes."""
+    _fields_ = [("valid", C.c_int32), ("upright", C.c_int32), ("cx", C.c_double), ("cy", C.c_double), ("ax", C.c_double),
+                ("ay", C.c_double)]
+
+
 E_RING_FULL = -4
 E_RING_EMPTY = -5
 ABI_VERSION = 9          # must equal OATGPU_ABI_VERSION of include/oatgpu.h
 MAX_TARGETS = 8          # OATGPU_MAX_TARGETS
+CROP_OFF, CROP_UPRIGHT, CROP_AXIS = 0, 1, 2      # OATGPU_CROP_*
+CROP_MAX_SIDE, CROP_MAX_WINDOWS = 256, 8         # OATGPU_CROP_MAX_SIDE, OATGPU_CROP_MAX_WINDOWS
 TAP_THRESHOLD, TAP_MORPH, TAP_FINAL = 0, 1, 2
 BAYER_RGGB, BAYER_BGGR, BAYER_GRBG, BAYER_GBRG = 1, 2, 3, 4      # OATGPU_BAYER_*: the tile at rows 0-1, columns 0-1
 
@@ -168,6 +176,9 @@ SIGNATURES = {
     "oatgpu_tracks_update": (C.c_int, [_ctx, C.POINTER(Position), C.POINTER(Track)]),
     "oatgpu_set_target_shapes": (C.c_int, [_ctx, C.c_int32]),
     "oatgpu_target_shapes": (C.c_int, [_ctx, C.POINTER(Shape), C.c_int32]),
+    "oatgpu_set_target_crops": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32]),
+    "oatgpu_target_crops": (C.c_int, [_ctx, _u8p, C.c_int32]),
+    "oatgpu_crop_windows_dev": (C.c_int, [_ctx, C.c_void_p, C.POINTER(CropWindow), C.c_int32, C.c_int32, C.c_int32, _u8p]),
     "oatgpu_mog_apply": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_mog_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_bgr2hsv": (C.c_int, [_ctx, _u8p, _u8p]),

@@ -20,11 +20,16 @@
 //                 diff [--bgr|--bayer P], hsv --bsub, thresh --bsub with --track-sinks T0,T1,.. --kalman ..: target tracks
 //                 (oatgpu_set_tracks): K = the list's length persistent track slots behind the K ranked blobs; sink i carries slot
 //                 i's filtered Position2D on every frame, invalid while the slot is empty -- the slot is the identity on the wire
+//                 diff [--bgr], hsv --bsub, thresh --bsub with --crop-sinks C0,C1,.. --crop-size HxW [--crop-axis] beside
+//                 --target-sinks or --track-sinks: target crops (oatgpu_set_target_crops): frame sink j carries rank j's H x W window
+//                 of the SOURCE frame (with --track-sinks: the window of the rank track slot j took) in the source's colour with
+//                 the frame's Sample on every frame, zeros where there is none
 // Same positional arguments and option names as src/positiondetector/main.cpp:85-271.
 #include "component.hpp"
 #include "filter_chain.hpp"
 #include "target_sinks.hpp"
 
+#include <algorithm>
 #include <cfloat>
 
 using namespace oat;
@@ -65,6 +70,9 @@ public:
     bool target_shape_{false};                           // --target-shape: rank j's token carries the blob's body axis as its heading
     std::vector<std::string> track_sink_addresses_;      // --track-sinks: track slot i of every frame on the i-th address
     double track_gate_{HUGE_VAL};                        // --track-gate: pixels (default: no gate)
+    std::vector<std::string> crop_sink_addresses_;       // --crop-sinks: rank j's (track slot j's) window of every frame on the j-th address
+    int crop_h_{0}, crop_w_{0};                          // --crop-size HxW
+    bool crop_axis_{false};                              // --crop-axis: the window is turned to the blob's body axis
     // the sinks beside the SINK: the target sinks, then the track sinks
     std::vector<std::string> extra_sink_addresses() const
     {
@@ -81,7 +89,45 @@ protected:
             return PositionDetector::connectToNode();
         } catch (...) {
             bind_target_sinks(false);
+            bind_crop_sinks(false);
             throw;
+        }
+    }
+    // the crop sinks: frame sinks of crop_h_ x crop_w_ pixels in the source's colour
+    void bind_crop_sinks(bool loud)
+    {
+        const size_t bytes = (size_t)crop_h_ * crop_w_ * color_bytes(required_color_);
+        if (crop_sinks_.empty()) crop_sinks_ = std::vector<Sink<Frame>>(crop_sink_addresses_.size());
+        for (size_t j = crop_shared_.size(); j < crop_sinks_.size(); ++j) {
+            try {
+                crop_sinks_[j].bind(crop_sink_addresses_[j], bytes);
+                crop_shared_.push_back(crop_sinks_[j].retrieve((size_t)crop_h_, (size_t)crop_w_, color_cvtype(required_color_), required_color_));
+            } catch (...) {
+                if (loud) throw;
+                return;
+            }
+        }
+    }
+    // the frame's windows to their sinks, every one with the frame's Sample: rank j's on sink j, or, with track sinks, the window
+    // of the rank slot j took this frame; zeros where there is none
+    void publish_crops(const Position2D &position)
+    {
+        const size_t C = crop_sink_addresses_.size();
+        if (!C) return;
+        const size_t K = std::max(target_sink_addresses_.size(), track_sink_addresses_.size());
+        const size_t bytes = (size_t)crop_h_ * crop_w_ * color_bytes(required_color_);
+        crop_set_.resize(K * bytes);
+        if (oatgpu_target_crops(gpu_.ctx, crop_set_.data(), 1) != 1) gpu_.check(OATGPU_E_INVALID);
+        oatgpu_track slots[OATGPU_MAX_TARGETS];
+        const bool by_track = !track_sink_addresses_.empty();
+        if (by_track && oatgpu_tracks(gpu_.ctx, slots, 1) != 1) gpu_.check(OATGPU_E_INVALID);
+        for (size_t j = 0; j < C; ++j) {
+            const int rank = by_track ? (slots[j].id ? slots[j].rank : -1) : (int)j;
+            crop_sinks_[j].wait();
+            if (rank >= 0) memcpy(crop_shared_[j].data(), crop_set_.data() + (size_t)rank * bytes, bytes);
+            else memset(crop_shared_[j].data(), 0, bytes);
+            crop_shared_[j].sample() = position.sample();
+            crop_sinks_[j].post();
         }
     }
     void bind_target_sinks(bool loud)
@@ -168,7 +214,10 @@ protected:
             const oatgpu_marker_filters f = chain_of(rs);
             gpu_.check(oatgpu_set_tracks(gpu_.ctx, &f, track_gate_));
         }
+        if (!crop_sink_addresses_.empty())
+            gpu_.check(oatgpu_set_target_crops(gpu_.ctx, crop_axis_ ? OATGPU_CROP_AXIS : OATGPU_CROP_UPRIGHT, crop_h_, crop_w_));
         if (n_targets) bind_target_sinks(true);
+        bind_crop_sinks(true);
     }
     // HSVDetector.cpp:142-173 / SimpleThreshold.cpp:114-134
     // Deferred (oatgpu_set_deferred): the call returns when the frame has left shared memory, PositionDetector::process posts
@@ -208,6 +257,7 @@ protected:
         }
         publish_targets(position);
         publish_tracks(position);
+        publish_crops(position);
     }
     Kind kind_;
     bool bgr_, bsub_;
@@ -218,6 +268,9 @@ protected:
     GpuCtx gpu_;
     std::vector<Sink<Position2D>> target_sinks_;         // [K] (after gpu_: the sinks go END before the context is destroyed)
     std::vector<Position2D *> target_shared_;
+    std::vector<Sink<Frame>> crop_sinks_;                // [C] frame sinks behind them
+    std::vector<Frame> crop_shared_;
+    std::vector<uint8_t> crop_set_;                      // the frame's crop set, [K][h][w][channels]
 };
 
 static void usage()
@@ -262,7 +315,15 @@ static void usage()
                  "        Kalman filter expects its object, new objects take free slots.  Sink Ti carries slot i's filtered Position2D\n"
                  "        with the frame's sample on every frame (position, velocity, region, WORLD units under a homography), invalid\n"
                  "        while the slot is empty: the slot is the identity.  Switches targets on itself; the chain options describe\n"
-                 "        both the SINK's chain and the tracks.  With --target-sinks too, both lists have the same length.\n";
+                 "        both the SINK's chain and the tracks.  With --target-sinks too, both lists have the same length.\n"
+                 "diff [--bgr], hsv --bsub, thresh --bsub:\n"
+                 "        --crop-sinks C0,C1,.. --crop-size HxW [--crop-axis]  (beside --target-sinks or --track-sinks; at most K names;\n"
+                 "        crop-sinks = \"C0,C1\", crop-size = \"64x64\", crop-axis = true in a -c file) target crops: frame sink Cj carries\n"
+                 "        the H x W window of the SOURCE frame around rank j's centroid, in the source's colour with the frame's sample,\n"
+                 "        on every frame; zeros where the rank is empty.  1 <= H <= 256, 4 <= W <= 256, W a multiple of 4.  --crop-axis\n"
+                 "        (needs --target-shape) turns each window so that the blob's body axis lies along its +x; a blob without an\n"
+                 "        axis keeps the upright window.  With --track-sinks, sink Ci carries the window of the rank track slot i took,\n"
+                 "        zeros while the slot has none: the sink is the identity.  Not with --bayer or --camera-matrix.\n";
 }
 
 int main(int argc, char **argv)
@@ -273,7 +334,7 @@ int main(int argc, char **argv)
         Options o = Options::parse(argc, argv,
             {{"H", "h-thresh"}, {"S", "s-thresh"}, {"V", "v-thresh"}, {"T", "thresh"}, {"e", "erode"},
              {"d", is_diff ? "diff-threshold" : "dilate"}, {"b", "blur"}, {"a", "area"}, {"t", "tune"}, {"h", "help"}, {"v", "version"}},
-            {"help", "version", "tune", "bgr", "bsub", "kalman", "target-shape"});
+            {"help", "version", "tune", "bgr", "bsub", "kalman", "target-shape", "crop-axis"});
         if (o.has("version")) { std::cout << "oat-posidet-hip (MI355X drop-in, liboatgpu ABI " << oatgpu_abi_version() << ")\n"; return 0; }
         if (o.has("help") || o.positional.size() != 3) { usage(); return o.has("help") ? 0 : -1; }
         const std::string type = o.positional[0];
@@ -281,14 +342,15 @@ int main(int argc, char **argv)
         // option names per TYPE: HSVDetector.cpp:49-75, SimpleThreshold.cpp:49-69, DifferenceDetector.cpp:41-62
         if (type == "hsv")
             o.apply_config({"h-thresh", "s-thresh", "v-thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer",
-                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "target-shape", "track-sinks", "track-gate"},
-                           {"tune", "bsub", "kalman", "target-shape"});
+                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "target-shape", "track-sinks", "track-gate", "crop-sinks", "crop-size", "crop-axis"},
+                           {"tune", "bsub", "kalman", "target-shape", "crop-axis"});
         else if (type == "thresh")
             o.apply_config({"thresh", "erode", "dilate", "area", "tune", "gpu-index", "bsub", "bsub-alpha", "bsub-background", "bayer",
-                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "target-shape", "track-sinks", "track-gate"},
-                           {"tune", "bsub", "kalman", "target-shape"});
+                            "camera-matrix", "distortion-coeffs", "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "target-shape", "track-sinks", "track-gate", "crop-sinks", "crop-size", "crop-axis"},
+                           {"tune", "bsub", "kalman", "target-shape", "crop-axis"});
         else o.apply_config({"diff-threshold", "blur", "area", "tune", "gpu-index", "bgr", "bayer", "camera-matrix", "distortion-coeffs",
-                             "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "target-shape", "track-sinks", "track-gate"}, {"tune", "bgr", "kalman", "target-shape"});
+                             "kalman", "dt", "timeout", "sigma-accel", "sigma-noise", "homography", "target-sinks", "target-shape", "track-sinks", "track-gate", "crop-sinks", "crop-size", "crop-axis"},
+                            {"tune", "bgr", "kalman", "target-shape", "crop-axis"});
         if (o.has("bgr") && type != "diff") throw std::runtime_error("--bgr goes with TYPE diff only");
         if (type == "diff" && (o.has("bsub") || o.has("bsub-alpha") || o.has("bsub-background")))
             throw std::runtime_error("--bsub goes with TYPE hsv or thresh only");
@@ -354,11 +416,44 @@ int main(int argc, char **argv)
                 throw std::runtime_error("--track-sinks names " + std::to_string(track_sinks.size()) + " sinks, --target-sinks " +
                                          std::to_string(target_sinks.size()) + ": K is one number");
         }
+        // --crop-sinks: the ranks' (the track slots') windows of every frame, checked before any device is opened
+        std::vector<std::string> crop_sinks;
+        int crop_h = 0, crop_w = 0;
+        if ((o.has("crop-size") || o.has("crop-axis")) && !o.has("crop-sinks"))
+            throw std::runtime_error("--crop-size and --crop-axis are parameters of --crop-sinks");
+        if (o.has("crop-sinks")) {
+            if (type != "diff" && !o.has("bsub"))
+                throw std::runtime_error("--crop-sinks with TYPE " + type + " needs --bsub: crops are cut behind the batched trackers (diff, hsv "
+                                         "--bsub, thresh --bsub), not behind the single-stage detector");
+            if (bayer || undistort)
+                throw std::runtime_error("--crop-sinks does not go with --bayer or --camera-matrix / --distortion-coeffs: crops are cut from "
+                                         "the frame as the SOURCE serves it");
+            if (target_sinks.empty() && track_sinks.empty())
+                throw std::runtime_error("--crop-sinks needs --target-sinks or --track-sinks: a window is cut around a ranked blob");
+            const std::vector<std::string> lists = o.all.count("crop-sinks") ? o.all["crop-sinks"] : target_sink_lists_of_config(o.kv["crop-sinks"]);
+            std::vector<std::string> taken = target_sinks;
+            taken.insert(taken.end(), track_sinks.begin(), track_sinks.end());
+            crop_sinks = check_target_sinks(lists, {o.positional[2]}, false, "--crop-sinks", taken)[0];
+            const size_t k = std::max(target_sinks.size(), track_sinks.size());
+            if (crop_sinks.size() > k)
+                throw std::runtime_error("--crop-sinks names " + std::to_string(crop_sinks.size()) + " sinks for " + std::to_string(k) +
+                                         " ranked blobs: at most K");
+            if (o.has("crop-axis") && !o.has("target-shape"))
+                throw std::runtime_error("--crop-axis needs --target-shape: the window is turned to the body axis of the blob's shape");
+            if (!o.has("crop-size")) throw std::runtime_error("--crop-sinks needs --crop-size HxW");
+            std::string size = o.kv.at("crop-size");
+            size.erase(std::remove_if(size.begin(), size.end(), [](char ch) { return ch == '"' || ch == '\''; }), size.end());
+            char x = 0, rest = 0;
+            if (sscanf(size.c_str(), "%d%c%d%c", &crop_h, &x, &crop_w, &rest) != 3 || (x != 'x' && x != 'X'))
+                throw std::runtime_error("--crop-size: expected HxW, got '" + size + "'");
+            if (crop_h < 1 || crop_h > OATGPU_CROP_MAX_SIDE || crop_w < 4 || crop_w > OATGPU_CROP_MAX_SIDE || crop_w % 4 != 0)
+                throw std::runtime_error("--crop-size: a window is 1..256 rows by 4..256 columns, the columns a multiple of 4 (got '" + size + "')");
+        }
         if (o.has("tune")) throw std::runtime_error("--tune needs a GUI and is not available in the hip detector");
         auto d = std::make_unique<GpuDetector>(o.positional[1], o.positional[2],
                                                type == "hsv" ? Kind::HSV : type == "thresh" ? Kind::THRESH : Kind::DIFF,
                                                o.has("bgr") || (bayer && type == "diff"), o.has("bsub"), bayer,
-                                               undistort ? &cal : nullptr, filters || !track_sinks.empty());
+                                               undistort ? &cal : nullptr, filters || !track_sinks.empty() || !crop_sinks.empty());
         d->kalman_ = o.has("kalman");
         d->dt_ = o.num("dt", 0.02, 0, 1e9);                         // KalmanFilter2D.cpp:69-85 (lower bound 0)
         d->timeout_ = o.num("timeout", 0.0, 0, 1e18);
@@ -370,6 +465,9 @@ int main(int argc, char **argv)
         d->target_sink_addresses_ = target_sinks;
         d->target_shape_ = o.has("target-shape");
         d->track_sink_addresses_ = track_sinks;
+        d->crop_sink_addresses_ = crop_sinks;
+        d->crop_h_ = crop_h; d->crop_w_ = crop_w;
+        d->crop_axis_ = o.has("crop-axis");
         if (o.has("track-gate")) {
             char *end = nullptr;
             const std::string g = o.kv.at("track-gate");
