@@ -52,7 +52,9 @@ extern "C" {
  * chain behind the motion and the subtraction tracker -- oatgpu_set_tracker_filters, oatgpu_tracker_filtered; target tracks --
  * oatgpu_set_tracks, oatgpu_tracks, oatgpu_tracks_update, with the struct oatgpu_track; target shapes --
  * oatgpu_set_target_shapes, oatgpu_target_shapes, with the struct oatgpu_shape; target crops -- oatgpu_set_target_crops,
- * oatgpu_target_crops, oatgpu_crop_windows_dev, with the struct oatgpu_crop_window and the OATGPU_CROP_* modes. */
+ * oatgpu_target_crops, oatgpu_crop_windows_dev, with the struct oatgpu_crop_window and the OATGPU_CROP_* modes; crop tensors --
+ * oatgpu_set_target_crop_tensor, oatgpu_target_crop_tensor_sets, oatgpu_crop_tensor_windows_dev, with the struct
+ * oatgpu_crop_tensor_fmt and the OATGPU_TENSOR_* dtypes. */
 
 enum {
     OATGPU_OK = 0,
@@ -796,8 +798,8 @@ int oatgpu_target_shapes(oatgpu_ctx *ctx, oatgpu_shape *out, int32_t max_sets);
  * detectors deliver no crops: with crops on they behave as with crops off, exactly as they do for tracks.
  *
  * Left out: crops inside the fused tracker's own batch, ring and sequence calls and in oat-track-hip (ring frames may be
- * overwritten after oatgpu_track_input_consumed); crops from RAW8 or undistorted front ends; crops delivered into device memory
- * or a torch tensor; crops on marker planes; scaling, or a window turned by the velocity's sign; several GPUs. */
+ * overwritten after oatgpu_track_input_consumed); crops from RAW8 or undistorted front ends; crops on marker planes; a window
+ * turned by the velocity's sign; several GPUs.  (Crops in device memory, and scaling: crop tensors, below.) */
 #define OATGPU_CROP_OFF 0
 #define OATGPU_CROP_UPRIGHT 1
 #define OATGPU_CROP_AXIS 2
@@ -831,6 +833,81 @@ typedef struct oatgpu_crop_window {
  * results are outstanding. */
 int oatgpu_crop_windows_dev(oatgpu_ctx *ctx, const void *frames_dev, const oatgpu_crop_window *win, int32_t per_stream,
                             int32_t h, int32_t w, uint8_t *out);
+
+/* ---- crop tensors: target windows in device memory, zoomed and converted for a network ----
+ * Target crops end in page-locked host memory.  A pose network or a closed-loop classifier runs on the GPU that cut them, and
+ * wants them there, in its number format, at its scale.  With crop tensors on, the same six calls -- the batch and sequence calls
+ * of the motion and the subtraction tracker -- also write, for every frame set, rank and camera, a window into DEVICE memory the
+ * caller owns: one more kernel (k_crop_tensor) behind the frame's ranking (k_blob_shape, k_target_crops), launched only while the
+ * switch is on; no byte crosses the host link.  oatgpu_crop_tensor_windows_dev is the explicit form.  The reference has nothing
+ * like this: the semantics are this project's own.
+ *
+ * A crop tensor element is a window of "target crops" above, followed by a conversion.
+ *
+ * Window.  With zoom == 1.0 the window of rank j is exactly the window of target crops for the mode: OATGPU_CROP_UPRIGHT the copy
+ * around the rounded centroid; OATGPU_CROP_AXIS the axis rule where the rank's shape has axis_valid, else the upright rule.  With
+ * any other zoom it is ALWAYS the axis (gather) rule above, along (ax, ay) = (zoom * axis_x, zoom * axis_y) in axis mode where the
+ * rank has an axis, and along (zoom, 0.0) otherwise -- each product one fp64 multiply; the direction is then used as given, not
+ * normalised, exactly as oatgpu_crop_window's.  zoom is in source pixels per output pixel: zoom = 2 shows a 128 x 128 region of the
+ * frame in a 64 x 64 window, zoom = 0.5 a 32 x 32 region.  This is point-sampled bilinear, not an area filter: every output pixel
+ * is the fixed-point interpolation of the four frame pixels around ONE position, so a zoom above 1 skips pixels and aliases as any
+ * point sampling does.  1/16 <= zoom <= 16, and zoom must be finite.  An invalid window and every pixel outside the frame give the
+ * uint8 value 0 before the conversion, as in target crops.
+ *
+ * Conversion, by oatgpu_crop_tensor_fmt.dtype; p is the window's uint8 value, C the context's channels, in the frame's order (BGR;
+ * GREY contexts have C = 1):
+ *   OATGPU_TENSOR_U8:   p itself, interleaved [h][w][C]: at zoom == 1 byte for byte the layout and content of oatgpu_target_crops.
+ *                       scale and bias are not used (but must be finite).
+ *   OATGPU_TENSOR_F32:  planar [C][h][w]; the value is fl32(fl32((float)p * scale[c]) + bias[c]) -- two fp32 roundings, no fused
+ *                       multiply-add.
+ *   OATGPU_TENSOR_F16:  planar [C][h][w]; that fp32 value rounded to nearest even to IEEE half.
+ * An invalid window therefore holds bias[c] (as fp32 or half), not 0.
+ *
+ * Crop tensors are read-only passengers: the ordinary results, oatgpu_targets, oatgpu_target_shapes, oatgpu_target_crops,
+ * oatgpu_tracks, both filter chains, taps, models and every state are bit for bit what they are with the switch off.  The fused
+ * tracker's own calls and the single-stage detectors deliver none: with the switch on they behave as with it off, as with crops.
+ * The switch is independent of oatgpu_set_target_crops: either, both or neither may be on, and they may differ in size and mode; a
+ * context with only tensors on has no host-mapped crop sets and pays for no store into them.
+ *
+ * Left out: tensors inside the fused tracker's own calls and in the host binaries; RAW8 or undistorted front ends; an
+ * area-filtered downscale; RGB channel order; marker planes; several GPUs. */
+#define OATGPU_TENSOR_U8 0
+#define OATGPU_TENSOR_F16 1
+#define OATGPU_TENSOR_F32 2
+typedef struct oatgpu_crop_tensor_fmt {
+    int32_t dtype;                 /* OATGPU_TENSOR_U8 | _F16 | _F32 */
+    int32_t reserved;              /* 0 */
+    float scale[3], bias[3];       /* per channel, in the frame's order; a GREY context uses [0] */
+} oatgpu_crop_tensor_fmt;          /* 32 bytes */
+/* mode OATGPU_CROP_OFF switches crop tensors off (the default); nothing else is looked at.  Otherwise h, w within the limits of
+ * oatgpu_set_target_crops, zoom and fmt as above, and out_dev: CALLER-OWNED DEVICE memory of capacity_sets (>= 1) entries of
+ * n_streams * K * C * h * w elements of the dtype, 16-byte aligned.  The library never allocates, frees or copies it; the caller
+ * keeps it alive and unchanged in place until the switch is off.  Frame set t of a delivering call is written into entry t -- one
+ * entry for a batch call, n_frames for a sequence call -- in oatgpu_targets' order: element
+ * (((t * n_streams + s) * K + j) * C + c) * h * w + i * w + x for F16 / F32, ((((t * n_streams + s) * K + j) * h + i) * w + x) * C + c
+ * for U8.  Every element of such an entry is written on every launch (a stale window never survives); entries past the delivered
+ * count are not touched.  The entry is complete when the call returns.  A sequence call of more frames than capacity_sets is
+ * refused with OATGPU_E_INVALID before anything is launched and with nothing changed.
+ * Requires targets on, OATGPU_CROP_AXIS target shapes on; drains outstanding work; allocates nothing.  OATGPU_E_INVALID, with
+ * nothing changed, when a parameter is out of range (mode, h, w; a dtype that is none of the three; reserved != 0; a zoom outside
+ * 1/16 .. 16 or not finite; a scale or bias that is not finite; out_dev null or not 16-byte aligned; capacity_sets < 1), results
+ * are outstanding or a frame set is partly staged, targets (or, for OATGPU_CROP_AXIS, shapes) are off, or
+ * oatgpu_set_tracker_bayer or oatgpu_set_tracker_undistort is on.  While the switch is on, those two switches and
+ * oatgpu_set_targets are refused, and oatgpu_set_target_shapes(0) is refused in axis mode. */
+int oatgpu_set_target_crop_tensor(oatgpu_ctx *ctx, int32_t mode, int32_t h, int32_t w, double zoom,
+                                  const oatgpu_crop_tensor_fmt *fmt, void *out_dev, int32_t capacity_sets);
+/* The number of entries the LATEST delivering call wrote (1 for a batch call, n_frames for a sequence call).  OATGPU_E_INVALID when
+ * crop tensors are off, or no such call has run since oatgpu_set_target_crop_tensor (or the latest delivering call was not one of
+ * the six). */
+int oatgpu_target_crop_tensor_sets(oatgpu_ctx *ctx);
+/* The explicit form, one synchronous step like oatgpu_crop_windows_dev: per_stream (1..OATGPU_CROP_MAX_WINDOWS) windows for each
+ * of the context's n_streams frames.  The table win[s * per_stream + q] is on the host; there is no zoom argument -- the caller
+ * puts the zoom into (ax, ay) of a window that is not upright.  out_dev: n_streams * per_stream entries of C * h * w elements in
+ * device memory, 16-byte aligned, complete when the call returns.  Needs no switch and touches nothing a switch owns (its table is
+ * made by the first call: OATGPU_E_NOMEM).  It is how the fused tracker, the single-stage detectors and any outside detector
+ * reach tensors.  Refused while results are outstanding. */
+int oatgpu_crop_tensor_windows_dev(oatgpu_ctx *ctx, const void *frames_dev, const oatgpu_crop_window *win, int32_t per_stream,
+                                   int32_t h, int32_t w, const oatgpu_crop_tensor_fmt *fmt, void *out_dev);
 
 /* Deferred completion of the stage-by-stage operators below (default off).  With on = 1 a frame filter (oatgpu_mog_filter,
  * _bsub_filter, _mask_filter, _thresh_filter, _undistort_filter, _bgr2hsv, _cvt_color) or a detector (oatgpu_detect_hsv / _thresh / _diff)

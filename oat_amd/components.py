@@ -536,6 +536,87 @@ class _Detector(_Context):
         self._chk(self.lib.oatgpu_crop_windows_dev(self.ctx, C.c_void_p(frames_dev), arr, per, int(h), int(w), ffi.u8(out)))
         return out
 
+    # -- crop tensors (oatgpu_set_target_crop_tensor / oatgpu_target_crop_tensor_sets / oatgpu_crop_tensor_windows_dev) --
+    _TENSOR_DTYPES = {"uint8": ffi.TENSOR_U8, "float16": ffi.TENSOR_F16, "float32": ffi.TENSOR_F32}
+
+    def _tensor_fmt(self, dtype, scale, bias):
+        name = str(dtype).replace("torch.", "")
+        if name not in self._TENSOR_DTYPES:
+            raise ValueError(f"dtype must be 'uint8', 'float16' or 'float32', got {dtype!r}")
+
+        def three(v, what):
+            v = [float(x) for x in (v if hasattr(v, "__len__") else [v] * self.channels)]
+            if len(v) != self.channels:
+                raise ValueError(f"{what}: a scalar or one value per channel ({self.channels}), got {len(v)}")
+            return (C.c_float * 3)(*(v + [v[-1]] * (3 - len(v))))
+        return name, ffi.CropTensorFmt(self._TENSOR_DTYPES[name], 0, three(scale, "scale"), three(bias, "bias"))
+
+    def _tensor_shape(self, name, lead, h, w):
+        return tuple(lead) + ((h, w, self.channels) if name == "uint8" else (self.channels, h, w))
+
+    def _torch_device(self):
+        import torch
+        return torch.device("cuda", self.cfg.device)
+
+    def set_target_crop_tensor(self, h, w=None, axis=False, zoom=1.0, dtype="float16", scale=1.0, bias=0.0, capacity=1):
+        """Crop tensors: the windows of set_target_crops as a torch tensor on the context's device, written by the same track /
+        track_dev / track_sequence_dev calls of a batched tracker with no host round trip (set_targets must be on; axis=True needs
+        set_target_shapes).  zoom: source pixels per output pixel (1/16 .. 16; not 1: always the bilinear gather, point-sampled).
+        dtype "float16" / "float32": planar values float32(float32(p * scale[c]) + bias[c]), scale and bias scalars or one value
+        per channel in the frame's order (BGR); "uint8": the window's bytes.  Allocates a zeroed tensor
+        [capacity, n_streams, k, C, h, w] ([capacity, n_streams, k, h, w, C] for "uint8"; C = 1 for GREY contexts), keeps it alive
+        and returns it; frame set t of a call lands in entry t, so a sequence call takes at most `capacity` frames.
+        set_target_crop_tensor(None) switches it off and drops the tensor.  Independent of set_target_crops."""
+        if h is None:
+            self._chk(self.lib.oatgpu_set_target_crop_tensor(self.ctx, ffi.CROP_OFF, 0, 0, 1.0, None, None, 0))
+            self._crop_tensor = None
+            return None
+        import torch
+        w = h if w is None else w
+        name, fmt = self._tensor_fmt(dtype, scale, bias)
+        k = getattr(self, "_targets_k", 0)
+        shape = self._tensor_shape(name, (max(int(capacity), 1), self.n_streams, max(k, 1)), max(int(h), 1), max(int(w), 1))
+        t = torch.zeros(shape, dtype=getattr(torch, name), device=self._torch_device())
+        torch.cuda.synchronize(t.device)
+        self._chk(self.lib.oatgpu_set_target_crop_tensor(self.ctx, ffi.CROP_AXIS if axis else ffi.CROP_UPRIGHT, int(h), int(w), float(zoom),
+                                                         C.byref(fmt), C.c_void_p(t.data_ptr()), int(capacity)))
+        self._crop_tensor = t
+        return t
+
+    def target_crop_tensor(self):
+        """The entries the latest track / track_dev / track_sequence_dev call of a batched tracker wrote: the zero-copy view
+        tensor[:sets] of set_target_crop_tensor's tensor (one entry for a step, one per frame for a sequence call)."""
+        sets = self.lib.oatgpu_target_crop_tensor_sets(self.ctx)
+        if sets < 0:
+            self._chk(sets)
+        return self._crop_tensor[:sets]
+
+    def crop_tensor_windows(self, frames_dev, windows, h, w, dtype="float16", scale=1.0, bias=0.0):
+        """oatgpu_crop_tensor_windows_dev: crop_windows' windows, converted, as a fresh torch tensor on the context's device --
+        [n_streams, per_stream, C, h, w], or [n_streams, per_stream, h, w, C] for "uint8".  There is no zoom argument: a window
+        that is not upright carries it in (ax, ay)."""
+        import torch
+        n = self.n_streams
+        if len(windows) != n:
+            raise ValueError(f"expected windows of {n} cameras, got {len(windows)}")
+        per = len(windows[0])
+        if any(len(cam) != per for cam in windows):
+            raise ValueError("every camera takes the same number of windows")
+        arr = (ffi.CropWindow * max(n * per, 1))()
+        for s, cam in enumerate(windows):
+            for q, win in enumerate(cam):
+                if not isinstance(win, ffi.CropWindow):
+                    valid, upright, cx, cy, ax, ay = win
+                    win = ffi.CropWindow(int(bool(valid)), int(bool(upright)), float(cx), float(cy), float(ax), float(ay))
+                arr[s * per + q] = win
+        name, fmt = self._tensor_fmt(dtype, scale, bias)
+        out = torch.zeros(self._tensor_shape(name, (n, max(per, 1)), max(int(h), 1), max(int(w), 1)), dtype=getattr(torch, name),
+                          device=self._torch_device())
+        torch.cuda.synchronize(out.device)
+        self._chk(self.lib.oatgpu_crop_tensor_windows_dev(self.ctx, C.c_void_p(frames_dev), arr, per, int(h), int(w), C.byref(fmt),
+                                                          C.c_void_p(out.data_ptr())))
+        return out
+
     # -- target tracks (oatgpu_set_tracks / oatgpu_tracks / oatgpu_tracks_update, DESIGN.md 9j) --
     def set_tracks(self, kalman=None, gate=float("inf"), homography=None, regions=None):
         """oatgpu_set_tracks: k persistent track slots per camera (k of set_targets, which must be on) behind the ranked

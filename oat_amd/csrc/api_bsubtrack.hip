@@ -33,11 +33,11 @@ static int bsub_refusals(oatgpu_ctx *c, const char *what, double alpha)
 }
 
 // The front kernel of one frame set (f2: and the next) on stream A into the bits of `slot` (and slot2).  bsub_have is the state
-// the first frame met; it moves on.
-static int bsub_front(oatgpu_ctx *c, const void *f1, const void *f2, double alpha, int slot, int slot2)
+// the first frame met; it moves on.  entry: f1's place in the call (tracker_front).
+static int bsub_front(oatgpu_ctx *c, const void *f1, const void *f2, double alpha, int slot, int slot2, int entry)
 {
     BsubLaunch a{};
-    tracker_front(c, c->bs, f1, f2, slot, slot2, a);
+    tracker_front(c, c->bs, f1, f2, slot, slot2, entry, a);
     a.bg = c->bsub_bg; a.acc = c->bsub_f; a.have = c->bsub_have.data();
     a.rp = range_of(detector_of(c->cfg));
     a.learn = alpha > 0.0; a.a = (float)alpha; a.b = 1 - a.a;        // accW_: AT a = (AT)alpha, b = 1 - a
@@ -76,7 +76,7 @@ static int bsub_step(oatgpu_ctx *c, const void *frames_dev, double alpha, oatgpu
     chain_begin(c->tf);
     targets_begin(c);
     tracks_begin(c);
-    int rc = bsub_front(c, frames_dev, nullptr, alpha, 0, 0);
+    int rc = bsub_front(c, frames_dev, nullptr, alpha, 0, 0, 0);
     if (rc) return rc;
     rc = bsub_back(c, 0, c->stream);
     if (rc) return rc;
@@ -120,6 +120,8 @@ extern "C" int oatgpu_bsub_track_sequence_dev(oatgpu_ctx *c, const void *const *
     if (rc) return rc;
     rc = bsub_refusals(c, "bsub_track_sequence", alpha);
     if (rc) return rc;
+    rc = crop_tensor_room(c, n_frames, "bsub_track_sequence");
+    if (rc) return rc;
     if (n_frames == 0) return OATGPU_OK;
     rc = open_sync(c);
     if (rc) return rc;
@@ -130,7 +132,7 @@ extern "C" int oatgpu_bsub_track_sequence_dev(oatgpu_ctx *c, const void *const *
     tracks_begin(c);
     return run_sequence_in_flight(
         c, n_frames, c->bs.ev_front, c->bs.ev_done, [&](int t) { return t + 1 < n_frames ? 2 : 1; },
-        [&](int t, int nf, int q, int q2) { return bsub_front(c, frames_dev[t], nf == 2 ? frames_dev[t + 1] : nullptr, alpha, q, q2); },
+        [&](int t, int nf, int q, int q2) { return bsub_front(c, frames_dev[t], nf == 2 ? frames_dev[t + 1] : nullptr, alpha, q, q2, t); },
         [&](int q, int, hipStream_t B) { return bsub_back(c, q, B, std::exchange(prev, q)); },
         [&](int q, int frame) { tracker_hand_out(c, c->bs, q, out + (size_t)frame * n); });
 }

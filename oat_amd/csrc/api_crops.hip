@@ -48,7 +48,7 @@ void crops_keep(oatgpu_ctx *c, const TargetSets &ts, int slot)
     tg.last_crop_sets++;
 }
 
-static int check_crop_size(oatgpu_ctx *c, const char *what, int h, int w)
+int check_crop_size(oatgpu_ctx *c, const char *what, int h, int w)
 {
     if (h < 1 || h > kCropMaxSide || w < 4 || w > kCropMaxSide || w % 4 != 0)
         return fail(c, OATGPU_E_INVALID, "%s: a window is 1..%d rows by 4..%d columns, the columns a multiple of 4 (got %d x %d)", what,

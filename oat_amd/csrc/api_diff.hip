@@ -24,11 +24,11 @@ extern "C" int oatgpu_diff_reset(oatgpu_ctx *c, int32_t s)
 }
 
 // The front kernel of one frame set (f2: and the next, every stream has a last image) on stream A into the bits of `slot`
-// (and slot2).  have[] is the state the frame(s) met; diff_have moves on.
-static int diff_front(oatgpu_ctx *c, const void *f1, const void *f2, int slot, int slot2)
+// (and slot2).  have[] is the state the frame(s) met; diff_have moves on.  entry: f1's place in the call (tracker_front).
+static int diff_front(oatgpu_ctx *c, const void *f1, const void *f2, int slot, int slot2, int entry)
 {
     DiffLaunch a{};
-    tracker_front(c, c->df, f1, f2, slot, slot2, a);
+    tracker_front(c, c->df, f1, f2, slot, slot2, entry, a);
     a.last = c->diff_last; a.have_last = c->diff_have.data(); a.thr = c->cfg.diff_threshold;
     launch_diff_front(c->g, a, c->cfg.n_streams, c->stream);
     HIPCHK(c, hipGetLastError());
@@ -71,7 +71,7 @@ static int diff_step(oatgpu_ctx *c, const void *frames_dev, oatgpu_position *out
     chain_begin(c->tf);
     targets_begin(c);
     tracks_begin(c);
-    int rc = diff_front(c, frames_dev, nullptr, 0, 0);
+    int rc = diff_front(c, frames_dev, nullptr, 0, 0, 0);
     if (rc) return rc;
     c->diff_have.assign(have.size(), 1);
     rc = diff_back(c, 0, have.data(), c->stream);
@@ -114,6 +114,8 @@ extern "C" int oatgpu_diff_sequence_dev(oatgpu_ctx *c, const void *const *frames
     if (rc) return rc;
     rc = tracker_refusals(c, c->df, "diff", "diff_sequence");
     if (rc) return rc;
+    rc = crop_tensor_room(c, n_frames, "diff_sequence");
+    if (rc) return rc;
     if (n_frames == 0) return OATGPU_OK;
     rc = open_sync(c);
     if (rc) return rc;
@@ -132,7 +134,7 @@ extern "C" int oatgpu_diff_sequence_dev(oatgpu_ctx *c, const void *const *frames
         },
         [&](int t, int nf, int q, int q2) {
             have = c->diff_have;
-            const int r = diff_front(c, frames_dev[t], nf == 2 ? frames_dev[t + 1] : nullptr, q, q2);
+            const int r = diff_front(c, frames_dev[t], nf == 2 ? frames_dev[t + 1] : nullptr, q, q2, t);
             if (!r) c->diff_have.assign(have.size(), 1);
             return r;
         },

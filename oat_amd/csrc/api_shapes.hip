@@ -71,6 +71,8 @@ extern "C" int oatgpu_set_target_shapes(oatgpu_ctx *c, int32_t on)
     Targets &tg = c->tg;
     if (!on && tg.crop_mode == OATGPU_CROP_AXIS)
         return fail(c, OATGPU_E_INVALID, "set_target_shapes(0) while target crops follow the body axis: switch them off first (oatgpu_set_target_crops)");
+    if (!on && tg.ct.mode == OATGPU_CROP_AXIS)
+        return fail(c, OATGPU_E_INVALID, "set_target_shapes(0) while crop tensors follow the body axis: switch them off first (oatgpu_set_target_crop_tensor)");
     if (!on) {
         tg.shapes = false;
         tg.last_shapes.clear();

@@ -319,6 +319,8 @@ extern "C" int oatgpu_set_tracker_undistort(oatgpu_ctx *c, int32_t on)
             return fail(c, OATGPU_E_INVALID, "set_tracker_undistort with Bayer frames on (oatgpu_set_tracker_bayer) is not supported");
         if (c->tg.crop_mode)
             return fail(c, OATGPU_E_INVALID, "set_tracker_undistort with target crops on (oatgpu_set_target_crops) is not supported");
+        if (c->tg.ct.mode)
+            return fail(c, OATGPU_E_INVALID, "set_tracker_undistort with crop tensors on (oatgpu_set_target_crop_tensor) is not supported");
     }
     if (c->ring_count) return fail(c, OATGPU_E_INVALID, "set_tracker_undistort while enqueued results are outstanding");
     if (c->staged_count)
@@ -453,6 +455,8 @@ extern "C" int oatgpu_set_tracker_bayer(oatgpu_ctx *c, const int32_t *patterns, 
             return fail(c, OATGPU_E_INVALID, "set_tracker_bayer with undistortion on (oatgpu_set_tracker_undistort) is not supported");
         if (c->tg.crop_mode)
             return fail(c, OATGPU_E_INVALID, "set_tracker_bayer with target crops on (oatgpu_set_target_crops) is not supported");
+        if (c->tg.ct.mode)
+            return fail(c, OATGPU_E_INVALID, "set_tracker_bayer with crop tensors on (oatgpu_set_target_crop_tensor) is not supported");
         pat.resize((size_t)c->cfg.n_streams);
         for (int s = 0; s < c->cfg.n_streams; ++s) pat[(size_t)s] = patterns[n_patterns == 1 ? 0 : s];
     }

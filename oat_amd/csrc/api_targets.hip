@@ -5,7 +5,8 @@
 // call targets_launch; the calls that hand results out keep the sets they delivered (targets_begin, targets_keep) for
 // oatgpu_targets, the way the filter chains do (api_trackfilt.hip).  Target shapes (api_shapes.hip) ride on these
 // three: targets_launch launches k_blob_shape behind the ranking, targets_begin / targets_keep keep the shape sets beside the target sets.
-// Target crops (api_crops.hip) ride on them the same way, behind the shapes.
+// Target crops (api_crops.hip) ride on them the same way, behind the shapes, and crop tensors (api_croptensor.hip,
+// DESIGN.md 9m) behind those.
 #include "oatgpu_ctx.h"
 
 bool TargetSets::alloc(size_t slots, size_t n_streams, int k_)
@@ -22,11 +23,13 @@ int targets_launch(oatgpu_ctx *c, const BlobBuffers &bb, const TargetSets &ts, i
     if (!c->tg.k) return OATGPU_OK;
     launch_blob_rank(c->g, bb, c->cfg.min_area, c->cfg.max_area, c->tg.k, ts.rec_dev(slot), ts.found_dev(slot), s0, n, st);
     HIPCHK(c, hipGetLastError());
-    const int rc = shapes_launch(c, bb, ts, slot, s0, n, st);
-    return rc ? rc : crops_launch(c, ts, slot, s0, n, st);
+    int rc = shapes_launch(c, bb, ts, slot, s0, n, st);
+    if (rc) return rc;
+    rc = crops_launch(c, ts, slot, s0, n, st);
+    return rc ? rc : crop_tensor_launch(c, ts, slot, s0, n, st);
 }
 
-void targets_begin(oatgpu_ctx *c) { c->tg.last_sets = 0; shapes_begin(c); crops_begin(c); }
+void targets_begin(oatgpu_ctx *c) { c->tg.last_sets = 0; shapes_begin(c); crops_begin(c); crop_tensor_begin(c); }
 
 void targets_keep(oatgpu_ctx *c, const TargetSets &ts, int slot, int only)
 {
@@ -51,6 +54,7 @@ void targets_keep(oatgpu_ctx *c, const TargetSets &ts, int slot, int only)
     }
     shapes_keep(c, ts, slot, only);
     crops_keep(c, ts, slot);
+    crop_tensor_keep(c, ts);
     tg.last_sets++;
 }
 
@@ -62,6 +66,7 @@ extern "C" int oatgpu_set_targets(oatgpu_ctx *c, int32_t k)
     if (c->tk.on) return fail(c, OATGPU_E_INVALID, "set_targets while tracks are on: switch tracks off first (oatgpu_set_tracks)");
     if (c->tg.shapes) return fail(c, OATGPU_E_INVALID, "set_targets while target shapes are on: switch them off first (oatgpu_set_target_shapes)");
     if (c->tg.crop_mode) return fail(c, OATGPU_E_INVALID, "set_targets while target crops are on: switch them off first (oatgpu_set_target_crops)");
+    if (c->tg.ct.mode) return fail(c, OATGPU_E_INVALID, "set_targets while crop tensors are on: switch them off first (oatgpu_set_target_crop_tensor)");
     if (k > 0 && c->deferred) return fail(c, OATGPU_E_INVALID, "set_targets with deferred completion on (oatgpu_set_deferred) is not supported");
     if (k > 0 && c->mk.n) return fail(c, OATGPU_E_INVALID, "set_targets with marker sets configured (oatgpu_set_markers) is not supported");
     int rc = open_sync(c);

@@ -1,125 +1,21 @@
 // kernels_crops.hip -- target crops: an h x w window of the input frame around every ranked blob, upright or turned so that the
 // blob's body axis lies along the window's +x (oatgpu_set_target_crops, oatgpu_crop_windows_dev).  The text in
-// include/oatgpu.h ("target crops") is the contract; this is its one implementation on the device.
+// include/oatgpu.h ("target crops") is the contract; crops_inline.h is its one implementation on the device, shared with crop
+// tensors (kernels_croptensor.hip).
 //
 // k_target_crops is ONE body for both sources of windows: a target set with the shape set beside it (launched behind k_blob_rank
-// / k_blob_shape on the same HIP stream, api_crops.hip), or an explicit table (oatgpu_crop_windows_dev).
-// Grid: (row block, window, stream); a lane takes 4 output pixels of one row, w / 4 lanes a row, blockDim.x / (w / 4) rows a
-//   workgroup.  The window's record -- 4 + 6 words of TargetRec and ShapeRec, or the 5 words of a CropWin -- may live in
-//   host-mapped memory, where every dependent read is a round trip over the link (profiles/shapes_bench.txt): it is fetched once a
-//   workgroup, one lane a word, and lane 0 derives the window from the words in LDS with centroid_of / shape_of
-//   (posfilt_inline.h), the very functions the host hands positions and shapes out with.
-// Upright: a copy with unaligned source rows -- 4 pixels are one (GREY) or three (BGR) unaligned dword loads where they lie inside
-//   the frame, byte loads with 0 for what lies outside otherwise.  Axis: a gather, fp64 source position per pixel (one rounding per
-//   operation: the unit is built with -ffp-contract=off), then remap_core (undistort_inline.h): `framefilt undistort`'s fixed-point
-//   bilinear rule with BORDER_CONSTANT 0.
-// Stores: 32-bit, one to three a lane, consecutive lanes consecutive addresses (nothing wider than 64 bits; the
-//   crop set may be host-mapped memory).  Every byte of every window is written by every launch: an invalid window is zeros.
-#include "oatgpu_internal.h"
-#include "posfilt_inline.h"
-#include "undistort_inline.h"
+// / k_blob_shape on the same HIP stream, api_crops.hip), or an explicit table (oatgpu_crop_windows_dev).  It is the crop kernel
+// with the output it always had: the window's bytes, 32-bit stores into a crop set that may be host-mapped memory.
+#include "crops_inline.h"
 
 namespace oatgpu {
 
-constexpr int kCropBlock = 256;
-static_assert(sizeof(TargetRec) == 32 && sizeof(ShapeRec) == 48 && sizeof(CropWin) == 40, "the record words k_target_crops fetches");
-static_assert(kCropMaxSide / 4 <= 64, "a row's lanes fit the smallest workgroup");
-
-template <int CH>
-__global__ __launch_bounds__(kCropBlock) void k_target_crops(int H, int W, CropLaunch a)
-{
-    __shared__ u64 word[10];
-    __shared__ CropWin win;
-    const size_t at = (size_t)blockIdx.z * a.k + blockIdx.y;       // the window: stream blockIdx.z, rank blockIdx.y
-    const unsigned t = threadIdx.x;
-    if (a.recs) {
-        if (t < 4) word[t] = reinterpret_cast<const u64 *>(a.recs + at)[t];
-        else if (t < 10) word[t] = a.shp ? reinterpret_cast<const u64 *>(a.shp + at)[t - 4] : 0ull;
-    } else if (t < 5) {
-        word[t] = reinterpret_cast<const u64 *>(a.win + at)[t];
-    }
-    __syncthreads();
-    if (t == 0) {
-        CropWin v{};
-        if (a.recs) {
-            ResultRec r{};
-            r.a00 = (long long)word[0]; r.a10 = (long long)word[1]; r.a01 = (long long)word[2];
-            r.valid = (int)(word[3] >> 32) != 0;
-            v.valid = centroid_of(r, v.cx, v.cy) ? 1 : 0;
-            v.upright = 1;
-            if (v.valid && a.axis && (unsigned)word[9] != 0u) {
-                ShapeDerived d;
-                shape_of(r.a00, r.a10, r.a01, (long long)word[4], (long long)word[5], (long long)word[6], d);
-                if (d.axis_valid) { v.upright = 0; v.ax = d.axis_x; v.ay = d.axis_y; }
-            }
-        } else {
-            v.valid = (unsigned)word[0] != 0u;
-            v.upright = (unsigned)(word[0] >> 32) != 0u;
-            v.cx = __longlong_as_double((long long)word[1]); v.cy = __longlong_as_double((long long)word[2]);
-            v.ax = __longlong_as_double((long long)word[3]); v.ay = __longlong_as_double((long long)word[4]);
-        }
-        // a centre or an axis that is not finite, or a centre beyond +-1e6: no window (the comparisons are false for a NaN)
-        if (!(fabs(v.cx) <= 1e6 && fabs(v.cy) <= 1e6 && fabs(v.ax) <= DBL_MAX && fabs(v.ay) <= DBL_MAX)) v.valid = 0;
-        win = v;
-    }
-    __syncthreads();
-
-    const int lpr = a.w >> 2, rows_wg = (int)blockDim.x / lpr;
-    const int ri = (int)t / lpr, i = (int)blockIdx.x * rows_wg + ri, j0 = ((int)t - ri * lpr) * 4;
-    if (ri >= rows_wg || i >= a.h) return;
-
-    uint32_t px[4][CH];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        for (int c = 0; c < CH; ++c) px[q][c] = 0u;
-    const uint8_t *src = a.frames + (size_t)blockIdx.z * H * W * CH;
-    if (win.valid && win.upright) {
-        const int x = (int)rint(win.cx) - a.w / 2 + j0, y = (int)rint(win.cy) - a.h / 2 + i;
-        if ((unsigned)y < (unsigned)H) {
-            const uint8_t *p = src + ((ptrdiff_t)y * W + x) * CH;
-            if (x >= 0 && x + 3 < W) {
-                uint32_t w[CH];
-#pragma unroll
-                for (int c = 0; c < CH; ++c) w[c] = ld_u32(p + 4 * c);
-#pragma unroll
-                for (int b = 0; b < 4 * CH; ++b) px[b / CH][b % CH] = (w[b >> 2] >> ((b & 3) * 8)) & 255u;
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if ((unsigned)(x + q) < (unsigned)W)
-                        for (int c = 0; c < CH; ++c) px[q][c] = p[q * CH + c];
-            }
-        }
-    } else if (win.valid) {
-        const double cx = win.cx, cy = win.cy, ax = win.ax, ay = win.ay;
-        const double v = (double)(i - a.h / 2);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const double u = (double)(j0 + q - a.w / 2);
-            const double X = (cx + u * ax) - v * ay, Y = (cy + u * ay) + v * ax;
-            const double qxd = rint(X * 32.0), qyd = rint(Y * 32.0);
-            // (a position that is not finite or beyond 2^25 pixels lies outside every frame; the comparison is false for a NaN)
-            if (fabs(qxd) < 1073741824.0 && fabs(qyd) < 1073741824.0) {
-                const int qx = (int)qxd, qy = (int)qyd;
-                remap_core<CH>(src, H, W, qx >> 5, qy >> 5, qx & 31, qy & 31, px[q]);
-            }
-        }
-    }
-    uint32_t w[CH];
-#pragma unroll
-    for (int c = 0; c < CH; ++c) w[c] = 0u;
-#pragma unroll
-    for (int b = 0; b < 4 * CH; ++b) w[b >> 2] |= px[b / CH][b % CH] << ((b & 3) * 8);
-    uint32_t *o = reinterpret_cast<uint32_t *>(a.out + ((at * a.h + i) * a.w + j0) * CH);
-#pragma unroll
-    for (int c = 0; c < CH; ++c) __hip_atomic_store(o + c, w[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+template <int CH> constexpr auto k_target_crops = k_crop_windows<CH, kCropOutBytes>;
 
 void launch_target_crops(const Geom &g, const CropLaunch &a, int n_streams, hipStream_t st)
 {
-    const int lpr = a.w / 4;
-    const int threads = a.h * lpr <= 64 ? 64 : kCropBlock, rows_wg = threads / lpr;
-    const dim3 grid((a.h + rows_wg - 1) / rows_wg, a.k, n_streams), block(threads);
+    dim3 grid, block;
+    crop_grid(a, n_streams, grid, block);
     if (a.channels == 3) hipLaunchKernelGGL(k_target_crops<3>, grid, block, 0, st, g.H, g.W, a);
     else hipLaunchKernelGGL(k_target_crops<1>, grid, block, 0, st, g.H, g.W, a);
 }

@@ -140,7 +140,9 @@ struct ShapeSets {
 struct CropSets {
     HostMem<uint8_t> mem;                      // [slots][n][k][h][w][channels]
     size_t set_bytes = 0;
-    const uint8_t *frame[4] = {};              // [kSeqSlots] the frame set of the slot, as the caller gave it
+    const uint8_t *frame[4] = {};              // [kSeqSlots] the frame set of the slot, as the caller gave it ...
+    int entry[4] = {};                         // ... and its place in the call: 0 for a batch call, the frame's index in a sequence call
+                                               // (both kept while crops are off too: crop tensors cut from them, api_croptensor.hip)
     bool alloc(size_t slots, size_t n_streams, int k, int h, int w, int channels);     // false: hipGetLastError() has the reason
     bool on() const { return mem.host() != nullptr; }
     uint8_t *set_dev(int slot) const { return mem.dev() + (size_t)slot * set_bytes; }
@@ -160,6 +162,18 @@ struct TargetSets {
     const TargetRec *rec_host(int slot) const { return (const TargetRec *)(mem.host() + (size_t)slot * set_bytes); }
     const long long *found_host(int slot) const { return (const long long *)(rec_host(slot) + n * k); }
 };
+// Crop tensors (oatgpu_set_target_crop_tensor; api_croptensor.hip): the switch's parameters and the CALLER's
+// device memory -- never allocated, freed or copied here.  k_crop_tensor writes entry t of it for frame set t of a delivering call.
+struct CropTensor {
+    int mode = 0, h = 0, w = 0;                // OATGPU_CROP_*, the window
+    double zoom = 1.0;
+    oatgpu_crop_tensor_fmt fmt{};
+    uint8_t *out = nullptr;                    // device: [capacity][n][k][...] elements of fmt.dtype
+    int capacity = 0;
+    size_t entry_bytes = 0;
+    int last_sets = 0;                         // entries the latest delivering call wrote (oatgpu_target_crop_tensor_sets)
+    HostMem<CropWin> win;                      // host-mapped: [n][kCropMaxWindows] the table of oatgpu_crop_tensor_windows_dev, made by that call
+};
 struct Targets {
     int k = 0;                                 // K; 0: targets off
     TargetSets ring;                           // [ring_slots + 1] beside oatgpu_ctx::res: the ring's slots and the synchronous detectors' extra one
@@ -175,6 +189,7 @@ struct Targets {
     HostMem<CropWin> cw_win;                   // host-mapped: [n][kCropMaxWindows] the table of oatgpu_crop_windows_dev ...
     HostMem<uint8_t> cw_out;                   // ... and its windows, [cw_bytes]; made and grown by that call
     size_t cw_bytes = 0;
+    CropTensor ct;                             // oatgpu_set_target_crop_tensor; independent of crop_mode
 };
 
 // frames a batched tracker has in flight inside its sequence call (run_sequence_in_flight); each sits in a slot of its own
@@ -520,6 +535,15 @@ void shapes_keep(oatgpu_ctx *c, const TargetSets &ts, int slot, int only);
 int crops_launch(oatgpu_ctx *c, const TargetSets &ts, int slot, int s0, int n, hipStream_t st);
 void crops_begin(oatgpu_ctx *c);
 void crops_keep(oatgpu_ctx *c, const TargetSets &ts, int slot);
+int check_crop_size(oatgpu_ctx *c, const char *what, int h, int w);        // a window's limits, with the refusal's text (what: the call)
+// api_croptensor.hip: crops_launch's neighbour -- k_crop_tensor behind it on the same stream, from the frame set the slot
+// remembers into the entry the slot remembers of the caller's memory (a batched tracker's target sets only) --, the count a
+// delivering call keeps, and the refusal of a sequence call of more frames than the caller's memory has entries (what: the
+// call's name).  All do nothing while crop tensors are off.
+int crop_tensor_launch(oatgpu_ctx *c, const TargetSets &ts, int slot, int s0, int n, hipStream_t st);
+void crop_tensor_begin(oatgpu_ctx *c);
+void crop_tensor_keep(oatgpu_ctx *c, const TargetSets &ts);
+int crop_tensor_room(oatgpu_ctx *c, int n_frames, const char *what);
 // api_tracks.hip: k_target_tracks on the target set recs of the tracker's slot `slot`, on st right behind its k_blob_rank, into the
 // slot's track set `set`; prev_slot as tracker_filters_launch's.  The list a delivering call keeps (tracks_begin, tracks_keep) and a
 // batched tracker's own track sets (false: hipGetLastError() has the reason).  All do nothing while tracks are off.
@@ -559,12 +583,14 @@ static inline size_t track_in_bytes(const oatgpu_ctx *c) { return (size_t)c->g.H
 static inline size_t tracker_in_bytes(const oatgpu_ctx *c) { return (size_t)c->g.H * c->g.W * (c->tb_on ? 1 : c->cfg.channels); }
 // ... and what the front launch of either takes from the context: frame set f1 (f2: and the next) into the bits of `slot` (and
 // slot2), the ROI, the Bayer patterns with oatgpu_set_tracker_bayer on, the streams' maps with oatgpu_set_tracker_undistort on
-// (the slots' crop sets remember their frame set here: k_target_crops cuts from it behind the slot's ranking)
-static inline void tracker_front(const oatgpu_ctx *c, BatchedTrackerState &bt, const void *f1, const void *f2, int slot, int slot2, FrontLaunch &a)
+// (the slots' crop sets remember their frame set here, and its place `entry` in the call -- f2's is entry + 1: k_target_crops
+// and k_crop_tensor cut from it behind the slot's ranking, the latter into that entry of the caller's memory)
+static inline void tracker_front(const oatgpu_ctx *c, BatchedTrackerState &bt, const void *f1, const void *f2, int slot, int slot2, int entry,
+                                 FrontLaunch &a)
 {
     a.frames = (const uint8_t *)f1; a.frames2 = (const uint8_t *)f2; a.channels = c->cfg.channels;
-    bt.tgt.crp.frame[slot] = a.frames;
-    if (f2) bt.tgt.crp.frame[slot2] = a.frames2;
+    bt.tgt.crp.frame[slot] = a.frames; bt.tgt.crp.entry[slot] = entry;
+    if (f2) { bt.tgt.crp.frame[slot2] = a.frames2; bt.tgt.crp.entry[slot2] = entry + 1; }
     a.bits = bt.bits_of(slot); a.bits2 = f2 ? bt.bits_of(slot2) : nullptr;
     a.roi = c->roi;
     a.bayer = c->tb_on ? c->tb_pat.data() : nullptr;

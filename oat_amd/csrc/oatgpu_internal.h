@@ -378,6 +378,17 @@ struct CropLaunch {
 // A window's record is fetched once a workgroup; every byte of every window is written, zeros where the window is invalid.
 void launch_target_crops(const Geom &g, const CropLaunch &a, int n_streams, hipStream_t st);
 
+// --- kernels_croptensor.hip --- (crop tensors: those windows, zoomed and converted, in the caller's device memory;
+// oatgpu_set_target_crop_tensor, oatgpu_crop_tensor_windows_dev)
+// what the crop kernel (crops_inline.h) writes: k_target_crops' bytes, or a tensor's elements by oatgpu_crop_tensor_fmt's dtype
+constexpr int kCropOutBytes = -1, kCropOutU8 = 0, kCropOutF16 = 1, kCropOutF32 = 2;
+struct CropTensorLaunch : CropLaunch {   // out: [n_streams][k] windows of h * w * channels elements in DEVICE memory, 16-byte aligned
+    double zoom;             // records: source pixels an output pixel; 1.0: the window of target crops as it stands
+    float scale[3], bias[3]; // kCropOutF16 / kCropOutF32: per channel, in the frame's order
+};
+// The grid and the rules of launch_target_crops; every element of every window is written (an invalid window: bias[c], 0 for bytes).
+void launch_crop_tensor(const Geom &g, const CropTensorLaunch &a, int dtype, int n_streams, hipStream_t st);
+
 // --- kernels_markers.hip --- (marker sets: M colour windows per camera behind one MOG2 pass, `posicom mean`)
 constexpr int kMaxMarkers = 8;
 struct MarkerCombined {   // device-side record of k_marker_combine, one per stream per step: oatgpu_combined's layout

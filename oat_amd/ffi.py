@@ -106,12 +106,18 @@ class CropWindow(C.Structure):
                 ("ay", C.c_double)]
 
 
+class CropTensorFmt(C.Structure):
+    """oatgpu_crop_tensor_fmt: the element type of a crop tensor and, for float16 / float32, scale and bias per channel; 32 bytes."""
+    _fields_ = [("dtype", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
 E_RING_FULL = -4
 E_RING_EMPTY = -5
 ABI_VERSION = 9          # must equal OATGPU_ABI_VERSION of include/oatgpu.h
 MAX_TARGETS = 8          # OATGPU_MAX_TARGETS
 CROP_OFF, CROP_UPRIGHT, CROP_AXIS = 0, 1, 2      # OATGPU_CROP_*
 CROP_MAX_SIDE, CROP_MAX_WINDOWS = 256, 8         # OATGPU_CROP_MAX_SIDE, OATGPU_CROP_MAX_WINDOWS
+TENSOR_U8, TENSOR_F16, TENSOR_F32 = 0, 1, 2      # OATGPU_TENSOR_*
 TAP_THRESHOLD, TAP_MORPH, TAP_FINAL = 0, 1, 2
 BAYER_RGGB, BAYER_BGGR, BAYER_GRBG, BAYER_GBRG = 1, 2, 3, 4      # OATGPU_BAYER_*: the tile at rows 0-1, columns 0-1
 
@@ -179,6 +185,11 @@ SIGNATURES = {
     "oatgpu_set_target_crops": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32]),
     "oatgpu_target_crops": (C.c_int, [_ctx, _u8p, C.c_int32]),
     "oatgpu_crop_windows_dev": (C.c_int, [_ctx, C.c_void_p, C.POINTER(CropWindow), C.c_int32, C.c_int32, C.c_int32, _u8p]),
+    "oatgpu_set_target_crop_tensor": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(CropTensorFmt), C.c_void_p,
+                                                C.c_int32]),
+    "oatgpu_target_crop_tensor_sets": (C.c_int, [_ctx]),
+    "oatgpu_crop_tensor_windows_dev": (C.c_int, [_ctx, C.c_void_p, C.POINTER(CropWindow), C.c_int32, C.c_int32, C.c_int32,
+                                                 C.POINTER(CropTensorFmt), C.c_void_p]),
     "oatgpu_mog_apply": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_mog_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_bgr2hsv": (C.c_int, [_ctx, _u8p, _u8p]),
