@@ -426,6 +426,41 @@ class _Detector(_Context):
         self._chk(self.lib.oatgpu_set_detector(self.ctx, c.h_lo, c.h_hi, c.s_lo, c.s_hi, c.v_lo, c.v_hi,
                                                c.erode, c.dilate, c.min_area, c.max_area))
 
+    # -- what the readers of the target family share --
+    def _delivered(self, room, read):
+        """The sets the latest delivering call handed out, through one of the oatgpu_* readers: room(sets) -> buffers for `sets`
+        frame sets, read(buffers, sets) -> the reader's return.  A sequence call delivers more sets than there was room for at
+        first: the refusal names their number.  -> (buffers, sets delivered)"""
+        sets = 1
+        while True:
+            bufs = room(sets)
+            rc = read(bufs, sets)
+            if rc >= 0:
+                return bufs, rc
+            text = (self.lib.oatgpu_last_error(self.ctx) or b"").decode()
+            m = re.search(r"the latest call delivered (\d+)", text)
+            if not m or int(m.group(1)) <= sets:
+                self._chk(rc)
+            sets = int(m.group(1))
+
+    def _window_table(self, windows):
+        """windows: one list per camera, all of one length, of ffi.CropWindow or (valid, upright, cx, cy, ax, ay) -> (the table as
+        the explicit calls take it, windows a camera)"""
+        n = self.n_streams
+        if len(windows) != n:
+            raise ValueError(f"expected windows of {n} cameras, got {len(windows)}")
+        per = len(windows[0])
+        if any(len(cam) != per for cam in windows):
+            raise ValueError("every camera takes the same number of windows")
+        arr = (ffi.CropWindow * max(n * per, 1))()
+        for s, cam in enumerate(windows):
+            for q, win in enumerate(cam):
+                if not isinstance(win, ffi.CropWindow):
+                    valid, upright, cx, cy, ax, ay = win
+                    win = ffi.CropWindow(int(bool(valid)), int(bool(upright)), float(cx), float(cy), float(ax), float(ay))
+                arr[s * per + q] = win
+        return arr, per
+
     # -- multi-target detection (oatgpu_set_targets / oatgpu_targets, DESIGN.md 9i) --
     def set_targets(self, k):
         """The k largest blobs of every camera, ranked, beside the ordinary result of every detecting call; 0 switches it off
@@ -440,20 +475,11 @@ class _Detector(_Context):
         with one (ranks, n_found) pair per camera: ranks is k Position2D, area descending, ties to the later first pixel, rank
         0 the ordinary result, invalid where fewer candidates exist; n_found is the number of candidates (it may exceed k).
         Nothing is consumed."""
-        n, k, sets = self.n_streams, getattr(self, "_targets_k", 0), 1
-        while True:
-            out = (ffi.Position * (sets * n * max(k, 1)))()
-            found = (C.c_int32 * (sets * n))()
-            rc = self.lib.oatgpu_targets(self.ctx, out, found, sets)
-            if rc >= 0:
-                break
-            text = (self.lib.oatgpu_last_error(self.ctx) or b"").decode()
-            m = re.search(r"the latest call delivered (\d+)", text)
-            if not m or int(m.group(1)) <= sets:
-                self._chk(rc)
-            sets = int(m.group(1))           # a sequence call delivered more sets than there was room for
+        n, k = self.n_streams, getattr(self, "_targets_k", 0)
+        (out, found), got = self._delivered(lambda sets: ((ffi.Position * (sets * n * max(k, 1)))(), (C.c_int32 * (sets * n))()),
+                                            lambda bufs, sets: self.lib.oatgpu_targets(self.ctx, bufs[0], bufs[1], sets))
         return [[([Position2D.from_c(out[(t * n + s) * k + j]) for j in range(k)], int(found[t * n + s])) for s in range(n)]
-                for t in range(rc)]
+                for t in range(got)]
 
     # -- target shapes (oatgpu_set_target_shapes / oatgpu_target_shapes, DESIGN.md 9k) --
     def set_target_shapes(self, on=True):
@@ -465,18 +491,10 @@ class _Detector(_Context):
         """oatgpu_target_shapes: the shape sets of the frame sets the latest result-delivering call handed out -- a list with one
         entry per frame set, each a list with one list of k Shape (rank order, as targets()) per camera.  With tracks on,
         shapes[track.rank] is the shape of an identified animal.  Nothing is consumed."""
-        n, k, sets = self.n_streams, getattr(self, "_targets_k", 0), 1
-        while True:
-            out = (ffi.Shape * (sets * n * max(k, 1)))()
-            rc = self.lib.oatgpu_target_shapes(self.ctx, out, sets)
-            if rc >= 0:
-                break
-            text = (self.lib.oatgpu_last_error(self.ctx) or b"").decode()
-            m = re.search(r"the latest call delivered (\d+)", text)
-            if not m or int(m.group(1)) <= sets:
-                self._chk(rc)
-            sets = int(m.group(1))
-        return [[[Shape.from_c(out[(t * n + s) * k + j]) for j in range(k)] for s in range(n)] for t in range(rc)]
+        n, k = self.n_streams, getattr(self, "_targets_k", 0)
+        out, got = self._delivered(lambda sets: (ffi.Shape * (sets * n * max(k, 1)))(),
+                                   lambda out, sets: self.lib.oatgpu_target_shapes(self.ctx, out, sets))
+        return [[[Shape.from_c(out[(t * n + s) * k + j]) for j in range(k)] for s in range(n)] for t in range(got)]
 
     # -- target crops (oatgpu_set_target_crops / oatgpu_target_crops / oatgpu_crop_windows_dev, DESIGN.md 9l) --
     def _crop_shape(self, *lead):
@@ -500,19 +518,11 @@ class _Detector(_Context):
         batched tracker handed out -- a uint8 array [sets, n_streams, k, h, w] (GREY) or [sets, n_streams, k, h, w, 3]; rank
         order as targets(), zeros where a rank is empty.  With tracks on, crops[t, s, track.rank] is the window of an
         identified animal.  Nothing is consumed."""
-        n, k, sets = self.n_streams, getattr(self, "_targets_k", 0), 1
+        n, k = self.n_streams, getattr(self, "_targets_k", 0)
         h, w = getattr(self, "_crop_hw", None) or (1, 4)
-        while True:
-            out = np.empty(self._crop_shape(sets, n, max(k, 1), h, w), np.uint8)
-            rc = self.lib.oatgpu_target_crops(self.ctx, ffi.u8(out), sets)
-            if rc >= 0:
-                break
-            text = (self.lib.oatgpu_last_error(self.ctx) or b"").decode()
-            m = re.search(r"the latest call delivered (\d+)", text)
-            if not m or int(m.group(1)) <= sets:
-                self._chk(rc)
-            sets = int(m.group(1))
-        return out[:rc]
+        out, got = self._delivered(lambda sets: np.empty(self._crop_shape(sets, n, max(k, 1), h, w), np.uint8),
+                                   lambda out, sets: self.lib.oatgpu_target_crops(self.ctx, ffi.u8(out), sets))
+        return out[:got]
 
     def crop_windows(self, frames_dev, windows, h, w):
         """oatgpu_crop_windows_dev: h x w windows at given centres and axes from one frame set in device memory (frames_dev: the
@@ -520,18 +530,7 @@ class _Detector(_Context):
         all of one length 1..8, of ffi.CropWindow or (valid, upright, cx, cy, ax, ay).  Returns a uint8 array
         [n_streams, per_stream, h, w] or [..., 3]; an invalid window is zeros."""
         n = self.n_streams
-        if len(windows) != n:
-            raise ValueError(f"expected windows of {n} cameras, got {len(windows)}")
-        per = len(windows[0])
-        if any(len(cam) != per for cam in windows):
-            raise ValueError("every camera takes the same number of windows")
-        arr = (ffi.CropWindow * max(n * per, 1))()
-        for s, cam in enumerate(windows):
-            for q, win in enumerate(cam):
-                if not isinstance(win, ffi.CropWindow):
-                    valid, upright, cx, cy, ax, ay = win
-                    win = ffi.CropWindow(int(bool(valid)), int(bool(upright)), float(cx), float(cy), float(ax), float(ay))
-                arr[s * per + q] = win
+        arr, per = self._window_table(windows)
         out = np.empty(self._crop_shape(n, max(per, 1), max(int(h), 1), max(int(w), 1)), np.uint8)
         self._chk(self.lib.oatgpu_crop_windows_dev(self.ctx, C.c_void_p(frames_dev), arr, per, int(h), int(w), ffi.u8(out)))
         return out
@@ -597,18 +596,7 @@ class _Detector(_Context):
         that is not upright carries it in (ax, ay)."""
         import torch
         n = self.n_streams
-        if len(windows) != n:
-            raise ValueError(f"expected windows of {n} cameras, got {len(windows)}")
-        per = len(windows[0])
-        if any(len(cam) != per for cam in windows):
-            raise ValueError("every camera takes the same number of windows")
-        arr = (ffi.CropWindow * max(n * per, 1))()
-        for s, cam in enumerate(windows):
-            for q, win in enumerate(cam):
-                if not isinstance(win, ffi.CropWindow):
-                    valid, upright, cx, cy, ax, ay = win
-                    win = ffi.CropWindow(int(bool(valid)), int(bool(upright)), float(cx), float(cy), float(ax), float(ay))
-                arr[s * per + q] = win
+        arr, per = self._window_table(windows)
         name, fmt = self._tensor_fmt(dtype, scale, bias)
         out = torch.zeros(self._tensor_shape(name, (n, max(per, 1)), max(int(h), 1), max(int(w), 1)), dtype=getattr(torch, name),
                           device=self._torch_device())
@@ -638,18 +626,10 @@ class _Detector(_Context):
     def tracks(self):
         """oatgpu_tracks: the track sets of the frame sets the latest delivering call handed out -- a list with one entry per
         frame set, each a list with one list of k Track (slot order) per camera.  Nothing is consumed."""
-        n, k, sets = self.n_streams, getattr(self, "_targets_k", 0), 1
-        while True:
-            out = (ffi.Track * (sets * n * max(k, 1)))()
-            rc = self.lib.oatgpu_tracks(self.ctx, out, sets)
-            if rc >= 0:
-                break
-            text = (self.lib.oatgpu_last_error(self.ctx) or b"").decode()
-            m = re.search(r"the latest call delivered (\d+)", text)
-            if not m or int(m.group(1)) <= sets:
-                self._chk(rc)
-            sets = int(m.group(1))
-        return self._tracks_out(out, rc)
+        n, k = self.n_streams, getattr(self, "_targets_k", 0)
+        out, got = self._delivered(lambda sets: (ffi.Track * (sets * n * max(k, 1)))(),
+                                   lambda out, sets: self.lib.oatgpu_tracks(self.ctx, out, sets))
+        return self._tracks_out(out, got)
 
     def update_tracks(self, targets):
         """oatgpu_tracks_update: one association step on one frame set of detections -- targets: one entry of targets(), or a

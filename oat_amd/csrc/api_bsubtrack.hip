@@ -48,8 +48,8 @@ static int bsub_front(oatgpu_ctx *c, const void *f1, const void *f2, double alph
 }
 
 // The back half of the frame in `slot` on stream st, every stream in one launch sequence: the context's erode / dilate and area
-// window.  Touches neither last_slot nor last_morph / last_fin: those stay with the ordinary calls.  Behind it the filter chain
-// on the slot's records, where one is configured (prev_slot: tracker_filters_launch).
+// window.  Touches neither last_slot nor last_morph / last_fin: those stay with the ordinary calls.  Behind it whatever rides on
+// the slot (tracker_tail; prev_slot: the slot of the frame before).
 static int bsub_back(oatgpu_ctx *c, int slot, hipStream_t st, int prev_slot = -1)
 {
     const Geom &g = c->g;
@@ -65,17 +65,13 @@ static int bsub_back(oatgpu_ctx *c, int slot, hipStream_t st, int prev_slot = -1
     HIPCHK(c, hipGetLastError());
     c->bs.last = slot;
     c->bs.last_tap = m.tap;
-    { const int rc = targets_launch(c, bb, c->bs.tgt, slot, 0, n, st); if (rc) return rc; }
-    { const int rc = tracks_launch(c, c->bs.tgt.rec_dev(slot), c->bs.trk.dev(), slot, prev_slot, st); if (rc) return rc; }
-    return tracker_filters_launch(c, rd, slot, prev_slot, st);
+    return tracker_tail(c, c->bs, bb, rd, slot, prev_slot, st);
 }
 
 // one synchronous step on frames in device memory; the context is drained (open_sync)
 static int bsub_step(oatgpu_ctx *c, const void *frames_dev, double alpha, oatgpu_position *out)
 {
-    chain_begin(c->tf);
-    targets_begin(c);
-    tracks_begin(c);
+    tracker_begin(c);
     int rc = bsub_front(c, frames_dev, nullptr, alpha, 0, 0, 0);
     if (rc) return rc;
     rc = bsub_back(c, 0, c->stream);
@@ -126,10 +122,8 @@ extern "C" int oatgpu_bsub_track_sequence_dev(oatgpu_ctx *c, const void *const *
     rc = open_sync(c);
     if (rc) return rc;
     const int n = c->cfg.n_streams;
-    int prev = -1;                         // slot of the frame before (the filter chain's order)
-    chain_begin(c->tf);
-    targets_begin(c);
-    tracks_begin(c);
+    int prev = -1;                         // slot of the frame before (the order of the tracks and of the filter chain)
+    tracker_begin(c);
     return run_sequence_in_flight(
         c, n_frames, c->bs.ev_front, c->bs.ev_done, [&](int t) { return t + 1 < n_frames ? 2 : 1; },
         [&](int t, int nf, int q, int q2) { return bsub_front(c, frames_dev[t], nf == 2 ? frames_dev[t + 1] : nullptr, alpha, q, q2, t); },

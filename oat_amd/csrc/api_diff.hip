@@ -37,9 +37,9 @@ static int diff_front(oatgpu_ctx *c, const void *f1, const void *f2, int slot, i
 
 // The back half of the frame in `slot` on stream st: once for each maximal run of consecutive streams in the same first-frame
 // state (have[s] != 0: blur as dilation; 0: the first frame is analysed as it is), erode never.  Touches neither last_slot nor
-// last_morph / last_fin: those stay with the ordinary calls.  Behind it the filter chain on the slot's records, where one is
-// configured (prev_slot: tracker_filters_launch).  With targets on every run takes the global route and ONE k_blob_rank launch
-// behind the last of them ranks all streams into the slot's target set.
+// last_morph / last_fin: those stay with the ordinary calls.  Behind it whatever rides on the slot (tracker_tail; prev_slot: the
+// slot of the frame before).  With targets on every run takes the global route and ONE k_blob_rank launch behind the last of them
+// ranks all streams into the slot's target set.
 static int diff_back(oatgpu_ctx *c, int slot, const char *have, hipStream_t st, int prev_slot = -1)
 {
     const Geom &g = c->g;
@@ -59,18 +59,14 @@ static int diff_back(oatgpu_ctx *c, int slot, const char *have, hipStream_t st, 
     }
     HIPCHK(c, hipGetLastError());
     c->df.last = slot;
-    { const int rc = targets_launch(c, bb, c->df.tgt, slot, 0, n, st); if (rc) return rc; }      // (every stream's roots and sums are still in the set)
-    { const int rc = tracks_launch(c, c->df.tgt.rec_dev(slot), c->df.trk.dev(), slot, prev_slot, st); if (rc) return rc; }
-    return tracker_filters_launch(c, rd, slot, prev_slot, st);
+    return tracker_tail(c, c->df, bb, rd, slot, prev_slot, st);
 }
 
 // one synchronous step on frames in device memory; the context is drained (open_sync)
 static int diff_step(oatgpu_ctx *c, const void *frames_dev, oatgpu_position *out)
 {
     const std::vector<char> have = c->diff_have;
-    chain_begin(c->tf);
-    targets_begin(c);
-    tracks_begin(c);
+    tracker_begin(c);
     int rc = diff_front(c, frames_dev, nullptr, 0, 0, 0);
     if (rc) return rc;
     c->diff_have.assign(have.size(), 1);
@@ -122,10 +118,8 @@ extern "C" int oatgpu_diff_sequence_dev(oatgpu_ctx *c, const void *const *frames
     const int n = c->cfg.n_streams;
     const std::vector<char> all(c->diff_have.size(), 1);
     std::vector<char> have;                // the state the launch's first frame met
-    int prev = -1;                         // slot of the frame before (the filter chain's order)
-    chain_begin(c->tf);
-    targets_begin(c);
-    tracks_begin(c);
+    int prev = -1;                         // slot of the frame before (the order of the tracks and of the filter chain)
+    tracker_begin(c);
     return run_sequence_in_flight(
         c, n_frames, c->df.ev_front, c->df.ev_done,
         [&](int t) {

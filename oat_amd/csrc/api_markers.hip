@@ -278,7 +278,7 @@ extern "C" int oatgpu_track_markers_dev(oatgpu_ctx *c, const void *frames_dev, d
     for (int s = 0; s < n; ++s)
         for (int m = 0; m < M; ++m) to_position(r[(size_t)m * n + s], &markers[(size_t)s * M + m]);
     if (mean) memcpy(mean, r + (size_t)M * n, (size_t)n * sizeof(oatgpu_combined));
-    if (c->mf.on) { chain_begin(c->mf); chain_keep(c, c->mf, c->mf.out_host.host()); }
+    if (c->mf.on) { c->mf.last.begin(); c->mf.last.keep((size_t)c->cfg.n_streams, c->mf.out_host.host()); }
     return OATGPU_OK;
 }
 

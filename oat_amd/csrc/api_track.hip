@@ -806,8 +806,8 @@ static int collect_frame(oatgpu_ctx *c, oatgpu_position *out, oatgpu_position *m
                 for (int m = 0; m < M; ++m) to_position(mr[(size_t)m * n + s], &markers[(size_t)s * M + m]);
         if (mean) memcpy(mean, mr + (size_t)M * n, (size_t)n * sizeof(oatgpu_combined));
         if (c->mf.on && markers) {           // a marker-result call: what oatgpu_marker_filtered hands out -- this set, or one more
-            if (!c->mf.append) chain_begin(c->mf);          // of oatgpu_track_markers_sequence_dev's
-            chain_keep(c, c->mf, (const MarkerFiltered *)((const MarkerCombined *)(mr + (size_t)M * n) + n));
+            if (!c->mf.append) c->mf.last.begin();          // of oatgpu_track_markers_sequence_dev's
+            c->mf.last.keep((size_t)n, (const MarkerCombined *)(mr + (size_t)M * n) + n);
         }
         c->mkp.last_slot = slot;
     }
@@ -952,7 +952,7 @@ extern "C" int oatgpu_track_markers_sequence_dev(oatgpu_ctx *c, const void *cons
     if (!c->mkp.on) return fail(c, OATGPU_E_INVALID, "the marker pipeline is off (oatgpu_set_marker_pipeline)");
     if (c->ring_count) return fail(c, OATGPU_E_INVALID, "track_sequence while enqueued results are outstanding");
     c->mf.append = true;                 // oatgpu_marker_filtered: the n_frames sets of this call
-    chain_begin(c->mf);
+    c->mf.last.begin();
     const int rc = sequence_dev(c, frames_dev, n_frames, lr, fg, nullptr, nullptr, markers, mean);
     c->mf.append = false;
     return rc;

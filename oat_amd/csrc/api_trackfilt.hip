@@ -1,11 +1,13 @@
 // api_trackfilt.hip -- what the motion and the subtraction tracker share on the host, and the filter chain on the host.
 // `posifilt kalman` -> `posifilt homography` -> `posifilt region` has ONE owner here for both of its users, the marker sets'
 // combined record (api_markers.hip) and the trackers' own result records: the checked parameters (chain_params),
-// the list a delivering call keeps (chain_begin, chain_keep) and its hand-out (chain_hand_out); the setters' body is
-// configure_chain (oatgpu_ctx.h).  The trackers' chain runs one launch a frame behind the slot's back half, in frame order
-// (kernels_trackfilt.hip); api_diff.hip and api_bsubtrack.hip call tracker_filters_launch, chain_begin and tracker_hand_out from
-// their steps.
+// and the hand-out of the list a delivering call keeps (chain_hand_out; delivered_refusals for every such list of the library);
+// the setters' body is configure_chain (oatgpu_ctx.h).  The trackers' chain runs one launch a frame behind the slot's back half,
+// in frame order (kernels_trackfilt.hip).  A step of either tracker is tracker_begin, its own front and blob launches,
+// tracker_tail -- everything that rides on the slot, the chain last -- and tracker_hand_out.
 #include "oatgpu_ctx.h"
+
+static_assert(sizeof(oatgpu_filtered) == sizeof(MarkerFiltered), "k_marker_filters and k_tracker_filters write oatgpu_filtered's layout");
 
 // --- what the two trackers' entry points have in common (BatchedTrackerState, oatgpu_ctx.h) ---
 
@@ -17,10 +19,7 @@ bool BatchedTrackerState::alloc(const oatgpu_ctx *c)
     bool ok = bits.alloc(K * words * 8) == hipSuccess;
     ok = ok && masks.alloc(K * planes * words * 8) == hipSuccess;
     ok = ok && rec.alloc(K * n * sizeof(ResultRec), hipHostMallocMapped) == hipSuccess;
-    ok = ok && (!c->tg.k || tgt.alloc(K, n, c->tg.k));
-    ok = ok && (!c->tg.shapes || tgt.shp.alloc(K, n, c->tg.k));
-    ok = ok && (!c->tg.crop_mode || tgt.crp.alloc(K, n, c->tg.k, c->tg.crop_h, c->tg.crop_w, c->cfg.channels));
-    ok = ok && (!c->tk.on || tracks_alloc_sets(c, trk, c->tk.k));
+    ok = ok && tgt.alloc(wants_of(c), K, n, c->cfg.channels, true);
     // (the taps: words beyond the frame are never written by the back half)
     ok = ok && hipMemsetAsync(bits, 0, K * words * 8, c->stream) == hipSuccess;
     ok = ok && hipMemsetAsync(masks, 0, K * planes * words * 8, c->stream) == hipSuccess;
@@ -90,22 +89,34 @@ int reset_have(oatgpu_ctx *c, std::vector<char> &have, int s)
     return OATGPU_OK;
 }
 
-// the finished frame in `slot` to the caller: its records as positions, its filtered set and its target set into the call's
+// --- a step of either tracker around its front and blob launches (the declarations in oatgpu_ctx.h say what each does) ---
+
+void tracker_begin(oatgpu_ctx *c)
+{
+    c->tf.last.begin();
+    targets_begin(c);
+    c->tk.last.begin();
+}
+
+int tracker_tail(oatgpu_ctx *c, const BatchedTrackerState &bt, const BlobBuffers &bb, const ResultRec *rd, int slot, int prev_slot, hipStream_t st)
+{
+    int rc = targets_launch(c, bb, bt.tgt, slot, 0, c->cfg.n_streams, st);      // (every stream's roots and sums are still in the set)
+    if (!rc) rc = crops_launch(c, bt, slot, st);
+    if (!rc) rc = crop_tensor_launch(c, bt, slot, st);
+    if (!rc) rc = tracks_launch(c, bt.tgt, slot, prev_slot, st);
+    return rc ? rc : tracker_filters_launch(c, rd, slot, prev_slot, st);      // (the caller records the slot's "done" event behind this)
+}
+
 void tracker_hand_out(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, oatgpu_position *out)
 {
     for (size_t s = 0; s < bt.n; ++s) to_position(bt.rec.host()[(size_t)slot * bt.n + s], out + s);
-    if (c->tf.on) chain_keep(c, c->tf, c->tf.out.host() + (size_t)slot * bt.n);
+    if (c->tf.on) c->tf.last.keep(bt.n, c->tf.out.host() + (size_t)slot * bt.n);
     targets_keep(c, bt.tgt, slot);
-    if (c->tk.on) tracks_keep(c, bt.trk.host() + (size_t)slot * bt.n * (size_t)c->tk.k);
+    crops_keep(c, bt, slot);
+    crop_tensor_keep(c);
+    if (c->tk.on) c->tk.last.keep(bt.n * (size_t)c->tk.k, bt.tgt.trk_host(slot));
 }
 
-// --- the trackers' launch of the filter chain ---
-
-// The chain on the frame whose result records are rec_dev (the tracker's slot `slot`), on stream st right behind that frame's
-// back half.  Inside a sequence call (st is a B stream) consecutive frames sit on different HIP streams: the launch waits for
-// the filter event of the frame before it (prev_slot; -1: the first frame of the call, everything before it has drained) and
-// records its own.  The synchronous step runs on stream A alone and needs neither.  The caller records the slot's "done" event
-// behind this.
 int tracker_filters_launch(oatgpu_ctx *c, const ResultRec *rec_dev, int slot, int prev_slot, hipStream_t st)
 {
     TrackerFilters &tf = c->tf;
@@ -158,26 +169,20 @@ int chain_params(oatgpu_ctx *c, const oatgpu_marker_filters *f, MarkerFilterPara
     return OATGPU_OK;
 }
 
-// What oatgpu_marker_filtered / oatgpu_tracker_filtered hand out is the list of the latest delivering call.  ONE convention: the
-// call starts the list over where it begins to deliver (chain_begin), every set it delivers joins the list (chain_keep).
-void chain_begin(PosfiltChain &ch) { ch.last_sets = 0; }
-void chain_keep(oatgpu_ctx *c, PosfiltChain &ch, const MarkerFiltered *set)
+// What a reader of a Delivered list refuses (oatgpu_ctx.h): its switch is off, no call has delivered since, too little room
+int delivered_refusals(oatgpu_ctx *c, bool on, const char *off, const char *none_yet, int sets, int max_sets)
 {
-    static_assert(sizeof(oatgpu_filtered) == sizeof(MarkerFiltered), "k_marker_filters and k_tracker_filters write oatgpu_filtered's layout");
-    const size_t n = (size_t)c->cfg.n_streams;
-    ch.last.resize((size_t)(ch.last_sets + 1) * n);
-    memcpy(ch.last.data() + (size_t)ch.last_sets * n, set, n * sizeof(oatgpu_filtered));
-    ch.last_sets++;
+    if (!on) return fail(c, OATGPU_E_INVALID, "%s", off);
+    if (sets == 0) return fail(c, OATGPU_E_INVALID, "%s", none_yet);
+    if (max_sets < sets) return fail(c, OATGPU_E_INVALID, "room for %d frame sets, the latest call delivered %d", max_sets, sets);
+    return OATGPU_OK;
 }
 
 // oatgpu_marker_filtered / oatgpu_tracker_filtered behind their null checks; none_yet: the text where nothing was delivered yet
 int chain_hand_out(oatgpu_ctx *c, const PosfiltChain &ch, const char *who, const char *none_yet, oatgpu_filtered *out, int max_sets)
 {
-    if (!ch.on) return fail(c, OATGPU_E_INVALID, "no filter chain is configured (oatgpu_set_%s_filters)", who);
-    if (ch.last_sets == 0) return fail(c, OATGPU_E_INVALID, "%s", none_yet);
-    if (max_sets < ch.last_sets) return fail(c, OATGPU_E_INVALID, "room for %d frame sets, the latest call delivered %d", max_sets, ch.last_sets);
-    memcpy(out, ch.last.data(), (size_t)ch.last_sets * c->cfg.n_streams * sizeof(oatgpu_filtered));
-    return ch.last_sets;
+    const std::string off = std::string("no filter chain is configured (oatgpu_set_") + who + "_filters)";
+    return delivered_to(c, ch.last, ch.on, off.c_str(), none_yet, out, max_sets);
 }
 
 extern "C" int oatgpu_set_tracker_filters(oatgpu_ctx *c, const oatgpu_marker_filters *f)

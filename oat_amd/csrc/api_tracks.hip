@@ -1,43 +1,23 @@
 // api_tracks.hip -- target tracks: identity across frames for the K ranked blobs of every camera.
-// While tracks are on, the back halves of the motion and the subtraction tracker (diff_back, api_diff.hip; bsub_back,
-// api_bsubtrack.hip) launch k_target_tracks (kernels_tracks.hip) behind targets_launch on the same HIP stream, into the track set
-// of the frame's slot; inside the sequence calls the host orders consecutive frames with an event per slot, exactly like
-// tracker_filters_launch (api_trackfilt.hip).  The calls that hand results out keep the sets they delivered (tracks_begin,
-// tracks_keep) for oatgpu_tracks, the way targets_keep does.  oatgpu_tracks_update is the same kernel on positions from the host.
+// While tracks are on, the tail of a step of the motion and the subtraction tracker (tracker_tail, api_trackfilt.hip) launches
+// k_target_tracks (kernels_tracks.hip) behind the ranking on the same HIP stream, into the track set of the frame's slot
+// (TargetSets::trk); inside the sequence calls the host orders consecutive frames with an event per slot, exactly like
+// tracker_filters_launch.  tracker_hand_out keeps the sets a call delivered for oatgpu_tracks.
+// oatgpu_tracks_update is the same kernel on positions from the host.
 #include "oatgpu_ctx.h"
 
 static_assert(sizeof(oatgpu_track) == sizeof(TrackRec), "k_target_tracks writes oatgpu_track's layout");
 
-bool tracks_alloc_sets(const oatgpu_ctx *c, HostMem<TrackRec> &sets, int k)
-{
-    const size_t bytes = (size_t)kSeqSlots * (size_t)c->cfg.n_streams * (size_t)k * sizeof(TrackRec);
-    if (sets.alloc(bytes, hipHostMallocMapped) != hipSuccess) return false;
-    memset(sets.host(), 0, bytes);
-    return true;
-}
-
-int tracks_launch(oatgpu_ctx *c, const TargetRec *recs, TrackRec *sets, int slot, int prev_slot, hipStream_t st)
+int tracks_launch(oatgpu_ctx *c, const TargetSets &ts, int slot, int prev_slot, hipStream_t st)
 {
     Tracks &tk = c->tk;
     if (!tk.on) return OATGPU_OK;
     const int n = c->cfg.n_streams;
     if (prev_slot >= 0) HIPCHK(c, hipStreamWaitEvent(st, tk.ev[prev_slot], 0));
-    launch_target_tracks(tk.launch(), recs, nullptr, sets + (size_t)slot * n * (size_t)tk.k, n, st);
+    launch_target_tracks(tk.launch(), ts.rec_dev(slot), nullptr, ts.trk_dev(slot), n, st);
     HIPCHK(c, hipGetLastError());
     if (st != c->stream) HIPCHK(c, hipEventRecord(tk.ev[slot], st));
     return OATGPU_OK;
-}
-
-void tracks_begin(oatgpu_ctx *c) { c->tk.last_sets = 0; }
-
-void tracks_keep(oatgpu_ctx *c, const TrackRec *set)
-{
-    Tracks &tk = c->tk;
-    if (!tk.on) return;
-    const size_t per = (size_t)c->cfg.n_streams * (size_t)tk.k;
-    tk.last.resize((size_t)(tk.last_sets + 1) * per);
-    memcpy(tk.last.data() + (size_t)tk.last_sets * per, set, per * sizeof(oatgpu_track));
-    tk.last_sets++;
 }
 
 extern "C" int oatgpu_set_tracks(oatgpu_ctx *c, const oatgpu_marker_filters *f, double gate)
@@ -48,7 +28,7 @@ extern "C" int oatgpu_set_tracks(oatgpu_ctx *c, const oatgpu_marker_filters *f, 
         const int rc = open_sync(c);
         if (rc) return rc;
         c->tk = {};
-        c->df.trk = {}; c->bs.trk = {};
+        for_each_target_home(c, [](TargetSets &ts, size_t, bool, bool) { ts.trk = {}; });
         return OATGPU_OK;
     }
     if (!c->tg.k) return fail(c, OATGPU_E_INVALID, "set_tracks: targets are off (oatgpu_set_targets)");
@@ -62,7 +42,6 @@ extern "C" int oatgpu_set_tracks(oatgpu_ctx *c, const oatgpu_marker_filters *f, 
     // everything is built aside: a failed allocation leaves the context as it was
     const size_t n = (size_t)c->cfg.n_streams, k = (size_t)c->tg.k;
     Tracks made;
-    HostMem<TrackRec> df, bs;
     bool ok = made.params.alloc(sizeof(MarkerFilterParams)) == hipSuccess;
     ok = ok && made.state.alloc(n * k * sizeof(KalmanState)) == hipSuccess;
     ok = ok && made.meta.alloc(n * k * sizeof(TrackMeta)) == hipSuccess;
@@ -70,9 +49,9 @@ extern "C" int oatgpu_set_tracks(oatgpu_ctx *c, const oatgpu_marker_filters *f, 
     ok = ok && made.upd_in.alloc(n * k * sizeof(TrackTriple), hipHostMallocMapped) == hipSuccess;
     ok = ok && made.upd_out.alloc(n * k * sizeof(TrackRec), hipHostMallocMapped) == hipSuccess;
     for (auto &e : made.ev) ok = ok && e.create(hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
-    ok = ok && (!c->df.on || tracks_alloc_sets(c, df, (int)k));
-    ok = ok && (!c->bs.on || tracks_alloc_sets(c, bs, (int)k));
     if (!ok) return fail(c, OATGPU_E_NOMEM, "tracks: allocation failed: %s", hipGetErrorString(hipGetLastError()));
+    TargetWants w = wants_of(c);
+    w.tracks = true;
     memset(made.upd_out.host(), 0, n * k * sizeof(TrackRec));
     const std::vector<long long> first(n, 1);
     HIPCHK(c, hipMemcpy(made.params, hp.data(), sizeof(MarkerFilterParams), hipMemcpyHostToDevice));
@@ -81,25 +60,21 @@ extern "C" int oatgpu_set_tracks(oatgpu_ctx *c, const oatgpu_marker_filters *f, 
     launch_kalman_reset(made.state, (int)(n * k), 0u, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    rc = rebuild_target_sets(c, w, "tracks");            // (last: nothing after it can fail)
+    if (rc) return rc;
     made.on = true;
     made.k = (int)k;
     made.gate2 = gate * gate;
-    made.last.reserve(n * k);
+    made.last.items.reserve(n * k);
     c->tk = std::move(made);
-    c->df.trk = std::move(df);
-    c->bs.trk = std::move(bs);
     return OATGPU_OK;
 }
 
 extern "C" int oatgpu_tracks(oatgpu_ctx *c, oatgpu_track *out, int32_t max_sets)
 {
     if (!c || !out) return fail(c, OATGPU_E_INVALID, "null argument");
-    const Tracks &tk = c->tk;
-    if (!tk.on) return fail(c, OATGPU_E_INVALID, "tracks are off (oatgpu_set_tracks)");
-    if (tk.last_sets == 0) return fail(c, OATGPU_E_INVALID, "no call has delivered a track set since tracks were switched on");
-    if (max_sets < tk.last_sets) return fail(c, OATGPU_E_INVALID, "room for %d frame sets, the latest call delivered %d", max_sets, tk.last_sets);
-    memcpy(out, tk.last.data(), (size_t)tk.last_sets * c->cfg.n_streams * (size_t)tk.k * sizeof(oatgpu_track));
-    return tk.last_sets;
+    return delivered_to(c, c->tk.last, c->tk.on, "tracks are off (oatgpu_set_tracks)",
+                        "no call has delivered a track set since tracks were switched on", out, max_sets);
 }
 
 extern "C" int oatgpu_tracks_update(oatgpu_ctx *c, const oatgpu_position *targets, oatgpu_track *out)
@@ -121,7 +96,7 @@ extern "C" int oatgpu_tracks_update(oatgpu_ctx *c, const oatgpu_position *target
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     memcpy(out, tk.upd_out.host(), per * sizeof(oatgpu_track));
-    tracks_begin(c);
-    tracks_keep(c, tk.upd_out.host());
+    tk.last.begin();
+    tk.last.keep(per, tk.upd_out.host());
     return OATGPU_OK;
 }

@@ -99,15 +99,31 @@ struct MarkerPipeline {
     // a record set: M x n result records, n combined records, n filtered records (written only while a chain is configured)
     size_t set_bytes = 0;                      // = M n sizeof(ResultRec) + n (sizeof(MarkerCombined) + sizeof(MarkerFiltered))
 };
+// The list a delivering call keeps: the sets it handed out, for the reader that hands them out again (oatgpu_targets,
+// oatgpu_tracks, oatgpu_*_filtered, ...).  ONE convention for every such list: the call starts it over where it begins to deliver
+// (begin), every set it delivers joins it (keep: room for one more set of `per` items, filled by the caller), and delivered_to
+// (below) is the reader, with its three refusals.  Every list has its own count.
+template <class T> struct Delivered {
+    std::vector<T> items;                      // [sets][per]
+    size_t per = 0;                            // items a set, as the latest keep had it
+    int sets = 0;
+    void begin() { sets = 0; }
+    T *keep(size_t per_)
+    {
+        per = per_;
+        items.resize((size_t)(sets + 1) * per);
+        return items.data() + (size_t)sets++ * per;
+    }
+    void keep(size_t per_, const void *set) { memcpy(keep(per_), set, per_ * sizeof(T)); }
+};
 // A filter chain kalman -> homography -> region (chain_step, posfilt_inline.h) as the host keeps it: what the marker chain and the
-// trackers' chain have in common.  api_trackfilt.hip configures it (configure_chain), keeps what a call delivered (chain_begin,
-// chain_keep) and hands that out (chain_hand_out); the owners below add the buffers their kernels write.
+// trackers' chain have in common.  api_trackfilt.hip configures it (configure_chain) and hands out what a call delivered
+// (chain_hand_out); the owners below add the buffers their kernels write.
 struct PosfiltChain {
     bool on = false;
     DevMem<MarkerFilterParams> params;         // device: the chain's parameters and the region table
     DevMem<KalmanState> state;                 // device: [n] the chain's own filter state, one per camera stream (not c->kal's)
-    std::vector<oatgpu_filtered> last;         // [sets][n] what the latest delivering call delivered (oatgpu_*_filtered)
-    int last_sets = 0;
+    Delivered<oatgpu_filtered> last;           // [sets][n] what the latest delivering call delivered (oatgpu_*_filtered)
 };
 // the filter chain behind the combined record (oatgpu_set_marker_filters): ONE launch behind k_marker_combine on the same HIP
 // stream.  Made by the setter, dropped with the marker set.
@@ -117,10 +133,14 @@ struct MarkerFilters : PosfiltChain {
     bool append = false;                       // inside oatgpu_track_markers_sequence_dev: every collected set is kept
 };
 
-// Target shapes (oatgpu_set_target_shapes; api_shapes.hip).  A shape set is what k_blob_shape writes for one frame
+// The target family: what rides on the slot of a ranked result.  Target sets live in three homes -- the result ring
+// and the slots of the two batched trackers (for_each_target_home) --, and every home owns, slot for slot, what the context's
+// switches ask for: TargetSets::alloc makes all of it, for the setters (rebuild_target_sets, api_targets.hip) and for a batched
+// tracker switched on later (BatchedTrackerState::alloc); nothing is made inside a step.
+//
+// Target shapes (oatgpu_set_target_shapes; api_targets.hip).  A shape set is what k_blob_shape writes for one frame
 // set: [n][k] ShapeRec, host-mapped.  ShapeSets owns one for each slot of the TargetSets it stands beside, and the slot's device
-// accumulator and arrival counter (frames in flight sit in different slots, so no two launches share them); everything is made by
-// oatgpu_set_target_shapes (or by a batched tracker switched on while shapes are on), never inside a step.  Empty while shapes are off.
+// accumulator and arrival counter (frames in flight sit in different slots, so no two launches share them).  Empty while shapes are off.
 struct ShapeSets {
     HostMem<ShapeRec> mem;                     // [slots][n][k]
     DevMem<u64> accum;                         // [slots][n][k][kShapeAccWords], all zero between launches
@@ -134,36 +154,36 @@ struct ShapeSets {
 };
 // Target crops (oatgpu_set_target_crops; api_crops.hip).  A crop set is what k_target_crops writes for one frame set:
 // [n][k][h][w][channels] bytes, host-mapped.  CropSets owns one for each slot of the TargetSets it stands beside -- a batched
-// tracker's: the fused tracker and the single-stage detectors deliver no crops, their target sets have none -- and remembers the
-// frame set each slot's front launch read (tracker_front).  Everything is made by oatgpu_set_target_crops (or by a batched tracker
-// switched on while crops are on), never inside a step.  Empty while crops are off.
+// tracker's: the fused tracker and the single-stage detectors deliver no crops, their target sets have none.  Empty while crops are off.
 struct CropSets {
     HostMem<uint8_t> mem;                      // [slots][n][k][h][w][channels]
     size_t set_bytes = 0;
-    const uint8_t *frame[4] = {};              // [kSeqSlots] the frame set of the slot, as the caller gave it ...
-    int entry[4] = {};                         // ... and its place in the call: 0 for a batch call, the frame's index in a sequence call
-                                               // (both kept while crops are off too: crop tensors cut from them, api_croptensor.hip)
     bool alloc(size_t slots, size_t n_streams, int k, int h, int w, int channels);     // false: hipGetLastError() has the reason
-    bool on() const { return mem.host() != nullptr; }
     uint8_t *set_dev(int slot) const { return mem.dev() + (size_t)slot * set_bytes; }
     const uint8_t *set_host(int slot) const { return mem.host() + (size_t)slot * set_bytes; }
 };
+// the switches of the family that decide what stands beside a slot
+struct TargetWants { int k; bool shapes; int crop_mode, crop_h, crop_w; bool tracks; };
 // Multi-target detection (oatgpu_set_targets; api_targets.hip).  A target set is what k_blob_rank writes for one
-// frame set: [n][k] TargetRec, then [n] candidate counts.  TargetSets owns one for each slot of a result ring, host-mapped;
-// everything is made by oatgpu_set_targets (or by a batched tracker switched on while targets are on), never inside a step.
+// frame set: [n][k] TargetRec, then [n] candidate counts.  TargetSets owns one for each slot of one home, host-mapped, and the
+// riders' sets beside them.
 struct TargetSets {
     HostMem<char> mem;
     ShapeSets shp;                             // the shape sets beside the target sets, slot for slot, while shapes are on
     CropSets crp;                              // the crop sets beside them, while crops are on (a batched tracker's sets only)
+    HostMem<TrackRec> trk;                     // [slots][n][k] the track sets beside them, while tracks are on (likewise)
     size_t n = 0, k = 0, set_bytes = 0;
-    bool alloc(size_t slots, size_t n_streams, int k_);        // false: hipGetLastError() has the reason
+    // everything `w` asks for (nothing with w.k == 0), zeroed; of_tracker: the slots of a batched tracker.  false: hipGetLastError() has the reason
+    bool alloc(const TargetWants &w, size_t slots, size_t n_streams, int channels, bool of_tracker);
     TargetRec *rec_dev(int slot) const { return (TargetRec *)(mem.dev() + (size_t)slot * set_bytes); }
     long long *found_dev(int slot) const { return (long long *)(rec_dev(slot) + n * k); }
     const TargetRec *rec_host(int slot) const { return (const TargetRec *)(mem.host() + (size_t)slot * set_bytes); }
     const long long *found_host(int slot) const { return (const long long *)(rec_host(slot) + n * k); }
+    TrackRec *trk_dev(int slot) const { return trk.dev() + (size_t)slot * n * k; }
+    const TrackRec *trk_host(int slot) const { return trk.host() + (size_t)slot * n * k; }
 };
-// Crop tensors (oatgpu_set_target_crop_tensor; api_croptensor.hip): the switch's parameters and the CALLER's
-// device memory -- never allocated, freed or copied here.  k_crop_tensor writes entry t of it for frame set t of a delivering call.
+// Crop tensors (oatgpu_set_target_crop_tensor; api_croptensor.hip): the switch's parameters and the CALLER's device
+// memory -- never allocated, freed or copied here.  k_crop_tensor writes entry t of it for frame set t of a delivering call.
 struct CropTensor {
     int mode = 0, h = 0, w = 0;                // OATGPU_CROP_*, the window
     double zoom = 1.0;
@@ -172,24 +192,25 @@ struct CropTensor {
     int capacity = 0;
     size_t entry_bytes = 0;
     int last_sets = 0;                         // entries the latest delivering call wrote (oatgpu_target_crop_tensor_sets)
-    HostMem<CropWin> win;                      // host-mapped: [n][kCropMaxWindows] the table of oatgpu_crop_tensor_windows_dev, made by that call
 };
 struct Targets {
     int k = 0;                                 // K; 0: targets off
     TargetSets ring;                           // [ring_slots + 1] beside oatgpu_ctx::res: the ring's slots and the synchronous detectors' extra one
-    std::vector<oatgpu_position> last;         // [sets][n][k] what the latest delivering call delivered (oatgpu_targets)
-    std::vector<int32_t> last_found;           // [sets][n]
-    int last_sets = 0;
     bool append = false;                       // inside oatgpu_track_sequence_dev: every collected set is kept
     bool shapes = false;                       // oatgpu_set_target_shapes: every TargetSets of the context has its ShapeSets
-    std::vector<oatgpu_shape> last_shapes;     // [sets][n][k] beside last, while shapes are on (oatgpu_target_shapes)
     int crop_mode = 0, crop_h = 0, crop_w = 0; // oatgpu_set_target_crops: OATGPU_CROP_*, the window
-    std::vector<uint8_t> last_crops;           // [crop_sets][n][k][h][w][channels] what the latest delivering call delivered (oatgpu_target_crops)
-    int last_crop_sets = 0;                    // (a call of the fused tracker or a single-stage detector delivers none)
-    HostMem<CropWin> cw_win;                   // host-mapped: [n][kCropMaxWindows] the table of oatgpu_crop_windows_dev ...
-    HostMem<uint8_t> cw_out;                   // ... and its windows, [cw_bytes]; made and grown by that call
-    size_t cw_bytes = 0;
     CropTensor ct;                             // oatgpu_set_target_crop_tensor; independent of crop_mode
+    // what the latest delivering call delivered (targets_begin starts all of them over, and ct.last_sets)
+    Delivered<oatgpu_position> last;           // [sets][n][k] oatgpu_targets ...
+    Delivered<int32_t> last_found;             // [sets][n] ... and its candidate counts
+    Delivered<oatgpu_shape> last_shapes;       // [sets][n][k] while shapes are on (oatgpu_target_shapes)
+    Delivered<uint8_t> last_crops;             // [sets][n][k][h][w][channels] while crops are on (oatgpu_target_crops); a call of the
+                                               // fused tracker or a single-stage detector delivers none
+    // the explicit window calls (oatgpu_crop_windows_dev, oatgpu_crop_tensor_windows_dev): made and grown by them; they outlive
+    // both crop switches
+    HostMem<CropWin> win;                      // host-mapped: [n][kCropMaxWindows] the table of windows of either call
+    HostMem<uint8_t> cw_out;                   // host-mapped: [cw_bytes] the windows oatgpu_crop_windows_dev copies out
+    size_t cw_bytes = 0;
 };
 
 // frames a batched tracker has in flight inside its sequence call (run_sequence_in_flight); each sits in a slot of its own
@@ -208,8 +229,9 @@ struct BatchedTrackerState {
     DevMem<u64> bits;                          // [kSeqSlots][n][Palloc/64] the front kernel's threshold words
     DevMem<u64> masks;                         // [kSeqSlots][planes][n][Palloc/64] the slot's planes (the taps)
     HostMem<ResultRec> rec;                    // host-mapped: [kSeqSlots][n] result records, written by the blob kernels through dev()
-    TargetSets tgt;                            // [kSeqSlots] target sets beside rec, while targets are on (oatgpu_set_targets)
-    HostMem<TrackRec> trk;                     // host-mapped: [kSeqSlots][n][K] track sets beside tgt, while tracks are on (oatgpu_set_tracks)
+    TargetSets tgt;                            // [kSeqSlots] target sets beside rec and what rides on them, as the family's switches stand
+    const uint8_t *frame[kSeqSlots] = {};      // the frame set the slot's front launch read, as the caller gave it (tracker_front) ...
+    int entry[kSeqSlots] = {};                 // ... and its place in the call: 0 for a batch call, the frame's index in a sequence call
     Event ev_front[kSeqSlots];                 // stream A: the front launch that wrote this slot's bits has finished
     Event ev_done[kSeqSlots];                  // the slot's back half has finished
     int last = -1;                             // slot of the tracker's latest frame (oatgpu_read_*_mask); -1: none yet
@@ -245,7 +267,7 @@ struct TrackerFilters : PosfiltChain {
 // Target tracks (oatgpu_set_tracks; api_tracks.hip, kernels_tracks.hip): K persistent track slots per camera
 // stream behind the ranked detections of the motion and the subtraction tracker, one k_target_tracks launch a frame behind the
 // slot's k_blob_rank, in frame order.  One state for the context -- both trackers and oatgpu_tracks_update advance it.  Everything
-// below, and BatchedTrackerState::trk, is made by the setter (or by a batched tracker switched on later), never inside a step.
+// below is made by the setter, never inside a step; the trackers' track sets are TargetSets::trk.
 struct Tracks {
     bool on = false;
     int k = 0;                                 // K of oatgpu_set_targets when tracks were switched on
@@ -257,8 +279,7 @@ struct Tracks {
     HostMem<TrackTriple> upd_in;               // host-mapped: [n][K] the detections of oatgpu_tracks_update
     HostMem<TrackRec> upd_out;                 // host-mapped: [n][K] ... and its track set
     Event ev[kSeqSlots];                       // the slot's track launch has finished: frame t's launch waits for frame t - 1's
-    std::vector<oatgpu_track> last;            // [sets][n][K] what the latest delivering call delivered (oatgpu_tracks)
-    int last_sets = 0;
+    Delivered<oatgpu_track> last;              // [sets][n][K] what the latest delivering call delivered (oatgpu_tracks)
     TrackLaunch launch() const { return {params, state, meta, next_id, gate2, k}; }
 };
 
@@ -501,14 +522,12 @@ int upload_frames(oatgpu_ctx *c, const uint8_t *const *frames_host, size_t frame
 // api_markers.hip
 bool own_window_is_nonzero(const oatgpu_config &k);
 int launch_marker_work(oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, int nj, const StepPlan &plan);
-// api_trackfilt.hip
-int tracker_filters_launch(oatgpu_ctx *c, const ResultRec *rec_dev, int slot, int prev_slot, hipStream_t st);
-// ... and the chain as both of its owners use it (who: "marker" or "tracker", in the messages): the checked parameters for
-// configure_chain below, the list a delivering call keeps, and that list to the caller
+// api_trackfilt.hip: the chain as both of its owners use it (who: "marker" or "tracker", in the messages) -- the checked parameters
+// for configure_chain below, and the list of the latest delivering call to the caller
 int chain_params(oatgpu_ctx *c, const oatgpu_marker_filters *f, MarkerFilterParams &p);
-void chain_begin(PosfiltChain &ch);
-void chain_keep(oatgpu_ctx *c, PosfiltChain &ch, const MarkerFiltered *set);
 int chain_hand_out(oatgpu_ctx *c, const PosfiltChain &ch, const char *who, const char *none_yet, oatgpu_filtered *out, int max_sets);
+// ... what every reader of a Delivered list refuses (delivered_to, below): off and none_yet are the texts of the first two
+int delivered_refusals(oatgpu_ctx *c, bool on, const char *off, const char *none_yet, int sets, int max_sets);
 // ... and what the two batched trackers share; `name` is "diff" or "bsub", `what` the call's name in a refusal
 int tracker_refusals(oatgpu_ctx *c, const BatchedTrackerState &bt, const char *name, const char *what);
 int check_batch_dev(oatgpu_ctx *c, const void *frames_dev, const oatgpu_position *out);
@@ -516,44 +535,77 @@ int check_batch(oatgpu_ctx *c, const uint8_t *const *frames_host, int n, const o
 int check_sequence_dev(oatgpu_ctx *c, const void *const *frames_dev, int n_frames, const oatgpu_position *out);
 int open_tap(oatgpu_ctx *c, const BatchedTrackerState &bt, const char *name, const char *none_yet, int s, int which, const uint8_t *out);
 int reset_have(oatgpu_ctx *c, std::vector<char> &have, int s);
+// A step of a batched tracker around its front and blob launches: tracker_begin where the call begins to deliver --
+// every list a tracker's call delivers starts over --; tracker_tail behind the blob launch of the frame in `slot` on st: rank,
+// shape, crops, crop tensor, tracks, filters (bb: the slot's scratch set, rd: its result records; prev_slot: the slot of the frame
+// before inside a sequence call, whose track and filter launches this frame's wait for, -1: none); tracker_hand_out: the finished
+// frame in `slot` to the caller, and every set of it into its list -- the only place a tracker's call keeps.
+void tracker_begin(oatgpu_ctx *c);
+int tracker_tail(oatgpu_ctx *c, const BatchedTrackerState &bt, const BlobBuffers &bb, const ResultRec *rd, int slot, int prev_slot, hipStream_t st);
 void tracker_hand_out(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, oatgpu_position *out);
-// api_targets.hip: k_blob_rank behind a kBlobGlobal back half of scratch set bb on st, for streams [s0, s0 + n), into `slot` of ts;
-// the list a delivering call keeps (targets_begin where it starts to deliver, targets_keep for every set; only: the one stream a
-// single-stage detector analysed, -1: all) -- both do nothing while targets are off
+// api_targets.hip: k_blob_rank behind a kBlobGlobal back half of scratch set bb on st, for streams [s0, s0 + n), into `slot` of ts,
+// and k_blob_shape behind it while shapes are on; the lists a delivering call keeps (targets_begin where it starts to deliver: the
+// whole family's lists start over; targets_keep for every set, its shape set with it; only: the one stream a single-stage detector
+// analysed, -1: all) -- all do nothing while targets are off.  rebuild_target_sets: every home's sets made anew for the switches
+// `w`, built aside -- a failed allocation ("<what>: allocation failed") leaves the context as it was.
 int targets_launch(oatgpu_ctx *c, const BlobBuffers &bb, const TargetSets &ts, int slot, int s0, int n, hipStream_t st);
 void targets_begin(oatgpu_ctx *c);
 void targets_keep(oatgpu_ctx *c, const TargetSets &ts, int slot, int only = -1);
-// api_shapes.hip: k_blob_shape behind targets_launch's k_blob_rank into `slot` of ts.shp (called from targets_launch alone), and the
-// shapes' share of the list a delivering call keeps (called from targets_begin / targets_keep, so that every call that delivers
-// targets delivers shapes) -- all do nothing while shapes are off
-int shapes_launch(oatgpu_ctx *c, const BlobBuffers &bb, const TargetSets &ts, int slot, int s0, int n, hipStream_t st);
-void shapes_begin(oatgpu_ctx *c);
-void shapes_keep(oatgpu_ctx *c, const TargetSets &ts, int slot, int only);
-// api_crops.hip: k_target_crops behind shapes_launch into `slot` of ts.crp, from the frame set the slot remembers (called from
-// targets_launch alone), and the crops' share of the list a delivering call keeps (called from targets_begin / targets_keep) -- all
-// do nothing while crops are off or for a target set without crop sets
-int crops_launch(oatgpu_ctx *c, const TargetSets &ts, int slot, int s0, int n, hipStream_t st);
-void crops_begin(oatgpu_ctx *c);
-void crops_keep(oatgpu_ctx *c, const TargetSets &ts, int slot);
-int check_crop_size(oatgpu_ctx *c, const char *what, int h, int w);        // a window's limits, with the refusal's text (what: the call)
-// api_croptensor.hip: crops_launch's neighbour -- k_crop_tensor behind it on the same stream, from the frame set the slot
-// remembers into the entry the slot remembers of the caller's memory (a batched tracker's target sets only) --, the count a
-// delivering call keeps, and the refusal of a sequence call of more frames than the caller's memory has entries (what: the
-// call's name).  All do nothing while crop tensors are off.
-int crop_tensor_launch(oatgpu_ctx *c, const TargetSets &ts, int slot, int s0, int n, hipStream_t st);
-void crop_tensor_begin(oatgpu_ctx *c);
-void crop_tensor_keep(oatgpu_ctx *c, const TargetSets &ts);
+int rebuild_target_sets(oatgpu_ctx *c, const TargetWants &w, const char *what);
+// api_crops.hip: k_target_crops on the ranked frame in the tracker's slot, from the frame set the slot remembers into the slot's crop
+// set, and the crop set tracker_hand_out keeps -- both do nothing while crops are off.  And what target crops and crop tensors
+// share (what: the call's name in a refusal): the CropLaunch base from a tracker's slot and from the context's table of explicit
+// windows; the checks of a mode, of a window's size, and of what the context must be for a crop switch to go on; an explicit call's
+// own checks (check_windows: per_stream and the window) and the rest up to its launch (load_windows: results outstanding, the
+// context drained, the caller's windows in the context's table -- made on first use, built aside).
+int crops_launch(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, hipStream_t st);
+void crops_keep(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot);
+void crop_launch_from_slot(CropLaunch &a, const oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, int mode, int h, int w);
+void crop_launch_from_table(CropLaunch &a, const oatgpu_ctx *c, const void *frames_dev, int per_stream, int h, int w);
+int check_crop_mode(oatgpu_ctx *c, const char *what, int mode);
+int check_crop_size(oatgpu_ctx *c, const char *what, int h, int w);
+int check_crop_switch(oatgpu_ctx *c, const char *what, int mode);
+int check_windows(oatgpu_ctx *c, const char *what, int per_stream, int h, int w);
+int load_windows(oatgpu_ctx *c, const char *what, const oatgpu_crop_window *win, int per_stream);
+// api_croptensor.hip: crops_launch's neighbour -- k_crop_tensor behind it on the same stream, from the slot's frame set into the
+// entry the slot remembers of the caller's memory --, the count tracker_hand_out keeps, and the refusal of a sequence call of more
+// frames than the caller's memory has entries.  All do nothing while crop tensors are off.
+int crop_tensor_launch(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, hipStream_t st);
+void crop_tensor_keep(oatgpu_ctx *c);
 int crop_tensor_room(oatgpu_ctx *c, int n_frames, const char *what);
-// api_tracks.hip: k_target_tracks on the target set recs of the tracker's slot `slot`, on st right behind its k_blob_rank, into the
-// slot's track set `set`; prev_slot as tracker_filters_launch's.  The list a delivering call keeps (tracks_begin, tracks_keep) and a
-// batched tracker's own track sets (false: hipGetLastError() has the reason).  All do nothing while tracks are off.
-int tracks_launch(oatgpu_ctx *c, const TargetRec *recs, TrackRec *set, int slot, int prev_slot, hipStream_t st);
-void tracks_begin(oatgpu_ctx *c);
-void tracks_keep(oatgpu_ctx *c, const TrackRec *set);
-bool tracks_alloc_sets(const oatgpu_ctx *c, HostMem<TrackRec> &sets, int k);
+// api_tracks.hip: k_target_tracks on the target set of the tracker's slot `slot`, on st behind its ranking, into the slot's track set;
+// the filter chain on the slot's result records behind that.  Inside a sequence call (st is a B stream) consecutive frames sit on
+// different HIP streams: each launch waits for its own event of the frame before it (prev_slot) and records its own; the
+// synchronous step runs on stream A alone and needs neither.  Each does nothing while its switch is off.
+int tracks_launch(oatgpu_ctx *c, const TargetSets &ts, int slot, int prev_slot, hipStream_t st);
+int tracker_filters_launch(oatgpu_ctx *c, const ResultRec *rec_dev, int slot, int prev_slot, hipStream_t st);      // (api_trackfilt.hip)
 // api_measure.hip
 void prof_fold(oatgpu_ctx *c);
 #pragma GCC visibility pop
+
+// A Delivered list to its reader, behind the reader's null checks -> the number of sets
+template <class T>
+static int delivered_to(oatgpu_ctx *c, const Delivered<T> &d, bool on, const char *off, const char *none_yet, void *out, int max_sets)
+{
+    const int rc = delivered_refusals(c, on, off, none_yet, d.sets, max_sets);
+    if (rc) return rc;
+    memcpy(out, d.items.data(), (size_t)d.sets * d.per * sizeof(T));
+    return d.sets;
+}
+
+// The homes of target sets: f(sets, slots, of_tracker, on) for the result ring and the two batched trackers' slots; on: the home
+// exists at the moment (a tracker that is off has no sets)
+template <class F> static void for_each_target_home(oatgpu_ctx *c, F f)
+{
+    f(c->tg.ring, (size_t)c->ring_slots + 1, false, true);
+    f(c->df.tgt, (size_t)kSeqSlots, true, c->df.on);
+    f(c->bs.tgt, (size_t)kSeqSlots, true, c->bs.on);
+}
+// ... and the family's switches as they stand
+static inline TargetWants wants_of(const oatgpu_ctx *c)
+{
+    return {c->tg.k, c->tg.shapes, c->tg.crop_mode, c->tg.crop_h, c->tg.crop_w, c->tk.on};
+}
 
 // the ten values of a detector: an oatgpu_marker holds a marker's, the context's own come out of its config
 static inline oatgpu_marker detector_of(const oatgpu_config &k)
@@ -583,14 +635,14 @@ static inline size_t track_in_bytes(const oatgpu_ctx *c) { return (size_t)c->g.H
 static inline size_t tracker_in_bytes(const oatgpu_ctx *c) { return (size_t)c->g.H * c->g.W * (c->tb_on ? 1 : c->cfg.channels); }
 // ... and what the front launch of either takes from the context: frame set f1 (f2: and the next) into the bits of `slot` (and
 // slot2), the ROI, the Bayer patterns with oatgpu_set_tracker_bayer on, the streams' maps with oatgpu_set_tracker_undistort on
-// (the slots' crop sets remember their frame set here, and its place `entry` in the call -- f2's is entry + 1: k_target_crops
-// and k_crop_tensor cut from it behind the slot's ranking, the latter into that entry of the caller's memory)
+// (the slots remember their frame set here, and its place `entry` in the call -- f2's is entry + 1: k_target_crops and k_crop_tensor
+// cut from it behind the slot's ranking, the latter into that entry of the caller's memory)
 static inline void tracker_front(const oatgpu_ctx *c, BatchedTrackerState &bt, const void *f1, const void *f2, int slot, int slot2, int entry,
                                  FrontLaunch &a)
 {
     a.frames = (const uint8_t *)f1; a.frames2 = (const uint8_t *)f2; a.channels = c->cfg.channels;
-    bt.tgt.crp.frame[slot] = a.frames; bt.tgt.crp.entry[slot] = entry;
-    if (f2) { bt.tgt.crp.frame[slot2] = a.frames2; bt.tgt.crp.entry[slot2] = entry + 1; }
+    bt.frame[slot] = a.frames; bt.entry[slot] = entry;
+    if (f2) { bt.frame[slot2] = a.frames2; bt.entry[slot2] = entry + 1; }
     a.bits = bt.bits_of(slot); a.bits2 = f2 ? bt.bits_of(slot2) : nullptr;
     a.roi = c->roi;
     a.bayer = c->tb_on ? c->tb_pat.data() : nullptr;
@@ -662,7 +714,7 @@ static int configure_chain(oatgpu_ctx *c, Chain &cur, const oatgpu_marker_filter
         ok = ok && ch.state.alloc(n * sizeof(KalmanState)) == hipSuccess;
         ok = ok && extra(ch, n);
         if (!ok) return fail(c, OATGPU_E_NOMEM, "%s filters: allocation failed: %s", who, hipGetErrorString(hipGetLastError()));
-        ch.last.reserve(n);
+        ch.last.items.reserve(n);
     }
     HIPCHK(c, hipMemcpy(ch.params, hp.data(), sizeof(MarkerFilterParams), hipMemcpyHostToDevice));
     launch_kalman_reset(ch.state, (int)n, 0u, c->stream);
@@ -670,7 +722,7 @@ static int configure_chain(oatgpu_ctx *c, Chain &cur, const oatgpu_marker_filter
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (first) cur = std::move(made);
     cur.on = true;
-    cur.last_sets = 0;
+    cur.last.begin();
     return OATGPU_OK;
 }
 
