@@ -54,7 +54,8 @@ extern "C" {
  * oatgpu_set_target_shapes, oatgpu_target_shapes, with the struct oatgpu_shape; target crops -- oatgpu_set_target_crops,
  * oatgpu_target_crops, oatgpu_crop_windows_dev, with the struct oatgpu_crop_window and the OATGPU_CROP_* modes; crop tensors --
  * oatgpu_set_target_crop_tensor, oatgpu_target_crop_tensor_sets, oatgpu_crop_tensor_windows_dev, with the struct
- * oatgpu_crop_tensor_fmt and the OATGPU_TENSOR_* dtypes. */
+ * oatgpu_crop_tensor_fmt and the OATGPU_TENSOR_* dtypes; target masks -- oatgpu_set_target_mask_tensor,
+ * oatgpu_target_mask_tensor_sets. */
 
 enum {
     OATGPU_OK = 0,
@@ -908,6 +909,62 @@ int oatgpu_target_crop_tensor_sets(oatgpu_ctx *ctx);
  * reach tensors.  Refused while results are outstanding. */
 int oatgpu_crop_tensor_windows_dev(oatgpu_ctx *ctx, const void *frames_dev, const oatgpu_crop_window *win, int32_t per_stream,
                                    int32_t h, int32_t w, const oatgpu_crop_tensor_fmt *fmt, void *out_dev);
+
+/* ---- target masks: each ranked blob's own pixels as a device tensor ----
+ * A crop or a crop tensor shows an h x w window of the frame around every ranked blob.  With two animals near each other the window
+ * of rank 0 also holds rank 1, a reflection, or a blob too small to be ranked.  With target masks on, the same six calls -- the batch
+ * and sequence calls of the motion and the subtraction tracker -- also write, for every frame set, rank and camera, which elements
+ * of that window are THIS blob, into DEVICE memory the caller owns: one more kernel (k_target_mask) behind the frame's ranking,
+ * launched only while the switch is on; nothing is downloaded and nothing is labelled on the host.  The reference has nothing like
+ * this: the semantics are this project's own.
+ *
+ * Window.  The window of (stream, rank) is exactly the window of "crop tensors" above for the same mode, h, w and zoom: valid,
+ * upright, centre and direction as derived there (the rank's centroid; the body axis in OATGPU_CROP_AXIS where the shape has
+ * axis_valid; any zoom but 1.0 makes it a gather along (zoom * axis_x, zoom * axis_y), or (zoom, 0.0) otherwise), with the same
+ * check: a centre or a direction that is not finite, or a centre beyond +-1e6, is no window.
+ *
+ * Source pixel of element (i, j), 0 <= i < h, 0 <= j < w.  Upright (the copy): (rint(cx) - w/2 + j, rint(cy) - h/2 + i).
+ * Otherwise (the gather): the crop's X = (cx + u * ax) - v * ay, Y = (cy + u * ay) + v * ax in fp64 with u = j - w/2, v = i - h/2,
+ * then qx = rint(32 * X), qy = rint(32 * Y) under the same range check (|qx|, |qy| < 2^30, else outside every frame); the source
+ * pixel is ((qx + 16) >> 5, (qy + 16) >> 5) with arithmetic shifts.  This is the nearest pixel to the position the crop's bilinear
+ * gather samples (a tie goes up), so a mask and a crop tensor of the same setting are aligned.
+ *
+ * Value.  The element is ON when all three hold: the source pixel is inside the frame; its bit in the final mask is set -- the
+ * mask findContours sees, after erode / dilate, with the one-pixel frame zeroed --; and it belongs to the 8-connected component
+ * whose first pixel in raster order is this rank's first_pixel.  Otherwise it is OFF: background, another component, a blob inside
+ * this blob's hole, the hole itself, a pixel outside the frame, an invalid rank or window.  ON / OFF are 255 / 0 for
+ * OATGPU_TENSOR_U8 and 1.0 / 0.0 for OATGPU_TENSOR_F16 and OATGPU_TENSOR_F32.
+ *
+ * mode OATGPU_CROP_OFF switches target masks off (the default); nothing else is looked at.  Otherwise mode, h, w and zoom have the
+ * meaning and the limits of oatgpu_set_target_crop_tensor, dtype is one of the three OATGPU_TENSOR_* values, and out_dev is
+ * CALLER-OWNED DEVICE memory, 16-byte aligned, of capacity_sets (>= 1) entries of n_streams * K * h * w elements of the dtype, laid
+ * out [sets][n][K][h][w]: element (((t * n_streams + s) * K + j) * h + i) * w + x.  There is no channel axis.  The library never
+ * allocates, frees or copies it.  Frame set t of a delivering call goes into entry t, not into the tracker's slot; every element of
+ * a delivered entry is written on every launch; entries past the delivered count are not touched; the entry is complete when the
+ * call returns.  A sequence call of more frames than capacity_sets is refused with OATGPU_E_INVALID before anything is launched
+ * and with nothing changed.  The fused tracker's own calls and the single-stage detectors deliver none and reset the count, as for
+ * crop tensors.
+ *
+ * Target masks are read-only passengers and the switch allocates nothing: the ordinary results, oatgpu_targets,
+ * oatgpu_target_shapes, oatgpu_target_crops, the crop tensor, oatgpu_tracks, both filter chains, the taps and every state are bit
+ * for bit what they are with the switch off.  The switch is independent of oatgpu_set_target_crops and
+ * oatgpu_set_target_crop_tensor.  The mask lives in the tracker's own pixel domain -- behind oatgpu_set_tracker_bayer the
+ * demosaiced frame's, behind oatgpu_set_tracker_undistort the undistorted frame's --, so unlike those two it is NOT refused with
+ * either front end, in either order of switching.
+ *
+ * OATGPU_E_INVALID, with nothing changed and a working context, when: targets are off; shapes are off for OATGPU_CROP_AXIS;
+ * results are outstanding or a frame set is partly staged; mode, h, w or zoom is out of range as for crop tensors; the dtype is
+ * none of the three; out_dev is null or not 16-byte aligned; capacity_sets < 1.  While the switch is on oatgpu_set_targets is
+ * refused, and in axis mode oatgpu_set_target_shapes(0).
+ *
+ * Left out: an explicit-window form; masks in the fused tracker's own calls and in the host binaries; a plane of rank labels;
+ * masked crops (tensor * mask is one line for the caller); marker planes; several GPUs. */
+int oatgpu_set_target_mask_tensor(oatgpu_ctx *ctx, int32_t mode, int32_t h, int32_t w, double zoom, int32_t dtype, void *out_dev,
+                                  int32_t capacity_sets);
+/* The number of entries the LATEST delivering call wrote (1 for a batch call, n_frames for a sequence call).  OATGPU_E_INVALID when
+ * target masks are off, or no such call has run since oatgpu_set_target_mask_tensor (or the latest delivering call was not one of
+ * the six). */
+int oatgpu_target_mask_tensor_sets(oatgpu_ctx *ctx);
 
 /* Deferred completion of the stage-by-stage operators below (default off).  With on = 1 a frame filter (oatgpu_mog_filter,
  * _bsub_filter, _mask_filter, _thresh_filter, _undistort_filter, _bgr2hsv, _cvt_color) or a detector (oatgpu_detect_hsv / _thresh / _diff)

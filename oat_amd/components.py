@@ -605,6 +605,43 @@ class _Detector(_Context):
                                                           C.c_void_p(out.data_ptr())))
         return out
 
+    # -- target masks (oatgpu_set_target_mask_tensor / oatgpu_target_mask_tensor_sets) --
+    def set_target_mask_tensor(self, h, w=None, axis=False, zoom=1.0, dtype="uint8", capacity=1):
+        """Target masks: for the window set_target_crop_tensor(h, w, axis, zoom) cuts around every ranked blob, which of its pixels
+        ARE that blob -- not another animal, a reflection, a blob in its hole or background -- as a torch tensor on the context's
+        device, written by the same track / track_dev / track_sequence_dev calls of a batched tracker (set_targets must be on;
+        axis=True needs set_target_shapes).  An element is ON where the pixel nearest to where the crop tensor samples is set in
+        the final mask and belongs to the rank's 8-connected component: 255 / 0 for "uint8", 1.0 / 0.0 for "float16" / "float32".
+        Allocates a zeroed tensor [capacity, n_streams, k, h, w] (no channel axis), keeps it alive and returns it; frame set t of
+        a call lands in entry t, so a sequence call takes at most `capacity` frames.  set_target_mask_tensor(None) switches it off
+        and drops the tensor.  Independent of set_target_crops and set_target_crop_tensor; works behind bayer(...) and
+        undistort(True), where those two are refused."""
+        if h is None:
+            self._chk(self.lib.oatgpu_set_target_mask_tensor(self.ctx, ffi.CROP_OFF, 0, 0, 1.0, 0, None, 0))
+            self._mask_tensor = None
+            return None
+        import torch
+        w = h if w is None else w
+        name = str(dtype).replace("torch.", "")
+        if name not in self._TENSOR_DTYPES:
+            raise ValueError(f"dtype must be 'uint8', 'float16' or 'float32', got {dtype!r}")
+        k = getattr(self, "_targets_k", 0)
+        shape = (max(int(capacity), 1), self.n_streams, max(k, 1), max(int(h), 1), max(int(w), 1))
+        t = torch.zeros(shape, dtype=getattr(torch, name), device=self._torch_device())
+        torch.cuda.synchronize(t.device)
+        self._chk(self.lib.oatgpu_set_target_mask_tensor(self.ctx, ffi.CROP_AXIS if axis else ffi.CROP_UPRIGHT, int(h), int(w), float(zoom),
+                                                         self._TENSOR_DTYPES[name], C.c_void_p(t.data_ptr()), int(capacity)))
+        self._mask_tensor = t
+        return t
+
+    def target_mask_tensor(self):
+        """The entries the latest track / track_dev / track_sequence_dev call of a batched tracker wrote: the zero-copy view
+        tensor[:sets] of set_target_mask_tensor's tensor (one entry for a step, one per frame for a sequence call)."""
+        sets = self.lib.oatgpu_target_mask_tensor_sets(self.ctx)
+        if sets < 0:
+            self._chk(sets)
+        return self._mask_tensor[:sets]
+
     # -- target tracks (oatgpu_set_tracks / oatgpu_tracks / oatgpu_tracks_update, DESIGN.md 9j) --
     def set_tracks(self, kalman=None, gate=float("inf"), homography=None, regions=None):
         """oatgpu_set_tracks: k persistent track slots per camera (k of set_targets, which must be on) behind the ranked

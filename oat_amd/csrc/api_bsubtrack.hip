@@ -117,6 +117,7 @@ extern "C" int oatgpu_bsub_track_sequence_dev(oatgpu_ctx *c, const void *const *
     rc = bsub_refusals(c, "bsub_track_sequence", alpha);
     if (rc) return rc;
     rc = crop_tensor_room(c, n_frames, "bsub_track_sequence");
+    if (!rc) rc = mask_tensor_room(c, n_frames, "bsub_track_sequence");
     if (rc) return rc;
     if (n_frames == 0) return OATGPU_OK;
     rc = open_sync(c);

@@ -64,12 +64,29 @@ int check_crop_size(oatgpu_ctx *c, const char *what, int h, int w)
     return OATGPU_OK;
 }
 
-// what the context must be for a crop switch to go on
-int check_crop_switch(oatgpu_ctx *c, const char *what, int mode)
+// a zoom of crop tensors and of target masks
+int check_crop_zoom(oatgpu_ctx *c, const char *what, double zoom)
+{
+    if (!(zoom >= 1.0 / 16 && zoom <= 16.0))          // (false for a NaN)
+        return fail(c, OATGPU_E_INVALID, "%s: the zoom must be in 1/16 .. 16 (got %g)", what, zoom);
+    return OATGPU_OK;
+}
+
+// what every switch that puts a window around a ranked blob needs of the target family
+int check_window_riders(oatgpu_ctx *c, const char *what, int mode)
 {
     if (!c->tg.k) return fail(c, OATGPU_E_INVALID, "%s: targets are off (oatgpu_set_targets)", what);
     if (mode == OATGPU_CROP_AXIS && !c->tg.shapes)
         return fail(c, OATGPU_E_INVALID, "%s: windows along the body axis need target shapes (oatgpu_set_target_shapes)", what);
+    return OATGPU_OK;
+}
+
+// what the context must be for a crop switch to go on: that, and a front end whose frames are the caller's own (the windows are cut
+// from the caller's frame set; target masks, cut from the tracker's own mask, do not share these two: api_targetmask.hip)
+int check_crop_switch(oatgpu_ctx *c, const char *what, int mode)
+{
+    const int rc = check_window_riders(c, what, mode);
+    if (rc) return rc;
     if (c->tb_on) return fail(c, OATGPU_E_INVALID, "%s with Bayer frames on (oatgpu_set_tracker_bayer) is not supported", what);
     if (c->tu_on) return fail(c, OATGPU_E_INVALID, "%s with undistortion on (oatgpu_set_tracker_undistort) is not supported", what);
     return OATGPU_OK;

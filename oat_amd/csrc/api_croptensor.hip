@@ -77,8 +77,8 @@ extern "C" int oatgpu_set_target_crop_tensor(oatgpu_ctx *c, int32_t mode, int32_
     if (mode != OATGPU_CROP_OFF) {
         rc = check_crop_size(c, what, h, w);
         if (rc) return rc;
-        if (!(zoom >= 1.0 / 16 && zoom <= 16.0))          // (false for a NaN)
-            return fail(c, OATGPU_E_INVALID, "%s: the zoom must be in 1/16 .. 16 (got %g)", what, zoom);
+        rc = check_crop_zoom(c, what, zoom);
+        if (rc) return rc;
         rc = check_fmt(c, what, fmt, out_dev);
         if (rc) return rc;
         if (capacity_sets < 1) return fail(c, OATGPU_E_INVALID, "%s: room for at least one frame set is needed (got %d)", what, capacity_sets);

@@ -111,6 +111,7 @@ extern "C" int oatgpu_diff_sequence_dev(oatgpu_ctx *c, const void *const *frames
     rc = tracker_refusals(c, c->df, "diff", "diff_sequence");
     if (rc) return rc;
     rc = crop_tensor_room(c, n_frames, "diff_sequence");
+    if (!rc) rc = mask_tensor_room(c, n_frames, "diff_sequence");
     if (rc) return rc;
     if (n_frames == 0) return OATGPU_OK;
     rc = open_sync(c);

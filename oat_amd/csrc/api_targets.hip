@@ -73,6 +73,7 @@ void targets_begin(oatgpu_ctx *c)
     Targets &tg = c->tg;
     tg.last.begin(); tg.last_found.begin(); tg.last_shapes.begin(); tg.last_crops.begin();
     tg.ct.last_sets = 0;
+    tg.mt.last_sets = 0;
 }
 
 static oatgpu_shape shape_out(const TargetRec &t, const ShapeRec &r)
@@ -123,6 +124,7 @@ extern "C" int oatgpu_set_targets(oatgpu_ctx *c, int32_t k)
     if (c->tg.shapes) return fail(c, OATGPU_E_INVALID, "set_targets while target shapes are on: switch them off first (oatgpu_set_target_shapes)");
     if (c->tg.crop_mode) return fail(c, OATGPU_E_INVALID, "set_targets while target crops are on: switch them off first (oatgpu_set_target_crops)");
     if (c->tg.ct.mode) return fail(c, OATGPU_E_INVALID, "set_targets while crop tensors are on: switch them off first (oatgpu_set_target_crop_tensor)");
+    if (c->tg.mt.mode) return fail(c, OATGPU_E_INVALID, "set_targets while target masks are on: switch them off first (oatgpu_set_target_mask_tensor)");
     if (k > 0 && c->deferred) return fail(c, OATGPU_E_INVALID, "set_targets with deferred completion on (oatgpu_set_deferred) is not supported");
     if (k > 0 && c->mk.n) return fail(c, OATGPU_E_INVALID, "set_targets with marker sets configured (oatgpu_set_markers) is not supported");
     int rc = open_sync(c);
@@ -162,6 +164,8 @@ extern "C" int oatgpu_set_target_shapes(oatgpu_ctx *c, int32_t on)
         return fail(c, OATGPU_E_INVALID, "set_target_shapes(0) while target crops follow the body axis: switch them off first (oatgpu_set_target_crops)");
     if (!on && tg.ct.mode == OATGPU_CROP_AXIS)
         return fail(c, OATGPU_E_INVALID, "set_target_shapes(0) while crop tensors follow the body axis: switch them off first (oatgpu_set_target_crop_tensor)");
+    if (!on && tg.mt.mode == OATGPU_CROP_AXIS)
+        return fail(c, OATGPU_E_INVALID, "set_target_shapes(0) while target masks follow the body axis: switch them off first (oatgpu_set_target_mask_tensor)");
     if (!on) {
         tg.shapes = false;
         tg.last_shapes.begin();

@@ -103,6 +103,7 @@ int tracker_tail(oatgpu_ctx *c, const BatchedTrackerState &bt, const BlobBuffers
     int rc = targets_launch(c, bb, bt.tgt, slot, 0, c->cfg.n_streams, st);      // (every stream's roots and sums are still in the set)
     if (!rc) rc = crops_launch(c, bt, slot, st);
     if (!rc) rc = crop_tensor_launch(c, bt, slot, st);
+    if (!rc) rc = mask_tensor_launch(c, bt, bb, slot, st);
     if (!rc) rc = tracks_launch(c, bt.tgt, slot, prev_slot, st);
     return rc ? rc : tracker_filters_launch(c, rd, slot, prev_slot, st);      // (the caller records the slot's "done" event behind this)
 }
@@ -114,6 +115,7 @@ void tracker_hand_out(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, oa
     targets_keep(c, bt.tgt, slot);
     crops_keep(c, bt, slot);
     crop_tensor_keep(c);
+    mask_tensor_keep(c);
     if (c->tk.on) c->tk.last.keep(bt.n * (size_t)c->tk.k, bt.tgt.trk_host(slot));
 }
 

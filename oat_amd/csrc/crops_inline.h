@@ -1,7 +1,9 @@
 // crops_inline.h -- the crop kernel: ONE definition of a window, of its two pixel rules and of the lane mapping for both kernels
 // that cut windows out of frames -- k_target_crops (kernels_crops.hip: bytes into a crop set that may be host-mapped memory,
 // DESIGN.md 9l) and k_crop_tensor (kernels_croptensor.hip: bytes, halves or floats into the caller's device memory).
-// The text in include/oatgpu.h ("target crops", "crop tensors") is the contract.
+// A third kernel takes the window and nothing of the pixels: k_target_mask (kernels_targetmask.hip) writes, for the
+// crop tensor's window, which source pixels are the rank's own blob.
+// The text in include/oatgpu.h ("target crops", "crop tensors", "target masks") is the contract.
 //
 // The body is one kernel template, k_crop_windows<CH, OUT>, and the two kernels are its instantiations by OUT: the rules are
 // written once, and what differs -- the zoom of a rank's window, the conversion, the stores -- stands under `if constexpr`.  Helper
@@ -23,9 +25,17 @@
 //   kCropOutBytes  32-bit, one to three a lane (nothing wider than 64 bits; the crop set may be host-mapped memory)
 //   kCropOutU8     the same dwords, plain stores into device memory
 //   kCropOutF16    planar, one 64-bit store a channel;  kCropOutF32  planar, two 64-bit stores a channel
+//   kCropOutMask + one of the three: one plane [h][w], the same stores -- one dword, one 64-bit store, two 64-bit stores a lane
+// Target masks (OUT >= kCropOutMask; CH = 1): the pixel fetch is replaced.  The source pixel of an element is where the copy reads,
+//   or the pixel nearest to where the gather samples -- ((qx + 16) >> 5, (qy + 16) >> 5) --; the element is ON where that pixel lies
+//   inside the frame, its bit of the final mask `fin` is set, and the root of its run is the rank's (the padded index of
+//   TargetRec.first_pixel, as k_blob_shape forms it).  Only a set bit costs lookups: run_head, then uf_root (blobruns_inline.h),
+//   the last (head -> root) pair kept across the lane's four pixels -- consecutive pixels of a row mostly share a run.  Plain loads:
+//   what is read is final from the end of k_merge to the set's next row scan (kernels_blob.hip, k_blob_shape's comment).
 #pragma once
 #include "oatgpu_internal.h"
 #include "posfilt_inline.h"
+#include "blobruns_inline.h"
 #include "undistort_inline.h"
 
 namespace oatgpu {
@@ -39,7 +49,8 @@ static_assert(kCropMaxSide / 4 <= 64, "a row's lanes fit the smallest workgroup"
 __device__ __forceinline__ void crop_keep_stores_apart() { asm volatile("" ::: "memory"); }
 
 // what a launch takes by OUT: k_target_crops its CropLaunch as it always did, k_crop_tensor the CropTensorLaunch around it
-template <int OUT> struct CropLaunchOf { typedef CropTensorLaunch type; };
+// ... and k_target_mask the MaskTensorLaunch around that
+template <int OUT> struct CropLaunchOf { typedef std::conditional_t<(OUT >= kCropOutMask), MaskTensorLaunch, CropTensorLaunch> type; };
 template <> struct CropLaunchOf<kCropOutBytes> { typedef CropLaunch type; };
 
 template <int CH, int OUT>
@@ -98,36 +109,73 @@ __global__ __launch_bounds__(kCropBlock) void k_crop_windows(int H, int W, typen
 #pragma unroll
     for (int q = 0; q < 4; ++q)
         for (int c = 0; c < CH; ++c) px[q][c] = 0u;
-    const uint8_t *src = a.frames + (size_t)blockIdx.z * H * W * CH;
-    if (win.valid && win.upright) {
-        const int x = (int)rint(win.cx) - a.w / 2 + j0, y = (int)rint(win.cy) - a.h / 2 + i;
-        if ((unsigned)y < (unsigned)H) {
-            const uint8_t *p = src + ((ptrdiff_t)y * W + x) * CH;
-            if (x >= 0 && x + 3 < W) {
-                uint32_t w[CH];
+    if constexpr (OUT < kCropOutMask) {
+        const uint8_t *src = a.frames + (size_t)blockIdx.z * H * W * CH;
+        if (win.valid && win.upright) {
+            const int x = (int)rint(win.cx) - a.w / 2 + j0, y = (int)rint(win.cy) - a.h / 2 + i;
+            if ((unsigned)y < (unsigned)H) {
+                const uint8_t *p = src + ((ptrdiff_t)y * W + x) * CH;
+                if (x >= 0 && x + 3 < W) {
+                    uint32_t w[CH];
 #pragma unroll
-                for (int c = 0; c < CH; ++c) w[c] = ld_u32(p + 4 * c);
+                    for (int c = 0; c < CH; ++c) w[c] = ld_u32(p + 4 * c);
 #pragma unroll
-                for (int b = 0; b < 4 * CH; ++b) px[b / CH][b % CH] = (w[b >> 2] >> ((b & 3) * 8)) & 255u;
-            } else {
+                    for (int b = 0; b < 4 * CH; ++b) px[b / CH][b % CH] = (w[b >> 2] >> ((b & 3) * 8)) & 255u;
+                } else {
 #pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if ((unsigned)(x + q) < (unsigned)W)
-                        for (int c = 0; c < CH; ++c) px[q][c] = p[q * CH + c];
+                    for (int q = 0; q < 4; ++q)
+                        if ((unsigned)(x + q) < (unsigned)W)
+                            for (int c = 0; c < CH; ++c) px[q][c] = p[q * CH + c];
+                }
+            }
+        } else if (win.valid) {
+            const double cx = win.cx, cy = win.cy, ax = win.ax, ay = win.ay;
+            const double v = (double)(i - a.h / 2);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const double u = (double)(j0 + q - a.w / 2);
+                const double X = (cx + u * ax) - v * ay, Y = (cy + u * ay) + v * ax;
+                const double qxd = rint(X * 32.0), qyd = rint(Y * 32.0);
+                // (a position that is not finite or beyond 2^25 pixels lies outside every frame; the comparison is false for a NaN)
+                if (fabs(qxd) < 1073741824.0 && fabs(qyd) < 1073741824.0) {
+                    const int qx = (int)qxd, qy = (int)qyd;
+                    remap_core<CH>(src, H, W, qx >> 5, qy >> 5, qx & 31, qy & 31, px[q]);
+                }
             }
         }
-    } else if (win.valid) {
-        const double cx = win.cx, cy = win.cy, ax = win.ax, ay = win.ay;
-        const double v = (double)(i - a.h / 2);
+    } else {
+        // a target mask: px[q][0] = 1 where the element's source pixel is the rank's own
+        static_assert(CH == 1, "a mask has no channel axis");
+        if (win.valid) {
+            const Geom &g = a.g;
+            const size_t soff = (size_t)blockIdx.z * (g.Palloc >> 6);
+            const u64 *fin = a.b.fin + soff, *trans = a.b.trans + soff;
+            const int *carry = a.b.carry + (size_t)blockIdx.z * g.H * g.words;
+            const int *parent = a.b.parent + (size_t)blockIdx.z * g.Palloc;
+            const int fp = (int)(unsigned)word[3], fy = fp / W;            // TargetRec.first_pixel -> the rank's root, a padded index
+            const int root_j = fy * g.Wp + (fp - fy * W);
+            const double cx = win.cx, cy = win.cy, ax = win.ax, ay = win.ay;
+            const double v = (double)(i - a.h / 2);
+            int m_head = -1, m_root = -1;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const double u = (double)(j0 + q - a.w / 2);
-            const double X = (cx + u * ax) - v * ay, Y = (cy + u * ay) + v * ax;
-            const double qxd = rint(X * 32.0), qyd = rint(Y * 32.0);
-            // (a position that is not finite or beyond 2^25 pixels lies outside every frame; the comparison is false for a NaN)
-            if (fabs(qxd) < 1073741824.0 && fabs(qyd) < 1073741824.0) {
-                const int qx = (int)qxd, qy = (int)qyd;
-                remap_core<CH>(src, H, W, qx >> 5, qy >> 5, qx & 31, qy & 31, px[q]);
+            for (int q = 0; q < 4; ++q) {
+                int x = -1, y = -1;
+                if (win.upright) {
+                    x = (int)rint(cx) - a.w / 2 + j0 + q; y = (int)rint(cy) - a.h / 2 + i;
+                } else {
+                    const double u = (double)(j0 + q - a.w / 2);
+                    const double X = (cx + u * ax) - v * ay, Y = (cy + u * ay) + v * ax;
+                    const double qxd = rint(X * 32.0), qyd = rint(Y * 32.0);
+                    if (fabs(qxd) < 1073741824.0 && fabs(qyd) < 1073741824.0) {      // (as the gather: outside every frame otherwise)
+                        x = ((int)qxd + 16) >> 5; y = ((int)qyd + 16) >> 5;
+                    }
+                }
+                if ((unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H &&
+                    ((fin[(size_t)y * g.words + (x >> 6)] >> (x & 63)) & 1ull) != 0ull) {
+                    const int head = run_head(g, trans, carry, y, x);
+                    if (head != m_head) { m_head = head; m_root = uf_root(parent, head); }
+                    px[q][0] = m_root == root_j ? 1u : 0u;
+                }
             }
         }
     }
@@ -150,6 +198,21 @@ __global__ __launch_bounds__(kCropBlock) void k_crop_windows(int H, int W, typen
         uint32_t *o = reinterpret_cast<uint32_t *>(a.out + ((at * a.h + i) * a.w + j0) * CH);
 #pragma unroll
         for (int c = 0; c < CH; ++c) { o[c] = w[c]; crop_keep_stores_apart(); }
+    } else if constexpr (OUT >= kCropOutMask) {
+        // a mask plane [h][w]: ON / OFF are 255 / 0 in bytes, 1.0 / 0.0 in halves and floats
+        const size_t e = (at * a.h + i) * a.w + j0;
+        if constexpr (OUT == kCropOutMask + kCropOutU8) {
+            *reinterpret_cast<uint32_t *>(a.out + e) = (px[0][0] | px[1][0] << 8 | px[2][0] << 16 | px[3][0] << 24) * 255u;
+        } else if constexpr (OUT == kCropOutMask + kCropOutF16) {
+            *reinterpret_cast<uint2 *>(reinterpret_cast<unsigned short *>(a.out) + e) =
+                make_uint2((px[0][0] | px[1][0] << 16) * 0x3c00u, (px[2][0] | px[3][0] << 16) * 0x3c00u);
+        } else {
+            static_assert(OUT == kCropOutMask + kCropOutF32, "the three tensor dtypes");
+            float2 *o = reinterpret_cast<float2 *>(reinterpret_cast<float *>(a.out) + e);
+            o[0] = make_float2((float)px[0][0], (float)px[1][0]);
+            crop_keep_stores_apart();
+            o[1] = make_float2((float)px[2][0], (float)px[3][0]);
+        }
     } else {
         // planar [CH][h][w]: fl32(fl32((float)p * scale[c]) + bias[c]), two roundings (__fmul_rn / __fadd_rn never contract), then
         // to nearest even to half for kCropOutF16; 4 values a lane a channel: one 64-bit store of halves, two of floats

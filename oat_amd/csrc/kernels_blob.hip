@@ -21,12 +21,11 @@
 //   * each foreground pixel emits at most one directed polygon edge per side
 //     facing OUTSIDE background; exact int64 Green sums per root.
 #include "oatgpu_internal.h"
+#include "blobruns_inline.h"     // msb64, low_mask_incl, run_head, run_head_w, uf_root: shared with the target-mask kernel
 
 namespace oatgpu {
 
-__device__ __forceinline__ int msb64(u64 v) { return 63 - __clzll((long long)v); }
 __device__ __forceinline__ int lsb64(u64 v) { return __ffsll((long long)v) - 1; }
-__device__ __forceinline__ u64 low_mask_incl(int i) { return (i >= 63) ? ~0ull : ((2ull << i) - 1ull); }
 
 // bits of word w that are real pixels (x < W)
 __device__ __forceinline__ u64 valid_bits(const Geom &g, int w)
@@ -458,21 +457,7 @@ __device__ __forceinline__ void uf_union(int *parent, int a, int b)
     }
 }
 
-// head (first pixel, padded index) of the run that contains pixel (x, y)
-__device__ __forceinline__ int run_head(const Geom &g, const u64 *trans, const int *carry, int y, int x)
-{
-    const int w = x >> 6, i = x & 63;
-    const u64 t = trans[(size_t)y * g.words + w] & low_mask_incl(i);
-    const int sx = t ? (w * 64 + msb64(t)) : carry[(size_t)y * g.words + w];
-    return y * g.Wp + sx;
-}
-// same, with this word's T / carry already in registers
-__device__ __forceinline__ int run_head_w(const Geom &g, u64 Tw, int cw, int y, int w, int i)
-{
-    const u64 t = Tw & low_mask_incl(i);
-    const int sx = t ? (w * 64 + msb64(t)) : cw;
-    return y * g.Wp + sx;
-}
+// (run_head / run_head_w -- the head of the run that contains a pixel -- are blobruns_inline.h's)
 
 // One thread = one word of row y (y >= 1): unite runs of row y with the runs
 // of row y-1 they touch.  Background: 4-connected.  Foreground: 8-connected.
@@ -533,13 +518,7 @@ __global__ __launch_bounds__(256) void k_merge(Geom g, BlobBuffers b, int first_
     }
 }
 
-// read-only walk to the root (after the merge kernel has completed: plain loads)
-__device__ __forceinline__ int uf_root(const int *parent, int i)
-{
-    int p = parent[i];
-    while (p != i) { i = p; p = parent[i]; }
-    return i;
-}
+// (uf_root, the read-only walk to the root once the merge kernel has completed, is blobruns_inline.h's)
 
 // K5: contour sums + selection in ONE kernel.
 // Phase 1, one thread = one word of an interior row:
@@ -1467,6 +1446,8 @@ void launch_blob_rank(const Geom &g, const BlobBuffers &b, double min_area, doub
 //   it; every launcher of this file issues these kernels on ONE HIP stream in the order row scan, merge, selection, and the host
 //   launches the ranking and this kernel on that very stream before the set's next row scan (targets_launch, api_targets.hip).  So
 //   all four hold the frame's final data from the end of k_merge until the set's next row scan -- as roots / acc do for k_blob_rank.
+//   k_target_mask (crops_inline.h, kernels_targetmask.hip) relies on exactly this too: the batched trackers launch it
+//   on that very stream behind the ranking (tracker_tail), it reads fin, trans, carry and parent with plain loads and writes none.
 // The edges are k_green_select's, word for word: one directed edge (x0, y0) -> (x1, y1) per side of a foreground pixel that faces
 //   OUTSIDE background (root 0); an edge facing a hole is not one.  With d = x0 y1 - x1 y0, per ranked root, exact in int64:
 //     a20 += d (x0 (x0 + x1) + x1 x1)     a11 += d (x0 ((y0 + y1) + y0) + x1 ((y0 + y1) + y1))     a02 += d (y0 (y0 + y1) + y1 y1)

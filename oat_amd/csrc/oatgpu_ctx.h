@@ -193,6 +193,17 @@ struct CropTensor {
     size_t entry_bytes = 0;
     int last_sets = 0;                         // entries the latest delivering call wrote (oatgpu_target_crop_tensor_sets)
 };
+// Target masks (oatgpu_set_target_mask_tensor; api_targetmask.hip): the switch's parameters and the CALLER's device
+// memory, as for crop tensors.  k_target_mask writes entry t of it for frame set t of a delivering call.
+struct MaskTensor {
+    int mode = 0, h = 0, w = 0;                // OATGPU_CROP_*, the window
+    double zoom = 1.0;
+    int dtype = 0;                             // OATGPU_TENSOR_*
+    uint8_t *out = nullptr;                    // device: [capacity][n][k][h][w] elements of the dtype
+    int capacity = 0;
+    size_t entry_bytes = 0;
+    int last_sets = 0;                         // entries the latest delivering call wrote (oatgpu_target_mask_tensor_sets)
+};
 struct Targets {
     int k = 0;                                 // K; 0: targets off
     TargetSets ring;                           // [ring_slots + 1] beside oatgpu_ctx::res: the ring's slots and the synchronous detectors' extra one
@@ -200,7 +211,8 @@ struct Targets {
     bool shapes = false;                       // oatgpu_set_target_shapes: every TargetSets of the context has its ShapeSets
     int crop_mode = 0, crop_h = 0, crop_w = 0; // oatgpu_set_target_crops: OATGPU_CROP_*, the window
     CropTensor ct;                             // oatgpu_set_target_crop_tensor; independent of crop_mode
-    // what the latest delivering call delivered (targets_begin starts all of them over, and ct.last_sets)
+    MaskTensor mt;                             // oatgpu_set_target_mask_tensor; independent of both
+    // what the latest delivering call delivered (targets_begin starts all of them over, and ct.last_sets and mt.last_sets)
     Delivered<oatgpu_position> last;           // [sets][n][k] oatgpu_targets ...
     Delivered<int32_t> last_found;             // [sets][n] ... and its candidate counts
     Delivered<oatgpu_shape> last_shapes;       // [sets][n][k] while shapes are on (oatgpu_target_shapes)
@@ -537,7 +549,7 @@ int open_tap(oatgpu_ctx *c, const BatchedTrackerState &bt, const char *name, con
 int reset_have(oatgpu_ctx *c, std::vector<char> &have, int s);
 // A step of a batched tracker around its front and blob launches: tracker_begin where the call begins to deliver --
 // every list a tracker's call delivers starts over --; tracker_tail behind the blob launch of the frame in `slot` on st: rank,
-// shape, crops, crop tensor, tracks, filters (bb: the slot's scratch set, rd: its result records; prev_slot: the slot of the frame
+// shape, crops, crop tensor, target mask, tracks, filters (bb: the slot's scratch set, rd: its result records; prev_slot: the slot of the frame
 // before inside a sequence call, whose track and filter launches this frame's wait for, -1: none); tracker_hand_out: the finished
 // frame in `slot` to the caller, and every set of it into its list -- the only place a tracker's call keeps.
 void tracker_begin(oatgpu_ctx *c);
@@ -564,6 +576,8 @@ void crop_launch_from_slot(CropLaunch &a, const oatgpu_ctx *c, const BatchedTrac
 void crop_launch_from_table(CropLaunch &a, const oatgpu_ctx *c, const void *frames_dev, int per_stream, int h, int w);
 int check_crop_mode(oatgpu_ctx *c, const char *what, int mode);
 int check_crop_size(oatgpu_ctx *c, const char *what, int h, int w);
+int check_crop_zoom(oatgpu_ctx *c, const char *what, double zoom);
+int check_window_riders(oatgpu_ctx *c, const char *what, int mode);
 int check_crop_switch(oatgpu_ctx *c, const char *what, int mode);
 int check_windows(oatgpu_ctx *c, const char *what, int per_stream, int h, int w);
 int load_windows(oatgpu_ctx *c, const char *what, const oatgpu_crop_window *win, int per_stream);
@@ -573,6 +587,12 @@ int load_windows(oatgpu_ctx *c, const char *what, const oatgpu_crop_window *win,
 int crop_tensor_launch(oatgpu_ctx *c, const BatchedTrackerState &bt, int slot, hipStream_t st);
 void crop_tensor_keep(oatgpu_ctx *c);
 int crop_tensor_room(oatgpu_ctx *c, int n_frames, const char *what);
+// api_targetmask.hip: crop_tensor_launch's neighbour -- k_target_mask behind it on the same stream, from the scratch set bb of the
+// slot's back half into the entry the slot remembers of the caller's memory --, the count tracker_hand_out keeps, and the refusal
+// of a sequence call of more frames than the caller's memory has entries.  All do nothing while target masks are off.
+int mask_tensor_launch(oatgpu_ctx *c, const BatchedTrackerState &bt, const BlobBuffers &bb, int slot, hipStream_t st);
+void mask_tensor_keep(oatgpu_ctx *c);
+int mask_tensor_room(oatgpu_ctx *c, int n_frames, const char *what);
 // api_tracks.hip: k_target_tracks on the target set of the tracker's slot `slot`, on st behind its ranking, into the slot's track set;
 // the filter chain on the slot's result records behind that.  Inside a sequence call (st is a B stream) consecutive frames sit on
 // different HIP streams: each launch waits for its own event of the frame before it (prev_slot) and records its own; the

@@ -389,6 +389,20 @@ struct CropTensorLaunch : CropLaunch {   // out: [n_streams][k] windows of h * w
 // The grid and the rules of launch_target_crops; every element of every window is written (an invalid window: bias[c], 0 for bytes).
 void launch_crop_tensor(const Geom &g, const CropTensorLaunch &a, int dtype, int n_streams, hipStream_t st);
 
+// --- kernels_targetmask.hip --- (target masks: each ranked blob's own pixels in the window of its crop tensor, in the caller's
+// device memory; oatgpu_set_target_mask_tensor)
+// The crop kernel's further outputs: kCropOutMask + a tensor dtype.  The window is the crop tensor's; instead of a frame pixel an
+// element is ON where its source pixel is set in the final mask and belongs to the rank's 8-connected component.
+constexpr int kCropOutMask = 8;
+struct MaskTensorLaunch : CropTensorLaunch {   // frames, channels, win, scale and bias are not used; recs is never null
+    Geom g;                  // the tracker's pixel domain: the window's source pixels are pixels of the final mask
+    BlobBuffers b;           // the scratch set of the slot's global back half: fin, trans, carry, parent are read, nothing is written
+};
+// Behind launch_blob_rank (and launch_blob_shape for windows along the axis) on the HIP stream of a kBlobGlobal back half, before
+// the set's next row scan; out: [n_streams][k][h][w] elements of the dtype (kCropOutU8: 255 / 0, the floats 1.0 / 0.0) in DEVICE
+// memory, every element written.
+void launch_target_mask(const MaskTensorLaunch &a, int dtype, int n_streams, hipStream_t st);
+
 // --- kernels_markers.hip --- (marker sets: M colour windows per camera behind one MOG2 pass, `posicom mean`)
 constexpr int kMaxMarkers = 8;
 struct MarkerCombined {   // device-side record of k_marker_combine, one per stream per step: oatgpu_combined's layout

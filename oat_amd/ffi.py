@@ -190,6 +190,8 @@ SIGNATURES = {
     "oatgpu_target_crop_tensor_sets": (C.c_int, [_ctx]),
     "oatgpu_crop_tensor_windows_dev": (C.c_int, [_ctx, C.c_void_p, C.POINTER(CropWindow), C.c_int32, C.c_int32, C.c_int32,
                                                  C.POINTER(CropTensorFmt), C.c_void_p]),
+    "oatgpu_set_target_mask_tensor": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_int32]),
+    "oatgpu_target_mask_tensor_sets": (C.c_int, [_ctx]),
     "oatgpu_mog_apply": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_mog_filter": (C.c_int, [_ctx, C.c_int32, _u8p, _u8p, C.c_double]),
     "oatgpu_bgr2hsv": (C.c_int, [_ctx, _u8p, _u8p]),

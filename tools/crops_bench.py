@@ -6,6 +6,7 @@ delivered crop set.
     python tools/crops_bench.py [--steps 200] [--warmup 20] [--quick]
     python tools/crops_bench.py --off-only --tree DIR      # the off legs alone with the package of another checkout (the parent)
     python tools/crops_bench.py --tensor                   # crop tensors against the host-mapped crops, see below
+    python tools/crops_bench.py --mask                     # target masks beside crop tensors, see below
 
 The shape of tools/targets_bench.py --target-shapes: 1 x 4K, 16 x 1080p and 1 x 640x480, BGR frames in device memory; the motion
 tracker (diff_threshold 16, blur 2) and the subtraction tracker (alpha 0, a window on the brightness of the difference); frames with
@@ -25,6 +26,10 @@ each a new context in one process: off, off_again; crops -- the host-mapped crop
 bytes, left on the device; u8_copy -- the same followed by ONE copy_ of the delivered entries into a pinned host tensor and a device
 synchronisation ("a device set plus one async copy"); f16 -- the tensor in half, scale 1/255, zoom 1; f16_zoom2 -- the same at zoom 2.
 
+--mask measures target masks (oatgpu_set_target_mask_tensor; profiles/mask_tensor_bench.txt) the same way: off,
+off_again; tensor_u8 -- the crop tensor in bytes; mask_u8 -- the mask in bytes; both -- the two beside each other; mask_f16_zoom2 --
+the mask in half at zoom 2.
+
 Without a GPU the tool fails (no fallback)."""
 import argparse
 import json
@@ -42,9 +47,10 @@ CROPS = (("up64", 64, 64, False), ("ax64", 64, 64, True), ("ax128", 128, 128, Tr
 
 TENSOR_SIZES = (64, 128)
 TENSOR_LEGS = ("off", "off_again", "crops", "u8", "u8_copy", "f16", "f16_zoom2")
+MASK_LEGS = ("off", "off_again", "tensor_u8", "mask_u8", "both", "mask_f16_zoom2")
 
 
-def tensor_main(a, torch, oat_amd, np, makers, tree):
+def tensor_main(a, torch, oat_amd, np, makers, tree, legs=TENSOR_LEGS, tool="--tensor"):
     from oat_amd.synth import SyntheticStream
     out = []
     for name, n, rows, cols in SHAPES:
@@ -62,11 +68,17 @@ def tensor_main(a, torch, oat_amd, np, makers, tree):
                 for side in TENSOR_SIZES:
                     rec = {"shape": name, "streams": n, "rows": rows, "cols": cols, "tracker": tracker, "blobs": 12, "k": k, "side": side,
                            "steps": a.steps, "warmup": a.warmup}
-                    for leg in TENSOR_LEGS:
+                    for leg in legs:
                         tr = make(rows, cols, n)
                         tr.set_targets(k)
                         tr.set_target_shapes()
-                        tensor = pinned = None
+                        tensor = pinned = mask = None
+                        if leg in ("tensor_u8", "both"):
+                            tensor = tr.set_target_crop_tensor(side, side, axis=True, dtype="uint8", capacity=POOL)
+                        if leg in ("mask_u8", "both"):
+                            mask = tr.set_target_mask_tensor(side, side, axis=True, dtype="uint8", capacity=POOL)
+                        elif leg == "mask_f16_zoom2":
+                            mask = tr.set_target_mask_tensor(side, side, axis=True, zoom=2.0, dtype="float16", capacity=POOL)
                         if leg == "crops":
                             tr.set_target_crops(side, side, axis=True)
                         elif leg in ("u8", "u8_copy"):
@@ -96,12 +108,17 @@ def tensor_main(a, torch, oat_amd, np, makers, tree):
                             torch.cuda.synchronize()
                             rec[f"entry_bytes_{leg}"] = int(tensor[0].numel() * tensor.element_size())
                             rec[f"nonzero_windows_{leg}"] = int((tensor[0].reshape(n * k, -1) != 0).any(dim=1).sum().item())
+                        if mask is not None:
+                            torch.cuda.synchronize()
+                            rec[f"mask_entry_bytes_{leg}"] = int(mask[0].numel() * mask.element_size())
+                            rec[f"mask_nonzero_windows_{leg}"] = int((mask[0].reshape(n * k, -1) != 0).any(dim=1).sum().item())
+                            rec[f"mask_on_fraction_{leg}"] = round(float((mask[0] != 0).float().mean().item()), 4)
                         tr.close()
-                        del tensor, pinned
+                        del tensor, pinned, mask
                     out.append(rec)
         del dev
         torch.cuda.empty_cache()
-    print(json.dumps({"tool": "crops_bench --tensor", "unit": "us a frame set, host clock around synchronous calls, median",
+    print(json.dumps({"tool": "crops_bench " + tool, "unit": "us a frame set, host clock around synchronous calls, median",
                       "tree": os.path.relpath(tree, ROOT), "library": os.path.relpath(oat_amd.lib_path(), tree), "shapes": out,
                       "device": torch.cuda.get_device_name(0)}))
 
@@ -113,6 +130,7 @@ def main():
     ap.add_argument("--quick", action="store_true", help="few steps (a rehearsal)")
     ap.add_argument("--off-only", action="store_true", help="the two off legs alone: nothing that needs oatgpu_set_target_crops")
     ap.add_argument("--tensor", action="store_true", help="crop tensors against the host-mapped crops (DESIGN.md 9m)")
+    ap.add_argument("--mask", action="store_true", help="target masks beside crop tensors (DESIGN.md 9o)")
     ap.add_argument("--shapes", default="", help="comma list of shape names (default: all)")
     ap.add_argument("--trackers", default="", help="motion, subtraction or both (default)")
     ap.add_argument("--blobs", default="1,12", help="blobs a camera, comma list")
@@ -139,6 +157,8 @@ def main():
 
     if a.tensor:
         return tensor_main(a, torch, oat_amd, np, (("motion", motion), ("subtraction", subtraction)), tree)
+    if a.mask:
+        return tensor_main(a, torch, oat_amd, np, (("motion", motion), ("subtraction", subtraction)), tree, MASK_LEGS, "--mask")
     legs = [("off", None), ("off_again", None)] + ([] if a.off_only else [(name, (h, w, axis)) for name, h, w, axis in CROPS])
     out = []
     for name, n, rows, cols in SHAPES:
