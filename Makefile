@@ -9,7 +9,7 @@ HIPFLAGS ?= --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fPIC -Wall 
 CSRC     = oat_amd/csrc
 LIB      = oat_amd/lib/liboatgpu.so
 # the units of the library, listed once: the kernels, and the C ABI above them by feature (oatgpu_ctx.h is their shared header)
-KERNELS  = kernels_mog kernels_stages kernels_measure kernels_blob kernels_kalman kernels_undistort kernels_debayer kernels_markers kernels_diff kernels_bsubtrack kernels_trackfilt kernels_tracks kernels_crops kernels_croptensor kernels_targetmask
+KERNELS  = kernels_mog kernels_stages kernels_measure kernels_rowscan kernels_bloblds kernels_blob kernels_kalman kernels_undistort kernels_debayer kernels_markers kernels_diff kernels_bsubtrack kernels_trackfilt kernels_tracks kernels_crops kernels_croptensor kernels_targetmask
 API      = api_context api_stages api_track api_markers api_diff api_bsubtrack api_trackfilt api_targets api_tracks api_crops api_croptensor api_targetmask api_model api_measure
 UNITS    = $(KERNELS) $(API)
 OBJS     = $(UNITS:%=$(CSRC)/%.o)

@@ -354,7 +354,7 @@ static StepPlan plan_step(const oatgpu_ctx *c, const oatgpu_ctx::FrameJob *j, in
     // targets on (oatgpu_set_targets): every frame takes back_half's global route with k_blob_rank behind it -- the plain order,
     // nothing paired, nothing speculative (and not early: above)
     if (c->tg.k) p.paired = p.spec_plain = false;
-    // Rows a row-scan workgroup (kernels_blob.hip "Rows a workgroup").  The wide form takes fewer wave slots from the per-pixel
+    // Rows a row-scan workgroup (kernels_rowscan.hip "Rows a workgroup").  The wide form takes fewer wave slots from the per-pixel
     // kernel beside it and delivers the frame later: up to ~85 us at 4K, ~28 us at 1080p (profiles/r07y_rowscan_rows_per_workgroup_ab.txt).
     // A step is DEEP when kDeepAhead frames launched earlier are still uncollected: results are collected in order, so nobody can
     // ask for this step's before those -- two launch periods, ~100 us at 4K; both sides scale with the frame.  Rings of 2 and 4

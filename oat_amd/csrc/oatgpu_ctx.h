@@ -342,7 +342,7 @@ struct oatgpu_ctx {
     DevMem<KalmanState> kal_state;   // ... the owner of kal.state
     bool kal_on = false;
     unsigned kal_ticket = 0;         // ticket of the next enqueued frame
-    // Early dispatch of the blob workgroup (kernels_blob.hip): the row scans of a device-frame step go down B0 / B1 by frame
+    // Early dispatch of the blob workgroup (kernels_bloblds.hip): the row scans of a device-frame step go down B0 / B1 by frame
     // parity, as on the plain path; the k_blob_lds workgroups of the step's frames are submitted with them as ONE launch on
     // B2 and wait on the device for their row scans' tickets.  Scratch sets 0 .. 3 by frame index mod 4; repairs of declined
     // frames use set 4 on B2.

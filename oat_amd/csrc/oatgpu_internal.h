@@ -231,7 +231,8 @@ bool debayer_is_wide(int W, const uint8_t *const *in, uint8_t *const *out, int n
 void launch_debayer_frames(const uint8_t *const *in, uint8_t *const *out, int n_frames, const int *patterns, int H, int W,
                            int n_streams, hipStream_t st);
 
-// --- kernels_blob.hip ---
+// --- the blob stage: kernels_rowscan.hip (morphology, row scan), kernels_bloblds.hip (k_blob_lds), kernels_blob.hip (the global
+// kernels, the riders and the orchestration of all three) ---
 struct BlobBuffers {
     u64 *thr;        // [2][n][Palloc/64] inRange output, double-buffered across frames
     u64 *tmp;        // [n][Palloc/64] morphology ping
@@ -248,7 +249,7 @@ struct BlobBuffers {
     unsigned short *wpre;  // [n][H*words] run starts of the row in the words before this one
     int *rowinfo;          // [n][H]       0: no foreground in the row; else its number of runs
     unsigned *lds_ok;      // [n]          1: k_blob_lds wrote this frame's result, k_merge / k_green_select stand down
-    // the early blob workgroup (kernels_blob.hip "Early dispatch"): a one-lane kernel behind the row scan publishes the frame's
+    // the early blob workgroup (kernels_bloblds.hip "Early dispatch"): a one-lane kernel behind the row scan publishes the frame's
     // ticket, the k_blob_lds workgroup that was dispatched ahead of it waits for exactly that ticket
     unsigned *ready;       // [n]          ticket of the latest frame whose row scan is complete (k_publish_ticket)
     unsigned *nopark;      // [1], one per CONTEXT (every scratch set points at it): set by the first parked workgroup that gave up
@@ -281,7 +282,7 @@ struct KalmanLaunch {
     unsigned ticket;         // this frame's index
 };
 #ifdef OATGPU_RS_TIMING
-void oatgpu_debug_rs_set_k1_end(const unsigned long long *p);     // measurement builds (kernels_blob.hip)
+void oatgpu_debug_rs_set_k1_end(const unsigned long long *p);     // measurement builds (kernels_rowscan.hip)
 #endif
 void launch_kalman(const KalmanLaunch &k, ResultRec *results, int n_streams, hipStream_t st);
 void launch_kalman_reset(KalmanState *state, int n_streams, unsigned ticket, hipStream_t st);
@@ -294,11 +295,21 @@ void launch_morph(const Geom &g, const u64 *src, u64 *dst, int k, bool is_erode,
 // results: device-visible (host-mapped) array indexed by stream.
 constexpr size_t kRowscanLdsMax = 64 * 1024;
 size_t rowscan_lds_bytes(const Geom &g, int dil_k);
-// Rows a row-scan workgroup takes where a step is launched deep in the pipeline (kernels_blob.hip "Rows a workgroup"; the default
+// Rows a row-scan workgroup takes where a step is launched deep in the pipeline (kernels_rowscan.hip "Rows a workgroup"; the default
 // height, kRsRows, stays with the kernel).  A step takes it only if rowscan_lds_bytes_rows(g, dil_k, kRsRowsDeep) <= kRowscanLdsMax.
 constexpr int kRsRowsNarrow = 4, kRsRowsDeep = 16;
 constexpr int kRsRowsDeepAlt = 32;      // (measurement builds: the other height of profiles/rowscan_deep_rows.txt)
 size_t rowscan_lds_bytes_rows(const Geom &g, int dil_k, int rows);
+// The row scan alone (the launchers below are made of it): src / b are nf (1 or 2) frames' source masks and scratch sets, one launch
+// for both; clear: reset lds_ok too (nobody else will); tag: measurement builds' row-group stamp.
+void launch_rowscan(const Geom &g, const u64 *const *src, int ero_k, int dil_k, const BlobBuffers *b, int nf, int first_stream,
+                    int n_streams, int clear, hipStream_t st, unsigned tag = 0u, int rows = kRsRowsNarrow);
+// The global kernels' grid (k_green_select, k_blob_shape; blobedges_inline.h: chunk_bits, border_chunk).
+// kGreenChunks threads per mask word, each owning 64 / kGreenChunks of its bits: the per-bit loops are
+// serial, and a word on a horizontal edge of a blob has up to 64 border pixels -- with one thread per word
+// that thread alone ran 10+ us at 1080p while a frame without a blob took 5 (profiles/r02_backhalf_latency_*.md).
+constexpr int kGreenChunks = 4;
+constexpr int kGreenBlock = 1024;          // big workgroups: every workgroup costs one same-address arrival atomic (~12 ns each, serialised)
 // mode: kBlobFull  = row scan + k_blob_lds + k_merge + k_green_select (the last two stand down when the LDS
 //                     kernel took the frame);
 //       kBlobSpec  = row scan + k_blob_lds only: a frame too busy for it comes back with valid == kNeedsGlobal and
@@ -310,7 +321,7 @@ constexpr int kPathTimeout = 2;
 constexpr int kPathNoPark = 3;     // beside valid == kNeedsGlobal: declined without waiting, an earlier workgroup of the context had timed out
 void launch_blob(const Geom &g, const BlobBuffers &b, const u64 *src_bits, int ero_k, int dil_k, double min_area,
                  double max_area, ResultRec *results, int first_stream, int n_streams, hipStream_t st, int mode = kBlobFull);
-// The same in two halves on two HIP streams (kernels_blob.hip "Early dispatch"): the row scan with a one-lane kernel behind
+// The same in two halves on two HIP streams (kernels_bloblds.hip "Early dispatch"): the row scan with a one-lane kernel behind
 // it that publishes `ticket`, and everything behind the row scan, whose k_blob_lds workgroup may be dispatched long before
 // the row scan has run and waits for `ticket` on the device.  ticket != 0.
 void launch_rowscan_signal(const Geom &g, const BlobBuffers &b, const u64 *src_bits, int ero_k, int dil_k, int first_stream,
@@ -331,6 +342,15 @@ struct BlobTab {
 };
 void launch_blob_table(const Geom &g, const BlobBuffers *b, const u64 *const *src, const BlobTab *tab, int max_dil,
                        ResultRec *const *results, int n_planes, int nf, hipStream_t st);
+// its row scan: plane s of the launch with the erode / dilate sizes of tab[s], the LDS sized by max_dil
+void launch_rowscan_table(const Geom &g, const u64 *const *src, const BlobTab *tab, int max_dil, const BlobBuffers *b, int nf,
+                          int n_planes, hipStream_t st);
+// k_blob_lds, one workgroup a stream and frame: grid (1, ny, nz), frame z (0 or 1) on scratch set bz into resultsz, waiting for
+// ticketz if that is not 0; spec: a declined frame comes back marked kNeedsGlobal; tab != nullptr: the area window of plane s is
+// tab[s]'s (the TAB form)
+void launch_blob_lds(const Geom &g, int ny, int nz, const BlobBuffers &b0, const BlobBuffers &b1, double min_area, double max_area,
+                     ResultRec *results0, ResultRec *results1, int first_stream, int spec, unsigned ticket0, unsigned ticket1,
+                     const BlobTab *tab, hipStream_t st);
 
 // Multi-target detection (oatgpu_set_targets; kernels_blob.hip, k_blob_rank): the k largest candidates of every
 // stream, ranked, out of what a kBlobGlobal back half has left in its scratch set b -- launched on the same HIP stream directly

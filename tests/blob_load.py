@@ -1,4 +1,4 @@
-"""What the blob stage's single-workgroup kernel (k_blob_lds, oat_amd/csrc/kernels_blob.hip) counts on a final mask,
+"""What the blob stage's single-workgroup kernel (k_blob_lds, oat_amd/csrc/kernels_bloblds.hip) counts on a final mask,
 restated in numpy, and masks that land exactly on a requested count.
 
 The final mask is the threshold mask after erode / dilate with the image frame zeroed, as O.sift_contours sees it.

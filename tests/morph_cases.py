@@ -1,8 +1,8 @@
 """The case table of the bit-packed morphology (k_morph, erode_word / dilate_word / dilate_word_lds and k_rowscan in
-oat_amd/csrc/kernels_blob.hip), shared by tests/test_morph_cases_cpu.py and tests/test_morph_routes_gpu.py.
+oat_amd/csrc/kernels_rowscan.hip), shared by tests/test_morph_cases_cpu.py and tests/test_morph_routes_gpu.py.
 
 The kernel's constants are held here once; the CPU file reads them out of the sources and fails when the two disagree.
-rowscan_lds_bytes() and ero_apart() restate the sources' formulas (kernels_blob.hip, plan_morph in api_track.hip), and
+rowscan_lds_bytes() and ero_apart() restate the sources' formulas (kernels_rowscan.hip, plan_morph in api_track.hip), and
 every geometry "on an edge" is DERIVED from them:
 
   mechanism                                     one side                          other side
@@ -45,7 +45,7 @@ def palloc(H, W):
 
 
 def rowscan_lds_bytes(H, W, dil):
-    """kernels_blob.hip, rowscan_lds_bytes(): the eroded rows a workgroup's dilation windows touch, 8 bytes a word."""
+    """kernels_rowscan.hip, rowscan_lds_bytes(): the eroded rows a workgroup's dilation windows touch, 8 bytes a word."""
     return (RS_ROWS + (dil if dil > 1 else 1) - 1) * words(W) * 8
 
 

@@ -31,7 +31,7 @@ def _final(raw, ero, dil):
 # ------------------------------------------------------------------------------------- the sources' limits ---
 
 def test_kernel_constants_are_the_edge_tables():
-    s = _src("kernels_blob.hip")
+    s, rs = _src("kernels_bloblds.hip"), _src("kernels_rowscan.hip")
     consts = {k: int(v) for k, v in re.findall(r"\b(kLds(?:Rows|Runs|Roots|Block|Trip))\s*=\s*(\d+)", s)}
     assert consts == dict(kLdsRows=B.LDS_ROWS, kLdsRuns=B.LDS_RUNS, kLdsRoots=B.LDS_ROOTS, kLdsBlock=B.LDS_BLOCK,
                           kLdsTrip=B.LDS_TRIP)
@@ -40,7 +40,7 @@ def test_kernel_constants_are_the_edge_tables():
     assert re.search(r"int ric\[(\d+)\]", s).group(1) == str(B.PHASE_A_ROWS)
     assert re.findall(r"NF \* (\d+)u <= \(unsigned\)kLdsBlock \? (\d) :", s) == [("16", "4"), ("8", "3")]
     # k_rowscan: one lane per word, chunks of 64 words
-    assert len(re.findall(r"for \(int c0 = 0; c0 < g\.words; c0 \+= 64\)", s)) == 2
+    assert len(re.findall(r"for \(int c0 = 0; c0 < g\.words; c0 \+= 64\)", rs)) == 2
     assert B.ROWSCAN_CHUNK_PX == 64 * 64
 
 

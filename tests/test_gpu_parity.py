@@ -1330,7 +1330,7 @@ def test_back_half_speculation_and_repair(A):
 
 @pytest.mark.parametrize("fusion,ring,kalman", [(2, 4, False), (1, 2, False), (2, 3, True), (2, 3, False), (2, 5, False), (1, 3, False)])
 def test_early_blob_dispatch_equals_the_plain_path(A, fusion, ring, kalman):
-    """Early dispatch of the blob workgroup (r04; oatgpu_set_early_blob, kernels_blob.hip): on the pipelined device-frame path
+    """Early dispatch of the blob workgroup (r04; oatgpu_set_early_blob, kernels_bloblds.hip): on the pipelined device-frame path
     the k_blob_lds workgroup of a frame is submitted on its own stream ahead of the frame's row scan and waits on the
     device for the row scan's ticket.  Frames big enough to take that path (>= 4 MP a step), quiet and BUSY ones in every
     pattern a ring can see (busy = declined by the LDS kernel -> repaired by the global kernels in scratch set 2; then the

@@ -29,7 +29,7 @@ def _flat(s):
 # ------------------------------------------------------------------------------------- the sources' constants ---
 
 def test_constants_are_the_kernels():
-    blob, api, hdr = _flat(_src("kernels_blob.hip")), _flat(_src("api_context.hip")), _flat(_src("oatgpu_internal.h"))
+    blob, api, hdr = _flat(_src("kernels_rowscan.hip")), _flat(_src("api_context.hip")), _flat(_src("oatgpu_internal.h"))
     assert re.search(r"constexpr int kRsWaves = \d+, kRsRows = (\d+);", blob).group(1) == str(M.RS_ROWS)
     m = re.search(r"constexpr size_t kRowscanLdsMax = (\d+) \* (\d+);", hdr)
     assert int(m.group(1)) * int(m.group(2)) == M.ROWSCAN_LDS_MAX
@@ -44,7 +44,7 @@ def test_constants_are_the_kernels():
 
 
 def test_route_predicates_are_the_sources():
-    blob, api = _flat(_src("kernels_blob.hip")), _flat(_src("api_track.hip"))
+    blob, api = _flat(_src("kernels_rowscan.hip")), _flat(_src("api_track.hip"))
     markers, ctx = _flat(_src("api_markers.hip")), _flat(_src("oatgpu_ctx.h"))
     # rowscan_lds_bytes(): (kRsRows + max(dil, 1) - 1) rows of g.words 8-byte words
     assert "return (size_t)(kRsRows + (dil_k > 1 ? dil_k : 1) - 1) * g.words * sizeof(u64);" in blob
